@@ -6,20 +6,25 @@ gradient, tangent projection, step, per-edge simplex projection, new S_vec) on a
 synthetic Uniform_Topology graph whose structure, rotations and cycle
 inconsistencies are already resident in HBM when the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W [--workload C1..C5]
+    python bench.py --gpus N --steps K --warmup W [--workload C1..C5] [--dump-outputs DIR] [--full]
 
 `value` is BASELINE.json configs[3] (C4: Uniform n=5000 p=0.2 q=0.3 sigma=0.1 -- the workload the north star's
 target is quoted on; 4 GB, fits one GPU) at every N: strong scaling, the total work is fixed, at N > 1 the
 edges-with-cycles are sharded over the ranks with a reduce-scatter and an all-gather per iteration
-(desc_amd/sharded.py).  The default line additionally carries `secondary_config`: the same measurement on C2
-(configs[1], n=1000 p=0.5).
+(desc_amd/sharded.py).
+
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` also writes what the
+last timed step left (S_vec and the objective / average-change traces, float64) as DIR/<name>.npy.  Everything
+else is measured under `--full` only: the per-kernel `roofline` leg (dominant kernels: column sums + sweep,
+HBM-bound, algorithmic bytes 72*m_cycle + 12*m_pos per iteration), the timed `end_to_end` solve
+calls, the run to the patience exit, `cpu_baseline` (the oracle's OpenMP C restatement timed on this host for a
+bounded number of iterations of the same workload; rank 0) with `parity_vs_cpu`, and `secondary_config`: the
+same measurement on C2 (configs[1], n=1000 p=0.5).
 
 `--gpus N` without WORLD_SIZE in the environment starts the N ranks itself (one child process per GPU, before
 anything in this process touches a GPU); under `python -m torch.distributed.run` the ranks are already there.
-Rank 0 prints ONE JSON line with the contract's fields plus `roofline` (dominant kernels: column sums + sweep,
-HBM-bound, algorithmic bytes 72*m_cycle + 12*m_pos per iteration), `cpu_baseline` (the oracle's
-OpenMP C restatement timed on this host for a bounded number of iterations of the same workload; rank 0, N = 1
-only) and, at N > 1, `rccl_ranks` (ncclCommCount of the communicator the collectives ran on).
+Rank 0 prints ONE JSON line with the contract's fields, at N > 1 with `rccl_ranks` (ncclCommCount of the
+communicator the collectives ran on).
 """
 from __future__ import annotations
 
@@ -165,9 +170,10 @@ def load_traffic(name):
     return None, None
 
 
-def measure(lib, name, K, W, seed, convergence, keep_arrays, n_sample_min=30):
-    """One workload on one GPU: K timed iterations (inputs resident in HBM), the per-kernel roofline leg, one really
-    timed desc_pgd_solve call (host arrays in -> S_vec out, 100 iterations), optionally the run to the patience exit."""
+def measure(lib, name, K, W, seed, n_sample_min=30, full=False, convergence=False, keep_arrays=False, want_outputs=False):
+    """One workload on one GPU: K timed iterations (inputs resident in HBM); with want_outputs, what the last of them left
+    (`outputs`: the arrays Solver.download hands a caller).  full: also the per-kernel roofline leg, one really timed
+    desc_pgd_solve call (host arrays in -> S_vec out, 100 iterations), optionally the run to the patience exit."""
     t0 = time.perf_counter()
     mo, nn, ii, jj, rij = generate(name)
     t_gen = time.perf_counter() - t0
@@ -195,11 +201,18 @@ def measure(lib, name, K, W, seed, convergence, keep_arrays, n_sample_min=30):
     solver.iterate(K)
     solver.sync()
     dt = time.perf_counter() - t0
+    # taken before anything else runs on the handle, so a plain run and a --full run write the same arrays
+    outputs = solver.download() if want_outputs else None
+    m_cycle, m_pos, m = solver.m_cycle, solver.m_pos, solver.m
+    res = dict(name=name, nn=nn, m=m, m_pos=m_pos, m_cycle=m_cycle, n_sample=int(sizes["n_sample"]), dt=dt, outputs=outputs,
+               setup_ms={"generate": t_gen * 1e3, "structure_device": t_struct * 1e3, "upload_layout_cycle_d": t_create * 1e3})
+    if not full:
+        solver.destroy()
+        return res
     # ---- roofline leg: the same K sweeps again, each iteration's kernels bracketed by HIP events
     #      on the launch stream (not part of `value`) ----
     _, ms_kernel = solver.iterate_timed(K, per_kernel=True)
     out = solver.download()
-    m_cycle, m_pos, m = solver.m_cycle, solver.m_pos, solver.m
     kname = solver.kernel_name()
     lay = solver.layout_stats()
     conv = None
@@ -238,9 +251,8 @@ def measure(lib, name, K, W, seed, convergence, keep_arrays, n_sample_min=30):
     node_layout = any(x in kname for x in ("node", "band", "small"))
     floor_bytes = 28.0 * m_cycle + 10.0 * lay.get("colsum_entries", 0) + 12.0 * m_pos if node_layout else bytes_per_launch
     sec = ms_kernel * 1e-3 if ms_kernel else float("inf")
-    res = dict(
-        name=name, mo=mo, nn=nn, ii=ii, jj=jj, rij=rij, prob=prob, arrays=arrays, dt=dt, out=out, m=m, m_pos=m_pos, m_cycle=m_cycle,
-        n_sample=int(sizes["n_sample"]),
+    res.update(
+        mo=mo, ii=ii, jj=jj, rij=rij, prob=prob, arrays=arrays, out=out,
         roofline={"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                   "traffic": traffic, "traffic_source": traffic_src,
                   "frac_traffic": (traffic / sec / 1e9 / HBM_PEAK_GBS) if traffic else None,
@@ -251,7 +263,6 @@ def measure(lib, name, K, W, seed, convergence, keep_arrays, n_sample_min=30):
                   "layout": lay,
                   "kernel": ("k_colsum_node + " + kname + "0> (one iteration = both launches)") if node_layout else kname,
                   "bytes_per_launch": bytes_per_launch, "kernel_ms": ms_kernel},
-        setup_ms={"generate": t_gen * 1e3, "structure_device": t_struct * 1e3, "upload_layout_cycle_d": t_create * 1e3},
         end_to_end={"ms": t_e2e * 1e3, "what": "one timed desc_pgd_solve call: host arrays in -> S_vec out, 100 iterations, warm HIP context, every block allocated afresh",
                     "ms_structure": e2e["ms_structure"], "ms_upload": e2e["ms_upload"], "ms_layout_cycle_d": e2e["ms_cycle_d"],
                     "ms_pgd": e2e["ms_pgd"], "ms_total_in_library": e2e["ms_total"],
@@ -262,6 +273,18 @@ def measure(lib, name, K, W, seed, convergence, keep_arrays, n_sample_min=30):
          "mean_abs_err_vs_truth": float(np.mean(np.abs(conv["S_vec"] - mo.ErrVec)))},
         err=float(np.mean(np.abs(out["S_vec"] - mo.ErrVec))))
     return res
+
+
+def dump_outputs(directory, outputs):
+    """--dump-outputs: the arrays the timed path hands a caller after its last step, float64.  Whole, not sampled: S_vec has
+    m entries, at most ~5e6 (C5: 40 MB)."""
+    arrays = {"S_vec": outputs["S_vec"], "obj": outputs["obj"], "avg": outputs["avg"]}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the 64 MB the outputs may take")
+    os.makedirs(directory, exist_ok=True)
+    for key, a in arrays.items():
+        np.save(os.path.join(directory, key + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def free_port():
@@ -338,11 +361,15 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-convergence", action="store_true", help="skip the run to the patience exit (profiling: keeps the kernel statistics to the timed sweeps)")
-    ap.add_argument("--no-secondary", "--no-north-star", dest="no_secondary", action="store_true", help="skip the extra C2 measurement of the default run")
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline as well: roofline leg, timed end-to-end "
+                    "solve calls, run to the patience exit, CPU baseline with parity, and C2 as secondary_config")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step left (S_vec, obj, avg; "
+                    "float64) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-convergence", action="store_true", help="--full without the run to the patience exit")
+    ap.add_argument("--no-secondary", "--no-north-star", dest="no_secondary", action="store_true", help="--full without the extra C2 measurement")
     ap.add_argument("--seed", type=int, default=0, help="cycle-sampling seed")
-    ap.add_argument("--full", action="store_true", help="no cycle sampling: n_sample_min above every codegree, all triangles swept "
+    ap.add_argument("--all-triangles", action="store_true", help="no cycle sampling: n_sample_min above every codegree, all triangles swept "
                     "(BASELINE configs[4]: ~1.7e8 triangles = 5e8 edge-cycle slots at C5)")
     ap.add_argument("--dry-launch", action="store_true", help="start the ranks, let them count themselves over gloo, touch no GPU (launch test)")
     args = ap.parse_args()
@@ -356,6 +383,11 @@ def main():
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: refusing to report a line for the wrong rank count", file=sys.stderr)
         return 2
     if world > 1 or os.environ.get("DESC_FORCE_SHARDED") == "1":   # the env switch rehearses the N>1 code path on one GPU
+        if args.dump_outputs:
+            print("bench.py: --dump-outputs is not implemented for the sharded path", file=sys.stderr)
+            return 2
+        if not args.full:
+            args.no_secondary = args.no_cpu_baseline = True
         from desc_amd.sharded import bench_sharded
         return bench_sharded(args, WORKLOADS, describe, generate, cpu_baseline)
 
@@ -363,24 +395,32 @@ def main():
     name = args.workload or "C4"
     K, W = args.steps, args.warmup
     warm_up(_lib)
-    nsm = (1 << 16) if args.full else 30
+    nsm = (1 << 16) if args.all_triangles else 30
     # (unsampled: ConstantStepSize(1) never meets the patience rule -- 5000 sweeps measured at C5 -- so that leg is skipped)
-    r = measure(_lib, name, K, W, args.seed, not args.no_convergence and not args.full, not args.no_cpu_baseline, nsm)
+    r = measure(_lib, name, K, W, args.seed, nsm, full=args.full, convergence=not args.no_convergence and not args.all_triangles,
+                keep_arrays=args.full and not args.no_cpu_baseline, want_outputs=args.dump_outputs is not None)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r["outputs"])
     dt = r["dt"]
     line = {
         "metric": "DESC_PGD iters/sec", "value": K / dt, "unit": "iters/s", "n_gpus": 1, "steps": K, "warmup": W,
         "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
         "dtype": "f64", "data": "synthetic",
-        "config": {"workload": describe(name) + ("; all triangles (no cycle sampling)" if args.full else ""), "n": r["nn"], "m": r["m"], "m_pos": r["m_pos"], "m_cycle": r["m_cycle"],
+        "config": {"workload": describe(name) + ("; all triangles (no cycle sampling)" if args.all_triangles else ""), "n": r["nn"], "m": r["m"], "m_pos": r["m_pos"], "m_cycle": r["m_cycle"],
                    "n_sample": r["n_sample"], "sampling_seed": args.seed, "parallelism": "1 GPU"},
-        "roofline": r["roofline"],
         "cycle_updates_per_s": r["m_cycle"] * K / dt,
         "setup_ms": r["setup_ms"],
+    }
+    if not args.full:
+        print(json.dumps(line))
+        return 0
+    line.update({
+        "roofline": r["roofline"],
         "end_to_end_100_iters_ms": r["end_to_end"]["ms"],
         "end_to_end": r["end_to_end"],
         "to_patience_exit_lr1": r["conv"],
         "mean_abs_err_vs_truth": r["err"],
-    }
+    })
     if not args.no_cpu_baseline:
         # the oracle's C/OpenMP port on the same workload, a bounded number of iterations (C4: ~0.5 s each on 16 threads)
         cb, ref, it = cpu_baseline(r["nn"], r["ii"], r["jj"], r["rij"], r["arrays"], budget_s=12.0, max_iters=10 if name in ("C4", "C5") else 50)
@@ -392,7 +432,7 @@ def main():
         line["cpu_baseline"] = None
     if args.workload is None and not args.no_secondary:
         # BASELINE configs[1] (C2, n=1000 p=0.5): same measurement, its own roofline and CPU data points
-        x = measure(_lib, "C2", K, W, args.seed, not args.no_convergence, not args.no_cpu_baseline)
+        x = measure(_lib, "C2", K, W, args.seed, full=True, convergence=not args.no_convergence, keep_arrays=not args.no_cpu_baseline)
         sec = {"workload": describe("C2"), "value": K / x["dt"], "unit": "iters/s", "steps": K, "warmup": W, "ms_per_step": x["dt"] / K * 1e3,
                "m_cycle": x["m_cycle"], "m_pos": x["m_pos"], "n_sample": x["n_sample"], "roofline": x["roofline"],
                "setup_ms": x["setup_ms"], "end_to_end": x["end_to_end"], "to_patience_exit_lr1": x["conv"], "mean_abs_err_vs_truth": x["err"]}
