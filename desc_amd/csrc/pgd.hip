@@ -2343,7 +2343,8 @@ int setup_node(desc_pgd* h, const desc_problem* prob, const desc_structure* s, c
                  (int64_t)2 * m * 8 < (1ll << 32);          // 32-bit byte offsets into the CSR-aligned arrays (buffer instructions): m < 2.7e8 edges
     // exchange parts: the reduce-scatter of part c + 1 travels while part c is swept (band sweep only; DESC_SHARD_PARTS overrides, 1 = one reduce-scatter)
     // (segments of up to 64 cycles: every step plugin then runs on the band sweep; longer ones fall back to k_sweep_node for Adam, which sweeps in one launch)
-    const int xparts = (h->world > 1 && h->band_ok && h->max_cnt <= 64) ? std::max(1, std::min(8, env_int("DESC_SHARD_PARTS", 2))) : 1;
+    // every part's sweep writes band_grid (= ncu) partial pairs into its SHARD_PARTS / xparts of them: at most 4 parts with 256 CUs
+    const int xparts = (h->world > 1 && h->band_ok && h->max_cnt <= 64) ? std::max(1, std::min({8, SHARD_PARTS / ncu, env_int("DESC_SHARD_PARTS", 2)})) : 1;
     if ((rc = make_node_plan(prob, s, h->max_deg, h->world, h->max_cnt <= 32 ? 32 : h->max_cnt <= 128 ? 16 : 8, h->band_ok ? band_row_cap(h->max_deg) : 0, P, xparts))) return rc;   // 8 waves x 64/lps segments
     h->xparts = P.xparts;
     h->band = P.band;
@@ -3178,6 +3179,12 @@ int desc_pgd_shard_bind(desc_pgd* h, double* T_send, double* T_recv, double* sal
     int rc = set_device(h); if (rc) return rc;
     DESC_HIP(hipStreamSynchronize(h->stream));
     if (sweep_parts(h, false) > SHARD_PARTS || h->grid > SHARD_PARTS) return fail(DESC_ERR_STATE, "sweep grid exceeds the partials area of the exchange slice");
+    // every exchange part's band sweep writes band_grid + its tail pairs into its own share of the partials area (shard_enqueue_sweep)
+    if (h->band_ok)
+        for (int c = 0; c < h->xparts; ++c)
+            if (h->band_grid + h->xntail[c] > SHARD_PARTS / h->xparts)
+                return fail(DESC_ERR_STATE, "exchange part %d: %d sweep workgroups + %d tail pieces exceed its %d partial pairs", c, h->band_grid, h->xntail[c],
+                            SHARD_PARTS / h->xparts);
     if (!T_send && !T_recv && !sall) {       // library-owned exchange buffers (the fused protocol does not need torch tensors)
         const int64_t t_len = (int64_t)h->world * h->xparts * h->t_part + 1;
         if ((rc = dalloc(h, &T_send, (size_t)t_len))) return rc;

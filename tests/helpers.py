@@ -41,3 +41,71 @@ def assert_structure_equal(a, b):
     assert a["m_pos"] == b["m_pos"] and a["m_cycle"] == b["m_cycle"] and a["n_sample"] == b["n_sample"]
     for key in STRUCT_KEYS:
         assert np.array_equal(a[key], b[key]), key
+
+
+def emulate_sharded(lib, nn, ii, jj, rij, p, world, check_every=5, where=None, nmin=30):
+    """`world` ranks emulated in one process on one GPU: every rank's shard on the same card and stream, the collectives done by hand
+    between their exchange buffers.  Returns every rank's download (with the sweep it launched last) and its (seg_lo, seg_hi, cyc_lo, cyc_hi)."""
+    import torch
+    from desc_amd.sharded import HipShard
+    prob = lib.ProblemArrays(nn, ii, jj, rij)
+    st = lib.Structure.build(prob, nmin, p.seed, lib.BUILD_HOST if where is None else where, 0)
+    stream = torch.cuda.Stream(torch.device("cuda", 0))      # one stream for every emulated rank
+    shards = [HipShard(prob, st, 0, r, world, stream=stream) for r in range(world)]
+    st.free()
+    L = shards[0].slice_len
+    ctx = torch.cuda.stream(stream)
+    ctx.__enter__()
+
+    def all_gather():
+        for r in range(world):
+            piece = shards[r].sall.view(world, L)[r].clone()
+            for s in shards:
+                s.sall.view(world, L)[r].copy_(piece)
+
+    def reduce_scatter():                                    # part by part (desc_shard_info.xparts): blocks [c * world, (c + 1) * world) -> block c
+        Lp, X = shards[0].info.t_part, shards[0].info.xparts
+        for c in range(X):
+            tot = torch.zeros(world * Lp, dtype=shards[0].T.dtype, device=shards[0].T.device)
+            for s in shards:
+                tot += s.T[c * world * Lp:(c + 1) * world * Lp]
+            for r, s in enumerate(shards):
+                s.T_recv[c * Lp:(c + 1) * Lp].copy_(tot.view(world, Lp)[r])
+
+    for s in shards: s.reset(p)
+    for s in shards: s.finish(1)
+    all_gather()
+    for s in shards: s.finish(2)
+    left = p.iters
+    while left > 0:
+        n = min(left, check_every)
+        for _ in range(n):
+            for s in shards: s.colsum()
+            reduce_scatter()
+            for s in shards: s.sweep()
+            all_gather()
+            for s in shards: s.finish(0)
+        left -= n
+        flags = [s.stopped() for s in shards]
+        assert len(set(flags)) == 1
+        if left > 0 and flags[0]:
+            break
+    for s in shards: s.objective(0)
+    all_gather()
+    for s in shards: s.objective(1)
+    outs = [s.download() for s in shards]
+    ctx.__exit__(None, None, None)
+    segs = [(s.info.seg_lo, s.info.seg_hi, s.info.cyc_lo, s.info.cyc_hi) for s in shards]
+    for o, s in zip(outs, shards):
+        o["last_sweep"], o["kernel"] = s.solver.last_sweep(), s.solver.kernel_name()
+    for s in shards: s.destroy()
+    return outs, segs
+
+
+def run_unsharded(lib, prob, st, p):
+    """One rank through the plain path on a structure built by the caller (its n_sample_min and seed are the caller's)."""
+    solver = lib.Solver(prob, st, 0)
+    out = solver.run(p)
+    out["kernel"], out["last_sweep"] = solver.kernel_name(), solver.last_sweep()
+    solver.destroy()
+    return out

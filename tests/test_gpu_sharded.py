@@ -8,67 +8,10 @@ import socket
 import numpy as np
 import pytest
 
-from tests.helpers import c_params, make_problem, oracle_reference
+from tests.helpers import c_params, emulate_sharded as _emulate, make_problem, oracle_reference, run_unsharded as _unsharded
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
-
-
-def _emulate(lib, nn, ii, jj, rij, p, world, check_every=5, where=None, nmin=30):
-    import torch
-    from desc_amd.sharded import HipShard
-    prob = lib.ProblemArrays(nn, ii, jj, rij)
-    st = lib.Structure.build(prob, nmin, p.seed, lib.BUILD_HOST if where is None else where, 0)
-    stream = torch.cuda.Stream(torch.device("cuda", 0))      # one stream for every emulated rank
-    shards = [HipShard(prob, st, 0, r, world, stream=stream) for r in range(world)]
-    st.free()
-    L = shards[0].slice_len
-    ctx = torch.cuda.stream(stream)
-    ctx.__enter__()
-
-    def all_gather():
-        for r in range(world):
-            piece = shards[r].sall.view(world, L)[r].clone()
-            for s in shards:
-                s.sall.view(world, L)[r].copy_(piece)
-
-    def reduce_scatter():                                    # part by part (desc_shard_info.xparts): blocks [c * world, (c + 1) * world) -> block c
-        Lp, X = shards[0].info.t_part, shards[0].info.xparts
-        for c in range(X):
-            tot = torch.zeros(world * Lp, dtype=shards[0].T.dtype, device=shards[0].T.device)
-            for s in shards:
-                tot += s.T[c * world * Lp:(c + 1) * world * Lp]
-            for r, s in enumerate(shards):
-                s.T_recv[c * Lp:(c + 1) * Lp].copy_(tot.view(world, Lp)[r])
-
-    for s in shards: s.reset(p)
-    for s in shards: s.finish(1)
-    all_gather()
-    for s in shards: s.finish(2)
-    left = p.iters
-    while left > 0:
-        n = min(left, check_every)
-        for _ in range(n):
-            for s in shards: s.colsum()
-            reduce_scatter()
-            for s in shards: s.sweep()
-            all_gather()
-            for s in shards: s.finish(0)
-        left -= n
-        flags = [s.stopped() for s in shards]
-        assert len(set(flags)) == 1
-        if left > 0 and flags[0]:
-            break
-    for s in shards: s.objective(0)
-    all_gather()
-    for s in shards: s.objective(1)
-    outs = [s.download() for s in shards]
-    ctx.__exit__(None, None, None)
-    segs = [(s.info.seg_lo, s.info.seg_hi, s.info.cyc_lo, s.info.cyc_hi) for s in shards]
-    for o, s in zip(outs, shards):
-        o["last_sweep"], o["kernel"] = s.solver.last_sweep(), s.solver.kernel_name()
-    for s in shards: s.destroy()
-    return outs, segs
 
 
 @pytest.mark.parametrize("world", [1, 2, 3])
@@ -338,14 +281,6 @@ def test_exchange_layout_invariants(lib, world, row_cap, monkeypatch):
         assert sum(1 for i in infos if i.seg_hi > i.seg_lo) == 1
 
 
-def _unsharded(lib, prob, st, p):
-    solver = lib.Solver(prob, st, 0)
-    out = solver.run(p)
-    out["kernel"], out["last_sweep"] = solver.kernel_name(), solver.last_sweep()
-    solver.destroy()
-    return out
-
-
 @pytest.mark.parametrize("world", [2, 8])
 def test_sharded_c2_full_size_equals_unsharded(lib, world):
     """BASELINE configs[1] (n = 1000, 15.7 M cycles), device-built structure, default kernel choice: every emulated rank runs the XT instance
@@ -398,21 +333,37 @@ def test_fused_protocol_forced_collectives_c2(lib, monkeypatch):
     assert np.allclose(out["obj"], one["obj"], rtol=1e-12, atol=0)
 
 
-@pytest.mark.parametrize("parts", ["1", "3", "4"])
-def test_exchange_parts_other_counts(lib, oracle, parts, monkeypatch):
+PARTS_CASES = dict(                           # graph, n_sample_min, row cap (~24 bands), iterations, step
+    const=dict(n=150, p=0.6, nmin=30, row_cap="560", iters=25, kw=dict(lr=0.01)),
+    adam=dict(n=150, p=0.6, nmin=30, row_cap="560", iters=20, kw=dict(lr=0.01, step_kind=2)),          # split into parts through band_adam_ok
+    long=dict(n=120, p=0.7, nmin=33, row_cap="420", iters=20, kw=dict(lr=0.01)),                     # 33 cycles per segment: k_sweep_band<16,4>
+)
+
+
+@pytest.mark.parametrize("parts,case", [pytest.param(str(k), "const", id=str(k)) for k in range(1, 9)] +
+                         [pytest.param(k, c, id=f"{c}-{k}") for c in ("adam", "long") for k in ("2", "4", "8")])
+def test_exchange_parts_other_counts(lib, oracle, parts, case, monkeypatch):
     """DESC_SHARD_PARTS other than the default 2 (1 = one reduce-scatter as in round 3; 3, 4: parts that need not divide a rank's bands evenly; some
-    may be empty): the same bits as one rank, for world 3 on a graph of ~24 bands."""
+    may be empty; 5..8: more than the 1024 partial pairs of a slice hold at 256 workgroups a part, clamped to 4): the same bits as one rank, for
+    world 3 on a graph of ~24 bands."""
+    cfg = PARTS_CASES[case]
     monkeypatch.setenv("DESC_DEBUG_VARIANT", "3")
-    monkeypatch.setenv("DESC_DEBUG_ROW_CAP", "560")
+    monkeypatch.setenv("DESC_DEBUG_ROW_CAP", cfg["row_cap"])
     monkeypatch.setenv("DESC_SHARD_PARTS", parts)
-    mo, nn, ii, jj, rij = make_problem("uniform", n=150, p=0.6, q=0.2, sigma=0.1, seed=8)
-    st, S0, ref = oracle_reference(oracle, nn, ii, jj, rij, seed=3, iters=25, lr=0.01)
-    outs, segs = _emulate(lib, nn, ii, jj, rij, c_params(25, lr=0.01, seed=3), 3, where=lib.BUILD_DEVICE)
+    mo, nn, ii, jj, rij = make_problem("uniform", n=cfg["n"], p=cfg["p"], q=0.2, sigma=0.1, seed=8)
+    st = oracle.build_structure(nn, ii, jj, seed=3, n_sample_min=cfg["nmin"])
+    S0 = oracle.cycle_d(ii, jj, rij.reshape(-1, 9), st)
+    ref = oracle.pgd_run(st, S0, cfg["iters"], **cfg["kw"])
+    if case == "long":
+        assert 32 < int(np.diff(st["cum_ind"]).max()) <= 64
+    p = c_params(cfg["iters"], seed=3, **cfg["kw"])
+    outs, segs = _emulate(lib, nn, ii, jj, rij, p, 3, where=lib.BUILD_DEVICE, nmin=cfg["nmin"])
     prob = lib.ProblemArrays(nn, ii, jj, rij)
-    dst = lib.Structure.build(prob, 30, 3, lib.BUILD_DEVICE, 0)
-    one = _unsharded(lib, prob, dst, c_params(25, lr=0.01, seed=3))
+    dst = lib.Structure.build(prob, cfg["nmin"], 3, lib.BUILD_DEVICE, 0)
+    one = _unsharded(lib, prob, dst, p)
     dst.free()
+    tol = 1e-9 if case == "adam" else TOL
     for out in outs:
         assert ",XT>" in out["last_sweep"]
-        assert np.abs(out["S_vec"] - ref["S_vec"]).max() <= TOL and np.array_equal(out["S_vec"], one["S_vec"])
+        assert np.abs(out["S_vec"] - ref["S_vec"]).max() <= tol and np.array_equal(out["S_vec"], one["S_vec"])
         assert np.allclose(out["obj"], ref["obj"], rtol=1e-12, atol=1e-9)
