@@ -30,7 +30,7 @@ EXPORTS = [
     "desc_pgd_create_shard", "desc_pgd_shard_info", "desc_pgd_shard_bind", "desc_pgd_shard_colsum", "desc_pgd_shard_sweep",
     "desc_pgd_shard_finish", "desc_pgd_shard_objective", "desc_pgd_shard_set_collectives", "desc_pgd_shard_start",
     "desc_pgd_shard_iterate", "desc_pgd_shard_run", "desc_pgd_stopped", "desc_device_synchronize", "desc_memcpy_d2h", "desc_memcpy_h2d", "desc_debug_band_plan", "desc_debug_spmm_variants", "desc_debug_wg_clock", "desc_debug_wg_plan", "desc_debug_last_sweep", "desc_debug_shard_layout", "desc_trim_memory", "desc_spectral_run", "desc_cemp_run", "desc_refine_run",
-    "desc_marshal_edges", "desc_marshal_rij",
+    "desc_marshal_edges", "desc_marshal_rij", "desc_mst_run", "desc_mst_run_dev", "desc_mpls_run", "desc_mpls_run_dev",
 ]
 
 I32P = C.POINTER(C.c_int32)
@@ -96,6 +96,18 @@ class SpectralInfo(C.Structure):
 class RefineInfo(C.Structure):
     _fields_ = [("iters", C.c_int32), ("cg_iters", C.c_int32), ("verbose", C.c_int32), ("cg_unconverged", C.c_int32),
                 ("score", C.c_double), ("ms_total", C.c_double), ("cg_residual", C.c_double)]
+
+
+class MplsParams(C.Structure):
+    _fields_ = [("cemp_beta", F64P), ("n_cemp_beta", C.c_int32), ("cemp_max_iter", C.c_int32), ("nsample", C.c_int32), ("verbose", C.c_int32),
+                ("seed", C.c_uint64), ("stop_threshold", C.c_double), ("max_iter", C.c_int32), ("n_beta", C.c_int32), ("beta", F64P),
+                ("tau", F64P), ("alpha", F64P), ("n_tau", C.c_int32), ("n_alpha", C.c_int32)]
+
+
+class MplsInfo(C.Structure):
+    _fields_ = [("iters", C.c_int32), ("cg_iters", C.c_int32), ("cg_unconverged", C.c_int32), ("reserved", C.c_int32), ("m_pos", C.c_int64),
+                ("score", C.c_double), ("cg_residual", C.c_double), ("ms_cemp", C.c_double), ("ms_mst", C.c_double), ("ms_loop", C.c_double),
+                ("ms_total", C.c_double)]
 
 
 ERR_INVALID, ERR_HIP, ERR_TOO_LARGE, ERR_STATE = -1, -2, -3, -4
@@ -198,6 +210,10 @@ def load():
     L.desc_cemp_run.argtypes = [C.POINTER(Problem), F64P, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, F64P,
                                 C.POINTER(C.c_double)]
     L.desc_refine_run.argtypes = [C.POINTER(Problem), F64P, F64P, C.c_double, C.c_int32, C.c_int32, F64P, C.POINTER(RefineInfo)]
+    L.desc_mst_run.argtypes = [C.POINTER(Problem), F64P, C.c_int32, F64P, I32P]
+    L.desc_mst_run_dev.argtypes = [C.c_void_p, F64P, F64P, I32P]
+    L.desc_mpls_run.argtypes = [C.POINTER(Problem), C.POINTER(MplsParams), C.c_int32, F64P, F64P, F64P, C.POINTER(MplsInfo)]
+    L.desc_mpls_run_dev.argtypes = [C.c_void_p, C.POINTER(MplsParams), F64P, F64P, F64P, C.POINTER(MplsInfo)]
     _lib = L
     return L
 
@@ -623,6 +639,43 @@ def refine_run(prob, s_vec, R_init, stop_threshold=1e-3, max_iters=100, device=0
         check(L.desc_refine_run(C.byref(prob.c), ptr(S, F64P), ptr(Ri, F64P), stop_threshold, max_iters, device, ptr(Ro, F64P), C.byref(info)))
     return Ro[:9 * n].reshape((3, 3, n), order="F"), dict(iters=info.iters, cg_iters=info.cg_iters, score=info.score, ms_total=info.ms_total,
                                                         cg_unconverged=info.cg_unconverged, cg_residual=info.cg_residual)
+
+
+def mst_run(prob, s_vec, device=0):
+    """desc_mst_run[_dev] -> (R (3,3,n), tree edge indices ascending (n - 1,), sorted order)."""
+    n = prob.n
+    S = np.ascontiguousarray(s_vec, dtype=np.float64).reshape(-1)
+    if S.size != prob.m:
+        raise ValueError("s_vec must have m entries")
+    R = out_buffer(9 * n)
+    T = out_buffer(max(n - 1, 1), np.int32)
+    L = load()
+    if isinstance(prob, DeviceProblem):
+        check(L.desc_mst_run_dev(prob.handle, ptr(S, F64P), ptr(R, F64P), ptr(T, I32P)))
+    else:
+        check(L.desc_mst_run(C.byref(prob.c), ptr(S, F64P), device, ptr(R, F64P), ptr(T, I32P)))
+    return R[:9 * n].reshape((3, 3, n), order="F"), T[:n - 1].copy()
+
+
+def mpls_run(prob, cemp_beta, cemp_max_iter, nsample, stop_threshold, max_iter, beta, tau, alpha, seed=0, device=0, verbose=False):
+    """desc_mpls_run[_dev] -> (R_est (3,3,n), R_init (3,3,n), CEMP's SVec (m,), info dict); sorted edge order."""
+    n, m = prob.n, prob.m
+    vec = [np.ascontiguousarray(np.atleast_1d(np.asarray(v, dtype=np.float64)).reshape(-1)) for v in (cemp_beta, beta, tau, alpha)]
+    if any(v.size == 0 for v in vec):
+        raise ValueError("the reweighting / thresholding / cycle_info_ratio vectors need at least one entry")
+    p = MplsParams(ptr(vec[0], F64P), vec[0].size, int(cemp_max_iter), int(nsample), 1 if verbose else 0, int(seed), float(stop_threshold),
+                   int(max_iter), vec[1].size, ptr(vec[1], F64P), ptr(vec[2], F64P), ptr(vec[3], F64P), vec[2].size, vec[3].size)
+    R_est, R_init, S = out_buffer(9 * n), out_buffer(9 * n), out_buffer(m)
+    info = MplsInfo()
+    L = load()
+    if isinstance(prob, DeviceProblem):
+        check(L.desc_mpls_run_dev(prob.handle, C.byref(p), ptr(R_est, F64P), ptr(R_init, F64P), ptr(S, F64P), C.byref(info)))
+    else:
+        check(L.desc_mpls_run(C.byref(prob.c), C.byref(p), device, ptr(R_est, F64P), ptr(R_init, F64P), ptr(S, F64P), C.byref(info)))
+    shape = lambda R: R[:9 * n].reshape((3, 3, n), order="F")      # noqa: E731
+    return shape(R_est), shape(R_init), S[:m], dict(iters=info.iters, cg_iters=info.cg_iters, cg_unconverged=info.cg_unconverged, m_pos=info.m_pos,
+                                                    score=info.score, cg_residual=info.cg_residual, ms_cemp=info.ms_cemp, ms_mst=info.ms_mst,
+                                                    ms_loop=info.ms_loop, ms_total=info.ms_total)
 
 
 def spmm_variants(dprob: DeviceProblem, reps=20):

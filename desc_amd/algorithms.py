@@ -312,6 +312,95 @@ def CEMP(Ind, RijMat, CEMP_parameters, return_info=False):
     return (S, dict(ms_total=ms)) if return_info else S
 
 
+def _param_vec(params, name, what):
+    v = _get(params, name)
+    if v is None:
+        raise ValueError(f"{what}.{name} is required")
+    v = np.atleast_1d(np.asarray(v, dtype=np.float64)).reshape(-1)
+    if v.size == 0:
+        raise ValueError(f"{what}.{name} needs at least one entry")
+    return v
+
+
+def MPLS(Ind, RijMat, CEMP_parameters, MPLS_parameters, return_info=False):
+    """[R_est, R_init] = MPLS(Ind, RijMat, CEMP_parameters, MPLS_parameters) -- Algorithms/MPLS.m:31.
+
+    ``R_init`` is the CEMP+MST initialisation (MPLS.m:160-193), ``R_est`` the result of the cycle-reweighted Lie-algebraic
+    averaging (:196-254).  Fields read, as Demo/compare_algorithms.m:26-36 sets them: ``CEMP_parameters.max_iter``,
+    ``.reweighting``, ``.nsample``; ``MPLS_parameters.stop_threshold``, ``.max_iter``, ``.reweighting``, ``.thresholding``,
+    ``.cycle_info_ratio``.  Optional (not in the reference): ``seed`` (cycle sampling), ``device`` and ``verbose`` (the reference's
+    disp / fprintf lines; default off), read from CEMP_parameters.  One device problem serves all three stages.  With
+    ``return_info`` also a dict: iterations, score, PCG counts, m_pos, per-stage milliseconds and CEMP's ``SVec`` (caller's order)."""
+    n, ii, jj, rij, perm = marshal_edges(Ind, RijMat)
+    if ii.shape[0] == 0:
+        raise ValueError("empty edge list")
+    cemp_beta = _param_vec(CEMP_parameters, "reweighting", "CEMP_parameters")
+    beta = _param_vec(MPLS_parameters, "reweighting", "MPLS_parameters")
+    tau = _param_vec(MPLS_parameters, "thresholding", "MPLS_parameters")
+    alpha = _param_vec(MPLS_parameters, "cycle_info_ratio", "MPLS_parameters")
+    verbose = bool(_get(CEMP_parameters, "verbose", False))
+    prob = _lib.ProblemArrays(n, ii, jj, rij)
+    dprob = _lib.DeviceProblem(prob, int(_get(CEMP_parameters, "device", 0)))
+    try:
+        if verbose:
+            import sys
+            sys.stdout.flush()
+        R_est, R_init, S, info = _lib.mpls_run(dprob, cemp_beta, int(_get(CEMP_parameters, "max_iter")), int(_get(CEMP_parameters, "nsample")),
+                                               float(_get(MPLS_parameters, "stop_threshold")), int(_get(MPLS_parameters, "max_iter")),
+                                               beta, tau, alpha, seed=int(_get(CEMP_parameters, "seed", 0)), verbose=verbose)
+    finally:
+        dprob.free()
+    if return_info:
+        if perm is not None:
+            out = np.empty_like(S); out[perm] = S; S = out
+        info["SVec"] = S
+        return R_est, R_init, info
+    return R_est, R_init
+
+
+def MST(Ind, RijMat, SVec, device=0, return_info=False):
+    """R_est = the tree step of MPLS (Algorithms/MPLS.m:160-193): the minimum spanning tree of the graph weighted by SVec + 1,
+    rotations multiplied along it from node 1 (R_1 = I).
+
+    This follows MPLS.m:162 (weights ``SVec + 1``), not ``Utils/MST.m``, whose ``sparse`` call drops the edges with
+    ``SVec == 0``.  Ties of the computed ``SVec + 1`` are broken by the edge's (i, j) order, so the tree is unique.  A graph that
+    is not connected raises DescError.  With ``return_info`` also a dict whose ``tree_edges`` are the 0-based rows of the caller's
+    ``Ind`` that form the tree (ascending)."""
+    n, ii, jj, rij, perm = marshal_edges(Ind, RijMat)
+    if ii.shape[0] == 0:
+        raise ValueError("empty edge list")
+    S = np.asarray(SVec, dtype=np.float64).reshape(-1)
+    if S.shape[0] != ii.shape[0]:
+        raise ValueError("SVec must have one entry per edge")
+    if perm is not None:
+        S = S[perm]
+    prob = _lib.ProblemArrays(n, ii, jj, rij)
+    R, tree = _lib.mst_run(prob, S, device=device)
+    if not return_info:
+        return R
+    rows = np.sort(perm[tree]) if perm is not None else tree
+    return R, dict(tree_edges=rows)
+
+
+def CEMP_GCW(Ind, RijMat, CEMP_parameters, return_info=False):
+    """R_est = CEMP_GCW(Ind, RijMat, CEMP_parameters) -- Algorithms/CEMP_GCW.m: CEMP's SVec, then the row-normalised weighted
+    spectral step with the weights 1/(SVec + 1e-8) of CEMP_GCW.m:144 (GCW() uses 1/(SVec^1.5 + 1e-8), GCW.m:20).  Both stages
+    run on one device problem."""
+    n, ii, jj, rij, perm = marshal_edges(Ind, RijMat)
+    if ii.shape[0] == 0:
+        raise ValueError("empty edge list")
+    beta = _param_vec(CEMP_parameters, "reweighting", "CEMP_parameters")
+    prob = _lib.ProblemArrays(n, ii, jj, rij)
+    dprob = _lib.DeviceProblem(prob, int(_get(CEMP_parameters, "device", 0)))
+    try:
+        S, ms = _lib.cemp_run(dprob, beta, int(_get(CEMP_parameters, "max_iter")), int(_get(CEMP_parameters, "nsample")),
+                              int(_get(CEMP_parameters, "seed", 0)))
+        R, info = _lib.spectral_run(dprob, 1.0 / (S + 1e-8), True)                               # CEMP_GCW.m:144-146
+    finally:
+        dprob.free()
+    return (R, dict(info, ms_cemp=ms)) if return_info else R
+
+
 def DESC(Ind, RijMat, params, return_info=False):
     """[R_est, R_init, S_vec] = DESC(Ind, RijMat, params) -- Algorithms/DESC.m:14 (the call of
     Demo/compare_algorithms.m:72): DESC_PGD (:16-261) -> GCW initialisation (:263) -> reweighted

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "device_utils.h"
+#include "cemp_state.h"
 
 namespace desc {
 namespace {
@@ -138,8 +139,18 @@ __global__ __launch_bounds__(256) void k_cemp_node_seg(const int32_t* pos_edge, 
     }
 }
 
+// Epilogue MP = false: CEMP.m:125-126, the round's new s_ij.  MP = true: the H step of MPLS (MPLS.m:223-240) -- the gathered values are the
+// residuals (S_old = ResVec), and the edge's h_ij goes straight into RH[e] = (1 - alpha) Res[e] + alpha h_ij (:240).
+template <bool MP>
+__device__ __forceinline__ void cemp_store(double* S_new, int slot_a, int slot_b, int e, double acc, const double* res, double* rh, double alpha) {
+    if (MP) rh[e] = (1.0 - alpha) * res[e] + alpha * acc;
+    else { S_new[slot_a] = acc; if (slot_b >= 0) S_new[slot_b] = acc; }
+}
+
+template <bool MP>
 __global__ __launch_bounds__(256) void k_cemp_round(const int32_t* pos_edge, const int32_t* e_jk, const int32_t* e_ki, const double* S0,
-                                                    const double* S_old, double* S_new, int m_pos, int nsample, double beta) {
+                                                    const double* S_old, double* S_new, int m_pos, int nsample, double beta,
+                                                    const double* res, double* rh, double alpha) {
     const int lane = threadIdx.x & 63;
     const int64_t wid = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, nw = ((int64_t)gridDim.x * 256) >> 6;
     for (int64_t l = wid; l < m_pos; l += nw) {
@@ -162,7 +173,7 @@ __global__ __launch_bounds__(256) void k_cemp_round(const int32_t* pos_edge, con
 #pragma unroll
             for (int u = 0; u < 4; ++u) if (lane + 64 * u < nsample) acc += (wr[u] * rws) * dr[u];   // :122-125
             acc = group_sum<64>(acc);
-            if (lane == 0) S_new[pos_edge[l]] = acc;
+            if (lane == 0) cemp_store<MP>(S_new, pos_edge[l], -1, pos_edge[l], acc, res, rh, alpha);
             continue;
         }
         double wsum = 0.0;
@@ -178,7 +189,7 @@ __global__ __launch_bounds__(256) void k_cemp_round(const int32_t* pos_edge, con
             acc += (w / wsum) * S0[c];                                               // :122-125
         }
         acc = group_sum<64>(acc);
-        if (lane == 0) S_new[pos_edge[l]] = acc;
+        if (lane == 0) cemp_store<MP>(S_new, pos_edge[l], -1, pos_edge[l], acc, res, rh, alpha);
     }
 }
 
@@ -199,9 +210,10 @@ __global__ __launch_bounds__(256) void k_cemp_extract(const double* Sfull, const
 // numbered j-block-major, so the workgroups in flight at any moment gather S({j,k}) from the same JB rows.  poe: edge -> index among the edges
 // with cycles (NULL: every edge has cycles and the map is the identity).
 constexpr int CEMP_MAXB = 16;                      // nodes per band at most
+template <bool MP>
 __global__ __launch_bounds__(256) void k_cemp_round_tile(const int32_t* rowptr, const int32_t* adj, const int32_t* adj_eid, const int32_t* poe, const int32_t* slot_b,
                                                          const uint32_t* pk, const double* S0, const double* S_old, double* S_new, int n, int BI, int JB, int n_iband,
-                                                         int nsample, double beta) {
+                                                         int nsample, double beta, const double* res, double* rh, double alpha) {
     extern __shared__ double s_rows[];             // rows of the band: S_old[rowptr[i0] .. rowptr[i1])
     __shared__ int s_a[CEMP_MAXB], s_cnt[CEMP_MAXB + 1], s_rb[CEMP_MAXB];      // per node of the band: first slot of its run, edges in the tile, its row's offset in s_rows
     const int jb = blockIdx.x / n_iband, ib = blockIdx.x % n_iband;
@@ -262,7 +274,7 @@ __global__ __launch_bounds__(256) void k_cemp_round_tile(const int32_t* rowptr, 
                 const double w = act ? exp(-beta * (si + sj[u])) : 0.0;                                     // :118-120  s_ik + s_jk
                 const double rws = 1.0 / group_sum<64>(w);      // one division per edge (the reference divides every weight: the same to 1 ulp)
                 const double acc = group_sum<64>(act ? (w * rws) * dd[u] : 0.0);                            // :122-125
-                if (lane == 0 && on[u]) { S_new[slot[u]] = acc; S_new[slot_b[ee[u]]] = acc; }
+                if (lane == 0 && on[u]) cemp_store<MP>(S_new, slot[u], MP ? -1 : slot_b[ee[u]], ee[u], acc, res, rh, alpha);
             }
         }
         return;
@@ -307,7 +319,7 @@ __global__ __launch_bounds__(256) void k_cemp_round_tile(const int32_t* rowptr, 
             }
         }
         acc = group_sum<64>(acc);
-        if (lane == 0) { S_new[slot] = acc; S_new[slot_b[e]] = acc; }
+        if (lane == 0) cemp_store<MP>(S_new, slot, MP ? -1 : slot_b[e], e, acc, res, rh, alpha);
     }
 }
 
@@ -320,18 +332,132 @@ __global__ __launch_bounds__(256) void k_cemp_inverse(const int32_t* pos_edge, i
 }
 int env_int_c(const char* name, int dflt) { const char* v = std::getenv(name); return v ? std::atoi(v) : dflt; }
 
-struct DevC {
-    hvec<void*> p;
-    ~DevC() { for (void* q : p) dev_free(q); }
-    template <class T> int alloc(T** out, size_t count) {
-        void* q = nullptr;
-        DESC_HIP(dev_alloc(&q, sizeof(T) * (count ? count : 1)));
-        p.push_back(q); *out = (T*)q;
+}  // namespace
+
+template <class T> int CempState::alloc(T** out, size_t count) {
+    void* q = nullptr;
+    DESC_HIP(dev_alloc(&q, sizeof(T) * (count ? count : 1)));
+    blocks.push_back(q); *out = (T*)q;
+    return DESC_OK;
+}
+CempState::~CempState() { for (void* q : blocks) dev_free(q); }
+
+int cemp_build(const desc_device_problem* dp, int32_t nsample, uint64_t seed, bool need_poe, CempState& st) {
+    int rc = DESC_OK;
+    const int64_t m = dp->m, n = dp->n;
+    st.n = n; st.m = m; st.nsample = nsample;
+    // samples: on the device; graphs beyond the device sampler's staging budget fall back to the host sampler
+    int64_t mp = 0;
+    int32_t max_deg = 0;
+    const bool want_tiles = env_int_c("DESC_DEBUG_CEMP_TILES", 1) != 0;
+    rc = build_cemp_samples_device(dp, nsample, seed, &mp, &st.d_pos, &st.d_k, &st.d_ejk, &st.d_eki, want_tiles ? &st.d_pk : nullptr, &max_deg);
+    for (void* q : {(void*)st.d_pos, (void*)st.d_k, (void*)st.d_ejk, (void*)st.d_eki, (void*)st.d_pk}) if (q) st.blocks.push_back(q);
+    if (rc == DESC_ERR_TOO_LARGE) {
+        hvec<int32_t> pos_edge, kk, e_jk, e_ki;
+        const desc_problem hv = host_view(dp);
+        if ((rc = build_cemp_samples_host(&hv, nsample, seed, pos_edge, kk, e_jk, e_ki))) return rc;
+        mp = (int64_t)pos_edge.size();
+        const int64_t mch = mp * nsample;
+        if (mch >= (1ll << 31)) return fail(DESC_ERR_TOO_LARGE, "m_pos * nsample exceeds 2^31");
+        if (mp) {
+            if ((rc = st.alloc(&st.d_pos, mp)) || (rc = st.alloc(&st.d_k, mch)) || (rc = st.alloc(&st.d_ejk, mch)) || (rc = st.alloc(&st.d_eki, mch))) return rc;
+            DESC_HIP(hipMemcpy(st.d_pos, pos_edge.data(), sizeof(int32_t) * mp, hipMemcpyHostToDevice));
+            DESC_HIP(hipMemcpy(st.d_k, kk.data(), sizeof(int32_t) * mch, hipMemcpyHostToDevice));
+            DESC_HIP(hipMemcpy(st.d_ejk, e_jk.data(), sizeof(int32_t) * mch, hipMemcpyHostToDevice));
+            DESC_HIP(hipMemcpy(st.d_eki, e_ki.data(), sizeof(int32_t) * mch, hipMemcpyHostToDevice));
+        }
+    } else if (rc) return rc;
+    const int64_t mc = mp * nsample;
+    st.mp = mp; st.mc = mc; st.max_deg = max_deg;
+    const int32_t *d_ii = dp->d_ii, *d_jj = dp->d_jj; const double* d_rij = dp->d_rij;
+    // tiles: the device sampler delivered the packed row positions (rows shorter than 2^16); the band of one tile must fit the LDS
+    const bool tiles = st.d_pk != nullptr && mp > 0 && max_deg > 0 && (size_t)max_deg * sizeof(double) <= 64 * 1024;
+    st.tiles = tiles;
+    const int64_t slen = tiles ? 2 * m : m;                                          // CSR-aligned: every edge value in both endpoint rows
+    if ((rc = st.alloc(&st.d_S0, mc)) || (rc = st.alloc(&st.d_S[0], slen)) || (rc = st.alloc(&st.d_S[1], slen))) return rc;
+    if (tiles && ((rc = st.alloc(&st.d_slot_a, m)) || (rc = st.alloc(&st.d_slot_b, m)) || (rc = st.alloc(&st.d_out, m)))) return rc;
+    if (m) {
+        const int g = (int)std::min<int64_t>(1024, (slen + 255) / 256);
+        hipLaunchKernelGGL(k_fill1, dim3(g), dim3(256), 0, 0, st.d_S[0], slen, 1.0);     // SVec(~IndPosbin) = 1 (:103)
+        hipLaunchKernelGGL(k_fill1, dim3(g), dim3(256), 0, 0, st.d_S[1], slen, 1.0);
+        if (tiles) hipLaunchKernelGGL(k_cemp_slots, dim3((unsigned)std::min<int64_t>(4096, (m + 255) / 256)), dim3(256), 0, 0, d_ii, d_jj, dp->d_rowptr, dp->d_adj, st.d_slot_a, st.d_slot_b, m);
+    }
+    st.cur = 0;
+    if (need_poe && mp == 0 && m) {                                                  // no edge has a cycle
+        if ((rc = st.alloc(&st.d_poe, m))) return rc;
+        DESC_HIP(hipMemsetAsync(st.d_poe, 0xFF, sizeof(int32_t) * m, 0));
+    }
+    if (!mp) return DESC_OK;
+    st.g = (int)std::min<int64_t>(8192, (mp + 3) / 4);
+    const size_t lds0 = (size_t)max_deg * 10 * sizeof(double);
+    if (tiles && lds0 <= 150 * 1024 && env_int_c("DESC_DEBUG_STAGED_LAYOUT", 1) != 0) {       // node i's rotation blocks in the LDS
+        int32_t* d_node_seg = nullptr;
+        if ((rc = st.alloc(&d_node_seg, n + 1))) return rc;
+        hipLaunchKernelGGL(k_cemp_node_seg, dim3((unsigned)std::min<int64_t>(4096, (mp + 255) / 256)), dim3(256), 0, 0, st.d_pos, d_ii, mp, (int)n, d_node_seg);
+        if (lds0 > 64 * 1024) DESC_HIP(hipFuncSetAttribute((const void*)k_cemp_s0_staged, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds0));
+        hipLaunchKernelGGL(k_cemp_s0_staged, dim3((unsigned)std::max<int64_t>(1, n)), dim3(512), lds0, 0, st.d_pos, d_ii, d_jj, st.d_k, st.d_ejk, st.d_pk, dp->d_rowptr, dp->d_adj_eid,
+                           d_node_seg, d_rij, st.d_S0, st.d_S[0], st.d_S[1], (int)n, nsample, st.d_slot_a, st.d_slot_b);
+    } else
+    hipLaunchKernelGGL(k_cemp_s0, dim3(st.g), dim3(256), 0, 0, st.d_pos, d_ii, d_jj, st.d_k, st.d_ejk, st.d_eki, d_rij, st.d_S0, st.d_S[0], st.d_S[1], (int)mp, nsample,
+                       tiles ? st.d_slot_a : (const int32_t*)nullptr, tiles ? st.d_slot_b : (const int32_t*)nullptr);
+    // tile shape: the band's rows in <= 32 KiB of LDS (several workgroups per CU), the rows of a j-block ~2.5 MiB (they share an XCD's L2 with the streams)
+    const int64_t avg_deg = std::max<int64_t>(1, 2 * m / std::max<int64_t>(1, n));
+    int BI = (int)std::max<int64_t>(1, std::min<int64_t>(CEMP_MAXB, (32 * 1024 / 8) / std::max(max_deg, 1)));
+    BI = std::max(1, std::min(BI, env_int_c("DESC_DEBUG_CEMP_BI", BI)));
+    const int JB = (int)std::max<int64_t>(32, env_int_c("DESC_DEBUG_CEMP_JB", (int)std::max<int64_t>(32, (5ll << 19) / (8 * avg_deg))));      // measured: flat from ~2.5 MiB of rows on (profiles/r04_cemp_tile_scan.txt)
+    st.BI = BI; st.JB = JB;
+    st.n_iband = (int)((n + BI - 1) / BI); st.n_jblock = (int)((n + JB - 1) / JB);
+    st.lds = (size_t)BI * (size_t)max_deg * sizeof(double);
+    if ((tiles || need_poe) && mp != m) {                                            // edge -> index among the edges with cycles
+        if ((rc = st.alloc(&st.d_poe, m))) return rc;
+        DESC_HIP(hipMemsetAsync(st.d_poe, 0xFF, sizeof(int32_t) * m, 0));
+        hipLaunchKernelGGL(k_cemp_inverse, dim3((unsigned)std::min<int64_t>(4096, (mp + 255) / 256)), dim3(256), 0, 0, st.d_pos, st.d_poe, mp);
+    }
+    if (tiles && st.lds > 64 * 1024) {
+        DESC_HIP(hipFuncSetAttribute((const void*)k_cemp_round_tile<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)st.lds));
+        DESC_HIP(hipFuncSetAttribute((const void*)k_cemp_round_tile<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)st.lds));
+    }
+    return DESC_OK;
+}
+
+int cemp_rounds(const desc_device_problem* dp, CempState& st, const double* beta, int32_t n_beta, int32_t max_iter, bool verbose) {
+    if (!st.mp) {
+        if (verbose) for (int it = 0; it < max_iter; ++it) printf("Reweighting Iteration %d Completed!\n", it + 1);
         return DESC_OK;
     }
-};
+    for (int it = 0; it < max_iter; ++it) {                                         // :107
+        const double b = beta[it < n_beta ? it : n_beta - 1];                       // :30-34: missing betas repeat the last one
+        const int cur = st.cur;
+        if (st.tiles)
+            hipLaunchKernelGGL(k_cemp_round_tile<false>, dim3((unsigned)((int64_t)st.n_iband * st.n_jblock)), dim3(256), st.lds, 0, dp->d_rowptr, dp->d_adj, dp->d_adj_eid, st.d_poe,
+                               st.d_slot_b, st.d_pk, st.d_S0, st.d_S[cur], st.d_S[cur ^ 1], (int)st.n, st.BI, st.JB, st.n_iband, st.nsample, b,
+                               (const double*)nullptr, (double*)nullptr, 0.0);
+        else
+            hipLaunchKernelGGL(k_cemp_round<false>, dim3(st.g), dim3(256), 0, 0, st.d_pos, st.d_ejk, st.d_eki, st.d_S0, st.d_S[cur], st.d_S[cur ^ 1], (int)st.mp, st.nsample, b,
+                               (const double*)nullptr, (double*)nullptr, 0.0);
+        st.cur ^= 1;
+        if (verbose) printf("Reweighting Iteration %d Completed!\n", it + 1);   // MPLS.m:156
+    }
+    DESC_HIP(hipGetLastError());
+    return DESC_OK;
+}
 
-}  // namespace
+const double* cemp_svec(CempState& st) {
+    if (!st.tiles) return st.d_S[st.cur];
+    hipLaunchKernelGGL(k_cemp_extract, dim3((unsigned)std::min<int64_t>(2048, (st.m + 255) / 256)), dim3(256), 0, 0, st.d_S[st.cur], st.d_slot_a, st.d_out, st.m);
+    return st.d_out;
+}
+
+void cemp_hstep(const desc_device_problem* dp, CempState& st, const double* res_full, const double* res, double* rh, double beta, double alpha) {
+    if (!st.mp) return;
+    if (st.tiles)
+        hipLaunchKernelGGL(k_cemp_round_tile<true>, dim3((unsigned)((int64_t)st.n_iband * st.n_jblock)), dim3(256), st.lds, 0, dp->d_rowptr, dp->d_adj, dp->d_adj_eid, st.d_poe,
+                           st.d_slot_b, st.d_pk, st.d_S0, res_full, (double*)nullptr, (int)st.n, st.BI, st.JB, st.n_iband, st.nsample, beta, res, rh, alpha);
+    else
+        hipLaunchKernelGGL(k_cemp_round<true>, dim3(st.g), dim3(256), 0, 0, st.d_pos, st.d_ejk, st.d_eki, st.d_S0, res, (double*)nullptr, (int)st.mp, st.nsample, beta,
+                           res, rh, alpha);
+}
+
 }  // namespace desc
 
 using namespace desc;
@@ -357,90 +483,12 @@ extern "C" int desc_cemp_run_dev(const desc_device_problem* dp, const double* be
     int rc = DESC_OK;
     auto t0 = std::chrono::steady_clock::now();
     DESC_HIP(hipSetDevice(dp->device));
-    const int64_t m = dp->m;
-    // samples: on the device; graphs beyond the device sampler's staging budget fall back to the host sampler
-    int64_t mp = 0;
-    int32_t *d_pos = nullptr, *d_k = nullptr, *d_ejk = nullptr, *d_eki = nullptr;
-    uint32_t* d_pk = nullptr;
-    int32_t max_deg = 0;
-    struct Owned { int32_t **a, **b, **c, **d; uint32_t** e; ~Owned() { for (int32_t** q : {a, b, c, d}) if (*q) dev_free(*q); if (*e) dev_free(*e); } } owned{&d_pos, &d_k, &d_ejk, &d_eki, &d_pk};
-    const bool want_tiles = env_int_c("DESC_DEBUG_CEMP_TILES", 1) != 0;
-    rc = build_cemp_samples_device(dp, nsample, seed, &mp, &d_pos, &d_k, &d_ejk, &d_eki, want_tiles ? &d_pk : nullptr, &max_deg);
-    if (rc == DESC_ERR_TOO_LARGE) {
-        hvec<int32_t> pos_edge, kk, e_jk, e_ki;
-        const desc_problem hv = host_view(dp);
-        if ((rc = build_cemp_samples_host(&hv, nsample, seed, pos_edge, kk, e_jk, e_ki))) return rc;
-        mp = (int64_t)pos_edge.size();
-        const int64_t mch = mp * nsample;
-        if (mch >= (1ll << 31)) return fail(DESC_ERR_TOO_LARGE, "m_pos * nsample exceeds 2^31");
-        if (mp) {
-            DESC_HIP(dev_alloc((void**)&d_pos, sizeof(int32_t) * mp)); DESC_HIP(dev_alloc((void**)&d_k, sizeof(int32_t) * mch));
-            DESC_HIP(dev_alloc((void**)&d_ejk, sizeof(int32_t) * mch)); DESC_HIP(dev_alloc((void**)&d_eki, sizeof(int32_t) * mch));
-            DESC_HIP(hipMemcpy(d_pos, pos_edge.data(), sizeof(int32_t) * mp, hipMemcpyHostToDevice));
-            DESC_HIP(hipMemcpy(d_k, kk.data(), sizeof(int32_t) * mch, hipMemcpyHostToDevice));
-            DESC_HIP(hipMemcpy(d_ejk, e_jk.data(), sizeof(int32_t) * mch, hipMemcpyHostToDevice));
-            DESC_HIP(hipMemcpy(d_eki, e_ki.data(), sizeof(int32_t) * mch, hipMemcpyHostToDevice));
-        }
-    } else if (rc) return rc;
-    const int64_t mc = mp * nsample;
-    const int64_t n = dp->n;
-    DevC D;
-    const int32_t *d_ii = dp->d_ii, *d_jj = dp->d_jj; const double* d_rij = dp->d_rij; double *d_S0, *d_S[2];
-    // tiles: the device sampler delivered the packed row positions (rows shorter than 2^16); the band of one tile must fit the LDS
-    const bool tiles = d_pk != nullptr && mp > 0 && max_deg > 0 && (size_t)max_deg * sizeof(double) <= 64 * 1024;
-    const int64_t slen = tiles ? 2 * m : m;                                          // CSR-aligned: every edge value in both endpoint rows
-    int32_t *d_slot_a = nullptr, *d_slot_b = nullptr, *d_poe = nullptr; double* d_out = nullptr;
-    if ((rc = D.alloc(&d_S0, mc)) || (rc = D.alloc(&d_S[0], slen)) || (rc = D.alloc(&d_S[1], slen))) return rc;
-    if (tiles && ((rc = D.alloc(&d_slot_a, m)) || (rc = D.alloc(&d_slot_b, m)) || (rc = D.alloc(&d_out, m)))) return rc;
-    if (m) {
-        const int g = (int)std::min<int64_t>(1024, (slen + 255) / 256);
-        hipLaunchKernelGGL(k_fill1, dim3(g), dim3(256), 0, 0, d_S[0], slen, 1.0);     // SVec(~IndPosbin) = 1 (:103)
-        hipLaunchKernelGGL(k_fill1, dim3(g), dim3(256), 0, 0, d_S[1], slen, 1.0);
-        if (tiles) hipLaunchKernelGGL(k_cemp_slots, dim3((unsigned)std::min<int64_t>(4096, (m + 255) / 256)), dim3(256), 0, 0, d_ii, d_jj, dp->d_rowptr, dp->d_adj, d_slot_a, d_slot_b, m);
-    }
-    int cur = 0;
-    if (mp) {
-        const int g = (int)std::min<int64_t>(8192, (mp + 3) / 4);
-        const size_t lds0 = (size_t)max_deg * 10 * sizeof(double);
-        if (tiles && lds0 <= 150 * 1024 && env_int_c("DESC_DEBUG_STAGED_LAYOUT", 1) != 0) {       // node i's rotation blocks in the LDS
-            int32_t* d_node_seg = nullptr;
-            if ((rc = D.alloc(&d_node_seg, n + 1))) return rc;
-            hipLaunchKernelGGL(k_cemp_node_seg, dim3((unsigned)std::min<int64_t>(4096, (mp + 255) / 256)), dim3(256), 0, 0, d_pos, d_ii, mp, (int)n, d_node_seg);
-            if (lds0 > 64 * 1024) DESC_HIP(hipFuncSetAttribute((const void*)k_cemp_s0_staged, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds0));
-            hipLaunchKernelGGL(k_cemp_s0_staged, dim3((unsigned)std::max<int64_t>(1, n)), dim3(512), lds0, 0, d_pos, d_ii, d_jj, d_k, d_ejk, d_pk, dp->d_rowptr, dp->d_adj_eid, d_node_seg, d_rij,
-                               d_S0, d_S[0], d_S[1], (int)n, nsample, d_slot_a, d_slot_b);
-        } else
-        hipLaunchKernelGGL(k_cemp_s0, dim3(g), dim3(256), 0, 0, d_pos, d_ii, d_jj, d_k, d_ejk, d_eki, d_rij, d_S0, d_S[0], d_S[1], (int)mp, nsample,
-                           tiles ? d_slot_a : (const int32_t*)nullptr, tiles ? d_slot_b : (const int32_t*)nullptr);
-        // tile shape: the band's rows in <= 32 KiB of LDS (several workgroups per CU), the rows of a j-block ~2.5 MiB (they share an XCD's L2 with the streams)
-        const int64_t avg_deg = std::max<int64_t>(1, 2 * m / std::max<int64_t>(1, n));
-        int BI = (int)std::max<int64_t>(1, std::min<int64_t>(CEMP_MAXB, (32 * 1024 / 8) / std::max(max_deg, 1)));
-        BI = std::max(1, std::min(BI, env_int_c("DESC_DEBUG_CEMP_BI", BI)));
-        const int JB = (int)std::max<int64_t>(32, env_int_c("DESC_DEBUG_CEMP_JB", (int)std::max<int64_t>(32, (5ll << 19) / (8 * avg_deg))));      // measured: flat from ~2.5 MiB of rows on (profiles/r04_cemp_tile_scan.txt)
-        const int n_iband = (int)((n + BI - 1) / BI), n_jblock = (int)((n + JB - 1) / JB);
-        const size_t lds = (size_t)BI * (size_t)max_deg * sizeof(double);
-        if (tiles) {
-            if (mp != m) {                                                           // edge -> index among the edges with cycles
-                if ((rc = D.alloc(&d_poe, m))) return rc;
-                DESC_HIP(hipMemsetAsync(d_poe, 0xFF, sizeof(int32_t) * m, 0));
-                hipLaunchKernelGGL(k_cemp_inverse, dim3((unsigned)std::min<int64_t>(4096, (mp + 255) / 256)), dim3(256), 0, 0, d_pos, d_poe, mp);
-            }
-            if (lds > 64 * 1024) DESC_HIP(hipFuncSetAttribute((const void*)k_cemp_round_tile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        }
-        for (int it = 0; it < max_iter; ++it) {                                     // :107
-            const double b = beta[it < n_beta ? it : n_beta - 1];                   // :30-34: missing betas repeat the last one
-            if (tiles)
-                hipLaunchKernelGGL(k_cemp_round_tile, dim3((unsigned)((int64_t)n_iband * n_jblock)), dim3(256), lds, 0, dp->d_rowptr, dp->d_adj, dp->d_adj_eid, d_poe, d_slot_b,
-                                   d_pk, d_S0, d_S[cur], d_S[cur ^ 1], (int)n, BI, JB, n_iband, nsample, b);
-            else
-                hipLaunchKernelGGL(k_cemp_round, dim3(g), dim3(256), 0, 0, d_pos, d_ejk, d_eki, d_S0, d_S[cur], d_S[cur ^ 1], (int)mp, nsample, b);
-            cur ^= 1;
-        }
-        DESC_HIP(hipGetLastError());
-    }
-    if (tiles && m) hipLaunchKernelGGL(k_cemp_extract, dim3((unsigned)std::min<int64_t>(2048, (m + 255) / 256)), dim3(256), 0, 0, d_S[cur], d_slot_a, d_out, m);
+    CempState st;
+    if ((rc = cemp_build(dp, nsample, seed, false, st))) return rc;                  // CEMP.m:44-103
+    if ((rc = cemp_rounds(dp, st, beta, n_beta, max_iter, false))) return rc;        // :107-128
+    const double* d_svec = dp->m ? cemp_svec(st) : nullptr;
     DESC_HIP(hipDeviceSynchronize());
-    if (m) DESC_HIP(hipMemcpy(s_vec, tiles ? d_out : d_S[cur], sizeof(double) * m, hipMemcpyDeviceToHost));
+    if (dp->m) DESC_HIP(hipMemcpy(s_vec, d_svec, sizeof(double) * dp->m, hipMemcpyDeviceToHost));
     if (ms_total) *ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return DESC_OK;
     });

@@ -113,6 +113,9 @@ int build_cemp_samples_device(const desc_device_problem* dp, int32_t nsample, ui
 inline desc_problem host_view(const desc_device_problem* dp) { return desc_problem{dp->n, dp->m, dp->ii.data(), dp->jj.data(), nullptr}; }
 int build_cemp_samples_host(const desc_problem* prob, int32_t nsample, uint64_t seed, hvec<int32_t>& pos_edge,
                             hvec<int32_t>& kk, hvec<int32_t>& e_jk, hvec<int32_t>& e_ki);
+// MPLS.m:160-193 (mst.hip): minimum spanning tree of the graph weighted by d_s + 1 (d_s: m doubles on the problem's device) and the
+// rotations propagated from node 1 along it into R_out (n*9 host doubles); tree_edges (nullable): the n - 1 edge ids, ascending
+int mst_device(const desc_device_problem* dp, const double* d_s, double* R_out, int32_t* tree_edges);
 // Worker threads of the host-side passes.  An exception that escapes a thread body (bad_alloc in a vector, system_error from the
 // thread constructor) would call std::terminate and take the MATLAB / Python host down: every body runs behind a catch, the
 // calling thread takes share 0 itself, all workers are joined, and the first exception is rethrown on the calling thread -- where

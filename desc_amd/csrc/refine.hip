@@ -20,11 +20,10 @@
 #include <vector>
 
 #include "device_utils.h"
+#include "laa.h"
 
 namespace desc {
 namespace {
-
-struct Quat { double a, x, y, z; };
 
 // ---- per-edge / per-node maps ------------------------------------------------------------
 // R2Q.m:9-12 for a column-major 3x3 block (optionally transposed)
@@ -321,18 +320,17 @@ int device_quantile(const double* d_x, int64_t m, double p, double* d_mm, unsign
     return DESC_OK;
 }
 
-struct DevR {
-    hvec<void*> p;
-    ~DevR() { for (void* q : p) dev_free(q); }
-    template <class T> int alloc(T** out, size_t count) {
-        void* q = nullptr;
-        DESC_HIP(dev_alloc(&q, sizeof(T) * (count ? count : 1)));
-        p.push_back(q); *out = (T*)q;
-        return DESC_OK;
-    }
-};
 
 }  // namespace
+
+template <class T> int LaaSolver::alloc(T** out, size_t count) {
+    void* q = nullptr;
+    DESC_HIP(dev_alloc(&q, sizeof(T) * (count ? count : 1)));
+    blocks.push_back(q); *out = (T*)q;
+    return DESC_OK;
+}
+LaaSolver::~LaaSolver() { for (void* q : blocks) dev_free(q); }
+
 }  // namespace desc
 
 using namespace desc;
@@ -344,6 +342,96 @@ __global__ void k_incidence_sign(const int32_t* rowptr, const int32_t* adj, int8
     for (int v = row0; v < n; v += nrows)
         for (int t = rowptr[v] + l16; t < rowptr[v + 1]; t += 16) sgn[t] = v < adj[t] ? -1 : +1;
 }
+
+namespace desc {
+
+int laa_setup(const desc_device_problem* dp, const double* R_init, LaaSolver& L) {
+    int rc = DESC_OK;
+    const int64_t n = dp->n, m = dp->m;
+    L.dp = dp; L.n = n; L.m = m;
+    CgScal* d_sc = nullptr;
+    if ((rc = L.alloc(&L.d_sgn, 2 * m)) || (rc = L.alloc(&L.d_Rinit, 9 * n)) || (rc = L.alloc(&L.d_w, m)) || (rc = L.alloc(&L.d_B, 3 * m)) ||
+        (rc = L.alloc(&L.d_rhs, 3 * n)) || (rc = L.alloc(&L.d_diag, n)) || (rc = L.alloc(&L.d_x, 3 * n)) || (rc = L.alloc(&L.d_r, 3 * n)) ||
+        (rc = L.alloc(&L.d_z, 3 * n)) || (rc = L.alloc(&L.d_p, 3 * n)) || (rc = L.alloc(&L.d_q, 3 * n)) || (rc = L.alloc(&L.d_Wv, 3 * n)) ||
+        (rc = L.alloc(&L.d_score, L.sgrid)) || (rc = L.alloc(&L.d_Rout, 9 * n)) || (rc = L.alloc(&L.d_Q, n)) || (rc = L.alloc(&L.d_QQ, m)) ||
+        (rc = L.alloc(&d_sc, 1)))
+        return rc;
+    L.d_sc = d_sc;
+    constexpr unsigned QCAP = 1u << 20;
+    if ((rc = L.alloc(&L.d_mm, 128)) || (rc = L.alloc(&L.d_cand, QCAP)) || (rc = L.alloc(&L.d_qh, QBINS + 1))) return rc;
+    L.part.resize(L.sgrid);
+    DESC_HIP(hipMemcpy(L.d_Rinit, R_init, sizeof(double) * 9 * n, hipMemcpyHostToDevice));
+    if (m)
+        hipLaunchKernelGGL(k_incidence_sign, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (n * 16 + 255) / 256))), dim3(256), 0, 0,
+                           dp->d_rowptr, dp->d_adj, L.d_sgn, (int)n);
+    L.egrid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (m + 255) / 256));
+    L.ngrid = (int)std::max<int64_t>(1, std::min<int64_t>(512, (n + 255) / 256));
+    L.rgrid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n * 16 + 255) / 256));
+    hipLaunchKernelGGL(k_r2q, dim3(L.ngrid), dim3(256), 0, 0, L.d_Rinit, L.d_Q, n, 0);              // Q = R2Q(R_init)        (DESC.m:270, MPLS.m:205)
+    if (m) hipLaunchKernelGGL(k_r2q, dim3(L.egrid), dim3(256), 0, 0, dp->d_rij, L.d_QQ, m, 1);      // QQ = R2Q(permute(RijMat)) (:265,271; MPLS.m:200,206)
+    return DESC_OK;
+}
+
+int laa_step(LaaSolver& L, double* score_out) {
+    const desc_device_problem* dp = L.dp;
+    const int64_t n = L.n, m = L.m;
+    const int32_t *d_rowptr = dp->d_rowptr, *d_adj = dp->d_adj, *d_eid = dp->d_adj_eid;
+    CgScal* d_sc = (CgScal*)L.d_sc;
+    const int egrid = L.egrid, ngrid = L.ngrid, rgrid = L.rgrid;
+    if (m) hipLaunchKernelGGL(k_edge_log, dim3(egrid), dim3(256), 0, 0, L.d_Q, L.d_QQ, dp->d_ii, dp->d_jj, L.d_B, m);
+    hipLaunchKernelGGL(k_rhs, dim3(rgrid), dim3(256), 0, 0, d_rowptr, d_eid, L.d_sgn, L.d_w, L.d_B, L.d_rhs, L.d_diag, (int)n);
+    hipLaunchKernelGGL(k_cg_init, dim3(ngrid), dim3(256), 0, 0, L.d_rhs, L.d_diag, L.d_x, L.d_r, L.d_z, L.d_p, (int)n);
+    hipLaunchKernelGGL(k_dot3, dim3(1), dim3(256), 0, 0, L.d_r, L.d_z, (int)n, &d_sc->rz[0]);
+    hipLaunchKernelGGL(k_dot3, dim3(1), dim3(256), 0, 0, L.d_r, L.d_r, (int)n, &d_sc->bnorm[0]);
+    const int cg_max = (int)std::min<int64_t>(20000, 20 * n + 200);
+    CgScal hs;
+    int k = 0;
+    for (k = 1; k <= cg_max; ++k) {
+        hipLaunchKernelGGL(k_lap, dim3(rgrid), dim3(256), 0, 0, d_rowptr, d_adj, d_eid, L.d_w, L.d_p, L.d_q, (int)n);
+        hipLaunchKernelGGL(k_dot3, dim3(1), dim3(256), 0, 0, L.d_p, L.d_q, (int)n, &d_sc->pq[0]);
+        hipLaunchKernelGGL(k_cg_update, dim3(ngrid), dim3(256), 0, 0, d_sc, L.d_diag, L.d_p, L.d_q, L.d_x, L.d_r, L.d_z, (int)n);
+        hipLaunchKernelGGL(k_dot3, dim3(1), dim3(256), 0, 0, L.d_r, L.d_z, (int)n, &d_sc->rz_new[0]);
+        hipLaunchKernelGGL(k_cg_dir, dim3(ngrid), dim3(256), 0, 0, d_sc, L.d_z, L.d_p, (int)n);
+        hipLaunchKernelGGL(k_cg_roll, dim3(1), dim3(64), 0, 0, d_sc);
+        if (k % 25 == 0 || k == cg_max) {                                               // convergence probe
+            hipLaunchKernelGGL(k_dot3, dim3(1), dim3(256), 0, 0, L.d_r, L.d_r, (int)n, &d_sc->rnorm[0]);
+            DESC_HIP(hipMemcpy(&hs, d_sc, sizeof hs, hipMemcpyDeviceToHost));
+            bool done = true;
+            for (int c = 0; c < 3; ++c) if (hs.rnorm[c] > 1e-26 * hs.bnorm[c] && hs.rnorm[c] > 1e-300) done = false;   // |r| <= 1e-13 |b|
+            if (done || k == cg_max) {
+                for (int c = 0; c < 3; ++c) if (hs.bnorm[c] > 0) L.cg_worst = std::max(L.cg_worst, std::sqrt(hs.rnorm[c] / hs.bnorm[c]));
+                if (!done) ++L.cg_unconverged;
+                break;
+            }
+        }
+    }
+    L.cg_total += std::min(k, cg_max);
+    hipLaunchKernelGGL(k_node_update, dim3(L.sgrid), dim3(256), 0, 0, L.d_x, L.d_Q, L.d_Wv, (int)n, L.d_score);
+    DESC_HIP(hipMemcpy(L.part.data(), L.d_score, sizeof(double) * L.sgrid, hipMemcpyDeviceToHost));
+    double score = 0.0; for (double v : L.part) score += v;
+    *score_out = score / (double)n;                                                     // Weighted_LAA.m:40
+    return DESC_OK;
+}
+
+void laa_weights(LaaSolver& L, const double* d_x, double thresh) {
+    if (L.m) hipLaunchKernelGGL(k_weights, dim3(L.egrid), dim3(256), 0, 0, d_x, L.d_w, L.m, thresh, 1e4, 1e-4);    // DESC.m:280-281, MPLS.m:211-212
+}
+
+int laa_quantile(LaaSolver& L, const double* d_x, double p, double* result) {
+    return device_quantile(d_x, L.m, p, L.d_mm, L.d_qh, L.d_cand, 1u << 20, result);
+}
+
+int laa_finish(LaaSolver& L, int iterations, double* R_out) {
+    if (L.cg_unconverged)
+        fprintf(stderr, "[desc_amd] warning: %d of %d Weighted_LAA solves stopped at the PCG iteration cap (relative residual up to %.3e)\n",
+                L.cg_unconverged, iterations, L.cg_worst);
+    hipLaunchKernelGGL(k_q2r, dim3(L.ngrid), dim3(256), 0, 0, L.d_Q, L.d_Rout, L.n);                // DESC.m:309-312, MPLS.m:251-254
+    DESC_HIP(hipDeviceSynchronize());
+    DESC_HIP(hipMemcpy(R_out, L.d_Rout, sizeof(double) * 9 * L.n, hipMemcpyDeviceToHost));
+    return DESC_OK;
+}
+
+}  // namespace desc
 
 extern "C" int desc_refine_run(const desc_problem* prob, const double* s_vec, const double* R_init, double stop_threshold,
                                int32_t max_iters, int32_t device, double* R_out, desc_refine_info* info) {
@@ -370,102 +458,40 @@ extern "C" int desc_refine_run_dev(const desc_device_problem* dp, const double* 
     auto t0 = std::chrono::steady_clock::now();
     if (stop_threshold <= 0) stop_threshold = 1e-3;      // DESC.m:272
     if (max_iters <= 0) max_iters = 100;
-    const double weight_max = 1e4, weight_min = 1e-4;    // DESC.m:280-281
 
     // initial weights (DESC.m:274-282): quantile(S_vec, 1) = max -> nothing is truncated yet; evaluated on
     // the device by the same kernel as the re-weighting steps
     double thresh0 = -INFINITY;
     for (int64_t e = 0; e < m; ++e) thresh0 = std::max(thresh0, s_vec[e]);
-    DevR D;
-    const int32_t *d_rowptr = dp->d_rowptr, *d_adj = dp->d_adj, *d_eid = dp->d_adj_eid, *d_ii = dp->d_ii, *d_jj = dp->d_jj;
-    const double* d_rij = dp->d_rij;
-    int8_t* d_sgn;
-    double *d_Rinit, *d_w, *d_S, *d_B, *d_RS, *d_rhs, *d_diag, *d_x, *d_r, *d_z, *d_p, *d_q, *d_Wv, *d_score, *d_Rout;
-    Quat *d_Q, *d_QQ; CgScal* d_sc;
-    const int sgrid = 64;
-    if ((rc = D.alloc(&d_sgn, 2 * m)) || (rc = D.alloc(&d_Rinit, 9 * n)) ||
-        (rc = D.alloc(&d_w, m)) || (rc = D.alloc(&d_S, m)) || (rc = D.alloc(&d_B, 3 * m)) || (rc = D.alloc(&d_RS, m)) ||
-        (rc = D.alloc(&d_rhs, 3 * n)) || (rc = D.alloc(&d_diag, n)) || (rc = D.alloc(&d_x, 3 * n)) || (rc = D.alloc(&d_r, 3 * n)) ||
-        (rc = D.alloc(&d_z, 3 * n)) || (rc = D.alloc(&d_p, 3 * n)) || (rc = D.alloc(&d_q, 3 * n)) || (rc = D.alloc(&d_Wv, 3 * n)) ||
-        (rc = D.alloc(&d_score, sgrid)) || (rc = D.alloc(&d_Rout, 9 * n)) || (rc = D.alloc(&d_Q, n)) || (rc = D.alloc(&d_QQ, m)) ||
-        (rc = D.alloc(&d_sc, 1))) return rc;
-    DESC_HIP(hipMemcpy(d_Rinit, R_init, sizeof(double) * 9 * n, hipMemcpyHostToDevice));
-    if (m) {
-        DESC_HIP(hipMemcpy(d_S, s_vec, sizeof(double) * m, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_incidence_sign, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (n * 16 + 255) / 256))), dim3(256), 0, 0,
-                           d_rowptr, d_adj, d_sgn, (int)n);
-    }
-    const int egrid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (m + 255) / 256));
-    if (m) hipLaunchKernelGGL(k_weights, dim3(egrid), dim3(256), 0, 0, d_S, d_w, m, thresh0, weight_max, weight_min);
-    const int ngrid = (int)std::max<int64_t>(1, std::min<int64_t>(512, (n + 255) / 256));
-    const int rgrid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n * 16 + 255) / 256));
-    hipLaunchKernelGGL(k_r2q, dim3(ngrid), dim3(256), 0, 0, d_Rinit, d_Q, n, 0);            // Q = R2Q(R_init)        (DESC.m:270)
-    if (m) hipLaunchKernelGGL(k_r2q, dim3(egrid), dim3(256), 0, 0, d_rij, d_QQ, m, 1);      // QQ = R2Q(permute(RijMat)) (:265,271)
+    LaaSolver L;
+    if ((rc = laa_setup(dp, R_init, L))) return rc;
+    double *d_S, *d_RS;
+    if ((rc = L.alloc(&d_S, m)) || (rc = L.alloc(&d_RS, m))) return rc;
+    if (m) DESC_HIP(hipMemcpy(d_S, s_vec, sizeof(double) * m, hipMemcpyHostToDevice));
+    laa_weights(L, d_S, thresh0);
 
     double score = INFINITY, quant_ratio = 1.0;
     const double quant_ratio_min = 0.8;
-    int Iteration = 1, cg_total = 0, cg_unconverged = 0;
-    double cg_worst = 0.0;
-    hvec<double> part(sgrid);
-    constexpr unsigned QCAP = 1u << 20;
-    double *d_mm, *d_cand; unsigned* d_qh;
-    if ((rc = D.alloc(&d_mm, 128)) || (rc = D.alloc(&d_cand, QCAP)) || (rc = D.alloc(&d_qh, QBINS + 1))) return rc;
-    CgScal hs;
+    int Iteration = 1;
     while (score > stop_threshold && Iteration < max_iters) {                               // DESC.m:287
         const double lam = 1.0 / (Iteration + 1);
-        // ---- Weighted_LAA
-        if (m) hipLaunchKernelGGL(k_edge_log, dim3(egrid), dim3(256), 0, 0, d_Q, d_QQ, d_ii, d_jj, d_B, m);
-        hipLaunchKernelGGL(k_rhs, dim3(rgrid), dim3(256), 0, 0, d_rowptr, d_eid, d_sgn, d_w, d_B, d_rhs, d_diag, (int)n);
-        hipLaunchKernelGGL(k_cg_init, dim3(ngrid), dim3(256), 0, 0, d_rhs, d_diag, d_x, d_r, d_z, d_p, (int)n);
-        hipLaunchKernelGGL(k_dot3, dim3(1), dim3(256), 0, 0, d_r, d_z, (int)n, &d_sc->rz[0]);
-        hipLaunchKernelGGL(k_dot3, dim3(1), dim3(256), 0, 0, d_r, d_r, (int)n, &d_sc->bnorm[0]);
-        const int cg_max = (int)std::min<int64_t>(20000, 20 * n + 200);
-        int k = 0;
-        for (k = 1; k <= cg_max; ++k) {
-            hipLaunchKernelGGL(k_lap, dim3(rgrid), dim3(256), 0, 0, d_rowptr, d_adj, d_eid, d_w, d_p, d_q, (int)n);
-            hipLaunchKernelGGL(k_dot3, dim3(1), dim3(256), 0, 0, d_p, d_q, (int)n, &d_sc->pq[0]);
-            hipLaunchKernelGGL(k_cg_update, dim3(ngrid), dim3(256), 0, 0, d_sc, d_diag, d_p, d_q, d_x, d_r, d_z, (int)n);
-            hipLaunchKernelGGL(k_dot3, dim3(1), dim3(256), 0, 0, d_r, d_z, (int)n, &d_sc->rz_new[0]);
-            hipLaunchKernelGGL(k_cg_dir, dim3(ngrid), dim3(256), 0, 0, d_sc, d_z, d_p, (int)n);
-            hipLaunchKernelGGL(k_cg_roll, dim3(1), dim3(64), 0, 0, d_sc);
-            if (k % 25 == 0 || k == cg_max) {                                               // convergence probe
-                hipLaunchKernelGGL(k_dot3, dim3(1), dim3(256), 0, 0, d_r, d_r, (int)n, &d_sc->rnorm[0]);
-                DESC_HIP(hipMemcpy(&hs, d_sc, sizeof hs, hipMemcpyDeviceToHost));
-                bool done = true;
-                for (int c = 0; c < 3; ++c) if (hs.rnorm[c] > 1e-26 * hs.bnorm[c] && hs.rnorm[c] > 1e-300) done = false;   // |r| <= 1e-13 |b|
-                if (done || k == cg_max) {
-                    for (int c = 0; c < 3; ++c) if (hs.bnorm[c] > 0) cg_worst = std::max(cg_worst, std::sqrt(hs.rnorm[c] / hs.bnorm[c]));
-                    if (!done) ++cg_unconverged;
-                    break;
-                }
-            }
-        }
-        cg_total += std::min(k, cg_max);
-        hipLaunchKernelGGL(k_node_update, dim3(sgrid), dim3(256), 0, 0, d_x, d_Q, d_Wv, (int)n, d_score);
-        DESC_HIP(hipMemcpy(part.data(), d_score, sizeof(double) * sgrid, hipMemcpyDeviceToHost));
-        score = 0.0; for (double v : part) score += v;
-        score /= (double)n;                                                                 // Weighted_LAA.m:40
+        if ((rc = laa_step(L, &score))) return rc;                                          // Weighted_LAA
         // ---- residuals and new weights (DESC.m:289-303)
         if (m) {
-            hipLaunchKernelGGL(k_rsvec, dim3(egrid), dim3(256), 0, 0, d_Wv, d_B, d_ii, d_jj, d_S, d_RS, m, lam);
+            hipLaunchKernelGGL(k_rsvec, dim3(L.egrid), dim3(256), 0, 0, L.d_Wv, L.d_B, dp->d_ii, dp->d_jj, d_S, d_RS, m, lam);
             quant_ratio = std::max(quant_ratio_min, quant_ratio - 0.05);
             double thresh = 0.0;                                                            // quantile(RSVec, quant_ratio)  (DESC.m:299)
-            if ((rc = device_quantile(d_RS, m, quant_ratio, d_mm, d_qh, d_cand, QCAP, &thresh))) return rc;
-            hipLaunchKernelGGL(k_weights, dim3(egrid), dim3(256), 0, 0, d_RS, d_w, m, thresh, weight_max, weight_min);
+            if ((rc = laa_quantile(L, d_RS, quant_ratio, &thresh))) return rc;
+            laa_weights(L, d_RS, thresh);
         }
         DESC_HIP(hipGetLastError());
         if (info && info->verbose) printf("Iter %d: ||\xce\x94R||= %f\n", Iteration, score);                 // DESC.m:305
         ++Iteration;
     }
-    if (cg_unconverged)
-        fprintf(stderr, "[desc_amd] warning: %d of %d Weighted_LAA solves stopped at the PCG iteration cap (relative residual up to %.3e)\n",
-                cg_unconverged, Iteration - 1, cg_worst);
-    hipLaunchKernelGGL(k_q2r, dim3(ngrid), dim3(256), 0, 0, d_Q, d_Rout, n);                // DESC.m:309-312
-    DESC_HIP(hipDeviceSynchronize());
-    DESC_HIP(hipMemcpy(R_out, d_Rout, sizeof(double) * 9 * n, hipMemcpyDeviceToHost));
+    if ((rc = laa_finish(L, Iteration - 1, R_out))) return rc;
     if (info) {
-        info->iters = Iteration - 1; info->score = score; info->cg_iters = cg_total;
-        info->cg_unconverged = cg_unconverged; info->cg_residual = cg_worst;
+        info->iters = Iteration - 1; info->score = score; info->cg_iters = L.cg_total;
+        info->cg_unconverged = L.cg_unconverged; info->cg_residual = L.cg_worst;
         info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     return DESC_OK;

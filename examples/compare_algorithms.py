@@ -3,10 +3,12 @@
 
 Same model (Uniform_Topology n, p, q, sigma, 'uniform'; the demo's defaults n = 100 ... BASELINE configs[0] uses n = 200), same
 parameter structs (:25-46), same calls in the same order, rotations aligned with Rotation_Alignment (:75-82) and tabulated (:85-99).
-Rows of the reference's table that belong to algorithms outside this library's scope (MPLS, CEMP+MST, IRLS-GM, IRLS-L0.5: SURVEY.md 2)
-are left out; CEMP+GCW is the composition CEMP() -> GCW() of the two entry points the library has.
+The default table has four rows: Spectral, CEMP+GCW (the composition CEMP() -> GCW()), DESC_init and DESC.  ``--full`` /
+``run(full=True)`` adds the demo's MPLS call (:59) with its MPLS_parameters (:32-36) -- the rows CEMP+MST and MPLS -- and takes
+CEMP+GCW from the reference's own CEMP_GCW() (weights 1/(SVec + 1e-8), CEMP_GCW.m:144): six rows.  The IRLS-GM and IRLS-L0.5 rows
+(third-party L1 / L_1/2 solvers) are left out.
 
-    python examples/compare_algorithms.py [--n 200] [--p 0.5] [--q 0.2] [--sigma 0.1] [--seed 0]
+    python examples/compare_algorithms.py [--n 200] [--p 0.5] [--q 0.2] [--sigma 0.1] [--seed 0] [--full]
 """
 import argparse
 import os
@@ -14,10 +16,12 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from desc_amd import CEMP, DESC, GCW, ConstantStepSize, Rotation_Alignment, Spectral, Uniform_Topology  # noqa: E402
+import numpy as np  # noqa: E402
+
+from desc_amd import CEMP, CEMP_GCW, DESC, GCW, MPLS, ConstantStepSize, Rotation_Alignment, Spectral, Uniform_Topology  # noqa: E402
 
 
-def run(n=200, p=0.5, q=0.2, sigma=0.1, seed=0, verbose=True):
+def run(n=200, p=0.5, q=0.2, sigma=0.1, seed=0, verbose=True, full=False):
     model_out = Uniform_Topology(n, p, q, sigma, "uniform", seed=seed)                  # :13
     Ind, RijMat, ErrVec, R_orig = model_out.Ind, model_out.RijMat, model_out.ErrVec, model_out.R_orig   # :20-23
     CEMP_parameters = dict(max_iter=6, reweighting=[2.0 ** k for k in range(6)], nsample=50, gcw_beta=5)   # :26-29
@@ -28,8 +32,15 @@ def run(n=200, p=0.5, q=0.2, sigma=0.1, seed=0, verbose=True):
     SVec = CEMP(Ind, RijMat, CEMP_parameters)                                            # :66 (CEMP_GCW.m = CEMP.m + GCW.m)
     R_CEMP_GCW = GCW(Ind, None, RijMat, SVec)
     R_DESC, R_DESC_init, S_vec = DESC(Ind, RijMat, DESC_parameters)                      # :72
+    table = [("Spectral", R_SP), ("CEMP+GCW", R_CEMP_GCW), ("DESC_init", R_DESC_init), ("DESC", R_DESC)]
+    if full:
+        MPLS_parameters = dict(stop_threshold=1e-3, max_iter=100, reweighting=CEMP_parameters["reweighting"][-1],      # :32-36
+                               thresholding=[0.95, 0.9, 0.85, 0.8], cycle_info_ratio=1.0 / (np.arange(1, 101) + 1))
+        R_MPLS, R_CEMP_MST = MPLS(Ind, RijMat, dict(CEMP_parameters, verbose=verbose), MPLS_parameters)               # :59
+        R_CEMP_GCW_ref = CEMP_GCW(Ind, RijMat, CEMP_parameters)                                                      # :66
+        table[1:2] = [("CEMP+MST", R_CEMP_MST), ("CEMP+GCW", R_CEMP_GCW_ref), ("MPLS", R_MPLS)]                      # the demo's six rows (:88-95)
     rows = []
-    for name, R in (("Spectral", R_SP), ("CEMP+GCW", R_CEMP_GCW), ("DESC_init", R_DESC_init), ("DESC", R_DESC)):
+    for name, R in table:
         _, _, mean_error, median_error = Rotation_Alignment(R, R_orig)                   # :75-82
         rows.append((name, float(mean_error), float(median_error)))
     return rows, dict(mean_abs_err_cemp=float(abs(SVec - ErrVec).mean()), mean_abs_err_desc=float(abs(S_vec - ErrVec).mean()))
@@ -40,12 +51,13 @@ def main():
     ap.add_argument("--n", type=int, default=200); ap.add_argument("--p", type=float, default=0.5)
     ap.add_argument("--q", type=float, default=0.2); ap.add_argument("--sigma", type=float, default=0.1)
     ap.add_argument("--seed", type=int, default=0); ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--full", action="store_true", help="add the CEMP+MST, MPLS and reference CEMP+GCW rows")
     a = ap.parse_args()
-    rows, extra = run(a.n, a.p, a.q, a.sigma, a.seed, verbose=not a.quiet)
+    rows, extra = run(a.n, a.p, a.q, a.sigma, a.seed, verbose=not a.quiet, full=a.full)
     print("\nResults =\n")                                                              # :85-99
-    print("    %-12s %-12s %-12s" % ("Algorithms", "MeanError", "MedianError"))
+    print("    %-16s %-12s %-12s" % ("Algorithms", "MeanError", "MedianError"))
     for name, me, md in rows:
-        print("    %-12s %-12.4f %-12.4f" % ('"' + name + '"', me, md))
+        print("    %-16s %-12.4f %-12.4f" % ('"' + name + '"', me, md))
     print("\n(degrees; corruption levels: mean |SVec - ErrVec| CEMP %.4f, DESC %.4f)" % (extra["mean_abs_err_cemp"], extra["mean_abs_err_desc"]))
 
 

@@ -339,6 +339,58 @@ int desc_refine_run(const desc_problem* prob, const double* s_vec, const double*
 int desc_refine_run_dev(const desc_device_problem* dp, const double* s_vec, const double* R_init, double stop_threshold,
                         int32_t max_iters, double* R_out, desc_refine_info* info);
 
+/* ------------------------------------------------------------- MPLS / CEMP+MST -- */
+/* R_est = MST step of Algorithms/MPLS.m:160-193: the minimum spanning tree of the graph with edge weights s_vec + 1 (:162 -- NOT
+ * Utils/MST.m, whose sparse() call drops the edges with s_vec == 0), rooted at node 1 with R_1 = I; a leaf reached through edge e
+ * gets R_e * R_root when it is e's smaller endpoint, R_e' * R_root otherwise (:178-193).  Edge order: the double fl(s_vec[e] + 1.0),
+ * ties broken by the edge index e (the (i, j)-sorted order), so the tree is unique; MATLAB's minspantree (:166-168) does not document
+ * its tie rule, and with distinct keys both trees coincide.  R_out: n*9 doubles; tree_edges (nullable): the n - 1 tree edges'
+ * indices, ascending.  A graph that is not connected -- two pieces, or a node id in 1..n that no edge touches -- is refused with
+ * DESC_ERR_INVALID and the number of components in desc_last_error() (the reference loops for ever there, :178). */
+int desc_mst_run(const desc_problem* prob, const double* s_vec, int32_t device, double* R_out, int32_t* tree_edges);
+int desc_mst_run_dev(const desc_device_problem* dp, const double* s_vec, double* R_out, int32_t* tree_edges);
+
+/* [R_est, R_init] = MPLS(Ind, RijMat, CEMP_parameters, MPLS_parameters) -- Algorithms/MPLS.m:31-257.  CEMP (:65-158, the text of
+ * CEMP.m:36-132, sampled as desc_cemp_run does) -> the MST initialisation above (:160-193) -> the MPLS loop (:196-249): Weighted_LAA
+ * (as desc_refine_run), residuals r = |A W(2:end,2:4) - B|/pi (:221-222), the cycle step h_ij = sum w .* S0Mat with
+ * w = exp(-beta_t (r_ik + r_jk)) normalised per edge over CEMP's own samples (:223-237), RH = (1 - alpha_t) r + alpha_t h (:240),
+ * weights min(1/RH^0.75, 1e4), 1e-4 where RH > quantile(RH, tau_t) (:241-245); initial weights min(1/SVec^0.75, 1e4) (:210-213);
+ * while score > stop_threshold && Iteration < max_iter (:218).  beta / tau / alpha are indexed by Iteration and padded with their
+ * last entry (:47-63), as is cemp_beta (:37-42).  As in the reference, an edge without a 3-cycle is not reset in the loop (:239 is
+ * commented out): its cycle product is the zero matrix, so its S0 is |acos(-1/2)|/pi = 2/3, its weights 1/nsample, its h 2/3.
+ * CEMP's samples and S0Mat stay resident for the whole loop (m_pos * nsample doubles; m_pos * nsample must stay below 2^31, else
+ * DESC_ERR_TOO_LARGE).  R_est, R_init (nullable): n*9 doubles; s_vec_out (nullable): CEMP's SVec, m doubles. */
+typedef struct desc_mpls_params {
+    const double* cemp_beta;  /* CEMP_parameters.reweighting                         MPLS.m:35 */
+    int32_t n_cemp_beta;
+    int32_t cemp_max_iter;    /* CEMP_parameters.max_iter                            MPLS.m:34 */
+    int32_t nsample;          /* CEMP_parameters.nsample                             MPLS.m:36 */
+    int32_t verbose;          /* print the reference's disp / fprintf lines                    */
+    uint64_t seed;            /* cycle-sampling key (MATLAB: global RNG, MPLS.m:93)            */
+    double stop_threshold;    /* MPLS_parameters.stop_threshold                      MPLS.m:45 */
+    int32_t max_iter;         /* MPLS_parameters.max_iter                            MPLS.m:46 */
+    int32_t n_beta;
+    const double* beta;       /* MPLS_parameters.reweighting                         MPLS.m:47 */
+    const double* tau;        /* MPLS_parameters.thresholding                        MPLS.m:53 */
+    const double* alpha;      /* MPLS_parameters.cycle_info_ratio                    MPLS.m:59 */
+    int32_t n_tau;
+    int32_t n_alpha;
+} desc_mpls_params;
+typedef struct desc_mpls_info {
+    int32_t iters;            /* MPLS iterations executed (Iteration - 1)                      */
+    int32_t cg_iters;         /* conjugate-gradient steps in total                             */
+    int32_t cg_unconverged;   /* Weighted_LAA solves that stopped at the PCG iteration cap     */
+    int32_t reserved;
+    int64_t m_pos;            /* edges with a 3-cycle                                          */
+    double  score;            /* last mean rotation update (Weighted_LAA.m:40)                 */
+    double  cg_residual;      /* largest relative residual |r|/|b| left by any solve           */
+    double  ms_cemp, ms_mst, ms_loop, ms_total;
+} desc_mpls_info;
+int desc_mpls_run(const desc_problem* prob, const desc_mpls_params* params, int32_t device, double* R_est, double* R_init,
+                  double* s_vec_out, desc_mpls_info* info);
+int desc_mpls_run_dev(const desc_device_problem* dp, const desc_mpls_params* params, double* R_est, double* R_init,
+                      double* s_vec_out, desc_mpls_info* info);
+
 /* One-shot: what the MEX shim calls.  Builds the structure (p->build_where),
  * uploads, runs, downloads, frees. */
 int desc_pgd_solve(const desc_problem* prob, const desc_params* p, desc_result* r);

@@ -6,6 +6,9 @@
  *   R     = desc_amd_mex('refine',   Ind0, RijMat, S_vec, R_init)        desc_refine_run, DESC.m:265-313
  *   [R_est, R_init, S_vec, info] = desc_amd_mex('desc', Ind0, RijMat, opt)   the whole DESC.m:16-313 on ONE device-resident
  *                                                      problem (desc_problem_upload): PGD -> GCW -> refinement
+ *   [R_est, R_init] = desc_amd_mex('mpls', Ind0, RijMat, cemp_beta, cemp_max_iter, nsample, seed,
+ *                                  stop_threshold, max_iter, beta, tau, alpha)      desc_mpls_run, MPLS.m:31-257
+ *   R     = desc_amd_mex('cemp_gcw', Ind0, RijMat, beta, max_iter, nsample, seed)   CEMP_GCW.m: CEMP, weights 1/(SVec + 1e-8), spectral
  *
  * Ind0: m x 2 int32, 0-based, sorted by (i,j); RijMat: 3 x 3 x m double (passed through);
  * R: 3 x 3 x n double.  Cannot be compiled in the build container (no mex.h):
@@ -51,7 +54,7 @@ static int at_exit_registered = 0;
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (!at_exit_registered) { mexAtExit(release_parked_blocks); at_exit_registered = 1; }
     char cmd[32];
-    if (nrhs < 3 || mxGetString(prhs[0], cmd, sizeof cmd)) mexErrMsgIdAndTxt("desc_amd:cmd", "first argument: 'spectral' | 'gcw' | 'cemp' | 'refine' | 'desc'");
+    if (nrhs < 3 || mxGetString(prhs[0], cmd, sizeof cmd)) mexErrMsgIdAndTxt("desc_amd:cmd", "first argument: 'spectral' | 'gcw' | 'cemp' | 'refine' | 'desc' | 'mpls' | 'cemp_gcw'");
     desc_problem prob;
     problem_from(prhs[1], prhs[2], &prob);
     int rc = DESC_OK;
@@ -71,6 +74,35 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         plhs[0] = mxCreateDoubleMatrix(1, prob.m, mxREAL);
         rc = desc_cemp_run(&prob, mxGetPr(prhs[3]), (int32_t)mxGetNumberOfElements(prhs[3]), (int32_t)mxGetScalar(prhs[4]),
                            (int32_t)mxGetScalar(prhs[5]), nrhs > 6 ? (uint64_t)mxGetScalar(prhs[6]) : 0, 0, mxGetPr(plhs[0]), NULL);
+    } else if (!strcmp(cmd, "mpls")) {
+        if (nrhs < 12) mexErrMsgIdAndTxt("desc_amd:mpls", "usage: ('mpls', Ind0, RijMat, cemp_beta, cemp_max_iter, nsample, seed, stop_threshold, max_iter, beta, tau, alpha)");
+        desc_mpls_params mp; memset(&mp, 0, sizeof mp);
+        mp.cemp_beta = mxGetPr(prhs[3]); mp.n_cemp_beta = (int32_t)mxGetNumberOfElements(prhs[3]);              /* MPLS.m:34-42 */
+        mp.cemp_max_iter = (int32_t)mxGetScalar(prhs[4]); mp.nsample = (int32_t)mxGetScalar(prhs[5]); mp.seed = (uint64_t)mxGetScalar(prhs[6]);
+        mp.stop_threshold = mxGetScalar(prhs[7]); mp.max_iter = (int32_t)mxGetScalar(prhs[8]);                   /* :45-63 */
+        mp.beta = mxGetPr(prhs[9]); mp.n_beta = (int32_t)mxGetNumberOfElements(prhs[9]);
+        mp.tau = mxGetPr(prhs[10]); mp.n_tau = (int32_t)mxGetNumberOfElements(prhs[10]);
+        mp.alpha = mxGetPr(prhs[11]); mp.n_alpha = (int32_t)mxGetNumberOfElements(prhs[11]);
+        mp.verbose = 1;
+        plhs[0] = rotations(prob.n);
+        mxArray* R_init = rotations(prob.n);
+        rc = desc_mpls_run(&prob, &mp, 0, mxGetPr(plhs[0]), mxGetPr(R_init), NULL, NULL);
+        if (nlhs > 1) plhs[1] = R_init;
+    } else if (!strcmp(cmd, "cemp_gcw")) {
+        if (nrhs < 7) mexErrMsgIdAndTxt("desc_amd:cemp_gcw", "usage: ('cemp_gcw', Ind0, RijMat, beta, max_iter, nsample, seed)");
+        mxArray* S = mxCreateDoubleMatrix(1, prob.m, mxREAL);
+        plhs[0] = rotations(prob.n);
+        desc_device_problem* dp = NULL;
+        rc = desc_problem_upload(&prob, 0, &dp);
+        if (rc == DESC_OK)
+            rc = desc_cemp_run_dev(dp, mxGetPr(prhs[3]), (int32_t)mxGetNumberOfElements(prhs[3]), (int32_t)mxGetScalar(prhs[4]),
+                                   (int32_t)mxGetScalar(prhs[5]), (uint64_t)mxGetScalar(prhs[6]), mxGetPr(S), NULL);
+        if (rc == DESC_OK) {
+            double* w = mxGetPr(S);
+            for (int64_t e = 0; e < prob.m; ++e) w[e] = 1.0 / (w[e] + 1e-8);                                  /* CEMP_GCW.m:144 */
+            rc = desc_spectral_run_dev(dp, w, 1, 0.0, 0, mxGetPr(plhs[0]), NULL);                               /* :145-160 */
+        }
+        if (dp) desc_problem_free(dp);
     } else if (!strcmp(cmd, "refine")) {
         if (nrhs < 5 || mxGetNumberOfElements(prhs[3]) != (mwSize)prob.m || mxGetNumberOfElements(prhs[4]) != (mwSize)(9 * prob.n))
             mexErrMsgIdAndTxt("desc_amd:refine", "usage: ('refine', Ind0, RijMat, S_vec (m), R_init (3x3xn))");
