@@ -31,6 +31,7 @@ EXPORTS = [
     "desc_pgd_shard_finish", "desc_pgd_shard_objective", "desc_pgd_shard_set_collectives", "desc_pgd_shard_start",
     "desc_pgd_shard_iterate", "desc_pgd_shard_run", "desc_pgd_stopped", "desc_device_synchronize", "desc_memcpy_d2h", "desc_memcpy_h2d", "desc_debug_band_plan", "desc_debug_spmm_variants", "desc_debug_wg_clock", "desc_debug_wg_plan", "desc_debug_last_sweep", "desc_debug_shard_layout", "desc_trim_memory", "desc_spectral_run", "desc_cemp_run", "desc_refine_run",
     "desc_marshal_edges", "desc_marshal_rij", "desc_mst_run", "desc_mst_run_dev", "desc_mpls_run", "desc_mpls_run_dev",
+    "desc_irls_run", "desc_irls_run_dev",
 ]
 
 I32P = C.POINTER(C.c_int32)
@@ -110,6 +111,20 @@ class MplsInfo(C.Structure):
                 ("ms_total", C.c_double)]
 
 
+class IrlsParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("max_iter_l1", C.c_int32), ("max_iter_irls", C.c_int32), ("verbose", C.c_int32), ("sigma_deg", C.c_double),
+                ("R_init", F64P), ("order", I32P)]
+
+
+class IrlsInfo(C.Structure):
+    _fields_ = [("comp_nodes", C.c_int64), ("comp_edges", C.c_int64), ("l1_iters", C.c_int32), ("irls_iters", C.c_int32),
+                ("l1_score", C.c_double), ("irls_score", C.c_double), ("pd_steps", C.c_int32), ("pd_ill", C.c_int32), ("pd_stuck", C.c_int32),
+                ("warned_edges", C.c_int32), ("cg_iters_l1", C.c_int32), ("cg_iters_irls", C.c_int32), ("cg_unconverged", C.c_int32),
+                ("pd_solves", C.c_int32), ("cg_residual", C.c_double), ("ms_project", C.c_double), ("ms_components", C.c_double),
+                ("ms_tree", C.c_double), ("ms_l1", C.c_double), ("ms_l1_pcg", C.c_double), ("ms_irls", C.c_double), ("ms_total", C.c_double)]
+
+
+IRLS_GM, IRLS_L12 = 0, 1
 ERR_INVALID, ERR_HIP, ERR_TOO_LARGE, ERR_STATE = -1, -2, -3, -4
 
 
@@ -214,6 +229,8 @@ def load():
     L.desc_mst_run_dev.argtypes = [C.c_void_p, F64P, F64P, I32P]
     L.desc_mpls_run.argtypes = [C.POINTER(Problem), C.POINTER(MplsParams), C.c_int32, F64P, F64P, F64P, C.POINTER(MplsInfo)]
     L.desc_mpls_run_dev.argtypes = [C.c_void_p, C.POINTER(MplsParams), F64P, F64P, F64P, C.POINTER(MplsInfo)]
+    L.desc_irls_run.argtypes = [C.POINTER(Problem), C.POINTER(IrlsParams), C.c_int32, F64P, F64P, C.POINTER(IrlsInfo)]
+    L.desc_irls_run_dev.argtypes = [C.c_void_p, C.POINTER(IrlsParams), F64P, F64P, C.POINTER(IrlsInfo)]
     _lib = L
     return L
 
@@ -676,6 +693,28 @@ def mpls_run(prob, cemp_beta, cemp_max_iter, nsample, stop_threshold, max_iter, 
     return shape(R_est), shape(R_init), S[:m], dict(iters=info.iters, cg_iters=info.cg_iters, cg_unconverged=info.cg_unconverged, m_pos=info.m_pos,
                                                     score=info.score, cg_residual=info.cg_residual, ms_cemp=info.ms_cemp, ms_mst=info.ms_mst,
                                                     ms_loop=info.ms_loop, ms_total=info.ms_total)
+
+
+def irls_run(prob, mode, max_iter_l1=10, max_iter_irls=100, sigma_deg=5.0, R_init=None, order=None, device=0, verbose=False):
+    """desc_irls_run[_dev] -> (R (3,3,n), R_l1 (3,3,n), info dict); sorted edge order, NaN outside the largest component.
+    order: the caller's 0-based row of every sorted edge (marshal_edges' perm), or None."""
+    n, m = prob.n, prob.m
+    Ri = None if R_init is None else np.ascontiguousarray(np.asarray(R_init, dtype=np.float64).reshape(-1, order="F"))
+    if Ri is not None and Ri.size != 9 * n:
+        raise ValueError("Rinit must be 3 x 3 x n")
+    od = None if order is None else np.ascontiguousarray(order, dtype=np.int32)
+    if od is not None and od.size != m:
+        raise ValueError("order must have m entries")
+    p = IrlsParams(int(mode), int(max_iter_l1), int(max_iter_irls), 1 if verbose else 0, float(sigma_deg), ptr(Ri, F64P), ptr(od, I32P))
+    R, R1 = out_buffer(9 * n), out_buffer(9 * n)
+    info = IrlsInfo()
+    L = load()
+    if isinstance(prob, DeviceProblem):
+        check(L.desc_irls_run_dev(prob.handle, C.byref(p), ptr(R, F64P), ptr(R1, F64P), C.byref(info)))
+    else:
+        check(L.desc_irls_run(C.byref(prob.c), C.byref(p), device, ptr(R, F64P), ptr(R1, F64P), C.byref(info)))
+    shape = lambda a: a[:9 * n].reshape((3, 3, n), order="F")      # noqa: E731
+    return shape(R), shape(R1), {k: getattr(info, k) for k, _ in IrlsInfo._fields_}
 
 
 def spmm_variants(dprob: DeviceProblem, reps=20):

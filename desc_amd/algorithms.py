@@ -401,6 +401,47 @@ def CEMP_GCW(Ind, RijMat, CEMP_parameters, return_info=False):
     return (R, dict(info, ms_cemp=ms)) if return_info else R
 
 
+def _irls(mode, RijMat, Ind, Rinit, SIGMA, MaxIterations, device, verbose, return_info):
+    R = np.asarray(RijMat)
+    if R.ndim == 2 and R.shape[0] == 4:
+        raise ValueError("the quaternion form of RR (4 x m) is not supported: pass RijMat as 3 x 3 x m rotation matrices")
+    mi = np.atleast_1d(np.asarray(MaxIterations, dtype=np.float64)).reshape(-1)
+    if mi.size != 2:
+        raise ValueError("MaxIterations must have two entries [L1, IRLS]")
+    sigma = 5.0 if SIGMA is None or np.size(SIGMA) == 0 else float(SIGMA)
+    n, ii, jj, rij, perm = marshal_edges(Ind, R)
+    if ii.shape[0] == 0:
+        raise ValueError("empty edge list")
+    if Rinit is not None and (np.ndim(Rinit) != 3 or np.shape(Rinit)[:2] != (3, 3) or np.shape(Rinit)[2] != n):
+        raise ValueError("Rinit must be 3 x 3 x max(Ind(:))")
+    prob = _lib.ProblemArrays(n, ii, jj, rij)
+    if verbose:
+        import sys
+        sys.stdout.flush()
+    Rout, R_l1, info = _lib.irls_run(prob, mode, int(mi[0]), int(mi[1]), sigma, R_init=Rinit, order=perm, device=device, verbose=verbose)
+    if return_info:
+        info["R_l1"] = R_l1
+        return Rout, info
+    return Rout
+
+
+def IRLS_GM(RijMat, Ind, Rinit=None, SIGMA=5, MaxIterations=(10, 100), device=0, verbose=False, return_info=False):
+    """R = IRLS_GM(RijMat, Ind, 'Rinit', Rinit, 'SIGMA', SIGMA, 'MaxIterations', [L1, IRLS]) -- Algorithms/IRLS_GM.m.  Note the
+    reference's argument order: RijMat first.  The largest connected component of the graph is solved (others get NaN): L1
+    initialisation by BoxMedianSO3Graph (spanning-tree start over the rows of Ind in the caller's order, three l1decode_pd solves
+    per iteration), then RobustMeanSO3Graph's Geman-McClure reweighted averaging with SIGMA in degrees.  An edge rotation with
+    det <= 0, or with all three singular values off 1 by >= 0.1, raises DescError naming the 1-based row.  ``verbose`` prints the
+    reference's progress lines.  With ``return_info`` also a dict: component size, iteration counts and scores, primal-dual step and
+    early-return counts, PCG totals, per-stage milliseconds and ``R_l1``, the L1 stage's estimate."""
+    return _irls(_lib.IRLS_GM, RijMat, Ind, Rinit, SIGMA, MaxIterations, device, verbose, return_info)
+
+
+def IRLS_L12(RijMat, Ind, Rinit=None, SIGMA=5, MaxIterations=(10, 100), device=0, verbose=False, return_info=False):
+    """R = IRLS_L12(RijMat, Ind, ...) -- Algorithms/IRLS_L12.m: as IRLS_GM, with Utils/L12.m's weights min(|E|^-0.75, 1e4) in the
+    reweighted stage (SIGMA is accepted and unused, as in the reference)."""
+    return _irls(_lib.IRLS_L12, RijMat, Ind, Rinit, SIGMA, MaxIterations, device, verbose, return_info)
+
+
 def DESC(Ind, RijMat, params, return_info=False):
     """[R_est, R_init, S_vec] = DESC(Ind, RijMat, params) -- Algorithms/DESC.m:14 (the call of
     Demo/compare_algorithms.m:72): DESC_PGD (:16-261) -> GCW initialisation (:263) -> reweighted

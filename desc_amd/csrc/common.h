@@ -116,6 +116,9 @@ int build_cemp_samples_host(const desc_problem* prob, int32_t nsample, uint64_t 
 // MPLS.m:160-193 (mst.hip): minimum spanning tree of the graph weighted by d_s + 1 (d_s: m doubles on the problem's device) and the
 // rotations propagated from node 1 along it into R_out (n*9 host doubles); tree_edges (nullable): the n - 1 edge ids, ascending
 int mst_device(const desc_device_problem* dp, const double* d_s, double* R_out, int32_t* tree_edges);
+// connected components (mst.hip: mst_device's Boruvka rounds with all keys equal): comp_out (n host ints) gets one label per node,
+// equal labels = one component; *count = the number of components
+int components_device(const desc_device_problem* dp, int32_t* comp_out, int64_t* count);
 // Worker threads of the host-side passes.  An exception that escapes a thread body (bad_alloc in a vector, system_error from the
 // thread constructor) would call std::terminate and take the MATLAB / Python host down: every body runs behind a catch, the
 // calling thread takes share 0 itself, all workers are joined, and the first exception is rethrown on the calling thread -- where

@@ -1,0 +1,853 @@
+// IRLS_GM / IRLS_L12 (Algorithms/IRLS_GM.m, IRLS_L12.m; Chatterjee & Govindu, "Efficient and robust large-scale rotation averaging").
+//   :52-53    RR = permute(RijMat, [2,1,3]), I = Ind'
+//   :65-67    largest connected component (components_device, mst.hip); sub-problem uploaded only when the graph is not connected
+//   :82-93    per-edge checks and projection RR = U round(S) V' (k_irls_project: 3x3 one-sided Jacobi SVD)
+//   :94-96    BoxMedianSO3Graph (Utils/BoxMedianSO3Graph.m): spanning-tree start (:79-114, host pass in the caller's row order),
+//             L1 loop (:138-187) with three l1decode_pd solves per iteration (:245-360), batched here: all state in HBM as m x 3
+//             edge and n x 3 node arrays, one Jacobi-PCG for the three Newton systems A' diag(sigx_c) A dx_c = w1p_c
+//   :96       RobustMeanSO3Graph (GM) or L12 (L 1/2): Weighted_LAA steps (refine.hip, laa.h), then residual-and-weight kernel
+// Deviations from the reference, by necessity:
+//   * graphconncomp's component numbering cannot be checked here: a tie of maximal sizes goes to the component holding the smallest
+//     node id (assumed to be graphconncomp's first); with distinct sizes nothing depends on it.
+//   * linsolve's LU and its rcond (hcond < 1e-14 -> "Matrix ill-conditioned") are a CG: the ill-conditioned return is taken on a CG
+//     breakdown (a non-finite p'Hp or r'z, or p'Hp <= 0 while r'z > 0).  A solve stopping at the iteration cap is counted in
+//     cg_unconverged and warned about.  A coordinate whose right-hand side is all zero makes the reference divide by zero (u = 0)
+//     and return its start 0 after "Stuck backtracking"; here the NaNs end it one way or the other, also with 0.
+//   * The primal-dual step scalars (tau, sdg, resnorm, step length) are formed on the host from fixed-order device partials, one
+//     read-back per backtracking trial; the CG keeps its scalars on the device and is probed every PD_PROBE = 5 steps.
+// Reductions are fixed-order partials (no float atomics): results are bitwise reproducible from run to run.
+#include <algorithm>
+#include <chrono>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "device_utils.h"
+#include "laa.h"
+
+namespace desc {
+namespace {
+
+constexpr int RG = 256;            // blocks of the partial-reduction kernels: partials are [RG][K], summed on the host in block order
+// The Newton-system CG is probed every PD_PROBE steps (one dot and one read-back): the reported step count is the solve's true count
+// rounded up to a multiple of PD_PROBE.  At C4 a CG step costs ~0.1 ms and a probe a few microseconds.
+constexpr int PD_PROBE = 5;
+
+double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
+
+// ---- stage 3: per-edge checks and projection ---------------------------------------------------------------------------------------
+// one-sided Jacobi SVD of a 3x3 column-major matrix: A V = U S; a[] ends as U S (columns), v[] as V; s sorted descending
+__device__ void svd3(double a[9], double v[9], double s[3]) {
+    for (int k = 0; k < 9; ++k) v[k] = (k % 4 == 0) ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 40; ++sweep) {
+        bool rotated = false;
+        for (int pr = 0; pr < 3; ++pr) {
+            const int p = pr == 2 ? 1 : 0, q = pr == 0 ? 1 : 2;
+            double al = 0, be = 0, ga = 0;
+            for (int r = 0; r < 3; ++r) { al += a[3 * p + r] * a[3 * p + r]; be += a[3 * q + r] * a[3 * q + r]; ga += a[3 * p + r] * a[3 * q + r]; }
+            if (!(fabs(ga) > 1e-300 && fabs(ga) > 1e-17 * sqrt(al * be))) continue;
+            rotated = true;
+            const double zeta = (be - al) / (2.0 * ga);
+            const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+            const double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
+            for (int r = 0; r < 3; ++r) {
+                const double ap = a[3 * p + r], aq = a[3 * q + r];
+                a[3 * p + r] = c * ap - sn * aq; a[3 * q + r] = sn * ap + c * aq;
+                const double vp = v[3 * p + r], vq = v[3 * q + r];
+                v[3 * p + r] = c * vp - sn * vq; v[3 * q + r] = sn * vp + c * vq;
+            }
+        }
+        if (!rotated) break;
+    }
+    for (int k = 0; k < 3; ++k) s[k] = sqrt(a[3 * k] * a[3 * k] + a[3 * k + 1] * a[3 * k + 1] + a[3 * k + 2] * a[3 * k + 2]);
+    for (int i = 0; i < 2; ++i)                                               // descending, as MATLAB's svd
+        for (int k = 0; k < 2 - i; ++k)
+            if (s[k] < s[k + 1]) {
+                double t = s[k]; s[k] = s[k + 1]; s[k + 1] = t;
+                for (int r = 0; r < 3; ++r) {
+                    t = a[3 * k + r]; a[3 * k + r] = a[3 * k + 3 + r]; a[3 * k + 3 + r] = t;
+                    t = v[3 * k + r]; v[3 * k + r] = v[3 * k + 3 + r]; v[3 * k + 3 + r] = t;
+                }
+            }
+}
+
+// IRLS_GM.m:82-93 for every edge: P = U round(S) V' of RR = Rij' (column-major, RR orientation).  status: 3 det <= 0, 2 all three
+// |s - 1| >= 0.1, 1 all three >= 0.01 (warning), 0 fine.  The smallest failing caller row goes to *bad_row (integer atomicMin),
+// warnings are counted.  only >= 0: that edge alone, its status / det / s into info[5].
+__global__ __launch_bounds__(256) void k_irls_project(const double* rij, const int32_t* order, int64_t m, double* P, int32_t* bad_row,
+                                                      int32_t* warn, int64_t only, double* info) {
+    const int64_t lo = only >= 0 ? only : 0, hi = only >= 0 ? only + 1 : m;
+    for (int64_t e = lo + (int64_t)blockIdx.x * 256 + threadIdx.x; e < hi; e += (int64_t)gridDim.x * 256) {
+        double a[9], v[9], s[3];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) a[r + 3 * c] = rij[9 * e + c + 3 * r];          // RR(r, c) = Rij(c, r)
+        const double det = a[0] * (a[4] * a[8] - a[7] * a[5]) - a[3] * (a[1] * a[8] - a[7] * a[2]) + a[6] * (a[1] * a[5] - a[4] * a[2]);
+        svd3(a, v, s);
+        bool all10 = true, all01 = true;
+        for (int k = 0; k < 3; ++k) { const double d = fabs(s[k] - 1.0); all10 = all10 && d >= 0.1; all01 = all01 && d >= 0.01; }
+        const int status = det <= 0.0 ? 3 : (all10 ? 2 : (all01 ? 1 : 0));
+        if (only >= 0) {
+            info[0] = status; info[1] = det; info[2] = s[0]; info[3] = s[1]; info[4] = s[2];
+            continue;
+        }
+        const int32_t row = order ? order[e] : (int32_t)e;
+        if (status >= 2) atomicMin(bad_row, row);
+        else if (status == 1) atomicAdd(warn, 1);
+        double out[9];
+        for (int k = 0; k < 9; ++k) out[k] = 0.0;
+        for (int k = 0; k < 3; ++k) {                                                  // U * round(S) * V'
+            if (!(s[k] > 0.0)) continue;
+            const double rs = round(s[k]);
+            for (int r = 0; r < 3; ++r) {
+                const double ur = (a[3 * k + r] / s[k]) * rs;
+                for (int c = 0; c < 3; ++c) out[r + 3 * c] += ur * v[3 * k + c];
+            }
+        }
+        for (int k = 0; k < 9; ++k) P[9 * e + k] = out[k];
+    }
+}
+
+// ---- stage 4: l1decode_pd, three coordinates batched ---------------------------------------------------------------------------------
+struct Pd3 { double tau[3], s[3], ymax[3]; int act[3]; };      // per-coordinate scalars of one launch (act: 1 = this coordinate takes part)
+
+// block reduction of K values per thread into out[K] (fixed tree order); OP: 0 sum, 1 min, 2 max (fmin / fmax skip NaN, as MATLAB)
+template <int K, int OP>
+__device__ __forceinline__ void block_reduce_store(double (&v)[K], double* out) {
+    __shared__ double sh[K][256];
+    for (int k = 0; k < K; ++k) sh[k][threadIdx.x] = v[k];
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st)
+            for (int k = 0; k < K; ++k) {
+                const double a = sh[k][threadIdx.x], b = sh[k][threadIdx.x + st];
+                sh[k][threadIdx.x] = OP == 1 ? fmin(a, b) : (OP == 2 ? fmax(a, b) : a + b);
+            }
+        __syncthreads();
+    }
+    if ((int)threadIdx.x < K) out[threadIdx.x] = sh[threadIdx.x][0];
+}
+
+// max |y - Ax| with Ax = 0 (:271): MATLAB's max, per coordinate
+__global__ __launch_bounds__(256) void k_pd_absmax(const double* y, int64_t m, double* part) {
+    double v[3] = {0, 0, 0};
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256)
+        for (int c = 0; c < 3; ++c) v[c] = fmax(v[c], fabs(y[3 * e + c]));
+    __shared__ double sh[3][256];
+    for (int c = 0; c < 3; ++c) sh[c][threadIdx.x] = v[c];
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) { if ((int)threadIdx.x < st) for (int c = 0; c < 3; ++c) sh[c][threadIdx.x] = fmax(sh[c][threadIdx.x], sh[c][threadIdx.x + st]); __syncthreads(); }
+    if (threadIdx.x < 3) part[3 * blockIdx.x + threadIdx.x] = sh[threadIdx.x][0];
+}
+// :268-276 with x0 = 0: Ax = 0, u, fu1, fu2, lamu1, lamu2; ev = lamu1 - lamu2 (for Atv, :278)
+__global__ __launch_bounds__(256) void k_pd_init(const double* y, int64_t m, Pd3 a, double* Ax, double* u, double* f1, double* f2, double* l1,
+                                                 double* l2, double* ev) {
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256)
+        for (int c = 0; c < 3; ++c) {
+            const int64_t k = 3 * e + c;
+            const double ax = 0.0, yy = y[k];
+            const double uu = 0.95 * fabs(yy - ax) + 0.10 * a.ymax[c];
+            const double g1 = (ax - yy) - uu, g2 = (-ax + yy) - uu;
+            const double m1 = -1.0 / g1, m2 = -1.0 / g2;
+            Ax[k] = ax; u[k] = uu; f1[k] = g1; f2[k] = g2; l1[k] = m1; l2[k] = m2; ev[k] = m1 - m2;
+        }
+}
+// A' v over the CSR rows (16 lanes per row, as k_rhs): MODE 0 out = A' ev1; MODE 1 out = coef .* (A' ev1) - A' ev2 (w1p, :303-304);
+// MODE 2 out = sum of ev1 over the row (the Jacobi diagonal of A' diag(ev1) A).  Row 0 (node 1, grounded) is 0.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_pd_gather(const int32_t* rowptr, const int32_t* eid, const int8_t* sgn, const double* ev1,
+                                                   const double* ev2, Pd3 a, double* out, int n) {
+    const int l16 = threadIdx.x & 15;
+    const int row0 = (blockIdx.x * 256 + threadIdx.x) >> 4, nrows = (gridDim.x * 256) >> 4;
+    for (int vb = row0 - (row0 % 4); vb < n; vb += nrows) {
+        const int v = vb + (row0 % 4);
+        double g[3] = {0, 0, 0}, h[3] = {0, 0, 0};
+        if (v < n && v > 0)
+            for (int t = rowptr[v] + l16; t < rowptr[v + 1]; t += 16) {
+                const int64_t e = eid[t];
+                const double sg = MODE == 2 ? 1.0 : (double)sgn[t];
+                for (int c = 0; c < 3; ++c) {
+                    g[c] += sg * ev1[3 * e + c];
+                    if (MODE == 1) h[c] += sg * ev2[3 * e + c];
+                }
+            }
+        for (int c = 0; c < 3; ++c) { g[c] = group16_sum(g[c]); if (MODE == 1) h[c] = group16_sum(h[c]); }
+        if (v < n && l16 == 0)
+            for (int c = 0; c < 3; ++c) out[3 * v + c] = MODE == 1 ? a.tau[c] * g[c] - h[c] : g[c];
+    }
+}
+// :296-304 per edge: w2, sig1, sig2, sigx; ev1 = -1./fu1 + 1./fu2 (w1), ev2 = (sig2./sig1).*w2 (w1p).  Coordinates not taking part get
+// sigx = 1 and zero right-hand sides: their CG ends at once.
+__global__ __launch_bounds__(256) void k_pd_pre(int64_t m, Pd3 a, const double* f1, const double* f2, const double* l1, const double* l2,
+                                                double* w2, double* s1, double* s2, double* sx, double* ev1, double* ev2) {
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256)
+        for (int c = 0; c < 3; ++c) {
+            const int64_t k = 3 * e + c;
+            if (!a.act[c]) { sx[k] = 1.0; ev1[k] = 0.0; ev2[k] = 0.0; continue; }
+            const double g1 = f1[k], g2 = f2[k], m1 = l1[k], m2 = l2[k], it = 1.0 / a.tau[c];
+            const double ww = -1.0 - it * (1.0 / g1 + 1.0 / g2);                     // :296
+            const double a1 = -m1 / g1 - m2 / g2;                                    // :298
+            const double a2 = m1 / g1 - m2 / g2;                                     // :299
+            const double ax = a1 - a2 * a2 / a1;                                     // :300
+            w2[k] = ww; s1[k] = a1; s2[k] = a2; sx[k] = ax;
+            ev1[k] = -1.0 / g1 + 1.0 / g2;                                           // :303
+            ev2[k] = (a2 / a1) * ww;                                                 // :304
+        }
+}
+// :315-324: Adx, du, dlamu1, dlamu2; ev = dlamu1 - dlamu2 (Atdv); the two step-length minima (:327-330; MATLAB's min skips NaN, so
+// does fmin) as block partials [RG][6]: lamu bound per coordinate, then fu bound per coordinate
+__global__ __launch_bounds__(256) void k_pd_dir(const int32_t* ii, const int32_t* jj, int64_t m, Pd3 a, const double* dx, const double* f1,
+                                                const double* f2, const double* l1, const double* l2, const double* w2, const double* s1,
+                                                const double* s2, double* Adx, double* du, double* d1, double* d2, double* ev, double* part) {
+    double mn[6] = {INFINITY, INFINITY, INFINITY, INFINITY, INFINITY, INFINITY};
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256) {
+        const int i = ii[e], j = jj[e];
+        for (int c = 0; c < 3; ++c) {
+            const int64_t k = 3 * e + c;
+            if (!a.act[c]) { ev[k] = 0.0; continue; }
+            const double adx = (j > 0 ? dx[3 * j + c] : 0.0) - (i > 0 ? dx[3 * i + c] : 0.0);
+            const double it = 1.0 / a.tau[c], g1 = f1[k], g2 = f2[k], m1 = l1[k], m2 = l2[k];
+            const double dd = (w2[k] - s2[k] * adx) / s1[k];                                 // :318
+            const double q1 = -(m1 / g1) * (adx - dd) - m1 - it * 1.0 / g1;                   // :320
+            const double q2 = (m2 / g2) * (adx + dd) - m2 - it * 1.0 / g2;                    // :321
+            Adx[k] = adx; du[k] = dd; d1[k] = q1; d2[k] = q2; ev[k] = q1 - q2;
+            if (q1 < 0) mn[c] = fmin(mn[c], -m1 / q1);                                        // :325-326
+            if (q2 < 0) mn[c] = fmin(mn[c], -m2 / q2);
+            if ((adx - dd) > 0) mn[3 + c] = fmin(mn[3 + c], -g1 / (adx - dd));               // :327-328
+            if ((-adx - dd) > 0) mn[3 + c] = fmin(mn[3 + c], -g2 / (-adx - dd));
+        }
+    }
+    block_reduce_store<6, 1>(mn, part + 6 * blockIdx.x);
+}
+// |[rdual; rcent]|^2 per coordinate as block partials [RG][3] (:280-283, :334-336, :347-349).  TRIAL: of the trial point at step a.s
+// (state + s * direction); else of the state itself.  rdual = gradf0 + [Atv; -lamu1 - lamu2], rcent = [-lamu1.*fu1; -lamu2.*fu2] - 1/tau.
+template <bool TRIAL>
+__global__ __launch_bounds__(256) void k_pd_resid(int64_t m, int n, Pd3 a, const double* y, const double* Ax, const double* u, const double* l1,
+                                                  const double* l2, const double* Atv, const double* Adx, const double* du, const double* d1,
+                                                  const double* d2, const double* Atdv, double* part) {
+    double acc[3] = {0, 0, 0};
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256)
+        for (int c = 0; c < 3; ++c) {
+            if (!a.act[c]) continue;
+            const int64_t k = 3 * e + c;
+            double ax = Ax[k], uu = u[k], m1 = l1[k], m2 = l2[k];
+            if (TRIAL) { const double s = a.s[c]; uu = u[k] + s * du[k]; ax = Ax[k] + s * Adx[k]; m1 = l1[k] + s * d1[k]; m2 = l2[k] + s * d2[k]; }
+            const double g1 = (ax - y[k]) - uu, g2 = (-ax + y[k]) - uu;
+            const double it = 1.0 / a.tau[c];
+            const double rd = 1.0 + (-m1 - m2);
+            const double r1 = -m1 * g1 - it, r2 = -m2 * g2 - it;
+            acc[c] += rd * rd + r1 * r1 + r2 * r2;
+        }
+    for (int v = blockIdx.x * 256 + threadIdx.x; v < n; v += gridDim.x * 256) {
+        if (v == 0) continue;
+        for (int c = 0; c < 3; ++c) {
+            if (!a.act[c]) continue;
+            const double t = TRIAL ? Atv[3 * v + c] + a.s[c] * Atdv[3 * v + c] : Atv[3 * v + c];
+            acc[c] += t * t;
+        }
+    }
+    block_reduce_store<3, 0>(acc, part + 3 * blockIdx.x);
+}
+// the accepted step (:340-344) for the coordinates with act set, then fu1'*lamu1 and fu2'*lamu2 of the new point as partials [RG][6]
+__global__ __launch_bounds__(256) void k_pd_accept(int64_t m, int n, Pd3 a, const double* y, double* Ax, double* u, double* l1, double* l2,
+                                                   double* f1, double* f2, double* x, double* Atv, const double* dx, const double* Adx,
+                                                   const double* du, const double* d1, const double* d2, const double* Atdv, double* part) {
+    double acc[6] = {0, 0, 0, 0, 0, 0};
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256)
+        for (int c = 0; c < 3; ++c) {
+            const int64_t k = 3 * e + c;
+            if (a.act[c]) {
+                const double s = a.s[c];
+                const double uu = u[k] + s * du[k], ax = Ax[k] + s * Adx[k], m1 = l1[k] + s * d1[k], m2 = l2[k] + s * d2[k];
+                const double g1 = (ax - y[k]) - uu, g2 = (-ax + y[k]) - uu;
+                u[k] = uu; Ax[k] = ax; l1[k] = m1; l2[k] = m2; f1[k] = g1; f2[k] = g2;
+            }
+            acc[c] += f1[k] * l1[k]; acc[3 + c] += f2[k] * l2[k];
+        }
+    for (int v = blockIdx.x * 256 + threadIdx.x; v < n; v += gridDim.x * 256)
+        for (int c = 0; c < 3; ++c)
+            if (a.act[c]) { x[3 * v + c] = x[3 * v + c] + a.s[c] * dx[3 * v + c]; Atv[3 * v + c] = Atv[3 * v + c] + a.s[c] * Atdv[3 * v + c]; }
+    block_reduce_store<6, 0>(acc, part + 6 * blockIdx.x);
+}
+
+// ---- Jacobi-PCG with one weight vector per coordinate (weights not squared): A' diag(w_c) A x_c = b_c, node 0 grounded ----------------
+struct Cg3 { double rz[3], rz_new[3], pq[3], bnorm[3], rnorm[3]; int bad[3], pad; };
+
+__device__ __forceinline__ bool cg_breaks(double pq, double rz) { return !isfinite(pq) || !isfinite(rz) || (pq <= 0.0 && rz > 0.0); }
+
+// q_v = sum_t w_e,c (p_v - p_u) for v != 0 (next to refine.hip's k_lap, which squares one weight vector)
+__global__ __launch_bounds__(256) void k_lap3w(const int32_t* rowptr, const int32_t* adj, const int32_t* eid, const double* w, const double* p,
+                                               double* q, int n) {
+    const int l16 = threadIdx.x & 15;
+    const int row0 = (blockIdx.x * 256 + threadIdx.x) >> 4, nrows = (gridDim.x * 256) >> 4;
+    for (int vb = row0 - (row0 % 4); vb < n; vb += nrows) {
+        const int v = vb + (row0 % 4);
+        double a0 = 0, a1 = 0, a2 = 0;
+        if (v < n && v > 0) {
+            const double p0 = p[3 * v], p1 = p[3 * v + 1], p2 = p[3 * v + 2];
+            for (int t = rowptr[v] + l16; t < rowptr[v + 1]; t += 16) {
+                const int u = adj[t];
+                const int64_t e = eid[t];
+                a0 += w[3 * e] * (p0 - p[3 * u]); a1 += w[3 * e + 1] * (p1 - p[3 * u + 1]); a2 += w[3 * e + 2] * (p2 - p[3 * u + 2]);
+            }
+        }
+        a0 = group16_sum(a0); a1 = group16_sum(a1); a2 = group16_sum(a2);
+        if (v < n && l16 == 0) { q[3 * v] = a0; q[3 * v + 1] = a1; q[3 * v + 2] = a2; }
+    }
+}
+// one workgroup: column-wise dot products of two n x 3 arrays (fixed order)
+__global__ __launch_bounds__(256) void k_cg3_dot(const double* a, const double* b, int n, double* out3) {
+    double s[3] = {0, 0, 0};
+    for (int v = threadIdx.x; v < n; v += 256) for (int c = 0; c < 3; ++c) s[c] += a[3 * v + c] * b[3 * v + c];
+    block_reduce_store<3, 0>(s, out3);
+}
+__global__ void k_cg3_init(Cg3* sc, const double* rhs, const double* diag, double* x, double* r, double* z, double* p, int n) {
+    if (blockIdx.x == 0 && threadIdx.x < 3) sc->bad[threadIdx.x] = 0;
+    for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x)
+        for (int c = 0; c < 3; ++c) {
+            const double rv = v > 0 ? rhs[3 * v + c] : 0.0;
+            const double zv = (v > 0 && diag[3 * v + c] > 0) ? rv / diag[3 * v + c] : 0.0;
+            x[3 * v + c] = 0.0; r[3 * v + c] = rv; z[3 * v + c] = zv; p[3 * v + c] = zv;
+        }
+}
+// alpha = rz/pq (0 once the coordinate broke down) ; x += alpha p ; r -= alpha q ; z = r/diag
+__global__ void k_cg3_update(Cg3* sc, const double* diag, const double* p, const double* q, double* x, double* r, double* z, int n) {
+    double al[3];
+    for (int c = 0; c < 3; ++c) {
+        const bool brk = sc->bad[c] || cg_breaks(sc->pq[c], sc->rz[c]);
+        al[c] = (!brk && sc->pq[c] > 0) ? sc->rz[c] / sc->pq[c] : 0.0;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && threadIdx.x < 3 && cg_breaks(sc->pq[threadIdx.x], sc->rz[threadIdx.x])) sc->bad[threadIdx.x] = 1;
+    for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x)
+        for (int c = 0; c < 3; ++c) {
+            const double xv = x[3 * v + c] + al[c] * p[3 * v + c];
+            const double rv = r[3 * v + c] - al[c] * q[3 * v + c];
+            x[3 * v + c] = xv; r[3 * v + c] = rv;
+            z[3 * v + c] = (v > 0 && diag[3 * v + c] > 0) ? rv / diag[3 * v + c] : 0.0;
+        }
+}
+__global__ void k_cg3_dir(const Cg3* sc, const double* z, double* p, int n) {
+    double be[3];
+    for (int c = 0; c < 3; ++c) be[c] = sc->rz[c] > 0 ? sc->rz_new[c] / sc->rz[c] : 0.0;
+    for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x)
+        for (int c = 0; c < 3; ++c) p[3 * v + c] = z[3 * v + c] + be[c] * p[3 * v + c];
+}
+__global__ void k_cg3_roll(Cg3* sc) {
+    if (threadIdx.x < 3) {
+        if (!isfinite(sc->rz_new[threadIdx.x])) sc->bad[threadIdx.x] = 1;
+        sc->rz[threadIdx.x] = sc->rz_new[threadIdx.x];
+    }
+}
+
+// BoxMedianSO3Graph.m:172-185: score partial max_v |W_v| (v >= 1), exp map (NaN -> 0), Q <- Q * W.  x row 0 is 0.
+__global__ __launch_bounds__(256) void k_l1_node_update(const double* x, Quat* Q, int n, double* part) {
+    double sc[1] = {0.0};
+    for (int v = blockIdx.x * 256 + threadIdx.x; v < n; v += gridDim.x * 256) {
+        const double t1 = x[3 * v], t2 = x[3 * v + 1], t3 = x[3 * v + 2];
+        const double theta = sqrt(t1 * t1 + t2 * t2 + t3 * t3);
+        if (v > 0) sc[0] = fmax(sc[0], theta);
+        double wa = cos(theta / 2.0);
+        const double f = sin(theta / 2.0) / theta;
+        double wx = t1 * f, wy = t2 * f, wz = t3 * f;
+        if (isnan(wa)) wa = 0.0;
+        if (isnan(wx)) wx = 0.0;
+        if (isnan(wy)) wy = 0.0;
+        if (isnan(wz)) wz = 0.0;
+        const Quat q = Q[v];
+        Quat o;
+        o.a = q.a * wa - (q.x * wx + q.y * wy + q.z * wz);
+        o.x = q.a * wx + wa * q.x + (q.y * wz - q.z * wy);
+        o.y = q.a * wy + wa * q.y + (q.z * wx - q.x * wz);
+        o.z = q.a * wz + wa * q.z + (q.x * wy - q.y * wx);
+        Q[v] = o;
+    }
+    block_reduce_store<1, 2>(sc, part + blockIdx.x);
+}
+
+// ---- stage 5: residuals and weights (RobustMeanSO3Graph.m:169-170, L12.m:169-171) from the solved W (before the exp map) --------------
+__global__ __launch_bounds__(256) void k_irls_weights(const double* x, const double* B, const int32_t* ii, const int32_t* jj, int64_t m, int mode,
+                                                      double sigma, double* w) {
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256) {
+        const int i = ii[e], j = jj[e];
+        double s = 0.0;
+        for (int c = 0; c < 3; ++c) {
+            const double ax = (j > 0 ? x[3 * j + c] : 0.0) - (i > 0 ? x[3 * i + c] : 0.0);
+            const double d = ax - B[3 * e + c];
+            s += d * d;
+        }
+        double wt;
+        if (mode == DESC_IRLS_GM) wt = sigma / (s + sigma * sigma);
+        else { wt = 1.0 / pow(sqrt(s), 0.75); if (wt > 1e4) wt = 1e4; }
+        w[e] = wt;
+    }
+}
+__global__ void k_fill(double* p, int64_t count, double v) {
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (int64_t)gridDim.x * blockDim.x) p[t] = v;
+}
+__global__ void k_gather_quat(const Quat* QQ, const int32_t* ids, int count, Quat* out) {
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < count; t += gridDim.x * blockDim.x) out[t] = QQ[ids[t]];
+}
+
+// ---- the L1 stage's batched primal-dual solver ---------------------------------------------------------------------------------------
+struct PdState {
+    LaaSolver* L = nullptr;
+    int64_t n = 0, m = 0;
+    int egrid = 1, ngrid = 1, rgrid = 1;
+    double *y, *Ax, *u, *f1, *f2, *l1, *l2, *w2, *s1, *s2, *sx, *ev1, *ev2, *Adx, *du, *d1, *d2;     // m x 3
+    double *x, *Atv, *w1p, *dg, *dx, *Atdv, *r, *z, *p, *q;                                          // n x 3
+    double* part;
+    Cg3* sc;
+    hvec<double> hpart;
+    // counters
+    int steps = 0, ill = 0, stuck = 0, solves = 0, cg_total = 0, cg_unconverged = 0;
+    double cg_worst = 0.0, ms_pcg = 0.0;
+    bool verbose = false;
+};
+
+int pd_alloc(PdState& S, LaaSolver& L) {
+    int rc = DESC_OK;
+    S.L = &L; S.n = L.n; S.m = L.m;
+    const int64_t m3 = 3 * S.m, n3 = 3 * S.n;
+    double** em[] = {&S.y, &S.Ax, &S.u, &S.f1, &S.f2, &S.l1, &S.l2, &S.w2, &S.s1, &S.s2, &S.sx, &S.ev1, &S.ev2, &S.Adx, &S.du, &S.d1, &S.d2};
+    double** nm[] = {&S.x, &S.Atv, &S.w1p, &S.dg, &S.dx, &S.Atdv, &S.r, &S.z, &S.p, &S.q};
+    for (auto* a : em) if ((rc = L.alloc(a, m3))) return rc;
+    for (auto* a : nm) if ((rc = L.alloc(a, n3))) return rc;
+    double* sc = nullptr;
+    if ((rc = L.alloc(&S.part, 6 * RG)) || (rc = L.alloc(&sc, (sizeof(Cg3) + 7) / 8))) return rc;
+    S.sc = (Cg3*)sc;
+    S.hpart.resize(6 * RG);
+    S.egrid = L.egrid; S.ngrid = L.ngrid; S.rgrid = L.rgrid;
+    return DESC_OK;
+}
+
+// fixed-order host sums / minima of [RG][K] partials
+int read_part(PdState& S, int K, double* out, bool take_min) {
+    DESC_HIP(hipMemcpy(S.hpart.data(), S.part, sizeof(double) * K * RG, hipMemcpyDeviceToHost));
+    for (int k = 0; k < K; ++k) {
+        double a = take_min ? INFINITY : 0.0;
+        for (int b = 0; b < RG; ++b) a = take_min ? std::fmin(a, S.hpart[(size_t)K * b + k]) : a + S.hpart[(size_t)K * b + k];
+        out[k] = a;
+    }
+    return DESC_OK;
+}
+
+// dx_c = (A' diag(sx_c) A) \ w1p_c for the coordinates in act; bad[c] set on a breakdown
+int pd_pcg(PdState& S, const int act[3], int bad[3]) {
+    const LaaSolver& L = *S.L;
+    const desc_device_problem* dp = L.dp;
+    const int n = (int)S.n;
+    Pd3 none{}; none.act[0] = none.act[1] = none.act[2] = 1;
+    hipLaunchKernelGGL(k_pd_gather<2>, dim3(S.rgrid), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj_eid, L.d_sgn, S.sx, nullptr, none, S.dg, n);
+    hipLaunchKernelGGL(k_cg3_init, dim3(S.ngrid), dim3(256), 0, 0, S.sc, S.w1p, S.dg, S.dx, S.r, S.z, S.p, n);
+    hipLaunchKernelGGL(k_cg3_dot, dim3(1), dim3(256), 0, 0, S.r, S.z, n, &S.sc->rz[0]);
+    hipLaunchKernelGGL(k_cg3_dot, dim3(1), dim3(256), 0, 0, S.r, S.r, n, &S.sc->bnorm[0]);
+    const int cg_max = (int)std::min<int64_t>(20000, 20 * S.n + 200);
+    Cg3 hs;
+    int k = 0;
+    bool done = false;
+    for (k = 1; k <= cg_max; ++k) {
+        hipLaunchKernelGGL(k_lap3w, dim3(S.rgrid), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj, dp->d_adj_eid, S.sx, S.p, S.q, n);
+        hipLaunchKernelGGL(k_cg3_dot, dim3(1), dim3(256), 0, 0, S.p, S.q, n, &S.sc->pq[0]);
+        hipLaunchKernelGGL(k_cg3_update, dim3(S.ngrid), dim3(256), 0, 0, S.sc, S.dg, S.p, S.q, S.dx, S.r, S.z, n);
+        hipLaunchKernelGGL(k_cg3_dot, dim3(1), dim3(256), 0, 0, S.r, S.z, n, &S.sc->rz_new[0]);
+        hipLaunchKernelGGL(k_cg3_dir, dim3(S.ngrid), dim3(256), 0, 0, S.sc, S.z, S.p, n);
+        hipLaunchKernelGGL(k_cg3_roll, dim3(1), dim3(64), 0, 0, S.sc);
+        if (k % PD_PROBE == 0 || k == cg_max) {                                            // convergence probe: |r| <= 1e-13 |b|
+            hipLaunchKernelGGL(k_cg3_dot, dim3(1), dim3(256), 0, 0, S.r, S.r, n, &S.sc->rnorm[0]);
+            DESC_HIP(hipMemcpy(&hs, S.sc, sizeof hs, hipMemcpyDeviceToHost));
+            done = true;
+            for (int c = 0; c < 3; ++c)
+                if (act[c] && !hs.bad[c] && hs.rnorm[c] > 1e-26 * hs.bnorm[c] && hs.rnorm[c] > 1e-300) done = false;
+            if (done || k == cg_max) break;
+        }
+    }
+    S.cg_total += std::min(k, cg_max);
+    ++S.solves;
+    for (int c = 0; c < 3; ++c) {
+        bad[c] = act[c] && hs.bad[c];
+        if (act[c] && !bad[c] && hs.bnorm[c] > 0) S.cg_worst = std::max(S.cg_worst, std::sqrt(hs.rnorm[c] / hs.bnorm[c]));
+    }
+    if (!done) ++S.cg_unconverged;
+    return DESC_OK;
+}
+
+// W(2:end, 2:4) = [l1decode_pd(0, A, [], B(:,c), eps, pdmaxiter, AtA) for c = 1..3] (BoxMedianSO3Graph.m:166-168) into S.x
+int pd_solve(PdState& S, const double* d_B, int pdmaxiter) {
+    int rc = DESC_OK;
+    const LaaSolver& L = *S.L;
+    const desc_device_problem* dp = L.dp;
+    const int64_t m = S.m;
+    const int n = (int)S.n;
+    const double pdtol = 2.220446049250313e-16, alpha = 0.01, beta = 0.5, mu = 10.0;   // :262-266
+    const double M = (double)m;
+    DESC_HIP(hipMemcpyAsync(S.y, d_B, sizeof(double) * 3 * m, hipMemcpyDeviceToDevice, 0));
+    DESC_HIP(hipMemsetAsync(S.x, 0, sizeof(double) * 3 * n, 0));
+    Pd3 a{}; for (int c = 0; c < 3; ++c) a.act[c] = 1;
+    // ---- start (:268-287)
+    hipLaunchKernelGGL(k_pd_absmax, dim3(RG), dim3(256), 0, 0, S.y, m, S.part);
+    {
+        DESC_HIP(hipMemcpy(S.hpart.data(), S.part, sizeof(double) * 3 * RG, hipMemcpyDeviceToHost));
+        for (int c = 0; c < 3; ++c) { double v = 0.0; for (int b = 0; b < RG; ++b) v = std::fmax(v, S.hpart[3 * b + c]); a.ymax[c] = v; }
+    }
+    hipLaunchKernelGGL(k_pd_init, dim3(S.egrid), dim3(256), 0, 0, S.y, m, a, S.Ax, S.u, S.f1, S.f2, S.l1, S.l2, S.ev1);
+    hipLaunchKernelGGL(k_pd_gather<0>, dim3(S.rgrid), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj_eid, L.d_sgn, S.ev1, nullptr, a, S.Atv, n);
+    double tau[3], resnorm[3], sdg[3], dots[6];
+    // sdg, tau, resnorm of the current point (:280-283, :347-350) for the coordinates in act; fu1'*lamu1 and fu2'*lamu2 are the
+    // partials the last k_pd_accept launch left in S.part (it forms them from the point it has just written)
+    auto scalars = [&](const int act[3]) -> int {
+        Pd3 b{};
+        int rc2 = read_part(S, 6, dots, false);
+        if (rc2) return rc2;
+        for (int c = 0; c < 3; ++c) {
+            if (!act[c]) continue;
+            sdg[c] = -(dots[c] + dots[3 + c]);
+            tau[c] = mu * 2.0 * M / sdg[c];
+            b.act[c] = 1; b.tau[c] = tau[c];
+        }
+        hipLaunchKernelGGL(k_pd_resid<false>, dim3(RG), dim3(256), 0, 0, m, n, b, S.y, S.Ax, S.u, S.l1, S.l2, S.Atv, S.Adx, S.du, S.d1, S.d2,
+                           S.Atdv, S.part);
+        double rr[3];
+        if ((rc2 = read_part(S, 3, rr, false))) return rc2;
+        for (int c = 0; c < 3; ++c) if (act[c]) resnorm[c] = std::sqrt(rr[c]);
+        return DESC_OK;
+    };
+    int run[3] = {1, 1, 1};
+    {
+        const Pd3 none{};                                                // no coordinate moves: only the dot partials of the start
+        hipLaunchKernelGGL(k_pd_accept, dim3(RG), dim3(256), 0, 0, m, n, none, S.y, S.Ax, S.u, S.l1, S.l2, S.f1, S.f2, S.x, S.Atv, S.dx, S.Adx,
+                           S.du, S.d1, S.d2, S.Atdv, S.part);
+    }
+    if ((rc = scalars(run))) return rc;
+    int pditer = 0;
+    for (int c = 0; c < 3; ++c) run[c] = !((sdg[c] < pdtol) | (pditer >= pdmaxiter));         // :287
+    while (run[0] || run[1] || run[2]) {
+        ++pditer;
+        for (int c = 0; c < 3; ++c) { a.act[c] = run[c]; a.tau[c] = tau[c]; }
+        // ---- Newton system (:296-312)
+        hipLaunchKernelGGL(k_pd_pre, dim3(S.egrid), dim3(256), 0, 0, m, a, S.f1, S.f2, S.l1, S.l2, S.w2, S.s1, S.s2, S.sx, S.ev1, S.ev2);
+        Pd3 g = a;
+        for (int c = 0; c < 3; ++c) g.tau[c] = run[c] ? -1.0 / tau[c] : 0.0;                 // w1 = -1/tau * (A' ...)
+        hipLaunchKernelGGL(k_pd_gather<1>, dim3(S.rgrid), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj_eid, L.d_sgn, S.ev1, S.ev2, g, S.w1p, n);
+        DESC_HIP(hipDeviceSynchronize());
+        auto tp = std::chrono::steady_clock::now();
+        int bad[3];
+        if ((rc = pd_pcg(S, run, bad))) return rc;
+        S.ms_pcg += ms_since(tp);
+        for (int c = 0; c < 3; ++c)
+            if (bad[c]) {                                                                    // :308-312
+                if (S.verbose) printf("Matrix ill-conditioned.  Returning previous iterate.  (See Section 4 of notes for more information.)\n");
+                ++S.ill; run[c] = 0; a.act[c] = 0;
+            }
+        if (!(run[0] || run[1] || run[2])) break;
+        for (int c = 0; c < 3; ++c) if (run[c]) ++S.steps;
+        // ---- direction and step length (:315-330)
+        hipLaunchKernelGGL(k_pd_dir, dim3(RG), dim3(256), 0, 0, dp->d_ii, dp->d_jj, m, a, S.dx, S.f1, S.f2, S.l1, S.l2, S.w2, S.s1, S.s2, S.Adx, S.du,
+                           S.d1, S.d2, S.ev1, S.part);
+        double mins[6];
+        if ((rc = read_part(S, 6, mins, true))) return rc;
+        hipLaunchKernelGGL(k_pd_gather<0>, dim3(S.rgrid), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj_eid, L.d_sgn, S.ev1, nullptr, a, S.Atdv, n);
+        double s[3] = {0, 0, 0};
+        for (int c = 0; c < 3; ++c)
+            if (run[c]) { s[c] = std::fmin(1.0, mins[c]); s[c] = 0.99 * std::fmin(s[c], mins[3 + c]); }
+        // ---- backtracking (:332-346): one trial of every searching coordinate per launch
+        int search[3], backiter[3] = {0, 0, 0}, accept[3] = {0, 0, 0};
+        double s_acc[3] = {0, 0, 0};
+        for (int c = 0; c < 3; ++c) search[c] = run[c];
+        while (search[0] || search[1] || search[2]) {
+            Pd3 t{};
+            for (int c = 0; c < 3; ++c) { t.act[c] = search[c]; t.s[c] = s[c]; t.tau[c] = tau[c]; }
+            hipLaunchKernelGGL(k_pd_resid<true>, dim3(RG), dim3(256), 0, 0, m, n, t, S.y, S.Ax, S.u, S.l1, S.l2, S.Atv, S.Adx, S.du, S.d1, S.d2,
+                               S.Atdv, S.part);
+            double rr[3];
+            if ((rc = read_part(S, 3, rr, false))) return rc;
+            for (int c = 0; c < 3; ++c) {
+                if (!search[c]) continue;
+                const bool suffdec = std::sqrt(rr[c]) <= (1.0 - alpha * s[c]) * resnorm[c];
+                const double s_tried = s[c];
+                s[c] = beta * s[c];
+                ++backiter[c];
+                if (backiter[c] > 32) {                                                      // :339-343
+                    if (S.verbose) printf("Stuck backtracking, returning last iterate.  (See Section 4 of notes for more information.)\n");
+                    ++S.stuck; search[c] = 0; run[c] = 0;
+                } else if (suffdec) { search[c] = 0; accept[c] = 1; s_acc[c] = s_tried; }
+            }
+        }
+        // ---- next iterate (:348-356)
+        Pd3 acc{};
+        for (int c = 0; c < 3; ++c) { acc.act[c] = accept[c]; acc.s[c] = s_acc[c]; }
+        hipLaunchKernelGGL(k_pd_accept, dim3(RG), dim3(256), 0, 0, m, n, acc, S.y, S.Ax, S.u, S.l1, S.l2, S.f1, S.f2, S.x, S.Atv, S.dx, S.Adx, S.du,
+                           S.d1, S.d2, S.Atdv, S.part);
+        if ((rc = scalars(accept))) return rc;
+        for (int c = 0; c < 3; ++c)
+            if (accept[c]) run[c] = !((sdg[c] < pdtol) | (pditer >= pdmaxiter));
+    }
+    DESC_HIP(hipGetLastError());
+    return DESC_OK;
+}
+
+// BoxMedianSO3Graph.m:79-114: the spanning-tree start, passes over the edges in `visit` order; Q n x 4 host quaternions
+int tree_start(const desc_device_problem* sp, const hvec<int32_t>& visit, const Quat* d_QQ, hvec<Quat>& Q) {
+    const int64_t n = sp->n;
+    const int32_t *ii = sp->ii.data(), *jj = sp->jj.data();
+    hvec<uint8_t> done((size_t)n, 0);
+    hvec<int32_t> seq_e, seq_dir;
+    seq_e.reserve((size_t)n); seq_dir.reserve((size_t)n);
+    done[0] = 1;                                                                            // :86-87 (a = 1)
+    int64_t count = 1;
+    while (count < n) {
+        bool span = false;
+        for (const int32_t e : visit) {
+            const int i = ii[e], j = jj[e];
+            if (done[i] && !done[j]) { seq_e.push_back(e); seq_dir.push_back(0); done[j] = 1; ++count; span = true; }
+            if (!done[i] && done[j]) { seq_e.push_back(e); seq_dir.push_back(1); done[i] = 1; ++count; span = true; }
+        }
+        if (!span && count < n) return fail(DESC_ERR_STATE, "spanning-tree start: %lld of %lld nodes reached", (long long)count, (long long)n);
+    }
+    const int cnt = (int)seq_e.size();
+    hvec<Quat> qq((size_t)std::max(cnt, 1));
+    if (cnt) {
+        int32_t* d_ids = nullptr; Quat* d_out = nullptr;
+        DESC_HIP(dev_alloc((void**)&d_ids, sizeof(int32_t) * cnt));
+        struct F { void* p; ~F() { dev_free(p); } } f1{d_ids};
+        DESC_HIP(dev_alloc((void**)&d_out, sizeof(Quat) * cnt));
+        struct F2 { void* p; ~F2() { dev_free(p); } } f2{d_out};
+        DESC_HIP(hipMemcpy(d_ids, seq_e.data(), sizeof(int32_t) * cnt, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_gather_quat, dim3((cnt + 255) / 256), dim3(256), 0, 0, d_QQ, d_ids, cnt, d_out);
+        DESC_HIP(hipMemcpy(qq.data(), d_out, sizeof(Quat) * cnt, hipMemcpyDeviceToHost));
+    }
+    Q.assign((size_t)n, Quat{1.0, 0.0, 0.0, 0.0});                                          // :78
+    for (int t = 0; t < cnt; ++t) {
+        const Quat g = qq[t];
+        const int e = seq_e[t];
+        if (seq_dir[t] == 0) {                                                              // :93-95: Q(j) = QQ * Q(i)
+            const Quat b = Q[ii[e]];
+            Quat o;
+            o.a = g.a * b.a - (g.x * b.x + g.y * b.y + g.z * b.z);
+            o.x = g.a * b.x + b.a * g.x + (g.y * b.z - g.z * b.y);
+            o.y = g.a * b.y + b.a * g.y + (g.z * b.x - g.x * b.z);
+            o.z = g.a * b.z + b.a * g.z + (g.x * b.y - g.y * b.x);
+            Q[jj[e]] = o;
+        } else {                                                                            // :101-103: Q(i) from Q(j)
+            const Quat b = Q[jj[e]];
+            const double na = -g.a;
+            Quat o;
+            o.a = na * b.a - (g.x * b.x + g.y * b.y + g.z * b.z);
+            o.x = na * b.x + b.a * g.x + (g.y * b.z - g.z * b.y);
+            o.y = na * b.y + b.a * g.y + (g.z * b.x - g.x * b.z);
+            o.z = na * b.z + b.a * g.z + (g.x * b.y - g.y * b.x);
+            Q[ii[e]] = o;
+        }
+    }
+    return DESC_OK;
+}
+
+struct ProbOwner { desc_device_problem* p = nullptr; ~ProbOwner() { if (p) desc_problem_free(p); } };
+
+}  // namespace
+}  // namespace desc
+
+using namespace desc;
+
+extern "C" int desc_irls_run(const desc_problem* prob, const desc_irls_params* params, int32_t device, double* R_out, double* R_l1,
+                             desc_irls_info* info) {
+    if (!prob || !params || !R_out) return fail(DESC_ERR_INVALID, "NULL argument");
+    auto t0 = std::chrono::steady_clock::now();
+    desc_device_problem* dp = nullptr;
+    int rc = desc_problem_upload(prob, device, &dp);
+    if (rc) return rc;
+    rc = desc_irls_run_dev(dp, params, R_out, R_l1, info);
+    desc_problem_free(dp);
+    if (!rc && info) info->ms_total = ms_since(t0);
+    return rc;
+}
+
+extern "C" int desc_irls_run_dev(const desc_device_problem* dp, const desc_irls_params* P, double* R_out, double* R_l1, desc_irls_info* info) {
+    return no_throw("desc_irls_run_dev", [&]() -> int {
+    if (!dp || !P || !R_out) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (P->mode != DESC_IRLS_GM && P->mode != DESC_IRLS_L12) return fail(DESC_ERR_INVALID, "mode must be DESC_IRLS_GM or DESC_IRLS_L12");
+    const int64_t n = dp->n, m = dp->m;
+    if (n < 2 || m < 1) return fail(DESC_ERR_INVALID, "empty graph");
+    const int max_l1 = P->max_iter_l1 > 0 ? P->max_iter_l1 : 10, max_irls = P->max_iter_irls > 0 ? P->max_iter_irls : 100;
+    const double sigma = (P->sigma_deg > 0 ? P->sigma_deg : 5.0) * M_PI / 180.0;            // RobustMeanSO3Graph.m:60
+    const bool verbose = P->verbose != 0;
+    int rc = DESC_OK;
+    if (P->order) {
+        hvec<uint8_t> seen((size_t)m, 0);
+        for (int64_t e = 0; e < m; ++e) {
+            const int32_t r = P->order[e];
+            if (r < 0 || r >= m || seen[r]) return fail(DESC_ERR_INVALID, "order must be a permutation of 0..m-1");
+            seen[r] = 1;
+        }
+    }
+    DESC_HIP(hipSetDevice(dp->device));
+    auto t0 = std::chrono::steady_clock::now();
+    desc_irls_info I{};
+    // ---- stage 3: checks and projection of every edge (IRLS_GM.m:82-93)
+    double* d_P = nullptr;
+    int32_t *d_flags = nullptr, *d_order = nullptr;
+    double* d_einfo = nullptr;
+    DESC_HIP(dev_alloc((void**)&d_P, sizeof(double) * 9 * m));
+    struct FreeP { void* p; ~FreeP() { dev_free(p); } } fP{d_P};
+    DESC_HIP(dev_alloc((void**)&d_flags, sizeof(int32_t) * 2));
+    struct FreeF { void* p; ~FreeF() { dev_free(p); } } fF{d_flags};
+    DESC_HIP(dev_alloc((void**)&d_einfo, sizeof(double) * 5));
+    struct FreeE { void* p; ~FreeE() { dev_free(p); } } fE{d_einfo};
+    if (P->order) {
+        DESC_HIP(dev_alloc((void**)&d_order, sizeof(int32_t) * m));
+        DESC_HIP(hipMemcpy(d_order, P->order, sizeof(int32_t) * m, hipMemcpyHostToDevice));
+    }
+    struct FreeO { void* p; ~FreeO() { if (p) dev_free(p); } } fO{d_order};
+    const int32_t init_flags[2] = {INT_MAX, 0};
+    DESC_HIP(hipMemcpy(d_flags, init_flags, sizeof init_flags, hipMemcpyHostToDevice));
+    const int egrid_full = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (m + 255) / 256));
+    hipLaunchKernelGGL(k_irls_project, dim3(egrid_full), dim3(256), 0, 0, dp->d_rij, d_order, m, d_P, d_flags, d_flags + 1, (int64_t)-1, d_einfo);
+    DESC_HIP(hipGetLastError());
+    int32_t flags[2];
+    DESC_HIP(hipMemcpy(flags, d_flags, sizeof flags, hipMemcpyDeviceToHost));
+    if (flags[0] != INT_MAX) {
+        int64_t e = flags[0];
+        if (P->order) for (int64_t t = 0; t < m; ++t) if (P->order[t] == flags[0]) { e = t; break; }
+        hipLaunchKernelGGL(k_irls_project, dim3(1), dim3(256), 0, 0, dp->d_rij, d_order, m, d_P, d_flags, d_flags + 1, e, d_einfo);
+        double ei[5];
+        DESC_HIP(hipMemcpy(ei, d_einfo, sizeof ei, hipMemcpyDeviceToHost));
+        if (ei[0] == 3) return fail(DESC_ERR_INVALID, "det(RR(:,:,%d))=%f", (int)flags[0] + 1, ei[1]);
+        return fail(DESC_ERR_INVALID, "svd(RR(:,:,%d))=[%f %f %f]", (int)flags[0] + 1, ei[2], ei[3], ei[4]);
+    }
+    I.warned_edges = flags[1];
+    if (flags[1]) fprintf(stderr, "[desc_amd] warning: %d edge rotations have all three singular values off 1 by >= 0.01: projected to SO(3)\n", flags[1]);
+    I.ms_project = ms_since(t0);
+    // ---- stage 2: the largest connected component (IRLS_GM.m:65-67)
+    auto t1 = std::chrono::steady_clock::now();
+    hvec<int32_t> comp((size_t)n);
+    int64_t ncomp = 0;
+    if ((rc = components_device(dp, comp.data(), &ncomp))) return rc;
+    const desc_device_problem* sp = dp;
+    ProbOwner sub;
+    const double* d_blocks = d_P;
+    hvec<int32_t> nodes, edge_map;                                                          // sub-problem node -> node, edge -> edge
+    hvec<int32_t> visit;                                                                    // sub-problem edges in the caller's row order
+    if (ncomp > 1) {
+        hvec<int64_t> size((size_t)n, 0);
+        for (int64_t v = 0; v < n; ++v) ++size[comp[v]];
+        hvec<uint8_t> seen((size_t)n, 0);
+        int32_t best = -1; int64_t best_size = 0;
+        for (int64_t v = 0; v < n; ++v) {                                                    // components by their smallest node: first of max size
+            const int32_t l = comp[v];
+            if (seen[l]) continue;
+            seen[l] = 1;
+            if (size[l] > best_size) { best_size = size[l]; best = l; }
+        }
+        hvec<int32_t> newid((size_t)n, -1);
+        for (int64_t v = 0; v < n; ++v) if (comp[v] == best) { newid[v] = (int32_t)nodes.size(); nodes.push_back((int32_t)v); }
+        hvec<int32_t> si, sj;
+        for (int64_t e = 0; e < m; ++e)
+            if (comp[dp->ii[e]] == best) { edge_map.push_back((int32_t)e); si.push_back(newid[dp->ii[e]]); sj.push_back(newid[dp->jj[e]]); }
+        const int64_t ms = (int64_t)edge_map.size();
+        hvec<double> hP((size_t)9 * m), sP((size_t)9 * ms);
+        DESC_HIP(hipMemcpy(hP.data(), d_P, sizeof(double) * 9 * m, hipMemcpyDeviceToHost));
+        for (int64_t t = 0; t < ms; ++t) std::copy(&hP[9 * (size_t)edge_map[t]], &hP[9 * (size_t)edge_map[t]] + 9, &sP[9 * (size_t)t]);
+        desc_problem q{(int64_t)nodes.size(), ms, si.data(), sj.data(), sP.data()};
+        if ((rc = desc_problem_upload(&q, dp->device, &sub.p))) return rc;
+        sp = sub.p; d_blocks = sub.p->d_rij;
+        visit.resize((size_t)ms);
+        for (int64_t t = 0; t < ms; ++t) visit[t] = (int32_t)t;
+        if (P->order) std::sort(visit.begin(), visit.end(), [&](int32_t a, int32_t b) { return P->order[edge_map[a]] < P->order[edge_map[b]]; });
+    } else {
+        visit.resize((size_t)m);
+        if (P->order) for (int64_t e = 0; e < m; ++e) visit[P->order[e]] = (int32_t)e;
+        else for (int64_t e = 0; e < m; ++e) visit[e] = (int32_t)e;
+    }
+    const int64_t nc = sp->n, mc = sp->m;
+    I.comp_nodes = nc; I.comp_edges = mc;
+    I.ms_components = ms_since(t1);
+    // ---- stage 4: BoxMedianSO3Graph (IRLS_GM.m:95)
+    auto t2 = std::chrono::steady_clock::now();
+    hvec<double> r_l1((size_t)9 * nc);
+    {
+        hvec<double> rinit((size_t)9 * nc, 0.0);
+        if (P->R_init) {
+            for (int64_t v = 0; v < nc; ++v) {
+                const int64_t src = nodes.empty() ? v : nodes[v];
+                std::copy(P->R_init + 9 * src, P->R_init + 9 * src + 9, &rinit[9 * (size_t)v]);
+            }
+        } else
+            for (int64_t v = 0; v < nc; ++v) rinit[9 * v] = rinit[9 * v + 4] = rinit[9 * v + 8] = 1.0;
+        LaaSolver L;
+        if ((rc = laa_setup(sp, rinit.data(), L))) return rc;                              // Q = R2Q(Rinit) (:64-69) when given
+        laa_set_qq(L, d_blocks);                                                            // QQ of the projected RR (:55-59)
+        if (!P->R_init) {
+            auto tt = std::chrono::steady_clock::now();
+            hvec<Quat> Q;
+            if ((rc = tree_start(sp, visit, L.d_QQ, Q))) return rc;
+            DESC_HIP(hipMemcpy(L.d_Q, Q.data(), sizeof(Quat) * nc, hipMemcpyHostToDevice));
+            I.ms_tree = ms_since(tt);
+        }
+        PdState S;
+        S.verbose = verbose;
+        if ((rc = pd_alloc(S, L))) return rc;
+        double* d_smax = nullptr;
+        if ((rc = L.alloc(&d_smax, L.sgrid))) return rc;
+        hvec<double> smax((size_t)L.sgrid);
+        double changeThreshold = .001, score = INFINITY;                                     // :56, :134
+        int Iteration = 0, L1Step = 2;
+        if (verbose) printf("Itr\tMaxChange\tTime\n%d  NaN  %g\n", 0, ms_since(t2) / 1e3);  // :136-137
+        while (((score >= changeThreshold) || (L1Step < 2)) && (Iteration < max_l1)) {     // :138
+            if (score < changeThreshold) { L1Step = L1Step * 4; changeThreshold = changeThreshold / 100; }   // :139
+            laa_edge_log(L);                                                                // :141-160
+            if ((rc = pd_solve(S, L.d_B, L1Step))) return rc;                               // :162-168
+            hipLaunchKernelGGL(k_l1_node_update, dim3(L.sgrid), dim3(256), 0, 0, S.x, L.d_Q, (int)nc, d_smax);   // :173-185
+            DESC_HIP(hipMemcpy(smax.data(), d_smax, sizeof(double) * L.sgrid, hipMemcpyDeviceToHost));
+            score = 0.0;
+            for (double v : smax) score = std::fmax(score, v);
+            ++Iteration;
+            if (verbose) printf("%d  %g  %g\n", Iteration, score, ms_since(t2) / 1e3);      // :188
+        }
+        if (verbose && Iteration >= max_l1) printf("Max iterations reached\n");              // :201
+        if ((rc = laa_finish(L, Iteration, r_l1.data()))) return rc;                         // real(q2R(Q)) (:192-197)
+        I.l1_iters = Iteration; I.l1_score = score;
+        I.pd_steps = S.steps; I.pd_ill = S.ill; I.pd_stuck = S.stuck; I.pd_solves = S.solves;
+        I.cg_iters_l1 = S.cg_total; I.cg_unconverged = S.cg_unconverged; I.cg_residual = S.cg_worst; I.ms_l1_pcg = S.ms_pcg;
+        if (S.cg_unconverged)
+            fprintf(stderr, "[desc_amd] warning: %d primal-dual Newton solves stopped at the PCG iteration cap (relative residual up to %.3e)\n",
+                    S.cg_unconverged, S.cg_worst);
+    }
+    I.ms_l1 = ms_since(t2);
+    // ---- stage 5: RobustMeanSO3Graph / L12 (IRLS_GM.m:96)
+    auto t3 = std::chrono::steady_clock::now();
+    hvec<double> r_out((size_t)9 * nc);
+    {
+        LaaSolver L;
+        if ((rc = laa_setup(sp, r_l1.data(), L))) return rc;                                // Q = R2Q(R) (:75-80)
+        laa_set_qq(L, d_blocks);
+        hipLaunchKernelGGL(k_fill, dim3(L.egrid), dim3(256), 0, 0, L.d_w, mc, 1.0);         // :127
+        double score = INFINITY;
+        int Iteration = 0;
+        if (verbose) printf("%d  NaN  %g\n", 0, ms_since(t3) / 1e3);                        // :129
+        while ((score > 1e-3) && (Iteration < max_irls)) {                                  // :130
+            if ((rc = laa_step(L, &score))) return rc;                                      // :132-186
+            hipLaunchKernelGGL(k_irls_weights, dim3(L.egrid), dim3(256), 0, 0, L.d_x, L.d_B, sp->d_ii, sp->d_jj, mc, P->mode, sigma, L.d_w);   // :169-171
+            DESC_HIP(hipGetLastError());
+            ++Iteration;
+            if (verbose) printf("%d  %g  %g\n", Iteration, score, ms_since(t3) / 1e3);       // :189
+        }
+        if (verbose && Iteration >= max_irls) printf("Max iterations reached\n");            // :202
+        if ((rc = laa_finish(L, Iteration, r_out.data()))) return rc;                        // q2R (:193-197)
+        I.irls_iters = Iteration; I.irls_score = score;
+        I.cg_iters_irls = L.cg_total; I.cg_unconverged += L.cg_unconverged; I.cg_residual = std::max(I.cg_residual, L.cg_worst);
+    }
+    I.ms_irls = ms_since(t3);
+    // ---- NaN outside the component (:94)
+    auto place = [&](const hvec<double>& src, double* dst) {
+        if (nodes.empty()) { std::copy(src.begin(), src.end(), dst); return; }
+        std::fill(dst, dst + 9 * n, NAN);
+        for (size_t v = 0; v < nodes.size(); ++v) std::copy(&src[9 * v], &src[9 * v] + 9, dst + 9 * (int64_t)nodes[v]);
+    };
+    place(r_out, R_out);
+    if (R_l1) place(r_l1, R_l1);
+    if (verbose) fflush(stdout);
+    I.ms_total = ms_since(t0);
+    if (info) *info = I;
+    return DESC_OK;
+    });
+}

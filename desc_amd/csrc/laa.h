@@ -32,6 +32,11 @@ struct LaaSolver {
 int laa_setup(const desc_device_problem* dp, const double* R_init, LaaSolver& L);
 // Weighted_LAA.m:4-51 with the weights in L.d_w: edge log map B, normal equations by PCG, Q <- Q * exp(W); *score = :40
 int laa_step(LaaSolver& L, double* score);
+// QQ = R2Q(blocks) of m blocks that are already in the reference's RR orientation (no transpose): replaces laa_setup's
+// R2Q(permute(RijMat, [2,1,3])) when the edge rotations were modified first (IRLS_GM.m:82-93, irls.hip)
+void laa_set_qq(LaaSolver& L, const double* d_blocks);
+// Weighted_LAA.m:9-35 alone: the edge log map of the current Q into L.d_B (BoxMedianSO3Graph.m:143-160 is the same text)
+void laa_edge_log(LaaSolver& L);
 // weights from a per-edge residual vector (DESC.m:298-303, MPLS.m:241-245): w = min(1/x^0.75, 1e4), 1e-4 where x > thresh
 void laa_weights(LaaSolver& L, const double* d_x, double thresh);
 // MATLAB quantile(x, p) of a device vector of m entries

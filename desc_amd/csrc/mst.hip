@@ -12,6 +12,7 @@
 // pattern of the key first, the index second), mutual choices hook the higher label under the lower, and labels are flattened by
 // pointer jumping.  The host drives the rounds with one read-back each, at most ceil(log2 n) + 2 of them; no device-side waits.
 // Rooting and propagation run on the host (O(n), microseconds) from the n - 1 tree edges and their 72-byte blocks.
+// components_device runs the same rounds with all keys equal and returns the component labels (IRLS_GM.m:65-67, irls.hip).
 #include <algorithm>
 #include <chrono>
 #include <climits>
@@ -118,28 +119,19 @@ void mul3(const double* A, bool transpose_a, const double* B, double* C) {
         }
 }
 
-}  // namespace
-
-int mst_device(const desc_device_problem* dp, const double* d_s, double* R_out, int32_t* tree_edges) {
+// The Boruvka rounds on the CSR index with edge order (d_key[e], e): on return d_comp holds every node's component label (the label of
+// a component is one of its nodes) and d_mark the forest's edges (d_mark must be zeroed by the caller).  Shared by mst_device and
+// components_device.
+int boruvka_rounds(const desc_device_problem* dp, const unsigned long long* d_key, int32_t* d_comp, uint8_t* d_mark, DevM& D) {
     int rc = DESC_OK;
-    const int64_t n = dp->n, m = dp->m;
-    if (n <= 0) return fail(DESC_ERR_INVALID, "empty graph");
-    DevM D;
-    unsigned long long *d_key, *d_rkey, *d_bkey;
-    int32_t *d_comp, *d_parent, *d_ridx, *d_bidx, *d_cnt, *d_ids;
-    uint8_t* d_mark;
-    double* d_blocks;
-    if ((rc = D.alloc(&d_key, m)) || (rc = D.alloc(&d_rkey, n)) || (rc = D.alloc(&d_bkey, n)) || (rc = D.alloc(&d_comp, n)) ||
-        (rc = D.alloc(&d_parent, n)) || (rc = D.alloc(&d_ridx, n)) || (rc = D.alloc(&d_bidx, n)) || (rc = D.alloc(&d_cnt, 2)) ||
-        (rc = D.alloc(&d_ids, n)) || (rc = D.alloc(&d_mark, m)) || (rc = D.alloc(&d_blocks, 9 * n)))
+    const int64_t n = dp->n;
+    unsigned long long *d_rkey, *d_bkey;
+    int32_t *d_parent, *d_ridx, *d_bidx, *d_cnt;
+    if ((rc = D.alloc(&d_rkey, n)) || (rc = D.alloc(&d_bkey, n)) || (rc = D.alloc(&d_parent, n)) || (rc = D.alloc(&d_ridx, n)) ||
+        (rc = D.alloc(&d_bidx, n)) || (rc = D.alloc(&d_cnt, 2)))
         return rc;
-    const int egrid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (m + 255) / 256));
     const int ngrid = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (n + 255) / 256));
     const int wgrid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n + 3) / 4));          // a wave per row
-    if (m) {
-        hipLaunchKernelGGL(k_mst_keys, dim3(egrid), dim3(256), 0, 0, d_s, d_key, m);
-        DESC_HIP(hipMemsetAsync(d_mark, 0, m, 0));
-    }
     hipLaunchKernelGGL(k_mst_init, dim3(ngrid), dim3(256), 0, 0, d_comp, d_parent, (int)n);
     const int log2n = (int)std::ceil(std::log2((double)n));
     const int max_rounds = log2n + 2, jumps = log2n + 1;
@@ -157,6 +149,29 @@ int mst_device(const desc_device_problem* dp, const double* d_s, double* R_out, 
         for (int t = 0; t < jumps; ++t) hipLaunchKernelGGL(k_mst_jump, dim3(ngrid), dim3(256), 0, 0, d_parent, (int)n);
         hipLaunchKernelGGL(k_mst_relabel, dim3(ngrid), dim3(256), 0, 0, d_comp, d_parent, (int)n);
     }
+    return DESC_OK;
+}
+
+}  // namespace
+
+int mst_device(const desc_device_problem* dp, const double* d_s, double* R_out, int32_t* tree_edges) {
+    int rc = DESC_OK;
+    const int64_t n = dp->n, m = dp->m;
+    if (n <= 0) return fail(DESC_ERR_INVALID, "empty graph");
+    DevM D;
+    unsigned long long* d_key;
+    int32_t *d_comp, *d_cnt, *d_ids;
+    uint8_t* d_mark;
+    double* d_blocks;
+    if ((rc = D.alloc(&d_key, m)) || (rc = D.alloc(&d_comp, n)) || (rc = D.alloc(&d_cnt, 2)) || (rc = D.alloc(&d_ids, n)) ||
+        (rc = D.alloc(&d_mark, m)) || (rc = D.alloc(&d_blocks, 9 * n)))
+        return rc;
+    const int egrid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (m + 255) / 256));
+    if (m) {
+        hipLaunchKernelGGL(k_mst_keys, dim3(egrid), dim3(256), 0, 0, d_s, d_key, m);
+        DESC_HIP(hipMemsetAsync(d_mark, 0, m, 0));
+    }
+    if ((rc = boruvka_rounds(dp, d_key, d_comp, d_mark, D))) return rc;
     DESC_HIP(hipMemsetAsync(d_cnt, 0, sizeof(int32_t), 0));
     if (m) hipLaunchKernelGGL(k_mst_collect, dim3(egrid), dim3(256), 0, 0, d_mark, dp->d_rij, m, d_ids, d_blocks, d_cnt, (int)n);
     DESC_HIP(hipGetLastError());
@@ -202,6 +217,33 @@ int mst_device(const desc_device_problem* dp, const double* d_s, double* R_out, 
         std::sort(ids.begin(), ids.end());
         std::copy(ids.begin(), ids.end(), tree_edges);
     }
+    return DESC_OK;
+}
+
+int components_device(const desc_device_problem* dp, int32_t* comp_out, int64_t* count) {
+    int rc = DESC_OK;
+    const int64_t n = dp->n, m = dp->m;
+    if (n <= 0) return fail(DESC_ERR_INVALID, "empty graph");
+    DevM D;
+    unsigned long long* d_key;
+    int32_t* d_comp;
+    uint8_t* d_mark;
+    if ((rc = D.alloc(&d_key, m)) || (rc = D.alloc(&d_comp, n)) || (rc = D.alloc(&d_mark, m))) return rc;
+    if (m) {                                                          // all keys equal: the edge index decides, any forest will do
+        DESC_HIP(hipMemsetAsync(d_key, 0, sizeof(unsigned long long) * m, 0));
+        DESC_HIP(hipMemsetAsync(d_mark, 0, m, 0));
+    }
+    if ((rc = boruvka_rounds(dp, d_key, d_comp, d_mark, D))) return rc;
+    DESC_HIP(hipGetLastError());
+    DESC_HIP(hipMemcpy(comp_out, d_comp, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    hvec<uint8_t> seen((size_t)n, 0);
+    int64_t c = 0;
+    for (int64_t v = 0; v < n; ++v) {
+        const int32_t l = comp_out[v];
+        if (l < 0 || l >= n) return fail(DESC_ERR_STATE, "component labelling: label %d out of range", (int)l);
+        if (!seen[l]) { seen[l] = 1; ++c; }
+    }
+    *count = c;
     return DESC_OK;
 }
 

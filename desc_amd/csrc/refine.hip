@@ -413,6 +413,14 @@ int laa_step(LaaSolver& L, double* score_out) {
     return DESC_OK;
 }
 
+void laa_set_qq(LaaSolver& L, const double* d_blocks) {
+    if (L.m) hipLaunchKernelGGL(k_r2q, dim3(L.egrid), dim3(256), 0, 0, d_blocks, L.d_QQ, L.m, 0);
+}
+
+void laa_edge_log(LaaSolver& L) {
+    if (L.m) hipLaunchKernelGGL(k_edge_log, dim3(L.egrid), dim3(256), 0, 0, L.d_Q, L.d_QQ, L.dp->d_ii, L.dp->d_jj, L.d_B, L.m);
+}
+
 void laa_weights(LaaSolver& L, const double* d_x, double thresh) {
     if (L.m) hipLaunchKernelGGL(k_weights, dim3(L.egrid), dim3(256), 0, 0, d_x, L.d_w, L.m, thresh, 1e4, 1e-4);    // DESC.m:280-281, MPLS.m:211-212
 }

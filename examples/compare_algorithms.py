@@ -5,10 +5,11 @@ Same model (Uniform_Topology n, p, q, sigma, 'uniform'; the demo's defaults n = 
 parameter structs (:25-46), same calls in the same order, rotations aligned with Rotation_Alignment (:75-82) and tabulated (:85-99).
 The default table has four rows: Spectral, CEMP+GCW (the composition CEMP() -> GCW()), DESC_init and DESC.  ``--full`` /
 ``run(full=True)`` adds the demo's MPLS call (:59) with its MPLS_parameters (:32-36) -- the rows CEMP+MST and MPLS -- and takes
-CEMP+GCW from the reference's own CEMP_GCW() (weights 1/(SVec + 1e-8), CEMP_GCW.m:144): six rows.  The IRLS-GM and IRLS-L0.5 rows
-(third-party L1 / L_1/2 solvers) are left out.
+CEMP+GCW from the reference's own CEMP_GCW() (weights 1/(SVec + 1e-8), CEMP_GCW.m:144): six rows.  ``--irls`` / ``run(irls=True)``
+adds the demo's IRLS_GM and IRLS_L12 calls (:68-69) -- the rows IRLS-GM and IRLS-L0.5; with both switches the table has the demo's
+eight rows in its order (:88-99).
 
-    python examples/compare_algorithms.py [--n 200] [--p 0.5] [--q 0.2] [--sigma 0.1] [--seed 0] [--full]
+    python examples/compare_algorithms.py [--n 200] [--p 0.5] [--q 0.2] [--sigma 0.1] [--seed 0] [--full] [--irls]
 """
 import argparse
 import os
@@ -18,10 +19,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import numpy as np  # noqa: E402
 
-from desc_amd import CEMP, CEMP_GCW, DESC, GCW, MPLS, ConstantStepSize, Rotation_Alignment, Spectral, Uniform_Topology  # noqa: E402
+from desc_amd import (CEMP, CEMP_GCW, DESC, GCW, IRLS_GM, IRLS_L12, MPLS, ConstantStepSize, Rotation_Alignment, Spectral,  # noqa: E402
+                      Uniform_Topology)
 
 
-def run(n=200, p=0.5, q=0.2, sigma=0.1, seed=0, verbose=True, full=False):
+def run(n=200, p=0.5, q=0.2, sigma=0.1, seed=0, verbose=True, full=False, irls=False):
     model_out = Uniform_Topology(n, p, q, sigma, "uniform", seed=seed)                  # :13
     Ind, RijMat, ErrVec, R_orig = model_out.Ind, model_out.RijMat, model_out.ErrVec, model_out.R_orig   # :20-23
     CEMP_parameters = dict(max_iter=6, reweighting=[2.0 ** k for k in range(6)], nsample=50, gcw_beta=5)   # :26-29
@@ -39,6 +41,10 @@ def run(n=200, p=0.5, q=0.2, sigma=0.1, seed=0, verbose=True, full=False):
         R_MPLS, R_CEMP_MST = MPLS(Ind, RijMat, dict(CEMP_parameters, verbose=verbose), MPLS_parameters)               # :59
         R_CEMP_GCW_ref = CEMP_GCW(Ind, RijMat, CEMP_parameters)                                                      # :66
         table[1:2] = [("CEMP+MST", R_CEMP_MST), ("CEMP+GCW", R_CEMP_GCW_ref), ("MPLS", R_MPLS)]                      # the demo's six rows (:88-95)
+    if irls:
+        R_IRLS_GM = IRLS_GM(RijMat, Ind)                                                 # :68
+        R_IRLS_L12 = IRLS_L12(RijMat, Ind)                                               # :69
+        table[1:1] = [("IRLS-GM", R_IRLS_GM), ("IRLS-L0.5", R_IRLS_L12)]                 # :90-91
     rows = []
     for name, R in table:
         _, _, mean_error, median_error = Rotation_Alignment(R, R_orig)                   # :75-82
@@ -52,8 +58,9 @@ def main():
     ap.add_argument("--q", type=float, default=0.2); ap.add_argument("--sigma", type=float, default=0.1)
     ap.add_argument("--seed", type=int, default=0); ap.add_argument("--quiet", action="store_true")
     ap.add_argument("--full", action="store_true", help="add the CEMP+MST, MPLS and reference CEMP+GCW rows")
+    ap.add_argument("--irls", action="store_true", help="add the IRLS-GM and IRLS-L0.5 rows")
     a = ap.parse_args()
-    rows, extra = run(a.n, a.p, a.q, a.sigma, a.seed, verbose=not a.quiet, full=a.full)
+    rows, extra = run(a.n, a.p, a.q, a.sigma, a.seed, verbose=not a.quiet, full=a.full, irls=a.irls)
     print("\nResults =\n")                                                              # :85-99
     print("    %-16s %-12s %-12s" % ("Algorithms", "MeanError", "MedianError"))
     for name, me, md in rows:

@@ -391,6 +391,63 @@ int desc_mpls_run(const desc_problem* prob, const desc_mpls_params* params, int3
 int desc_mpls_run_dev(const desc_device_problem* dp, const desc_mpls_params* params, double* R_est, double* R_init,
                       double* s_vec_out, desc_mpls_info* info);
 
+/* ------------------------------------------------------------- IRLS_GM / IRLS_L12 -- */
+/* R = IRLS_GM(RijMat, Ind) / IRLS_L12(RijMat, Ind) -- Algorithms/IRLS_GM.m, IRLS_L12.m (Chatterjee & Govindu).  Five stages:
+ *   1. RR = permute(RijMat, [2,1,3]), I = Ind' (:52-53).
+ *   2. the largest connected component (:65-67) of the graph on nodes 1..n = max(Ind(:)) (a node id no edge touches is a component of
+ *      its own).  Of several of maximal size the one holding the smallest node id is taken -- an assumption about how graphconncomp
+ *      numbers undirected components, which does not matter when the sizes differ.  Its nodes are renumbered in increasing id order,
+ *      its edges keep their order; every node outside it gets NaN in R_out (:94).  With R_init, the component's rows are used (the
+ *      reference passes the full-size Rinit to the sub-problem unindexed and fails there).
+ *   3. per edge, all of them (:82-93): det(RR) <= 0 is an error; an error too when ALL three singular values deviate from 1 by >= 0.1
+ *      (MATLAB's `if` on a vector), a warning when all three deviate by >= 0.01 (the count is printed to stderr and returned);
+ *      then RR = U * round(S) * V'.  The error names the smallest failing row of the caller's Ind (1-based, via `order`).
+ *   4. BoxMedianSO3Graph(RR, I, Rinit, max_iter_l1) (Utils/BoxMedianSO3Graph.m): Q from R_init, or from the spanning-tree pass
+ *      (:79-114) over the edges in the caller's row order; then while score >= 1e-3 (with L1Step = 2 the reference's L1Step branch
+ *      never fires; it is restated), per coordinate an l1-magic primal-dual solve of min |B(:,c) - A x|_1 (l1decode_pd, :245-360)
+ *      with pdtol = eps and at most L1Step steps; score = max_v |W_v| (:173); R_l1 = real(q2R(Q)).
+ *   5. RobustMeanSO3Graph (GM, weights SIGMA/(|E|^2 + SIGMA^2), SIGMA in radians) or L12 (weights min(|E|^-0.75, 1e4)) from
+ *      Q = R2Q(R_l1): Weighted_LAA steps with E = A W - B of the solved W, while score = sum |W_v| / n > 1e-3 (:130-176).
+ * Deviations: l1decode_pd's dense LU of H11p = A' diag(sigx) A is a Jacobi-preconditioned CG on the device (one weight vector per
+ * coordinate, |r| <= 1e-13 |b|); LAPACK's rcond test (hcond < 1e-14, "Matrix ill-conditioned") becomes a CG breakdown -- a
+ * non-finite value or p'Hp <= 0 -- and a solve that stops at its iteration cap is counted in cg_unconverged and warned about.  The
+ * weighted least squares of stage 5 are the normal equations by PCG, as desc_refine_run.  Input rules as elsewhere: 1-based,
+ * Ind(:,1) < Ind(:,2), no duplicate edge (the problem's edges sorted by (i, j); `order` gives the caller's row of each).
+ * R_out: n*9 doubles; R_l1 (nullable): the stage-4 estimate, n*9 doubles, NaN outside the component. */
+enum { DESC_IRLS_GM = 0, DESC_IRLS_L12 = 1 };
+typedef struct desc_irls_params {
+    int32_t mode;             /* DESC_IRLS_GM (RobustMeanSO3Graph) or DESC_IRLS_L12 (L12)                */
+    int32_t max_iter_l1;      /* MaxIterations(1); <= 0: 10                              IRLS_GM.m:59 */
+    int32_t max_iter_irls;    /* MaxIterations(2); <= 0: 100                             IRLS_GM.m:59 */
+    int32_t verbose;          /* print the reference's fprintf / disp lines and early-return messages     */
+    double sigma_deg;         /* SIGMA in degrees; <= 0: 5 (GM only)                     IRLS_GM.m:58 */
+    const double* R_init;     /* nullable: Rinit, n*9 doubles (3x3xn, column-major)      IRLS_GM.m:57 */
+    const int32_t* order;     /* nullable: order[e] = the caller's 0-based row of edge e (a permutation of 0..m-1): the
+                                 row order of the tree pass and of the error message; NULL = the edge order itself  */
+} desc_irls_params;
+typedef struct desc_irls_info {
+    int64_t comp_nodes;       /* nodes and edges of the largest component                               */
+    int64_t comp_edges;
+    int32_t l1_iters;         /* BoxMedianSO3Graph iterations                                           */
+    int32_t irls_iters;       /* RobustMeanSO3Graph / L12 iterations                                    */
+    double  l1_score;         /* last L1 score: max_v |W_v|                                             */
+    double  irls_score;       /* last IRLS score: sum_v |W_v| / n                                       */
+    int32_t pd_steps;         /* primal-dual steps taken, all coordinates and iterations                */
+    int32_t pd_ill;           /* l1decode_pd returns "Matrix ill-conditioned" (a CG breakdown here)     */
+    int32_t pd_stuck;         /* l1decode_pd returns "Stuck backtracking"                               */
+    int32_t warned_edges;     /* edges whose three singular values all deviate by >= 0.01               */
+    int32_t cg_iters_l1;      /* CG steps of the batched Newton solves, each rounded up to the probe interval 5 */
+    int32_t cg_iters_irls;    /* CG steps of the Weighted_LAA solves, each rounded up to laa_step's probe interval 25 */
+    int32_t cg_unconverged;   /* solves (both stages) that stopped at the CG iteration cap              */
+    int32_t pd_solves;        /* batched Newton solves of the L1 stage (one CG for the three coordinates) */
+    double  cg_residual;      /* largest relative residual |r|/|b| left by any solve                    */
+    double  ms_project, ms_components, ms_tree, ms_l1, ms_l1_pcg, ms_irls, ms_total;
+} desc_irls_info;
+int desc_irls_run(const desc_problem* prob, const desc_irls_params* params, int32_t device, double* R_out, double* R_l1,
+                  desc_irls_info* info);
+int desc_irls_run_dev(const desc_device_problem* dp, const desc_irls_params* params, double* R_out, double* R_l1,
+                      desc_irls_info* info);
+
 /* One-shot: what the MEX shim calls.  Builds the structure (p->build_where),
  * uploads, runs, downloads, frees. */
 int desc_pgd_solve(const desc_problem* prob, const desc_params* p, desc_result* r);

@@ -9,6 +9,9 @@
  *   [R_est, R_init] = desc_amd_mex('mpls', Ind0, RijMat, cemp_beta, cemp_max_iter, nsample, seed,
  *                                  stop_threshold, max_iter, beta, tau, alpha)      desc_mpls_run, MPLS.m:31-257
  *   R     = desc_amd_mex('cemp_gcw', Ind0, RijMat, beta, max_iter, nsample, seed)   CEMP_GCW.m: CEMP, weights 1/(SVec + 1e-8), spectral
+ *   [R, R_l1] = desc_amd_mex('irls_gm' | 'irls_l12', Ind0, RijMat, order0, max_iter_l1, max_iter_irls, sigma_deg [, Rinit])
+ *                                                      desc_irls_run, IRLS_GM.m / IRLS_L12.m; order0: the caller's 0-based row of
+ *                                                      every sorted edge (int32, m); NaN outside the largest component
  *
  * Ind0: m x 2 int32, 0-based, sorted by (i,j); RijMat: 3 x 3 x m double (passed through);
  * R: 3 x 3 x n double.  Cannot be compiled in the build container (no mex.h):
@@ -54,7 +57,7 @@ static int at_exit_registered = 0;
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (!at_exit_registered) { mexAtExit(release_parked_blocks); at_exit_registered = 1; }
     char cmd[32];
-    if (nrhs < 3 || mxGetString(prhs[0], cmd, sizeof cmd)) mexErrMsgIdAndTxt("desc_amd:cmd", "first argument: 'spectral' | 'gcw' | 'cemp' | 'refine' | 'desc' | 'mpls' | 'cemp_gcw'");
+    if (nrhs < 3 || mxGetString(prhs[0], cmd, sizeof cmd)) mexErrMsgIdAndTxt("desc_amd:cmd", "first argument: 'spectral' | 'gcw' | 'cemp' | 'refine' | 'desc' | 'mpls' | 'cemp_gcw' | 'irls_gm' | 'irls_l12'");
     desc_problem prob;
     problem_from(prhs[1], prhs[2], &prob);
     int rc = DESC_OK;
@@ -88,6 +91,24 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         mxArray* R_init = rotations(prob.n);
         rc = desc_mpls_run(&prob, &mp, 0, mxGetPr(plhs[0]), mxGetPr(R_init), NULL, NULL);
         if (nlhs > 1) plhs[1] = R_init;
+    } else if (!strcmp(cmd, "irls_gm") || !strcmp(cmd, "irls_l12")) {
+        if (nrhs < 7 || !mxIsInt32(prhs[3]) || mxGetNumberOfElements(prhs[3]) != (mwSize)prob.m)
+            mexErrMsgIdAndTxt("desc_amd:irls", "usage: ('irls_gm' | 'irls_l12', Ind0, RijMat, order0 (int32, m), max_iter_l1, max_iter_irls, sigma_deg [, Rinit])");
+        desc_irls_params ip; memset(&ip, 0, sizeof ip);
+        ip.mode = !strcmp(cmd, "irls_gm") ? DESC_IRLS_GM : DESC_IRLS_L12;
+        ip.order = (const int32_t*)mxGetData(prhs[3]);
+        ip.max_iter_l1 = (int32_t)mxGetScalar(prhs[4]); ip.max_iter_irls = (int32_t)mxGetScalar(prhs[5]);       /* IRLS_GM.m:59 */
+        ip.sigma_deg = mxGetScalar(prhs[6]);                                                                      /* :58 */
+        if (nrhs > 7 && !mxIsEmpty(prhs[7])) {                                                                    /* :57 */
+            if (!mxIsDouble(prhs[7]) || mxGetNumberOfElements(prhs[7]) != (mwSize)(9 * prob.n))
+                mexErrMsgIdAndTxt("desc_amd:irls", "Rinit must be 3 x 3 x n double");
+            ip.R_init = mxGetPr(prhs[7]);
+        }
+        ip.verbose = 1;
+        plhs[0] = rotations(prob.n);
+        mxArray* R_l1 = rotations(prob.n);
+        rc = desc_irls_run(&prob, &ip, 0, mxGetPr(plhs[0]), mxGetPr(R_l1), NULL);
+        if (nlhs > 1) plhs[1] = R_l1;                                 /* the library writes NAN (math.h) outside the component */
     } else if (!strcmp(cmd, "cemp_gcw")) {
         if (nrhs < 7) mexErrMsgIdAndTxt("desc_amd:cemp_gcw", "usage: ('cemp_gcw', Ind0, RijMat, beta, max_iter, nsample, seed)");
         mxArray* S = mxCreateDoubleMatrix(1, prob.m, mxREAL);
