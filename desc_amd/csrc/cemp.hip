@@ -334,14 +334,6 @@ int env_int_c(const char* name, int dflt) { const char* v = std::getenv(name); r
 
 }  // namespace
 
-template <class T> int CempState::alloc(T** out, size_t count) {
-    void* q = nullptr;
-    DESC_HIP(dev_alloc(&q, sizeof(T) * (count ? count : 1)));
-    blocks.push_back(q); *out = (T*)q;
-    return DESC_OK;
-}
-CempState::~CempState() { for (void* q : blocks) dev_free(q); }
-
 int cemp_build(const desc_device_problem* dp, int32_t nsample, uint64_t seed, bool need_poe, CempState& st) {
     int rc = DESC_OK;
     const int64_t m = dp->m, n = dp->n;
@@ -466,12 +458,8 @@ extern "C" int desc_cemp_run(const desc_problem* prob, const double* beta, int32
                              uint64_t seed, int32_t device, double* s_vec, double* ms_total) {
     if (!prob || !s_vec || !beta) return fail(DESC_ERR_INVALID, "NULL argument");
     auto t0 = std::chrono::steady_clock::now();
-    desc_device_problem* dp = nullptr;
-    int rc = desc_problem_upload(prob, device, &dp);
-    if (rc) return rc;
-    rc = desc_cemp_run_dev(dp, beta, n_beta, max_iter, nsample, seed, s_vec, nullptr);
-    desc_problem_free(dp);
-    if (ms_total) *ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const int rc = with_uploaded(prob, device, [&](const desc_device_problem* dp) { return desc_cemp_run_dev(dp, beta, n_beta, max_iter, nsample, seed, s_vec, nullptr); });
+    if (ms_total) *ms_total = ms_since(t0);
     return rc;
 }
 
@@ -489,7 +477,7 @@ extern "C" int desc_cemp_run_dev(const desc_device_problem* dp, const double* be
     const double* d_svec = dp->m ? cemp_svec(st) : nullptr;
     DESC_HIP(hipDeviceSynchronize());
     if (dp->m) DESC_HIP(hipMemcpy(s_vec, d_svec, sizeof(double) * dp->m, hipMemcpyDeviceToHost));
-    if (ms_total) *ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (ms_total) *ms_total = ms_since(t0);
     return DESC_OK;
     });
 }

@@ -1,12 +1,11 @@
 // Internal: CEMP's sampled cycles and their S0 kept on the device between the two steps of Algorithms/CEMP.m (build + S0Mat :44-103,
 // rounds :107-128), so that MPLS (Algorithms/MPLS.m:65-158, the same lines) can re-use them in its loop (:223-237).  Kernels in cemp.hip.
 #pragma once
-#include "common.h"
+#include "device_utils.h"
 
 namespace desc {
 
-struct CempState {
-    hvec<void*> blocks;                                   // device blocks owned by the state
+struct CempState : DevArena {                             // owns its device blocks
     int64_t n = 0, m = 0, mp = 0, mc = 0;                 // nodes, edges, edges with cycles, mp * nsample
     int32_t nsample = 0, max_deg = 0;
     bool tiles = false;                                   // the rounds run on the CSR-aligned copy in tiles (k_cemp_round_tile)
@@ -20,8 +19,6 @@ struct CempState {
     double* d_out = nullptr;                              // SVec edge-indexed (tile path)
     int BI = 1, JB = 32, n_iband = 1, n_jblock = 1, g = 1;
     size_t lds = 0;
-    ~CempState();
-    template <class T> int alloc(T** out, size_t count);
 };
 
 // CEMP.m:44-103: samples, S0Mat and the initial SVec.  need_poe: also build d_poe whenever some edge has no cycle (MPLS reads it on both

@@ -1,6 +1,8 @@
 // Internal declarations shared by the host-side translation units of libdesc_amd.so.
 #pragma once
+#include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -31,6 +33,13 @@ inline uint64_t mix64(uint64_t x) {
 inline uint64_t sample_key(uint64_t seed, uint64_t edge, uint64_t k) {
     uint64_t a = mix64(seed ^ ((edge + 1) * 0x9E3779B97F4A7C15ull));
     return mix64(a ^ ((k + 1) * 0xD1B54A32D192ED03ull));
+}
+
+// milliseconds of host time since t
+inline double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
+// blocks of a grid-stride launch over `count` items, per_block of them to a block: at least one, at most cap
+inline int grid_for(int64_t count, int64_t cap, int64_t per_block = 256) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(cap, (count + per_block - 1) / per_block));
 }
 
 }  // namespace desc
@@ -149,5 +158,15 @@ int no_throw(const char* what, F&& f) noexcept {
     catch (const std::bad_alloc&) { return fail(DESC_ERR_INVALID, "%s: out of host memory", what); }
     catch (const std::exception& e) { return fail(DESC_ERR_INVALID, "%s: %s", what, e.what()); }
     catch (...) { return fail(DESC_ERR_INVALID, "%s: unknown C++ exception", what); }
+}
+// The desc_*_run entry points: upload the problem, run(dp) -- the matching desc_*_run_dev -- and free the device problem again.
+template <class F>
+int with_uploaded(const desc_problem* prob, int32_t device, F&& run) {
+    desc_device_problem* dp = nullptr;
+    int rc = desc_problem_upload(prob, device, &dp);
+    if (rc) return rc;
+    rc = run(dp);
+    desc_problem_free(dp);
+    return rc;
 }
 }  // namespace desc

@@ -25,6 +25,22 @@ void dev_free_idle(void* p);                                   // the same witho
 hipError_t stream_acquire(hipStream_t* out);
 void stream_release(hipStream_t s);
 
+// Device blocks that live as long as their owner: typed alloc (a count of 0 still gives a valid block), all freed on destruction.
+struct DevArena {
+    hvec<void*> blocks;
+    DevArena() = default;
+    DevArena(const DevArena&) = delete;
+    DevArena& operator=(const DevArena&) = delete;
+    ~DevArena() { release(); }
+    void release() { for (void* q : blocks) dev_free(q); blocks.clear(); }
+    template <class T> int alloc(T** out, size_t count) {
+        void* q = nullptr;
+        DESC_HIP(dev_alloc(&q, sizeof(T) * (count ? count : 1)));
+        blocks.push_back(q); *out = (T*)q;
+        return DESC_OK;
+    }
+};
+
 // One DPP-moved copy of a double (two 32-bit v_mov_b32_dpp).  All four controls used
 // here are permutations of the full wave, so every lane is written and no `old` value
 // has to be preserved (mov_dpp leaves it undefined: no extra register copy).
@@ -96,6 +112,24 @@ __device__ __forceinline__ double group_sum(double v) {
     if (G >= 32) v = swap16_sum_f64(v);
     if (G >= 64) v = swap32_sum_f64(v);
     return v;
+}
+
+// Reduction of K values per thread over a workgroup of 256 into out[K]; OP: 0 sum, 1 min, 2 max (fmin / fmax skip NaN, as MATLAB).
+// The tree (strides 128, 64, ... 1, sh[t] = sh[t] OP sh[t + stride]) is fixed: every sum that goes through it keeps its bits.
+template <int K, int OP>
+__device__ __forceinline__ void block_reduce(double (&v)[K], double* out) {
+    __shared__ double sh[K][256];
+    for (int k = 0; k < K; ++k) sh[k][threadIdx.x] = v[k];
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st)
+            for (int k = 0; k < K; ++k) {
+                const double a = sh[k][threadIdx.x], b = sh[k][threadIdx.x + st];
+                sh[k][threadIdx.x] = OP == 1 ? fmin(a, b) : (OP == 2 ? fmax(a, b) : a + b);
+            }
+        __syncthreads();
+    }
+    if ((int)threadIdx.x < K) out[threadIdx.x] = sh[threadIdx.x][0];
 }
 
 // number of set predicate lanes in this lane's group of G

@@ -4,8 +4,8 @@
 //   :82-93    per-edge checks and projection RR = U round(S) V' (k_irls_project: 3x3 one-sided Jacobi SVD)
 //   :94-96    BoxMedianSO3Graph (Utils/BoxMedianSO3Graph.m): spanning-tree start (:79-114, host pass in the caller's row order),
 //             L1 loop (:138-187) with three l1decode_pd solves per iteration (:245-360), batched here: all state in HBM as m x 3
-//             edge and n x 3 node arrays, one Jacobi-PCG for the three Newton systems A' diag(sigx_c) A dx_c = w1p_c
-//   :96       RobustMeanSO3Graph (GM) or L12 (L 1/2): Weighted_LAA steps (refine.hip, laa.h), then residual-and-weight kernel
+//             edge and n x 3 node arrays, the averaging core's Jacobi-PCG (laa_pcg) for the three Newton systems A' diag(sigx_c) A dx_c = w1p_c
+//   :96       RobustMeanSO3Graph (GM) or L12 (L 1/2): Weighted_LAA steps (laa.h, laa.hip), then residual-and-weight kernel
 // Deviations from the reference, by necessity:
 //   * graphconncomp's component numbering cannot be checked here: a tie of maximal sizes goes to the component holding the smallest
 //     node id (assumed to be graphconncomp's first); with distinct sizes nothing depends on it.
@@ -17,13 +17,11 @@
 //     read-back per backtracking trial; the CG keeps its scalars on the device and is probed every PD_PROBE = 5 steps.
 // Reductions are fixed-order partials (no float atomics): results are bitwise reproducible from run to run.
 #include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
-#include "device_utils.h"
 #include "laa.h"
 
 namespace desc {
@@ -33,8 +31,6 @@ constexpr int RG = 256;            // blocks of the partial-reduction kernels: p
 // The Newton-system CG is probed every PD_PROBE steps (one dot and one read-back): the reported step count is the solve's true count
 // rounded up to a multiple of PD_PROBE.  At C4 a CG step costs ~0.1 ms and a probe a few microseconds.
 constexpr int PD_PROBE = 5;
-
-double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
 
 // ---- stage 3: per-edge checks and projection ---------------------------------------------------------------------------------------
 // one-sided Jacobi SVD of a 3x3 column-major matrix: A V = U S; a[] ends as U S (columns), v[] as V; s sorted descending
@@ -111,33 +107,12 @@ __global__ __launch_bounds__(256) void k_irls_project(const double* rij, const i
 // ---- stage 4: l1decode_pd, three coordinates batched ---------------------------------------------------------------------------------
 struct Pd3 { double tau[3], s[3], ymax[3]; int act[3]; };      // per-coordinate scalars of one launch (act: 1 = this coordinate takes part)
 
-// block reduction of K values per thread into out[K] (fixed tree order); OP: 0 sum, 1 min, 2 max (fmin / fmax skip NaN, as MATLAB)
-template <int K, int OP>
-__device__ __forceinline__ void block_reduce_store(double (&v)[K], double* out) {
-    __shared__ double sh[K][256];
-    for (int k = 0; k < K; ++k) sh[k][threadIdx.x] = v[k];
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st)
-            for (int k = 0; k < K; ++k) {
-                const double a = sh[k][threadIdx.x], b = sh[k][threadIdx.x + st];
-                sh[k][threadIdx.x] = OP == 1 ? fmin(a, b) : (OP == 2 ? fmax(a, b) : a + b);
-            }
-        __syncthreads();
-    }
-    if ((int)threadIdx.x < K) out[threadIdx.x] = sh[threadIdx.x][0];
-}
-
 // max |y - Ax| with Ax = 0 (:271): MATLAB's max, per coordinate
 __global__ __launch_bounds__(256) void k_pd_absmax(const double* y, int64_t m, double* part) {
     double v[3] = {0, 0, 0};
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256)
         for (int c = 0; c < 3; ++c) v[c] = fmax(v[c], fabs(y[3 * e + c]));
-    __shared__ double sh[3][256];
-    for (int c = 0; c < 3; ++c) sh[c][threadIdx.x] = v[c];
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) { if ((int)threadIdx.x < st) for (int c = 0; c < 3; ++c) sh[c][threadIdx.x] = fmax(sh[c][threadIdx.x], sh[c][threadIdx.x + st]); __syncthreads(); }
-    if (threadIdx.x < 3) part[3 * blockIdx.x + threadIdx.x] = sh[threadIdx.x][0];
+    block_reduce<3, 2>(v, part + 3 * blockIdx.x);
 }
 // :268-276 with x0 = 0: Ax = 0, u, fu1, fu2, lamu1, lamu2; ev = lamu1 - lamu2 (for Atv, :278)
 __global__ __launch_bounds__(256) void k_pd_init(const double* y, int64_t m, Pd3 a, double* Ax, double* u, double* f1, double* f2, double* l1,
@@ -217,7 +192,7 @@ __global__ __launch_bounds__(256) void k_pd_dir(const int32_t* ii, const int32_t
             if ((-adx - dd) > 0) mn[3 + c] = fmin(mn[3 + c], -g2 / (-adx - dd));
         }
     }
-    block_reduce_store<6, 1>(mn, part + 6 * blockIdx.x);
+    block_reduce<6, 1>(mn, part + 6 * blockIdx.x);
 }
 // |[rdual; rcent]|^2 per coordinate as block partials [RG][3] (:280-283, :334-336, :347-349).  TRIAL: of the trial point at step a.s
 // (state + s * direction); else of the state itself.  rdual = gradf0 + [Atv; -lamu1 - lamu2], rcent = [-lamu1.*fu1; -lamu2.*fu2] - 1/tau.
@@ -246,7 +221,7 @@ __global__ __launch_bounds__(256) void k_pd_resid(int64_t m, int n, Pd3 a, const
             acc[c] += t * t;
         }
     }
-    block_reduce_store<3, 0>(acc, part + 3 * blockIdx.x);
+    block_reduce<3, 0>(acc, part + 3 * blockIdx.x);
 }
 // the accepted step (:340-344) for the coordinates with act set, then fu1'*lamu1 and fu2'*lamu2 of the new point as partials [RG][6]
 __global__ __launch_bounds__(256) void k_pd_accept(int64_t m, int n, Pd3 a, const double* y, double* Ax, double* u, double* l1, double* l2,
@@ -267,115 +242,26 @@ __global__ __launch_bounds__(256) void k_pd_accept(int64_t m, int n, Pd3 a, cons
     for (int v = blockIdx.x * 256 + threadIdx.x; v < n; v += gridDim.x * 256)
         for (int c = 0; c < 3; ++c)
             if (a.act[c]) { x[3 * v + c] = x[3 * v + c] + a.s[c] * dx[3 * v + c]; Atv[3 * v + c] = Atv[3 * v + c] + a.s[c] * Atdv[3 * v + c]; }
-    block_reduce_store<6, 0>(acc, part + 6 * blockIdx.x);
-}
-
-// ---- Jacobi-PCG with one weight vector per coordinate (weights not squared): A' diag(w_c) A x_c = b_c, node 0 grounded ----------------
-struct Cg3 { double rz[3], rz_new[3], pq[3], bnorm[3], rnorm[3]; int bad[3], pad; };
-
-__device__ __forceinline__ bool cg_breaks(double pq, double rz) { return !isfinite(pq) || !isfinite(rz) || (pq <= 0.0 && rz > 0.0); }
-
-// q_v = sum_t w_e,c (p_v - p_u) for v != 0 (next to refine.hip's k_lap, which squares one weight vector)
-__global__ __launch_bounds__(256) void k_lap3w(const int32_t* rowptr, const int32_t* adj, const int32_t* eid, const double* w, const double* p,
-                                               double* q, int n) {
-    const int l16 = threadIdx.x & 15;
-    const int row0 = (blockIdx.x * 256 + threadIdx.x) >> 4, nrows = (gridDim.x * 256) >> 4;
-    for (int vb = row0 - (row0 % 4); vb < n; vb += nrows) {
-        const int v = vb + (row0 % 4);
-        double a0 = 0, a1 = 0, a2 = 0;
-        if (v < n && v > 0) {
-            const double p0 = p[3 * v], p1 = p[3 * v + 1], p2 = p[3 * v + 2];
-            for (int t = rowptr[v] + l16; t < rowptr[v + 1]; t += 16) {
-                const int u = adj[t];
-                const int64_t e = eid[t];
-                a0 += w[3 * e] * (p0 - p[3 * u]); a1 += w[3 * e + 1] * (p1 - p[3 * u + 1]); a2 += w[3 * e + 2] * (p2 - p[3 * u + 2]);
-            }
-        }
-        a0 = group16_sum(a0); a1 = group16_sum(a1); a2 = group16_sum(a2);
-        if (v < n && l16 == 0) { q[3 * v] = a0; q[3 * v + 1] = a1; q[3 * v + 2] = a2; }
-    }
-}
-// one workgroup: column-wise dot products of two n x 3 arrays (fixed order)
-__global__ __launch_bounds__(256) void k_cg3_dot(const double* a, const double* b, int n, double* out3) {
-    double s[3] = {0, 0, 0};
-    for (int v = threadIdx.x; v < n; v += 256) for (int c = 0; c < 3; ++c) s[c] += a[3 * v + c] * b[3 * v + c];
-    block_reduce_store<3, 0>(s, out3);
-}
-__global__ void k_cg3_init(Cg3* sc, const double* rhs, const double* diag, double* x, double* r, double* z, double* p, int n) {
-    if (blockIdx.x == 0 && threadIdx.x < 3) sc->bad[threadIdx.x] = 0;
-    for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x)
-        for (int c = 0; c < 3; ++c) {
-            const double rv = v > 0 ? rhs[3 * v + c] : 0.0;
-            const double zv = (v > 0 && diag[3 * v + c] > 0) ? rv / diag[3 * v + c] : 0.0;
-            x[3 * v + c] = 0.0; r[3 * v + c] = rv; z[3 * v + c] = zv; p[3 * v + c] = zv;
-        }
-}
-// alpha = rz/pq (0 once the coordinate broke down) ; x += alpha p ; r -= alpha q ; z = r/diag
-__global__ void k_cg3_update(Cg3* sc, const double* diag, const double* p, const double* q, double* x, double* r, double* z, int n) {
-    double al[3];
-    for (int c = 0; c < 3; ++c) {
-        const bool brk = sc->bad[c] || cg_breaks(sc->pq[c], sc->rz[c]);
-        al[c] = (!brk && sc->pq[c] > 0) ? sc->rz[c] / sc->pq[c] : 0.0;
-    }
-    __syncthreads();
-    if (blockIdx.x == 0 && threadIdx.x < 3 && cg_breaks(sc->pq[threadIdx.x], sc->rz[threadIdx.x])) sc->bad[threadIdx.x] = 1;
-    for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x)
-        for (int c = 0; c < 3; ++c) {
-            const double xv = x[3 * v + c] + al[c] * p[3 * v + c];
-            const double rv = r[3 * v + c] - al[c] * q[3 * v + c];
-            x[3 * v + c] = xv; r[3 * v + c] = rv;
-            z[3 * v + c] = (v > 0 && diag[3 * v + c] > 0) ? rv / diag[3 * v + c] : 0.0;
-        }
-}
-__global__ void k_cg3_dir(const Cg3* sc, const double* z, double* p, int n) {
-    double be[3];
-    for (int c = 0; c < 3; ++c) be[c] = sc->rz[c] > 0 ? sc->rz_new[c] / sc->rz[c] : 0.0;
-    for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x)
-        for (int c = 0; c < 3; ++c) p[3 * v + c] = z[3 * v + c] + be[c] * p[3 * v + c];
-}
-__global__ void k_cg3_roll(Cg3* sc) {
-    if (threadIdx.x < 3) {
-        if (!isfinite(sc->rz_new[threadIdx.x])) sc->bad[threadIdx.x] = 1;
-        sc->rz[threadIdx.x] = sc->rz_new[threadIdx.x];
-    }
+    block_reduce<6, 0>(acc, part + 6 * blockIdx.x);
 }
 
 // BoxMedianSO3Graph.m:172-185: score partial max_v |W_v| (v >= 1), exp map (NaN -> 0), Q <- Q * W.  x row 0 is 0.
 __global__ __launch_bounds__(256) void k_l1_node_update(const double* x, Quat* Q, int n, double* part) {
     double sc[1] = {0.0};
     for (int v = blockIdx.x * 256 + threadIdx.x; v < n; v += gridDim.x * 256) {
-        const double t1 = x[3 * v], t2 = x[3 * v + 1], t3 = x[3 * v + 2];
-        const double theta = sqrt(t1 * t1 + t2 * t2 + t3 * t3);
+        double theta;
+        const Quat w = qexp(x[3 * v], x[3 * v + 1], x[3 * v + 2], &theta);
         if (v > 0) sc[0] = fmax(sc[0], theta);
-        double wa = cos(theta / 2.0);
-        const double f = sin(theta / 2.0) / theta;
-        double wx = t1 * f, wy = t2 * f, wz = t3 * f;
-        if (isnan(wa)) wa = 0.0;
-        if (isnan(wx)) wx = 0.0;
-        if (isnan(wy)) wy = 0.0;
-        if (isnan(wz)) wz = 0.0;
-        const Quat q = Q[v];
-        Quat o;
-        o.a = q.a * wa - (q.x * wx + q.y * wy + q.z * wz);
-        o.x = q.a * wx + wa * q.x + (q.y * wz - q.z * wy);
-        o.y = q.a * wy + wa * q.y + (q.z * wx - q.x * wz);
-        o.z = q.a * wz + wa * q.z + (q.x * wy - q.y * wx);
-        Q[v] = o;
+        Q[v] = qmul(Q[v], w);
     }
-    block_reduce_store<1, 2>(sc, part + blockIdx.x);
+    block_reduce<1, 2>(sc, part + blockIdx.x);
 }
 
 // ---- stage 5: residuals and weights (RobustMeanSO3Graph.m:169-170, L12.m:169-171) from the solved W (before the exp map) --------------
 __global__ __launch_bounds__(256) void k_irls_weights(const double* x, const double* B, const int32_t* ii, const int32_t* jj, int64_t m, int mode,
                                                       double sigma, double* w) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256) {
-        const int i = ii[e], j = jj[e];
-        double s = 0.0;
-        for (int c = 0; c < 3; ++c) {
-            const double ax = (j > 0 ? x[3 * j + c] : 0.0) - (i > 0 ? x[3 * i + c] : 0.0);
-            const double d = ax - B[3 * e + c];
-            s += d * d;
-        }
+        const double s = edge_residual_sq(x, B, ii, jj, e);
         double wt;
         if (mode == DESC_IRLS_GM) wt = sigma / (s + sigma * sigma);
         else { wt = 1.0 / pow(sqrt(s), 0.75); if (wt > 1e4) wt = 1e4; }
@@ -395,13 +281,13 @@ struct PdState {
     int64_t n = 0, m = 0;
     int egrid = 1, ngrid = 1, rgrid = 1;
     double *y, *Ax, *u, *f1, *f2, *l1, *l2, *w2, *s1, *s2, *sx, *ev1, *ev2, *Adx, *du, *d1, *d2;     // m x 3
-    double *x, *Atv, *w1p, *dg, *dx, *Atdv, *r, *z, *p, *q;                                          // n x 3
+    double *x, *Atv, *w1p, *dg, *dx, *Atdv;                                                          // n x 3 (the PCG works in L's arrays)
     double* part;
-    Cg3* sc;
     hvec<double> hpart;
     // counters
-    int steps = 0, ill = 0, stuck = 0, solves = 0, cg_total = 0, cg_unconverged = 0;
-    double cg_worst = 0.0, ms_pcg = 0.0;
+    int steps = 0, ill = 0, stuck = 0, solves = 0;
+    CgCount cg;
+    double ms_pcg = 0.0;
     bool verbose = false;
 };
 
@@ -410,12 +296,10 @@ int pd_alloc(PdState& S, LaaSolver& L) {
     S.L = &L; S.n = L.n; S.m = L.m;
     const int64_t m3 = 3 * S.m, n3 = 3 * S.n;
     double** em[] = {&S.y, &S.Ax, &S.u, &S.f1, &S.f2, &S.l1, &S.l2, &S.w2, &S.s1, &S.s2, &S.sx, &S.ev1, &S.ev2, &S.Adx, &S.du, &S.d1, &S.d2};
-    double** nm[] = {&S.x, &S.Atv, &S.w1p, &S.dg, &S.dx, &S.Atdv, &S.r, &S.z, &S.p, &S.q};
+    double** nm[] = {&S.x, &S.Atv, &S.w1p, &S.dg, &S.dx, &S.Atdv};
     for (auto* a : em) if ((rc = L.alloc(a, m3))) return rc;
     for (auto* a : nm) if ((rc = L.alloc(a, n3))) return rc;
-    double* sc = nullptr;
-    if ((rc = L.alloc(&S.part, 6 * RG)) || (rc = L.alloc(&sc, (sizeof(Cg3) + 7) / 8))) return rc;
-    S.sc = (Cg3*)sc;
+    if ((rc = L.alloc(&S.part, 6 * RG))) return rc;
     S.hpart.resize(6 * RG);
     S.egrid = L.egrid; S.ngrid = L.ngrid; S.rgrid = L.rgrid;
     return DESC_OK;
@@ -434,42 +318,11 @@ int read_part(PdState& S, int K, double* out, bool take_min) {
 
 // dx_c = (A' diag(sx_c) A) \ w1p_c for the coordinates in act; bad[c] set on a breakdown
 int pd_pcg(PdState& S, const int act[3], int bad[3]) {
-    const LaaSolver& L = *S.L;
-    const desc_device_problem* dp = L.dp;
-    const int n = (int)S.n;
+    LaaSolver& L = *S.L;
     Pd3 none{}; none.act[0] = none.act[1] = none.act[2] = 1;
-    hipLaunchKernelGGL(k_pd_gather<2>, dim3(S.rgrid), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj_eid, L.d_sgn, S.sx, nullptr, none, S.dg, n);
-    hipLaunchKernelGGL(k_cg3_init, dim3(S.ngrid), dim3(256), 0, 0, S.sc, S.w1p, S.dg, S.dx, S.r, S.z, S.p, n);
-    hipLaunchKernelGGL(k_cg3_dot, dim3(1), dim3(256), 0, 0, S.r, S.z, n, &S.sc->rz[0]);
-    hipLaunchKernelGGL(k_cg3_dot, dim3(1), dim3(256), 0, 0, S.r, S.r, n, &S.sc->bnorm[0]);
-    const int cg_max = (int)std::min<int64_t>(20000, 20 * S.n + 200);
-    Cg3 hs;
-    int k = 0;
-    bool done = false;
-    for (k = 1; k <= cg_max; ++k) {
-        hipLaunchKernelGGL(k_lap3w, dim3(S.rgrid), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj, dp->d_adj_eid, S.sx, S.p, S.q, n);
-        hipLaunchKernelGGL(k_cg3_dot, dim3(1), dim3(256), 0, 0, S.p, S.q, n, &S.sc->pq[0]);
-        hipLaunchKernelGGL(k_cg3_update, dim3(S.ngrid), dim3(256), 0, 0, S.sc, S.dg, S.p, S.q, S.dx, S.r, S.z, n);
-        hipLaunchKernelGGL(k_cg3_dot, dim3(1), dim3(256), 0, 0, S.r, S.z, n, &S.sc->rz_new[0]);
-        hipLaunchKernelGGL(k_cg3_dir, dim3(S.ngrid), dim3(256), 0, 0, S.sc, S.z, S.p, n);
-        hipLaunchKernelGGL(k_cg3_roll, dim3(1), dim3(64), 0, 0, S.sc);
-        if (k % PD_PROBE == 0 || k == cg_max) {                                            // convergence probe: |r| <= 1e-13 |b|
-            hipLaunchKernelGGL(k_cg3_dot, dim3(1), dim3(256), 0, 0, S.r, S.r, n, &S.sc->rnorm[0]);
-            DESC_HIP(hipMemcpy(&hs, S.sc, sizeof hs, hipMemcpyDeviceToHost));
-            done = true;
-            for (int c = 0; c < 3; ++c)
-                if (act[c] && !hs.bad[c] && hs.rnorm[c] > 1e-26 * hs.bnorm[c] && hs.rnorm[c] > 1e-300) done = false;
-            if (done || k == cg_max) break;
-        }
-    }
-    S.cg_total += std::min(k, cg_max);
+    hipLaunchKernelGGL(k_pd_gather<2>, dim3(S.rgrid), dim3(256), 0, 0, L.dp->d_rowptr, L.dp->d_adj_eid, L.d_sgn, S.sx, nullptr, none, S.dg, (int)S.n);
     ++S.solves;
-    for (int c = 0; c < 3; ++c) {
-        bad[c] = act[c] && hs.bad[c];
-        if (act[c] && !bad[c] && hs.bnorm[c] > 0) S.cg_worst = std::max(S.cg_worst, std::sqrt(hs.rnorm[c] / hs.bnorm[c]));
-    }
-    if (!done) ++S.cg_unconverged;
-    return DESC_OK;
+    return laa_pcg<true, true>(L, S.sx, S.w1p, S.dg, S.dx, act, PD_PROBE, S.cg, bad);
 }
 
 // W(2:end, 2:4) = [l1decode_pd(0, A, [], B(:,c), eps, pdmaxiter, AtA) for c = 1..3] (BoxMedianSO3Graph.m:166-168) into S.x
@@ -607,11 +460,10 @@ int tree_start(const desc_device_problem* sp, const hvec<int32_t>& visit, const 
     const int cnt = (int)seq_e.size();
     hvec<Quat> qq((size_t)std::max(cnt, 1));
     if (cnt) {
+        DevArena A;                                                                         // freed before the host pass below
         int32_t* d_ids = nullptr; Quat* d_out = nullptr;
-        DESC_HIP(dev_alloc((void**)&d_ids, sizeof(int32_t) * cnt));
-        struct F { void* p; ~F() { dev_free(p); } } f1{d_ids};
-        DESC_HIP(dev_alloc((void**)&d_out, sizeof(Quat) * cnt));
-        struct F2 { void* p; ~F2() { dev_free(p); } } f2{d_out};
+        int rc = DESC_OK;
+        if ((rc = A.alloc(&d_ids, cnt)) || (rc = A.alloc(&d_out, cnt))) return rc;
         DESC_HIP(hipMemcpy(d_ids, seq_e.data(), sizeof(int32_t) * cnt, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(k_gather_quat, dim3((cnt + 255) / 256), dim3(256), 0, 0, d_QQ, d_ids, cnt, d_out);
         DESC_HIP(hipMemcpy(qq.data(), d_out, sizeof(Quat) * cnt, hipMemcpyDeviceToHost));
@@ -620,24 +472,8 @@ int tree_start(const desc_device_problem* sp, const hvec<int32_t>& visit, const 
     for (int t = 0; t < cnt; ++t) {
         const Quat g = qq[t];
         const int e = seq_e[t];
-        if (seq_dir[t] == 0) {                                                              // :93-95: Q(j) = QQ * Q(i)
-            const Quat b = Q[ii[e]];
-            Quat o;
-            o.a = g.a * b.a - (g.x * b.x + g.y * b.y + g.z * b.z);
-            o.x = g.a * b.x + b.a * g.x + (g.y * b.z - g.z * b.y);
-            o.y = g.a * b.y + b.a * g.y + (g.z * b.x - g.x * b.z);
-            o.z = g.a * b.z + b.a * g.z + (g.x * b.y - g.y * b.x);
-            Q[jj[e]] = o;
-        } else {                                                                            // :101-103: Q(i) from Q(j)
-            const Quat b = Q[jj[e]];
-            const double na = -g.a;
-            Quat o;
-            o.a = na * b.a - (g.x * b.x + g.y * b.y + g.z * b.z);
-            o.x = na * b.x + b.a * g.x + (g.y * b.z - g.z * b.y);
-            o.y = na * b.y + b.a * g.y + (g.z * b.x - g.x * b.z);
-            o.z = na * b.z + b.a * g.z + (g.x * b.y - g.y * b.x);
-            Q[ii[e]] = o;
-        }
+        if (seq_dir[t] == 0) Q[jj[e]] = qmul(g, Q[ii[e]]);                                  // :93-95: Q(j) = QQ * Q(i)
+        else Q[ii[e]] = qmul(Quat{-g.a, g.x, g.y, g.z}, Q[jj[e]]);                          // :101-103: Q(i) from Q(j)
     }
     return DESC_OK;
 }
@@ -653,11 +489,7 @@ extern "C" int desc_irls_run(const desc_problem* prob, const desc_irls_params* p
                              desc_irls_info* info) {
     if (!prob || !params || !R_out) return fail(DESC_ERR_INVALID, "NULL argument");
     auto t0 = std::chrono::steady_clock::now();
-    desc_device_problem* dp = nullptr;
-    int rc = desc_problem_upload(prob, device, &dp);
-    if (rc) return rc;
-    rc = desc_irls_run_dev(dp, params, R_out, R_l1, info);
-    desc_problem_free(dp);
+    const int rc = with_uploaded(prob, device, [&](const desc_device_problem* dp) { return desc_irls_run_dev(dp, params, R_out, R_l1, info); });
     if (!rc && info) info->ms_total = ms_since(t0);
     return rc;
 }
@@ -687,21 +519,12 @@ extern "C" int desc_irls_run_dev(const desc_device_problem* dp, const desc_irls_
     double* d_P = nullptr;
     int32_t *d_flags = nullptr, *d_order = nullptr;
     double* d_einfo = nullptr;
-    DESC_HIP(dev_alloc((void**)&d_P, sizeof(double) * 9 * m));
-    struct FreeP { void* p; ~FreeP() { dev_free(p); } } fP{d_P};
-    DESC_HIP(dev_alloc((void**)&d_flags, sizeof(int32_t) * 2));
-    struct FreeF { void* p; ~FreeF() { dev_free(p); } } fF{d_flags};
-    DESC_HIP(dev_alloc((void**)&d_einfo, sizeof(double) * 5));
-    struct FreeE { void* p; ~FreeE() { dev_free(p); } } fE{d_einfo};
-    if (P->order) {
-        DESC_HIP(dev_alloc((void**)&d_order, sizeof(int32_t) * m));
-        DESC_HIP(hipMemcpy(d_order, P->order, sizeof(int32_t) * m, hipMemcpyHostToDevice));
-    }
-    struct FreeO { void* p; ~FreeO() { if (p) dev_free(p); } } fO{d_order};
+    DevArena A;
+    if ((rc = A.alloc(&d_P, 9 * m)) || (rc = A.alloc(&d_flags, 2)) || (rc = A.alloc(&d_einfo, 5)) || (P->order && (rc = A.alloc(&d_order, m)))) return rc;
+    if (P->order) DESC_HIP(hipMemcpy(d_order, P->order, sizeof(int32_t) * m, hipMemcpyHostToDevice));
     const int32_t init_flags[2] = {INT_MAX, 0};
     DESC_HIP(hipMemcpy(d_flags, init_flags, sizeof init_flags, hipMemcpyHostToDevice));
-    const int egrid_full = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (m + 255) / 256));
-    hipLaunchKernelGGL(k_irls_project, dim3(egrid_full), dim3(256), 0, 0, dp->d_rij, d_order, m, d_P, d_flags, d_flags + 1, (int64_t)-1, d_einfo);
+    hipLaunchKernelGGL(k_irls_project, dim3(grid_for(m, 2048)), dim3(256), 0, 0, dp->d_rij, d_order, m, d_P, d_flags, d_flags + 1, (int64_t)-1, d_einfo);
     DESC_HIP(hipGetLastError());
     int32_t flags[2];
     DESC_HIP(hipMemcpy(flags, d_flags, sizeof flags, hipMemcpyDeviceToHost));
@@ -807,10 +630,10 @@ extern "C" int desc_irls_run_dev(const desc_device_problem* dp, const desc_irls_
         if ((rc = laa_finish(L, Iteration, r_l1.data()))) return rc;                         // real(q2R(Q)) (:192-197)
         I.l1_iters = Iteration; I.l1_score = score;
         I.pd_steps = S.steps; I.pd_ill = S.ill; I.pd_stuck = S.stuck; I.pd_solves = S.solves;
-        I.cg_iters_l1 = S.cg_total; I.cg_unconverged = S.cg_unconverged; I.cg_residual = S.cg_worst; I.ms_l1_pcg = S.ms_pcg;
-        if (S.cg_unconverged)
+        I.cg_iters_l1 = S.cg.total; I.cg_unconverged = S.cg.unconverged; I.cg_residual = S.cg.worst; I.ms_l1_pcg = S.ms_pcg;
+        if (S.cg.unconverged)
             fprintf(stderr, "[desc_amd] warning: %d primal-dual Newton solves stopped at the PCG iteration cap (relative residual up to %.3e)\n",
-                    S.cg_unconverged, S.cg_worst);
+                    S.cg.unconverged, S.cg.worst);
     }
     I.ms_l1 = ms_since(t2);
     // ---- stage 5: RobustMeanSO3Graph / L12 (IRLS_GM.m:96)
@@ -834,7 +657,7 @@ extern "C" int desc_irls_run_dev(const desc_device_problem* dp, const desc_irls_
         if (verbose && Iteration >= max_irls) printf("Max iterations reached\n");            // :202
         if ((rc = laa_finish(L, Iteration, r_out.data()))) return rc;                        // q2R (:193-197)
         I.irls_iters = Iteration; I.irls_score = score;
-        I.cg_iters_irls = L.cg_total; I.cg_unconverged += L.cg_unconverged; I.cg_residual = std::max(I.cg_residual, L.cg_worst);
+        I.cg_iters_irls = L.cg.total; I.cg_unconverged += L.cg.unconverged; I.cg_residual = std::max(I.cg_residual, L.cg.worst);
     }
     I.ms_irls = ms_since(t3);
     // ---- NaN outside the component (:94)

@@ -1,16 +1,22 @@
-// Internal: the reweighted Lie-algebraic averaging step (Utils/Weighted_LAA.m) on a device problem, shared by the DESC
-// refinement tail (Algorithms/DESC.m:265-313) and MPLS (Algorithms/MPLS.m:196-254).  Kernels and driver in refine.hip.
+// Internal: the Lie-algebraic averaging core on a device problem -- the reweighted step of Utils/Weighted_LAA.m, the Jacobi-PCG on the
+// grounded graph Laplacian under it, the quantile and the quaternion maps.  Implemented in laa.hip; used by the DESC refinement tail
+// (Algorithms/DESC.m:265-313, refine.hip), MPLS (Algorithms/MPLS.m:196-254, mpls.hip) and IRLS_GM / IRLS_L12 (irls.hip).
 #pragma once
-#include "common.h"
+#include "device_utils.h"
 
 namespace desc {
 
 struct Quat { double a, x, y, z; };
 
+// the PCG's device-resident scalars, per coordinate; bad: the coordinate broke down (only set when breakdowns are tracked)
+struct CgScal { double rz[3], rz_new[3], pq[3], bnorm[3], rnorm[3]; int bad[3], pad; };
+// PCG bookkeeping over the solves of one loop: steps (each solve's true count rounded up to its probe interval), solves that stopped at
+// the iteration cap, the largest relative residual |r| / |b| a solve ended with
+struct CgCount { int total = 0, unconverged = 0; double worst = 0.0; };
+
 // Device state of one refinement loop: rotations as quaternions, the relative rotations' quaternions, the edge weights,
 // the PCG work arrays and the quantile scratch.  laa_setup allocates and fills it; the buffers live until destruction.
-struct LaaSolver {
-    hvec<void*> blocks;
+struct LaaSolver : DevArena {
     const desc_device_problem* dp = nullptr;
     int64_t n = 0, m = 0;
     int egrid = 1, ngrid = 1, rgrid = 1, sgrid = 64;
@@ -18,20 +24,27 @@ struct LaaSolver {
     double *d_Rinit = nullptr, *d_w = nullptr, *d_B = nullptr, *d_rhs = nullptr, *d_diag = nullptr, *d_x = nullptr, *d_r = nullptr,
            *d_z = nullptr, *d_p = nullptr, *d_q = nullptr, *d_Wv = nullptr, *d_score = nullptr, *d_Rout = nullptr;
     Quat *d_Q = nullptr, *d_QQ = nullptr;
-    void* d_sc = nullptr;                     // CG scalars (device-resident)
+    CgScal* d_sc = nullptr;
     double *d_mm = nullptr, *d_cand = nullptr;
     unsigned* d_qh = nullptr;
-    int cg_total = 0, cg_unconverged = 0;
-    double cg_worst = 0.0;
+    CgCount cg;                               // of laa_step's solves
     hvec<double> part;
-    ~LaaSolver();
-    template <class T> int alloc(T** out, size_t count);
 };
 
 // allocate, upload R_init (n*9 host doubles, 3x3xn column-major), Q = R2Q(R_init), QQ = R2Q(permute(RijMat, [2,1,3]))
 int laa_setup(const desc_device_problem* dp, const double* R_init, LaaSolver& L);
 // Weighted_LAA.m:4-51 with the weights in L.d_w: edge log map B, normal equations by PCG, Q <- Q * exp(W); *score = :40
 int laa_step(LaaSolver& L, double* score);
+// Jacobi-PCG for the three systems A' diag(w_c) A x_c = rhs_c (A: incidence matrix with node 0 grounded) in L's work arrays: scalars
+// on the device, the host probes |r| <= 1e-13 |b| every `probe` steps over the coordinates in act; x, rhs, diag are n x 3 / n device
+// arrays of the caller.
+//   W3     the operator weight of edge e, coordinate c is w[3 e + c] and the Jacobi diagonal diag[3 v + c] (the primal-dual Newton
+//          systems); else w[e] * w[e] for all three and diag[v] (Weighted_LAA's normal equations)
+//   TRACK  a breakdown (a non-finite p'Hp or r'z, or p'Hp <= 0 while r'z > 0) freezes its coordinate (alpha = 0 from then on), takes it
+//          out of the convergence test and is returned in bad[c]; else bad[] comes back 0.  Off for laa_step, and to stay off: with
+//          it a degenerate input would return something else.
+template <bool W3, bool TRACK>
+int laa_pcg(LaaSolver& L, const double* w, const double* rhs, const double* diag, double* x, const int act[3], int probe, CgCount& count, int bad[3]);
 // QQ = R2Q(blocks) of m blocks that are already in the reference's RR orientation (no transpose): replaces laa_setup's
 // R2Q(permute(RijMat, [2,1,3])) when the edge rotations were modified first (IRLS_GM.m:82-93, irls.hip)
 void laa_set_qq(LaaSolver& L, const double* d_blocks);
@@ -43,5 +56,43 @@ void laa_weights(LaaSolver& L, const double* d_x, double thresh);
 int laa_quantile(LaaSolver& L, const double* d_x, double p, double* result);
 // q2R.m of every node into R_out (n*9 host doubles); prints the reference's warning when a PCG solve stopped at its cap
 int laa_finish(LaaSolver& L, int iterations, double* R_out);
+
+// ---- device helpers.  The library is built without contraction and fast-math: an expression tree kept as it is gives the same bits, so
+// operand order and bracketing below are part of the interface.
+// Hamilton product a * b.  inv(q) * b as the reference writes it (the negated product, the same rotation) is qmul({-q.a, q.x, q.y, q.z}, b).
+__host__ __device__ __forceinline__ Quat qmul(const Quat& a, const Quat& b) {
+    Quat o;
+    o.a = a.a * b.a - (a.x * b.x + a.y * b.y + a.z * b.z);
+    o.x = a.a * b.x + b.a * a.x + (a.y * b.z - a.z * b.y);
+    o.y = a.a * b.y + b.a * a.y + (a.z * b.x - a.x * b.z);
+    o.z = a.a * b.z + b.a * a.z + (a.x * b.y - a.y * b.x);
+    return o;
+}
+// exp map of the tangent vector t (Weighted_LAA.m:42-46, BoxMedianSO3Graph.m:176-180): *theta = |t|; NaN -> 0 (theta = 0 gives the zero
+// quaternion part, as the reference)
+__device__ __forceinline__ Quat qexp(double t1, double t2, double t3, double* theta) {
+    const double th = sqrt(t1 * t1 + t2 * t2 + t3 * t3);
+    Quat w;
+    w.a = cos(th / 2.0);
+    const double f = sin(th / 2.0) / th;
+    w.x = t1 * f; w.y = t2 * f; w.z = t3 * f;
+    if (isnan(w.a)) w.a = 0.0;
+    if (isnan(w.x)) w.x = 0.0;
+    if (isnan(w.y)) w.y = 0.0;
+    if (isnan(w.z)) w.z = 0.0;
+    *theta = th;
+    return w;
+}
+// |(A x - B)_e|^2 of edge e = (i, j): sum over the coordinates of ((x_j - x_i)_c - B_e,c)^2, node 0 grounded (its x counts as 0)
+__device__ __forceinline__ double edge_residual_sq(const double* x, const double* B, const int32_t* ii, const int32_t* jj, int64_t e) {
+    const int i = ii[e], j = jj[e];
+    double s = 0.0;
+    for (int c = 0; c < 3; ++c) {
+        const double ax = (j > 0 ? x[3 * j + c] : 0.0) - (i > 0 ? x[3 * i + c] : 0.0);
+        const double d = ax - B[3 * e + c];
+        s += d * d;
+    }
+    return s;
+}
 
 }  // namespace desc

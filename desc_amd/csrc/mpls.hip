@@ -1,19 +1,17 @@
 // MPLS (Algorithms/MPLS.m:31-257): CEMP -> CEMP+MST initialisation -> cycle-reweighted Lie-algebraic averaging.
 //   :65-158   CEMP, the text of CEMP.m:36-132: cemp.hip's two steps, whose samples and S0Mat stay resident for the loop
 //   :160-193  minimum spanning tree and rotations along it: mst.hip
-//   :196-216  Q = R2Q(R_init), QQ = R2Q(RijMat'), weights min(1/SVec^0.75, 1e4): the refinement's set-up (refine.hip, laa.h)
-//   :218-249  per iteration: Weighted_LAA (refine.hip); residuals (k_mpls_res); the H step -- CEMP's round on the residuals with
+//   :196-216  Q = R2Q(R_init), QQ = R2Q(RijMat'), weights min(1/SVec^0.75, 1e4): the averaging core's set-up (laa.h, laa.hip)
+//   :218-249  per iteration: Weighted_LAA (laa.hip); residuals (k_mpls_res); the H step -- CEMP's round on the residuals with
 //             the kept S0Mat, epilogue RH = (1 - alpha) Res + alpha H fused (cemp.hip, k_cemp_round*<true>); quantile and weights
 // Edges without a 3-cycle keep the reference's quirk: :239 (HVec(~IndPosbin) = 1) is commented out, their cycle product is the zero
 // matrix (Rki0 / Rjk0 stay zero, :109-114), so S0 = |acos(-1/2)|/pi = 2/3, both residual terms 0, every weight 1/nsample: H = 2/3 up
 // to round-off.  k_mpls_res writes their RH; the H step writes the others.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <vector>
 
 #include "cemp_state.h"
-#include "device_utils.h"
 #include "laa.h"
 
 namespace desc {
@@ -25,14 +23,7 @@ __global__ __launch_bounds__(256) void k_mpls_res(const double* Wv, const double
                                                   double* res_full, const int32_t* slot_a, const int32_t* slot_b, const int32_t* poe, double* rh,
                                                   double alpha, int nsample) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256) {
-        const int i = ii[e], j = jj[e];
-        double s = 0.0;
-        for (int c = 0; c < 3; ++c) {
-            const double ax = (j > 0 ? Wv[3 * j + c] : 0.0) - (i > 0 ? Wv[3 * i + c] : 0.0);
-            const double d = ax - B[3 * e + c];
-            s += d * d;
-        }
-        const double r = sqrt(s) / M_PI;
+        const double r = sqrt(edge_residual_sq(Wv, B, ii, jj, e)) / M_PI;
         res[e] = r;
         if (res_full) { res_full[slot_a[e]] = r; res_full[slot_b[e]] = r; }
         if (poe && poe[e] < 0) {
@@ -43,8 +34,6 @@ __global__ __launch_bounds__(256) void k_mpls_res(const double* Wv, const double
         }
     }
 }
-
-double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
 
 // :37-63: a parameter vector shorter than the loop repeats its last entry
 double padded(const double* v, int32_t len, int idx) { return v[idx < len ? idx : len - 1]; }
@@ -58,11 +47,7 @@ extern "C" int desc_mpls_run(const desc_problem* prob, const desc_mpls_params* p
                              double* s_vec_out, desc_mpls_info* info) {
     if (!prob || !params || !R_est) return fail(DESC_ERR_INVALID, "NULL argument");
     auto t0 = std::chrono::steady_clock::now();
-    desc_device_problem* dp = nullptr;
-    int rc = desc_problem_upload(prob, device, &dp);
-    if (rc) return rc;
-    rc = desc_mpls_run_dev(dp, params, R_est, R_init, s_vec_out, info);
-    desc_problem_free(dp);
+    const int rc = with_uploaded(prob, device, [&](const desc_device_problem* dp) { return desc_mpls_run_dev(dp, params, R_est, R_init, s_vec_out, info); });
     if (!rc && info) info->ms_total = ms_since(t0);
     return rc;
 }
@@ -130,8 +115,8 @@ extern "C" int desc_mpls_run_dev(const desc_device_problem* dp, const desc_mpls_
     say("DONE!");
     if (verbose) fflush(stdout);
     if (info) {
-        info->iters = Iteration - 1; info->cg_iters = L.cg_total; info->cg_unconverged = L.cg_unconverged; info->reserved = 0;
-        info->m_pos = cs.mp; info->score = score; info->cg_residual = L.cg_worst;
+        info->iters = Iteration - 1; info->cg_iters = L.cg.total; info->cg_unconverged = L.cg.unconverged; info->reserved = 0;
+        info->m_pos = cs.mp; info->score = score; info->cg_residual = L.cg.worst;
         info->ms_cemp = ms_cemp; info->ms_mst = ms_mst; info->ms_loop = ms_since(t2); info->ms_total = ms_since(t0);
     }
     return DESC_OK;

@@ -14,7 +14,6 @@
 // Rooting and propagation run on the host (O(n), microseconds) from the n - 1 tree edges and their 72-byte blocks.
 // components_device runs the same rounds with all keys equal and returns the component labels (IRLS_GM.m:65-67, irls.hip).
 #include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cmath>
 #include <vector>
@@ -98,17 +97,6 @@ __global__ __launch_bounds__(256) void k_mst_collect(const uint8_t* mark, const 
     }
 }
 
-struct DevM {
-    hvec<void*> p;
-    ~DevM() { for (void* q : p) dev_free(q); }
-    template <class T> int alloc(T** out, size_t count) {
-        void* q = nullptr;
-        DESC_HIP(dev_alloc(&q, sizeof(T) * (count ? count : 1)));
-        p.push_back(q); *out = (T*)q;
-        return DESC_OK;
-    }
-};
-
 // C = A * B, or A' * B, 3x3 column-major
 void mul3(const double* A, bool transpose_a, const double* B, double* C) {
     for (int r = 0; r < 3; ++r)
@@ -122,7 +110,7 @@ void mul3(const double* A, bool transpose_a, const double* B, double* C) {
 // The Boruvka rounds on the CSR index with edge order (d_key[e], e): on return d_comp holds every node's component label (the label of
 // a component is one of its nodes) and d_mark the forest's edges (d_mark must be zeroed by the caller).  Shared by mst_device and
 // components_device.
-int boruvka_rounds(const desc_device_problem* dp, const unsigned long long* d_key, int32_t* d_comp, uint8_t* d_mark, DevM& D) {
+int boruvka_rounds(const desc_device_problem* dp, const unsigned long long* d_key, int32_t* d_comp, uint8_t* d_mark, DevArena& D) {
     int rc = DESC_OK;
     const int64_t n = dp->n;
     unsigned long long *d_rkey, *d_bkey;
@@ -130,8 +118,8 @@ int boruvka_rounds(const desc_device_problem* dp, const unsigned long long* d_ke
     if ((rc = D.alloc(&d_rkey, n)) || (rc = D.alloc(&d_bkey, n)) || (rc = D.alloc(&d_parent, n)) || (rc = D.alloc(&d_ridx, n)) ||
         (rc = D.alloc(&d_bidx, n)) || (rc = D.alloc(&d_cnt, 2)))
         return rc;
-    const int ngrid = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (n + 255) / 256));
-    const int wgrid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n + 3) / 4));          // a wave per row
+    const int ngrid = grid_for(n, 1024);
+    const int wgrid = grid_for(n, 2048, 4);          // a wave per row
     hipLaunchKernelGGL(k_mst_init, dim3(ngrid), dim3(256), 0, 0, d_comp, d_parent, (int)n);
     const int log2n = (int)std::ceil(std::log2((double)n));
     const int max_rounds = log2n + 2, jumps = log2n + 1;
@@ -158,7 +146,7 @@ int mst_device(const desc_device_problem* dp, const double* d_s, double* R_out, 
     int rc = DESC_OK;
     const int64_t n = dp->n, m = dp->m;
     if (n <= 0) return fail(DESC_ERR_INVALID, "empty graph");
-    DevM D;
+    DevArena D;
     unsigned long long* d_key;
     int32_t *d_comp, *d_cnt, *d_ids;
     uint8_t* d_mark;
@@ -166,7 +154,7 @@ int mst_device(const desc_device_problem* dp, const double* d_s, double* R_out, 
     if ((rc = D.alloc(&d_key, m)) || (rc = D.alloc(&d_comp, n)) || (rc = D.alloc(&d_cnt, 2)) || (rc = D.alloc(&d_ids, n)) ||
         (rc = D.alloc(&d_mark, m)) || (rc = D.alloc(&d_blocks, 9 * n)))
         return rc;
-    const int egrid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (m + 255) / 256));
+    const int egrid = grid_for(m, 2048);
     if (m) {
         hipLaunchKernelGGL(k_mst_keys, dim3(egrid), dim3(256), 0, 0, d_s, d_key, m);
         DESC_HIP(hipMemsetAsync(d_mark, 0, m, 0));
@@ -224,7 +212,7 @@ int components_device(const desc_device_problem* dp, int32_t* comp_out, int64_t*
     int rc = DESC_OK;
     const int64_t n = dp->n, m = dp->m;
     if (n <= 0) return fail(DESC_ERR_INVALID, "empty graph");
-    DevM D;
+    DevArena D;
     unsigned long long* d_key;
     int32_t* d_comp;
     uint8_t* d_mark;
@@ -253,21 +241,17 @@ using namespace desc;
 
 extern "C" int desc_mst_run(const desc_problem* prob, const double* s_vec, int32_t device, double* R_out, int32_t* tree_edges) {
     if (!prob || !s_vec || !R_out) return fail(DESC_ERR_INVALID, "NULL argument");
-    desc_device_problem* dp = nullptr;
-    int rc = desc_problem_upload(prob, device, &dp);
-    if (rc) return rc;
-    rc = desc_mst_run_dev(dp, s_vec, R_out, tree_edges);
-    desc_problem_free(dp);
-    return rc;
+    return with_uploaded(prob, device, [&](const desc_device_problem* dp) { return desc_mst_run_dev(dp, s_vec, R_out, tree_edges); });
 }
 
 extern "C" int desc_mst_run_dev(const desc_device_problem* dp, const double* s_vec, double* R_out, int32_t* tree_edges) {
     return no_throw("desc_mst_run_dev", [&]() -> int {
     if (!dp || !s_vec || !R_out) return fail(DESC_ERR_INVALID, "NULL argument");
     DESC_HIP(hipSetDevice(dp->device));
+    DevArena A;
     double* d_s = nullptr;
-    DESC_HIP(dev_alloc((void**)&d_s, sizeof(double) * (dp->m ? dp->m : 1)));
-    struct Free { double* p; ~Free() { dev_free(p); } } fr{d_s};
+    int rc = A.alloc(&d_s, dp->m);
+    if (rc) return rc;
     if (dp->m) DESC_HIP(hipMemcpy(d_s, s_vec, sizeof(double) * dp->m, hipMemcpyHostToDevice));
     return mst_device(dp, d_s, R_out, tree_edges);
     });

@@ -344,17 +344,6 @@ void project_so3(const double* M, double* R) {
     for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) R[r * 3 + c] = U[r * 3 + 0] * V[c * 3 + 0] + U[r * 3 + 1] * V[c * 3 + 1] + d * U[r * 3 + 2] * V[c * 3 + 2];
 }
 
-struct Dev {
-    hvec<void*> p;
-    ~Dev() { for (void* q : p) dev_free(q); }
-    template <class T> int alloc(T** out, size_t count) {
-        void* q = nullptr;
-        DESC_HIP(dev_alloc(&q, sizeof(T) * (count ? count : 1)));
-        p.push_back(q); *out = (T*)q;
-        return DESC_OK;
-    }
-};
-
 }  // namespace
 }  // namespace desc
 
@@ -365,12 +354,8 @@ extern "C" int desc_spectral_run(const desc_problem* prob, const double* weights
     if (!prob || !R_out) return fail(DESC_ERR_INVALID, "NULL argument");
     if (prob->n == 0) return validate_problem(prob, true);
     auto t0 = std::chrono::steady_clock::now();
-    desc_device_problem* dp = nullptr;
-    int rc = desc_problem_upload(prob, device, &dp);
-    if (rc) return rc;
-    rc = desc_spectral_run_dev(dp, weights, normalize_rows, tol, max_iters, R_out, info);
-    desc_problem_free(dp);
-    if (!rc && info) info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const int rc = with_uploaded(prob, device, [&](const desc_device_problem* dp) { return desc_spectral_run_dev(dp, weights, normalize_rows, tol, max_iters, R_out, info); });
+    if (!rc && info) info->ms_total = ms_since(t0);
     return rc;
 }
 
@@ -407,7 +392,7 @@ static int spectral_impl(const desc_device_problem* dp, const double* weights, c
         if (!timing) return;
         (void)hipDeviceSynchronize();
         auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[desc_amd] spectral %-22s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_lap).count());
+        fprintf(stderr, "[desc_amd] spectral %-22s %8.3f ms\n", what, ms_since(t_lap));
         t_lap = now;
     };
     if (tol <= 0) tol = 1e-13;
@@ -416,15 +401,15 @@ static int spectral_impl(const desc_device_problem* dp, const double* weights, c
     // block CSR: every edge in both endpoint rows; the index part lives with the device problem, the 2m blocks are
     // assembled on the device ((i,j) slot = R, (j,i) slot = R')
     hvec<double> deg((size_t)n, 0.0);
-    Dev W;                                                  // edge weights on the device (NULL: all ones)
+    DevArena W;                                                  // edge weights on the device (NULL: all ones)
     double* d_w = nullptr;
     if (gcw_svec) {                                         // weights and weighted degrees entirely on the device
         double *d_s, *d_deg;
-        Dev Tmp;
+        DevArena Tmp;
         if ((rc = W.alloc(&d_w, m)) || (rc = Tmp.alloc(&d_s, m)) || (rc = Tmp.alloc(&d_deg, n))) return rc;
         if (m) DESC_HIP(hipMemcpy(d_s, gcw_svec, sizeof(double) * m, hipMemcpyHostToDevice));
         if (m) hipLaunchKernelGGL(k_gcw_weights, dim3((unsigned)std::min<int64_t>(2048, (m + 255) / 256)), dim3(256), 0, 0, d_s, d_w, m);
-        hipLaunchKernelGGL(k_row_wsum, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (n * 16 + 255) / 256))), dim3(256), 0, 0,
+        hipLaunchKernelGGL(k_row_wsum, dim3(grid_for(n * 16, 2048)), dim3(256), 0, 0,
                            dp->d_rowptr, dp->d_adj_eid, d_w, d_deg, (int)n);
         DESC_HIP(hipMemcpy(deg.data(), d_deg, sizeof(double) * n, hipMemcpyDeviceToHost));
         for (int64_t v = 0; v < n; ++v) if (!std::isfinite(deg[v])) return fail(DESC_ERR_INVALID, "S_vec holds a negative or non-finite entry (node %lld)", (long long)v);
@@ -456,13 +441,13 @@ static int spectral_impl(const desc_device_problem* dp, const double* weights, c
     hvec<double> X0((size_t)rows * BW);
     for (size_t t = 0; t < X0.size(); ++t) X0[t] = (double)(int64_t)(mix64(0xC0FFEEull + t) >> 11) / 4503599627370496.0 - 1.0;
 
-    Dev D;
+    DevArena D;
     const int32_t *d_rowptr = dp->d_rowptr, *d_adj = dp->d_adj; double *d_blocks, *d_X, *d_Y, *d_part;
     const int ggrid = 256;
     if ((rc = D.alloc(&d_blocks, 18 * m)) ||
         (rc = D.alloc(&d_X, rows * BW)) || (rc = D.alloc(&d_Y, rows * BW)) || (rc = D.alloc(&d_part, (size_t)ggrid * 2 * BW * BW))) return rc;
     if (m) {
-        Dev T;                                               // assembly inputs, released before the iteration starts
+        DevArena T;                                               // assembly inputs, released before the iteration starts
         const int32_t* d_eid = dp->d_adj_eid; const double* d_rij = dp->d_rij; double* d_dinv;
         if ((rc = T.alloc(&d_dinv, n))) return rc;
         DESC_HIP(hipMemcpy(d_dinv, dinv.data(), sizeof(double) * n, hipMemcpyHostToDevice));
@@ -649,7 +634,7 @@ static int spectral_impl(const desc_device_problem* dp, const double* weights, c
         info->residual = res;
         for (int c = 0; c < 3; ++c) info->eigenvalues[c] = theta[c];
         info->products = products;
-        info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        info->ms_total = ms_since(t0);
     }
     return DESC_OK;
 }
@@ -666,7 +651,7 @@ extern "C" int desc_debug_spmm_variants(const desc_device_problem* dp, int32_t r
     const int64_t n = dp->n, m = dp->m, rows = 3 * n;
     if (n == 0 || m == 0) return fail(DESC_ERR_INVALID, "empty problem");
     int rc;
-    Dev D;
+    DevArena D;
     double *d_blocks, *d_X, *d_Y1, *d_Y2, *d_dinv;
     if ((rc = D.alloc(&d_blocks, 18 * m)) || (rc = D.alloc(&d_X, rows * BW)) || (rc = D.alloc(&d_Y1, rows * BW)) || (rc = D.alloc(&d_Y2, rows * BW)) ||
         (rc = D.alloc(&d_dinv, n))) return rc;

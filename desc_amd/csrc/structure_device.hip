@@ -360,18 +360,6 @@ __global__ void k_iota(int32_t* p, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = (int32_t)i;
 }
 
-struct DevBuf {
-    hvec<void*> p;
-    ~DevBuf() { release(); }
-    void release() { for (void* q : p) dev_free(q); p.clear(); }
-    template <class T> int alloc(T** out, size_t count) {
-        void* q = nullptr;
-        DESC_HIP(dev_alloc(&q, sizeof(T) * (count ? count : 1)));
-        p.push_back(q); *out = (T*)q;
-        return DESC_OK;
-    }
-};
-
 // Compaction of the edges with cycles (DESC_PGD.m:36-37) and the prefix sums of their sampled cycle counts min(codeg, n_sample) (:45-49), as three
 // launches: per tile of 1024 edges the number of edges with cycles and of their cycles (k_tile_sums), an exclusive scan of the tile totals by one
 // workgroup (k_scan_tiles), and the scatter with the in-tile scan redone in the LDS (k_compact_tiles).  (The first form used hipCUB's device scans:
@@ -457,7 +445,7 @@ int build_structure_device(const desc_problem* prob, int32_t n_sample_min, uint6
         if (!timing) return;
         if (wait) (void)hipDeviceSynchronize();
         auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[desc_amd] structure_device %-18s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_lap).count());
+        fprintf(stderr, "[desc_amd] structure_device %-18s %8.3f ms\n", what, ms_since(t_lap));
         t_lap = now;
     };
     const int64_t n = prob->n, m = prob->m;
@@ -477,7 +465,7 @@ int build_structure_device(const desc_problem* prob, int32_t n_sample_min, uint6
         *out = (std::remove_reference_t<decltype(*out)>)q;
         return DESC_OK;
     };
-    DevBuf D;
+    DevArena D;
     int rc;
     int32_t *d_codeg, *d_hist, *d_deg, *d_low, *d_upstart;
     unsigned long long* d_bits;
@@ -504,7 +492,7 @@ int build_structure_device(const desc_problem* prob, int32_t n_sample_min, uint6
         hipLaunchKernelGGL(k_rank, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_bits, s->d_rank, (int)n, (int)words);
         hipLaunchKernelGGL(k_degrees, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_bits, s->d_rank, d_deg, d_low, (int)n, (int)words);
         hipLaunchKernelGGL(k_scan_rows, dim3(1), dim3(1024), 0, 0, d_deg, d_low, s->d_rowptr, d_upstart, (int)n);
-        hipLaunchKernelGGL(k_csr_from_bits, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (n * 16 + 255) / 256))), dim3(256), 0, 0,
+        hipLaunchKernelGGL(k_csr_from_bits, dim3(grid_for(n * 16, 4096)), dim3(256), 0, 0,
                            d_bits, s->d_rank, s->d_rowptr, d_low, d_upstart, s->d_adj, s->d_adj_eid, (int)n, (int)words);
         DESC_HIP(hipGetLastError());
         DESC_HIP(hipMemcpy(rowptr.data(), s->d_rowptr, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToHost));
@@ -610,13 +598,13 @@ int build_structure_device(const desc_problem* prob, int32_t n_sample_min, uint6
         if (s->cum_ind[mp] != mc) return fail(DESC_ERR_STATE, "cycle prefix sums (%lld) disagree with the codegree histogram (%lld)", (long long)s->cum_ind[mp], (long long)mc);
         lap("tables to host", false);
         // the builder's own scratch (codegrees, histogram, degree tables) is still being read by the kernels in flight: the structure keeps it
-        for (void* q : D.p) s->d_build_blocks.push_back(q);
-        D.p.clear();
+        for (void* q : D.blocks) s->d_build_blocks.push_back(q);
+        D.blocks.clear();
         const char* sf = getenv("DESC_DEBUG_SYNC_FILL");
         if (sf && atoi(sf) != 0) DESC_HIP(hipDeviceSynchronize());
         lap("fill (launched)", false);
     } else if (m) DESC_HIP(hipMemcpy(s->codeg.data(), d_codeg, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
-    s->ms_build = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    s->ms_build = ms_since(t0);
     return DESC_OK;
 }
 
@@ -631,7 +619,7 @@ int build_cemp_samples_device(const desc_device_problem* dp, int32_t nsample, ui
     if (o_max_deg) *o_max_deg = max_deg;
     if ((double)n * (double)words * 12.0 > 64.0 * 1073741824.0) return fail(DESC_ERR_TOO_LARGE, "adjacency bitmaps do not fit the device budget");
     DESC_HIP(hipSetDevice(dp->device));
-    DevBuf D;
+    DevArena D;
     int rc;
     const int32_t *d_rowptr = dp->d_rowptr, *d_adj = dp->d_adj, *d_adj_eid = dp->d_adj_eid, *d_ii = dp->d_ii, *d_jj = dp->d_jj;   // CSR index: the device problem's
     int32_t *d_codeg, *d_hist;
@@ -707,7 +695,7 @@ int structure_ensure_host(desc_structure* s) {
         s->codeg.resize((size_t)s->m);
         DESC_HIP(hipMemcpy(s->codeg.data(), s->d_codeg, sizeof(int32_t) * s->m, hipMemcpyDeviceToHost));
     }
-    DevBuf D;
+    DevArena D;
     int rc;
     int32_t *d_ejk, *d_eki, *d_ikj, *d_jki;
     if ((rc = D.alloc(&d_ejk, mc)) || (rc = D.alloc(&d_eki, mc)) || (rc = D.alloc(&d_ikj, mc)) || (rc = D.alloc(&d_jki, mc))) return rc;

@@ -3,7 +3,8 @@
 
 One desc_irls_run_dev call per mode on a resident device problem; the stages are desc_irls_info's (projection, components, tree
 start, L1 stage and the PCG part of it, IRLS stage, total), with the CG steps per batched Newton solve (one CG for the three
-coordinates; each solve's count is rounded up to the probe interval 5) and per IRLS step (laa_step probes every 25 steps, so that
+coordinates; each solve's count is rounded up to the probe interval 5) and per IRLS step (laa_step goes through the same PCG,
+laa_pcg in csrc/laa.hip, and probes every 25 steps, so that
 figure is an upper bound in steps of 25), and the mean / median rotation error after Rotation_Alignment.
 
     python tools/irls_stages.py [--configs C2,C4] [--modes GM,L12] [--reps 2]
