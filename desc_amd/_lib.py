@@ -31,7 +31,7 @@ EXPORTS = [
     "desc_pgd_shard_finish", "desc_pgd_shard_objective", "desc_pgd_shard_set_collectives", "desc_pgd_shard_start",
     "desc_pgd_shard_iterate", "desc_pgd_shard_run", "desc_pgd_stopped", "desc_device_synchronize", "desc_memcpy_d2h", "desc_memcpy_h2d", "desc_debug_band_plan", "desc_debug_spmm_variants", "desc_debug_wg_clock", "desc_debug_wg_plan", "desc_debug_last_sweep", "desc_debug_shard_layout", "desc_trim_memory", "desc_spectral_run", "desc_cemp_run", "desc_refine_run",
     "desc_marshal_edges", "desc_marshal_rij", "desc_mst_run", "desc_mst_run_dev", "desc_mpls_run", "desc_mpls_run_dev",
-    "desc_irls_run", "desc_irls_run_dev",
+    "desc_irls_run", "desc_irls_run_dev", "desc_lp_params_default", "desc_lp_sij_run", "desc_lp_sij_run_dev",
 ]
 
 I32P = C.POINTER(C.c_int32)
@@ -122,6 +122,17 @@ class IrlsInfo(C.Structure):
                 ("warned_edges", C.c_int32), ("cg_iters_l1", C.c_int32), ("cg_iters_irls", C.c_int32), ("cg_unconverged", C.c_int32),
                 ("pd_solves", C.c_int32), ("cg_residual", C.c_double), ("ms_project", C.c_double), ("ms_components", C.c_double),
                 ("ms_tree", C.c_double), ("ms_l1", C.c_double), ("ms_l1_pcg", C.c_double), ("ms_irls", C.c_double), ("ms_total", C.c_double)]
+
+
+class LpParams(C.Structure):
+    _fields_ = [("nsample", C.c_int32), ("check_every", C.c_int32), ("seed", C.c_uint64), ("tol", C.c_double), ("max_iter", C.c_int32),
+                ("restart", C.c_int32), ("verbose", C.c_int32), ("reserved", C.c_int32), ("pos_out", I32P)]
+
+
+class LpInfo(C.Structure):
+    _fields_ = [("nsample", C.c_int32), ("iters", C.c_int32), ("restarts", C.c_int32), ("converged", C.c_int32), ("m_pos", C.c_int64),
+                ("rows", C.c_int64), ("viol", C.c_double), ("pobj", C.c_double), ("dobj", C.c_double), ("ms_samples", C.c_double),
+                ("ms_transpose", C.c_double), ("ms_loop", C.c_double), ("ms_col", C.c_double), ("ms_row", C.c_double), ("ms_total", C.c_double)]
 
 
 IRLS_GM, IRLS_L12 = 0, 1
@@ -231,6 +242,10 @@ def load():
     L.desc_mpls_run_dev.argtypes = [C.c_void_p, C.POINTER(MplsParams), F64P, F64P, F64P, C.POINTER(MplsInfo)]
     L.desc_irls_run.argtypes = [C.POINTER(Problem), C.POINTER(IrlsParams), C.c_int32, F64P, F64P, C.POINTER(IrlsInfo)]
     L.desc_irls_run_dev.argtypes = [C.c_void_p, C.POINTER(IrlsParams), F64P, F64P, C.POINTER(IrlsInfo)]
+    L.desc_lp_params_default.argtypes = [C.POINTER(LpParams)]
+    L.desc_lp_params_default.restype = None
+    L.desc_lp_sij_run.argtypes = [C.POINTER(Problem), C.POINTER(LpParams), C.c_int32, F64P, F64P, I32P, C.POINTER(LpInfo)]
+    L.desc_lp_sij_run_dev.argtypes = [C.c_void_p, C.POINTER(LpParams), F64P, F64P, I32P, C.POINTER(LpInfo)]
     _lib = L
     return L
 
@@ -715,6 +730,55 @@ def irls_run(prob, mode, max_iter_l1=10, max_iter_irls=100, sigma_deg=5.0, R_ini
         check(L.desc_irls_run(C.byref(prob.c), C.byref(p), device, ptr(R, F64P), ptr(R1, F64P), C.byref(info)))
     shape = lambda a: a[:9 * n].reshape((3, 3, n), order="F")      # noqa: E731
     return shape(R), shape(R1), {k: getattr(info, k) for k, _ in IrlsInfo._fields_}
+
+
+def default_lp_params():
+    p = LpParams()
+    load().desc_lp_params_default(C.byref(p))
+    return p
+
+
+def lp_sij_run(prob, params=None, device=0, want_y=False, want_k=True):
+    """desc_lp_sij_run[_dev] -> (S_vec (m,), y (m_pos, nsample, 2) or None, k (m_pos, nsample) 1-based or None, info dict); sorted edge order.
+    With want_k the info dict also holds "pos_edges", the 0-based (sorted) edge ids of the LP's variables.
+    prob: ProblemArrays or DeviceProblem; params: LpParams (None: the defaults)."""
+    m = prob.m
+    p = params if params is not None else default_lp_params()
+    L = load()
+    S = out_buffer(m)
+    info = LpInfo()
+
+    def call(pp, y, k):
+        if isinstance(prob, DeviceProblem):
+            check(L.desc_lp_sij_run_dev(prob.handle, C.byref(pp), ptr(S, F64P), ptr(y, F64P), ptr(k, I32P), C.byref(info)))
+        else:
+            check(L.desc_lp_sij_run(C.byref(prob.c), C.byref(pp), device, ptr(S, F64P), ptr(y, F64P), ptr(k, I32P), C.byref(info)))
+
+    y = k = None
+    ns = int(p.nsample)
+    mp = m
+    if want_y or want_k:                    # the buffers are sized by nsample and m_pos: a call without steps and outputs returns the sizes
+        q = LpParams.from_buffer_copy(p)
+        q.max_iter = 0
+        call(q, None, None)
+        ns, mp = int(info.nsample), int(info.m_pos)
+    if want_y:
+        y = out_buffer(2 * ns * mp)
+    pos = None
+    if want_k:
+        k = out_buffer(ns * mp, np.int32)
+        pos = out_buffer(mp, np.int32)
+        p = LpParams.from_buffer_copy(p)
+        p.pos_out = ptr(pos, I32P)
+    call(p, y, k)
+    out = {name: getattr(info, name) for name, _ in LpInfo._fields_}
+    mp, ns = int(info.m_pos), int(info.nsample)
+    if y is not None:
+        y = y[:2 * ns * mp].reshape(mp, ns, 2)
+    if k is not None:
+        k = k[:ns * mp].reshape(mp, ns)
+        out["pos_edges"] = pos[:mp].copy()
+    return S[:m], y, k, out
 
 
 def spmm_variants(dprob: DeviceProblem, reps=20):

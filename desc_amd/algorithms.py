@@ -442,16 +442,14 @@ def IRLS_L12(RijMat, Ind, Rinit=None, SIGMA=5, MaxIterations=(10, 100), device=0
     return _irls(_lib.IRLS_L12, RijMat, Ind, Rinit, SIGMA, MaxIterations, device, verbose, return_info)
 
 
-def DESC(Ind, RijMat, params, return_info=False):
-    """[R_est, R_init, S_vec] = DESC(Ind, RijMat, params) -- Algorithms/DESC.m:14 (the call of
-    Demo/compare_algorithms.m:72): DESC_PGD (:16-261) -> GCW initialisation (:263) -> reweighted
-    Lie-algebraic refinement (:265-313).  All three stages run on the GPU."""
+def _pgd_with_upload(Ind, RijMat, params, body):
+    """DESC_PGD with the upload of the device problem overlapped (a helper thread), then body(dprob, perm, S_vec, S_sorted, info) on it."""
     n, ii, jj, rij, perm = marshal_edges(Ind, RijMat)
     if ii.shape[0] == 0:
         raise ValueError("empty edge list")
     prob = _lib.ProblemArrays(n, ii, jj, rij)
     device = int(_get(params, "device", 0))
-    # Ind / RijMat / CSR index go to HBM once for all three stages -- on a helper thread, while DESC_PGD builds the cycle structure (which needs
+    # Ind / RijMat / CSR index go to HBM once for all stages -- on a helper thread, while DESC_PGD builds the cycle structure (which needs
     # only the edge list): DESC_PGD asks for the device problem when it creates the solver
     import threading
     box = {}
@@ -473,11 +471,22 @@ def DESC(Ind, RijMat, params, return_info=False):
             raise box["err"]
         return box["dp"]
 
-    dprob = None
     try:
         S_vec, info = DESC_PGD(Ind, RijMat, params, return_info=True, _marshalled=(perm, prob, _dprob))
         dprob = _dprob()
         S_sorted = S_vec if perm is None else S_vec[perm]
+        return body(dprob, S_vec, S_sorted, info)
+    finally:
+        th.join()
+        if "dp" in box:
+            box["dp"].free()
+
+
+def DESC(Ind, RijMat, params, return_info=False):
+    """[R_est, R_init, S_vec] = DESC(Ind, RijMat, params) -- Algorithms/DESC.m:14 (the call of
+    Demo/compare_algorithms.m:72): DESC_PGD (:16-261) -> GCW initialisation (:263) -> reweighted
+    Lie-algebraic refinement (:265-313).  All three stages run on the GPU."""
+    def body(dprob, S_vec, S_sorted, info):
         R_init, ginfo = _lib.gcw_run(dprob, S_sorted)                    # GCW.m:9-36, weights (GCW.m:20) formed on the device
         verbose = bool(_get(params, "verbose", True))
         if verbose:
@@ -485,13 +494,89 @@ def DESC(Ind, RijMat, params, return_info=False):
         R_est, rinfo = _lib.refine_run(dprob, S_sorted, R_init, verbose=verbose)
         if verbose:
             print("DONE!")                                                                    # DESC.m:313
+        if return_info:
+            return R_est, R_init, S_vec, dict(pgd=info, gcw=ginfo, refine=rinfo)
+        return R_est, R_init, S_vec
+
+    return _pgd_with_upload(Ind, RijMat, params, body)
+
+
+def DESC_init(Ind, RijMat, params, return_info=False):
+    """[R_est, S_vec] = DESC_init(Ind, RijMat, params) -- Algorithms/DESC_init.m: DESC_PGD followed by GCW, without the refinement: what
+    DESC() returns as R_init and S_vec.  Both stages run on one device problem, uploaded while the cycle structure is built.  With
+    ``params.make_plots`` the info dict holds DESC_PGD's traces; the two CSV files the reference appends to when plotting
+    (DESC_init.m:262-263) are written only when ``params.csv_dir`` names a directory: one row of MSE_means to
+    ``linear_convergence_rotation_error.csv`` and one of svec_errors to ``linear_convergence_svec_error.csv``."""
+    def body(dprob, S_vec, S_sorted, info):
+        R_est, ginfo = _lib.gcw_run(dprob, S_sorted)                     # DESC_init.m: R_est = GCW(Ind, AdjMat, RijMat, S_vec)
+        csv_dir = _get(params, "csv_dir")
+        if csv_dir is not None and bool(_get(params, "make_plots", False)):
+            for name, key in (("linear_convergence_rotation_error", "MSE_means"), ("linear_convergence_svec_error", "svec_errors")):
+                with open(os.path.join(str(csv_dir), name + ".csv"), "a") as f:                  # :262-263 (dlmwrite ... '-append': 5 digits)
+                    f.write(",".join("%.5g" % v for v in info[key]) + "\n")
+        if return_info:
+            return R_est, S_vec, dict(pgd=info, gcw=ginfo)
+        return R_est, S_vec
+
+    return _pgd_with_upload(Ind, RijMat, params, body)
+
+
+def linprog_sij(Ind, RijMat, params=None, return_info=False):
+    """[Rest, S_vec] = linprog_sij(Ind, RijMat) -- Algorithms/linprog_sij.m:16.  Three stages on one device problem:
+    the LP  min sum s_ij  s.t.  |s_ij - d_ijk| <= s_ik + s_jk on sampled 3-cycles, 0 <= s <= 1 (:16-139; a matrix-free PDHG solver on
+    the GPU, desc_lp_sij_run_dev), the row-normalised weighted spectral step with weights exp(-5 S_vec) (:154-174), and the reweighted
+    Lie-algebraic refinement of DESC.m:265-313 with maxIters = 200 (:176-351).  Edges without a 3-cycle keep S_vec = 1.
+
+    Optional ``params`` fields, none of them in the reference: ``seed`` (cycle sampling; MATLAB uses its global RNG), ``device``,
+    ``tol`` (1e-4), ``max_iter`` (200000), ``nsample`` (the rule of :43), ``verbose``, ``return_dual``.  With ``return_info`` a third
+    result: the LP record (``lp``: nsample, m_pos, rows, iters, restarts, converged, viol, pobj, dobj, stage milliseconds),
+    ``pos_edges`` (0-based rows of the caller's ``Ind`` that are LP variables, in variable order), ``k`` (m_pos x nsample sampled third
+    nodes, 1-based), ``y`` (m_pos x nsample x 2 row duals, with ``return_dual``), ``R_gcw`` and the ``spectral`` / ``refine`` records.
+    The LP optimum is not unique: compare solutions through viol / pobj / dobj, not element by element."""
+    params = {} if params is None else params
+    n, ii, jj, rij, perm = marshal_edges(Ind, RijMat)
+    if ii.shape[0] == 0:
+        raise ValueError("empty edge list")
+    prob = _lib.ProblemArrays(n, ii, jj, rij)
+    p = _lib.default_lp_params()
+    p.seed = int(_get(params, "seed", 0))
+    if _get(params, "tol") is not None:
+        p.tol = float(_get(params, "tol"))
+    if _get(params, "max_iter") is not None:
+        p.max_iter = int(_get(params, "max_iter"))
+    if _get(params, "nsample") is not None:
+        p.nsample = int(_get(params, "nsample"))
+    for name in ("check_every", "restart"):                  # test / measurement hooks
+        if _get(params, name) is not None:
+            setattr(p, name, int(_get(params, name)))
+    verbose = _get(params, "verbose", False)
+    p.verbose = int(verbose) if not isinstance(verbose, bool) else (1 if verbose else 0)
+    want_y = bool(_get(params, "return_dual", False))
+    if p.verbose:
+        import sys
+        sys.stdout.flush()
+    dprob = _lib.DeviceProblem(prob, int(_get(params, "device", 0)))
+    try:
+        S, y, k, lpinfo = _lib.lp_sij_run(dprob, p, want_y=want_y, want_k=bool(return_info))
+        if p.verbose:
+            for _ in range(1000, int(lpinfo["m_pos"]) + 1, 1000):
+                print("next 1000 done")                                                       # linprog_sij.m:115-117
+        R_gcw, sinfo = _lib.spectral_run(dprob, np.exp(-5.0 * S), True)                       # :154-174, beta_T = 5
+        Rest, rinfo = _lib.refine_run(dprob, S, R_gcw, 1e-3, 200)                             # :176-351 (the per-step line is commented out, :293)
+        if p.verbose and rinfo["iters"] >= 200:
+            print("Max iterations reached")                                                   # :349
     finally:
-        th.join()
-        if "dp" in box:
-            box["dp"].free()
-    if return_info:
-        return R_est, R_init, S_vec, dict(pgd=info, gcw=ginfo, refine=rinfo)
-    return R_est, R_init, S_vec
+        dprob.free()
+    S_vec = S
+    if perm is not None:
+        S_vec = np.empty_like(S); S_vec[perm] = S
+    if not return_info:
+        return Rest, S_vec
+    pos = lpinfo.pop("pos_edges")
+    info = dict(lp=lpinfo, pos_edges=pos if perm is None else perm[pos], k=k, R_gcw=R_gcw, spectral=sinfo, refine=rinfo)
+    if want_y:
+        info["y"] = y
+    return Rest, S_vec, info
 
 
 def Rotation_Alignment(R_est, R_gt):

@@ -22,7 +22,7 @@ struct CempState : DevArena {                             // owns its device blo
 };
 
 // CEMP.m:44-103: samples, S0Mat and the initial SVec.  need_poe: also build d_poe whenever some edge has no cycle (MPLS reads it on both
-// paths); DESC_ERR_TOO_LARGE when m_pos * nsample reaches 2^31.
+// paths); DESC_ERR_TOO_LARGE when m_pos * nsample reaches 2^31.  nsample <= 0: the rule of linprog_sij.m:43 (st.nsample says what it gave).
 int cemp_build(const desc_device_problem* dp, int32_t nsample, uint64_t seed, bool need_poe, CempState& st);
 // CEMP.m:107-128: max_iter rounds, beta[it] padded with its last entry; verbose: the reference's per-round line (:127)
 int cemp_rounds(const desc_device_problem* dp, CempState& st, const double* beta, int32_t n_beta, int32_t max_iter, bool verbose);

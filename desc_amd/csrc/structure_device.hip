@@ -609,7 +609,7 @@ int build_structure_device(const desc_problem* prob, int32_t n_sample_min, uint6
 }
 
 int build_cemp_samples_device(const desc_device_problem* dp, int32_t nsample, uint64_t seed, int64_t* m_pos,
-                              int32_t** o_pos, int32_t** o_k, int32_t** o_ejk, int32_t** o_eki, uint32_t** o_pk, int32_t* o_max_deg) {
+                              int32_t** o_pos, int32_t** o_k, int32_t** o_ejk, int32_t** o_eki, uint32_t** o_pk, int32_t* o_max_deg, int32_t* o_nsample) {
     const int64_t n = dp->n, m = dp->m;
     const int64_t words = (n + 63) / 64;
     *m_pos = 0; *o_pos = *o_k = *o_ejk = *o_eki = nullptr;
@@ -641,6 +641,21 @@ int build_cemp_samples_device(const desc_device_problem* dp, int32_t nsample, ui
     DESC_HIP(hipMemcpy(hist.data(), d_hist, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToHost));
     int32_t max_codeg = 0;
     for (int64_t c = 1; c <= n; ++c) if (hist[c]) max_codeg = (int32_t)c;
+    if (nsample <= 0) {                                                   // the rule of DESC_PGD.m:43 / linprog_sij.m:43, from the histogram
+        int64_t hp = 0;
+        for (int64_t c = 1; c <= n; ++c) hp += hist[c];
+        nsample = 30;
+        if (hp > 0) {
+            auto kth = [&](int64_t r) {        // r-th smallest positive codegree, r = 0-based
+                int64_t acc = 0;
+                for (int64_t c = 1; c <= n; ++c) { acc += hist[c]; if (acc > r) return (double)c; }
+                return (double)max_codeg;
+            };
+            const double med = (hp & 1) ? kth(hp / 2) : 0.5 * (kth(hp / 2 - 1) + kth(hp / 2));     // MATLAB median
+            nsample = std::max(30, (int32_t)std::ceil(med / 4.0));
+        }
+    }
+    if (o_nsample) *o_nsample = nsample;
     const bool all_pos = m > 0 && hist[0] == 0;
     if (!all_pos) {
         hvec<int32_t> codeg((size_t)m);

@@ -448,6 +448,48 @@ int desc_irls_run(const desc_problem* prob, const desc_irls_params* params, int3
 int desc_irls_run_dev(const desc_device_problem* dp, const desc_irls_params* params, double* R_out, double* R_l1,
                       desc_irls_info* info);
 
+/* ------------------------------------------------------------------ linprog_sij -- */
+/* S_vec of Algorithms/linprog_sij.m:16-139: the LP  min sum_l s_l  s.t.  |s_l - d_lt| <= s_ik + s_jk  on nsample sampled 3-cycles per edge
+ * with cycles ("pos" edges, ascending edge order), 0 <= s <= 1; edges without a cycle keep 1 (:104).  nsample = 0: the rule
+ * max(ceil(median(codeg of pos edges) / 4), 30) (:43, = desc_structure_info.n_sample of the same graph).  The t-th sample of edge l is
+ * CoInd[desc_sample_key(seed, l, t) mod codeg] (desc_cemp_run's rule, in place of datasample at :68).  Rows of cycle (l, t) with
+ * d = S0Mat(t, l), a = {i,k}, b = {j,k}:  s_l - s_a - s_b <= d  and  -s_l - s_a - s_b <= -d.  One deliberate departure: :84-85 index
+ * Ind_i(l) / Ind_j(l) with l running over the pos edges; the edge's own endpoints are used (equal whenever every edge lies on a triangle).
+ * Solver (lp.hip): matrix-free PDHG on the device in f64,  x+ = clip(x - tau o (1 + K'y), 0, 1),  y+ = max(y + sigma o (K(2x+ - x) - b), 0),
+ * tau_l = 1 / (w sum_r |K_rl|), sigma_r = w / 3, primal weight w = 1 until the first restart; restarts to the running average as in PDLP.
+ * Every check_every steps:  viol = max_r max((Kx - b)_r, 0),  P = sum x,  D = -b'y + sum_l min(0, 1 + (K'y)_l) (<= the optimum for every
+ * y >= 0); stop when viol <= tol and P - D <= tol (1 + |P| + |D|).  Reaching max_iter is no error: converged = 0 and a warning on stderr.
+ * restart = 0 and tol = 0: exactly max_iter plain steps from x = 0, y = 0 with w = 1.  Two runs on the same input return the same bits.
+ * s_vec: m doubles.  y (nullable): 2 nsample m_pos doubles, [pos edge][t][row 1, row 2].  k_out (nullable): nsample m_pos sampled third
+ * nodes, 1-based, [pos edge][t].  A call with max_iter = 0 and y = k_out = NULL takes no step and only fills info (nsample, m_pos, rows):
+ * what a caller needs to size y, k_out and params->pos_out. */
+typedef struct desc_lp_params {
+    int32_t nsample;          /* 0: the rule of :43                                            */
+    int32_t check_every;      /* steps between two evaluations of the certificates; 0: 64      */
+    uint64_t seed;            /* cycle-sampling key                                            */
+    double  tol;              /* 1e-4                                                          */
+    int32_t max_iter;         /* 200000                                                        */
+    int32_t restart;          /* 1: averages, restarts and primal weight; 0: the plain recurrence */
+    int32_t verbose;          /* 1: one line per check; 2: also hipEvent laps of the two kernels (every step synchronises) */
+    int32_t reserved;
+    int32_t* pos_out;         /* nullable: receives the m_pos pos edges (0-based edge ids, ascending): the LP's variables */
+} desc_lp_params;             /* 48 bytes */
+void desc_lp_params_default(desc_lp_params* p);
+typedef struct desc_lp_info {
+    int32_t nsample, iters, restarts, converged;
+    int64_t m_pos, rows;      /* variables; inequality rows = 2 nsample m_pos                  */
+    double  viol, pobj, dobj; /* the certificates of what was returned                         */
+    double  ms_samples;       /* samples + S0Mat                                               */
+    double  ms_transpose;     /* the transposed incidence                                      */
+    double  ms_loop;
+    double  ms_col, ms_row;   /* verbose = 2: mean per step of the two kernels                 */
+    double  ms_total;
+} desc_lp_info;               /* 104 bytes */
+int desc_lp_sij_run(const desc_problem* prob, const desc_lp_params* params, int32_t device, double* s_vec, double* y, int32_t* k_out,
+                    desc_lp_info* info);
+int desc_lp_sij_run_dev(const desc_device_problem* dp, const desc_lp_params* params, double* s_vec, double* y, int32_t* k_out,
+                        desc_lp_info* info);
+
 /* One-shot: what the MEX shim calls.  Builds the structure (p->build_where),
  * uploads, runs, downloads, frees. */
 int desc_pgd_solve(const desc_problem* prob, const desc_params* p, desc_result* r);

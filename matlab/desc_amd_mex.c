@@ -57,7 +57,7 @@ static int at_exit_registered = 0;
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (!at_exit_registered) { mexAtExit(release_parked_blocks); at_exit_registered = 1; }
     char cmd[32];
-    if (nrhs < 3 || mxGetString(prhs[0], cmd, sizeof cmd)) mexErrMsgIdAndTxt("desc_amd:cmd", "first argument: 'spectral' | 'gcw' | 'cemp' | 'refine' | 'desc' | 'mpls' | 'cemp_gcw' | 'irls_gm' | 'irls_l12'");
+    if (nrhs < 3 || mxGetString(prhs[0], cmd, sizeof cmd)) mexErrMsgIdAndTxt("desc_amd:cmd", "first argument: 'spectral' | 'gcw' | 'cemp' | 'refine' | 'desc' | 'mpls' | 'cemp_gcw' | 'irls_gm' | 'irls_l12' | 'lp'");
     desc_problem prob;
     problem_from(prhs[1], prhs[2], &prob);
     int rc = DESC_OK;
@@ -124,6 +124,54 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             rc = desc_spectral_run_dev(dp, w, 1, 0.0, 0, mxGetPr(plhs[0]), NULL);                               /* :145-160 */
         }
         if (dp) desc_problem_free(dp);
+    } else if (!strcmp(cmd, "lp")) {
+        /* [Rest, S_vec, info] = ('lp', Ind0, RijMat [, opt]): Algorithms/linprog_sij.m -- the LP (:16-139), the spectral step weighted by
+         * exp(-5 S_vec) (:154-174) and the refinement with maxIters = 200 (:176-351) on one device problem */
+        if (nrhs > 3 && !mxIsStruct(prhs[3])) mexErrMsgIdAndTxt("desc_amd:lp", "usage: ('lp', Ind0, RijMat [, opt])");
+        desc_lp_params lp;
+        desc_lp_params_default(&lp);
+        int32_t device = 0;
+        if (nrhs > 3) {
+            lp.seed = (uint64_t)field_or(prhs[3], "seed", 0);
+            lp.tol = field_or(prhs[3], "tol", lp.tol);
+            lp.max_iter = (int32_t)field_or(prhs[3], "max_iter", lp.max_iter);
+            lp.nsample = (int32_t)field_or(prhs[3], "nsample", 0);
+            lp.verbose = (int32_t)field_or(prhs[3], "verbose", 0);
+            device = (int32_t)field_or(prhs[3], "device", 0);
+        }
+        mxArray* S = mxCreateDoubleMatrix(1, prob.m, mxREAL);
+        mxArray* W = mxCreateDoubleMatrix(1, prob.m, mxREAL);
+        mxArray* R_gcw = rotations(prob.n);
+        plhs[0] = rotations(prob.n);
+        desc_lp_info li; memset(&li, 0, sizeof li);
+        desc_refine_info rinfo; memset(&rinfo, 0, sizeof rinfo);
+        desc_device_problem* dp = NULL;
+        rc = desc_problem_upload(&prob, device, &dp);
+        if (rc == DESC_OK) rc = desc_lp_sij_run_dev(dp, &lp, mxGetPr(S), NULL, NULL, &li);
+        if (rc == DESC_OK) {
+            const double* s = mxGetPr(S); double* w = mxGetPr(W);
+            for (int64_t e = 0; e < prob.m; ++e) w[e] = exp(-5.0 * s[e]);                                         /* :156, beta_T = 5 */
+            rc = desc_spectral_run_dev(dp, w, 1, 0.0, 0, mxGetPr(R_gcw), NULL);                                  /* :154-174 */
+        }
+        if (rc == DESC_OK) rc = desc_refine_run_dev(dp, mxGetPr(S), mxGetPr(R_gcw), 1e-3, 200, mxGetPr(plhs[0]), &rinfo);   /* :176-351 */
+        if (dp) desc_problem_free(dp);
+        if (rc == DESC_OK && rinfo.iters >= 200) mexPrintf("Max iterations reached\n");                          /* :349 */
+        if (nlhs > 1) plhs[1] = S;
+        if (nlhs > 2) {
+            const char* names[] = {"nsample", "m_pos", "rows", "iters", "restarts", "converged", "viol", "pobj", "dobj", "R_gcw", "refine_iters"};
+            plhs[2] = mxCreateStructMatrix(1, 1, 11, names);
+            mxSetField(plhs[2], 0, "nsample", mxCreateDoubleScalar(li.nsample));
+            mxSetField(plhs[2], 0, "m_pos", mxCreateDoubleScalar((double)li.m_pos));
+            mxSetField(plhs[2], 0, "rows", mxCreateDoubleScalar((double)li.rows));
+            mxSetField(plhs[2], 0, "iters", mxCreateDoubleScalar(li.iters));
+            mxSetField(plhs[2], 0, "restarts", mxCreateDoubleScalar(li.restarts));
+            mxSetField(plhs[2], 0, "converged", mxCreateDoubleScalar(li.converged));
+            mxSetField(plhs[2], 0, "viol", mxCreateDoubleScalar(li.viol));
+            mxSetField(plhs[2], 0, "pobj", mxCreateDoubleScalar(li.pobj));
+            mxSetField(plhs[2], 0, "dobj", mxCreateDoubleScalar(li.dobj));
+            mxSetField(plhs[2], 0, "R_gcw", R_gcw);
+            mxSetField(plhs[2], 0, "refine_iters", mxCreateDoubleScalar(rinfo.iters));
+        }
     } else if (!strcmp(cmd, "refine")) {
         if (nrhs < 5 || mxGetNumberOfElements(prhs[3]) != (mwSize)prob.m || mxGetNumberOfElements(prhs[4]) != (mwSize)(9 * prob.n))
             mexErrMsgIdAndTxt("desc_amd:refine", "usage: ('refine', Ind0, RijMat, S_vec (m), R_init (3x3xn))");
