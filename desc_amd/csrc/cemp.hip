@@ -342,11 +342,13 @@ int cemp_build(const desc_device_problem* dp, int32_t nsample, uint64_t seed, bo
     int64_t mp = 0;
     int32_t max_deg = 0;
     const bool want_tiles = env_int_c("DESC_DEBUG_CEMP_TILES", 1) != 0;
+    const bool by_rule = nsample <= 0;              // the caller left nsample to the sampler's rule (linprog_sij.m:43)
     rc = build_cemp_samples_device(dp, nsample, seed, &mp, &st.d_pos, &st.d_k, &st.d_ejk, &st.d_eki, want_tiles ? &st.d_pk : nullptr, &max_deg, &nsample);
-    st.nsample = nsample;                           // nsample <= 0 on entry: the sampler's rule (linprog_sij.m:43)
+    st.nsample = nsample;                           // by_rule: the value the sampler's rule gave
     for (void* q : {(void*)st.d_pos, (void*)st.d_k, (void*)st.d_ejk, (void*)st.d_eki, (void*)st.d_pk}) if (q) st.blocks.push_back(q);
     if (rc == DESC_ERR_TOO_LARGE) {
-        if (nsample <= 0) return rc;                // the rule needs the device sampler's codegree histogram
+        if (by_rule) return rc;                     // the rule is the device sampler's: no host fall-back without an explicit nsample (the sampler
+                                                    // hands the rule's value back before it refuses, so nsample itself no longer tells)
         hvec<int32_t> pos_edge, kk, e_jk, e_ki;
         const desc_problem hv = host_view(dp);
         if ((rc = build_cemp_samples_host(&hv, nsample, seed, pos_edge, kk, e_jk, e_ki))) return rc;

@@ -518,6 +518,11 @@ static int spectral_impl(const desc_device_problem* dp, const double* weights, c
     double res_prev = -1.0;
     double *d_P, *d_Q;
     if ((rc = D.alloc(&d_P, rows * BW)) || (rc = D.alloc(&d_Q, rows * BW))) return rc;
+    // The fixed scheme has no cap on what a pass amplifies: where the wanted eigenvalues stand far above everything else (a row-normalised
+    // star: spectrum {1, 0, -1}) a pass of degree 16 lifts them ~1e13 over the guard vectors and the Gram matrix of the filtered block is
+    // singular.  It keeps a copy of the basis and repeats such a pass with half the degree.
+    double* d_Xkeep = nullptr;
+    if (!tight && (rc = D.alloc(&d_Xkeep, rows * BW))) return rc;
     double theta[BW] = {}, Z[BW * BW], res = 1e300;
     int it = 0, products = 0;
     bool converged = false;
@@ -552,7 +557,10 @@ static int spectral_impl(const desc_device_problem* dp, const double* weights, c
         cut = theta[BW - 1];
         const double top = theta[0];
         if (tight_ok && it >= 2) {
-            if (theta[BW - 1] <= lo || (res_prev > 0.0 && res > res_prev)) { lo = -sigma; tight_ok = false; }          // drifting to the negative end: the safe bound
+            if (theta[BW - 1] <= lo || (res_prev > 0.0 && res > res_prev)) {          // drifting to the negative end: the safe bound
+                lo = -sigma; tight_ok = false;
+                if (timing) fprintf(stderr, "[desc_amd] spectral  outer %d: back to the safe lower bound %.6g (theta_6 %.6g, residual %.3e after %.3e)\n", it, lo, theta[BW - 1], res, res_prev);
+            }
             else lo = std::max(-sigma, -std::max(2.0 * std::max(std::fabs(theta[3]), std::fabs(theta[BW - 1])), 0.02 * sigma));
         }
         if (!(cut > lo) || !(top > cut)) cut = lo + 0.5 * (top - lo);   // degenerate block: fall back to a mild filter
@@ -565,26 +573,38 @@ static int spectral_impl(const desc_device_problem* dp, const double* weights, c
                 cheb_deg = (int)std::max<double>(CHEB_MIN, std::min<double>(CHEB_DEG, std::ceil(std::min(want, cap) / std::acosh(xi3))));
             }
         }
-        res_prev = res; deg_prev = cheb_deg;
-        double s_prev = e / (top - c);
-        const double s1c = s_prev;
-        // P = (A X - c X) * s_prev / e
-        spmm(d_X, d_X, d_P, s_prev / e, -c * s_prev / e, 0.0);
-        double* Xp = d_X; double* Pp = d_P; double* Qp = d_Q;  // X_{k-1}, X_k, scratch
-        for (int k = 2; k <= cheb_deg; ++k) {
-            const double s_new = 1.0 / (2.0 / s1c - s_prev);
-            // Q = (2 s_new / e) (A P - c P) - (s_prev s_new) X_{k-1}
-            spmm(Pp, Xp, Qp, 2.0 * s_new / e, -2.0 * s_new * c / e, -s_prev * s_new);
-            double* t3 = Xp; Xp = Pp; Pp = Qp; Qp = t3;
-            s_prev = s_new;
+        if (!tight) cheb_deg = CHEB_DEG;
+        if (d_Xkeep) DESC_HIP(hipMemcpyAsync(d_Xkeep, d_X, sizeof(double) * rows * BW, hipMemcpyDeviceToDevice, 0));
+        res_prev = res;
+        double* Pp = nullptr;
+        for (;;) {
+            deg_prev = cheb_deg;
+            double s_prev = e / (top - c);
+            const double s1c = s_prev;
+            // P = (A X - c X) * s_prev / e
+            spmm(d_X, d_X, d_P, s_prev / e, -c * s_prev / e, 0.0);
+            double* Xp = d_X; Pp = d_P; double* Qp = d_Q;           // X_{k-1}, X_k, scratch
+            for (int k = 2; k <= cheb_deg; ++k) {
+                const double s_new = 1.0 / (2.0 / s1c - s_prev);
+                // Q = (2 s_new / e) (A P - c P) - (s_prev s_new) X_{k-1}
+                spmm(Pp, Xp, Qp, 2.0 * s_new / e, -2.0 * s_new * c / e, -s_prev * s_new);
+                double* t3 = Xp; Xp = Pp; Pp = Qp; Qp = t3;
+                s_prev = s_new;
+            }
+            // ---- X <- orth(filtered block)
+            if ((rc = grams(Pp, Pp))) return rc;
+            SmallMat Co;
+            if (!ortho_coeffs(G2, Ident, Co)) {
+                if (!d_Xkeep || cheb_deg <= CHEB_MIN) return fail(DESC_ERR_INVALID, "subspace iteration broke down (rank-deficient block)");
+                cheb_deg = std::max(CHEB_MIN, cheb_deg / 2);         // fixed scheme: the same pass again from the kept basis, half the degree
+                DESC_HIP(hipMemcpyAsync(d_X, d_Xkeep, sizeof(double) * rows * BW, hipMemcpyDeviceToDevice, 0));
+                continue;
+            }
+            double* Xn = (Pp == d_X) ? (Xp == d_P ? d_Q : d_P) : d_X;       // a buffer that is not Pp
+            hipLaunchKernelGGL(k_combine, dim3(512), dim3(256), 0, 0, Pp, Xn, rows, Co);
+            if (Xn != d_X) DESC_HIP(hipMemcpyAsync(d_X, Xn, sizeof(double) * rows * BW, hipMemcpyDeviceToDevice, 0));
+            break;
         }
-        // ---- X <- orth(filtered block)
-        if ((rc = grams(Pp, Pp))) return rc;
-        SmallMat Co;
-        if (!ortho_coeffs(G2, Ident, Co)) return fail(DESC_ERR_INVALID, "subspace iteration broke down (rank-deficient block)");
-        double* Xn = (Pp == d_X) ? (Xp == d_P ? d_Q : d_P) : d_X;       // a buffer that is not Pp
-        hipLaunchKernelGGL(k_combine, dim3(512), dim3(256), 0, 0, Pp, Xn, rows, Co);
-        if (Xn != d_X) DESC_HIP(hipMemcpyAsync(d_X, Xn, sizeof(double) * rows * BW, hipMemcpyDeviceToDevice, 0));
     }
     // Ritz vectors of the converged subspace: V = X Z (X still holds the basis G1 was formed with)
     // Z belongs to the basis in d_X in both exits (the loop leaves right after a Rayleigh-Ritz,

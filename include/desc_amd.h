@@ -462,7 +462,11 @@ int desc_irls_run_dev(const desc_device_problem* dp, const desc_irls_params* par
  * restart = 0 and tol = 0: exactly max_iter plain steps from x = 0, y = 0 with w = 1.  Two runs on the same input return the same bits.
  * s_vec: m doubles.  y (nullable): 2 nsample m_pos doubles, [pos edge][t][row 1, row 2].  k_out (nullable): nsample m_pos sampled third
  * nodes, 1-based, [pos edge][t].  A call with max_iter = 0 and y = k_out = NULL takes no step and only fills info (nsample, m_pos, rows):
- * what a caller needs to size y, k_out and params->pos_out. */
+ * what a caller needs to size y, k_out and params->pos_out.
+ * Size limits: 2 nsample m_pos < 2^31 (DESC_ERR_TOO_LARGE).  The cycles are sampled on the device while no edge has more than 4096
+ * common neighbours; beyond that the host sampler takes over -- same keyed rule, same samples -- but only for an explicit nsample > 0.
+ * With nsample = 0 (the rule, which belongs to the device sampler) such a graph is refused: DESC_ERR_TOO_LARGE, "an edge has <c> common
+ * neighbours".  Pass nsample to solve it. */
 typedef struct desc_lp_params {
     int32_t nsample;          /* 0: the rule of :43                                            */
     int32_t check_every;      /* steps between two evaluations of the certificates; 0: 64      */
