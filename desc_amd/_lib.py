@@ -14,7 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DESC_AMD_LIB", os.path.join(HERE, "libdesc_amd.so"))   # override: diagnostic builds only
 
 DESC_OK = 0
-STEP_CONSTANT, STEP_PIECEWISE, STEP_HYBRID = 0, 1, 2
+STEP_CONSTANT, STEP_PIECEWISE, STEP_HYBRID, STEP_EXTERNAL = 0, 1, 2, 3
+MEM_HOST, MEM_DEVICE = 0, 1
 BUILD_HOST, BUILD_DEVICE = 0, 1
 
 # every symbol include/desc_amd.h declares (tests check that the library exports them)
@@ -32,6 +33,7 @@ EXPORTS = [
     "desc_pgd_shard_iterate", "desc_pgd_shard_run", "desc_pgd_stopped", "desc_device_synchronize", "desc_memcpy_d2h", "desc_memcpy_h2d", "desc_debug_band_plan", "desc_debug_spmm_variants", "desc_debug_wg_clock", "desc_debug_wg_plan", "desc_debug_last_sweep", "desc_debug_shard_layout", "desc_trim_memory", "desc_spectral_run", "desc_cemp_run", "desc_refine_run",
     "desc_marshal_edges", "desc_marshal_rij", "desc_mst_run", "desc_mst_run_dev", "desc_mpls_run", "desc_mpls_run_dev",
     "desc_irls_run", "desc_irls_run_dev", "desc_lp_params_default", "desc_lp_sij_run", "desc_lp_sij_run_dev",
+    "desc_pgd_ext_begin", "desc_pgd_ext_grad", "desc_pgd_ext_apply", "desc_pgd_ext_laps",
 ]
 
 I32P = C.POINTER(C.c_int32)
@@ -193,6 +195,10 @@ def load():
     L.desc_pgd_iterate_timed.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.desc_pgd_sync.argtypes = [C.c_void_p]
     L.desc_pgd_download.argtypes = [C.c_void_p, C.POINTER(Result)]
+    L.desc_pgd_ext_begin.argtypes = [C.c_void_p, C.POINTER(Params)]
+    L.desc_pgd_ext_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    L.desc_pgd_ext_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, F64P, F64P, I32P]
+    L.desc_pgd_ext_laps.argtypes = [C.c_void_p, F64P]
     L.desc_pgd_get_s0.argtypes = [C.c_void_p, F64P]
     L.desc_pgd_sizes.argtypes = [C.c_void_p, I64P, I64P, I64P, I32P]
     L.desc_pgd_solve.argtypes = [C.POINTER(Problem), C.POINTER(Params), C.POINTER(Result)]
@@ -401,6 +407,48 @@ class Structure:
             pass
 
 
+def validate_step(step, m_cycle, like=None):
+    """What a GetStep callback returned (DESC_PGD.m:207), checked before it reaches the library: a float64 vector of m_cycle entries --
+    a NumPy array, or, when the gradient was handed out as the torch tensor `like`, a tensor on the same device.  Returns it contiguous
+    and flat.  ValueError otherwise; whether the values are finite is the caller's business, as in the reference."""
+    if like is not None:
+        import torch
+        if not isinstance(step, torch.Tensor):
+            raise ValueError(f"GetStep was given a torch tensor and must return one, not {type(step).__name__}")
+        if step.dtype != like.dtype:
+            raise ValueError(f"GetStep must return a {like.dtype} tensor, not {step.dtype}")
+        if step.device != like.device:
+            raise ValueError(f"GetStep must return a tensor on {like.device}, not on {step.device}")
+        if step.numel() != m_cycle:
+            raise ValueError(f"GetStep must return m_cycle = {m_cycle} entries, not {step.numel()}")
+        return step.detach().reshape(-1).contiguous()
+    if not isinstance(step, np.ndarray):
+        raise ValueError(f"GetStep must return a NumPy array of m_cycle = {m_cycle} float64 entries, not {type(step).__name__}")
+    if step.dtype != np.float64:
+        raise ValueError(f"GetStep must return a float64 array, not {step.dtype}")
+    if step.size != m_cycle:
+        raise ValueError(f"GetStep must return m_cycle = {m_cycle} entries, not {step.size}")
+    return np.ascontiguousarray(step).reshape(-1)
+
+
+def torch_for_device_mode():
+    """torch for a plugin with ``device_tensors = True``.  PyTorch bundles its own ROCm runtime and a process can hold only one: torch
+    has to be imported before this library is loaded (see load()).  DescError when that is no longer possible, when torch is not
+    installed, or when it sees no GPU."""
+    import sys
+    if "torch" not in sys.modules and _lib is not None:
+        raise DescError("a plugin with device_tensors = True needs torch, and torch must be imported before libdesc_amd.so is loaded: "
+                        "import torch first (or set DESC_AMD_PRELOAD_TORCH=1)", ERR_STATE)
+    try:
+        import torch
+    except ImportError as e:
+        raise DescError(f"a plugin with device_tensors = True needs torch, which cannot be imported ({e}); "
+                        "without it the plugin runs in the NumPy mode (device_tensors = False)", ERR_STATE) from None
+    if not torch.cuda.is_available():
+        raise DescError("a plugin with device_tensors = True needs a GPU that torch can see (torch.cuda.is_available() is False)", ERR_HIP)
+    return torch
+
+
 class Solver:
     """Owner of a desc_pgd* (problem + structure resident in HBM)."""
 
@@ -494,6 +542,79 @@ class Solver:
         k = out["iters_run"]
         out["svec_errors"] = se[:k]
         out["R_est_all"] = Rall[:k * 9 * n].reshape(k, 9 * n).reshape((k, n, 3, 3)).transpose(0, 3, 2, 1)     # (t, r, c, node) from 3 x 3 x n column-major
+        return out
+
+    # ---- caller-supplied step rule (desc_pgd_ext_*): the iteration cut at DESC_PGD.m:207
+    def ext_begin(self, params: Params):
+        self._iters_cap = params.iters
+        check(load().desc_pgd_ext_begin(self.handle, C.byref(params)))
+
+    def ext_grad(self, out, where=MEM_HOST):
+        """grad_long of the current iterate into `out`: a float64 NumPy array of m_cycle entries, or (where=MEM_DEVICE) a device address."""
+        check(load().desc_pgd_ext_grad(self.handle, C.c_void_p(out.ctypes.data if isinstance(out, np.ndarray) else int(out)), where))
+
+    def ext_apply(self, step, where=MEM_HOST):
+        """Finish the iteration with `step` (as ext_grad's `out`) -> (average_change, objective, stopped)."""
+        avg, obj, stop = C.c_double(), C.c_double(), C.c_int32()
+        check(load().desc_pgd_ext_apply(self.handle, C.c_void_p(step.ctypes.data if isinstance(step, np.ndarray) else int(step)), where,
+                                        C.byref(avg), C.byref(obj), C.byref(stop)))
+        return avg.value, obj.value, bool(stop.value)
+
+    def ext_laps(self):
+        """Device milliseconds of the last gradient pass, apply pass, objective + stop rule."""
+        out = np.zeros(3)
+        check(load().desc_pgd_ext_laps(self.handle, ptr(out, F64P)))
+        return tuple(float(x) for x in out)
+
+    def run_external(self, params: Params, get_step, device_tensors=False, device=0, want_w=False, progress=None, after_step=None):
+        """The PGD loop (DESC_PGD.m:182-257) around a step rule the library does not know: per iteration the gradient pass, then
+        ``step = get_step(grad_long)`` (:207), then the apply pass with the objective and the stop rule.  ``get_step`` is called exactly
+        iters_run times.  ``grad_long`` and the step are in the reference's cycle order (segment l at cum_ind[l] .. cum_ind[l+1]).
+
+        Default mode: ``grad_long`` is a fresh float64 NumPy array and a NumPy array comes back -- 2 x 8 m_cycle bytes cross PCIe per
+        iteration: slow, always available.  ``device_tensors``: ``grad_long`` is a float64 torch tensor on ``cuda:<device>`` that the
+        gradient pass wrote in place (read-only for the callback; it is overwritten by the next iteration) and the returned tensor is
+        read in place after torch's current stream has been synchronised: no per-cycle data leaves the device.
+
+        progress(it, average_change, objective) and after_step(it) are called after every applied step."""
+        p = Params.from_buffer_copy(params)
+        p.step_kind = STEP_EXTERNAL
+        p.progress = None; p.progress_user = None; p.verbose = 0
+        mc = self.m_cycle
+        torch = grad_t = None
+        if device_tensors:
+            torch = torch_for_device_mode()
+            dev = torch.device("cuda", device)
+            grad_t = torch.empty(max(mc, 1), dtype=torch.float64, device=dev)[:mc]
+        else:
+            grad_buf = out_buffer(mc)
+        import time
+        t0 = time.perf_counter()
+        self.ext_begin(p)
+        calls = 0
+        for it in range(1, p.iters + 1):
+            if device_tensors:
+                self.ext_grad(grad_t.data_ptr(), MEM_DEVICE)
+                step = get_step(grad_t)
+                calls += 1
+                step = validate_step(step, mc, like=grad_t)
+                torch.cuda.current_stream(dev).synchronize()          # the step must be complete: the library orders only its own stream
+                avg, obj, stopped = self.ext_apply(step.data_ptr(), MEM_DEVICE)
+            else:
+                self.ext_grad(grad_buf, MEM_HOST)
+                step = get_step(grad_buf[:mc].copy())                 # value semantics, as MATLAB's: a plugin may keep what it is given
+                calls += 1
+                step = validate_step(step, mc)
+                avg, obj, stopped = self.ext_apply(step, MEM_HOST)
+            if progress is not None:
+                progress(it, avg, obj)
+            if after_step is not None:
+                after_step(it)                                        # :235-239 come before the stop test of the same iteration
+            if stopped:
+                break
+        out = self.download(want_w=want_w)
+        out["ms_total"] = (time.perf_counter() - t0) * 1e3
+        out["calls"] = calls
         return out
 
     def reset(self, params: Params):

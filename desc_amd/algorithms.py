@@ -105,18 +105,30 @@ def gradient_to_params(G, p: _lib.Params):
         p.decay_interval = float(G.decay_interval)
         p.hybrid_strategy = int(G.strategy)
         p.t0 = int(G.t)
+    elif callable(getattr(G, "GetStep", None)):
+        # any other handle object with a GetStep method (DESC_PGD.m:207): the library hands out grad_long and takes the step back
+        p.step_kind = _lib.STEP_EXTERNAL
+        p.t0 = 0
     else:
-        raise TypeError("params.Gradient must be a ConstantStepSize, PiecewiseStepSize or HybridGradient "
-                        "object (Utils/*.m); arbitrary GetStep callbacks cannot run inside the HIP sweep")
+        raise TypeError("params.Gradient must be an object with a callable GetStep(grad_long) method (DESC_PGD.m:207): a "
+                        "ConstantStepSize, PiecewiseStepSize or HybridGradient (Utils/*.m), which run inside the HIP sweep, "
+                        "or any plugin of your own, which runs between the gradient pass and the apply pass")
+
+
+def is_external(G):
+    """True for a params.Gradient plugin the library does not know by class: its GetStep is called from the loop."""
+    return not isinstance(G, (ConstantStepSize, PiecewiseStepSize, HybridGradient)) and callable(getattr(G, "GetStep", None))
 
 
 def make_c_params(params):
+    G = _get(params, "Gradient")
+    if G is not None and is_external(G) and getattr(G, "device_tensors", False):
+        _lib.torch_for_device_mode()          # torch has to come before the library is loaded
     p = _lib.default_params()
     iters = _get(params, "iters")
     if iters is None:
         raise ValueError("params.iters is required (DESC_PGD.m:170)")
     p.iters = int(iters)
-    G = _get(params, "Gradient")
     if G is None:
         raise ValueError("params.Gradient is required (DESC_PGD.m:207)")
     gradient_to_params(G, p)
@@ -133,6 +145,14 @@ def DESC_PGD(Ind, RijMat, params, return_info=False, _marshalled=None):
     Returns the estimated corruption level of every edge (length-m vector in the
     caller's edge order).  With ``return_info`` also a dict with the objective and
     average-change traces, iteration count, timings and structure sizes.
+
+    ``params.Gradient`` is any object with a ``GetStep(grad_long)`` method (:207).  The three classes of desc_amd.stepsize (and their
+    subclasses) run inside the HIP sweep.  Any other object is called once per iteration between the gradient pass and the apply pass
+    (_run_external): by default with a NumPy float64 array of m_cycle entries, returning one (2 x 8 m_cycle bytes over PCIe per
+    iteration: slow, always available); with the attribute ``device_tensors = True`` with a float64 torch tensor on the solver's GPU,
+    read-only, returning a tensor of the same dtype, device and length (import torch before desc_amd loads its library).
+    ``grad_long`` follows the cycle order of the problem sorted by (i, j): segment l at cum_ind[l] .. cum_ind[l+1]; an unsorted ``Ind``
+    permutes the edge vectors only.
     ``_marshalled`` (internal, used by DESC()): (perm, ProblemArrays, DeviceProblem or a callable that returns it) already prepared."""
     p, G = make_c_params(params)
     make_plots = bool(_get(params, "make_plots", False))
@@ -155,7 +175,8 @@ def DESC_PGD(Ind, RijMat, params, return_info=False, _marshalled=None):
         p.progress = C.cast(cb, C.c_void_p)
         p.verbose = 0
     hybrid_state = isinstance(G, HybridGradient) and G.strategy == 0       # carries m_cycle-long moment vectors in and out
-    if _marshalled is None and not make_plots and not return_info and not hybrid_state:
+    external = is_external(G)                                              # a plugin of the caller's: its GetStep runs between two passes
+    if _marshalled is None and not make_plots and not return_info and not hybrid_state and not external:
         # the reference's own signature, S_vec = DESC_PGD(Ind, RijMat, params): ONE C call (desc_pgd_solve), in which the rotations go up
         # while the structure is built (C4: 13 ms hidden)
         if verbose:
@@ -199,7 +220,9 @@ def DESC_PGD(Ind, RijMat, params, return_info=False, _marshalled=None):
             if mt.shape[0] != solver.m_cycle:
                 raise ValueError("HybridGradient state has a different length than this problem's cycle vector")
             adam = (np.ascontiguousarray(mt, dtype=np.float64).copy(), np.ascontiguousarray(vt, dtype=np.float64).copy())
-        if not make_plots:
+        if external:
+            out = _run_external(solver, p, G, params, prob, dprob, perm, verbose, make_plots)
+        elif not make_plots:
             out = solver.run(p, adam=adam)
         else:
             out = _run_with_plots(solver, p, params, prob, dprob, perm, verbose, adam)
@@ -247,6 +270,44 @@ def _run_with_plots(solver, p, params, prob, dprob, perm, verbose, adam=None):
     svec_errors = out["svec_errors"]
     k = out["iters_run"]
     out["svec_errors"] = np.array(svec_errors[:k]); out["MSE_means"] = np.array(mse_means[:k]); out["MSE_medians"] = np.array(mse_medians[:k])
+    return out
+
+
+def _run_external(solver, p, G, params, prob, dprob, perm, verbose, make_plots):
+    """The loop of DESC_PGD.m:182-257 around a plugin the library does not know (Solver.run_external): G.GetStep is called once per
+    iteration, exactly iters_run times, with grad_long in the cycle order of the SORTED problem (an unsorted Ind permutes the edge vectors
+    only: segment l belongs to the l-th edge with cycles in (i, j) order).  A plugin with ``device_tensors = True`` is given and returns
+    float64 torch tensors on the solver's GPU; any other plugin NumPy arrays.  What GetStep raises propagates unchanged.  With
+    make_plots, :235-239 run after every applied step and give the keys of _run_with_plots."""
+    line = None
+    if verbose:
+        def line(it, avg, obj):
+            print("iter %d: average change in S_vec %f, objective value: %f" % (it, avg, obj), flush=True)      # DESC_PGD.m:241
+    after = own = None
+    if make_plots:
+        if not isinstance(dprob, _lib.DeviceProblem):
+            own = dprob = _lib.DeviceProblem(prob, p.device)
+        ErrVec = np.asarray(_get(params, "ErrVec"), dtype=np.float64).reshape(-1)
+        R_orig = np.asarray(_get(params, "R_orig"), dtype=np.float64)
+        if perm is not None:
+            ErrVec = ErrVec[perm]
+        svec_errors, mse_means, mse_medians = [], [], []
+
+        def after(it):
+            S = solver.download()["S_vec"]
+            svec_errors.append(float(np.mean(np.abs(ErrVec - S))))                               # :236
+            R_est, _ = _lib.gcw_run(dprob, S)                                                    # :237
+            _, _, mean_e, med_e = Rotation_Alignment(R_est, R_orig)                              # :238
+            mse_means.append(mean_e); mse_medians.append(med_e)
+    try:
+        out = solver.run_external(p, G.GetStep, device_tensors=bool(getattr(G, "device_tensors", False)), device=p.device,
+                                  progress=line, after_step=after)
+    finally:
+        if own is not None:
+            own.free()
+    if make_plots:
+        k = out["iters_run"]
+        out["svec_errors"] = np.array(svec_errors[:k]); out["MSE_means"] = np.array(mse_means[:k]); out["MSE_medians"] = np.array(mse_medians[:k])
     return out
 
 

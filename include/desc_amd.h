@@ -43,6 +43,12 @@ extern "C" {
 #define DESC_STEP_CONSTANT   0   /* Utils/ConstantStepSize.m:9-11   step = -lr*g                       */
 #define DESC_STEP_PIECEWISE  1   /* Utils/PiecewiseStepSize.m:13-18 step = -lr/(fix(t/decay)+1)*g      */
 #define DESC_STEP_HYBRID     2   /* Utils/HybridGradient.m:23-41    Adam, or 100*lr/(fix(t/decay)+1)   */
+#define DESC_STEP_EXTERNAL   3   /* params.Gradient is an object the library does not know: the caller
+                                    supplies the step of every iteration (the stepping calls below)    */
+
+/* where a per-cycle vector of the stepping calls lives */
+#define DESC_MEM_HOST        0
+#define DESC_MEM_DEVICE      1   /* device memory on the handle's device                               */
 
 /* where a-1..a-3 (graph, codegree, sampling, mirror maps) are built */
 #define DESC_BUILD_HOST      0
@@ -211,6 +217,36 @@ int desc_pgd_sizes(const desc_pgd* h, int64_t* m, int64_t* m_pos, int64_t* m_cyc
 int desc_pgd_layout_stats(const desc_pgd* h, int64_t* out, int32_t cap);
 /* name of the main-sweep kernel variant chosen for this handle (rocprof cross-reference) */
 const char* desc_pgd_kernel_name(const desc_pgd* h);
+
+/* ------------------------------------------- caller-supplied step rule -- */
+/* DESC_PGD.m:207 reads  wijk = wijk + params.Gradient.GetStep(grad_long)  for ANY handle object with a GetStep method.  The three
+ * classes of Utils/ run inside the sweep (DESC_STEP_CONSTANT / PIECEWISE / HYBRID); every other rule runs through these calls, which
+ * cut the iteration at that line: the library computes grad_long, the caller turns it into a step, the library finishes the iteration.
+ *     desc_pgd_ext_begin(h, p);                          p->step_kind == DESC_STEP_EXTERNAL; lr, beta*, decay_interval are not read
+ *     for (t = 1; t <= p->iters; ++t) {
+ *         desc_pgd_ext_grad(h, grad, where);             :185-204 on the current iterate
+ *         ... step = GetStep(grad) ...                   :207, the caller's
+ *         desc_pgd_ext_apply(h, step, where, &avg, &obj, &stopped);      :207-257
+ *         if (stopped) break;                            the patience rule of :243-256 (p->patience, p->stop_tol)
+ *     }
+ *     desc_pgd_download(h, &r);                          iters_run = steps applied, t_end = p->t0 + iters_run, traces filled
+ * grad_long and step hold m_cycle doubles in the reference's cycle order: segment l (the l-th edge with cycles, desc_structure_view
+ * pos_edge[l]) at cum_ind[l] .. cum_ind[l+1], its entries in the order of k (IJK) -- whatever layout the handle keeps internally.
+ * where = DESC_MEM_HOST: caller host memory, copied down / up (2 x 8 m_cycle bytes per iteration: the slow mode that always works).
+ * where = DESC_MEM_DEVICE: device memory of the handle's device; the two passes write / read it in place and no per-cycle data moves
+ * between host and device -- only the three scalars do.  The step buffer must be COMPLETE when desc_pgd_ext_apply is called: the
+ * library orders its work on the handle's own stream only, so a caller that fills the buffer on another stream synchronises that
+ * stream first.  desc_pgd_ext_grad must not be given a buffer the caller still reads on another stream.  Both calls return with
+ * the handle's stream synchronised: grad_long is complete, step may be reused.  A non-finite step is the caller's business.
+ * Call order: begin, then grad / apply in turns.  apply without a gradient handed out for the iteration, either call before begin,
+ * after the stop rule fired or after p->iters steps, and any of the three on a sharded handle (world > 1): DESC_ERR_STATE, nothing is
+ * launched.  desc_pgd_reset / desc_pgd_run return the handle to the built-in rules. */
+int desc_pgd_ext_begin(desc_pgd* h, const desc_params* p);                                             /* :148-180 */
+int desc_pgd_ext_grad(desc_pgd* h, double* grad_long, int32_t where);                                  /* :185-204 */
+int desc_pgd_ext_apply(desc_pgd* h, const double* step, int32_t where,                                 /* :207-257 */
+                       double* average_change, double* objective, int32_t* stopped);
+/* device milliseconds (HIP events) of the last gradient pass, apply pass, and objective + stop rule (tools/stepfn_stages.py) */
+int desc_pgd_ext_laps(const desc_pgd* h, double* ms3);
 
 /* ------------------------------------------------------------- multi-GPU -- */
 /* One process per GPU.  The edges with cycles (in the library's band-major order) are cut
