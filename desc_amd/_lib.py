@@ -34,6 +34,8 @@ EXPORTS = [
     "desc_marshal_edges", "desc_marshal_rij", "desc_mst_run", "desc_mst_run_dev", "desc_mpls_run", "desc_mpls_run_dev",
     "desc_irls_run", "desc_irls_run_dev", "desc_lp_params_default", "desc_lp_sij_run", "desc_lp_sij_run_dev",
     "desc_pgd_ext_begin", "desc_pgd_ext_grad", "desc_pgd_ext_apply", "desc_pgd_ext_laps",
+    "desc_pgd_batch_create", "desc_pgd_batch_sizes", "desc_pgd_batch_get_structure", "desc_pgd_batch_get_s0", "desc_pgd_batch_run",
+    "desc_pgd_batch_destroy", "desc_pgd_batch_concat",
 ]
 
 I32P = C.POINTER(C.c_int32)
@@ -74,6 +76,12 @@ class Result(C.Structure):
     _fields_ = [("s_vec", F64P), ("obj_trace", F64P), ("avg_change_trace", F64P), ("w", F64P),
                 ("adam_m", F64P), ("adam_v", F64P), ("iters_run", C.c_int32), ("t_end", C.c_int32),
                 ("ms_structure", C.c_double), ("ms_upload", C.c_double), ("ms_cycle_d", C.c_double),
+                ("ms_pgd", C.c_double), ("ms_total", C.c_double)]
+
+
+class BatchResult(C.Structure):
+    _fields_ = [("s_vec", F64P), ("obj_trace", F64P), ("avg_change_trace", F64P), ("w", F64P), ("adam_m", F64P), ("adam_v", F64P),
+                ("iters_run", I32P), ("t_end", I32P), ("ms_structure", C.c_double), ("ms_upload", C.c_double), ("ms_cycle_d", C.c_double),
                 ("ms_pgd", C.c_double), ("ms_total", C.c_double)]
 
 
@@ -252,6 +260,14 @@ def load():
     L.desc_lp_params_default.restype = None
     L.desc_lp_sij_run.argtypes = [C.POINTER(Problem), C.POINTER(LpParams), C.c_int32, F64P, F64P, I32P, C.POINTER(LpInfo)]
     L.desc_lp_sij_run_dev.argtypes = [C.c_void_p, C.POINTER(LpParams), F64P, F64P, I32P, C.POINTER(LpInfo)]
+    L.desc_pgd_batch_create.argtypes = [C.POINTER(Problem), C.c_int32, C.POINTER(Params), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p)]
+    L.desc_pgd_batch_sizes.argtypes = [C.c_void_p, I32P, I64P, I64P, I32P]
+    L.desc_pgd_batch_get_structure.argtypes = [C.c_void_p, C.c_int32, C.POINTER(StructureView)]
+    L.desc_pgd_batch_get_s0.argtypes = [C.c_void_p, F64P]
+    L.desc_pgd_batch_run.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(BatchResult)]
+    L.desc_pgd_batch_destroy.argtypes = [C.c_void_p]
+    L.desc_pgd_batch_destroy.restype = None
+    L.desc_pgd_batch_concat.argtypes = [C.POINTER(C.c_void_p), C.c_int32, I64P, I64P, I64P, I32P, I32P, I32P, I32P, I32P, I32P]
     _lib = L
     return L
 
@@ -405,6 +421,99 @@ class Structure:
             self.free()
         except Exception:
             pass
+
+
+class Batch:
+    """Owner of a desc_pgd_batch*: B independent problems behind one another in one set of device arrays (desc_pgd_batch_*).
+    ``probs`` is a sequence of ProblemArrays; ``seeds`` an optional sequence of per-problem sampling seeds."""
+
+    def __init__(self, probs, params: Params, seeds=None):
+        self.probs = list(probs)                     # keeps the NumPy buffers alive
+        self.count = B = len(self.probs)
+        arr = (Problem * max(B, 1))(*[q.c for q in self.probs])
+        sd = None
+        if seeds is not None:
+            if len(seeds) != B:
+                raise ValueError(f"seeds must hold one entry per problem ({B}), not {len(seeds)}")
+            sd = (C.c_uint64 * max(B, 1))(*[int(x) for x in seeds])
+        h = C.c_void_p()
+        check(load().desc_pgd_batch_create(arr, B, C.byref(params), sd, C.byref(h)))
+        self.handle = h
+        eo, co, ns = np.zeros(B + 1, dtype=np.int64), np.zeros(B + 1, dtype=np.int64), np.zeros(max(B, 1), dtype=np.int32)
+        check(load().desc_pgd_batch_sizes(h, None, ptr(eo, I64P), ptr(co, I64P), ptr(ns, I32P)))
+        self.edge_off, self.cycle_off, self.n_sample = eo, co, ns[:B]
+        self.m, self.m_cycle = int(eo[B]), int(co[B])
+
+    def structure(self, b):
+        v = StructureView()
+        check(load().desc_pgd_batch_get_structure(self.handle, b, C.byref(v)))
+        return _view_arrays(v)
+
+    def s0(self):
+        """S0_long of every problem (a list of per-problem vectors)."""
+        out = out_buffer(self.m_cycle)
+        check(load().desc_pgd_batch_get_s0(self.handle, ptr(out, F64P)))
+        return [out[self.cycle_off[b]:self.cycle_off[b + 1]] for b in range(self.count)]
+
+    def run(self, params: Params, want_w=False, adam=None):
+        """One batched run.  adam: (m_t, v_t), two writable contiguous float64 arrays of cycle_off[count] entries, read when
+        params.t0 > 0 and written.  Returns a list of per-problem dicts (views of the concatenated buffers) and the call's timings."""
+        B, iters = self.count, int(params.iters)
+        bufs = dict(s_vec=out_buffer(self.m), obj=out_buffer(B * iters), avg=out_buffer(B * iters), iters_run=out_buffer(B, np.int32),
+                    t_end=out_buffer(B, np.int32))
+        r = BatchResult()
+        r.s_vec, r.obj_trace, r.avg_change_trace = ptr(bufs["s_vec"], F64P), ptr(bufs["obj"], F64P), ptr(bufs["avg"], F64P)
+        r.iters_run, r.t_end = ptr(bufs["iters_run"], I32P), ptr(bufs["t_end"], I32P)
+        if want_w:
+            bufs["w"] = out_buffer(self.m_cycle)
+            r.w = ptr(bufs["w"], F64P)
+        if adam is not None:
+            for a in adam:
+                if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.flags.writeable
+                        and (a.size == self.m_cycle or self.m_cycle == 0)):
+                    raise ValueError(f"Adam state must be two writable contiguous float64 arrays of {self.m_cycle} entries (all problems' cycles)")
+            r.adam_m, r.adam_v = ptr(adam[0], F64P), ptr(adam[1], F64P)
+        check(load().desc_pgd_batch_run(self.handle, C.byref(params), C.byref(r)))
+        outs = []
+        for b in range(B):
+            e0, e1, c0, c1 = self.edge_off[b], self.edge_off[b + 1], self.cycle_off[b], self.cycle_off[b + 1]
+            it = int(bufs["iters_run"][b])
+            o = dict(S_vec=bufs["s_vec"][e0:e1], obj=bufs["obj"][b * iters:b * iters + it], avg=bufs["avg"][b * iters:b * iters + it],
+                     iters_run=it, t_end=int(bufs["t_end"][b]), n_sample=int(self.n_sample[b]))
+            if want_w:
+                o["w"] = bufs["w"][c0:c1]
+            if adam is not None:
+                o["adam_m"], o["adam_v"] = adam[0][c0:c1], adam[1][c0:c1]
+            outs.append(o)
+        timings = dict(ms_structure=r.ms_structure, ms_upload=r.ms_upload, ms_cycle_d=r.ms_cycle_d, ms_pgd=r.ms_pgd, ms_total=r.ms_total)
+        return outs, timings
+
+    def destroy(self):
+        if self.handle:
+            load().desc_pgd_batch_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def batch_concat(structures):
+    """desc_pgd_batch_concat on a list of Structure objects: the host part of the batch set-up (offsets and globalised index arrays)."""
+    B = len(structures)
+    hs = (C.c_void_p * max(B, 1))(*[s.handle for s in structures])
+    eo, co, so = (np.zeros(B + 1, dtype=np.int64) for _ in range(3))
+    L = load()
+    check(L.desc_pgd_batch_concat(hs, B, ptr(eo, I64P), ptr(co, I64P), ptr(so, I64P), None, None, None, None, None, None))
+    mp, mc = int(so[B]), int(co[B])
+    pos, cum = out_buffer(mp, np.int32), out_buffer(mp + 1, np.int32)
+    ejk, eki, ikj, jki = (out_buffer(mc, np.int32) for _ in range(4))
+    check(L.desc_pgd_batch_concat(hs, B, ptr(eo, I64P), ptr(co, I64P), ptr(so, I64P), ptr(pos, I32P), ptr(cum, I32P), ptr(ejk, I32P),
+                                  ptr(eki, I32P), ptr(ikj, I32P), ptr(jki, I32P)))
+    return dict(edge_off=eo, cycle_off=co, seg_off=so, pos_edge=pos[:mp], cum=cum[:mp + 1], e_jk=ejk[:mc], e_ki=eki[:mc], ikj=ikj[:mc],
+                jki=jki[:mc])
 
 
 def validate_step(step, m_cycle, like=None):

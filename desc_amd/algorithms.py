@@ -247,6 +247,87 @@ def DESC_PGD(Ind, RijMat, params, return_info=False, _marshalled=None):
     return S_vec
 
 
+def DESC_PGD_batch(problems, params, seeds=None, return_info=False):
+    """DESC_PGD on B independent problems in one GPU pass (desc_pgd_batch_*; the reference has no such call).
+
+    ``problems`` is a sequence of ``(Ind, RijMat)`` pairs or of model objects with ``.Ind`` / ``.RijMat``; ``params`` as for DESC_PGD,
+    one for the whole batch; ``seeds`` an optional sequence of per-problem sampling seeds (default: ``params.seed`` for every problem).
+    Problem b gets what ``DESC_PGD(Ind_b, RijMat_b, params)`` returns with the same seed and the host structure builder: its own
+    n_sample, traces, patience rule and stop iteration; its result does not depend, in any bit, on the batch around it.
+
+    Returns a list of S_vec arrays (caller's edge order).  With ``return_info`` a list of dicts: ``S_vec``, ``iters_run``, ``obj_vals``,
+    ``average_change``, ``n_sample``, ``w`` (cycle order of the problem sorted by (i, j)), ``t_end`` and the call's ``timings``; with a
+    HybridGradient (Adam) also ``m_t`` / ``v_t``.  The plugin object is shared by the batch and is NOT updated: its counter ``t`` is
+    read as the starting counter of every problem, the moments start at zero, and each problem's state comes back in its dict.
+
+    Refused (ValueError): a Gradient object of the caller's own (external GetStep), ``make_plots``, a problem whose n_sample exceeds 64
+    (solve it with DESC_PGD)."""
+    import collections.abc
+    if isinstance(problems, (str, bytes, np.ndarray)) or not isinstance(problems, collections.abc.Sequence):
+        raise ValueError("problems must be a sequence of (Ind, RijMat) pairs or of model objects with .Ind / .RijMat")
+    G = _get(params, "Gradient")
+    if G is not None and is_external(G):
+        raise ValueError("DESC_PGD_batch runs the three step rules of Utils/ (ConstantStepSize, PiecewiseStepSize, HybridGradient); "
+                         "a Gradient object with a GetStep of its own runs through DESC_PGD, one problem at a time")
+    if bool(_get(params, "make_plots", False)):
+        raise ValueError("DESC_PGD_batch does not support params.make_plots: use DESC_PGD for the traced run of one problem")
+    B = len(problems)
+    if seeds is not None:
+        seeds = [int(x) for x in seeds]
+        if len(seeds) != B:
+            raise ValueError(f"seeds must hold one entry per problem ({B}), not {len(seeds)}")
+    p, G = make_c_params(params)
+    p.verbose = 0
+    if B == 0:
+        return []
+    probs, perms = [], []
+    for b, item in enumerate(problems):
+        if hasattr(item, "Ind") and hasattr(item, "RijMat"):
+            Ind, RijMat = item.Ind, item.RijMat
+        else:
+            try:
+                Ind, RijMat = item
+            except (TypeError, ValueError):
+                raise ValueError(f"problem {b}: expected an (Ind, RijMat) pair or an object with .Ind / .RijMat") from None
+        try:
+            n, ii, jj, rij, perm = marshal_edges(Ind, RijMat)
+        except ValueError as e:
+            raise ValueError(f"problem {b}: {e}") from None
+        if ii.shape[0] == 0:
+            raise ValueError(f"problem {b}: empty edge list")
+        probs.append(_lib.ProblemArrays(n, ii, jj, rij))
+        perms.append(perm)
+    try:
+        batch = _lib.Batch(probs, p, seeds)
+    except _lib.DescError as e:
+        if e.code == _lib.ERR_INVALID:
+            raise ValueError(str(e).split(": ", 1)[-1]) from None
+        raise
+    try:
+        hybrid = isinstance(G, HybridGradient) and G.strategy == 0
+        adam = (np.zeros(max(batch.m_cycle, 1)), np.zeros(max(batch.m_cycle, 1))) if hybrid else None
+        if adam is not None:
+            adam = (adam[0][:batch.m_cycle], adam[1][:batch.m_cycle])
+        outs, timings = batch.run(p, want_w=return_info, adam=adam)
+    finally:
+        batch.destroy()
+    result = []
+    for o, perm in zip(outs, perms):
+        S_vec = o["S_vec"]
+        if perm is not None:
+            S_sorted, S_vec = S_vec, np.empty_like(S_vec)
+            S_vec[perm] = S_sorted
+        if not return_info:
+            result.append(S_vec)
+            continue
+        d = dict(S_vec=S_vec, iters_run=o["iters_run"], obj_vals=o["obj"], average_change=o["avg"], n_sample=o["n_sample"], w=o["w"],
+                 t_end=o["t_end"], timings=timings)
+        if hybrid:
+            d["m_t"], d["v_t"] = o["adam_m"], o["adam_v"]
+        result.append(d)
+    return result
+
+
 def _run_with_plots(solver, p, params, prob, dprob, perm, verbose, adam=None):
     """params.make_plots = true (DESC_PGD.m:235-239): after every iteration the error of S_vec against params.ErrVec and
     the rotation error of GCW(S_vec) against params.R_orig (GlobalSOdCorrectRight = the alignment of Rotation_Alignment).

@@ -94,6 +94,8 @@ namespace desc {
 // a-1..a-3 on the host (structure_host.cpp)
 int build_structure_host(const desc_problem* prob, int32_t n_sample_min, uint64_t seed,
                          desc_structure* out);
+// set by a caller that already runs one builder per host thread (batch.hip): this thread's build_structure_host starts no threads of its own
+extern thread_local bool g_structure_serial;
 // a-1..a-3 on the device (structure_device.hip)
 int build_structure_device(const desc_problem* prob, int32_t n_sample_min, uint64_t seed,
                            int32_t device, desc_structure* out);

@@ -56,6 +56,7 @@
 
 #include "device_utils.h"
 #include "node_plan.h"
+#include "pgd_math.h"
 
 namespace desc {
 
@@ -68,81 +69,9 @@ struct DevState {
                            // iterations evaluates the objective early, the next sweep must not count it again
 };
 
-struct StepArgs {
-    const double* adam_m;                 // HybridGradient.m_t / v_t before this GetStep call ...
-    const double* adam_v;
-    double* adam_m_out;                   // ... and after it: double-buffered like w, because the stop decision for
-    double* adam_v_out;                   // iteration t falls during sweep t+1, whose update must be discardable
-    double step;                          // step size of this GetStep call
-    double lr, beta1, beta2, bc1, bc2;    // Adam (HybridGradient.m:28-35)
-};
-
-__device__ __forceinline__ double abs_acos_ext(double x) {
-    // MATLAB abs(acos(x)) with the complex extension outside [-1,1] (DESC_PGD.m:147)
-    if (x > 1.0) return acosh(x);
-    if (x < -1.0) return hypot(M_PI, acosh(-x));
-    return acos(x);
-}
-
 // The mirror-weight sums travel as 64-bit fixed-point integers (k_colsum_node: order-independent adds; sharded runs reduce-scatter them as
 // ncclInt64, so the totals -- and with them S_vec and the weights -- are bitwise the same for every number of ranks).  `t` holds the bits.
 __device__ __forceinline__ double fx_to_double(double t, double fx_inv) { return (double)__double_as_longlong(t) * fx_inv; }
-
-template <int STEP>
-__device__ __forceinline__ double apply_step(const StepArgs& a, double w, double g, int64_t c) {
-    if (STEP == DESC_STEP_HYBRID) {               // HybridGradient.m:28-35 (strategy 0)
-        double mt = (a.beta1 * a.adam_m[c]) + (1.0 - a.beta1) * g;
-        double vt = (a.beta2 * a.adam_v[c]) + (1.0 - a.beta2) * (g * g);
-        a.adam_m_out[c] = mt; a.adam_v_out[c] = vt;
-        double cm = mt / a.bc1, cv = vt / a.bc2;
-        return w + (-a.lr * cm / (sqrt(cv) + 1e-8));
-    }
-    return w + (-a.step * g);                     // ConstantStepSize.m:10 / PiecewiseStepSize.m:17
-}
-
-// Simplex projection threshold (DESC_PGD.m:215-223) for one segment held one value per
-// lane in a group of G lanes: T with sum(max(ws - T, 0)) = 1.  Michelot's fixed point
-// reaches the same active set as the reference's sort-and-scan (the first sorted i with
-// sum(w(i:end)-w(i)) < 1).
-template <int G>
-__device__ __forceinline__ double simplex_threshold(double ws, bool act0, int lane) {
-    bool act = act0;
-    double T = 0.0;
-    for (;;) {
-        const double s = group_sum<G>(act ? ws : 0.0);
-        const int na = group_count<G>(act, lane);
-        T = (s - 1.0) / (double)max(na, 1);
-        const bool keep = act && (ws > T);
-        const bool changed = keep != act;
-        act = keep;
-        if (!__any(changed)) break;
-    }
-    return T;
-}
-
-// product-of-three trace in the reference's accumulation order (DESC_PGD.m:137-146)
-__device__ __forceinline__ double cycle_trace(const double* A, const double* pb, bool tb, const double* pc, bool tc) {
-    double Bm[9], Cm[9], B[9], C[9];
-    load_block9(pb, Bm); load_block9(pc, Cm);
-    for (int r = 0; r < 3; ++r)
-        for (int s = 0; s < 3; ++s) {
-            B[r + 3 * s] = tb ? Bm[s + 3 * r] : Bm[r + 3 * s];
-            C[r + 3 * s] = tc ? Cm[s + 3 * r] : Cm[r + 3 * s];
-        }
-    double tr = 0.0;
-    for (int r = 0; r < 3; ++r) {
-        double P[3];
-        for (int s = 0; s < 3; ++s) {
-            double acc = 0.0;
-            for (int u = 0; u < 3; ++u) acc = acc + A[r + 3 * u] * B[u + 3 * s];
-            P[s] = acc;
-        }
-        double acc = 0.0;
-        for (int u = 0; u < 3; ++u) acc = acc + P[u] * C[u + 3 * r];
-        tr = tr + acc;
-    }
-    return tr;
-}
 
 // the same with the third factor already loaded (k_layout_node_dev<.., STAGED>: node i's blocks sit in the LDS)
 __device__ __forceinline__ double cycle_trace_regs(const double* A, const double* pb, bool tb, const double* Cm, bool tc) {

@@ -20,6 +20,7 @@
 #include "common.h"
 
 namespace desc {
+thread_local bool g_structure_serial = false;
 namespace {
 
 struct Graph {
@@ -38,7 +39,7 @@ template <class F>
 void parallel_for(int64_t count, F&& body) {
     unsigned hw = std::thread::hardware_concurrency();
     int nt = (int)std::min<int64_t>(std::max(1u, std::min(hw, 32u)), std::max<int64_t>(1, count / 2048));
-    if (nt <= 1) { body(0, count, 0); return; }
+    if (nt <= 1 || g_structure_serial) { body(0, count, 0); return; }
     // interleaved blocks: low-numbered edges have larger neighbour lists on average
     const int64_t chunk = 1024;
     run_threads(nt, [&](int t) {

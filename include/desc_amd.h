@@ -530,6 +530,53 @@ int desc_lp_sij_run(const desc_problem* prob, const desc_lp_params* params, int3
 int desc_lp_sij_run_dev(const desc_device_problem* dp, const desc_lp_params* params, double* s_vec, double* y, int32_t* k_out,
                         desc_lp_info* info);
 
+/* ------------------------------------------------- many small problems in one pass -- */
+/* B independent problems (the Monte-Carlo studies of the paper: graphs of 100-200 nodes, many trials) share one set of device arrays and
+ * ONE sweep launch per iteration.  Problem b returns what desc_pgd_solve(probs[b], p) returns with seed seeds[b] (p->seed when seeds is
+ * NULL) and the host builder: its own n_sample, its cycles sampled with its LOCAL edge and node ids, its own S0_long, traces, patience
+ * rule and stop iteration.  A problem that stops is frozen while the others run on; the call ends when all have stopped or after
+ * p->iters iterations.  The result of a problem is bitwise independent of the batch around it (position, neighbours, batch size): how
+ * its segments are cut into workgroups and the order its partial sums are added in depend on that problem alone; no floating-point
+ * atomics anywhere.  All problems sit behind one another: edges of problem b at edge_off[b] .. edge_off[b+1] of every per-edge vector,
+ * its cycles at cycle_off[b] .. cycle_off[b+1] of every per-cycle vector (the problem's own cycle order).
+ * desc_pgd_batch_create: validates, builds the structures on min(count, 16) host threads, refuses -- all before any device work, naming
+ * the problem -- a problem whose n_sample exceeds 64 (DESC_ERR_INVALID: solve it with desc_pgd_solve) and totals of m_cycle >= 2^31 - 1
+ * or m >= 2^30 (DESC_ERR_TOO_LARGE); then uploads and evaluates S0_long of the whole batch.  p: n_sample_min, seed and device are read.
+ * count == 0 is legal.  Step rules: DESC_STEP_CONSTANT / PIECEWISE / HYBRID, one desc_params for the whole batch. */
+typedef struct desc_pgd_batch desc_pgd_batch;   /* opaque */
+typedef struct desc_batch_result {
+    double* s_vec;            /* edge_off[count]   out: S_vec of every problem                                  */
+    double* obj_trace;        /* count * p->iters  out or NULL: row b = obj_vals of problem b; entries past
+                                 iters_run[b] are zero                                                          */
+    double* avg_change_trace; /* count * p->iters  out or NULL: average_change, likewise                        */
+    double* w;                /* cycle_off[count]  out or NULL: wijk                                            */
+    double* adam_m;           /* cycle_off[count]  in/out or NULL: HybridGradient.m_t (read when p->t0 > 0)     */
+    double* adam_v;           /* cycle_off[count]  in/out or NULL: HybridGradient.v_t                           */
+    int32_t* iters_run;       /* count             out: iterations problem b executed                           */
+    int32_t* t_end;           /* count             out or NULL: plugin counter of problem b after the run       */
+    double ms_structure;      /* host structure builds + concatenation (wall clock of desc_pgd_batch_create's host part) */
+    double ms_upload;         /* host -> HBM                                                                    */
+    double ms_cycle_d;        /* S0_long kernel                                                                 */
+    double ms_pgd;            /* PGD loop, device time (HIP events)                                             */
+    double ms_total;          /* wall clock of desc_pgd_batch_run                                               */
+} desc_batch_result;          /* 104 bytes */
+int desc_pgd_batch_create(const desc_problem* probs, int32_t count, const desc_params* p, const uint64_t* seeds /* count, nullable */,
+                          desc_pgd_batch** out);
+/* count (nullable), edge_off[count+1], cycle_off[count+1], n_sample[count] (each nullable): what a binding needs to size its buffers */
+int desc_pgd_batch_sizes(const desc_pgd_batch* h, int32_t* count, int64_t* edge_off, int64_t* cycle_off, int32_t* n_sample);
+/* the structure of problem b, local ids (parity tests); the view stays valid until desc_pgd_batch_destroy */
+int desc_pgd_batch_get_structure(const desc_pgd_batch* h, int32_t b, desc_structure_view* view);
+int desc_pgd_batch_get_s0(desc_pgd_batch* h, double* s0 /* cycle_off[count] */);
+/* init + loop + download.  p->check_every: the host reads one "problems still running" word every this many iterations (0: 32);
+ * results do not depend on it.  progress / verbose are not used. */
+int desc_pgd_batch_run(desc_pgd_batch* h, const desc_params* p, desc_batch_result* r);
+void desc_pgd_batch_destroy(desc_pgd_batch* h);
+/* Host part of the set-up (no device): the structures of `count` problems behind one another, per-problem edge / cycle / segment offsets
+ * added to pos_edge, cum, e_jk, e_ki, ikj, jki (-1 stays -1).  edge_off, cycle_off, seg_off: count + 1 entries each; cum: seg_off[count] + 1
+ * entries; any of the seven arrays may be NULL (offsets only: what a caller needs to size the others). */
+int desc_pgd_batch_concat(const desc_structure* const* s, int32_t count, int64_t* edge_off, int64_t* cycle_off, int64_t* seg_off,
+                          int32_t* pos_edge, int32_t* cum, int32_t* e_jk, int32_t* e_ki, int32_t* ikj, int32_t* jki);
+
 /* One-shot: what the MEX shim calls.  Builds the structure (p->build_where),
  * uploads, runs, downloads, frees. */
 int desc_pgd_solve(const desc_problem* prob, const desc_params* p, desc_result* r);
