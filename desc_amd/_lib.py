@@ -36,6 +36,7 @@ EXPORTS = [
     "desc_pgd_ext_begin", "desc_pgd_ext_grad", "desc_pgd_ext_apply", "desc_pgd_ext_laps",
     "desc_pgd_batch_create", "desc_pgd_batch_sizes", "desc_pgd_batch_get_structure", "desc_pgd_batch_get_s0", "desc_pgd_batch_run",
     "desc_pgd_batch_destroy", "desc_pgd_batch_concat",
+    "desc_gcw_batch_max_n", "desc_gcw_batch_create", "desc_gcw_batch_sizes", "desc_gcw_batch_csr", "desc_gcw_batch_run", "desc_gcw_batch_destroy",
 ]
 
 I32P = C.POINTER(C.c_int32)
@@ -102,6 +103,11 @@ class Collectives(C.Structure):
 class SpectralInfo(C.Structure):
     _fields_ = [("iters", C.c_int32), ("products", C.c_int32), ("converged", C.c_int32), ("reserved", C.c_int32), ("residual", C.c_double),
                 ("eigenvalues", C.c_double * 3), ("ms_total", C.c_double)]
+
+
+class GcwBatchTimings(C.Structure):
+    _fields_ = [("ms_structure", C.c_double), ("ms_upload", C.c_double), ("ms_eig", C.c_double), ("ms_project", C.c_double),
+                ("ms_total", C.c_double)]
 
 
 class RefineInfo(C.Structure):
@@ -268,6 +274,15 @@ def load():
     L.desc_pgd_batch_destroy.argtypes = [C.c_void_p]
     L.desc_pgd_batch_destroy.restype = None
     L.desc_pgd_batch_concat.argtypes = [C.POINTER(C.c_void_p), C.c_int32, I64P, I64P, I64P, I32P, I32P, I32P, I32P, I32P, I32P]
+    L.desc_gcw_batch_max_n.restype = C.c_int32
+    L.desc_gcw_batch_max_n.argtypes = []
+    L.desc_gcw_batch_create.argtypes = [C.POINTER(Problem), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.desc_gcw_batch_sizes.argtypes = [C.c_void_p, I32P, I64P, I64P]
+    L.desc_gcw_batch_csr.argtypes = [C.POINTER(Problem), C.c_int32, I64P, I64P, I32P, I32P, I32P]
+    L.desc_gcw_batch_run.argtypes = [C.c_void_p, F64P, F64P, C.c_int32, C.c_double, C.c_int32, F64P, C.POINTER(SpectralInfo),
+                                     C.POINTER(GcwBatchTimings)]
+    L.desc_gcw_batch_destroy.argtypes = [C.c_void_p]
+    L.desc_gcw_batch_destroy.restype = None
     _lib = L
     return L
 
@@ -498,6 +513,80 @@ class Batch:
             self.destroy()
         except Exception:
             pass
+
+
+def gcw_batch_max_n():
+    """desc_gcw_batch_max_n: the largest problem (nodes) the batched eigen-solve takes."""
+    return int(load().desc_gcw_batch_max_n())
+
+
+class GcwBatch:
+    """Owner of a desc_gcw_batch*: the Spectral / GCW eigen-solve of B small problems in one launch (desc_gcw_batch_*).
+    ``probs`` is a sequence of ProblemArrays.  The handle may be run any number of times."""
+
+    def __init__(self, probs, device=0):
+        self.probs = list(probs)                     # keeps the NumPy buffers alive
+        self.count = B = len(self.probs)
+        arr = (Problem * max(B, 1))(*[q.c for q in self.probs])
+        h = C.c_void_p()
+        check(load().desc_gcw_batch_create(arr, B, int(device), C.byref(h)))
+        self.handle = h
+        no, eo = np.zeros(B + 1, dtype=np.int64), np.zeros(B + 1, dtype=np.int64)
+        check(load().desc_gcw_batch_sizes(h, None, ptr(no, I64P), ptr(eo, I64P)))
+        self.node_off, self.edge_off = no, eo
+        self.n, self.m = int(no[B]), int(eo[B])
+
+    def run(self, s_vec=None, weights=None, normalize_rows=False, tol=1e-13, max_iters=500):
+        """One batched eigen-solve.  s_vec: the concatenated S_vec (GCW mode); weights: concatenated host weights; neither: Spectral.
+        Returns a list of per-problem (R (3,3,n_b) Fortran-ordered, info dict) and the call's timings."""
+        B = self.count
+        vec = None
+        for name, v in (("s_vec", s_vec), ("weights", weights)):
+            if v is None:
+                continue
+            vec = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+            if vec.size != self.m:
+                raise ValueError(f"{name} must hold {self.m} entries (all problems' edges behind one another), not {vec.size}")
+        R = out_buffer(9 * self.n)
+        infos = (SpectralInfo * max(B, 1))()
+        tm = GcwBatchTimings()
+        check(load().desc_gcw_batch_run(self.handle, ptr(vec, F64P) if s_vec is not None else None,
+                                        ptr(vec, F64P) if s_vec is None and weights is not None else None, 1 if normalize_rows else 0,
+                                        tol, max_iters, ptr(R, F64P), infos, C.byref(tm)))
+        outs = []
+        for b in range(B):
+            n0, n1 = int(self.node_off[b]), int(self.node_off[b + 1])
+            i = infos[b]
+            outs.append((R[9 * n0:9 * n1].reshape((3, 3, n1 - n0), order="F"),
+                         dict(iters=i.iters, products=i.products, converged=bool(i.converged), residual=i.residual,
+                              eigenvalues=list(i.eigenvalues), ms_total=i.ms_total)))
+        timings = dict(ms_structure=tm.ms_structure, ms_upload=tm.ms_upload, ms_eig=tm.ms_eig, ms_project=tm.ms_project, ms_total=tm.ms_total)
+        return outs, timings
+
+    def destroy(self):
+        if self.handle:
+            load().desc_gcw_batch_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def gcw_batch_csr(probs):
+    """desc_gcw_batch_csr on a sequence of ProblemArrays: the per-problem CSR the batched eigen-solve uploads (host only)."""
+    probs = list(probs)
+    B = len(probs)
+    arr = (Problem * max(B, 1))(*[q.c for q in probs])
+    no, eo = np.zeros(B + 1, dtype=np.int64), np.zeros(B + 1, dtype=np.int64)
+    L = load()
+    check(L.desc_gcw_batch_csr(arr, B, ptr(no, I64P), ptr(eo, I64P), None, None, None))
+    N, M = int(no[B]), int(eo[B])
+    rowptr, adj, eid = out_buffer(N + B, np.int32), out_buffer(2 * M, np.int32), out_buffer(2 * M, np.int32)
+    check(L.desc_gcw_batch_csr(arr, B, ptr(no, I64P), ptr(eo, I64P), ptr(rowptr, I32P), ptr(adj, I32P), ptr(eid, I32P)))
+    return dict(node_off=no, edge_off=eo, rowptr=rowptr[:N + B], adj=adj[:2 * M], adj_eid=eid[:2 * M])
 
 
 def batch_concat(structures):

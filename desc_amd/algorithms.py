@@ -247,41 +247,26 @@ def DESC_PGD(Ind, RijMat, params, return_info=False, _marshalled=None):
     return S_vec
 
 
-def DESC_PGD_batch(problems, params, seeds=None, return_info=False):
-    """DESC_PGD on B independent problems in one GPU pass (desc_pgd_batch_*; the reference has no such call).
-
-    ``problems`` is a sequence of ``(Ind, RijMat)`` pairs or of model objects with ``.Ind`` / ``.RijMat``; ``params`` as for DESC_PGD,
-    one for the whole batch; ``seeds`` an optional sequence of per-problem sampling seeds (default: ``params.seed`` for every problem).
-    Problem b gets what ``DESC_PGD(Ind_b, RijMat_b, params)`` returns with the same seed and the host structure builder: its own
-    n_sample, traces, patience rule and stop iteration; its result does not depend, in any bit, on the batch around it.
-
-    Returns a list of S_vec arrays (caller's edge order).  With ``return_info`` a list of dicts: ``S_vec``, ``iters_run``, ``obj_vals``,
-    ``average_change``, ``n_sample``, ``w`` (cycle order of the problem sorted by (i, j)), ``t_end`` and the call's ``timings``; with a
-    HybridGradient (Adam) also ``m_t`` / ``v_t``.  The plugin object is shared by the batch and is NOT updated: its counter ``t`` is
-    read as the starting counter of every problem, the moments start at zero, and each problem's state comes back in its dict.
-
-    Refused (ValueError): a Gradient object of the caller's own (external GetStep), ``make_plots``, a problem whose n_sample exceeds 64
-    (solve it with DESC_PGD)."""
+def _check_sequence(problems):
     import collections.abc
     if isinstance(problems, (str, bytes, np.ndarray)) or not isinstance(problems, collections.abc.Sequence):
         raise ValueError("problems must be a sequence of (Ind, RijMat) pairs or of model objects with .Ind / .RijMat")
-    G = _get(params, "Gradient")
-    if G is not None and is_external(G):
-        raise ValueError("DESC_PGD_batch runs the three step rules of Utils/ (ConstantStepSize, PiecewiseStepSize, HybridGradient); "
-                         "a Gradient object with a GetStep of its own runs through DESC_PGD, one problem at a time")
-    if bool(_get(params, "make_plots", False)):
-        raise ValueError("DESC_PGD_batch does not support params.make_plots: use DESC_PGD for the traced run of one problem")
-    B = len(problems)
-    if seeds is not None:
-        seeds = [int(x) for x in seeds]
-        if len(seeds) != B:
-            raise ValueError(f"seeds must hold one entry per problem ({B}), not {len(seeds)}")
-    p, G = make_c_params(params)
-    p.verbose = 0
-    if B == 0:
-        return []
+
+
+class _Marshalled:
+    """A problem of a batch call that has been through marshal_edges already (DESC_init_batch hands these to DESC_PGD_batch)."""
+
+    def __init__(self, prob, perm):
+        self.prob, self.perm = prob, perm
+
+
+def _marshal_problems(problems):
+    """The problems of a batch call -> (list of ProblemArrays, list of edge permutations); ValueError names the problem."""
     probs, perms = [], []
     for b, item in enumerate(problems):
+        if isinstance(item, _Marshalled):
+            probs.append(item.prob); perms.append(item.perm)
+            continue
         if hasattr(item, "Ind") and hasattr(item, "RijMat"):
             Ind, RijMat = item.Ind, item.RijMat
         else:
@@ -297,6 +282,41 @@ def DESC_PGD_batch(problems, params, seeds=None, return_info=False):
             raise ValueError(f"problem {b}: empty edge list")
         probs.append(_lib.ProblemArrays(n, ii, jj, rij))
         perms.append(perm)
+    return probs, perms
+
+
+def DESC_PGD_batch(problems, params, seeds=None, return_info=False):
+    """DESC_PGD on B independent problems in one GPU pass (desc_pgd_batch_*; the reference has no such call).
+
+    ``problems`` is a sequence of ``(Ind, RijMat)`` pairs or of model objects with ``.Ind`` / ``.RijMat``; ``params`` as for DESC_PGD,
+    one for the whole batch; ``seeds`` an optional sequence of per-problem sampling seeds (default: ``params.seed`` for every problem).
+    Problem b gets what ``DESC_PGD(Ind_b, RijMat_b, params)`` returns with the same seed and the host structure builder: its own
+    n_sample, traces, patience rule and stop iteration; its result does not depend, in any bit, on the batch around it.
+
+    Returns a list of S_vec arrays (caller's edge order).  With ``return_info`` a list of dicts: ``S_vec``, ``iters_run``, ``obj_vals``,
+    ``average_change``, ``n_sample``, ``w`` (cycle order of the problem sorted by (i, j)), ``t_end`` and the call's ``timings``; with a
+    HybridGradient (Adam) also ``m_t`` / ``v_t``.  The plugin object is shared by the batch and is NOT updated: its counter ``t`` is
+    read as the starting counter of every problem, the moments start at zero, and each problem's state comes back in its dict.
+
+    Refused (ValueError): a Gradient object of the caller's own (external GetStep), ``make_plots``, a problem whose n_sample exceeds 64
+    (solve it with DESC_PGD)."""
+    _check_sequence(problems)
+    G = _get(params, "Gradient")
+    if G is not None and is_external(G):
+        raise ValueError("DESC_PGD_batch runs the three step rules of Utils/ (ConstantStepSize, PiecewiseStepSize, HybridGradient); "
+                         "a Gradient object with a GetStep of its own runs through DESC_PGD, one problem at a time")
+    if bool(_get(params, "make_plots", False)):
+        raise ValueError("DESC_PGD_batch does not support params.make_plots: use DESC_PGD for the traced run of one problem")
+    B = len(problems)
+    if seeds is not None:
+        seeds = [int(x) for x in seeds]
+        if len(seeds) != B:
+            raise ValueError(f"seeds must hold one entry per problem ({B}), not {len(seeds)}")
+    p, G = make_c_params(params)
+    p.verbose = 0
+    if B == 0:
+        return []
+    probs, perms = _marshal_problems(problems)
     try:
         batch = _lib.Batch(probs, p, seeds)
     except _lib.DescError as e:
@@ -326,6 +346,106 @@ def DESC_PGD_batch(problems, params, seeds=None, return_info=False):
             d["m_t"], d["v_t"] = o["adam_m"], o["adam_v"]
         result.append(d)
     return result
+
+
+def _check_gcw_batch_sizes(probs):
+    """The batched eigen-solve's size cap, checked before the device is touched."""
+    cap = _lib.gcw_batch_max_n()
+    for b, q in enumerate(probs):
+        if q.n > cap:
+            raise ValueError(f"problem {b}: n = {q.n} exceeds {cap} (the 3n x 6 blocks of the eigen-solve must fit the LDS of one workgroup): "
+                             "solve it with GCW / DESC_init")
+
+
+def _sorted_s_list(probs, perms, S_list):
+    """One S_vec per problem in the caller's edge order -> the concatenation in the library's order; refusals name the problem."""
+    if isinstance(S_list, (str, bytes)) or not hasattr(S_list, "__len__") or len(S_list) != len(probs):
+        got = len(S_list) if hasattr(S_list, "__len__") else type(S_list).__name__
+        raise ValueError(f"S_list must hold one S_vec per problem ({len(probs)}), not {got}")
+    parts = []
+    for b, (q, perm, S) in enumerate(zip(probs, perms, S_list)):
+        S = np.asarray(S, dtype=np.float64).reshape(-1)
+        if S.shape[0] != q.m:
+            raise ValueError(f"problem {b}: S_vec must have one entry per edge ({q.m}), not {S.shape[0]}")
+        if perm is not None:
+            S = S[perm]
+        bad = np.flatnonzero(~(np.isfinite(S) & (S >= 0)))
+        if bad.size:
+            raise ValueError(f"problem {b}: S_vec holds a negative or non-finite entry (node {int(q.ind_i[bad[0]])})")
+        parts.append(S)
+    return np.concatenate(parts) if parts else np.zeros(0)
+
+
+def _gcw_batch_run(probs, device, **run_args):
+    try:
+        batch = _lib.GcwBatch(probs, device)
+    except _lib.DescError as e:
+        if e.code == _lib.ERR_INVALID:
+            raise ValueError(str(e).split(": ", 1)[-1]) from None
+        raise
+    try:
+        return batch.run(**run_args)
+    finally:
+        batch.destroy()
+
+
+def Spectral_batch(problems, device=0, return_info=False):
+    """Spectral (Algorithms/Spectral.m:15) on B independent small problems in one GPU launch (desc_gcw_batch_*; the reference has no such
+    call).  ``problems`` as for DESC_PGD_batch.  Returns a list of R (3 x 3 x n_b); with ``return_info`` a list of (R, info) with the
+    record Spectral() gives plus the call's ``timings``.  Problem b's result does not depend, in any bit, on the batch around it.
+    Refused (ValueError): an empty edge list, a problem of more than ``_lib.gcw_batch_max_n()`` nodes (solve it with Spectral)."""
+    _check_sequence(problems)
+    probs, perms = _marshal_problems(problems)
+    if not probs:
+        return []
+    _check_gcw_batch_sizes(probs)
+    outs, timings = _gcw_batch_run(probs, device, normalize_rows=False)
+    return [(R, dict(info, timings=timings)) for R, info in outs] if return_info else [R for R, _ in outs]
+
+
+def GCW_batch(problems, S_list, device=0, return_info=False):
+    """GCW (Utils/GCW.m) on B independent small problems in one GPU launch: ``S_list[b]`` is problem b's S_vec in the caller's edge
+    order; the weights 1/(S^1.5 + 1e-8) are formed on the device.  Returns a list of R (3 x 3 x n_b); with ``return_info`` a list of
+    (R, info).  Refused (ValueError, before the device is touched): S_list of the wrong length or an entry of the wrong size, a negative
+    or non-finite S entry, an empty edge list, a problem of more than ``_lib.gcw_batch_max_n()`` nodes (solve it with GCW)."""
+    _check_sequence(problems)
+    probs, perms = _marshal_problems(problems)
+    S = _sorted_s_list(probs, perms, S_list)
+    if not probs:
+        return []
+    _check_gcw_batch_sizes(probs)
+    outs, timings = _gcw_batch_run(probs, device, s_vec=S)
+    return [(R, dict(info, timings=timings)) for R, info in outs] if return_info else [R for R, _ in outs]
+
+
+def DESC_init_batch(problems, params, seeds=None, return_info=False):
+    """DESC_init (Algorithms/DESC_init.m: DESC_PGD, then GCW) on B independent small problems: DESC_PGD_batch's pass, then the batched
+    eigen-solve on the resulting S_vec -- two GPU passes for the whole batch.  Returns a list of (R_est, S_vec); problem b's S_vec is
+    bit for bit what DESC_PGD_batch returns for it.  With ``return_info`` a list of (R_est, S_vec, dict(pgd=..., gcw=...)).
+    Refused (ValueError, before the device is touched): what DESC_PGD_batch refuses, and a problem of more than
+    ``_lib.gcw_batch_max_n()`` nodes (solve it with DESC_init)."""
+    _check_sequence(problems)
+    G = _get(params, "Gradient")
+    if G is not None and is_external(G):
+        raise ValueError("DESC_init_batch runs the three step rules of Utils/ (ConstantStepSize, PiecewiseStepSize, HybridGradient); "
+                         "a Gradient object with a GetStep of its own runs through DESC_init, one problem at a time")
+    if bool(_get(params, "make_plots", False)):
+        raise ValueError("DESC_init_batch does not support params.make_plots: use DESC_init for the traced run of one problem")
+    if seeds is not None:
+        seeds = [int(x) for x in seeds]
+        if len(seeds) != len(problems):
+            raise ValueError(f"seeds must hold one entry per problem ({len(problems)}), not {len(seeds)}")
+    probs, perms = _marshal_problems(problems)
+    _check_gcw_batch_sizes(probs)
+    pgd = DESC_PGD_batch([_Marshalled(q, perm) for q, perm in zip(probs, perms)], params, seeds=seeds, return_info=True)
+    if not probs:
+        return []
+    # DESC_PGD_batch gave S_vec in the caller's order; the eigen-solve takes the library's
+    S_sorted = [d["S_vec"] if perm is None else d["S_vec"][perm] for d, perm in zip(pgd, perms)]
+    outs, timings = _gcw_batch_run(probs, int(_get(params, "device", 0)), s_vec=np.concatenate(S_sorted))
+    if return_info:
+        return [(R, d["S_vec"], dict(pgd=d, gcw=dict(info, timings=timings))) for (R, info), d in zip(outs, pgd)]
+    return [(R, d["S_vec"]) for (R, _), d in zip(outs, pgd)]
 
 
 def _run_with_plots(solver, p, params, prob, dprob, perm, verbose, adam=None):

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "device_utils.h"
+#include "small_dense.h"
 
 namespace desc {
 namespace {
@@ -278,71 +279,7 @@ __global__ void k_combine(const double* Y, double* Xn, int64_t rows, SmallMat C)
     }
 }
 
-// ---- small dense helpers (host) ---------------------------------------------------------
-// cyclic Jacobi eigen-decomposition of a symmetric N x N matrix (row-major); eigenvalues
-// descending in w, eigenvectors in the columns of V
-template <int N>
-void jacobi_eig(const double* Ain, double* w, double* V) {
-    double A[N][N];
-    for (int i = 0; i < N; ++i) for (int j = 0; j < N; ++j) { A[i][j] = 0.5 * (Ain[i * N + j] + Ain[j * N + i]); V[i * N + j] = i == j; }
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        double off = 0.0;
-        for (int p = 0; p < N; ++p) for (int q = p + 1; q < N; ++q) off += A[p][q] * A[p][q];
-        if (off < 1e-300) break;
-        for (int p = 0; p < N; ++p)
-            for (int q = p + 1; q < N; ++q) {
-                if (std::fabs(A[p][q]) < 1e-300) continue;
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < N; ++k) { const double akp = A[k][p], akq = A[k][q]; A[k][p] = c * akp - s * akq; A[k][q] = s * akp + c * akq; }
-                for (int k = 0; k < N; ++k) { const double apk = A[p][k], aqk = A[q][k]; A[p][k] = c * apk - s * aqk; A[q][k] = s * apk + c * aqk; }
-                for (int k = 0; k < N; ++k) { const double vkp = V[k * N + p], vkq = V[k * N + q]; V[k * N + p] = c * vkp - s * vkq; V[k * N + q] = s * vkp + c * vkq; }
-            }
-    }
-    int idx[N];
-    for (int i = 0; i < N; ++i) idx[i] = i;
-    std::sort(idx, idx + N, [&](int a, int b) { return A[a][a] > A[b][b]; });
-    double Vs[N * N];
-    for (int c = 0; c < N; ++c) { w[c] = A[idx[c]][idx[c]]; for (int k = 0; k < N; ++k) Vs[k * N + c] = V[k * N + idx[c]]; }
-    std::memcpy(V, Vs, sizeof Vs);
-}
-
-// R = U*diag(1,1,det(U*V'))*V' for the 3x3 block M (row-major)  (Spectral.m:43-45)
-void project_so3(const double* M, double* R) {
-    // eigen-decomposition of M'M gives V and the singular values; U = M V / sigma
-    double MtM[9], w[3], V[9];
-    for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) { double s = 0; for (int k = 0; k < 3; ++k) s += M[k * 3 + a] * M[k * 3 + b]; MtM[a * 3 + b] = s; }
-    jacobi_eig<3>(MtM, w, V);
-    double U[9];
-    const double s0 = std::sqrt(std::max(w[0], 0.0));
-    int good = 0;
-    for (int c = 0; c < 3; ++c) {
-        const double sc = std::sqrt(std::max(w[c], 0.0));
-        if (sc > 1e-12 * std::max(s0, 1e-300) && sc > 1e-300) {
-            for (int r = 0; r < 3; ++r) { double s = 0; for (int k = 0; k < 3; ++k) s += M[r * 3 + k] * V[k * 3 + c]; U[r * 3 + c] = s / sc; }
-            good = c + 1;
-        } else break;
-    }
-    if (good == 0) { for (int i = 0; i < 9; ++i) { U[i] = (i % 4 == 0); V[i] = (i % 4 == 0); } good = 3; }   // svd(0): U = V = I
-    if (good == 1) {      // complete an orthonormal basis
-        double a[3] = {U[0], U[3], U[6]}; int k = std::fabs(a[0]) < std::fabs(a[1]) ? (std::fabs(a[0]) < std::fabs(a[2]) ? 0 : 2) : (std::fabs(a[1]) < std::fabs(a[2]) ? 1 : 2);
-        double e[3] = {0, 0, 0}; e[k] = 1;
-        double b[3] = {a[1] * e[2] - a[2] * e[1], a[2] * e[0] - a[0] * e[2], a[0] * e[1] - a[1] * e[0]};
-        const double nb = std::sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
-        for (int r = 0; r < 3; ++r) U[r * 3 + 1] = b[r] / nb;
-        good = 2;
-    }
-    if (good == 2) {
-        const double a[3] = {U[0], U[3], U[6]}, b[3] = {U[1], U[4], U[7]};
-        U[2] = a[1] * b[2] - a[2] * b[1]; U[5] = a[2] * b[0] - a[0] * b[2]; U[8] = a[0] * b[1] - a[1] * b[0];
-    }
-    auto det3 = [](const double* A) { return A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6]) + A[2] * (A[3] * A[7] - A[4] * A[6]); };
-    double UVt[9];
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) { double s = 0; for (int k = 0; k < 3; ++k) s += U[r * 3 + k] * V[c * 3 + k]; UVt[r * 3 + c] = s; }
-    const double d = det3(UVt) < 0 ? -1.0 : 1.0;
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) R[r * 3 + c] = U[r * 3 + 0] * V[c * 3 + 0] + U[r * 3 + 1] * V[c * 3 + 1] + d * U[r * 3 + 2] * V[c * 3 + 2];
-}
+// the small dense helpers (jacobi_eig, ortho_coeffs, project_so3) live in small_dense.h, shared with gcw_batch.hip
 
 }  // namespace
 }  // namespace desc
@@ -467,24 +404,8 @@ static int spectral_impl(const desc_device_problem* dp, const double* weights, c
         for (int t = 0; t < BW * BW; ++t) { double s1 = 0, s2 = 0; for (int b = 0; b < ggrid; ++b) { s1 += part[(size_t)b * 2 * BW * BW + t]; s2 += part[(size_t)b * 2 * BW * BW + BW * BW + t]; } G1[t] = s1; G2[t] = s2; }
         return DESC_OK;
     };
-    // C = Z * L^-T where K = Z' G Z = L L'  (columns of Y*C are orthonormal)
-    auto ortho_coeffs = [&](const double* G, const double* Z, SmallMat& C) -> bool {
-        double K[BW][BW], L[BW][BW] = {};
-        for (int a = 0; a < BW; ++a) for (int b = 0; b < BW; ++b) { double s = 0; for (int p = 0; p < BW; ++p) for (int q = 0; q < BW; ++q) s += Z[p * BW + a] * G[p * BW + q] * Z[q * BW + b]; K[a][b] = s; }
-        for (int a = 0; a < BW; ++a) {
-            for (int b = 0; b <= a; ++b) {
-                double s = 0.5 * (K[a][b] + K[b][a]);
-                for (int k = 0; k < b; ++k) s -= L[a][k] * L[b][k];
-                if (a == b) { if (!(s > 0)) return false; L[a][a] = std::sqrt(s); } else L[a][b] = s / L[b][b];
-            }
-        }
-        // Linv' : solve L' X = I  -> X = L^-T ; then C = Z X
-        double Li[BW][BW] = {};
-        for (int c = 0; c < BW; ++c)
-            for (int r = BW - 1; r >= 0; --r) { double s = (r == c); for (int k = r + 1; k < BW; ++k) s -= L[k][r] * Li[k][c]; Li[r][c] = s / L[r][r]; }
-        for (int a = 0; a < BW; ++a) for (int b = 0; b < BW; ++b) { double s = 0; for (int k = 0; k < BW; ++k) s += Z[a * BW + k] * Li[k][b]; C.c[a * BW + b] = s; }
-        return true;
-    };
+    // C = Z * L^-T where K = Z' G Z = L L'  (columns of Y*C are orthonormal): small_dense.h
+    auto ortho_coeffs = [&](const double* G, const double* Z, SmallMat& C) -> bool { return desc::ortho_coeffs<BW>(G, Z, C.c); };
     double Ident[BW * BW];
     for (int t = 0; t < BW * BW; ++t) Ident[t] = (t % (BW + 1) == 0);
     // X = orth(X0)

@@ -2,7 +2,10 @@
 """A small Monte-Carlo study in ONE batched call: mean |S_vec - ErrVec| against the corruption level q, averaged over a few trials
 of Uniform_Topology(100, 0.5, q, 0.1) -- the shape of the figures the DESC paper draws (error against q on graphs of 100-200 nodes).
 
-    python examples/monte_carlo.py [--trials 5] [--n 100] [--iters 100]
+    python examples/monte_carlo.py [--trials 5] [--n 100] [--iters 100] [--rotations]
+
+--rotations: the demo's own metric next to it -- one DESC_init_batch call (the PGD pass, then the batched GCW eigen-solve) and the mean
+rotation error in degrees (Rotation_Alignment against the ground truth), the column of Demo/compare_algorithms.m.
 """
 import argparse
 import os
@@ -13,7 +16,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from desc_amd import ConstantStepSize, DESC_PGD_batch, Uniform_Topology  # noqa: E402
+from desc_amd import ConstantStepSize, DESC_PGD_batch, DESC_init_batch, Rotation_Alignment, Uniform_Topology  # noqa: E402
 
 
 def main():
@@ -21,14 +24,27 @@ def main():
     ap.add_argument("--trials", type=int, default=5)
     ap.add_argument("--n", type=int, default=100)
     ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--rotations", action="store_true", help="one DESC_init_batch call: the mean rotation error next to the S_vec error")
     a = ap.parse_args()
     qs = [0.0, 0.1, 0.2, 0.3, 0.4, 0.5]
     models = [Uniform_Topology(a.n, 0.5, q, 0.1, "uniform", seed=1000 * k + t) for k, q in enumerate(qs) for t in range(a.trials)]
+    params = dict(iters=a.iters, Gradient=ConstantStepSize(0.01), seed=0, verbose=False)
     t0 = time.perf_counter()
-    S = DESC_PGD_batch(models, dict(iters=a.iters, Gradient=ConstantStepSize(0.01), seed=0, verbose=False))
+    if a.rotations:
+        out = DESC_init_batch(models, params)
+        S = [s for _, s in out]
+    else:
+        S = DESC_PGD_batch(models, params)
     ms = (time.perf_counter() - t0) * 1e3
     err = np.array([np.abs(s - mo.ErrVec).mean() for s, mo in zip(S, models)]).reshape(len(qs), a.trials)
-    print(f"{len(models)} problems (n = {a.n}, {a.trials} trials per q) in one DESC_PGD_batch call: {ms:.1f} ms")
+    print(f"{len(models)} problems (n = {a.n}, {a.trials} trials per q) in one {'DESC_init_batch' if a.rotations else 'DESC_PGD_batch'} call: {ms:.1f} ms")
+    if a.rotations:
+        rot = np.array([Rotation_Alignment(R, mo.R_orig)[2] for (R, _), mo in zip(out, models)]).reshape(len(qs), a.trials)
+        print("    q   mean |S_vec - ErrVec|   (min .. max)          mean rotation error, degrees   (min .. max over the trials)")
+        for q, row, rr in zip(qs, err, rot):
+            print(f" {q:4.2f}   {row.mean():.4f}                ({row.min():.4f} .. {row.max():.4f})      {rr.mean():8.4f}"
+                  f"                      ({rr.min():.4f} .. {rr.max():.4f})")
+        return
     print("    q   mean |S_vec - ErrVec|   (min .. max over the trials)")
     for q, row in zip(qs, err):
         print(f" {q:4.2f}   {row.mean():.4f}                ({row.min():.4f} .. {row.max():.4f})")

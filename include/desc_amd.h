@@ -577,6 +577,41 @@ void desc_pgd_batch_destroy(desc_pgd_batch* h);
 int desc_pgd_batch_concat(const desc_structure* const* s, int32_t count, int64_t* edge_off, int64_t* cycle_off, int64_t* seg_off,
                           int32_t* pos_edge, int32_t* cum, int32_t* e_jk, int32_t* e_ki, int32_t* ikj, int32_t* jki);
 
+/* Spectral / GCW for B independent small problems in ONE launch: the rotation step behind desc_pgd_batch_* (S_vec -> R_est, GCW.m:9-36 /
+ * DESC.m:263).  One workgroup per problem runs the whole Chebyshev-filtered subspace iteration of desc_spectral_run on the chip (its
+ * 3n x 6 blocks in LDS, the 6x6 Jacobi and the Cholesky coefficients inside the kernel, no host round trip); the tail (back-scaling,
+ * unit columns, det sign, per-node projection onto SO(3)) runs per problem on host threads.  Problem b's result is bitwise independent
+ * of the batch around it (position, neighbours, batch size, the LDS size of the launch).  It agrees with desc_spectral_run /
+ * desc_gcw_run_dev to the accuracy of the eigen-solve, not bit for bit: the Gram sums are taken in another (fixed) order.
+ * desc_gcw_batch_max_n: the largest n whose blocks fit the 160 KiB of LDS a workgroup may declare (278).
+ * desc_gcw_batch_create: validates every problem and refuses -- before any device work, naming the problem -- an empty edge list and
+ * n > desc_gcw_batch_max_n() (DESC_ERR_INVALID: solve it with GCW / DESC_init); builds the per-problem CSR (local ids) and uploads
+ * rotations and indices in one copy each.  count == 0 is legal.  The handle may be run any number of times.
+ * desc_gcw_batch_sizes: node_off[count+1], edge_off[count+1] (each nullable).
+ * desc_gcw_batch_csr: the host part of create alone (no device): rowptr (problem b's n_b + 1 entries at node_off[b] + b), adj and adj_eid
+ * (its 2 m_b entries at 2 edge_off[b]; local node / edge ids); the three arrays are nullable (offsets only, to size them).
+ * desc_gcw_batch_run: s_vec = the edge_off[count] concatenated S_vec in the library's edge order: GCW mode (weights 1/(S^1.5 + 1e-8)
+ * formed on the device, rows normalised); s_vec NULL and weights NULL: Spectral mode with normalize_rows == 0; s_vec NULL and weights
+ * set: host weights as desc_spectral_run.  A negative or non-finite S_vec entry (or weight) is refused, naming the problem and the node.
+ * R_out: problem b's 3x3xn_b column-major blocks at 9 * node_off[b]; infos: count entries (ms_total = the call's).  tol <= 0: 1e-13,
+ * max_iters <= 0: 500.  A problem that does not converge reports converged = 0 and the rotations of its last basis. */
+typedef struct desc_gcw_batch desc_gcw_batch;   /* opaque */
+typedef struct desc_gcw_batch_timings {
+    double ms_structure;      /* validation + per-problem CSR (wall clock of create's host part)   */
+    double ms_upload;         /* host -> HBM (create)                                               */
+    double ms_eig;            /* the eigen-solve launch, device time (HIP events)                   */
+    double ms_project;        /* the tail on host threads                                           */
+    double ms_total;          /* wall clock of desc_gcw_batch_run                                   */
+} desc_gcw_batch_timings;     /* 40 bytes */
+int32_t desc_gcw_batch_max_n(void);
+int desc_gcw_batch_create(const desc_problem* probs, int32_t count, int32_t device, desc_gcw_batch** out);
+int desc_gcw_batch_sizes(const desc_gcw_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off);
+int desc_gcw_batch_csr(const desc_problem* probs, int32_t count, int64_t* node_off, int64_t* edge_off, int32_t* rowptr, int32_t* adj,
+                       int32_t* adj_eid);
+int desc_gcw_batch_run(desc_gcw_batch* h, const double* s_vec, const double* weights, int32_t normalize_rows, double tol, int32_t max_iters,
+                       double* R_out, desc_spectral_info* infos, desc_gcw_batch_timings* timings /* nullable */);
+void desc_gcw_batch_destroy(desc_gcw_batch* h);
+
 /* One-shot: what the MEX shim calls.  Builds the structure (p->build_where),
  * uploads, runs, downloads, frees. */
 int desc_pgd_solve(const desc_problem* prob, const desc_params* p, desc_result* r);
