@@ -37,6 +37,8 @@ EXPORTS = [
     "desc_pgd_batch_create", "desc_pgd_batch_sizes", "desc_pgd_batch_get_structure", "desc_pgd_batch_get_s0", "desc_pgd_batch_run",
     "desc_pgd_batch_destroy", "desc_pgd_batch_concat",
     "desc_gcw_batch_max_n", "desc_gcw_batch_create", "desc_gcw_batch_sizes", "desc_gcw_batch_csr", "desc_gcw_batch_run", "desc_gcw_batch_destroy",
+    "desc_cemp_batch_max_degree", "desc_cemp_batch_create", "desc_cemp_batch_sizes", "desc_cemp_batch_get_samples", "desc_cemp_batch_run",
+    "desc_cemp_batch_destroy", "desc_mst_batch_max_n", "desc_mst_batch_check", "desc_mst_batch_run",
 ]
 
 I32P = C.POINTER(C.c_int32)
@@ -107,6 +109,16 @@ class SpectralInfo(C.Structure):
 
 class GcwBatchTimings(C.Structure):
     _fields_ = [("ms_structure", C.c_double), ("ms_upload", C.c_double), ("ms_eig", C.c_double), ("ms_project", C.c_double),
+                ("ms_total", C.c_double)]
+
+
+class CempBatchTimings(C.Structure):
+    _fields_ = [("ms_structure", C.c_double), ("ms_upload", C.c_double), ("ms_build", C.c_double), ("ms_rounds", C.c_double),
+                ("ms_total", C.c_double)]
+
+
+class MstBatchTimings(C.Structure):
+    _fields_ = [("ms_structure", C.c_double), ("ms_upload", C.c_double), ("ms_tree", C.c_double), ("ms_propagate", C.c_double),
                 ("ms_total", C.c_double)]
 
 
@@ -283,6 +295,19 @@ def load():
                                      C.POINTER(GcwBatchTimings)]
     L.desc_gcw_batch_destroy.argtypes = [C.c_void_p]
     L.desc_gcw_batch_destroy.restype = None
+    L.desc_cemp_batch_max_degree.restype = C.c_int32
+    L.desc_cemp_batch_max_degree.argtypes = []
+    L.desc_cemp_batch_create.argtypes = [C.POINTER(Problem), C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_uint64), C.c_int32,
+                                         C.POINTER(C.c_void_p)]
+    L.desc_cemp_batch_sizes.argtypes = [C.c_void_p, I32P, I64P, I64P]
+    L.desc_cemp_batch_get_samples.argtypes = [C.c_void_p, I32P, I32P, F64P, C.POINTER(C.c_uint8)]
+    L.desc_cemp_batch_run.argtypes = [C.c_void_p, F64P, C.c_int32, C.c_int32, F64P, C.POINTER(CempBatchTimings)]
+    L.desc_cemp_batch_destroy.argtypes = [C.c_void_p]
+    L.desc_cemp_batch_destroy.restype = None
+    L.desc_mst_batch_max_n.restype = C.c_int32
+    L.desc_mst_batch_max_n.argtypes = []
+    L.desc_mst_batch_check.argtypes = [C.POINTER(Problem), C.c_int32]
+    L.desc_mst_batch_run.argtypes = [C.POINTER(Problem), C.c_int32, F64P, C.c_int32, F64P, I32P, C.POINTER(MstBatchTimings)]
     _lib = L
     return L
 
@@ -573,6 +598,105 @@ class GcwBatch:
             self.destroy()
         except Exception:
             pass
+
+
+def cemp_batch_max_degree():
+    """desc_cemp_batch_max_degree: the longest CSR row (neighbours of one node) the batched CEMP sampler stages."""
+    return int(load().desc_cemp_batch_max_degree())
+
+
+class CempBatch:
+    """Owner of a desc_cemp_batch*: CEMP on B small problems in one GPU pass (desc_cemp_batch_*).  ``probs`` is a sequence of
+    ProblemArrays; ``seeds`` an optional sequence of per-problem sampling seeds.  Sampling, S0 and the initial means are computed here;
+    the handle may be run any number of times."""
+
+    def __init__(self, probs, nsample, seed=0, seeds=None, device=0):
+        self.probs = list(probs)                     # keeps the NumPy buffers alive
+        self.count = B = len(self.probs)
+        self.nsample = int(nsample)
+        arr = (Problem * max(B, 1))(*[q.c for q in self.probs])
+        sd = None
+        if seeds is not None:
+            if len(seeds) != B:
+                raise ValueError(f"seeds must hold one entry per problem ({B}), not {len(seeds)}")
+            sd = (C.c_uint64 * max(B, 1))(*[int(x) for x in seeds])
+        h = C.c_void_p()
+        check(load().desc_cemp_batch_create(arr, B, self.nsample, int(seed), sd, int(device), C.byref(h)))
+        self.handle = h
+        no, eo = np.zeros(B + 1, dtype=np.int64), np.zeros(B + 1, dtype=np.int64)
+        check(load().desc_cemp_batch_sizes(h, None, ptr(no, I64P), ptr(eo, I64P)))
+        self.node_off, self.edge_off = no, eo
+        self.n, self.m = int(no[B]), int(eo[B])
+
+    def samples(self):
+        """What create sampled, per problem: a list of dicts e_jk / e_ki (m_b x nsample local edge ids, -1 without a cycle), s0
+        (m_b x nsample), has_cycle (m_b bools)."""
+        mc = self.m * self.nsample
+        ejk, eki, s0, hc = out_buffer(mc, np.int32), out_buffer(mc, np.int32), out_buffer(mc), out_buffer(self.m, np.uint8)
+        check(load().desc_cemp_batch_get_samples(self.handle, ptr(ejk, I32P), ptr(eki, I32P), ptr(s0, F64P), ptr(hc, C.POINTER(C.c_uint8))))
+        outs = []
+        for b in range(self.count):
+            e0, e1 = int(self.edge_off[b]), int(self.edge_off[b + 1])
+            sl = slice(e0 * self.nsample, e1 * self.nsample)
+            outs.append(dict(e_jk=ejk[sl].reshape(e1 - e0, self.nsample), e_ki=eki[sl].reshape(e1 - e0, self.nsample),
+                             s0=s0[sl].reshape(e1 - e0, self.nsample), has_cycle=hc[e0:e1].astype(bool)))
+        return outs
+
+    def run(self, beta, max_iter):
+        """The rounds (CEMP.m:107-128) from the initial means.  Returns a list of per-problem S_vec (library's edge order; views of one
+        buffer) and the call's timings."""
+        b = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
+        S = out_buffer(self.m)
+        tm = CempBatchTimings()
+        check(load().desc_cemp_batch_run(self.handle, ptr(b, F64P), b.shape[0], int(max_iter), ptr(S, F64P), C.byref(tm)))
+        outs = [S[int(self.edge_off[k]):int(self.edge_off[k + 1])] for k in range(self.count)]
+        timings = dict(ms_structure=tm.ms_structure, ms_upload=tm.ms_upload, ms_build=tm.ms_build, ms_rounds=tm.ms_rounds, ms_total=tm.ms_total)
+        return outs, timings
+
+    def destroy(self):
+        if self.handle:
+            load().desc_cemp_batch_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def mst_batch_max_n():
+    """desc_mst_batch_max_n: the largest problem (nodes) the batched tree kernel takes."""
+    return int(load().desc_mst_batch_max_n())
+
+
+def mst_batch_check(probs):
+    """desc_mst_batch_check on a sequence of ProblemArrays: the size cap and connectivity of every problem (host only; raises DescError)."""
+    probs = list(probs)
+    arr = (Problem * max(len(probs), 1))(*[q.c for q in probs])
+    check(load().desc_mst_batch_check(arr, len(probs)))
+
+
+def mst_batch_run(probs, s_vec, device=0):
+    """desc_mst_batch_run on a sequence of ProblemArrays and the concatenated S_vec (library's edge order) -> a list of per-problem
+    (R (3,3,n_b) Fortran-ordered, tree edge ids ascending (n_b - 1,), sorted order) and the call's timings."""
+    probs = list(probs)
+    B = len(probs)
+    arr = (Problem * max(B, 1))(*[q.c for q in probs])
+    S = np.ascontiguousarray(s_vec, dtype=np.float64).reshape(-1)
+    no = np.concatenate([[0], np.cumsum([q.n for q in probs], dtype=np.int64)]).astype(np.int64)
+    if S.size != sum(q.m for q in probs):
+        raise ValueError("s_vec must hold one entry per edge of the batch")
+    R = out_buffer(9 * int(no[B]))
+    T = out_buffer(max(int(no[B]) - B, 1), np.int32)
+    tm = MstBatchTimings()
+    check(load().desc_mst_batch_run(arr, B, ptr(S, F64P), int(device), ptr(R, F64P), ptr(T, I32P), C.byref(tm)))
+    outs = []
+    for b in range(B):
+        n0, n1 = int(no[b]), int(no[b + 1])
+        outs.append((R[9 * n0:9 * n1].reshape((3, 3, n1 - n0), order="F"), T[n0 - b:n1 - b - 1].copy()))
+    timings = dict(ms_structure=tm.ms_structure, ms_upload=tm.ms_upload, ms_tree=tm.ms_tree, ms_propagate=tm.ms_propagate, ms_total=tm.ms_total)
+    return outs, timings
 
 
 def gcw_batch_csr(probs):

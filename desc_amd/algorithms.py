@@ -448,6 +448,166 @@ def DESC_init_batch(problems, params, seeds=None, return_info=False):
     return [(R, d["S_vec"]) for (R, _), d in zip(outs, pgd)]
 
 
+def _cemp_batch_params(CEMP_parameters, B, seeds):
+    """The fields CEMP reads, checked once for the whole batch -> (beta, max_iter, nsample, seed, device, seeds)."""
+    beta = _param_vec(CEMP_parameters, "reweighting", "CEMP_parameters")
+    max_iter, nsample = _get(CEMP_parameters, "max_iter"), _get(CEMP_parameters, "nsample")
+    if max_iter is None or int(max_iter) < 0:
+        raise ValueError("CEMP_parameters.max_iter must be an integer >= 0")
+    if nsample is None or int(nsample) < 1:
+        raise ValueError("CEMP_parameters.nsample must be an integer >= 1")
+    if seeds is not None:
+        seeds = [int(x) for x in seeds]
+        if len(seeds) != B:
+            raise ValueError(f"seeds must hold one entry per problem ({B}), not {len(seeds)}")
+    return beta, int(max_iter), int(nsample), int(_get(CEMP_parameters, "seed", 0)), int(_get(CEMP_parameters, "device", 0)), seeds
+
+
+def _check_cemp_batch_degrees(probs):
+    """The batched sampler's staging cap (neighbours of one node), checked before the device is touched."""
+    cap = _lib.cemp_batch_max_degree()
+    for b, q in enumerate(probs):
+        deg = np.bincount(q.ind_i, minlength=q.n) + np.bincount(q.ind_j, minlength=q.n)
+        v = int(np.argmax(deg))
+        if deg[v] > cap:
+            raise ValueError(f"problem {b}: node {v} has {int(deg[v])} neighbours, more than the {cap} the batched sampler stages per row: "
+                             "solve it with CEMP")
+
+
+def _check_mst_batch(probs):
+    """The tree kernel's size cap and connectivity (a host union-find of the library), checked before the device is touched."""
+    try:
+        _lib.mst_batch_check(probs)
+    except _lib.DescError as e:
+        if e.code == _lib.ERR_INVALID:
+            raise ValueError(str(e).split(": ", 1)[-1]) from None
+        raise
+
+
+def _unsort(S, perm):
+    if perm is None:
+        return S
+    out = np.empty_like(S)
+    out[perm] = S
+    return out
+
+
+def CEMP_batch(problems, CEMP_parameters, seeds=None, return_info=False):
+    """CEMP (Algorithms/CEMP.m:24) on B independent small problems in one GPU pass (desc_cemp_batch_*; the reference has no such call).
+
+    ``problems`` as for DESC_PGD_batch; one ``CEMP_parameters`` for the whole batch (``max_iter``, ``reweighting``, ``nsample``, optional
+    ``seed`` / ``device``); ``seeds`` an optional sequence of per-problem sampling seeds.  Returns a list of SVec (caller's edge order):
+    entry b is bit for bit ``CEMP(Ind_b, RijMat_b, CEMP_parameters)`` with that problem's seed, and no bit of it depends on the batch
+    around it.  With ``return_info`` a list of (SVec, dict) carrying the call's ``timings``.
+
+    Refused (ValueError, before the device is touched): not a sequence, an empty edge list, a ``seeds`` list of the wrong length,
+    ``nsample < 1``, ``max_iter < 0``, a missing or empty ``reweighting``, a node of more neighbours than
+    ``_lib.cemp_batch_max_degree()`` (solve that problem with CEMP)."""
+    _check_sequence(problems)
+    beta, max_iter, nsample, seed, device, seeds = _cemp_batch_params(CEMP_parameters, len(problems), seeds)
+    probs, perms = _marshal_problems(problems)
+    if not probs:
+        return []
+    _check_cemp_batch_degrees(probs)
+    try:
+        batch = _lib.CempBatch(probs, nsample, seed, seeds, device)
+    except _lib.DescError as e:
+        if e.code == _lib.ERR_INVALID:
+            raise ValueError(str(e).split(": ", 1)[-1]) from None
+        raise
+    try:
+        outs, timings = batch.run(beta, max_iter)
+    finally:
+        batch.destroy()
+    S = [_unsort(o, perm) for o, perm in zip(outs, perms)]
+    return [(s, dict(timings=timings)) for s in S] if return_info else S
+
+
+def CEMP_GCW_batch(problems, CEMP_parameters, seeds=None, return_info=False):
+    """CEMP_GCW (Algorithms/CEMP_GCW.m) on B independent small problems: CEMP_batch's pass, then the batched eigen-solve with the host
+    weights 1/(SVec + 1e-8) and normalised rows (CEMP_GCW.m:144-146) -- two GPU passes for the whole batch.  Returns a list of R_est
+    (3 x 3 x n_b); with ``return_info`` a list of (R_est, SVec, dict(cemp=..., gcw=...)), SVec bit for bit CEMP_batch's.
+    Refused (ValueError, before the device is touched): what CEMP_batch refuses, and a problem of more than
+    ``_lib.gcw_batch_max_n()`` nodes (solve it with CEMP_GCW)."""
+    _check_sequence(problems)
+    _cemp_batch_params(CEMP_parameters, len(problems), seeds)
+    probs, perms = _marshal_problems(problems)
+    if not probs:
+        return []
+    _check_cemp_batch_degrees(probs)
+    _check_gcw_batch_sizes(probs)
+    cemp = CEMP_batch([_Marshalled(q, perm) for q, perm in zip(probs, perms)], CEMP_parameters, seeds=seeds, return_info=True)
+    # CEMP_batch gave SVec in the caller's order; the eigen-solve takes the library's
+    w = np.concatenate([1.0 / ((S if perm is None else S[perm]) + 1e-8) for (S, _), perm in zip(cemp, perms)])      # CEMP_GCW.m:144
+    outs, timings = _gcw_batch_run(probs, int(_get(CEMP_parameters, "device", 0)), weights=w, normalize_rows=True)
+    if return_info:
+        return [(R, S, dict(cemp=ci, gcw=dict(info, timings=timings))) for (R, info), (S, ci) in zip(outs, cemp)]
+    return [R for R, _ in outs]
+
+
+def _sorted_s_list_mst(probs, perms, S_list):
+    """One SVec per problem in the caller's edge order -> the concatenation in the library's order; refusals name the problem."""
+    if isinstance(S_list, (str, bytes)) or not hasattr(S_list, "__len__") or len(S_list) != len(probs):
+        got = len(S_list) if hasattr(S_list, "__len__") else type(S_list).__name__
+        raise ValueError(f"S_list must hold one SVec per problem ({len(probs)}), not {got}")
+    parts = []
+    for b, (q, perm, S) in enumerate(zip(probs, perms, S_list)):
+        S = np.asarray(S, dtype=np.float64).reshape(-1)
+        if S.shape[0] != q.m:
+            raise ValueError(f"problem {b}: SVec must have one entry per edge ({q.m}), not {S.shape[0]}")
+        if perm is not None:
+            S = S[perm]
+        bad = np.flatnonzero(~np.isfinite(S))
+        if bad.size:
+            raise ValueError(f"problem {b}: SVec entry {int(bad[0] if perm is None else perm[bad[0]])} is not finite")
+        parts.append(S)
+    return np.concatenate(parts) if parts else np.zeros(0)
+
+
+def MST_batch(problems, S_list, device=0, return_info=False):
+    """The tree step of MPLS (Algorithms/MPLS.m:160-193, as MST()) on B independent small problems in one GPU launch
+    (desc_mst_batch_run): ``S_list[b]`` is problem b's SVec in the caller's edge order.  Returns a list of R (3 x 3 x n_b): entry b is
+    bit for bit ``MST(Ind_b, RijMat_b, S_b)``.  With ``return_info`` a list of (R, dict(tree_edges=..., timings=...)), ``tree_edges`` the
+    0-based rows of the caller's ``Ind`` that form the tree (ascending), as MST() returns them.
+    Refused (ValueError, before the device is touched): not a sequence, an empty edge list, an S_list of the wrong length or an entry of
+    the wrong size or holding a non-finite value, a problem of more than ``_lib.mst_batch_max_n()`` nodes (solve it with MST), a
+    disconnected problem (a node id in 1..max(Ind) that no edge touches counts as a component)."""
+    _check_sequence(problems)
+    probs, perms = _marshal_problems(problems)
+    S = _sorted_s_list_mst(probs, perms, S_list)
+    if not probs:
+        return []
+    _check_mst_batch(probs)
+    try:
+        outs, timings = _lib.mst_batch_run(probs, S, device)
+    except _lib.DescError as e:
+        if e.code == _lib.ERR_INVALID:
+            raise ValueError(str(e).split(": ", 1)[-1]) from None
+        raise
+    if not return_info:
+        return [R for R, _ in outs]
+    return [(R, dict(tree_edges=tree if perm is None else np.sort(perm[tree]), timings=timings)) for (R, tree), perm in zip(outs, perms)]
+
+
+def CEMP_MST_batch(problems, CEMP_parameters, seeds=None, return_info=False):
+    """The CEMP+MST initialisation (MPLS.m:36-193, the "CEMP+MST" row of Demo/compare_algorithms.m) on B independent small problems:
+    CEMP_batch, then MST_batch on its SVec.  Returns a list of R_init (3 x 3 x n_b); with ``return_info`` a list of
+    (R_init, SVec, dict(cemp=..., mst=...)).  Refused (ValueError, before the device is touched): what CEMP_batch and MST_batch refuse."""
+    _check_sequence(problems)
+    _cemp_batch_params(CEMP_parameters, len(problems), seeds)
+    probs, perms = _marshal_problems(problems)
+    if not probs:
+        return []
+    _check_cemp_batch_degrees(probs)
+    _check_mst_batch(probs)
+    marshalled = [_Marshalled(q, perm) for q, perm in zip(probs, perms)]
+    cemp = CEMP_batch(marshalled, CEMP_parameters, seeds=seeds, return_info=True)
+    mst = MST_batch(marshalled, [S for S, _ in cemp], device=int(_get(CEMP_parameters, "device", 0)), return_info=True)
+    if return_info:
+        return [(R, S, dict(cemp=ci, mst=mi)) for (R, mi), (S, ci) in zip(mst, cemp)]
+    return [R for R, _ in mst]
+
+
 def _run_with_plots(solver, p, params, prob, dprob, perm, verbose, adam=None):
     """params.make_plots = true (DESC_PGD.m:235-239): after every iteration the error of S_vec against params.ErrVec and
     the rotation error of GCW(S_vec) against params.R_orig (GlobalSOdCorrectRight = the alignment of Rotation_Alignment).

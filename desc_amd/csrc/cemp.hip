@@ -18,16 +18,11 @@
 #include <vector>
 
 #include "device_utils.h"
+#include "cemp_math.h"
 #include "cemp_state.h"
 
 namespace desc {
 namespace {
-
-__device__ __forceinline__ double abs_acos_ext_c(double x) {
-    if (x > 1.0) return acosh(x);
-    if (x < -1.0) return hypot(M_PI, acosh(-x));
-    return acos(x);
-}
 
 __global__ __launch_bounds__(256) void k_cemp_s0(const int32_t* pos_edge, const int32_t* ind_i, const int32_t* ind_j, const int32_t* kk,
                                                  const int32_t* e_jk, const int32_t* e_ki, const double* rij, double* S0,
@@ -45,20 +40,7 @@ __global__ __launch_bounds__(256) void k_cemp_s0(const int32_t* pos_edge, const 
             double pb[9], pc[9];                           // the two gathered blocks, in registers (16-byte loads)
             load_block9(rij + 9 * (int64_t)e_jk[c], pb);
             load_block9(rij + 9 * (int64_t)e_ki[c], pc);
-            const bool tb = !(j < k), tc = !(k < i);
-            double tr = 0.0;
-            for (int r = 0; r < 3; ++r) {
-                double P[3];
-                for (int q = 0; q < 3; ++q) {
-                    double a2 = 0.0;
-                    for (int u = 0; u < 3; ++u) a2 = a2 + A[r + 3 * u] * (tb ? pb[q + 3 * u] : pb[u + 3 * q]);
-                    P[q] = a2;
-                }
-                double a3 = 0.0;
-                for (int u = 0; u < 3; ++u) a3 = a3 + P[u] * (tc ? pc[r + 3 * u] : pc[u + 3 * r]);
-                tr = tr + a3;
-            }
-            const double d = abs_acos_ext_c((tr - 1.0) / 2.0) / M_PI;
+            const double d = cemp_cycle_dist(A, pb, pc, !(j < k), !(k < i));
             S0[c] = d;
             acc += d;
         }
@@ -104,20 +86,7 @@ __global__ __launch_bounds__(512) void k_cemp_s0_staged(const int32_t* pos_edge,
                 const double2 c0 = *reinterpret_cast<const double2*>(sb), c1 = *reinterpret_cast<const double2*>(sb + 2), c2 = *reinterpret_cast<const double2*>(sb + 4),
                               c3 = *reinterpret_cast<const double2*>(sb + 6);
                 pc[0] = c0.x; pc[1] = c0.y; pc[2] = c1.x; pc[3] = c1.y; pc[4] = c2.x; pc[5] = c2.y; pc[6] = c3.x; pc[7] = c3.y; pc[8] = sb[8];
-                const bool tb = !(j < k), tc = !(k < i);
-                double tr = 0.0;
-                for (int r = 0; r < 3; ++r) {
-                    double P[3];
-                    for (int q = 0; q < 3; ++q) {
-                        double a2 = 0.0;
-                        for (int u = 0; u < 3; ++u) a2 = a2 + A[r + 3 * u] * (tb ? pb[q + 3 * u] : pb[u + 3 * q]);
-                        P[q] = a2;
-                    }
-                    double a3 = 0.0;
-                    for (int u = 0; u < 3; ++u) a3 = a3 + P[u] * (tc ? pc[r + 3 * u] : pc[u + 3 * r]);
-                    tr = tr + a3;
-                }
-                const double dd = abs_acos_ext_c((tr - 1.0) / 2.0) / M_PI;
+                const double dd = cemp_cycle_dist(A, pb, pc, !(j < k), !(k < i));
                 S0[c] = dd;
                 acc += dd;
             }
@@ -154,41 +123,7 @@ __global__ __launch_bounds__(256) void k_cemp_round(const int32_t* pos_edge, con
     const int lane = threadIdx.x & 63;
     const int64_t wid = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, nw = ((int64_t)gridDim.x * 256) >> 6;
     for (int64_t l = wid; l < m_pos; l += nw) {
-        if (nsample <= 4 * 64) {                       // weights stay in registers: one pass over the samples
-            double wr[4] = {0.0, 0.0, 0.0, 0.0}, dr[4] = {0.0, 0.0, 0.0, 0.0};
-            double wsum = 0.0;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int s = lane + 64 * u;
-                if (s < nsample) {
-                    const int64_t c = l * nsample + s;
-                    wr[u] = exp(-beta * (S_old[e_ki[c]] + S_old[e_jk[c]]));      // :118-120
-                    dr[u] = S0[c];
-                    wsum += wr[u];
-                }
-            }
-            wsum = group_sum<64>(wsum);
-            double acc = 0.0;
-            const double rws = 1.0 / wsum;                 // one division per edge (the reference divides every weight: the same to 1 ulp)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) if (lane + 64 * u < nsample) acc += (wr[u] * rws) * dr[u];   // :122-125
-            acc = group_sum<64>(acc);
-            if (lane == 0) cemp_store<MP>(S_new, pos_edge[l], -1, pos_edge[l], acc, res, rh, alpha);
-            continue;
-        }
-        double wsum = 0.0;
-        for (int s = lane; s < nsample; s += 64) {
-            const int64_t c = l * nsample + s;
-            wsum += exp(-beta * (S_old[e_ki[c]] + S_old[e_jk[c]]));                  // :118-120
-        }
-        wsum = group_sum<64>(wsum);
-        double acc = 0.0;
-        for (int s = lane; s < nsample; s += 64) {
-            const int64_t c = l * nsample + s;
-            const double w = exp(-beta * (S_old[e_ki[c]] + S_old[e_jk[c]]));
-            acc += (w / wsum) * S0[c];                                               // :122-125
-        }
-        acc = group_sum<64>(acc);
+        const double acc = cemp_edge_round(l, lane, nsample, beta, e_jk, e_ki, S0, S_old);      // cemp_math.h
         if (lane == 0) cemp_store<MP>(S_new, pos_edge[l], -1, pos_edge[l], acc, res, rh, alpha);
     }
 }

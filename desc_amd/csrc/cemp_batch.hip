@@ -1,0 +1,329 @@
+// CEMP for many small problems in one GPU pass (desc_cemp_batch_*): the baseline curve of a Monte-Carlo study next to desc_pgd_batch_*.
+//
+// cemp.hip solves one problem per call: the device sampler's bitmap / rank / codegree launches, a histogram read-back, allocations, the S0
+// launch, max_iter round launches, one synchronise and one download -- a latency chain of a few milliseconds for a 100-node graph.  Here
+// the edge lists of all B problems lie behind one another and TWO kernels walk the concatenation, one wave per edge:
+//
+//   k_cemp_batch_build  CEMP.m:44-103, ONE launch in create.  The wave of edge (i, j) finds its problem through a per-edge table, intersects
+//                       the CSR rows of i and j in ascending k (lanes stride over the shorter row and binary-search the longer one, hits are
+//                       ranked by ballot / popcount), stages the common neighbours' positions in the two rows in LDS, draws sample t as
+//                       staged[desc_sample_key(seed_b, local edge id, t) mod codeg] -- desc_cemp_run's rule -- writes e_jk / e_ki as
+//                       batch-global edge ids, evaluates S0 and the initial mean.  An edge without a common neighbour gets S = 1 in both
+//                       ping-pong buffers and a cleared has_cycle flag.
+//   k_cemp_batch_round  :107-128, max_iter launches for the whole batch.
+//
+// Layout.  A fixed stride of nsample slots per edge of the batch: slot (g, t) at g * nsample + t for the batch-global edge id g.  No
+// compaction of the edges with cycles, no histogram, no host round trip; the rounds skip an edge whose flag is cleared.
+//
+// Bit-equality with desc_cemp_run.  The sampled cycles are the same (the same ascending list of common neighbours, the same key), the
+// per-cycle trace product and the per-edge round are the text of cemp_math.h that cemp.hip runs, sample s sits on lane s & 63 in both,
+// and the sums over lanes are group_sum<64>.
+//
+// Composition independence.  An edge's wave reads its own problem's rows, rotations and S values and writes its own slots; which
+// workgroup runs it, how many edges the grid strides over and how much LDS the launch declares (sized from the longest row of the batch,
+// addressed with the edge's own codegree) enter no result.
+//
+// Control flow.  No grid-wide barrier, no spinning on memory, nothing between workgroups, no atomics.  Every loop is bounded by a row
+// length or nsample.  The kernels contain no workgroup barrier at all: a wave's staging area is private to it (wave barriers only).
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "batch_csr.h"
+#include "cemp_math.h"
+#include "device_utils.h"
+
+namespace desc {
+namespace {
+
+constexpr int CEMP_BATCH_MAX_DEGREE = 4096;            // longest CSR row: 4 waves x 4096 staged positions x 4 B = the 64 KiB every launch may declare
+static_assert(CEMP_BATCH_MAX_DEGREE >= 512 && CEMP_BATCH_MAX_DEGREE <= 65536, "row positions are packed in 16 bits each");
+static_assert(4 * CEMP_BATCH_MAX_DEGREE * 4 <= 64 * 1024, "LDS budget");
+
+struct CbProb { int32_t n, m, node_off, edge_off; uint64_t seed; };
+
+struct CbArgs {
+    const CbProb* prob;
+    const int32_t* eprob;       // batch-global edge id -> problem
+    const int32_t* ii;          // local endpoints of every edge
+    const int32_t* jj;
+    const int32_t* rowptr;      // problem b's n_b + 1 row starts at node_off[b] + b, counted inside the problem
+    const int32_t* adj;         // 2 m_b local neighbour ids at 2 edge_off[b]
+    const int32_t* adj_eid;     // 2 m_b local edge ids
+    const double* rij;          // 9 per edge
+    int32_t* e_jk;              // M * nsample batch-global edge ids (-1: the edge has no cycle)
+    int32_t* e_ki;
+    double* S0;                 // M * nsample
+    double* S_init;             // M: the initial means (:102-103), kept for the next run of the handle
+    double* S_a;                // M: the ping-pong buffers of the rounds
+    double* S_b;
+    uint8_t* has_cycle;         // M
+    int32_t M, nsample, lds_cap;
+};
+
+__global__ __launch_bounds__(256) void k_cemp_batch_build(CbArgs a) {
+    extern __shared__ uint32_t cb_stage[];             // per wave: lds_cap packed positions (in row i | in row j << 16) of the common neighbours
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t* st = cb_stage + (size_t)wv * a.lds_cap;
+    const int nsample = a.nsample;
+    const int64_t wid = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, nw = ((int64_t)gridDim.x * 256) >> 6;
+    for (int64_t g64 = wid; g64 < a.M; g64 += nw) {
+        const int g = __builtin_amdgcn_readfirstlane((int)g64);
+        const int b = uniform_load(a.eprob, g);
+        const CbProb pd = a.prob[b];
+        const int e = g - pd.edge_off;                                   // the edge's index in its problem's (i, j)-sorted list
+        const int i = uniform_load(a.ii, g), j = uniform_load(a.jj, g);
+        const int32_t* rp = a.rowptr + pd.node_off + b;
+        const int32_t* adj = a.adj + 2 * (int64_t)pd.edge_off;
+        const int32_t* eid = a.adj_eid + 2 * (int64_t)pd.edge_off;
+        const int ri = uniform_load(rp, i), di = uniform_load(rp, i + 1) - ri;
+        const int rj = uniform_load(rp, j), dj = uniform_load(rp, j + 1) - rj;
+        // ---- the common neighbours in ascending k (:48-56): stride over the shorter row, search the longer one
+        const bool i_short = di <= dj;
+        const int rs = i_short ? ri : rj, ds = i_short ? di : dj, rl = i_short ? rj : ri, dl = i_short ? dj : di;
+        int cd = 0;
+        for (int t0 = 0; t0 < ds; t0 += 64) {
+            const int t = t0 + lane;
+            bool hit = false;
+            int lo = 0;
+            if (t < ds) {
+                const int k = adj[rs + t];
+                int hi = dl;
+                while (lo < hi) { const int mid = (lo + hi) >> 1; if (adj[rl + mid] < k) lo = mid + 1; else hi = mid; }
+                hit = lo < dl && adj[rl + lo] == k;
+            }
+            const unsigned long long mk = __ballot(hit);
+            const int pos = cd + __popcll(mk & ((1ull << lane) - 1ull));
+            if (hit && pos < a.lds_cap) st[pos] = i_short ? ((uint32_t)t | (uint32_t)lo << 16) : ((uint32_t)lo | (uint32_t)t << 16);
+            cd += __popcll(mk);
+        }
+        cd = __builtin_amdgcn_readfirstlane(cd);
+        __builtin_amdgcn_wave_barrier();
+        const int64_t base = (int64_t)g * nsample;
+        if (cd == 0) {                                                   // :103 SVec(~IndPosbin) = 1
+            for (int t = lane; t < nsample; t += 64) { a.e_jk[base + t] = -1; a.e_ki[base + t] = -1; a.S0[base + t] = 0.0; }
+            if (lane == 0) { a.S_init[g] = 1.0; a.S_a[g] = 1.0; a.S_b[g] = 1.0; a.has_cycle[g] = 0; }
+            continue;
+        }
+        // ---- nsample draws with replacement (:57-65), S0 (:70-100) and the initial mean (:102)
+        double A[9];
+        load_block9(a.rij + 9 * (int64_t)g, A);
+        double acc = 0.0;
+        for (int s = lane; s < nsample; s += 64) {
+            const uint32_t p = st[d_sample_key(pd.seed, (uint64_t)e, (uint64_t)s) % (uint64_t)cd];
+            const int xi = (int)(p & 0xFFFFu), xj = (int)(p >> 16);
+            const int k = adj[ri + xi];
+            const int eki = pd.edge_off + eid[ri + xi], ejk = pd.edge_off + eid[rj + xj];
+            double pb[9], pc[9];
+            load_block9(a.rij + 9 * (int64_t)ejk, pb);
+            load_block9(a.rij + 9 * (int64_t)eki, pc);
+            const double d = cemp_cycle_dist(A, pb, pc, !(j < k), !(k < i));
+            a.e_jk[base + s] = ejk; a.e_ki[base + s] = eki; a.S0[base + s] = d;
+            acc += d;
+        }
+        acc = group_sum<64>(acc);
+        if (lane == 0) {                                                 // :102
+            const double mean = acc / (double)nsample;
+            a.S_init[g] = mean; a.S_a[g] = mean; a.S_b[g] = mean; a.has_cycle[g] = 1;
+        }
+        __builtin_amdgcn_wave_barrier();                                 // the staging area is reused by the wave's next edge
+    }
+}
+
+__global__ __launch_bounds__(256) void k_cemp_batch_round(const int32_t* e_jk, const int32_t* e_ki, const double* S0, const uint8_t* has_cycle,
+                                                          const double* S_old, double* S_new, int M, int nsample, double beta) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wid = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, nw = ((int64_t)gridDim.x * 256) >> 6;
+    for (int64_t g = wid; g < M; g += nw) {
+        if (!has_cycle[g]) continue;                                     // no cycles: SVec stays 1 (:103, :126); the same in all 64 lanes
+        const double acc = cemp_edge_round(g, lane, nsample, beta, e_jk, e_ki, S0, S_old);      // cemp_math.h
+        if (lane == 0) S_new[g] = acc;
+    }
+}
+
+}  // namespace
+}  // namespace desc
+
+using namespace desc;
+
+struct desc_cemp_batch : desc::BatchCsr {
+    int device = 0;
+    int32_t nsample = 0, max_deg = 0, grid = 1;
+    hipStream_t stream = nullptr;
+    DevArena mem;
+    CbArgs a{};
+    double ms_structure = 0, ms_upload = 0, ms_build = 0;
+};
+
+namespace {
+
+void cb_free(desc_cemp_batch* h) {
+    if (!h) return;
+    if (h->stream) { (void)hipSetDevice(h->device); (void)hipStreamSynchronize(h->stream); }
+    h->mem.release();
+    if (h->stream) stream_release(h->stream);
+    delete h;
+}
+
+template <class T>
+int cb_upload(desc_cemp_batch* h, const T** dst, const T* src, size_t n) {
+    T* d = nullptr;
+    int rc = h->mem.alloc(&d, n); if (rc) return rc;
+    if (n) DESC_HIP(hipMemcpyAsync(d, src, sizeof(T) * n, hipMemcpyHostToDevice, h->stream));
+    *dst = d;
+    return DESC_OK;
+}
+
+int cb_create(const desc_problem* probs, int32_t count, int32_t nsample, uint64_t seed, const uint64_t* seeds, int32_t device, desc_cemp_batch* h) {
+    auto t0 = std::chrono::steady_clock::now();
+    h->device = device; h->nsample = nsample;
+    if (nsample < 1) return fail(DESC_ERR_INVALID, "need nsample >= 1");
+    // ---- host: validation, the per-problem CSR, the degree maxima
+    int rc = batch_csr_host(probs, count, nullptr, h);
+    if (rc) return rc;
+    for (int32_t b = 0; b < count; ++b) {
+        const int32_t* rp = h->rowptr.data() + h->node_off[(size_t)b] + b;
+        for (int64_t v = 0; v < probs[b].n; ++v) {
+            const int32_t d = rp[v + 1] - rp[v];
+            if (d > CEMP_BATCH_MAX_DEGREE)
+                return fail(DESC_ERR_INVALID, "problem %d: node %lld has %d neighbours, more than the %d the batched sampler stages per row: solve it with CEMP",
+                            b, (long long)v, (int)d, CEMP_BATCH_MAX_DEGREE);
+            h->max_deg = std::max(h->max_deg, d);
+        }
+    }
+    if ((int64_t)h->M * nsample >= (1ll << 31))
+        return fail(DESC_ERR_TOO_LARGE, "the batch holds %lld edges with %d samples each: m_total * nsample exceeds 2^31, split the batch", (long long)h->M, (int)nsample);
+    h->ms_structure = ms_since(t0);
+    if (count == 0) return DESC_OK;
+
+    // ---- device: nothing above touched it
+    int ndev = desc_device_count();
+    if (ndev < 0) return ndev;
+    if (ndev == 0) return fail(DESC_ERR_HIP, "no HIP device visible: the batched CEMP has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(DESC_ERR_INVALID, "device %d out of range (0..%d)", device, ndev - 1);
+    hipError_t he = hipSetDevice(device);
+    if (he == hipSuccess) he = stream_acquire(&h->stream);
+    if (he != hipSuccess) return fail(DESC_ERR_HIP, "device %d: %s", device, hipGetErrorString(he));
+    auto t1 = std::chrono::steady_clock::now();
+    const size_t M = (size_t)h->M, MC = M * (size_t)nsample;
+    hvec<CbProb> pr((size_t)count);
+    hvec<int32_t> eprob(M);
+    hvec<double> rij(9 * M);                           // all rotations in one copy
+    for (int32_t b = 0; b < count; ++b) {
+        const size_t eo = (size_t)h->edge_off[(size_t)b], m = (size_t)probs[b].m;
+        pr[(size_t)b] = CbProb{(int32_t)probs[b].n, (int32_t)m, (int32_t)h->node_off[(size_t)b], (int32_t)eo, seeds ? seeds[b] : seed};
+        std::fill(eprob.begin() + eo, eprob.begin() + eo + m, b);
+        std::memcpy(rij.data() + 9 * eo, probs[b].rij, sizeof(double) * 9 * m);
+    }
+    CbArgs& a = h->a;
+    if ((rc = cb_upload(h, &a.prob, pr.data(), pr.size())) || (rc = cb_upload(h, &a.eprob, eprob.data(), M)) ||
+        (rc = cb_upload(h, &a.ii, h->ii.data(), M)) || (rc = cb_upload(h, &a.jj, h->jj.data(), M)) ||
+        (rc = cb_upload(h, &a.rowptr, h->rowptr.data(), h->rowptr.size())) || (rc = cb_upload(h, &a.adj, h->adj.data(), 2 * M)) ||
+        (rc = cb_upload(h, &a.adj_eid, h->adj_eid.data(), 2 * M)) || (rc = cb_upload(h, &a.rij, rij.data(), 9 * M))) return rc;
+    if ((rc = h->mem.alloc(&a.e_jk, MC)) || (rc = h->mem.alloc(&a.e_ki, MC)) || (rc = h->mem.alloc(&a.S0, MC)) || (rc = h->mem.alloc(&a.S_init, M)) ||
+        (rc = h->mem.alloc(&a.S_a, M)) || (rc = h->mem.alloc(&a.S_b, M)) || (rc = h->mem.alloc(&a.has_cycle, M))) return rc;
+    DESC_HIP(hipStreamSynchronize(h->stream));         // the staging vectors go out of scope below
+    h->ms_upload = ms_since(t1);
+
+    // ---- CEMP.m:44-103 for the whole batch: one launch
+    auto t2 = std::chrono::steady_clock::now();
+    a.M = (int32_t)M; a.nsample = nsample;
+    a.lds_cap = std::max(64, (h->max_deg + 63) / 64 * 64);              // the longest row bounds every codegree
+    h->grid = grid_for((int64_t)M, 8192, 4);
+    const size_t lds = (size_t)4 * (size_t)a.lds_cap * sizeof(uint32_t);
+    if (lds > 64 * 1024) return fail(DESC_ERR_STATE, "LDS budget exceeded (%zu bytes)", lds);
+    hipLaunchKernelGGL(k_cemp_batch_build, dim3((unsigned)h->grid), dim3(256), lds, h->stream, a);
+    DESC_HIP(hipGetLastError());
+    DESC_HIP(hipStreamSynchronize(h->stream));
+    h->ms_build = ms_since(t2);
+    return DESC_OK;
+}
+
+int cb_run(desc_cemp_batch* h, const double* beta, int32_t n_beta, int32_t max_iter, double* s_vec, desc_cemp_batch_timings* tm) {
+    auto t0 = std::chrono::steady_clock::now();
+    if (tm) { tm->ms_structure = h->ms_structure; tm->ms_upload = h->ms_upload; tm->ms_build = h->ms_build; tm->ms_rounds = 0; tm->ms_total = 0; }
+    if (!beta || n_beta < 1 || max_iter < 0) return fail(DESC_ERR_INVALID, "need beta, n_beta >= 1 and max_iter >= 0");
+    if (h->count == 0) { if (tm) tm->ms_total = ms_since(t0); return DESC_OK; }
+    if (!s_vec) return fail(DESC_ERR_INVALID, "s_vec is NULL");
+    DESC_HIP(hipSetDevice(h->device));
+    const CbArgs& a = h->a;
+    const size_t M = (size_t)h->M;
+    // every run starts from the initial means: S_b already holds 1 where the rounds never write, and is written everywhere else before it is read
+    DESC_HIP(hipMemcpyAsync(a.S_a, a.S_init, sizeof(double) * M, hipMemcpyDeviceToDevice, h->stream));
+    double* S[2] = {a.S_a, a.S_b};
+    int cur = 0;
+    for (int it = 0; it < max_iter; ++it) {                                         // :107
+        const double b = beta[it < n_beta ? it : n_beta - 1];                       // :30-34: missing betas repeat the last one
+        hipLaunchKernelGGL(k_cemp_batch_round, dim3((unsigned)h->grid), dim3(256), 0, h->stream, a.e_jk, a.e_ki, a.S0, a.has_cycle, S[cur], S[cur ^ 1], a.M, a.nsample, b);
+        cur ^= 1;
+    }
+    DESC_HIP(hipGetLastError());
+    DESC_HIP(hipMemcpyAsync(s_vec, S[cur], sizeof(double) * M, hipMemcpyDeviceToHost, h->stream));
+    DESC_HIP(hipStreamSynchronize(h->stream));
+    if (tm) { tm->ms_rounds = ms_since(t0); tm->ms_total = tm->ms_rounds; }
+    return DESC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t desc_cemp_batch_max_degree(void) { return CEMP_BATCH_MAX_DEGREE; }
+
+int desc_cemp_batch_create(const desc_problem* probs, int32_t count, int32_t nsample, uint64_t seed, const uint64_t* seeds, int32_t device,
+                           desc_cemp_batch** out) {
+    return no_throw("desc_cemp_batch_create", [&]() -> int {
+        if (!out) return fail(DESC_ERR_INVALID, "out is NULL");
+        *out = nullptr;
+        if (count < 0 || (count > 0 && !probs)) return fail(DESC_ERR_INVALID, "NULL argument or negative count");
+        desc_cemp_batch* h = new desc_cemp_batch();
+        int rc;
+        try { rc = cb_create(probs, count, nsample, seed, seeds, device, h); }
+        catch (...) { cb_free(h); throw; }
+        if (rc) { const std::string msg = desc_last_error(); cb_free(h); return fail(rc, "%s", msg.c_str()); }
+        *out = h;
+        return DESC_OK;
+    });
+}
+
+int desc_cemp_batch_sizes(const desc_cemp_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off) {
+    if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
+    if (count) *count = h->count;
+    if (node_off) std::copy(h->node_off.begin(), h->node_off.end(), node_off);
+    if (edge_off) std::copy(h->edge_off.begin(), h->edge_off.end(), edge_off);
+    return DESC_OK;
+}
+
+int desc_cemp_batch_get_samples(desc_cemp_batch* h, int32_t* e_jk, int32_t* e_ki, double* s0, uint8_t* has_cycle) {
+    return no_throw("desc_cemp_batch_get_samples", [&]() -> int {
+        if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
+        if (h->count == 0) return DESC_OK;
+        DESC_HIP(hipSetDevice(h->device));
+        const size_t M = (size_t)h->M, MC = M * (size_t)h->nsample;
+        if (e_jk) DESC_HIP(hipMemcpyAsync(e_jk, h->a.e_jk, sizeof(int32_t) * MC, hipMemcpyDeviceToHost, h->stream));
+        if (e_ki) DESC_HIP(hipMemcpyAsync(e_ki, h->a.e_ki, sizeof(int32_t) * MC, hipMemcpyDeviceToHost, h->stream));
+        if (s0) DESC_HIP(hipMemcpyAsync(s0, h->a.S0, sizeof(double) * MC, hipMemcpyDeviceToHost, h->stream));
+        if (has_cycle) DESC_HIP(hipMemcpyAsync(has_cycle, h->a.has_cycle, M, hipMemcpyDeviceToHost, h->stream));
+        DESC_HIP(hipStreamSynchronize(h->stream));
+        for (int32_t b = 0; b < h->count; ++b) {                         // batch-global -> local edge ids (-1 stays -1)
+            const int32_t eo = (int32_t)h->edge_off[(size_t)b];
+            const size_t c0 = (size_t)eo * (size_t)h->nsample, c1 = (size_t)h->edge_off[(size_t)b + 1] * (size_t)h->nsample;
+            for (int32_t* q : {e_jk, e_ki}) if (q) for (size_t c = c0; c < c1; ++c) if (q[c] >= 0) q[c] -= eo;
+        }
+        return DESC_OK;
+    });
+}
+
+int desc_cemp_batch_run(desc_cemp_batch* h, const double* beta, int32_t n_beta, int32_t max_iter, double* s_vec, desc_cemp_batch_timings* timings) {
+    return no_throw("desc_cemp_batch_run", [&]() -> int {
+        if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
+        return cb_run(h, beta, n_beta, max_iter, s_vec, timings);
+    });
+}
+
+void desc_cemp_batch_destroy(desc_cemp_batch* h) { cb_free(h); }
+
+}  // extern "C"

@@ -129,6 +129,9 @@ int build_cemp_samples_host(const desc_problem* prob, int32_t nsample, uint64_t 
 // MPLS.m:160-193 (mst.hip): minimum spanning tree of the graph weighted by d_s + 1 (d_s: m doubles on the problem's device) and the
 // rotations propagated from node 1 along it into R_out (n*9 host doubles); tree_edges (nullable): the n - 1 edge ids, ascending
 int mst_device(const desc_device_problem* dp, const double* d_s, double* R_out, int32_t* tree_edges);
+// the tail of mst_device, shared with mst_batch.hip: rooting at node 1 (R_1 = I) and breadth-first propagation (MPLS.m:171-193) along the
+// cnt = n - 1 tree edges ids[] (any order; ii / jj: the problem's endpoints), blk: their 72-byte blocks in the order of ids
+int mst_propagate(int64_t n, const int32_t* ii, const int32_t* jj, const int32_t* ids, int cnt, const double* blk, double* R_out);
 // connected components (mst.hip: mst_device's Boruvka rounds with all keys equal): comp_out (n host ints) gets one label per node,
 // equal labels = one component; *count = the number of components
 int components_device(const desc_device_problem* dp, int32_t* comp_out, int64_t* count);

@@ -34,6 +34,7 @@
 #include <new>
 #include <vector>
 
+#include "batch_csr.h"
 #include "device_utils.h"
 #include "small_dense.h"
 
@@ -339,16 +340,48 @@ __global__ __launch_bounds__(256, 2) void k_gcw_batch(GbArgs a) {
 }  // namespace
 }  // namespace desc
 
+namespace desc {
+
+int batch_csr_host(const desc_problem* probs, int32_t count, const std::function<int(int32_t, const desc_problem&)>& extra, BatchCsr* h) {
+    h->count = count;
+    h->node_off.assign((size_t)count + 1, 0); h->edge_off.assign((size_t)count + 1, 0);
+    for (int32_t b = 0; b < count; ++b) {
+        int rc = validate_problem(&probs[b], true);
+        if (rc) { const std::string msg = desc_last_error(); return fail(rc, "problem %d: %s", b, msg.c_str()); }
+        if (probs[b].m == 0) return fail(DESC_ERR_INVALID, "problem %d: empty edge list", b);
+        if (extra && (rc = extra(b, probs[b]))) return rc;
+        h->node_off[(size_t)b + 1] = h->node_off[(size_t)b] + probs[b].n;
+        h->edge_off[(size_t)b + 1] = h->edge_off[(size_t)b] + probs[b].m;
+        h->max_n = std::max<int32_t>(h->max_n, (int32_t)probs[b].n);
+    }
+    h->N = h->node_off[(size_t)count]; h->M = h->edge_off[(size_t)count];
+    if (h->M >= (1ll << 30))
+        return fail(DESC_ERR_TOO_LARGE, "the batch holds %lld edges in total: the 2^30 index budget is exceeded, split the batch", (long long)h->M);
+    h->ii.resize((size_t)h->M); h->jj.resize((size_t)h->M);
+    h->rowptr.resize((size_t)h->N + (size_t)count); h->adj.resize(2 * (size_t)h->M); h->adj_eid.resize(2 * (size_t)h->M);
+    const int T = std::max(1, std::min(count, 16));
+    run_threads(T, [&](int t) {
+        hvec<int32_t> rp, ad, ae;
+        for (int32_t b = t; b < count; b += T) {
+            const int64_t n = probs[b].n, m = probs[b].m, eo = h->edge_off[(size_t)b];
+            std::memcpy(h->ii.data() + eo, probs[b].ind_i, sizeof(int32_t) * (size_t)m);
+            std::memcpy(h->jj.data() + eo, probs[b].ind_j, sizeof(int32_t) * (size_t)m);
+            build_csr(n, m, probs[b].ind_i, probs[b].ind_j, rp, ad, ae);
+            std::memcpy(h->rowptr.data() + h->node_off[(size_t)b] + b, rp.data(), sizeof(int32_t) * (size_t)(n + 1));
+            std::memcpy(h->adj.data() + 2 * eo, ad.data(), sizeof(int32_t) * 2 * (size_t)m);
+            std::memcpy(h->adj_eid.data() + 2 * eo, ae.data(), sizeof(int32_t) * 2 * (size_t)m);
+        }
+    });
+    return DESC_OK;
+}
+
+}  // namespace desc
+
 using namespace desc;
 
-struct desc_gcw_batch {
+struct desc_gcw_batch : desc::BatchCsr {     // offsets and the per-problem CSR (local ids): batch_csr.h
     int device = 0;
-    int32_t count = 0, max_n = 0;
     hipStream_t stream = nullptr;
-    hvec<int64_t> node_off, edge_off;
-    hvec<int32_t> ii, jj;                     // local endpoints of every problem behind one another (host checks, the refusal's node)
-    hvec<int32_t> rowptr, adj, adj_eid;       // per-problem CSR, local ids: rowptr of problem b at node_off[b] + b
-    int64_t N = 0, M = 0;
     DevArena mem;
     GbProb* d_prob = nullptr;
     int32_t *d_rowptr = nullptr, *d_adj = nullptr, *d_adj_eid = nullptr;
@@ -376,38 +409,12 @@ int gb_upload(desc_gcw_batch* h, T** dst, const T* src, size_t n) {
 
 // validation, offsets and the per-problem CSR: no device
 int gb_host_part(const desc_problem* probs, int32_t count, desc_gcw_batch* h) {
-    h->count = count;
-    h->node_off.assign((size_t)count + 1, 0); h->edge_off.assign((size_t)count + 1, 0);
-    for (int32_t b = 0; b < count; ++b) {
-        int rc = validate_problem(&probs[b], true);
-        if (rc) { const std::string msg = desc_last_error(); return fail(rc, "problem %d: %s", b, msg.c_str()); }
-        if (probs[b].m == 0) return fail(DESC_ERR_INVALID, "problem %d: empty edge list", b);
-        if (probs[b].n > GCW_BATCH_MAX_N)
+    return batch_csr_host(probs, count, [](int32_t b, const desc_problem& q) -> int {
+        if (q.n > GCW_BATCH_MAX_N)
             return fail(DESC_ERR_INVALID, "problem %d: n = %lld exceeds %d (the 3n x 6 blocks of the eigen-solve must fit the LDS of one workgroup): solve it with GCW / DESC_init",
-                        b, (long long)probs[b].n, GCW_BATCH_MAX_N);
-        h->node_off[(size_t)b + 1] = h->node_off[(size_t)b] + probs[b].n;
-        h->edge_off[(size_t)b + 1] = h->edge_off[(size_t)b] + probs[b].m;
-        h->max_n = std::max<int32_t>(h->max_n, (int32_t)probs[b].n);
-    }
-    h->N = h->node_off[(size_t)count]; h->M = h->edge_off[(size_t)count];
-    if (h->M >= (1ll << 30))
-        return fail(DESC_ERR_TOO_LARGE, "the batch holds %lld edges in total: the 2^30 index budget is exceeded, split the batch", (long long)h->M);
-    h->ii.resize((size_t)h->M); h->jj.resize((size_t)h->M);
-    h->rowptr.resize((size_t)h->N + (size_t)count); h->adj.resize(2 * (size_t)h->M); h->adj_eid.resize(2 * (size_t)h->M);
-    const int T = std::max(1, std::min(count, 16));
-    run_threads(T, [&](int t) {
-        hvec<int32_t> rp, ad, ae;
-        for (int32_t b = t; b < count; b += T) {
-            const int64_t n = probs[b].n, m = probs[b].m, eo = h->edge_off[(size_t)b];
-            std::memcpy(h->ii.data() + eo, probs[b].ind_i, sizeof(int32_t) * (size_t)m);
-            std::memcpy(h->jj.data() + eo, probs[b].ind_j, sizeof(int32_t) * (size_t)m);
-            build_csr(n, m, probs[b].ind_i, probs[b].ind_j, rp, ad, ae);
-            std::memcpy(h->rowptr.data() + h->node_off[(size_t)b] + b, rp.data(), sizeof(int32_t) * (size_t)(n + 1));
-            std::memcpy(h->adj.data() + 2 * eo, ad.data(), sizeof(int32_t) * 2 * (size_t)m);
-            std::memcpy(h->adj_eid.data() + 2 * eo, ae.data(), sizeof(int32_t) * 2 * (size_t)m);
-        }
-    });
-    return DESC_OK;
+                        b, (long long)q.n, GCW_BATCH_MAX_N);
+        return DESC_OK;
+    }, h);
 }
 
 int gb_create(const desc_problem* probs, int32_t count, int32_t device, desc_gcw_batch* h) {

@@ -19,17 +19,13 @@
 #include <vector>
 
 #include "device_utils.h"
+#include "mst_key.h"
 
 namespace desc {
 namespace {
 
 constexpr int32_t NO_EDGE = 0x7F7F7F7F;           // "no edge": the byte fill of bidx (hipMemset 0x7F); above every edge index (m < 2^31)
 
-// unsigned integer with the order of the double (positive: sign bit set; negative: all bits flipped)
-__device__ __forceinline__ unsigned long long order_key(double x) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(x);
-    return (u >> 63) ? ~u : (u | (1ull << 63));
-}
 __global__ __launch_bounds__(256) void k_mst_keys(const double* s, unsigned long long* key, int64_t m) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256) key[e] = order_key(s[e] + 1.0);   // MPLS.m:162
 }
@@ -142,6 +138,35 @@ int boruvka_rounds(const desc_device_problem* dp, const unsigned long long* d_ke
 
 }  // namespace
 
+int mst_propagate(int64_t n, const int32_t* ii, const int32_t* jj, const int32_t* ids, int cnt, const double* blk, double* R_out) {
+    // rooting at node 1 and propagation (MPLS.m:171-193): adjacency of the tree, breadth first
+    hvec<int32_t> deg((size_t)n + 1, 0), nb((size_t)2 * cnt), nbt((size_t)2 * cnt);
+    for (int t = 0; t < cnt; ++t) { ++deg[ii[ids[t]] + 1]; ++deg[jj[ids[t]] + 1]; }
+    for (int64_t v = 0; v < n; ++v) deg[v + 1] += deg[v];
+    hvec<int32_t> fill(deg.begin(), deg.end() - 1);
+    for (int t = 0; t < cnt; ++t) {
+        const int a = ii[ids[t]], b = jj[ids[t]];
+        nb[fill[a]] = b; nbt[fill[a]++] = t;
+        nb[fill[b]] = a; nbt[fill[b]++] = t;
+    }
+    hvec<uint8_t> added((size_t)n, 0);
+    hvec<int32_t> queue; queue.reserve((size_t)n);
+    for (int q = 0; q < 9; ++q) R_out[q] = (q % 4 == 0) ? 1.0 : 0.0;                 // :174
+    added[0] = 1; queue.push_back(0);
+    for (size_t h = 0; h < queue.size(); ++h) {
+        const int root = queue[h];
+        for (int s = deg[root]; s < deg[root + 1]; ++s) {
+            const int leaf = nb[s];
+            if (added[leaf]) continue;
+            const int t = nbt[s];
+            mul3(&blk[9 * (size_t)t], leaf != ii[ids[t]], R_out + 9 * (int64_t)root, R_out + 9 * (int64_t)leaf);     // :184-188
+            added[leaf] = 1; queue.push_back(leaf);
+        }
+    }
+    if ((int64_t)queue.size() != n) return fail(DESC_ERR_STATE, "minimum spanning tree does not span the graph");
+    return DESC_OK;
+}
+
 int mst_device(const desc_device_problem* dp, const double* d_s, double* R_out, int32_t* tree_edges) {
     int rc = DESC_OK;
     const int64_t n = dp->n, m = dp->m;
@@ -175,32 +200,7 @@ int mst_device(const desc_device_problem* dp, const double* d_s, double* R_out, 
         DESC_HIP(hipMemcpy(ids.data(), d_ids, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost));
         DESC_HIP(hipMemcpy(blk.data(), d_blocks, sizeof(double) * 9 * cnt, hipMemcpyDeviceToHost));
     }
-    // rooting at node 1 and propagation (MPLS.m:171-193): adjacency of the tree, breadth first
-    const int32_t *ii = dp->ii.data(), *jj = dp->jj.data();
-    hvec<int32_t> deg((size_t)n + 1, 0), nb((size_t)2 * cnt), nbt((size_t)2 * cnt);
-    for (int t = 0; t < cnt; ++t) { ++deg[ii[ids[t]] + 1]; ++deg[jj[ids[t]] + 1]; }
-    for (int64_t v = 0; v < n; ++v) deg[v + 1] += deg[v];
-    hvec<int32_t> fill(deg.begin(), deg.end() - 1);
-    for (int t = 0; t < cnt; ++t) {
-        const int a = ii[ids[t]], b = jj[ids[t]];
-        nb[fill[a]] = b; nbt[fill[a]++] = t;
-        nb[fill[b]] = a; nbt[fill[b]++] = t;
-    }
-    hvec<uint8_t> added((size_t)n, 0);
-    hvec<int32_t> queue; queue.reserve((size_t)n);
-    for (int q = 0; q < 9; ++q) R_out[q] = (q % 4 == 0) ? 1.0 : 0.0;                 // :174
-    added[0] = 1; queue.push_back(0);
-    for (size_t h = 0; h < queue.size(); ++h) {
-        const int root = queue[h];
-        for (int s = deg[root]; s < deg[root + 1]; ++s) {
-            const int leaf = nb[s];
-            if (added[leaf]) continue;
-            const int t = nbt[s];
-            mul3(&blk[9 * (size_t)t], leaf != ii[ids[t]], R_out + 9 * (int64_t)root, R_out + 9 * (int64_t)leaf);     // :184-188
-            added[leaf] = 1; queue.push_back(leaf);
-        }
-    }
-    if ((int64_t)queue.size() != n) return fail(DESC_ERR_STATE, "minimum spanning tree does not span the graph");
+    if ((rc = mst_propagate(n, dp->ii.data(), dp->jj.data(), ids.data(), cnt, blk.data(), R_out))) return rc;
     if (tree_edges) {
         std::sort(ids.begin(), ids.end());
         std::copy(ids.begin(), ids.end(), tree_edges);

@@ -1,0 +1,241 @@
+// The tree step of MPLS (Algorithms/MPLS.m:160-193) for many small problems in one launch (desc_mst_batch_*): the "CEMP+MST" row of
+// Demo/compare_algorithms.m for a whole Monte-Carlo batch.
+//
+// mst.hip runs Boruvka on one problem with one host read-back per round.  Here ONE launch grows all B trees: one workgroup of 256
+// threads per problem runs Prim from node 1 with, per node outside the tree, the lightest edge that joins it to the tree -- the pair
+// (order_key(fl(S_e + 1)), edge id), mst.hip's edge order -- in LDS.  A step takes the workgroup's arg-min of those pairs under the
+// lexicographic order (lanes by shuffles, the four waves through LDS), adds that node and relaxes its CSR row (every neighbour occurs
+// once in a row: no two threads write the same node).  The order is total, so the minimum spanning tree is unique: Prim's tree is the
+// Boruvka tree of mst_device, edge for edge.  The n - 1 edge ids go back to the host, where rooting and propagation run per problem on
+// up to 16 threads with mst_device's own tail (mst_propagate).  A node's rotation is the product along its unique tree path, so it does
+// not depend on the order the edges were found in: the result is mst_device's bit for bit.
+//
+// Control flow.  n - 1 steps, each bounded by n and a row length; the arg-min is computed by every thread from the same four LDS pairs,
+// so the branches around the barriers are uniform (steering integers go through readfirstlane).  No grid-wide barrier, no spinning on
+// memory, nothing between workgroups, no atomics.  A step that finds no candidate (a disconnected graph: refused on the host before
+// the launch) writes the problem's status word and the workgroup leaves.  The LDS of a launch is sized from the largest problem of the
+// batch; a problem addresses it with its own n.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <numeric>
+#include <vector>
+
+#include "batch_csr.h"
+#include "device_utils.h"
+#include "mst_key.h"
+
+namespace desc {
+namespace {
+
+constexpr int MST_BATCH_MAX_N = 4096;                  // 16 bytes of LDS per node: 64 KiB, what every launch may declare
+static_assert(MST_BATCH_MAX_N >= 1024 && 16 * MST_BATCH_MAX_N <= 64 * 1024, "LDS budget");
+constexpr int32_t MB_NONE = 0x7FFFFFFF;                // "no edge": above every edge id
+
+struct MbProb { int32_t n, m, node_off, edge_off; };
+
+__device__ __forceinline__ bool mb_less(unsigned long long ka, int ea, unsigned long long kb, int eb) { return ka < kb || (ka == kb && ea < eb); }
+
+__global__ __launch_bounds__(256) void k_mst_batch(const MbProb* prob, const int32_t* rowptr_all, const int32_t* adj_all, const int32_t* eid_all,
+                                                   const double* s_all, int32_t* tree_all, int32_t* status) {
+    extern __shared__ unsigned long long mb_lds[];     // key[n] (8 B), then best edge[n] and in-tree flag[n] (4 B each)
+    __shared__ unsigned long long r_key[4];
+    __shared__ int32_t r_edge[4], r_node[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const MbProb pd = prob[b];
+    const int n = __builtin_amdgcn_readfirstlane(pd.n);
+    const int32_t* rowptr = rowptr_all + pd.node_off + b;
+    const int32_t* adj = adj_all + 2 * (int64_t)pd.edge_off;
+    const int32_t* eid = eid_all + 2 * (int64_t)pd.edge_off;
+    const double* s = s_all + pd.edge_off;
+    int32_t* tree = tree_all + pd.node_off - b;        // n_b - 1 ids per problem
+    unsigned long long* key = mb_lds;
+    int32_t* best = (int32_t*)(mb_lds + n);
+    int32_t* in_tree = best + n;
+    for (int v = tid; v < n; v += 256) { key[v] = ~0ull; best[v] = MB_NONE; in_tree[v] = v == 0; }      // :171 the root is node 1
+    __syncthreads();
+    int u = 0;                                         // the node added last
+    for (int step = 0; step < n - 1; ++step) {
+        // ---- relax the row of u: every neighbour outside the tree keeps the lighter of its edge and {u, v}
+        const int t1 = rowptr[u + 1];
+        for (int t = rowptr[u] + tid; t < t1; t += 256) {
+            const int v = adj[t];
+            if (in_tree[v]) continue;
+            const int e = eid[t];
+            const unsigned long long k = order_key(s[e] + 1.0);          // MPLS.m:162
+            if (mb_less(k, e, key[v], best[v])) { key[v] = k; best[v] = e; }
+        }
+        __syncthreads();
+        // ---- the lightest edge that leaves the tree
+        unsigned long long bk = ~0ull; int be = MB_NONE, bv = -1;
+        for (int v = tid; v < n; v += 256)
+            if (!in_tree[v] && best[v] != MB_NONE && mb_less(key[v], best[v], bk, be)) { bk = key[v]; be = best[v]; bv = v; }
+        for (int off = 32; off >= 1; off >>= 1) {
+            const unsigned long long ok = __shfl_xor(bk, off);
+            const int oe = __shfl_xor(be, off), ov = __shfl_xor(bv, off);
+            if (mb_less(ok, oe, bk, be)) { bk = ok; be = oe; bv = ov; }
+        }
+        if (lane == 0) { r_key[wv] = bk; r_edge[wv] = be; r_node[wv] = bv; }
+        __syncthreads();
+        bk = r_key[0]; be = r_edge[0]; bv = r_node[0];
+        for (int w = 1; w < 4; ++w) if (mb_less(r_key[w], r_edge[w], bk, be)) { bk = r_key[w]; be = r_edge[w]; bv = r_node[w]; }
+        be = __builtin_amdgcn_readfirstlane(be); bv = __builtin_amdgcn_readfirstlane(bv);
+        if (be == MB_NONE) {                           // no edge leaves the tree: the same in every thread
+            if (tid == 0) status[b] = step + 1;
+            return;
+        }
+        if (tid == 0) { tree[step] = be; in_tree[bv] = 1; }
+        u = bv;
+        __syncthreads();                               // in_tree[u] is visible, r_* are free again
+    }
+    if (tid == 0) status[b] = 0;
+}
+
+// connected, with every node id touched by an edge: union-find over the problem's edge list; *comps = the number of components
+void mb_components(int64_t n, int64_t m, const int32_t* ii, const int32_t* jj, int64_t* comps) {
+    hvec<int32_t> par((size_t)n);
+    std::iota(par.begin(), par.end(), 0);
+    auto find = [&](int32_t x) { while (par[x] != x) { par[x] = par[par[x]]; x = par[x]; } return x; };
+    int64_t c = n;
+    for (int64_t e = 0; e < m; ++e) {
+        const int32_t a = find(ii[e]), b = find(jj[e]);
+        if (a != b) { par[std::max(a, b)] = std::min(a, b); --c; }
+    }
+    *comps = c;
+}
+
+// validation, the size cap, connectivity, the per-problem CSR: no device
+int mb_host_part(const desc_problem* probs, int32_t count, const double* s_vec, BatchCsr* h) {
+    int rc = batch_csr_host(probs, count, [](int32_t b, const desc_problem& q) -> int {
+        if (q.n > MST_BATCH_MAX_N)
+            return fail(DESC_ERR_INVALID, "problem %d: n = %lld exceeds %d (the per-node keys of the tree kernel must fit the LDS of one workgroup): solve it with MST / MPLS",
+                        b, (long long)q.n, MST_BATCH_MAX_N);
+        int64_t comps = 0;
+        mb_components(q.n, q.m, q.ind_i, q.ind_j, &comps);
+        if (comps != 1)                               // MPLS.m:178 would loop for ever
+            return fail(DESC_ERR_INVALID, "problem %d: the graph is disconnected: %lld components (a node id in 1..max(Ind) that no edge touches is one)",
+                        b, (long long)comps);
+        return DESC_OK;
+    }, h);
+    if (rc) return rc;
+    if (s_vec)
+        for (int32_t b = 0; b < count; ++b)
+            for (int64_t e = h->edge_off[(size_t)b]; e < h->edge_off[(size_t)b + 1]; ++e)
+                if (!std::isfinite(s_vec[e]))
+                    return fail(DESC_ERR_INVALID, "problem %d: S_vec entry %lld is not finite", b, (long long)(e - h->edge_off[(size_t)b]));
+    return DESC_OK;
+}
+
+template <class T>
+int mb_upload(DevArena& mem, hipStream_t st, T** dst, const T* src, size_t n) {
+    int rc = mem.alloc(dst, n); if (rc) return rc;
+    if (n) DESC_HIP(hipMemcpyAsync(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice, st));
+    return DESC_OK;
+}
+
+struct StreamGuard {
+    hipStream_t s = nullptr;
+    ~StreamGuard() { if (s) { (void)hipStreamSynchronize(s); stream_release(s); } }
+};
+
+int mb_run(const desc_problem* probs, int32_t count, const double* s_vec, int32_t device, double* R_out, int32_t* tree_edges, desc_mst_batch_timings* tm) {
+    auto t0 = std::chrono::steady_clock::now();
+    if (tm) { tm->ms_structure = 0; tm->ms_upload = 0; tm->ms_tree = 0; tm->ms_propagate = 0; tm->ms_total = 0; }
+    if (count == 0) return DESC_OK;
+    if (!s_vec || !R_out) return fail(DESC_ERR_INVALID, "s_vec or R_out is NULL");
+    BatchCsr h;
+    int rc = mb_host_part(probs, count, s_vec, &h);
+    if (rc) return rc;
+    const double ms_structure = ms_since(t0);
+
+    // ---- device: nothing above touched it
+    int ndev = desc_device_count();
+    if (ndev < 0) return ndev;
+    if (ndev == 0) return fail(DESC_ERR_HIP, "no HIP device visible: the batched tree step has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(DESC_ERR_INVALID, "device %d out of range (0..%d)", device, ndev - 1);
+    StreamGuard sg;
+    DevArena mem;                                      // released before the stream (declared after it)
+    hipError_t he = hipSetDevice(device);
+    if (he == hipSuccess) he = stream_acquire(&sg.s);
+    if (he != hipSuccess) return fail(DESC_ERR_HIP, "device %d: %s", device, hipGetErrorString(he));
+    auto t1 = std::chrono::steady_clock::now();
+    const size_t M = (size_t)h.M, N = (size_t)h.N;
+    hvec<MbProb> pr((size_t)count);
+    for (int32_t b = 0; b < count; ++b) pr[(size_t)b] = MbProb{(int32_t)probs[b].n, (int32_t)probs[b].m, (int32_t)h.node_off[(size_t)b], (int32_t)h.edge_off[(size_t)b]};
+    MbProb* d_prob; int32_t *d_rowptr, *d_adj, *d_eid, *d_tree, *d_status; double* d_s;
+    if ((rc = mb_upload(mem, sg.s, &d_prob, (const MbProb*)pr.data(), pr.size())) || (rc = mb_upload(mem, sg.s, &d_rowptr, (const int32_t*)h.rowptr.data(), h.rowptr.size())) ||
+        (rc = mb_upload(mem, sg.s, &d_adj, (const int32_t*)h.adj.data(), 2 * M)) || (rc = mb_upload(mem, sg.s, &d_eid, (const int32_t*)h.adj_eid.data(), 2 * M)) ||
+        (rc = mb_upload(mem, sg.s, &d_s, s_vec, M)) || (rc = mem.alloc(&d_tree, N)) || (rc = mem.alloc(&d_status, (size_t)count))) return rc;
+    DESC_HIP(hipMemsetAsync(d_status, 0xFF, sizeof(int32_t) * (size_t)count, sg.s));       // -1: the workgroup never finished
+    DESC_HIP(hipStreamSynchronize(sg.s));
+    const double ms_upload = ms_since(t1);
+
+    auto t2 = std::chrono::steady_clock::now();
+    const size_t lds = (size_t)16 * (size_t)h.max_n;
+    if (lds > 64 * 1024) return fail(DESC_ERR_STATE, "LDS budget exceeded (%zu bytes)", lds);
+    hipLaunchKernelGGL(k_mst_batch, dim3((unsigned)count), dim3(256), lds, sg.s, d_prob, d_rowptr, d_adj, d_eid, d_s, d_tree, d_status);
+    DESC_HIP(hipGetLastError());
+    hvec<int32_t> tree(std::max<size_t>(N, 1)), status((size_t)count);
+    DESC_HIP(hipMemcpyAsync(status.data(), d_status, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, sg.s));
+    if (N > (size_t)count) DESC_HIP(hipMemcpyAsync(tree.data(), d_tree, sizeof(int32_t) * (N - (size_t)count), hipMemcpyDeviceToHost, sg.s));
+    DESC_HIP(hipStreamSynchronize(sg.s));
+    const double ms_tree = ms_since(t2);
+    for (int32_t b = 0; b < count; ++b)
+        if (status[(size_t)b] != 0)
+            return fail(DESC_ERR_STATE, "problem %d: the tree kernel found no edge leaving the tree (status %d)", b, (int)status[(size_t)b]);
+
+    // ---- rooting and propagation (MPLS.m:171-193) per problem on host threads: the tail of mst_device
+    auto t3 = std::chrono::steady_clock::now();
+    hvec<int32_t> prc((size_t)count, DESC_OK);
+    const int T = std::max(1, std::min(count, 16));
+    run_threads(T, [&](int t) {
+        hvec<double> blk;
+        for (int32_t b = t; b < count; b += T) {
+            const int64_t no = h.node_off[(size_t)b], n = probs[b].n;
+            int32_t* ids = tree.data() + no - b;
+            const int cnt = (int)(n - 1);
+            bool ok = true;
+            for (int q = 0; q < cnt; ++q) ok = ok && ids[q] >= 0 && ids[q] < probs[b].m;
+            if (!ok) { prc[(size_t)b] = DESC_ERR_STATE; continue; }
+            blk.resize((size_t)9 * (size_t)std::max(cnt, 1));
+            for (int q = 0; q < cnt; ++q) std::memcpy(&blk[9 * (size_t)q], probs[b].rij + 9 * (size_t)ids[q], 72);
+            prc[(size_t)b] = mst_propagate(n, probs[b].ind_i, probs[b].ind_j, ids, cnt, blk.data(), R_out + 9 * (size_t)no);
+            if (tree_edges && prc[(size_t)b] == DESC_OK) {
+                std::sort(ids, ids + cnt);
+                std::copy(ids, ids + cnt, tree_edges + no - b);
+            }
+        }
+    });
+    for (int32_t b = 0; b < count; ++b)
+        if (prc[(size_t)b]) return fail(DESC_ERR_STATE, "problem %d: the tree kernel's edges do not span the graph", b);
+    if (tm) { tm->ms_structure = ms_structure; tm->ms_upload = ms_upload; tm->ms_tree = ms_tree; tm->ms_propagate = ms_since(t3); tm->ms_total = ms_since(t0); }
+    return DESC_OK;
+}
+
+}  // namespace
+}  // namespace desc
+
+using namespace desc;
+
+extern "C" {
+
+int32_t desc_mst_batch_max_n(void) { return MST_BATCH_MAX_N; }
+
+int desc_mst_batch_check(const desc_problem* probs, int32_t count) {
+    return no_throw("desc_mst_batch_check", [&]() -> int {
+        if (count < 0 || (count > 0 && !probs)) return fail(DESC_ERR_INVALID, "NULL argument or negative count");
+        BatchCsr h;
+        return mb_host_part(probs, count, nullptr, &h);
+    });
+}
+
+int desc_mst_batch_run(const desc_problem* probs, int32_t count, const double* s_vec, int32_t device, double* R_out, int32_t* tree_edges,
+                       desc_mst_batch_timings* timings) {
+    return no_throw("desc_mst_batch_run", [&]() -> int {
+        if (count < 0 || (count > 0 && !probs)) return fail(DESC_ERR_INVALID, "NULL argument or negative count");
+        return mb_run(probs, count, s_vec, device, R_out, tree_edges, timings);
+    });
+}
+
+}  // extern "C"

@@ -2,10 +2,12 @@
 """A small Monte-Carlo study in ONE batched call: mean |S_vec - ErrVec| against the corruption level q, averaged over a few trials
 of Uniform_Topology(100, 0.5, q, 0.1) -- the shape of the figures the DESC paper draws (error against q on graphs of 100-200 nodes).
 
-    python examples/monte_carlo.py [--trials 5] [--n 100] [--iters 100] [--rotations]
+    python examples/monte_carlo.py [--trials 5] [--n 100] [--iters 100] [--rotations] [--baselines]
 
 --rotations: the demo's own metric next to it -- one DESC_init_batch call (the PGD pass, then the batched GCW eigen-solve) and the mean
 rotation error in degrees (Rotation_Alignment against the ground truth), the column of Demo/compare_algorithms.m.
+--baselines: the curves DESC is drawn against, one batched call per curve -- CEMP's SVec error (CEMP_batch) and the rotation errors of
+CEMP+GCW (CEMP_GCW_batch) and CEMP+MST (CEMP_MST_batch), with the demo's CEMP parameters (compare_algorithms.m:26-29).
 """
 import argparse
 import os
@@ -16,7 +18,29 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from desc_amd import ConstantStepSize, DESC_PGD_batch, DESC_init_batch, Rotation_Alignment, Uniform_Topology  # noqa: E402
+from desc_amd import (CEMP_GCW_batch, CEMP_MST_batch, CEMP_batch, ConstantStepSize, DESC_PGD_batch, DESC_init_batch,  # noqa: E402
+                      Rotation_Alignment, Uniform_Topology)
+
+
+def baselines(models, qs, trials):
+    """One call per curve: CEMP_batch, CEMP_GCW_batch, CEMP_MST_batch."""
+    cemp = dict(max_iter=6, reweighting=[2.0 ** k for k in range(6)], nsample=50, seed=0)
+    t0 = time.perf_counter()
+    S = CEMP_batch(models, cemp)
+    t1 = time.perf_counter()
+    R_gcw = CEMP_GCW_batch(models, cemp)
+    t2 = time.perf_counter()
+    R_mst = CEMP_MST_batch(models, cemp)
+    t3 = time.perf_counter()
+    print(f"baselines, one call per curve: CEMP_batch {(t1 - t0) * 1e3:.1f} ms, CEMP_GCW_batch {(t2 - t1) * 1e3:.1f} ms, "
+          f"CEMP_MST_batch {(t3 - t2) * 1e3:.1f} ms")
+    shape = (len(qs), trials)
+    err = np.array([np.abs(s - mo.ErrVec).mean() for s, mo in zip(S, models)]).reshape(shape)
+    gcw = np.array([Rotation_Alignment(R, mo.R_orig)[2] for R, mo in zip(R_gcw, models)]).reshape(shape)
+    mst = np.array([Rotation_Alignment(R, mo.R_orig)[2] for R, mo in zip(R_mst, models)]).reshape(shape)
+    print("    q   CEMP mean |SVec - ErrVec|   CEMP+GCW rotation error, degrees   CEMP+MST rotation error, degrees   (means over the trials)")
+    for q, a, b, c in zip(qs, err, gcw, mst):
+        print(f" {q:4.2f}   {a.mean():.4f}                     {b.mean():8.4f}                           {c.mean():8.4f}")
 
 
 def main():
@@ -25,6 +49,7 @@ def main():
     ap.add_argument("--n", type=int, default=100)
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--rotations", action="store_true", help="one DESC_init_batch call: the mean rotation error next to the S_vec error")
+    ap.add_argument("--baselines", action="store_true", help="CEMP, CEMP+GCW and CEMP+MST next to DESC: one batched call per curve")
     a = ap.parse_args()
     qs = [0.0, 0.1, 0.2, 0.3, 0.4, 0.5]
     models = [Uniform_Topology(a.n, 0.5, q, 0.1, "uniform", seed=1000 * k + t) for k, q in enumerate(qs) for t in range(a.trials)]
@@ -44,10 +69,14 @@ def main():
         for q, row, rr in zip(qs, err, rot):
             print(f" {q:4.2f}   {row.mean():.4f}                ({row.min():.4f} .. {row.max():.4f})      {rr.mean():8.4f}"
                   f"                      ({rr.min():.4f} .. {rr.max():.4f})")
+        if a.baselines:
+            baselines(models, qs, a.trials)
         return
     print("    q   mean |S_vec - ErrVec|   (min .. max over the trials)")
     for q, row in zip(qs, err):
         print(f" {q:4.2f}   {row.mean():.4f}                ({row.min():.4f} .. {row.max():.4f})")
+    if a.baselines:
+        baselines(models, qs, a.trials)
 
 
 if __name__ == "__main__":

@@ -612,6 +612,66 @@ int desc_gcw_batch_run(desc_gcw_batch* h, const double* s_vec, const double* wei
                        double* R_out, desc_spectral_info* infos, desc_gcw_batch_timings* timings /* nullable */);
 void desc_gcw_batch_destroy(desc_gcw_batch* h);
 
+/* CEMP (Algorithms/CEMP.m:24-132) for B independent small problems in one GPU pass: the baseline next to desc_pgd_batch_*.  The edge
+ * lists lie behind one another; ONE launch in create samples the 3-cycles and evaluates S0 and the initial means for the whole batch
+ * (CEMP.m:44-103: one wave per edge intersects the two CSR rows in ascending k, draws sample t as
+ * CoInd[desc_sample_key(seed_b, local edge id, t) mod codeg] -- desc_cemp_run's rule -- and keeps nsample slots per edge of the batch, with
+ * or without cycles: no compaction, no host round trip), and every round (:107-128) is one launch for the whole batch.
+ * Problem b's S_vec is bit for bit what desc_cemp_run gives for it with its seed (the same samples, the same arithmetic text:
+ * csrc/cemp_math.h), and no bit of it depends on the batch around it (position, neighbours, batch size, launch geometry, the LDS size of
+ * the launch).
+ * desc_cemp_batch_max_degree: the longest CSR row the sampler stages (4096).
+ * desc_cemp_batch_create: validates every problem and refuses -- before any device work, naming the problem -- an empty edge list and a
+ * node of more neighbours than desc_cemp_batch_max_degree() (DESC_ERR_INVALID: solve it with CEMP); m_total * nsample >= 2^31 is
+ * DESC_ERR_TOO_LARGE.  seeds: one sampling seed per problem, or NULL (`seed` for every problem).  count == 0 is legal.  Without a device:
+ * DESC_ERR_HIP and *out = NULL.
+ * desc_cemp_batch_sizes: node_off[count+1], edge_off[count+1] (each nullable).
+ * desc_cemp_batch_get_samples: what create sampled, for parity tests; each array nullable.  e_jk / e_ki / s0: edge_off[count] * nsample
+ * entries, slot t of edge e of problem b at (edge_off[b] + e) * nsample + t; edge ids LOCAL to the problem, -1 (and s0 = 0) in the slots of
+ * an edge without a 3-cycle; has_cycle: one byte per edge.
+ * desc_cemp_batch_run: :107-128 with beta[min(it, n_beta - 1)] in round it, max_iter >= 0 rounds (0: the initial means of :102-103);
+ * s_vec: edge_off[count] doubles in the library's edge order.  The handle may be run any number of times: every run starts from the
+ * initial means. */
+typedef struct desc_cemp_batch desc_cemp_batch;   /* opaque */
+typedef struct desc_cemp_batch_timings {
+    double ms_structure;      /* validation + per-problem CSR + degree maxima (wall clock of create's host part) */
+    double ms_upload;         /* host -> HBM (create)                                                              */
+    double ms_build;          /* sampling + S0 + initial means: the one launch of create, wall clock               */
+    double ms_rounds;         /* the rounds and the download (desc_cemp_batch_run), wall clock                     */
+    double ms_total;          /* wall clock of desc_cemp_batch_run                                                 */
+} desc_cemp_batch_timings;    /* 40 bytes */
+int32_t desc_cemp_batch_max_degree(void);
+int desc_cemp_batch_create(const desc_problem* probs, int32_t count, int32_t nsample, uint64_t seed, const uint64_t* seeds /* nullable */,
+                           int32_t device, desc_cemp_batch** out);
+int desc_cemp_batch_sizes(const desc_cemp_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off);
+int desc_cemp_batch_get_samples(desc_cemp_batch* h, int32_t* e_jk, int32_t* e_ki, double* s0, uint8_t* has_cycle);
+int desc_cemp_batch_run(desc_cemp_batch* h, const double* beta, int32_t n_beta, int32_t max_iter, double* s_vec,
+                        desc_cemp_batch_timings* timings /* nullable */);
+void desc_cemp_batch_destroy(desc_cemp_batch* h);
+
+/* The tree step of MPLS (Algorithms/MPLS.m:160-193) for B independent small problems in ONE launch: one workgroup per problem runs Prim
+ * from node 1 under desc_mst_run's edge order (fl(S + 1), then the index in the (i, j)-sorted list: total, so the tree is unique and is
+ * desc_mst_run's); rooting and propagation (:171-193) run per problem on host threads with desc_mst_run's own code.  Problem b's R and
+ * tree edges are bit for bit what desc_mst_run gives for it.
+ * desc_mst_batch_max_n: the largest problem (nodes) the tree kernel takes (4096).
+ * desc_mst_batch_check: the host part alone (no device): DESC_ERR_INVALID naming the problem for an empty edge list, n >
+ * desc_mst_batch_max_n() (solve it with MST / MPLS) and a disconnected graph (union-find; a node id that no edge touches is a component).
+ * desc_mst_batch_run: the same checks and a non-finite s_vec entry are refused before any device work.  s_vec: the concatenated S_vec in
+ * the library's edge order; R_out: problem b's 3x3xn_b column-major blocks at 9 * node_off[b] (node_off = the running sum of n);
+ * tree_edges (nullable): problem b's n_b - 1 edge ids, local and ascending, at node_off[b] - b.  A step of Prim that finds no edge
+ * leaving the tree is DESC_ERR_STATE naming the problem. */
+typedef struct desc_mst_batch_timings {
+    double ms_structure;      /* validation + connectivity + per-problem CSR (host)      */
+    double ms_upload;         /* host -> HBM                                              */
+    double ms_tree;           /* the tree launch and the download of its edges            */
+    double ms_propagate;      /* rooting and propagation on host threads                  */
+    double ms_total;          /* wall clock of desc_mst_batch_run                         */
+} desc_mst_batch_timings;     /* 40 bytes */
+int32_t desc_mst_batch_max_n(void);
+int desc_mst_batch_check(const desc_problem* probs, int32_t count);
+int desc_mst_batch_run(const desc_problem* probs, int32_t count, const double* s_vec, int32_t device, double* R_out,
+                       int32_t* tree_edges /* nullable */, desc_mst_batch_timings* timings /* nullable */);
+
 /* One-shot: what the MEX shim calls.  Builds the structure (p->build_where),
  * uploads, runs, downloads, frees. */
 int desc_pgd_solve(const desc_problem* prob, const desc_params* p, desc_result* r);
