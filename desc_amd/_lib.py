@@ -39,6 +39,8 @@ EXPORTS = [
     "desc_gcw_batch_max_n", "desc_gcw_batch_create", "desc_gcw_batch_sizes", "desc_gcw_batch_csr", "desc_gcw_batch_run", "desc_gcw_batch_destroy",
     "desc_cemp_batch_max_degree", "desc_cemp_batch_create", "desc_cemp_batch_sizes", "desc_cemp_batch_get_samples", "desc_cemp_batch_run",
     "desc_cemp_batch_destroy", "desc_mst_batch_max_n", "desc_mst_batch_check", "desc_mst_batch_run",
+    "desc_test_laa_r2q", "desc_test_laa_q2r", "desc_test_laa_edge_log", "desc_test_laa_rhs", "desc_test_laa_pcg", "desc_test_laa_node_update",
+    "desc_test_irls_node_update", "desc_test_laa_weights", "desc_test_irls_weights", "desc_test_laa_quantile", "desc_test_irls_project",
 ]
 
 I32P = C.POINTER(C.c_int32)
@@ -308,6 +310,17 @@ def load():
     L.desc_mst_batch_max_n.argtypes = []
     L.desc_mst_batch_check.argtypes = [C.POINTER(Problem), C.c_int32]
     L.desc_mst_batch_run.argtypes = [C.POINTER(Problem), C.c_int32, F64P, C.c_int32, F64P, I32P, C.POINTER(MstBatchTimings)]
+    L.desc_test_laa_r2q.argtypes = [F64P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, F64P]
+    L.desc_test_laa_q2r.argtypes = [F64P, C.c_int64, C.c_int32, F64P]
+    L.desc_test_laa_edge_log.argtypes = [C.c_void_p, F64P, F64P, C.c_int64, F64P]
+    L.desc_test_laa_rhs.argtypes = [C.c_void_p, F64P, F64P, C.c_int64, F64P, F64P]
+    L.desc_test_laa_pcg.argtypes = [C.c_void_p, C.c_int32, F64P, F64P, F64P, C.c_int64, I32P, F64P, I32P, F64P, F64P, I32P, I32P, F64P]
+    L.desc_test_laa_node_update.argtypes = [F64P, F64P, C.c_int64, C.c_int32, F64P, F64P, F64P]
+    L.desc_test_irls_node_update.argtypes = [F64P, F64P, C.c_int64, C.c_int32, F64P, F64P]
+    L.desc_test_laa_weights.argtypes = [F64P, C.c_int64, C.c_double, C.c_int32, F64P]
+    L.desc_test_irls_weights.argtypes = [C.c_void_p, F64P, F64P, C.c_int64, C.c_int32, C.c_double, F64P]
+    L.desc_test_laa_quantile.argtypes = [F64P, C.c_int64, C.c_double, C.c_int64, C.c_int32, F64P]
+    L.desc_test_irls_project.argtypes = [F64P, I32P, C.c_int64, C.c_int64, C.c_int32, F64P, I32P, I32P, F64P]
     _lib = L
     return L
 
@@ -1246,3 +1259,105 @@ def device_count():
     if rc < 0:
         raise DescError(load().desc_last_error().decode())
     return rc
+
+
+# ---- test hooks into the Lie-algebraic averaging core (desc_test_laa_* / desc_test_irls_*, include/desc_amd.h): one operation on
+# NumPy arrays, launched as the library launches it.  Used by tests/test_gpu_laa_maps.py only.
+def _f64(a, size=None):
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+    if size is not None and a.size != size:
+        raise ValueError(f"expected {size} doubles, got {a.size}")
+    return a
+
+
+def hook_r2q(R, transpose=False, edge_grid=False, device=0):
+    """R: (count, 9) column-major blocks -> (count, 4) quaternions."""
+    R = _f64(R); count = R.size // 9
+    Q = out_buffer(4 * count)
+    check(load().desc_test_laa_r2q(ptr(R, F64P), count, int(bool(transpose)), int(bool(edge_grid)), device, ptr(Q, F64P)))
+    return Q[:4 * count].reshape(count, 4)
+
+
+def hook_q2r(Q, device=0):
+    """Q: (n, 4) -> (n, 9) column-major blocks."""
+    Q = _f64(Q); n = Q.size // 4
+    R = out_buffer(9 * n)
+    check(load().desc_test_laa_q2r(ptr(Q, F64P), n, device, ptr(R, F64P)))
+    return R[:9 * n].reshape(n, 9)
+
+
+def hook_edge_log(dprob: DeviceProblem, Q, QQ):
+    m = dprob.m
+    Q, QQ = _f64(Q, 4 * dprob.n), _f64(QQ, 4 * m)
+    B = out_buffer(3 * m)
+    check(load().desc_test_laa_edge_log(dprob.handle, ptr(Q, F64P), ptr(QQ, F64P), m, ptr(B, F64P)))
+    return B[:3 * m].reshape(m, 3)
+
+
+def hook_rhs(dprob: DeviceProblem, w, B):
+    n, m = dprob.n, dprob.m
+    w, B = _f64(w, m), _f64(B, 3 * m)
+    rhs, diag = out_buffer(3 * n), out_buffer(n)
+    check(load().desc_test_laa_rhs(dprob.handle, ptr(w, F64P), ptr(B, F64P), m, ptr(rhs, F64P), ptr(diag, F64P)))
+    return rhs[:3 * n].reshape(n, 3), diag[:n]
+
+
+def hook_pcg(dprob: DeviceProblem, w, rhs, diag, act=(1, 1, 1), w3=False):
+    """-> dict(x (n, 3), bad (3,), rnorm (3,), bnorm (3,), total, unconverged, worst); rnorm / bnorm are squared norms."""
+    n, m = dprob.n, dprob.m
+    w, rhs, diag = _f64(w, 3 * m if w3 else m), _f64(rhs, 3 * n), _f64(diag, 3 * n if w3 else n)
+    act = np.ascontiguousarray(act, dtype=np.int32)
+    x, bad, rn, bn = out_buffer(3 * n), out_buffer(3, np.int32), out_buffer(3), out_buffer(3)
+    tot, unc, worst = out_buffer(1, np.int32), out_buffer(1, np.int32), out_buffer(1)
+    check(load().desc_test_laa_pcg(dprob.handle, int(bool(w3)), ptr(w, F64P), ptr(rhs, F64P), ptr(diag, F64P), m, ptr(act, I32P), ptr(x, F64P),
+                                   ptr(bad, I32P), ptr(rn, F64P), ptr(bn, F64P), ptr(tot, I32P), ptr(unc, I32P), ptr(worst, F64P)))
+    return dict(x=x[:3 * n].reshape(n, 3), bad=bad[:3].copy(), rnorm=rn[:3].copy(), bnorm=bn[:3].copy(), total=int(tot[0]),
+                unconverged=int(unc[0]), worst=float(worst[0]))
+
+
+def hook_node_update(x, Q, l1=False, device=0):
+    """-> (Q_new (n, 4), Wv (n, 3) or None, score): score = sum of |x_v| over v >= 1, or its max for the L1 variant."""
+    Q = _f64(Q); n = Q.size // 4
+    x = _f64(x, 3 * n)
+    Qo, sc = out_buffer(4 * n), out_buffer(1)
+    if l1:
+        check(load().desc_test_irls_node_update(ptr(x, F64P), ptr(Q, F64P), n, device, ptr(Qo, F64P), ptr(sc, F64P)))
+        return Qo[:4 * n].reshape(n, 4), None, float(sc[0])
+    Wv = out_buffer(3 * n)
+    check(load().desc_test_laa_node_update(ptr(x, F64P), ptr(Q, F64P), n, device, ptr(Qo, F64P), ptr(Wv, F64P), ptr(sc, F64P)))
+    return Qo[:4 * n].reshape(n, 4), Wv[:3 * n].reshape(n, 3), float(sc[0])
+
+
+def hook_weights(x, thresh, device=0):
+    x = _f64(x); m = x.size
+    w = out_buffer(m)
+    check(load().desc_test_laa_weights(ptr(x, F64P), m, float(thresh), device, ptr(w, F64P)))
+    return w[:m]
+
+
+def hook_irls_weights(dprob: DeviceProblem, x, B, mode, sigma):
+    n, m = dprob.n, dprob.m
+    x, B = _f64(x, 3 * n), _f64(B, 3 * m)
+    w = out_buffer(m)
+    check(load().desc_test_irls_weights(dprob.handle, ptr(x, F64P), ptr(B, F64P), m, int(mode), float(sigma), ptr(w, F64P)))
+    return w[:m]
+
+
+HOOK_QCAP = 1 << 20      # laa.hip's QCAP: the capacity the library itself passes to device_quantile (the hook refuses more)
+
+
+def hook_quantile(x, p, cap=HOOK_QCAP, device=0):
+    x = _f64(x)
+    out = out_buffer(1)
+    check(load().desc_test_laa_quantile(ptr(x, F64P), x.size, float(p), int(cap), device, ptr(out, F64P)))
+    return float(out[0])
+
+
+def hook_project(rij, order=None, only=-1, device=0):
+    """rij: (m, 9) blocks Rij -> dict(P (m, 9), bad_row (-1: none), warn, info (5,))."""
+    rij = _f64(rij); m = rij.size // 9
+    od = None if order is None else np.ascontiguousarray(order, dtype=np.int32)
+    P, bad, warn, info = out_buffer(9 * m), out_buffer(1, np.int32), out_buffer(1, np.int32), out_buffer(5)
+    check(load().desc_test_irls_project(ptr(rij, F64P), ptr(od, I32P), m, int(only), device, ptr(P, F64P), ptr(bad, I32P), ptr(warn, I32P),
+                                        ptr(info, F64P)))
+    return dict(P=P[:9 * m].reshape(m, 9), bad_row=int(bad[0]), warn=int(warn[0]), info=info[:5].copy())

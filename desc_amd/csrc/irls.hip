@@ -674,3 +674,62 @@ extern "C" int desc_irls_run_dev(const desc_device_problem* dp, const desc_irls_
     return DESC_OK;
     });
 }
+
+// ---- test hooks (include/desc_amd.h, tests/test_gpu_laa_maps.py): the kernels of this file that belong to the averaging core's
+// arithmetic, one at a time on caller (host) arrays, launched as desc_irls_run_dev launches them.  Nothing in the library calls them.
+extern "C" int desc_test_irls_project(const double* rij, const int32_t* order, int64_t m, int64_t only, int32_t device, double* P,
+                                      int32_t* bad_row, int32_t* warn, double* info) {
+    return no_throw("desc_test_irls_project", [&]() -> int {
+    if (!rij || !P || !bad_row || !warn || !info) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (m < 0) return fail(DESC_ERR_INVALID, "negative count");
+    if (only >= m) return fail(DESC_ERR_INVALID, "only must be an edge or negative");
+    if (order)
+        for (int64_t e = 0; e < m; ++e) if (order[e] < 0) return fail(DESC_ERR_INVALID, "order holds a negative row");
+    DESC_HIP(hipSetDevice(device));
+    DevArena A; int rc; double *d_rij, *d_P, *d_einfo; int32_t *d_flags, *d_order = nullptr;
+    if ((rc = hook_upload(A, rij, 9 * m, &d_rij)) || (rc = A.alloc(&d_P, (size_t)(9 * m))) || (rc = A.alloc(&d_flags, 2)) || (rc = A.alloc(&d_einfo, 5)) ||
+        (order && (rc = hook_upload(A, order, m, &d_order))))
+        return rc;
+    const int32_t init_flags[2] = {INT_MAX, 0};
+    DESC_HIP(hipMemcpy(d_flags, init_flags, sizeof init_flags, hipMemcpyHostToDevice));
+    DESC_HIP(hipMemset(d_einfo, 0, sizeof(double) * 5));
+    if (m) hipLaunchKernelGGL(k_irls_project, dim3(grid_for(m, 2048)), dim3(256), 0, 0, d_rij, d_order, m, d_P, d_flags, d_flags + 1, (int64_t)-1, d_einfo);
+    if (only >= 0) hipLaunchKernelGGL(k_irls_project, dim3(1), dim3(256), 0, 0, d_rij, d_order, m, d_P, d_flags, d_flags + 1, only, d_einfo);
+    int32_t flags[2];
+    if ((rc = hook_download(flags, d_flags, 2))) return rc;
+    *bad_row = flags[0] == INT_MAX ? -1 : flags[0]; *warn = flags[1];
+    if ((rc = hook_download(info, d_einfo, 5))) return rc;
+    return hook_download(P, d_P, 9 * m);
+    });
+}
+
+extern "C" int desc_test_irls_node_update(const double* x, const double* Q, int64_t n, int32_t device, double* Q_out, double* score) {
+    return no_throw("desc_test_irls_node_update", [&]() -> int {
+    if (!x || !Q || !Q_out || !score) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (n < 0 || n > INT_MAX) return fail(DESC_ERR_INVALID, "n out of range");
+    DESC_HIP(hipSetDevice(device));
+    DevArena A; int rc; double *d_x, *d_part; Quat* d_Q;
+    const int sgrid = LaaSolver().sgrid;
+    if ((rc = hook_upload(A, x, 3 * n, &d_x)) || (rc = hook_upload(A, (const Quat*)Q, n, &d_Q)) || (rc = A.alloc(&d_part, (size_t)sgrid))) return rc;
+    hipLaunchKernelGGL(k_l1_node_update, dim3(sgrid), dim3(256), 0, 0, d_x, d_Q, (int)n, d_part);
+    hvec<double> part((size_t)sgrid);
+    if ((rc = hook_download(part.data(), d_part, sgrid))) return rc;
+    double s = 0.0; for (double v : part) s = std::fmax(s, v);
+    *score = s;
+    return hook_download((Quat*)Q_out, d_Q, n);
+    });
+}
+
+extern "C" int desc_test_irls_weights(const desc_device_problem* dp, const double* x, const double* B, int64_t m, int32_t mode, double sigma,
+                                      double* w) {
+    return no_throw("desc_test_irls_weights", [&]() -> int {
+    if (!dp || !x || !B || !w) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (m < 0 || m != dp->m) return fail(DESC_ERR_INVALID, "m does not match the device problem");
+    if (mode != DESC_IRLS_GM && mode != DESC_IRLS_L12) return fail(DESC_ERR_INVALID, "mode must be DESC_IRLS_GM or DESC_IRLS_L12");
+    DESC_HIP(hipSetDevice(dp->device));
+    DevArena A; int rc; double *d_x, *d_B, *d_w;
+    if ((rc = hook_upload(A, x, 3 * dp->n, &d_x)) || (rc = hook_upload(A, B, 3 * m, &d_B)) || (rc = A.alloc(&d_w, (size_t)m))) return rc;
+    if (m) hipLaunchKernelGGL(k_irls_weights, dim3(grid_for(m, 2048)), dim3(256), 0, 0, d_x, d_B, dp->d_ii, dp->d_jj, m, mode, sigma, d_w);
+    return hook_download(w, d_w, m);
+    });
+}

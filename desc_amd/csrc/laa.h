@@ -57,6 +57,23 @@ int laa_quantile(LaaSolver& L, const double* d_x, double p, double* result);
 // q2R.m of every node into R_out (n*9 host doubles); prints the reference's warning when a PCG solve stopped at its cap
 int laa_finish(LaaSolver& L, int iterations, double* R_out);
 
+// ---- copies of the test hooks (desc_test_laa_* in laa.hip, desc_test_irls_* in irls.hip): `count` host elements into a fresh block of
+// the arena; `count` elements back after the device has drained, with the launch errors it left
+template <class T>
+int hook_upload(DevArena& A, const T* host, int64_t count, T** out) {
+    int rc = A.alloc(out, (size_t)count);
+    if (rc) return rc;
+    if (count) DESC_HIP(hipMemcpy(*out, host, sizeof(T) * count, hipMemcpyHostToDevice));
+    return DESC_OK;
+}
+template <class T>
+int hook_download(T* host, const T* dev, int64_t count) {
+    DESC_HIP(hipDeviceSynchronize());
+    DESC_HIP(hipGetLastError());
+    if (count) DESC_HIP(hipMemcpy(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost));
+    return DESC_OK;
+}
+
 // ---- device helpers.  The library is built without contraction and fast-math: an expression tree kept as it is gives the same bits, so
 // operand order and bracketing below are part of the interface.
 // Hamilton product a * b.  inv(q) * b as the reference writes it (the negated product, the same rotation) is qmul({-q.a, q.x, q.y, q.z}, b).

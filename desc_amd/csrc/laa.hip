@@ -412,3 +412,145 @@ int laa_finish(LaaSolver& L, int iterations, double* R_out) {
 }
 
 }  // namespace desc
+
+// ---- test hooks (include/desc_amd.h, tests/test_gpu_laa_maps.py): one operation of the core on caller (host) arrays, with the kernel
+// and the grid rule of the product path (laa_setup's egrid / ngrid / rgrid / sgrid).  Nothing in the library calls them.
+using namespace desc;
+
+namespace {
+
+// the solver state of laa_setup on dp (identity R_init): grids, incidence signs, work arrays
+int hook_solver(const desc_device_problem* dp, LaaSolver& L) {
+    if (dp->m && !dp->d_rij) return fail(DESC_ERR_INVALID, "the device problem holds no rotations");
+    hvec<double> eye((size_t)9 * dp->n, 0.0);
+    for (int64_t v = 0; v < dp->n; ++v) eye[9 * v] = eye[9 * v + 4] = eye[9 * v + 8] = 1.0;
+    return laa_setup(dp, eye.data(), L);
+}
+
+}  // namespace
+
+extern "C" int desc_test_laa_r2q(const double* R, int64_t count, int32_t transpose, int32_t edge_grid, int32_t device, double* Q) {
+    return no_throw("desc_test_laa_r2q", [&]() -> int {
+    if (!R || !Q) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (count < 0) return fail(DESC_ERR_INVALID, "negative count");
+    DESC_HIP(hipSetDevice(device));
+    DevArena A; int rc; double* d_R; Quat* d_Q;
+    if ((rc = hook_upload(A, R, 9 * count, &d_R)) || (rc = A.alloc(&d_Q, (size_t)count))) return rc;
+    const int grid = edge_grid ? grid_for(count, 2048) : grid_for(count, 512);                       // laa_setup: egrid / ngrid
+    if (count) hipLaunchKernelGGL(k_r2q, dim3(grid), dim3(256), 0, 0, d_R, d_Q, count, transpose ? 1 : 0);
+    return hook_download((Quat*)Q, d_Q, count);
+    });
+}
+
+extern "C" int desc_test_laa_q2r(const double* Q, int64_t n, int32_t device, double* R) {
+    return no_throw("desc_test_laa_q2r", [&]() -> int {
+    if (!Q || !R) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (n < 0) return fail(DESC_ERR_INVALID, "negative count");
+    DESC_HIP(hipSetDevice(device));
+    DevArena A; int rc; Quat* d_Q; double* d_R;
+    if ((rc = hook_upload(A, (const Quat*)Q, n, &d_Q)) || (rc = A.alloc(&d_R, (size_t)(9 * n)))) return rc;
+    if (n) hipLaunchKernelGGL(k_q2r, dim3(grid_for(n, 512)), dim3(256), 0, 0, d_Q, d_R, n);          // laa_finish
+    return hook_download(R, d_R, 9 * n);
+    });
+}
+
+extern "C" int desc_test_laa_edge_log(const desc_device_problem* dp, const double* Q, const double* QQ, int64_t m, double* B) {
+    return no_throw("desc_test_laa_edge_log", [&]() -> int {
+    if (!dp || !Q || !QQ || !B) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (m < 0 || m != dp->m) return fail(DESC_ERR_INVALID, "m does not match the device problem");
+    DESC_HIP(hipSetDevice(dp->device));
+    LaaSolver L; int rc;
+    if ((rc = hook_solver(dp, L))) return rc;
+    DESC_HIP(hipMemcpy(L.d_Q, Q, sizeof(Quat) * L.n, hipMemcpyHostToDevice));
+    if (m) DESC_HIP(hipMemcpy(L.d_QQ, QQ, sizeof(Quat) * m, hipMemcpyHostToDevice));
+    laa_edge_log(L);
+    return hook_download(B, L.d_B, 3 * m);
+    });
+}
+
+extern "C" int desc_test_laa_rhs(const desc_device_problem* dp, const double* w, const double* B, int64_t m, double* rhs, double* diag) {
+    return no_throw("desc_test_laa_rhs", [&]() -> int {
+    if (!dp || !w || !B || !rhs || !diag) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (m < 0 || m != dp->m) return fail(DESC_ERR_INVALID, "m does not match the device problem");
+    DESC_HIP(hipSetDevice(dp->device));
+    LaaSolver L; int rc;
+    if ((rc = hook_solver(dp, L))) return rc;
+    if (m) { DESC_HIP(hipMemcpy(L.d_w, w, sizeof(double) * m, hipMemcpyHostToDevice)); DESC_HIP(hipMemcpy(L.d_B, B, sizeof(double) * 3 * m, hipMemcpyHostToDevice)); }
+    hipLaunchKernelGGL(k_rhs, dim3(L.rgrid), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj_eid, L.d_sgn, L.d_w, L.d_B, L.d_rhs, L.d_diag, (int)L.n);   // laa_step
+    if ((rc = hook_download(rhs, L.d_rhs, 3 * L.n))) return rc;
+    return hook_download(diag, L.d_diag, L.n);
+    });
+}
+
+extern "C" int desc_test_laa_pcg(const desc_device_problem* dp, int32_t w3, const double* w, const double* rhs, const double* diag, int64_t m,
+                                 const int32_t* act, double* x, int32_t* bad, double* rnorm, double* bnorm, int32_t* total,
+                                 int32_t* unconverged, double* worst) {
+    return no_throw("desc_test_laa_pcg", [&]() -> int {
+    if (!dp || !w || !rhs || !diag || !act || !x || !bad || !rnorm || !bnorm || !total || !unconverged || !worst)
+        return fail(DESC_ERR_INVALID, "NULL argument");
+    if (m < 0 || m != dp->m) return fail(DESC_ERR_INVALID, "m does not match the device problem");
+    DESC_HIP(hipSetDevice(dp->device));
+    LaaSolver L; int rc;
+    if ((rc = hook_solver(dp, L))) return rc;
+    const int64_t n = L.n, wlen = w3 ? 3 * m : m, dlen = w3 ? 3 * n : n;
+    double *d_w, *d_diag, *d_xx;
+    if ((rc = hook_upload<double>(L, w, wlen, &d_w)) || (rc = hook_upload<double>(L, diag, dlen, &d_diag)) || (rc = L.alloc(&d_xx, (size_t)(3 * n)))) return rc;
+    DESC_HIP(hipMemcpy(L.d_rhs, rhs, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
+    const int a3[3] = {act[0] != 0, act[1] != 0, act[2] != 0};
+    int b3[3] = {0, 0, 0};
+    CgCount cnt;
+    rc = w3 ? laa_pcg<true, true>(L, d_w, L.d_rhs, d_diag, d_xx, a3, 5, cnt, b3)                   // pd_pcg (irls.hip): PD_PROBE
+            : laa_pcg<false, false>(L, d_w, L.d_rhs, d_diag, d_xx, a3, 25, cnt, b3);               // laa_step
+    if (rc) return rc;
+    CgScal hs;
+    if ((rc = hook_download(&hs, L.d_sc, 1))) return rc;
+    for (int c = 0; c < 3; ++c) { bad[c] = b3[c]; rnorm[c] = hs.rnorm[c]; bnorm[c] = hs.bnorm[c]; }
+    *total = cnt.total; *unconverged = cnt.unconverged; *worst = cnt.worst;
+    return hook_download(x, d_xx, 3 * n);
+    });
+}
+
+extern "C" int desc_test_laa_node_update(const double* x, const double* Q, int64_t n, int32_t device, double* Q_out, double* Wv, double* score) {
+    return no_throw("desc_test_laa_node_update", [&]() -> int {
+    if (!x || !Q || !Q_out || !Wv || !score) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (n < 0 || n > INT32_MAX) return fail(DESC_ERR_INVALID, "n out of range");
+    DESC_HIP(hipSetDevice(device));
+    DevArena A; int rc; double *d_x, *d_Wv, *d_part; Quat* d_Q;
+    const int sgrid = LaaSolver().sgrid;
+    if ((rc = hook_upload(A, x, 3 * n, &d_x)) || (rc = hook_upload(A, (const Quat*)Q, n, &d_Q)) || (rc = A.alloc(&d_Wv, (size_t)(3 * n))) ||
+        (rc = A.alloc(&d_part, (size_t)sgrid)))
+        return rc;
+    hipLaunchKernelGGL(k_node_update, dim3(sgrid), dim3(256), 0, 0, d_x, d_Q, d_Wv, (int)n, d_part);   // laa_step
+    hvec<double> part((size_t)sgrid);
+    if ((rc = hook_download(part.data(), d_part, sgrid))) return rc;
+    double s = 0.0; for (double v : part) s += v;
+    *score = s;                                                                                      // laa_step divides this by n
+    if ((rc = hook_download((Quat*)Q_out, d_Q, n))) return rc;
+    return hook_download(Wv, d_Wv, 3 * n);
+    });
+}
+
+extern "C" int desc_test_laa_weights(const double* x, int64_t m, double thresh, int32_t device, double* w) {
+    return no_throw("desc_test_laa_weights", [&]() -> int {
+    if (!x || !w) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (m < 0) return fail(DESC_ERR_INVALID, "negative count");
+    DESC_HIP(hipSetDevice(device));
+    DevArena A; int rc; double *d_x, *d_w;
+    if ((rc = hook_upload(A, x, m, &d_x)) || (rc = A.alloc(&d_w, (size_t)m))) return rc;
+    if (m) hipLaunchKernelGGL(k_weights, dim3(grid_for(m, 2048)), dim3(256), 0, 0, d_x, d_w, m, thresh, 1e4, 1e-4);   // laa_weights
+    return hook_download(w, d_w, m);
+    });
+}
+
+extern "C" int desc_test_laa_quantile(const double* x, int64_t m, double p, int64_t cap, int32_t device, double* result) {
+    return no_throw("desc_test_laa_quantile", [&]() -> int {
+    if (!x || !result) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (m < 0) return fail(DESC_ERR_INVALID, "negative count");
+    if (!(p >= 0.0 && p <= 1.0)) return fail(DESC_ERR_INVALID, "p must lie in [0, 1]");
+    if (cap < 1 || cap > (int64_t)QCAP) return fail(DESC_ERR_INVALID, "cap must lie in [1, %u]", QCAP);
+    DESC_HIP(hipSetDevice(device));
+    DevArena A; int rc; double *d_x, *d_mm, *d_cand; unsigned* d_qh;
+    if ((rc = hook_upload(A, x, m, &d_x)) || (rc = A.alloc(&d_mm, 128)) || (rc = A.alloc(&d_cand, (size_t)cap)) || (rc = A.alloc(&d_qh, QBINS + 1))) return rc;
+    return device_quantile(d_x, m, p, d_mm, d_qh, d_cand, (unsigned)cap, result);
+    });
+}

@@ -736,6 +736,43 @@ int desc_debug_spmm_variants(const desc_device_problem* dp, int32_t reps, double
  * DPP / permlane-swap reduction; every element of a group receives the group total. */
 int desc_selftest_group_sum(const double* in, double* out, int32_t count, int32_t G, int32_t device);
 
+/* Test hooks (tests/test_gpu_laa_maps.py): one operation of the Lie-algebraic averaging core (laa.hip, irls.hip) on caller arrays
+ * in host memory, launched with the kernel and the grid rule the library itself uses; nothing in the library calls them.  Quaternions
+ * are 4 doubles (a, x, y, z), blocks 9 doubles column-major, per-edge / per-node vectors 3 doubles.  A NULL pointer, a negative count,
+ * p outside [0, 1] or an m that differs from the device problem's returns DESC_ERR_INVALID before any device work.
+ *   r2q          count blocks -> count quaternions (R2Q.m); transpose: of the transposed block; edge_grid: the grid rule of the edge
+ *                arrays (else of the node arrays)
+ *   q2r          n quaternions -> n blocks (q2R.m)
+ *   edge_log     Q (n), QQ (m) -> B (m x 3), Weighted_LAA.m:9-35; the device problem must hold rotations (any)
+ *   rhs          w (m), B (m x 3) -> rhs (n x 3), diag (n): A' W^2 B and the diagonal of A' W^2 A
+ *   pcg          the Jacobi-PCG: w3 = 0 Weighted_LAA's instance (w: m, diag: n, probed every 25 steps), w3 = 1 the primal-dual Newton
+ *                instance with breakdown tracking (w: 3m, diag: 3n, probed every 5 steps); act[3] selects the coordinates of the
+ *                convergence test.  Out: x (n x 3), bad[3], the last probe's |r|^2 and |b|^2 per coordinate (rnorm[3], bnorm[3]) and
+ *                the solve's bookkeeping (steps, 1 if it stopped at the cap, largest |r| / |b|)
+ *   node_update  x (n x 3), Q (n) -> Q * exp(x), the vector parts Wv (n x 3) and sum_{v >= 1} |x_v| (Weighted_LAA.m:40-50; the
+ *                library divides the sum by n); irls_node_update: the same with max_{v >= 1} |x_v| (BoxMedianSO3Graph.m:172-185)
+ *   weights      x (m), thresh -> min(1 / x^0.75, 1e4), 1e-4 where x > thresh (DESC.m:298-303)
+ *   irls_weights x (n x 3), B (m x 3) -> the GM / L12 weights of the edge residuals (mode: DESC_IRLS_GM / DESC_IRLS_L12)
+ *   quantile     MATLAB's quantile(x, p) of m values; cap: most values collected from the two histogram bins before the exact
+ *                host path takes over (the library passes 2^20)
+ *   irls_project m blocks Rij (+ optional caller rows `order`) -> P = U round(S) V' of their transposes (m x 9), the smallest failing
+ *                caller row (-1: none), the number of warned edges; only >= 0: also that edge's {status, det, s1, s2, s3} in info[5] */
+int desc_test_laa_r2q(const double* R, int64_t count, int32_t transpose, int32_t edge_grid, int32_t device, double* Q);
+int desc_test_laa_q2r(const double* Q, int64_t n, int32_t device, double* R);
+int desc_test_laa_edge_log(const desc_device_problem* dp, const double* Q, const double* QQ, int64_t m, double* B);
+int desc_test_laa_rhs(const desc_device_problem* dp, const double* w, const double* B, int64_t m, double* rhs, double* diag);
+int desc_test_laa_pcg(const desc_device_problem* dp, int32_t w3, const double* w, const double* rhs, const double* diag, int64_t m,
+                      const int32_t* act, double* x, int32_t* bad, double* rnorm, double* bnorm, int32_t* total, int32_t* unconverged,
+                      double* worst);
+int desc_test_laa_node_update(const double* x, const double* Q, int64_t n, int32_t device, double* Q_out, double* Wv, double* score);
+int desc_test_irls_node_update(const double* x, const double* Q, int64_t n, int32_t device, double* Q_out, double* score);
+int desc_test_laa_weights(const double* x, int64_t m, double thresh, int32_t device, double* w);
+int desc_test_irls_weights(const desc_device_problem* dp, const double* x, const double* B, int64_t m, int32_t mode, double sigma,
+                           double* w);
+int desc_test_laa_quantile(const double* x, int64_t m, double p, int64_t cap, int32_t device, double* result);
+int desc_test_irls_project(const double* rij, const int32_t* order, int64_t m, int64_t only, int32_t device, double* P,
+                           int32_t* bad_row, int32_t* warn, double* info);
+
 #ifdef __cplusplus
 }
 #endif
