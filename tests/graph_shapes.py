@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE -- seeded graph families whose *shape* is not Erdos-Renyi: hubs, bands, stars, bipartite, bridged, power-law,
-dense with pendants, two components.  Every family builds an adjacency pattern and then applies the measurement model of
+dense with pendants, two components, books.  Every family builds an adjacency pattern and then applies the measurement model of
 ``Uniform_Topology`` (desc_amd/models.py:88-104): Haar ground truth, noise of size ``sigma`` on the good edges, Haar outliers with
 probability ``q``.  The struct returned is the one ``Uniform_Topology`` returns: ``Ind`` (m x 2, 1-based, i < j, sorted by (i, j)),
 ``RijMat``, ``Rij_orig``, ``R_orig``, ``ErrVec``, ``corrupted``, ``AdjMat``.
@@ -53,12 +53,23 @@ def hub(n, p, hubs, q=0.2, sigma=0.1, seed=0):
     return _measure(n, np.concatenate(pairs), q, sigma, rng)
 
 
-def band(n, k, q=0.2, sigma=0.1, seed=0):
-    """i ~ i +- 1 .. +- k.  k = 1: the path."""
+def band(n, k, q=0.2, sigma=0.1, seed=0, chords=()):
+    """i ~ i +- 1 .. +- k.  k = 1: the path.  ``chords``: further (i, j) pairs."""
     rng = np.random.default_rng(seed)
     i = np.arange(1, n + 1)
     pairs = [np.stack([i[:-d], i[d:]], axis=1) for d in range(1, k + 1)]
+    if len(chords):
+        pairs.append(np.asarray(chords, dtype=np.int64).reshape(-1, 2))
     return _measure(n, np.concatenate(pairs), q, sigma, rng)
+
+
+def book(pages, q=0.2, sigma=0.1, seed=0):
+    """The spine {1, 2} and ``pages`` triangles on it: every page k = 3 .. pages + 2 is adjacent to 1 and to 2.  The spine has codegree
+    ``pages``, every page edge codegree 1 (its only cycle runs through the spine): n = pages + 2, m = 2 pages + 1."""
+    rng = np.random.default_rng(seed)
+    k = np.arange(3, pages + 3)
+    pairs = [np.array([[1, 2]]), np.stack([np.full(pages, 1), k], axis=1), np.stack([np.full(pages, 2), k], axis=1)]
+    return _measure(pages + 2, np.concatenate(pairs), q, sigma, rng)
 
 
 def star(n, hub_id, q=0.2, sigma=0.1, seed=0):

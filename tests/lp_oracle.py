@@ -25,9 +25,9 @@ def rule_nsample(codeg_pos):
     return int(max(np.ceil(matlab_median(np.asarray(codeg_pos, dtype=np.float64)) / 4.0), 30))
 
 
-def build_lp(Ind, RijMat, seed, nsample=None):
-    """-> (K (2 m_pos nsample x m_pos, CSR), b, pos (0-based edge ids with cycles, ascending), k (m_pos x nsample, 1-based), nsample).
-    ``Ind`` must be sorted by (i, j)."""
+def lp_arrays(Ind, RijMat, seed, nsample=None):
+    """-> (own, va, vb (m_pos nsample each: the three columns of cycle c = l nsample + t, variable indices), d (m_pos x nsample: S0Mat(t, l) at
+    [l][t]), pos (0-based edge ids with cycles, ascending), k (m_pos x nsample, 1-based), nsample).  ``Ind`` must be sorted by (i, j)."""
     Ind = np.asarray(Ind, dtype=np.int64)
     Ind_i, Ind_j = Ind[:, 0] - 1, Ind[:, 1] - 1
     n = int(Ind.max()); m = Ind.shape[0]
@@ -56,16 +56,24 @@ def build_lp(Ind, RijMat, seed, nsample=None):
     Rc = np.matmul(np.matmul(R[pos][:, None], Rjk), Rki)                                    # :88-100
     tr = Rc[..., 0, 0] + Rc[..., 1, 1] + Rc[..., 2, 2]
     d = matlab_abs_acos(((tr - 1) / 2).reshape(-1)).reshape(tr.shape) / np.pi               # S0Mat(t, l), here [l][t]  (:101)
-    nc = mp * nsample
     own = np.repeat(np.arange(mp), nsample); va = var[eki.reshape(-1)]; vb = var[ejk.reshape(-1)]
     assert (va >= 0).all() and (vb >= 0).all()          # the edges ik, jk of a triangle lie on that triangle
+    return own, va, vb, d, pos, k + 1, nsample
+
+
+def build_lp(Ind, RijMat, seed, nsample=None):
+    """-> (K (2 m_pos nsample x m_pos, CSR), b, pos (0-based edge ids with cycles, ascending), k (m_pos x nsample, 1-based), nsample).
+    ``Ind`` must be sorted by (i, j)."""
+    own, va, vb, d, pos, k, nsample = lp_arrays(Ind, RijMat, seed, nsample)
+    mp = pos.size
+    nc = mp * nsample
     rows = np.arange(nc)
     r = np.concatenate([2 * rows, 2 * rows, 2 * rows, 2 * rows + 1, 2 * rows + 1, 2 * rows + 1])
     c = np.concatenate([own, va, vb, own, va, vb])
     v = np.concatenate([np.ones(nc), -np.ones(nc), -np.ones(nc), -np.ones(nc), -np.ones(nc), -np.ones(nc)])
     K = sp.csr_matrix((v, (r, c)), shape=(2 * nc, mp))                                       # :107-131
     b = np.empty(2 * nc); b[0::2] = d.reshape(-1); b[1::2] = -d.reshape(-1)
-    return K, b, pos, k + 1, nsample
+    return K, b, pos, k, nsample
 
 
 def solve_highs(K, b):
@@ -90,6 +98,127 @@ def pdhg_plain(K, b, tau, sigma, N):
         y = np.maximum(y + sigma * (K @ (2.0 * xn - x) - b), 0.0)
         x = xn
     return x, y
+
+
+def _margin(a, b):
+    """Relative distance of the two sides of a comparison (inf against an infinite side, 0 for 0 against 0)."""
+    a, b = float(a), float(b)
+    if np.isinf(a) or np.isinf(b):
+        return np.inf
+    big = max(abs(a), abs(b))
+    return abs(a - b) / big if big > 0 else 0.0
+
+
+def pdhg_loop(own, va, vb, d, m_pos, nsample, max_iter, tol, check_every=64, restart=True, dtype=np.float64):
+    """The loop of desc_amd/csrc/lp.hip (its head comment), matrix-free: cycle c = l nsample + t has the columns own[c] = l, va[c], vb[c] and
+    the rows  x_l - x_a - x_b <= d_c  (dual y[c, 0]) and  -x_l - x_a - x_b <= -d_c  (dual y[c, 1]).  Every number is kept in ``dtype``.
+    -> dict: x (m_pos), y (m_pos x nsample x 2), iters, restarts, converged, rec = (viol, P, D) of the returned point, and log, one entry
+    per check: it, avg (the average was the candidate), fired (None, "0.2", "0.8+grew", "period": the restart condition), margins
+    (name -> relative margin of every comparison that was evaluated on the way to what the check did: "avg" e_avg against e_cur, "0.2" and
+    "0.8" e against that part of e_restart, "grew" e against e_prev, "period" cnt against 0.36 it, "stop" the stopping test: the closer of
+    its two comparisons when it passed, the farther of the failed ones when it did not)."""
+    T = dtype
+    mp, ns = int(m_pos), int(nsample)
+    nc = mp * ns
+    own, va, vb = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (own, va, vb))
+    d = np.asarray(d).reshape(-1).astype(T)
+    assert own.size == va.size == vb.size == d.size == nc
+    one, zero = T(1), T(0)
+    inc = np.bincount(va, minlength=mp) + np.bincount(vb, minlength=mp)
+    tau = one / (T(2) * T(ns) + T(2) * inc.astype(T))
+    sigma = one / T(3)
+    checks = bool(restart) or tol > 0
+    tolT = T(tol)
+
+    def reduced_cost(y1, y2):                                   # 1 + K'y
+        r = np.zeros(mp, dtype=T)
+        np.add.at(r, own, y1 - y2)
+        z = y1 + y2
+        np.add.at(r, va, -z); np.add.at(r, vb, -z)
+        return one + r
+
+    def record(x, y1, y2):                                      # (viol, P, D)
+        s = x[va] + x[vb]; xl = x[own]
+        viol = max(np.maximum((xl - s) - d, (-xl - s) + d).max(), zero) if nc else zero
+        return viol, x.sum(dtype=T), -(d * (y1 - y2)).sum(dtype=T) + np.minimum(reduced_cost(y1, y2), zero).sum(dtype=T)
+
+    def error_of(r):
+        return max(r[0], abs(r[1] - r[2]) / (one + abs(r[1]) + abs(r[2])))
+
+    x = np.zeros(mp, dtype=T); y1 = np.zeros(nc, dtype=T); y2 = np.zeros(nc, dtype=T)
+    xs, y1s, y2s = x.copy(), y1.copy(), y2.copy()
+    e_restart = e_prev = T(np.inf)
+    cnt = it = restarts = 0
+    converged = False
+    fin = None
+    log = []
+    while it < max_iter:
+        it += 1
+        xn = np.clip(x - tau * reduced_cost(y1, y2), zero, one)
+        xbar = T(2) * xn - x
+        x = xn
+        s = xbar[va] + xbar[vb]; xl = xbar[own]
+        y1 = np.maximum(y1 + sigma * ((xl - s) - d), zero)
+        y2 = np.maximum(y2 + sigma * ((-xl - s) + d), zero)
+        cnt += 1
+        if restart:
+            xs = xs + x; y1s = y1s + y1; y2s = y2s + y2
+        if not checks or (it % check_every != 0 and it != max_iter):
+            continue
+        margins = {}
+        cand = (x, y1, y2); rec = record(*cand)
+        use_avg = False
+        if restart:
+            avg = (xs / T(cnt), y1s / T(cnt), y2s / T(cnt)); rec_avg = record(*avg)
+            use_avg = bool(error_of(rec_avg) <= error_of(rec))
+            margins["avg"] = _margin(error_of(rec_avg), error_of(rec))
+            if use_avg:
+                cand, rec = avg, rec_avg
+        e = error_of(rec)
+        fin = (cand, rec)
+        entry = dict(it=it, avg=use_avg, fired=None, margins=margins)
+        log.append(entry)
+        if tol > 0:
+            P, D = rec[1], rec[2]
+            two = [(rec[0], tolT), (P - D, tolT * (one + abs(P) + abs(D)))]
+            ok = [bool(a <= b) for a, b in two]
+            m2 = [_margin(a, b) for a, b in two]
+            margins["stop"] = min(m2) if all(ok) else max(mm for mm, o in zip(m2, ok) if not o)
+            if all(ok):
+                converged = True
+                break
+        if not restart or it == max_iter:
+            continue
+        margins["0.2"] = _margin(e, T(0.2) * e_restart)
+        if e <= T(0.2) * e_restart:
+            entry["fired"] = "0.2"
+        else:
+            margins["0.8"] = _margin(e, T(0.8) * e_restart)
+            if e <= T(0.8) * e_restart:
+                margins["grew"] = _margin(e, e_prev)
+                if e > e_prev:
+                    entry["fired"] = "0.8+grew"
+            if entry["fired"] is None:
+                margins["period"] = _margin(T(cnt), T(0.36) * T(it))
+                if T(cnt) >= T(0.36) * T(it):
+                    entry["fired"] = "period"
+        if entry["fired"] is not None:
+            if use_avg:
+                x, y1, y2 = cand
+            xs = np.zeros(mp, dtype=T); y1s = np.zeros(nc, dtype=T); y2s = np.zeros(nc, dtype=T)
+            e_restart = e; e_prev = T(np.inf); cnt = 0; restarts += 1
+        else:
+            e_prev = e
+    if fin is None:
+        fin = ((x, y1, y2), record(x, y1, y2))
+    (xf, y1f, y2f), rec = fin
+    return dict(x=xf, y=np.stack([y1f, y2f], axis=1).reshape(mp, ns, 2), iters=it, restarts=restarts, converged=converged, rec=rec, log=log)
+
+
+def same_decisions(a, b):
+    """Two pdhg_loop results took the same way through the loop."""
+    key = lambda r: (r["iters"], r["restarts"], r["converged"], [(g["it"], g["avg"], g["fired"]) for g in r["log"]])      # noqa: E731
+    return key(a) == key(b)
 
 
 def certificates(K, b, x, y):
