@@ -39,6 +39,7 @@ EXPORTS = [
     "desc_gcw_batch_max_n", "desc_gcw_batch_create", "desc_gcw_batch_sizes", "desc_gcw_batch_csr", "desc_gcw_batch_run", "desc_gcw_batch_destroy",
     "desc_cemp_batch_max_degree", "desc_cemp_batch_create", "desc_cemp_batch_sizes", "desc_cemp_batch_get_samples", "desc_cemp_batch_run",
     "desc_cemp_batch_destroy", "desc_mst_batch_max_n", "desc_mst_batch_check", "desc_mst_batch_run",
+    "desc_refine_batch_max_n", "desc_refine_batch_create", "desc_refine_batch_sizes", "desc_refine_batch_run", "desc_refine_batch_destroy",
     "desc_test_laa_r2q", "desc_test_laa_q2r", "desc_test_laa_edge_log", "desc_test_laa_rhs", "desc_test_laa_pcg", "desc_test_laa_node_update",
     "desc_test_irls_node_update", "desc_test_laa_weights", "desc_test_irls_weights", "desc_test_laa_quantile", "desc_test_irls_project",
 ]
@@ -121,6 +122,11 @@ class CempBatchTimings(C.Structure):
 
 class MstBatchTimings(C.Structure):
     _fields_ = [("ms_structure", C.c_double), ("ms_upload", C.c_double), ("ms_tree", C.c_double), ("ms_propagate", C.c_double),
+                ("ms_total", C.c_double)]
+
+
+class RefineBatchTimings(C.Structure):
+    _fields_ = [("ms_structure", C.c_double), ("ms_upload", C.c_double), ("ms_input", C.c_double), ("ms_refine", C.c_double),
                 ("ms_total", C.c_double)]
 
 
@@ -310,6 +316,13 @@ def load():
     L.desc_mst_batch_max_n.argtypes = []
     L.desc_mst_batch_check.argtypes = [C.POINTER(Problem), C.c_int32]
     L.desc_mst_batch_run.argtypes = [C.POINTER(Problem), C.c_int32, F64P, C.c_int32, F64P, I32P, C.POINTER(MstBatchTimings)]
+    L.desc_refine_batch_max_n.restype = C.c_int32
+    L.desc_refine_batch_max_n.argtypes = []
+    L.desc_refine_batch_create.argtypes = [C.POINTER(Problem), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.desc_refine_batch_sizes.argtypes = [C.c_void_p, I32P, I64P, I64P]
+    L.desc_refine_batch_run.argtypes = [C.c_void_p, F64P, F64P, C.c_double, C.c_int32, F64P, C.POINTER(RefineInfo), C.POINTER(RefineBatchTimings)]
+    L.desc_refine_batch_destroy.argtypes = [C.c_void_p]
+    L.desc_refine_batch_destroy.restype = None
     L.desc_test_laa_r2q.argtypes = [F64P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, F64P]
     L.desc_test_laa_q2r.argtypes = [F64P, C.c_int64, C.c_int32, F64P]
     L.desc_test_laa_edge_log.argtypes = [C.c_void_p, F64P, F64P, C.c_int64, F64P]
@@ -710,6 +723,65 @@ def mst_batch_run(probs, s_vec, device=0):
         outs.append((R[9 * n0:9 * n1].reshape((3, 3, n1 - n0), order="F"), T[n0 - b:n1 - b - 1].copy()))
     timings = dict(ms_structure=tm.ms_structure, ms_upload=tm.ms_upload, ms_tree=tm.ms_tree, ms_propagate=tm.ms_propagate, ms_total=tm.ms_total)
     return outs, timings
+
+
+def refine_batch_max_n():
+    """desc_refine_batch_max_n: the largest problem (nodes) the batched refinement takes."""
+    return int(load().desc_refine_batch_max_n())
+
+
+class RefineBatch:
+    """Owner of a desc_refine_batch*: the DESC refinement tail of B small problems in one launch (desc_refine_batch_*).
+    ``probs`` is a sequence of ProblemArrays.  The handle may be run any number of times."""
+
+    def __init__(self, probs, device=0):
+        self.probs = list(probs)                     # keeps the NumPy buffers alive
+        self.count = B = len(self.probs)
+        arr = (Problem * max(B, 1))(*[q.c for q in self.probs])
+        h = C.c_void_p()
+        check(load().desc_refine_batch_create(arr, B, int(device), C.byref(h)))
+        self.handle = h
+        no, eo = np.zeros(B + 1, dtype=np.int64), np.zeros(B + 1, dtype=np.int64)
+        check(load().desc_refine_batch_sizes(h, None, ptr(no, I64P), ptr(eo, I64P)))
+        self.node_off, self.edge_off = no, eo
+        self.n, self.m = int(no[B]), int(eo[B])
+
+    def run(self, s_vec, R_init, stop_threshold=1e-3, max_iters=100):
+        """One batched refinement.  s_vec: the concatenated S_vec (library's edge order); R_init: the concatenated 9 n_b doubles per
+        problem (3 x 3 x n_b column-major).  Returns a list of per-problem (R (3,3,n_b) Fortran-ordered, info dict with refine_run's
+        keys) and the call's timings."""
+        B = self.count
+        S = np.ascontiguousarray(s_vec, dtype=np.float64).reshape(-1)
+        Ri = np.ascontiguousarray(R_init, dtype=np.float64).reshape(-1)
+        if S.size != self.m:
+            raise ValueError(f"s_vec must hold {self.m} entries (all problems' edges behind one another), not {S.size}")
+        if Ri.size != 9 * self.n:
+            raise ValueError(f"R_init must hold {9 * self.n} entries (all problems' 3 x 3 x n blocks behind one another), not {Ri.size}")
+        R = out_buffer(9 * self.n)
+        infos = (RefineInfo * max(B, 1))()
+        tm = RefineBatchTimings()
+        check(load().desc_refine_batch_run(self.handle, ptr(S, F64P), ptr(Ri, F64P), stop_threshold, int(max_iters), ptr(R, F64P), infos,
+                                           C.byref(tm)))
+        outs = []
+        for b in range(B):
+            n0, n1 = int(self.node_off[b]), int(self.node_off[b + 1])
+            i = infos[b]
+            outs.append((R[9 * n0:9 * n1].reshape((3, 3, n1 - n0), order="F"),
+                         dict(iters=i.iters, cg_iters=i.cg_iters, score=i.score, ms_total=i.ms_total, cg_unconverged=i.cg_unconverged,
+                              cg_residual=i.cg_residual)))
+        timings = dict(ms_structure=tm.ms_structure, ms_upload=tm.ms_upload, ms_input=tm.ms_input, ms_refine=tm.ms_refine, ms_total=tm.ms_total)
+        return outs, timings
+
+    def destroy(self):
+        if self.handle:
+            load().desc_refine_batch_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
 
 
 def gcw_batch_csr(probs):

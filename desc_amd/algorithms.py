@@ -448,6 +448,84 @@ def DESC_init_batch(problems, params, seeds=None, return_info=False):
     return [(R, d["S_vec"]) for (R, _), d in zip(outs, pgd)]
 
 
+def _check_refine_batch_sizes(probs):
+    """The batched refinement's size cap, checked before the device is touched."""
+    cap = _lib.refine_batch_max_n()
+    for b, q in enumerate(probs):
+        if q.n > cap:
+            raise ValueError(f"problem {b}: n = {q.n} exceeds {cap} (the per-node state of the refinement must fit the LDS of one workgroup): "
+                             "solve it with DESC")
+
+
+def _r_init_list(probs, R_init_list):
+    """One R_init (3 x 3 x n_b) per problem -> the concatenation of their column-major blocks; refusals name the problem."""
+    if isinstance(R_init_list, (str, bytes)) or not hasattr(R_init_list, "__len__") or len(R_init_list) != len(probs):
+        got = len(R_init_list) if hasattr(R_init_list, "__len__") else type(R_init_list).__name__
+        raise ValueError(f"R_init_list must hold one R_init per problem ({len(probs)}), not {got}")
+    parts = []
+    for b, (q, R) in enumerate(zip(probs, R_init_list)):
+        R = np.asarray(R, dtype=np.float64)
+        if R.shape != (3, 3, q.n):
+            raise ValueError(f"problem {b}: R_init must be 3 x 3 x {q.n}, not {' x '.join(str(k) for k in R.shape)}")
+        bad = np.flatnonzero(~np.isfinite(R).all(axis=(0, 1)))
+        if bad.size:
+            raise ValueError(f"problem {b}: R_init holds a non-finite entry (node {int(bad[0])})")
+        parts.append(R.reshape(-1, order="F"))
+    return np.concatenate(parts) if parts else np.zeros(0)
+
+
+def _refine_batch_run(probs, device, S, R_init, stop_threshold, max_iters):
+    try:
+        batch = _lib.RefineBatch(probs, device)
+    except _lib.DescError as e:
+        if e.code == _lib.ERR_INVALID:
+            raise ValueError(str(e).split(": ", 1)[-1]) from None
+        raise
+    try:
+        return batch.run(S, R_init, stop_threshold, max_iters)
+    finally:
+        batch.destroy()
+
+
+def DESC_refine_batch(problems, S_list, R_init_list, stop_threshold=1e-3, max_iters=100, device=0, return_info=False):
+    """The refinement tail of DESC (Algorithms/DESC.m:265-313) on B independent small problems in one GPU launch (desc_refine_batch_*;
+    the reference has no such call): ``S_list[b]`` is problem b's S_vec in the caller's edge order, ``R_init_list[b]`` its 3 x 3 x n_b
+    start (what GCW gave).  Returns a list of R_est (3 x 3 x n_b): entry b is bit for bit what the refinement stage of DESC() gives for
+    these inputs, and no bit of it depends on the batch around it.  With ``return_info`` a list of (R_est, info): the record of the
+    single refinement (``iters``, ``score``, ``cg_iters``, ``cg_unconverged``, ``cg_residual``, ``ms_total``) plus the call's ``timings``.
+    Refused (ValueError, before the device is touched): not a sequence, an empty edge list, an S_list / R_init_list of the wrong length
+    or an entry of the wrong size, a negative or non-finite S entry, a non-finite R_init entry, a problem of more than
+    ``_lib.refine_batch_max_n()`` nodes (solve it with DESC)."""
+    _check_sequence(problems)
+    probs, perms = _marshal_problems(problems)
+    S = _sorted_s_list(probs, perms, S_list)
+    R0 = _r_init_list(probs, R_init_list)
+    if not probs:
+        return []
+    _check_refine_batch_sizes(probs)
+    outs, timings = _refine_batch_run(probs, device, S, R0, stop_threshold, max_iters)
+    return [(R, dict(info, timings=timings)) for R, info in outs] if return_info else [R for R, _ in outs]
+
+
+def DESC_batch(problems, params, seeds=None, return_info=False):
+    """DESC (Algorithms/DESC.m:14: DESC_PGD, then GCW, then the reweighted Lie-algebraic refinement) on B independent small problems:
+    DESC_init_batch's two passes, then the batched refinement on their S_vec and R_init -- three GPU passes for the whole batch.
+    Returns a list of (R_est, R_init, S_vec); S_vec and R_init are bit for bit DESC_init_batch's.  With ``return_info`` a list of
+    (R_est, R_init, S_vec, dict(pgd=..., gcw=..., refine=...)).  The batch prints nothing: ``params.verbose`` is ignored.
+    Refused (ValueError, before the device is touched): what DESC_init_batch refuses."""
+    _check_sequence(problems)
+    probs, perms = _marshal_problems(problems)
+    init = DESC_init_batch([_Marshalled(q, perm) for q, perm in zip(probs, perms)], params, seeds=seeds, return_info=True)
+    if not init:
+        return []
+    S = np.concatenate([S_vec if perm is None else S_vec[perm] for (_, S_vec, _), perm in zip(init, perms)])
+    R0 = np.concatenate([R.reshape(-1, order="F") for R, _, _ in init])
+    outs, timings = _refine_batch_run(probs, int(_get(params, "device", 0)), S, R0, 1e-3, 100)
+    if return_info:
+        return [(R, R_init, S_vec, dict(info, refine=dict(rinfo, timings=timings))) for (R, rinfo), (R_init, S_vec, info) in zip(outs, init)]
+    return [(R, R_init, S_vec) for (R, _), (R_init, S_vec, _) in zip(outs, init)]
+
+
 def _cemp_batch_params(CEMP_parameters, B, seeds):
     """The fields CEMP reads, checked once for the whole batch -> (beta, max_iter, nsample, seed, device, seeds)."""
     beta = _param_vec(CEMP_parameters, "reweighting", "CEMP_parameters")

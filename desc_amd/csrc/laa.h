@@ -3,10 +3,9 @@
 // (Algorithms/DESC.m:265-313, refine.hip), MPLS (Algorithms/MPLS.m:196-254, mpls.hip) and IRLS_GM / IRLS_L12 (irls.hip).
 #pragma once
 #include "device_utils.h"
+#include "laa_math.h"
 
 namespace desc {
-
-struct Quat { double a, x, y, z; };
 
 // the PCG's device-resident scalars, per coordinate; bad: the coordinate broke down (only set when breakdowns are tracked)
 struct CgScal { double rz[3], rz_new[3], pq[3], bnorm[3], rnorm[3]; int bad[3], pad; };
@@ -72,44 +71,6 @@ int hook_download(T* host, const T* dev, int64_t count) {
     DESC_HIP(hipGetLastError());
     if (count) DESC_HIP(hipMemcpy(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost));
     return DESC_OK;
-}
-
-// ---- device helpers.  The library is built without contraction and fast-math: an expression tree kept as it is gives the same bits, so
-// operand order and bracketing below are part of the interface.
-// Hamilton product a * b.  inv(q) * b as the reference writes it (the negated product, the same rotation) is qmul({-q.a, q.x, q.y, q.z}, b).
-__host__ __device__ __forceinline__ Quat qmul(const Quat& a, const Quat& b) {
-    Quat o;
-    o.a = a.a * b.a - (a.x * b.x + a.y * b.y + a.z * b.z);
-    o.x = a.a * b.x + b.a * a.x + (a.y * b.z - a.z * b.y);
-    o.y = a.a * b.y + b.a * a.y + (a.z * b.x - a.x * b.z);
-    o.z = a.a * b.z + b.a * a.z + (a.x * b.y - a.y * b.x);
-    return o;
-}
-// exp map of the tangent vector t (Weighted_LAA.m:42-46, BoxMedianSO3Graph.m:176-180): *theta = |t|; NaN -> 0 (theta = 0 gives the zero
-// quaternion part, as the reference)
-__device__ __forceinline__ Quat qexp(double t1, double t2, double t3, double* theta) {
-    const double th = sqrt(t1 * t1 + t2 * t2 + t3 * t3);
-    Quat w;
-    w.a = cos(th / 2.0);
-    const double f = sin(th / 2.0) / th;
-    w.x = t1 * f; w.y = t2 * f; w.z = t3 * f;
-    if (isnan(w.a)) w.a = 0.0;
-    if (isnan(w.x)) w.x = 0.0;
-    if (isnan(w.y)) w.y = 0.0;
-    if (isnan(w.z)) w.z = 0.0;
-    *theta = th;
-    return w;
-}
-// |(A x - B)_e|^2 of edge e = (i, j): sum over the coordinates of ((x_j - x_i)_c - B_e,c)^2, node 0 grounded (its x counts as 0)
-__device__ __forceinline__ double edge_residual_sq(const double* x, const double* B, const int32_t* ii, const int32_t* jj, int64_t e) {
-    const int i = ii[e], j = jj[e];
-    double s = 0.0;
-    for (int c = 0; c < 3; ++c) {
-        const double ax = (j > 0 ? x[3 * j + c] : 0.0) - (i > 0 ? x[3 * i + c] : 0.0);
-        const double d = ax - B[3 * e + c];
-        s += d * d;
-    }
-    return s;
 }
 
 }  // namespace desc

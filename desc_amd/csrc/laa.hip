@@ -22,35 +22,14 @@ namespace desc {
 namespace {
 
 // ---- per-edge / per-node maps ------------------------------------------------------------
-// R2Q.m:9-12 for a column-major 3x3 block (optionally transposed)
-__device__ __forceinline__ Quat r2q(const double* R, bool transpose) {
-    const double r11 = R[0], r22 = R[4], r33 = R[8];
-    double r32 = R[5], r23 = R[7], r13 = R[6], r31 = R[2], r21 = R[1], r12 = R[3];      // (r,c) at r + 3c
-    if (transpose) { double t; t = r32; r32 = r23; r23 = t; t = r13; r13 = r31; r31 = t; t = r21; r21 = r12; r12 = t; }
-    Quat q;
-    q.a = (r11 + r22 + r33 - 1.0) / 2.0; q.x = (r32 - r23) / 2.0; q.y = (r13 - r31) / 2.0; q.z = (r21 - r12) / 2.0;
-    q.a = sqrt((q.a + 1.0) / 2.0);
-    q.x = (q.x / q.a) / 2.0; q.y = (q.y / q.a) / 2.0; q.z = (q.z / q.a) / 2.0;
-    return q;
-}
 __global__ void k_r2q(const double* R, Quat* Q, int64_t count, int transpose) {
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (int64_t)gridDim.x * blockDim.x) Q[t] = r2q(R + 9 * t, transpose);
 }
 // q2R.m
 __global__ void k_q2r(const Quat* Q, double* R, int64_t n) {
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
-        const Quat q = Q[t];
-        double M[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        const double c2 = q.a;
-        if (fabs(fabs(c2) - 1.0) > 1e-12) {
-            const double s2 = sqrt(q.x * q.x + q.y * q.y + q.z * q.z);
-            const double s = 2.0 * s2 * c2, c = 2.0 * c2 * c2 - 1.0, cc = 1.0 - c;
-            const double n1 = q.x / s2, n2 = q.y / s2, n3 = q.z / s2;
-            const double n12 = n1 * n2 * cc, n23 = n2 * n3 * cc, n31 = n3 * n1 * cc, n1s = n1 * s, n2s = n2 * s, n3s = n3 * s;
-            M[0] = c + n1 * n1 * cc; M[3] = n12 - n3s;        M[6] = n31 + n2s;        // column-major: (r,c) at r + 3c
-            M[1] = n12 + n3s;        M[4] = c + n2 * n2 * cc; M[7] = n23 - n1s;
-            M[2] = n31 - n2s;        M[5] = n23 + n1s;        M[8] = c + n3 * n3 * cc;
-        }
+        double M[9];
+        q2r(Q[t], M);
         for (int k = 0; k < 9; ++k) R[9 * t + k] = M[k];
     }
 }
@@ -58,19 +37,9 @@ __global__ void k_q2r(const Quat* Q, double* R, int64_t n) {
 // Weighted_LAA.m:9-37: residual quaternion w = -(conj(Qj) (QQ Qi)), B = log map (3 per edge)
 __global__ void k_edge_log(const Quat* Q, const Quat* QQ, const int32_t* ii, const int32_t* jj, double* B, int64_t m) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < m; e += (int64_t)gridDim.x * blockDim.x) {
-        const Quat qq = QQ[e], qi = Q[ii[e]], qj = Q[jj[e]];
-        const Quat w = qmul(qq, qi);
-        const Quat v = qmul(Quat{-qj.a, qj.x, qj.y, qj.z}, w);                       // inv(Qj) * w as written in the reference
-        const double s2 = sqrt(v.x * v.x + v.y * v.y + v.z * v.z);
-        double v1 = 2.0 * atan2(s2, v.a);
-        if (v1 < -M_PI) v1 += 2.0 * M_PI;
-        if (v1 >= M_PI) v1 -= 2.0 * M_PI;
-        const double f = v1 / s2;
-        double b1 = v.x * f, b2 = v.y * f, b3 = v.z * f;
-        if (isnan(b1)) b1 = 0.0;                                                     // :35
-        if (isnan(b2)) b2 = 0.0;
-        if (isnan(b3)) b3 = 0.0;
-        B[3 * e] = b1; B[3 * e + 1] = b2; B[3 * e + 2] = b3;
+        double b[3];
+        edge_log(QQ[e], Q[ii[e]], Q[jj[e]], b);
+        B[3 * e] = b[0]; B[3 * e + 1] = b[1]; B[3 * e + 2] = b[2];
     }
 }
 
@@ -83,16 +52,10 @@ __global__ __launch_bounds__(256) void k_rhs(const int32_t* rowptr, const int32_
     const int row0 = (blockIdx.x * 256 + threadIdx.x) >> 4, nrows = (gridDim.x * 256) >> 4;
     for (int vb = row0 - (row0 % 4); vb < n; vb += nrows) {
         const int v = vb + (row0 % 4);
-        double a0 = 0, a1 = 0, a2 = 0, dg = 0;
-        if (v < n)
-            for (int t = rowptr[v] + l16; t < rowptr[v + 1]; t += 16) {
-                const int e = eid[t];
-                const double w2 = wts[e] * wts[e], sg = (double)sgn[t];
-                a0 += sg * w2 * B[3 * (int64_t)e]; a1 += sg * w2 * B[3 * (int64_t)e + 1]; a2 += sg * w2 * B[3 * (int64_t)e + 2];
-                dg += w2;
-            }
-        a0 = group16_sum(a0); a1 = group16_sum(a1); a2 = group16_sum(a2); dg = group16_sum(dg);
-        if (v < n && l16 == 0) { rhs[3 * v] = a0; rhs[3 * v + 1] = a1; rhs[3 * v + 2] = a2; diag[v] = dg; }
+        double a[3], dg;
+        const bool on = v < n;
+        rhs_row16(eid, sgn, wts, B, on ? rowptr[v] : 0, on ? rowptr[v + 1] : 0, l16, a, &dg);
+        if (v < n && l16 == 0) { rhs[3 * v] = a[0]; rhs[3 * v + 1] = a[1]; rhs[3 * v + 2] = a[2]; diag[v] = dg; }
     }
 }
 
@@ -105,18 +68,11 @@ __global__ __launch_bounds__(256) void k_cg_lap(const int32_t* rowptr, const int
     const int row0 = (blockIdx.x * 256 + threadIdx.x) >> 4, nrows = (gridDim.x * 256) >> 4;
     for (int vb = row0 - (row0 % 4); vb < n; vb += nrows) {
         const int v = vb + (row0 % 4);
-        double a0 = 0, a1 = 0, a2 = 0;
-        if (v < n && v > 0) {
-            const double p0 = p[3 * v], p1 = p[3 * v + 1], p2 = p[3 * v + 2];
-            for (int t = rowptr[v] + l16; t < rowptr[v + 1]; t += 16) {
-                const int u = adj[t];
-                const int64_t e = eid[t];
-                const double w0 = W3 ? w[3 * e] : w[e] * w[e], w1 = W3 ? w[3 * e + 1] : w0, w2 = W3 ? w[3 * e + 2] : w0;
-                a0 += w0 * (p0 - p[3 * u]); a1 += w1 * (p1 - p[3 * u + 1]); a2 += w2 * (p2 - p[3 * u + 2]);
-            }
-        }
-        a0 = group16_sum(a0); a1 = group16_sum(a1); a2 = group16_sum(a2);
-        if (v < n && l16 == 0) { q[3 * v] = a0; q[3 * v + 1] = a1; q[3 * v + 2] = a2; }
+        double a[3];
+        int t0 = 0, t1 = 0;
+        if (v < n && v > 0) { t0 = rowptr[v]; t1 = rowptr[v + 1]; }                     // node 0 is the grounded one: its row stays empty
+        lap_row16<W3>(adj, eid, w, p, v, t0, t1, l16, a);
+        if (v < n && l16 == 0) { q[3 * v] = a[0]; q[3 * v + 1] = a[1]; q[3 * v + 2] = a[2]; }
     }
 }
 // one workgroup: column-wise dot products of two n x 3 arrays (fixed order -> reproducible)
@@ -126,12 +82,6 @@ __global__ __launch_bounds__(256) void k_cg_dot(const double* a, const double* b
     block_reduce<3, 0>(s, out3);
 }
 __device__ __forceinline__ bool cg_breaks(double pq, double rz) { return !isfinite(pq) || !isfinite(rz) || (pq <= 0.0 && rz > 0.0); }
-// z = r / diag (0 at the grounded node and where the diagonal is not positive)
-template <bool W3>
-__device__ __forceinline__ double jacobi(const double* diag, int v, int c, double rv) {
-    const double d = diag[W3 ? 3 * v + c : v];
-    return (v > 0 && d > 0) ? rv / d : 0.0;
-}
 // x = 0, r = rhs (node 0 zeroed), z = r/diag, p = z
 template <bool W3>
 __global__ void k_cg_init(CgScal* sc, const double* rhs, const double* diag, double* x, double* r, double* z, double* p, int n) {
@@ -149,7 +99,7 @@ __global__ void k_cg_update(CgScal* sc, const double* diag, const double* p, con
     double al[3];
     for (int c = 0; c < 3; ++c) {
         const bool brk = TRACK && (sc->bad[c] || cg_breaks(sc->pq[c], sc->rz[c]));
-        al[c] = (!brk && sc->pq[c] > 0) ? sc->rz[c] / sc->pq[c] : 0.0;
+        al[c] = brk ? 0.0 : cg_alpha(sc->rz[c], sc->pq[c]);
     }
     if (TRACK) {
         __syncthreads();
@@ -166,7 +116,7 @@ __global__ void k_cg_update(CgScal* sc, const double* diag, const double* p, con
 // beta = rz_new/rz ; p = z + beta p
 __global__ void k_cg_dir(const CgScal* sc, const double* z, double* p, int n) {
     double be[3];
-    for (int c = 0; c < 3; ++c) be[c] = sc->rz[c] > 0 ? sc->rz_new[c] / sc->rz[c] : 0.0;
+    for (int c = 0; c < 3; ++c) be[c] = cg_beta(sc->rz[c], sc->rz_new[c]);
     for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x)
         for (int c = 0; c < 3; ++c) p[3 * v + c] = z[3 * v + c] + be[c] * p[3 * v + c];
 }
@@ -184,25 +134,17 @@ __global__ __launch_bounds__(256) void k_node_update(const double* x, Quat* Q, d
                                                      int n, double* score_partial) {
     double sc = 0.0;
     for (int v = blockIdx.x * 256 + threadIdx.x; v < n; v += gridDim.x * 256) {
-        double theta;
-        const Quat w = qexp(x[3 * v], x[3 * v + 1], x[3 * v + 2], &theta);           // :42-46
+        const double theta = node_update(x + 3 * v, Q + v, Wv + 3 * v);          // :42-46
         if (v > 0) sc += theta;                                                       // :40 (rows 2:end)
-        Wv[3 * v] = w.x; Wv[3 * v + 1] = w.y; Wv[3 * v + 2] = w.z;
-        Q[v] = qmul(Q[v], w);
     }
-    sc = group_sum<64>(sc);                                                           // the score's order of summation: not to be moved
     __shared__ double sh[4];
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = sc;
-    __syncthreads();
-    if (threadIdx.x == 0) score_partial[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    const double tot = score_chunk_sum(sc, sh);
+    if (threadIdx.x == 0) score_partial[blockIdx.x] = tot;
 }
 // DESC.m:298-303
 __global__ void k_weights(const double* RS, double* wts, int64_t m, double thresh, double wmax, double wmin) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < m; e += (int64_t)gridDim.x * blockDim.x) {
-        double w = 1.0 / pow(RS[e], 0.75);
-        if (w > wmax) w = wmax;
-        if (RS[e] > thresh) w = wmin;
-        wts[e] = w;
+        wts[e] = laa_weight(RS[e], thresh, wmax, wmin);
     }
 }
 
@@ -238,15 +180,15 @@ __global__ __launch_bounds__(256) void k_qcollect(const double* x, int64_t m, do
 double matlab_quantile(hvec<double>& x, double p) {
     const size_t n = x.size();
     if (n == 0) return NAN;
-    double pos = p * (double)n + 0.5;                    // 1-based fractional index
-    if (pos <= 1.0) return *std::min_element(x.begin(), x.end());
-    if (pos >= (double)n) return *std::max_element(x.begin(), x.end());
-    const size_t lo = (size_t)std::floor(pos) - 1;       // 0-based
-    const double fr = pos - std::floor(pos);
+    int64_t k0 = 0; double fr = 0.0;
+    const int where = hazen_position((int64_t)n, p, &k0, &fr);
+    if (where == HAZEN_MIN) return *std::min_element(x.begin(), x.end());
+    if (where == HAZEN_MAX) return *std::max_element(x.begin(), x.end());
+    const size_t lo = (size_t)k0;                        // 0-based
     std::nth_element(x.begin(), x.begin() + lo, x.end());
     const double a = x[lo];
     const double b = *std::min_element(x.begin() + lo + 1, x.end());
-    return a + fr * (b - a);
+    return hazen_interp(a, b, fr);
 }
 
 // quantile(x, p) of a device vector, MATLAB's definition (the same order statistics as matlab_quantile above);
@@ -259,12 +201,11 @@ int device_quantile(const double* d_x, int64_t m, double p, double* d_mm, unsign
     DESC_HIP(hipMemcpy(mm, d_mm, sizeof mm, hipMemcpyDeviceToHost));
     double lo = INFINITY, hi = -INFINITY;
     for (int b = 0; b < 64; ++b) { lo = std::min(lo, mm[2 * b]); hi = std::max(hi, mm[2 * b + 1]); }
-    const double pos = p * (double)m + 0.5;                 // 1-based fractional index
-    if (pos <= 1.0) { *result = lo; return DESC_OK; }
-    if (pos >= (double)m) { *result = hi; return DESC_OK; }
-    if (!(hi > lo)) { *result = lo; return DESC_OK; }
-    const int64_t k0 = (int64_t)std::floor(pos) - 1;        // 0-based rank of the lower order statistic; the upper one is k0 + 1
-    const double fr = pos - std::floor(pos);
+    int64_t k0 = 0; double fr = 0.0;                        // 0-based rank of the lower order statistic; the upper one is k0 + 1
+    const int where = hazen_position(m, p, &k0, &fr);
+    if (where == HAZEN_MIN) { *result = lo; return DESC_OK; }
+    if (where == HAZEN_MAX) { *result = hi; return DESC_OK; }
+    if (hazen_flat(lo, hi)) { *result = lo; return DESC_OK; }
     const double scale = (double)QBINS / (hi - lo) * (1.0 - 1e-12);
     DESC_HIP(hipMemset(d_hist, 0, sizeof(unsigned) * (QBINS + 1)));
     hipLaunchKernelGGL(k_qhist, dim3(g), dim3(256), 0, 0, d_x, m, lo, scale, d_hist);
@@ -291,7 +232,7 @@ int device_quantile(const double* d_x, int64_t m, double p, double* d_mm, unsign
     // cand = bin b0 (ranks base0 ...) followed, if different, by bin b1 (which starts at rank >= k0 + 1)
     const double a = cand[(size_t)(k0 - base0)];
     const double bnext = (b1 == b0) ? cand[(size_t)(k0 + 1 - base0)] : cand[(size_t)hist[b0] + 0 + (size_t)0];
-    *result = a + fr * (bnext - a);
+    *result = hazen_interp(a, bnext, fr);
     return DESC_OK;
 }
 
@@ -354,7 +295,7 @@ int laa_pcg(LaaSolver& L, const double* w, const double* rhs, const double* diag
             DESC_HIP(hipMemcpy(&hs, sc, sizeof hs, hipMemcpyDeviceToHost));
             done = true;
             for (int c = 0; c < 3; ++c)
-                if (act[c] && !hs.bad[c] && hs.rnorm[c] > 1e-26 * hs.bnorm[c] && hs.rnorm[c] > 1e-300) done = false;
+                if (act[c] && !hs.bad[c] && cg_unfinished(hs.rnorm[c], hs.bnorm[c])) done = false;
             if (done || k == cg_max) break;
         }
     }

@@ -17,7 +17,7 @@ namespace {
 __global__ void k_rsvec(const double* Wv, const double* B, const int32_t* ii, const int32_t* jj, const double* S, double* RS,
                         int64_t m, double lam) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < m; e += (int64_t)gridDim.x * blockDim.x)
-        RS[e] = (1.0 - lam) * (sqrt(edge_residual_sq(Wv, B, ii, jj, e)) / M_PI) + lam * S[e];
+        RS[e] = rsvec_value(Wv, B, ii, jj, S, e, lam);
 }
 
 }  // namespace

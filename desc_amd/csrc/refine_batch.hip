@@ -1,0 +1,506 @@
+// The DESC refinement tail (Algorithms/DESC.m:265-313) for many small problems in one launch (desc_refine_batch_*): the last stage of the
+// "DESC" row of Demo/compare_algorithms.m for a whole Monte-Carlo batch.
+//
+// refine.hip runs one problem per call with a host-driven loop: seven launches per PCG step, a blocking read-back of the PCG scalars
+// every 25 steps, one for the score and two or three for the quantile, 10-30 times over -- a few thousand launches and dozens of host
+// round trips for a 100-node graph.  Here ONE launch refines all B problems: one workgroup of 256 threads per problem runs the whole
+// loop of desc_refine_run_dev for its problem, from Q = R2Q(R_init) to q2R, without a host round trip.
+//
+// State.  The per-node arrays (Q, the PCG's x r z p q, rhs, diag, the vector part Wv of the update) live in LDS, 26 doubles per node.
+// The LDS of a launch is sized from the largest problem of the batch; a problem addresses it with its own n, so nothing it computes
+// depends on that size.  The per-edge arrays (QQ, B, w, RS and the inputs S, ii, jj, rij) lie in global memory at the problem's edge
+// offset; the CSR (local ids) and the incidence sign per slot come from the host (batch_csr.h).
+//
+// Arithmetic and summation orders.  Every per-element expression is the text of laa_math.h, which the kernels of the single path call
+// too.  The single path's reductions all fit one workgroup and are reproduced in their orders: a CSR row by the 16 lanes of a DPP row
+// (rhs_row16 / lap_row16), the PCG's dot products by k_cg_dot's loop and block_reduce<3, 0>, the score in 256-row chunks
+// (score_chunk_sum) added in ascending order from 0.0.  The quantile's two order statistics are found exactly by a radix select over
+// the 64-bit order key (8-bit digits, integer histogram in LDS); an order statistic is a value, so device_quantile's interpolation of
+// them gives the same threshold.  The result is desc_refine_run's bit for bit.
+//
+// Control flow.  Every thread takes every decision (the stop rule, the PCG probe, the selected digit) from the same LDS values with the
+// same instructions, and the integers that steer loops and barriers go through readfirstlane: the branches around the barriers are
+// uniform.  Every loop is bounded by max_iters, cg_max, a row length, m or the 8 digit passes.  There is no grid-wide barrier, no
+// spinning on memory, nothing between workgroups and no floating-point atomic.  A problem whose selection finds no candidate or whose
+// score is not finite writes its status word and leaves.
+//
+// Composition independence.  Problem b's workgroup reads b's arrays and writes b's ranges; thread roles, loop bounds and summation
+// orders are functions of b's n, m and CSR alone.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "batch_csr.h"
+#include "device_utils.h"
+#include "laa_math.h"
+#include "mst_key.h"
+
+namespace desc {
+namespace {
+
+constexpr int RB_LDS_BYTES = 160 * 1024;               // what one workgroup may declare on gfx950
+constexpr int RB_NODE_DOUBLES = 4 + 6 * 3 + 1 + 3;     // Q; x r z p q rhs; diag; Wv
+constexpr int RB_STATIC_BYTES = 8 * 1024;              // set aside for the kernel's fixed LDS: block_reduce's tree (6 KiB), the histogram (1 KiB), scalars
+constexpr int REFINE_BATCH_MAX_N = (RB_LDS_BYTES - RB_STATIC_BYTES) / (8 * RB_NODE_DOUBLES);    // 748
+static_assert(REFINE_BATCH_MAX_N >= 278, "the cap of DESC_batch is the eigen-solve's");
+constexpr int RB_PROBE = 25;                           // laa_step's probe interval
+constexpr int RB_QR = 8;                               // entries of the quant_ratio table (the recurrence is constant after five steps)
+
+inline size_t rb_lds_bytes(int n) { return sizeof(double) * (size_t)RB_NODE_DOUBLES * (size_t)n; }
+
+struct RbProb { int32_t n, m; int64_t node_off, edge_off; };
+// status: 0 done, 1 the selection found no candidate, 2 a score that is not finite, -1 the workgroup never finished
+struct RbInfo { int32_t iters, cg_total, cg_unconverged, status; double score, worst_sq; };
+
+struct RbArgs {
+    const RbProb* prob;
+    const int32_t* rowptr;      // problem b's n_b + 1 row starts at node_off[b] + b, counted inside the problem
+    const int32_t* adj;         // 2 m_b local neighbour ids at 2 edge_off[b]
+    const int32_t* adj_eid;     // 2 m_b local edge ids
+    const int8_t* sgn;          // 2 m_b incidence signs (Build_Amatrix.m:10): -1 where the row's node is the edge's smaller endpoint
+    const int32_t *ii, *jj;     // m_b local endpoints at edge_off[b]
+    const double* rij;          // 9 m_b at 9 edge_off[b]
+    const double* S;            // m_b at edge_off[b]
+    const double* thresh0;      // per problem: max(S), the initial threshold
+    const double* R_init;       // 9 n_b at 9 node_off[b]
+    double* R_out;
+    Quat* QQ;                   // m_b
+    double *B, *w, *RS;         // 3 m_b, m_b, m_b
+    RbInfo* info;
+    double stop_threshold;
+    int32_t max_iters;
+    double qr[RB_QR];           // quant_ratio of step 1, 2, ...: the host's recurrence max(0.8, q - 0.05)
+};
+
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ double key_value(unsigned long long k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k & ~(1ull << 63)) : ~k));
+}
+
+// k_cg_dot in place: column-wise dot products of two n x 3 arrays into out3 (LDS).  Ends with a barrier.
+__device__ __forceinline__ void rb_dot(const double* a, const double* b, int n, double* out3) {
+    double s[3] = {0, 0, 0};
+    for (int v = threadIdx.x; v < n; v += 256) for (int c = 0; c < 3; ++c) s[c] += a[3 * v + c] * b[3 * v + c];
+    block_reduce<3, 0>(s, out3);
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void k_refine_batch(RbArgs a) {
+    extern __shared__ double rb_lds[];
+    __shared__ double cgs[15];                          // rz, rz_new, pq, bnorm, rnorm: CgScal's doubles
+    __shared__ double sh4[4], mm[8];
+    __shared__ unsigned hist[256];
+    __shared__ unsigned cnt_le;
+    __shared__ unsigned long long key_gt;
+    const int b = blockIdx.x, tid = threadIdx.x, l16 = tid & 15, row = tid >> 4;
+    const RbProb pd = a.prob[b];
+    const int n = uni(pd.n), m = uni(pd.m);
+    const int32_t* rowptr = a.rowptr + pd.node_off + b;
+    const int32_t* adj = a.adj + 2 * pd.edge_off;
+    const int32_t* eid = a.adj_eid + 2 * pd.edge_off;
+    const int8_t* sgn = a.sgn + 2 * pd.edge_off;
+    const int32_t* ii = a.ii + pd.edge_off;
+    const int32_t* jj = a.jj + pd.edge_off;
+    const double* S = a.S + pd.edge_off;
+    Quat* QQ = a.QQ + pd.edge_off;
+    double* B = a.B + 3 * pd.edge_off;
+    double* w = a.w + pd.edge_off;
+    double* RS = a.RS + pd.edge_off;
+    Quat* Q = (Quat*)rb_lds;
+    double* x = rb_lds + 4 * n;
+    double* r = x + 3 * n;
+    double* z = r + 3 * n;
+    double* p = z + 3 * n;
+    double* q = p + 3 * n;
+    double* rhs = q + 3 * n;
+    double* diag = rhs + 3 * n;
+    double* Wv = diag + n;
+    double *rz = cgs, *rz_new = cgs + 3, *pq = cgs + 6, *bnorm = cgs + 9, *rnorm = cgs + 12;
+
+    // ---- laa_setup: Q = R2Q(R_init), QQ = R2Q(permute(RijMat, [2,1,3])); the initial weights (DESC.m:274-282)
+    for (int v = tid; v < n; v += 256) Q[v] = r2q(a.R_init + 9 * (pd.node_off + v), false);
+    {
+        const double* rij = a.rij + 9 * pd.edge_off;
+        const double thresh0 = a.thresh0[b];
+        for (int e = tid; e < m; e += 256) { QQ[e] = r2q(rij + 9 * (int64_t)e, true); w[e] = laa_weight(S[e], thresh0, 1e4, 1e-4); }
+    }
+    __syncthreads();
+
+    const double stop = a.stop_threshold;
+    const int max_iters = a.max_iters;
+    const int cg_max = min(20000, 20 * n + 200);
+    double score = INFINITY, worst_sq = 0.0;
+    int it = 1, cg_total = 0, cg_unconverged = 0, status = 0;
+    while (uni(score > stop && it < max_iters)) {                                           // DESC.m:287
+        const double lam = 1.0 / (it + 1);
+        // ---- Weighted_LAA: the edge log map, the normal equations
+        for (int e = tid; e < m; e += 256) edge_log(QQ[e], Q[ii[e]], Q[jj[e]], B + 3 * (int64_t)e);
+        __syncthreads();
+        for (int vb = 0; vb < n; vb += 16) {
+            const int v = vb + row;
+            const bool on = v < n;
+            double s3[3], dg;
+            rhs_row16(eid, sgn, w, B, on ? rowptr[v] : 0, on ? rowptr[v + 1] : 0, l16, s3, &dg);
+            if (on && l16 == 0) { rhs[3 * v] = s3[0]; rhs[3 * v + 1] = s3[1]; rhs[3 * v + 2] = s3[2]; diag[v] = dg; }
+        }
+        __syncthreads();
+        // ---- laa_pcg<false, false>: x = 0, r = rhs (node 0 zeroed), z = r / diag, p = z
+        for (int v = tid; v < n; v += 256)
+            for (int c = 0; c < 3; ++c) {
+                const double rv = v > 0 ? rhs[3 * v + c] : 0.0;
+                const double zv = jacobi<false>(diag, v, c, rv);
+                x[3 * v + c] = 0.0; r[3 * v + c] = rv; z[3 * v + c] = zv; p[3 * v + c] = zv;
+            }
+        __syncthreads();
+        rb_dot(r, z, n, rz);
+        rb_dot(r, r, n, bnorm);
+        int done = 0, k = 0;
+        for (k = 1; k <= cg_max; ++k) {
+            for (int vb = 0; vb < n; vb += 16) {
+                const int v = vb + row;
+                const bool on = v < n && v > 0;
+                double s3[3];
+                lap_row16<false>(adj, eid, w, p, v, on ? rowptr[v] : 0, on ? rowptr[v + 1] : 0, l16, s3);
+                if (v < n && l16 == 0) { q[3 * v] = s3[0]; q[3 * v + 1] = s3[1]; q[3 * v + 2] = s3[2]; }
+            }
+            __syncthreads();
+            rb_dot(p, q, n, pq);
+            double al[3];
+            for (int c = 0; c < 3; ++c) al[c] = cg_alpha(rz[c], pq[c]);
+            for (int v = tid; v < n; v += 256)
+                for (int c = 0; c < 3; ++c) {
+                    const double xv = x[3 * v + c] + al[c] * p[3 * v + c];
+                    const double rv = r[3 * v + c] - al[c] * q[3 * v + c];
+                    x[3 * v + c] = xv; r[3 * v + c] = rv;
+                    z[3 * v + c] = jacobi<false>(diag, v, c, rv);
+                }
+            __syncthreads();
+            rb_dot(r, z, n, rz_new);
+            double be[3];
+            for (int c = 0; c < 3; ++c) be[c] = cg_beta(rz[c], rz_new[c]);
+            for (int v = tid; v < n; v += 256)
+                for (int c = 0; c < 3; ++c) p[3 * v + c] = z[3 * v + c] + be[c] * p[3 * v + c];
+            __syncthreads();                                                                // every thread has read rz
+            if (tid < 3) rz[tid] = rz_new[tid];
+            if (k % RB_PROBE == 0 || k == cg_max) {                                          // convergence probe: |r| <= 1e-13 |b|
+                rb_dot(r, r, n, rnorm);
+                int fin = 1;
+                for (int c = 0; c < 3; ++c) if (cg_unfinished(rnorm[c], bnorm[c])) fin = 0;
+                done = uni(fin);
+                if (done || k == cg_max) break;
+            }
+        }
+        __syncthreads();                                                                    // the last roll of rz is behind every thread
+        cg_total += min(k, cg_max);                                                         // the true count rounded up to the probe interval
+        for (int c = 0; c < 3; ++c)
+            if (bnorm[c] > 0) { const double ratio = rnorm[c] / bnorm[c]; if (worst_sq < ratio) worst_sq = ratio; }
+        if (!done) ++cg_unconverged;
+        // ---- Weighted_LAA.m:40-50: exp map, Q <- Q * W, the score in chunks of 256 rows
+        double tot = 0.0;
+        for (int base = 0; base < n; base += 256) {
+            const int v = base + tid;
+            double sc = 0.0;
+            if (v < n) {
+                const double theta = node_update(x + 3 * v, Q + v, Wv + 3 * v);
+                if (v > 0) sc += theta;
+            }
+            tot += score_chunk_sum(sc, sh4);
+            __syncthreads();
+        }
+        score = tot / (double)n;
+        if (uni(!isfinite(score))) { status = 2; break; }
+        // ---- residuals and new weights (DESC.m:289-303)
+        double lo = INFINITY, hi = -INFINITY;
+        for (int e = tid; e < m; e += 256) {
+            const double v = rsvec_value(Wv, B, ii, jj, S, e, lam);
+            RS[e] = v; lo = fmin(lo, v); hi = fmax(hi, v);
+        }
+        for (int off = 32; off >= 1; off >>= 1) { lo = fmin(lo, __shfl_xor(lo, off)); hi = fmax(hi, __shfl_xor(hi, off)); }
+        if ((tid & 63) == 0) { mm[tid >> 6] = lo; mm[4 + (tid >> 6)] = hi; }
+        __syncthreads();                                                                    // RS, the wave extrema
+        lo = fmin(fmin(mm[0], mm[1]), fmin(mm[2], mm[3])); hi = fmax(fmax(mm[4], mm[5]), fmax(mm[6], mm[7]));
+        const double qratio = a.qr[min(it - 1, RB_QR - 1)];
+        int64_t k0 = 0; double fr = 0.0, thresh;
+        const int where = uni(hazen_position((int64_t)m, qratio, &k0, &fr));
+        if (where == HAZEN_MIN) thresh = lo;
+        else if (where == HAZEN_MAX) thresh = hi;
+        else if (uni(hazen_flat(lo, hi))) thresh = lo;
+        else {
+            // the order statistic of rank k0: radix select over the order key, most significant digit first
+            unsigned long long prefix = 0;
+            unsigned rank = (unsigned)k0;
+            int found = 1;
+            for (int pass = 7; pass >= 0; --pass) {
+                const int shift = 8 * pass;
+                hist[tid] = 0;
+                __syncthreads();
+                for (int e = tid; e < m; e += 256) {
+                    const unsigned long long key = order_key(RS[e]);
+                    if (pass == 7 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(unsigned)(key >> shift) & 255u], 1u);
+                }
+                __syncthreads();
+                unsigned acc = 0; int d = -1;
+                for (int bin = 0; bin < 256; ++bin) {
+                    const unsigned hcount = hist[bin];
+                    if (d < 0) { if (acc + hcount > rank) d = bin; else acc += hcount; }
+                }
+                d = uni(d);
+                __syncthreads();                                                            // hist is free again
+                if (d < 0) { found = 0; break; }
+                rank -= uni((int)acc);
+                prefix |= (unsigned long long)d << shift;
+            }
+            if (!found) { status = 1; break; }
+            // rank k0 + 1: the same value if more than k0 + 1 keys are <= it, else the smallest key above it
+            if (tid == 0) { cnt_le = 0; key_gt = ~0ull; }
+            __syncthreads();
+            unsigned c_le = 0; unsigned long long k_gt = ~0ull;
+            for (int e = tid; e < m; e += 256) {
+                const unsigned long long key = order_key(RS[e]);
+                if (key <= prefix) ++c_le; else if (key < k_gt) k_gt = key;
+            }
+            atomicAdd(&cnt_le, c_le);
+            atomicMin(&key_gt, k_gt);
+            __syncthreads();
+            const unsigned le = cnt_le;
+            const unsigned long long next = key_gt;
+            __syncthreads();                                                                // cnt_le, key_gt are free again
+            unsigned long long upper = prefix;
+            if (!uni(le >= (unsigned)k0 + 2u)) {
+                if (uni(next == ~0ull)) { status = 1; break; }
+                upper = next;
+            }
+            thresh = hazen_interp(key_value(prefix), key_value(upper), fr);
+        }
+        for (int e = tid; e < m; e += 256) w[e] = laa_weight(RS[e], thresh, 1e4, 1e-4);
+        __syncthreads();
+        ++it;
+    }
+    if (status) {                                                                           // the same in every thread
+        if (tid == 0) { RbInfo o{}; o.status = status; o.iters = it - 1; o.score = score; a.info[b] = o; }
+        return;
+    }
+    // ---- laa_finish: q2R.m of every node
+    for (int v = tid; v < n; v += 256) {
+        double M[9];
+        q2r(Q[v], M);
+        double* o = a.R_out + 9 * (pd.node_off + v);
+        for (int c = 0; c < 9; ++c) o[c] = M[c];
+    }
+    if (tid == 0) {
+        RbInfo o;
+        o.iters = it - 1; o.cg_total = cg_total; o.cg_unconverged = cg_unconverged; o.status = 0; o.score = score; o.worst_sq = worst_sq;
+        a.info[b] = o;
+    }
+}
+
+}  // namespace
+}  // namespace desc
+
+using namespace desc;
+
+struct desc_refine_batch : desc::BatchCsr {  // offsets and the per-problem CSR (local ids): batch_csr.h
+    int device = 0;
+    hipStream_t stream = nullptr;
+    DevArena mem;
+    RbProb* d_prob = nullptr;
+    int32_t *d_rowptr = nullptr, *d_adj = nullptr, *d_adj_eid = nullptr, *d_ii = nullptr, *d_jj = nullptr;
+    int8_t* d_sgn = nullptr;
+    double *d_rij = nullptr, *d_S = nullptr, *d_thresh0 = nullptr, *d_Rinit = nullptr, *d_Rout = nullptr, *d_B = nullptr, *d_w = nullptr, *d_RS = nullptr;
+    Quat* d_QQ = nullptr;
+    RbInfo* d_info = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;        // around the launch of a run; made once in create
+    double ms_structure = 0, ms_upload = 0;
+};
+
+namespace {
+
+void rb_free(desc_refine_batch* h) {
+    if (!h) return;
+    if (h->stream) { (void)hipSetDevice(h->device); (void)hipStreamSynchronize(h->stream); }
+    h->mem.release();
+    if (h->ev0) (void)hipEventDestroy(h->ev0);
+    if (h->ev1) (void)hipEventDestroy(h->ev1);
+    if (h->stream) stream_release(h->stream);
+    delete h;
+}
+
+template <class T>
+int rb_upload(desc_refine_batch* h, T** dst, const T* src, size_t n) {
+    int rc = h->mem.alloc(dst, n); if (rc) return rc;
+    if (n) DESC_HIP(hipMemcpyAsync(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice, h->stream));
+    return DESC_OK;
+}
+
+// validation, offsets and the per-problem CSR: no device
+int rb_host_part(const desc_problem* probs, int32_t count, desc_refine_batch* h) {
+    return batch_csr_host(probs, count, [](int32_t b, const desc_problem& q) -> int {
+        if (q.n > REFINE_BATCH_MAX_N)
+            return fail(DESC_ERR_INVALID, "problem %d: n = %lld exceeds %d (the per-node state of the refinement must fit the LDS of one workgroup): solve it with DESC",
+                        b, (long long)q.n, REFINE_BATCH_MAX_N);
+        return DESC_OK;
+    }, h);
+}
+
+int rb_create(const desc_problem* probs, int32_t count, int32_t device, desc_refine_batch* h) {
+    auto t0 = std::chrono::steady_clock::now();
+    h->device = device;
+    int rc = rb_host_part(probs, count, h);
+    if (rc) return rc;
+    const size_t M = (size_t)h->M, N = (size_t)h->N;
+    hvec<int8_t> sgn(2 * M);                           // Build_Amatrix.m:10 per CSR slot: -1 at the smaller endpoint i, +1 at j
+    for (int32_t b = 0; b < count; ++b) {
+        const int32_t* rp = h->rowptr.data() + h->node_off[(size_t)b] + b;
+        const size_t so = 2 * (size_t)h->edge_off[(size_t)b];
+        for (int64_t v = 0; v < probs[b].n; ++v)
+            for (int32_t t = rp[v]; t < rp[v + 1]; ++t) sgn[so + (size_t)t] = v < h->adj[so + (size_t)t] ? -1 : +1;
+    }
+    h->ms_structure = ms_since(t0);
+    if (count == 0) return DESC_OK;
+
+    // ---- device: nothing above touched it
+    int ndev = desc_device_count();
+    if (ndev < 0) return ndev;
+    if (ndev == 0) return fail(DESC_ERR_HIP, "no HIP device visible: the batched refinement has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(DESC_ERR_INVALID, "device %d out of range (0..%d)", device, ndev - 1);
+    hipError_t he = hipSetDevice(device);
+    if (he == hipSuccess) he = stream_acquire(&h->stream);
+    if (he != hipSuccess) return fail(DESC_ERR_HIP, "device %d: %s", device, hipGetErrorString(he));
+    auto t1 = std::chrono::steady_clock::now();
+    hvec<RbProb> pr((size_t)count);
+    for (int32_t b = 0; b < count; ++b) pr[(size_t)b] = RbProb{(int32_t)probs[b].n, (int32_t)probs[b].m, h->node_off[(size_t)b], h->edge_off[(size_t)b]};
+    hvec<double> rij(9 * M);                           // all rotations in one copy
+    for (int32_t b = 0; b < count; ++b) std::memcpy(rij.data() + 9 * (size_t)h->edge_off[(size_t)b], probs[b].rij, sizeof(double) * 9 * (size_t)probs[b].m);
+    if ((rc = rb_upload(h, &h->d_prob, (const RbProb*)pr.data(), pr.size())) || (rc = rb_upload(h, &h->d_rowptr, (const int32_t*)h->rowptr.data(), h->rowptr.size())) ||
+        (rc = rb_upload(h, &h->d_adj, (const int32_t*)h->adj.data(), 2 * M)) || (rc = rb_upload(h, &h->d_adj_eid, (const int32_t*)h->adj_eid.data(), 2 * M)) ||
+        (rc = rb_upload(h, &h->d_sgn, (const int8_t*)sgn.data(), 2 * M)) || (rc = rb_upload(h, &h->d_ii, (const int32_t*)h->ii.data(), M)) ||
+        (rc = rb_upload(h, &h->d_jj, (const int32_t*)h->jj.data(), M)) || (rc = rb_upload(h, &h->d_rij, (const double*)rij.data(), 9 * M)))
+        return rc;
+    if ((rc = h->mem.alloc(&h->d_S, M)) || (rc = h->mem.alloc(&h->d_thresh0, (size_t)count)) || (rc = h->mem.alloc(&h->d_Rinit, 9 * N)) ||
+        (rc = h->mem.alloc(&h->d_Rout, 9 * N)) || (rc = h->mem.alloc(&h->d_QQ, M)) || (rc = h->mem.alloc(&h->d_B, 3 * M)) ||
+        (rc = h->mem.alloc(&h->d_w, M)) || (rc = h->mem.alloc(&h->d_RS, M)) || (rc = h->mem.alloc(&h->d_info, (size_t)count)))
+        return rc;
+    DESC_HIP(hipEventCreate(&h->ev0)); DESC_HIP(hipEventCreate(&h->ev1));      // rb_free destroys whichever exists
+    // the largest dynamic LDS any handle may ask for: the attribute belongs to the kernel, not to a handle, so it is never lowered
+    DESC_HIP(hipFuncSetAttribute((const void*)k_refine_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rb_lds_bytes(REFINE_BATCH_MAX_N)));
+    DESC_HIP(hipStreamSynchronize(h->stream));         // the staging vectors go out of scope below
+    h->ms_upload = ms_since(t1);
+    return DESC_OK;
+}
+
+int rb_run(desc_refine_batch* h, const double* s_vec, const double* R_init, double stop_threshold, int32_t max_iters, double* R_out,
+           desc_refine_info* infos, desc_refine_batch_timings* tm) {
+    auto t0 = std::chrono::steady_clock::now();
+    const int32_t count = h->count;
+    if (tm) { tm->ms_structure = h->ms_structure; tm->ms_upload = h->ms_upload; tm->ms_input = 0; tm->ms_refine = 0; tm->ms_total = 0; }
+    if (count == 0) { if (tm) tm->ms_total = ms_since(t0); return DESC_OK; }
+    if (!s_vec || !R_init || !R_out || !infos) return fail(DESC_ERR_INVALID, "s_vec, R_init, R_out or infos is NULL");
+    if (stop_threshold <= 0) stop_threshold = 1e-3;     // DESC.m:272
+    if (max_iters <= 0) max_iters = 100;
+    hvec<double> thresh0((size_t)count);                // DESC.m:274-282: quantile(S_vec, 1) = max
+    for (int32_t b = 0; b < count; ++b) {
+        double mx = -INFINITY;
+        for (int64_t e = h->edge_off[(size_t)b]; e < h->edge_off[(size_t)b + 1]; ++e) {
+            const double x = s_vec[e];
+            if (!(x >= 0) || !std::isfinite(x))
+                return fail(DESC_ERR_INVALID, "problem %d: S_vec holds a negative or non-finite entry (node %d)", b, (int)h->ii[(size_t)e]);
+            mx = std::max(mx, x);
+        }
+        thresh0[(size_t)b] = mx;
+        for (int64_t v = h->node_off[(size_t)b]; v < h->node_off[(size_t)b + 1]; ++v)
+            for (int c = 0; c < 9; ++c)
+                if (!std::isfinite(R_init[9 * v + c]))
+                    return fail(DESC_ERR_INVALID, "problem %d: R_init holds a non-finite entry (node %lld)", b, (long long)(v - h->node_off[(size_t)b]));
+    }
+    DESC_HIP(hipSetDevice(h->device));
+    const size_t M = (size_t)h->M, N = (size_t)h->N;
+    DESC_HIP(hipMemcpyAsync(h->d_S, s_vec, sizeof(double) * M, hipMemcpyHostToDevice, h->stream));
+    DESC_HIP(hipMemcpyAsync(h->d_Rinit, R_init, sizeof(double) * 9 * N, hipMemcpyHostToDevice, h->stream));
+    DESC_HIP(hipMemcpyAsync(h->d_thresh0, thresh0.data(), sizeof(double) * (size_t)count, hipMemcpyHostToDevice, h->stream));
+    DESC_HIP(hipMemsetAsync(h->d_info, 0xFF, sizeof(RbInfo) * (size_t)count, h->stream));    // status -1: the workgroup never finished
+    DESC_HIP(hipStreamSynchronize(h->stream));          // thresh0 goes out of use; the input's share of the wall clock
+    const double ms_input = ms_since(t0);
+    RbArgs a{};
+    a.prob = h->d_prob; a.rowptr = h->d_rowptr; a.adj = h->d_adj; a.adj_eid = h->d_adj_eid; a.sgn = h->d_sgn; a.ii = h->d_ii; a.jj = h->d_jj;
+    a.rij = h->d_rij; a.S = h->d_S; a.thresh0 = h->d_thresh0; a.R_init = h->d_Rinit; a.R_out = h->d_Rout; a.QQ = h->d_QQ; a.B = h->d_B;
+    a.w = h->d_w; a.RS = h->d_RS; a.info = h->d_info; a.stop_threshold = stop_threshold; a.max_iters = max_iters;
+    {
+        double quant_ratio = 1.0;                       // DESC.m:296: the recurrence of desc_refine_run_dev, in the host's arithmetic
+        const double quant_ratio_min = 0.8;
+        for (int i = 0; i < RB_QR; ++i) { quant_ratio = std::max(quant_ratio_min, quant_ratio - 0.05); a.qr[i] = quant_ratio; }
+        if (std::max(quant_ratio_min, quant_ratio - 0.05) != quant_ratio) return fail(DESC_ERR_STATE, "the quant_ratio recurrence has not settled");
+    }
+    const size_t lds = rb_lds_bytes(h->max_n);
+    if (lds + RB_STATIC_BYTES > (size_t)RB_LDS_BYTES) return fail(DESC_ERR_STATE, "LDS budget exceeded (%zu bytes)", lds);
+    const hipEvent_t e0 = h->ev0, e1 = h->ev1;
+    DESC_HIP(hipEventRecord(e0, h->stream));
+    hipLaunchKernelGGL(k_refine_batch, dim3((unsigned)count), dim3(256), lds, h->stream, a);
+    DESC_HIP(hipGetLastError());
+    DESC_HIP(hipEventRecord(e1, h->stream));
+    hvec<RbInfo> inf((size_t)count);
+    hvec<double> R(9 * N);
+    DESC_HIP(hipMemcpyAsync(inf.data(), h->d_info, sizeof(RbInfo) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
+    DESC_HIP(hipMemcpyAsync(R.data(), h->d_Rout, sizeof(double) * 9 * N, hipMemcpyDeviceToHost, h->stream));
+    DESC_HIP(hipStreamSynchronize(h->stream));
+    float ms = 0; DESC_HIP(hipEventElapsedTime(&ms, e0, e1));
+    for (int32_t b = 0; b < count; ++b) {
+        const RbInfo& g = inf[(size_t)b];
+        if (g.status == 1) return fail(DESC_ERR_STATE, "problem %d: the quantile selection found no candidate (step %d)", b, (int)g.iters + 1);
+        if (g.status == 2) return fail(DESC_ERR_STATE, "problem %d: the score of step %d is not finite", b, (int)g.iters + 1);
+        if (g.status) return fail(DESC_ERR_STATE, "problem %d: the refinement kernel did not finish (status %d)", b, (int)g.status);
+    }
+    std::memcpy(R_out, R.data(), sizeof(double) * 9 * N);
+    const double ms_total = ms_since(t0);
+    for (int32_t b = 0; b < count; ++b) {
+        const RbInfo& g = inf[(size_t)b];
+        desc_refine_info& o = infos[b];
+        o.iters = g.iters; o.cg_iters = g.cg_total; o.verbose = 0; o.cg_unconverged = g.cg_unconverged; o.score = g.score;
+        o.ms_total = ms_total; o.cg_residual = std::sqrt(g.worst_sq);       // sqrt is monotone: the largest |r|/|b| is the root of the largest ratio
+    }
+    if (tm) { tm->ms_input = ms_input; tm->ms_refine = ms; tm->ms_total = ms_total; }
+    return DESC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t desc_refine_batch_max_n(void) { return REFINE_BATCH_MAX_N; }
+
+int desc_refine_batch_create(const desc_problem* probs, int32_t count, int32_t device, desc_refine_batch** out) {
+    return no_throw("desc_refine_batch_create", [&]() -> int {
+        if (!out) return fail(DESC_ERR_INVALID, "out is NULL");
+        *out = nullptr;
+        if (count < 0 || (count > 0 && !probs)) return fail(DESC_ERR_INVALID, "NULL argument or negative count");
+        desc_refine_batch* h = new desc_refine_batch();
+        int rc;
+        try { rc = rb_create(probs, count, device, h); }
+        catch (...) { rb_free(h); throw; }
+        if (rc) { const std::string msg = desc_last_error(); rb_free(h); return fail(rc, "%s", msg.c_str()); }
+        *out = h;
+        return DESC_OK;
+    });
+}
+
+int desc_refine_batch_sizes(const desc_refine_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off) {
+    if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
+    if (count) *count = h->count;
+    if (node_off) std::copy(h->node_off.begin(), h->node_off.end(), node_off);
+    if (edge_off) std::copy(h->edge_off.begin(), h->edge_off.end(), edge_off);
+    return DESC_OK;
+}
+
+int desc_refine_batch_run(desc_refine_batch* h, const double* s_vec, const double* R_init, double stop_threshold, int32_t max_iters,
+                          double* R_out, desc_refine_info* infos, desc_refine_batch_timings* timings) {
+    return no_throw("desc_refine_batch_run", [&]() -> int {
+        if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
+        return rb_run(h, s_vec, R_init, stop_threshold, max_iters, R_out, infos, timings);
+    });
+}
+
+void desc_refine_batch_destroy(desc_refine_batch* h) { rb_free(h); }
+
+}  // extern "C"

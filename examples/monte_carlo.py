@@ -2,10 +2,12 @@
 """A small Monte-Carlo study in ONE batched call: mean |S_vec - ErrVec| against the corruption level q, averaged over a few trials
 of Uniform_Topology(100, 0.5, q, 0.1) -- the shape of the figures the DESC paper draws (error against q on graphs of 100-200 nodes).
 
-    python examples/monte_carlo.py [--trials 5] [--n 100] [--iters 100] [--rotations] [--baselines]
+    python examples/monte_carlo.py [--trials 5] [--n 100] [--iters 100] [--rotations] [--refined] [--baselines]
 
 --rotations: the demo's own metric next to it -- one DESC_init_batch call (the PGD pass, then the batched GCW eigen-solve) and the mean
 rotation error in degrees (Rotation_Alignment against the ground truth), the column of Demo/compare_algorithms.m.
+--refined: the headline row, DESC() itself -- one DESC_batch call (the two passes of DESC_init_batch, then the batched reweighted
+refinement) and the mean rotation error of R_est next to that of its initialisation R_init.
 --baselines: the curves DESC is drawn against, one batched call per curve -- CEMP's SVec error (CEMP_batch) and the rotation errors of
 CEMP+GCW (CEMP_GCW_batch) and CEMP+MST (CEMP_MST_batch), with the demo's CEMP parameters (compare_algorithms.m:26-29).
 """
@@ -18,8 +20,8 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from desc_amd import (CEMP_GCW_batch, CEMP_MST_batch, CEMP_batch, ConstantStepSize, DESC_PGD_batch, DESC_init_batch,  # noqa: E402
-                      Rotation_Alignment, Uniform_Topology)
+from desc_amd import (CEMP_GCW_batch, CEMP_MST_batch, CEMP_batch, ConstantStepSize, DESC_PGD_batch, DESC_batch,  # noqa: E402
+                      DESC_init_batch, Rotation_Alignment, Uniform_Topology)
 
 
 def baselines(models, qs, trials):
@@ -49,11 +51,27 @@ def main():
     ap.add_argument("--n", type=int, default=100)
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--rotations", action="store_true", help="one DESC_init_batch call: the mean rotation error next to the S_vec error")
+    ap.add_argument("--refined", action="store_true", help="one DESC_batch call: the rotation error of DESC() next to its initialisation's")
     ap.add_argument("--baselines", action="store_true", help="CEMP, CEMP+GCW and CEMP+MST next to DESC: one batched call per curve")
     a = ap.parse_args()
     qs = [0.0, 0.1, 0.2, 0.3, 0.4, 0.5]
     models = [Uniform_Topology(a.n, 0.5, q, 0.1, "uniform", seed=1000 * k + t) for k, q in enumerate(qs) for t in range(a.trials)]
     params = dict(iters=a.iters, Gradient=ConstantStepSize(0.01), seed=0, verbose=False)
+    if a.refined:
+        t0 = time.perf_counter()
+        out = DESC_batch(models, params)
+        ms = (time.perf_counter() - t0) * 1e3
+        shape = (len(qs), a.trials)
+        err = np.array([np.abs(s - mo.ErrVec).mean() for (_, _, s), mo in zip(out, models)]).reshape(shape)
+        est = np.array([Rotation_Alignment(R, mo.R_orig)[2] for (R, _, _), mo in zip(out, models)]).reshape(shape)
+        ini = np.array([Rotation_Alignment(R, mo.R_orig)[2] for (_, R, _), mo in zip(out, models)]).reshape(shape)
+        print(f"{len(models)} problems (n = {a.n}, {a.trials} trials per q) in one DESC_batch call: {ms:.1f} ms")
+        print("    q   mean |S_vec - ErrVec|   DESC rotation error, degrees   (min .. max)          its initialisation's (R_init)")
+        for q, row, re, ri in zip(qs, err, est, ini):
+            print(f" {q:4.2f}   {row.mean():.4f}                {re.mean():8.4f}                       ({re.min():.4f} .. {re.max():.4f})      {ri.mean():8.4f}")
+        if a.baselines:
+            baselines(models, qs, a.trials)
+        return
     t0 = time.perf_counter()
     if a.rotations:
         out = DESC_init_batch(models, params)

@@ -672,6 +672,41 @@ int desc_mst_batch_check(const desc_problem* probs, int32_t count);
 int desc_mst_batch_run(const desc_problem* probs, int32_t count, const double* s_vec, int32_t device, double* R_out,
                        int32_t* tree_edges /* nullable */, desc_mst_batch_timings* timings /* nullable */);
 
+/* The DESC refinement tail (Algorithms/DESC.m:265-313, desc_refine_run) for B independent small problems in ONE launch: the last stage
+ * of DESC() behind desc_pgd_batch_* and desc_gcw_batch_*.  One workgroup per problem runs the whole loop on the chip -- the edge log map,
+ * the normal equations, the Jacobi-PCG with its probe every 25 steps, the node update and the score, the residuals, an exact selection
+ * of the quantile's two order statistics, the new weights -- with the per-node state in LDS and no host round trip.  The arithmetic is
+ * the text desc_refine_run's kernels run (csrc/laa_math.h) and every sum is taken in desc_refine_run's order: problem b's R_out and
+ * record (iters, score, cg_iters, cg_unconverged, cg_residual) are bit for bit what desc_refine_run gives for it, and no bit of them
+ * depends on the batch around it (position, neighbours, batch size, the LDS size of the launch).
+ * desc_refine_batch_max_n: the largest n whose per-node state (26 doubles) fits the 160 KiB of LDS a workgroup may declare (748).
+ * desc_refine_batch_create: validates every problem and refuses -- before any device work, naming the problem -- an empty edge list and
+ * n > desc_refine_batch_max_n() (DESC_ERR_INVALID: solve it with DESC); builds the per-problem CSR (local ids) and the incidence signs
+ * and uploads rotations and indices in one copy each.  count == 0 is legal and touches no device.  Without a device: DESC_ERR_HIP and
+ * *out = NULL.  The handle may be run any number of times.
+ * desc_refine_batch_sizes: node_off[count+1], edge_off[count+1] (each nullable).
+ * desc_refine_batch_run: s_vec = the edge_off[count] concatenated S_vec in the library's edge order; R_init / R_out: problem b's 3x3xn_b
+ * column-major blocks at 9 * node_off[b]; infos: count entries (ms_total = the call's; verbose is not read: the batch prints nothing,
+ * not even the warning about a PCG solve that stopped at its cap -- cg_unconverged says so).  stop_threshold <= 0: 1e-3, max_iters <=
+ * 0: 100, as desc_refine_run_dev.  Refused before any device work, naming the problem: a negative or non-finite s_vec entry, a
+ * non-finite R_init entry (DESC_ERR_INVALID).  A problem whose selection finds no candidate or whose score is not finite is
+ * DESC_ERR_STATE naming the problem.  That is the one place where the batch differs from desc_refine_run, which returns DESC_OK there
+ * (it leaves its loop on a NaN score and goes on iterating on +inf): "bit for bit" above holds for every problem whose scores are finite. */
+typedef struct desc_refine_batch desc_refine_batch;   /* opaque */
+typedef struct desc_refine_batch_timings {
+    double ms_structure;      /* validation + per-problem CSR + incidence signs (wall clock of create's host part) */
+    double ms_upload;         /* host -> HBM (create)                                                                */
+    double ms_input;          /* run: the checks of s_vec / R_init and their copy to HBM                             */
+    double ms_refine;         /* the refinement launch, device time (HIP events)                                     */
+    double ms_total;          /* wall clock of desc_refine_batch_run                                                 */
+} desc_refine_batch_timings;  /* 40 bytes */
+int32_t desc_refine_batch_max_n(void);
+int desc_refine_batch_create(const desc_problem* probs, int32_t count, int32_t device, desc_refine_batch** out);
+int desc_refine_batch_sizes(const desc_refine_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off);
+int desc_refine_batch_run(desc_refine_batch* h, const double* s_vec, const double* R_init, double stop_threshold, int32_t max_iters,
+                          double* R_out, desc_refine_info* infos, desc_refine_batch_timings* timings /* nullable */);
+void desc_refine_batch_destroy(desc_refine_batch* h);
+
 /* One-shot: what the MEX shim calls.  Builds the structure (p->build_where),
  * uploads, runs, downloads, frees. */
 int desc_pgd_solve(const desc_problem* prob, const desc_params* p, desc_result* r);
