@@ -489,24 +489,78 @@ class Structure:
             pass
 
 
-class Batch:
+def _problem_array(probs):
+    """The desc_problem array of a list of ProblemArrays (one spare entry for an empty list: ctypes has no array of length 0)."""
+    return (Problem * max(len(probs), 1))(*[q.c for q in probs])
+
+
+def _seeds_array(seeds, B):
+    """Per-problem sampling seeds as a uint64 array, or None."""
+    if seeds is None:
+        return None
+    if len(seeds) != B:
+        raise ValueError(f"seeds must hold one entry per problem ({B}), not {len(seeds)}")
+    return (C.c_uint64 * max(B, 1))(*[int(x) for x in seeds])
+
+
+def _split_R(R, node_off):
+    """The per-problem (3,3,n_b) Fortran-ordered views of the concatenated rotations."""
+    return [R[9 * int(n0):9 * int(n1)].reshape((3, 3, int(n1 - n0)), order="F") for n0, n1 in zip(node_off[:-1], node_off[1:])]
+
+
+def _timings(tm):
+    """The ms_* fields of a timings (or result) structure as a dict."""
+    return {name: getattr(tm, name) for name, _ in tm._fields_ if name.startswith("ms_")}
+
+
+class _BatchHandle:
+    """Base of the owners of a batched handle desc_<_kind>_batch*.  A subclass's constructor calls _open with the arguments of its
+    create call that stand between ``count`` and ``out``; Batch, whose offsets are others, also overrides _read_sizes."""
+    _kind = None
+    handle = None
+
+    def _export(self, name):
+        return getattr(load(), f"desc_{self._kind}_batch_{name}")
+
+    def _open(self, probs, *create_args):
+        self.probs = list(probs)                     # keeps the NumPy buffers alive
+        self.count = B = len(self.probs)
+        h = C.c_void_p()
+        check(self._export("create")(_problem_array(self.probs), B, *create_args, C.byref(h)))
+        self.handle = h
+        self._read_sizes(B)
+
+    def _read_sizes(self, B):
+        no, eo = np.zeros(B + 1, dtype=np.int64), np.zeros(B + 1, dtype=np.int64)
+        check(self._export("sizes")(self.handle, None, ptr(no, I64P), ptr(eo, I64P)))
+        self.node_off, self.edge_off = no, eo
+        self.n, self.m = int(no[B]), int(eo[B])
+
+    def destroy(self):
+        if self.handle:
+            self._export("destroy")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class Batch(_BatchHandle):
     """Owner of a desc_pgd_batch*: B independent problems behind one another in one set of device arrays (desc_pgd_batch_*).
     ``probs`` is a sequence of ProblemArrays; ``seeds`` an optional sequence of per-problem sampling seeds."""
 
+    _kind = "pgd"
+
     def __init__(self, probs, params: Params, seeds=None):
-        self.probs = list(probs)                     # keeps the NumPy buffers alive
-        self.count = B = len(self.probs)
-        arr = (Problem * max(B, 1))(*[q.c for q in self.probs])
-        sd = None
-        if seeds is not None:
-            if len(seeds) != B:
-                raise ValueError(f"seeds must hold one entry per problem ({B}), not {len(seeds)}")
-            sd = (C.c_uint64 * max(B, 1))(*[int(x) for x in seeds])
-        h = C.c_void_p()
-        check(load().desc_pgd_batch_create(arr, B, C.byref(params), sd, C.byref(h)))
-        self.handle = h
+        probs = list(probs)
+        self._open(probs, C.byref(params), _seeds_array(seeds, len(probs)))
+
+    def _read_sizes(self, B):
         eo, co, ns = np.zeros(B + 1, dtype=np.int64), np.zeros(B + 1, dtype=np.int64), np.zeros(max(B, 1), dtype=np.int32)
-        check(load().desc_pgd_batch_sizes(h, None, ptr(eo, I64P), ptr(co, I64P), ptr(ns, I32P)))
+        check(self._export("sizes")(self.handle, None, ptr(eo, I64P), ptr(co, I64P), ptr(ns, I32P)))
         self.edge_off, self.cycle_off, self.n_sample = eo, co, ns[:B]
         self.m, self.m_cycle = int(eo[B]), int(co[B])
 
@@ -551,19 +605,7 @@ class Batch:
             if adam is not None:
                 o["adam_m"], o["adam_v"] = adam[0][c0:c1], adam[1][c0:c1]
             outs.append(o)
-        timings = dict(ms_structure=r.ms_structure, ms_upload=r.ms_upload, ms_cycle_d=r.ms_cycle_d, ms_pgd=r.ms_pgd, ms_total=r.ms_total)
-        return outs, timings
-
-    def destroy(self):
-        if self.handle:
-            load().desc_pgd_batch_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+        return outs, _timings(r)
 
 
 def gcw_batch_max_n():
@@ -571,21 +613,14 @@ def gcw_batch_max_n():
     return int(load().desc_gcw_batch_max_n())
 
 
-class GcwBatch:
+class GcwBatch(_BatchHandle):
     """Owner of a desc_gcw_batch*: the Spectral / GCW eigen-solve of B small problems in one launch (desc_gcw_batch_*).
     ``probs`` is a sequence of ProblemArrays.  The handle may be run any number of times."""
 
+    _kind = "gcw"
+
     def __init__(self, probs, device=0):
-        self.probs = list(probs)                     # keeps the NumPy buffers alive
-        self.count = B = len(self.probs)
-        arr = (Problem * max(B, 1))(*[q.c for q in self.probs])
-        h = C.c_void_p()
-        check(load().desc_gcw_batch_create(arr, B, int(device), C.byref(h)))
-        self.handle = h
-        no, eo = np.zeros(B + 1, dtype=np.int64), np.zeros(B + 1, dtype=np.int64)
-        check(load().desc_gcw_batch_sizes(h, None, ptr(no, I64P), ptr(eo, I64P)))
-        self.node_off, self.edge_off = no, eo
-        self.n, self.m = int(no[B]), int(eo[B])
+        self._open(probs, int(device))
 
     def run(self, s_vec=None, weights=None, normalize_rows=False, tol=1e-13, max_iters=500):
         """One batched eigen-solve.  s_vec: the concatenated S_vec (GCW mode); weights: concatenated host weights; neither: Spectral.
@@ -604,26 +639,9 @@ class GcwBatch:
         check(load().desc_gcw_batch_run(self.handle, ptr(vec, F64P) if s_vec is not None else None,
                                         ptr(vec, F64P) if s_vec is None and weights is not None else None, 1 if normalize_rows else 0,
                                         tol, max_iters, ptr(R, F64P), infos, C.byref(tm)))
-        outs = []
-        for b in range(B):
-            n0, n1 = int(self.node_off[b]), int(self.node_off[b + 1])
-            i = infos[b]
-            outs.append((R[9 * n0:9 * n1].reshape((3, 3, n1 - n0), order="F"),
-                         dict(iters=i.iters, products=i.products, converged=bool(i.converged), residual=i.residual,
-                              eigenvalues=list(i.eigenvalues), ms_total=i.ms_total)))
-        timings = dict(ms_structure=tm.ms_structure, ms_upload=tm.ms_upload, ms_eig=tm.ms_eig, ms_project=tm.ms_project, ms_total=tm.ms_total)
-        return outs, timings
-
-    def destroy(self):
-        if self.handle:
-            load().desc_gcw_batch_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+        outs = [(Rb, dict(iters=i.iters, products=i.products, converged=bool(i.converged), residual=i.residual,
+                          eigenvalues=list(i.eigenvalues), ms_total=i.ms_total)) for Rb, i in zip(_split_R(R, self.node_off), infos)]
+        return outs, _timings(tm)
 
 
 def cemp_batch_max_degree():
@@ -631,28 +649,17 @@ def cemp_batch_max_degree():
     return int(load().desc_cemp_batch_max_degree())
 
 
-class CempBatch:
+class CempBatch(_BatchHandle):
     """Owner of a desc_cemp_batch*: CEMP on B small problems in one GPU pass (desc_cemp_batch_*).  ``probs`` is a sequence of
     ProblemArrays; ``seeds`` an optional sequence of per-problem sampling seeds.  Sampling, S0 and the initial means are computed here;
     the handle may be run any number of times."""
 
+    _kind = "cemp"
+
     def __init__(self, probs, nsample, seed=0, seeds=None, device=0):
-        self.probs = list(probs)                     # keeps the NumPy buffers alive
-        self.count = B = len(self.probs)
+        probs = list(probs)
         self.nsample = int(nsample)
-        arr = (Problem * max(B, 1))(*[q.c for q in self.probs])
-        sd = None
-        if seeds is not None:
-            if len(seeds) != B:
-                raise ValueError(f"seeds must hold one entry per problem ({B}), not {len(seeds)}")
-            sd = (C.c_uint64 * max(B, 1))(*[int(x) for x in seeds])
-        h = C.c_void_p()
-        check(load().desc_cemp_batch_create(arr, B, self.nsample, int(seed), sd, int(device), C.byref(h)))
-        self.handle = h
-        no, eo = np.zeros(B + 1, dtype=np.int64), np.zeros(B + 1, dtype=np.int64)
-        check(load().desc_cemp_batch_sizes(h, None, ptr(no, I64P), ptr(eo, I64P)))
-        self.node_off, self.edge_off = no, eo
-        self.n, self.m = int(no[B]), int(eo[B])
+        self._open(probs, self.nsample, int(seed), _seeds_array(seeds, len(probs)), int(device))
 
     def samples(self):
         """What create sampled, per problem: a list of dicts e_jk / e_ki (m_b x nsample local edge ids, -1 without a cycle), s0
@@ -676,19 +683,7 @@ class CempBatch:
         tm = CempBatchTimings()
         check(load().desc_cemp_batch_run(self.handle, ptr(b, F64P), b.shape[0], int(max_iter), ptr(S, F64P), C.byref(tm)))
         outs = [S[int(self.edge_off[k]):int(self.edge_off[k + 1])] for k in range(self.count)]
-        timings = dict(ms_structure=tm.ms_structure, ms_upload=tm.ms_upload, ms_build=tm.ms_build, ms_rounds=tm.ms_rounds, ms_total=tm.ms_total)
-        return outs, timings
-
-    def destroy(self):
-        if self.handle:
-            load().desc_cemp_batch_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+        return outs, _timings(tm)
 
 
 def mst_batch_max_n():
@@ -699,8 +694,7 @@ def mst_batch_max_n():
 def mst_batch_check(probs):
     """desc_mst_batch_check on a sequence of ProblemArrays: the size cap and connectivity of every problem (host only; raises DescError)."""
     probs = list(probs)
-    arr = (Problem * max(len(probs), 1))(*[q.c for q in probs])
-    check(load().desc_mst_batch_check(arr, len(probs)))
+    check(load().desc_mst_batch_check(_problem_array(probs), len(probs)))
 
 
 def mst_batch_run(probs, s_vec, device=0):
@@ -708,7 +702,7 @@ def mst_batch_run(probs, s_vec, device=0):
     (R (3,3,n_b) Fortran-ordered, tree edge ids ascending (n_b - 1,), sorted order) and the call's timings."""
     probs = list(probs)
     B = len(probs)
-    arr = (Problem * max(B, 1))(*[q.c for q in probs])
+    arr = _problem_array(probs)
     S = np.ascontiguousarray(s_vec, dtype=np.float64).reshape(-1)
     no = np.concatenate([[0], np.cumsum([q.n for q in probs], dtype=np.int64)]).astype(np.int64)
     if S.size != sum(q.m for q in probs):
@@ -717,12 +711,8 @@ def mst_batch_run(probs, s_vec, device=0):
     T = out_buffer(max(int(no[B]) - B, 1), np.int32)
     tm = MstBatchTimings()
     check(load().desc_mst_batch_run(arr, B, ptr(S, F64P), int(device), ptr(R, F64P), ptr(T, I32P), C.byref(tm)))
-    outs = []
-    for b in range(B):
-        n0, n1 = int(no[b]), int(no[b + 1])
-        outs.append((R[9 * n0:9 * n1].reshape((3, 3, n1 - n0), order="F"), T[n0 - b:n1 - b - 1].copy()))
-    timings = dict(ms_structure=tm.ms_structure, ms_upload=tm.ms_upload, ms_tree=tm.ms_tree, ms_propagate=tm.ms_propagate, ms_total=tm.ms_total)
-    return outs, timings
+    outs = [(Rb, T[int(no[b]) - b:int(no[b + 1]) - b - 1].copy()) for b, Rb in enumerate(_split_R(R, no))]
+    return outs, _timings(tm)
 
 
 def refine_batch_max_n():
@@ -730,21 +720,14 @@ def refine_batch_max_n():
     return int(load().desc_refine_batch_max_n())
 
 
-class RefineBatch:
+class RefineBatch(_BatchHandle):
     """Owner of a desc_refine_batch*: the DESC refinement tail of B small problems in one launch (desc_refine_batch_*).
     ``probs`` is a sequence of ProblemArrays.  The handle may be run any number of times."""
 
+    _kind = "refine"
+
     def __init__(self, probs, device=0):
-        self.probs = list(probs)                     # keeps the NumPy buffers alive
-        self.count = B = len(self.probs)
-        arr = (Problem * max(B, 1))(*[q.c for q in self.probs])
-        h = C.c_void_p()
-        check(load().desc_refine_batch_create(arr, B, int(device), C.byref(h)))
-        self.handle = h
-        no, eo = np.zeros(B + 1, dtype=np.int64), np.zeros(B + 1, dtype=np.int64)
-        check(load().desc_refine_batch_sizes(h, None, ptr(no, I64P), ptr(eo, I64P)))
-        self.node_off, self.edge_off = no, eo
-        self.n, self.m = int(no[B]), int(eo[B])
+        self._open(probs, int(device))
 
     def run(self, s_vec, R_init, stop_threshold=1e-3, max_iters=100):
         """One batched refinement.  s_vec: the concatenated S_vec (library's edge order); R_init: the concatenated 9 n_b doubles per
@@ -762,33 +745,16 @@ class RefineBatch:
         tm = RefineBatchTimings()
         check(load().desc_refine_batch_run(self.handle, ptr(S, F64P), ptr(Ri, F64P), stop_threshold, int(max_iters), ptr(R, F64P), infos,
                                            C.byref(tm)))
-        outs = []
-        for b in range(B):
-            n0, n1 = int(self.node_off[b]), int(self.node_off[b + 1])
-            i = infos[b]
-            outs.append((R[9 * n0:9 * n1].reshape((3, 3, n1 - n0), order="F"),
-                         dict(iters=i.iters, cg_iters=i.cg_iters, score=i.score, ms_total=i.ms_total, cg_unconverged=i.cg_unconverged,
-                              cg_residual=i.cg_residual)))
-        timings = dict(ms_structure=tm.ms_structure, ms_upload=tm.ms_upload, ms_input=tm.ms_input, ms_refine=tm.ms_refine, ms_total=tm.ms_total)
-        return outs, timings
-
-    def destroy(self):
-        if self.handle:
-            load().desc_refine_batch_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+        outs = [(Rb, dict(iters=i.iters, cg_iters=i.cg_iters, score=i.score, ms_total=i.ms_total, cg_unconverged=i.cg_unconverged,
+                          cg_residual=i.cg_residual)) for Rb, i in zip(_split_R(R, self.node_off), infos)]
+        return outs, _timings(tm)
 
 
 def gcw_batch_csr(probs):
     """desc_gcw_batch_csr on a sequence of ProblemArrays: the per-problem CSR the batched eigen-solve uploads (host only)."""
     probs = list(probs)
     B = len(probs)
-    arr = (Problem * max(B, 1))(*[q.c for q in probs])
+    arr = _problem_array(probs)
     no, eo = np.zeros(B + 1, dtype=np.int64), np.zeros(B + 1, dtype=np.int64)
     L = load()
     check(L.desc_gcw_batch_csr(arr, B, ptr(no, I64P), ptr(eo, I64P), None, None, None))

@@ -20,6 +20,7 @@ over the same ABI are in matlab/.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import os
@@ -285,6 +286,39 @@ def _marshal_problems(problems):
     return probs, perms
 
 
+@contextlib.contextmanager
+def _invalid_as_value_error():
+    """A refusal of the library (DESC_ERR_INVALID) leaves the block as ValueError, without the entry point's name in front."""
+    try:
+        yield
+    except _lib.DescError as e:
+        if e.code == _lib.ERR_INVALID:
+            raise ValueError(str(e).split(": ", 1)[-1]) from None
+        raise
+
+
+@contextlib.contextmanager
+def _batch_handle(cls, *args):
+    """``cls(*args)``, one of _lib's batched handles, for the length of a with block: what create refuses is a ValueError, and the
+    handle is destroyed however the block ends."""
+    with _invalid_as_value_error():
+        batch = cls(*args)
+    try:
+        yield batch
+    finally:
+        batch.destroy()
+
+
+def _check_seeds(seeds, B):
+    """``seeds`` as a list of B ints, or None."""
+    if seeds is None:
+        return None
+    seeds = [int(x) for x in seeds]
+    if len(seeds) != B:
+        raise ValueError(f"seeds must hold one entry per problem ({B}), not {len(seeds)}")
+    return seeds
+
+
 def DESC_PGD_batch(problems, params, seeds=None, return_info=False):
     """DESC_PGD on B independent problems in one GPU pass (desc_pgd_batch_*; the reference has no such call).
 
@@ -308,29 +342,18 @@ def DESC_PGD_batch(problems, params, seeds=None, return_info=False):
     if bool(_get(params, "make_plots", False)):
         raise ValueError("DESC_PGD_batch does not support params.make_plots: use DESC_PGD for the traced run of one problem")
     B = len(problems)
-    if seeds is not None:
-        seeds = [int(x) for x in seeds]
-        if len(seeds) != B:
-            raise ValueError(f"seeds must hold one entry per problem ({B}), not {len(seeds)}")
+    seeds = _check_seeds(seeds, B)
     p, G = make_c_params(params)
     p.verbose = 0
     if B == 0:
         return []
     probs, perms = _marshal_problems(problems)
-    try:
-        batch = _lib.Batch(probs, p, seeds)
-    except _lib.DescError as e:
-        if e.code == _lib.ERR_INVALID:
-            raise ValueError(str(e).split(": ", 1)[-1]) from None
-        raise
-    try:
+    with _batch_handle(_lib.Batch, probs, p, seeds) as batch:
         hybrid = isinstance(G, HybridGradient) and G.strategy == 0
         adam = (np.zeros(max(batch.m_cycle, 1)), np.zeros(max(batch.m_cycle, 1))) if hybrid else None
         if adam is not None:
             adam = (adam[0][:batch.m_cycle], adam[1][:batch.m_cycle])
         outs, timings = batch.run(p, want_w=return_info, adam=adam)
-    finally:
-        batch.destroy()
     result = []
     for o, perm in zip(outs, perms):
         S_vec = o["S_vec"]
@@ -348,45 +371,41 @@ def DESC_PGD_batch(problems, params, seeds=None, return_info=False):
     return result
 
 
-def _check_gcw_batch_sizes(probs):
-    """The batched eigen-solve's size cap, checked before the device is touched."""
-    cap = _lib.gcw_batch_max_n()
+def _check_batch_sizes(probs, cap, what, instead):
+    """A batched kernel's size cap (nodes of one problem), checked before the device is touched."""
     for b, q in enumerate(probs):
         if q.n > cap:
-            raise ValueError(f"problem {b}: n = {q.n} exceeds {cap} (the 3n x 6 blocks of the eigen-solve must fit the LDS of one workgroup): "
-                             "solve it with GCW / DESC_init")
+            raise ValueError(f"problem {b}: n = {q.n} exceeds {cap} (the {what} must fit the LDS of one workgroup): solve it with {instead}")
 
 
-def _sorted_s_list(probs, perms, S_list):
-    """One S_vec per problem in the caller's edge order -> the concatenation in the library's order; refusals name the problem."""
+def _check_gcw_batch_sizes(probs):
+    _check_batch_sizes(probs, _lib.gcw_batch_max_n(), "3n x 6 blocks of the eigen-solve", "GCW / DESC_init")
+
+
+def _sorted_s_list(probs, perms, S_list, noun="S_vec", ok=lambda S: np.isfinite(S) & (S >= 0),
+                   describe_bad=lambda q, perm, t: f"S_vec holds a negative or non-finite entry (node {int(q.ind_i[t])})"):
+    """One S_vec per problem in the caller's edge order -> the concatenation in the library's order; refusals name the problem.
+    ``ok``: the entries a call takes; ``describe_bad``: its words for sorted entry t of problem q that is not among them."""
     if isinstance(S_list, (str, bytes)) or not hasattr(S_list, "__len__") or len(S_list) != len(probs):
         got = len(S_list) if hasattr(S_list, "__len__") else type(S_list).__name__
-        raise ValueError(f"S_list must hold one S_vec per problem ({len(probs)}), not {got}")
+        raise ValueError(f"S_list must hold one {noun} per problem ({len(probs)}), not {got}")
     parts = []
     for b, (q, perm, S) in enumerate(zip(probs, perms, S_list)):
         S = np.asarray(S, dtype=np.float64).reshape(-1)
         if S.shape[0] != q.m:
-            raise ValueError(f"problem {b}: S_vec must have one entry per edge ({q.m}), not {S.shape[0]}")
+            raise ValueError(f"problem {b}: {noun} must have one entry per edge ({q.m}), not {S.shape[0]}")
         if perm is not None:
             S = S[perm]
-        bad = np.flatnonzero(~(np.isfinite(S) & (S >= 0)))
+        bad = np.flatnonzero(~ok(S))
         if bad.size:
-            raise ValueError(f"problem {b}: S_vec holds a negative or non-finite entry (node {int(q.ind_i[bad[0]])})")
+            raise ValueError(f"problem {b}: {describe_bad(q, perm, bad[0])}")
         parts.append(S)
     return np.concatenate(parts) if parts else np.zeros(0)
 
 
 def _gcw_batch_run(probs, device, **run_args):
-    try:
-        batch = _lib.GcwBatch(probs, device)
-    except _lib.DescError as e:
-        if e.code == _lib.ERR_INVALID:
-            raise ValueError(str(e).split(": ", 1)[-1]) from None
-        raise
-    try:
+    with _batch_handle(_lib.GcwBatch, probs, device) as batch:
         return batch.run(**run_args)
-    finally:
-        batch.destroy()
 
 
 def Spectral_batch(problems, device=0, return_info=False):
@@ -431,10 +450,7 @@ def DESC_init_batch(problems, params, seeds=None, return_info=False):
                          "a Gradient object with a GetStep of its own runs through DESC_init, one problem at a time")
     if bool(_get(params, "make_plots", False)):
         raise ValueError("DESC_init_batch does not support params.make_plots: use DESC_init for the traced run of one problem")
-    if seeds is not None:
-        seeds = [int(x) for x in seeds]
-        if len(seeds) != len(problems):
-            raise ValueError(f"seeds must hold one entry per problem ({len(problems)}), not {len(seeds)}")
+    seeds = _check_seeds(seeds, len(problems))
     probs, perms = _marshal_problems(problems)
     _check_gcw_batch_sizes(probs)
     pgd = DESC_PGD_batch([_Marshalled(q, perm) for q, perm in zip(probs, perms)], params, seeds=seeds, return_info=True)
@@ -449,12 +465,7 @@ def DESC_init_batch(problems, params, seeds=None, return_info=False):
 
 
 def _check_refine_batch_sizes(probs):
-    """The batched refinement's size cap, checked before the device is touched."""
-    cap = _lib.refine_batch_max_n()
-    for b, q in enumerate(probs):
-        if q.n > cap:
-            raise ValueError(f"problem {b}: n = {q.n} exceeds {cap} (the per-node state of the refinement must fit the LDS of one workgroup): "
-                             "solve it with DESC")
+    _check_batch_sizes(probs, _lib.refine_batch_max_n(), "per-node state of the refinement", "DESC")
 
 
 def _r_init_list(probs, R_init_list):
@@ -475,16 +486,8 @@ def _r_init_list(probs, R_init_list):
 
 
 def _refine_batch_run(probs, device, S, R_init, stop_threshold, max_iters):
-    try:
-        batch = _lib.RefineBatch(probs, device)
-    except _lib.DescError as e:
-        if e.code == _lib.ERR_INVALID:
-            raise ValueError(str(e).split(": ", 1)[-1]) from None
-        raise
-    try:
+    with _batch_handle(_lib.RefineBatch, probs, device) as batch:
         return batch.run(S, R_init, stop_threshold, max_iters)
-    finally:
-        batch.destroy()
 
 
 def DESC_refine_batch(problems, S_list, R_init_list, stop_threshold=1e-3, max_iters=100, device=0, return_info=False):
@@ -534,10 +537,7 @@ def _cemp_batch_params(CEMP_parameters, B, seeds):
         raise ValueError("CEMP_parameters.max_iter must be an integer >= 0")
     if nsample is None or int(nsample) < 1:
         raise ValueError("CEMP_parameters.nsample must be an integer >= 1")
-    if seeds is not None:
-        seeds = [int(x) for x in seeds]
-        if len(seeds) != B:
-            raise ValueError(f"seeds must hold one entry per problem ({B}), not {len(seeds)}")
+    seeds = _check_seeds(seeds, B)
     return beta, int(max_iter), int(nsample), int(_get(CEMP_parameters, "seed", 0)), int(_get(CEMP_parameters, "device", 0)), seeds
 
 
@@ -554,12 +554,8 @@ def _check_cemp_batch_degrees(probs):
 
 def _check_mst_batch(probs):
     """The tree kernel's size cap and connectivity (a host union-find of the library), checked before the device is touched."""
-    try:
+    with _invalid_as_value_error():
         _lib.mst_batch_check(probs)
-    except _lib.DescError as e:
-        if e.code == _lib.ERR_INVALID:
-            raise ValueError(str(e).split(": ", 1)[-1]) from None
-        raise
 
 
 def _unsort(S, perm):
@@ -587,16 +583,8 @@ def CEMP_batch(problems, CEMP_parameters, seeds=None, return_info=False):
     if not probs:
         return []
     _check_cemp_batch_degrees(probs)
-    try:
-        batch = _lib.CempBatch(probs, nsample, seed, seeds, device)
-    except _lib.DescError as e:
-        if e.code == _lib.ERR_INVALID:
-            raise ValueError(str(e).split(": ", 1)[-1]) from None
-        raise
-    try:
+    with _batch_handle(_lib.CempBatch, probs, nsample, seed, seeds, device) as batch:
         outs, timings = batch.run(beta, max_iter)
-    finally:
-        batch.destroy()
     S = [_unsort(o, perm) for o, perm in zip(outs, perms)]
     return [(s, dict(timings=timings)) for s in S] if return_info else S
 
@@ -623,25 +611,6 @@ def CEMP_GCW_batch(problems, CEMP_parameters, seeds=None, return_info=False):
     return [R for R, _ in outs]
 
 
-def _sorted_s_list_mst(probs, perms, S_list):
-    """One SVec per problem in the caller's edge order -> the concatenation in the library's order; refusals name the problem."""
-    if isinstance(S_list, (str, bytes)) or not hasattr(S_list, "__len__") or len(S_list) != len(probs):
-        got = len(S_list) if hasattr(S_list, "__len__") else type(S_list).__name__
-        raise ValueError(f"S_list must hold one SVec per problem ({len(probs)}), not {got}")
-    parts = []
-    for b, (q, perm, S) in enumerate(zip(probs, perms, S_list)):
-        S = np.asarray(S, dtype=np.float64).reshape(-1)
-        if S.shape[0] != q.m:
-            raise ValueError(f"problem {b}: SVec must have one entry per edge ({q.m}), not {S.shape[0]}")
-        if perm is not None:
-            S = S[perm]
-        bad = np.flatnonzero(~np.isfinite(S))
-        if bad.size:
-            raise ValueError(f"problem {b}: SVec entry {int(bad[0] if perm is None else perm[bad[0]])} is not finite")
-        parts.append(S)
-    return np.concatenate(parts) if parts else np.zeros(0)
-
-
 def MST_batch(problems, S_list, device=0, return_info=False):
     """The tree step of MPLS (Algorithms/MPLS.m:160-193, as MST()) on B independent small problems in one GPU launch
     (desc_mst_batch_run): ``S_list[b]`` is problem b's SVec in the caller's edge order.  Returns a list of R (3 x 3 x n_b): entry b is
@@ -652,16 +621,13 @@ def MST_batch(problems, S_list, device=0, return_info=False):
     disconnected problem (a node id in 1..max(Ind) that no edge touches counts as a component)."""
     _check_sequence(problems)
     probs, perms = _marshal_problems(problems)
-    S = _sorted_s_list_mst(probs, perms, S_list)
+    S = _sorted_s_list(probs, perms, S_list, "SVec", np.isfinite,
+                       lambda q, perm, t: f"SVec entry {int(t if perm is None else perm[t])} is not finite")
     if not probs:
         return []
     _check_mst_batch(probs)
-    try:
+    with _invalid_as_value_error():
         outs, timings = _lib.mst_batch_run(probs, S, device)
-    except _lib.DescError as e:
-        if e.code == _lib.ERR_INVALID:
-            raise ValueError(str(e).split(": ", 1)[-1]) from None
-        raise
     if not return_info:
         return [R for R, _ in outs]
     return [(R, dict(tree_edges=tree if perm is None else np.sort(perm[tree]), timings=timings)) for (R, tree), perm in zip(outs, perms)]

@@ -29,7 +29,8 @@
 #include <new>
 #include <vector>
 
-#include "device_utils.h"
+#include "batch_csr.h"
+#include "batch_device.h"
 #include "pgd_math.h"
 
 namespace desc {
@@ -247,16 +248,13 @@ __global__ __launch_bounds__(256) void k_batch_settle(double* buf0, const double
 
 using namespace desc;
 
-struct desc_pgd_batch {
-    int device = 0;
+struct desc_pgd_batch : desc::BatchDevice {     // device, stream, arena, events
     int32_t count = 0;
-    hipStream_t stream = nullptr;
     std::vector<desc_structure*> st;          // per problem, local ids (desc_pgd_batch_get_structure)
     hvec<int64_t> edge_off, cycle_off, seg_off;
     hvec<int32_t> n_sample;
     int64_t M = 0, MC = 0, MP = 0;            // edges, cycles, segments of the whole batch
     int32_t nwg = 0;
-    DevArena mem;
     int32_t *d_cum = nullptr, *d_pos = nullptr, *d_ejk = nullptr, *d_eki = nullptr, *d_ikj = nullptr, *d_jki = nullptr;
     double *d_S0 = nullptr, *d_w[2] = {nullptr, nullptr}, *d_S[2] = {nullptr, nullptr};
     double *d_am[2] = {nullptr, nullptr}, *d_av[2] = {nullptr, nullptr};
@@ -267,19 +265,14 @@ struct desc_pgd_batch {
     BatchProb* d_prob = nullptr;
     int64_t *d_edge_off = nullptr, *d_cycle_off = nullptr;
     int32_t* d_running = nullptr;
-    double ms_structure = 0, ms_upload = 0, ms_cycle_d = 0;
+    double ms_cycle_d = 0;
+    ~desc_pgd_batch() {
+        close();                                  // the device first, as ever
+        for (desc_structure* s : st) if (s) { structure_free_device(s); delete s; }
+    }
 };
 
 namespace {
-
-void batch_free(desc_pgd_batch* h) {
-    if (!h) return;
-    if (h->stream) { (void)hipSetDevice(h->device); (void)hipStreamSynchronize(h->stream); }
-    h->mem.release();
-    if (h->stream) stream_release(h->stream);
-    for (desc_structure* s : h->st) if (s) { structure_free_device(s); delete s; }
-    delete h;
-}
 
 int batch_offsets(const desc_structure* const* s, int32_t count, int64_t* edge_off, int64_t* cycle_off, int64_t* seg_off) {
     edge_off[0] = cycle_off[0] = seg_off[0] = 0;
@@ -300,57 +293,33 @@ int batch_offsets(const desc_structure* const* s, int32_t count, int64_t* edge_o
 // globalised copies of problem b's index arrays (T threads share the problems)
 void batch_concat_fill(const desc_structure* const* s, int32_t count, const int64_t* edge_off, const int64_t* cycle_off, const int64_t* seg_off,
                        int32_t* pos_edge, int32_t* cum, int32_t* e_jk, int32_t* e_ki, int32_t* ikj, int32_t* jki) {
-    const int T = std::max(1, std::min(count, 16));
-    run_threads(T, [&](int t) {
-        for (int32_t b = t; b < count; b += T) {
-            const desc_structure* q = s[b];
-            const int32_t eo = (int32_t)edge_off[b], co = (int32_t)cycle_off[b];
-            const int64_t so = seg_off[b], c0 = cycle_off[b];
-            if (pos_edge) for (int64_t l = 0; l < q->m_pos; ++l) pos_edge[so + l] = q->pos_edge[l] + eo;
-            if (cum) for (int64_t l = 0; l < q->m_pos; ++l) cum[so + l] = (int32_t)(q->cum_ind[l] + c0);
-            for (int64_t c = 0; c < q->m_cycle; ++c) {
-                if (e_jk) e_jk[c0 + c] = q->e_jk[c] + eo;
-                if (e_ki) e_ki[c0 + c] = q->e_ki[c] + eo;
-                if (ikj) ikj[c0 + c] = q->ikj[c] < 0 ? -1 : q->ikj[c] + co;
-                if (jki) jki[c0 + c] = q->jki[c] < 0 ? -1 : q->jki[c] + co;
-            }
+    for_each_problem(count, [&](int32_t b) {
+        const desc_structure* q = s[b];
+        const int32_t eo = (int32_t)edge_off[b], co = (int32_t)cycle_off[b];
+        const int64_t so = seg_off[b], c0 = cycle_off[b];
+        if (pos_edge) for (int64_t l = 0; l < q->m_pos; ++l) pos_edge[so + l] = q->pos_edge[l] + eo;
+        if (cum) for (int64_t l = 0; l < q->m_pos; ++l) cum[so + l] = (int32_t)(q->cum_ind[l] + c0);
+        for (int64_t c = 0; c < q->m_cycle; ++c) {
+            if (e_jk) e_jk[c0 + c] = q->e_jk[c] + eo;
+            if (e_ki) e_ki[c0 + c] = q->e_ki[c] + eo;
+            if (ikj) ikj[c0 + c] = q->ikj[c] < 0 ? -1 : q->ikj[c] + co;
+            if (jki) jki[c0 + c] = q->jki[c] < 0 ? -1 : q->jki[c] + co;
         }
     });
     if (cum) cum[seg_off[count]] = (int32_t)cycle_off[count];
 }
 
-template <class T>
-int batch_upload(desc_pgd_batch* h, T** dst, const T* src, size_t n) {
-    int rc = h->mem.alloc(dst, n); if (rc) return rc;
-    if (n) DESC_HIP(hipMemcpyAsync(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice, h->stream));
-    return DESC_OK;
-}
-
-// the plugin's step of iteration t (make_step of pgd.hip: one GetStep call per iteration, the counter advances first)
+// the plugin's step of iteration t (as make_step of pgd.hip: one GetStep call per iteration, the counter advances first)
 StepArgs batch_step(const desc_pgd_batch* h, const desc_params& p, int t, int rd, int wr, bool* adam) {
     StepArgs s{};
     s.adam_m = h->d_am[rd]; s.adam_v = h->d_av[rd]; s.adam_m_out = h->d_am[wr]; s.adam_v_out = h->d_av[wr];
-    const int tp = p.t0 + t;
-    s.lr = p.lr; s.beta1 = p.beta1; s.beta2 = p.beta2; s.bc1 = 1.0; s.bc2 = 1.0;
-    s.step = p.lr;
-    *adam = false;
-    if (p.step_kind == DESC_STEP_PIECEWISE) {
-        s.step = p.lr / (std::trunc((double)tp / p.decay_interval) + 1.0);            // PiecewiseStepSize.m:16
-    } else if (p.step_kind == DESC_STEP_HYBRID) {
-        if (p.hybrid_strategy == 0) {
-            *adam = true;
-            s.bc1 = 1.0 - std::pow(p.beta1, (double)tp);                             // HybridGradient.m:32-33
-            s.bc2 = 1.0 - std::pow(p.beta2, (double)tp);
-        } else {
-            s.step = 100.0 * (p.lr / (std::trunc((double)tp / p.decay_interval) + 1.0));   // HybridGradient.m:39
-        }
-    }
+    *adam = plugin_step(p, p.t0 + t, s);
     return s;
 }
 
 int batch_create(const desc_problem* probs, int32_t count, const desc_params* p, const uint64_t* seeds, desc_pgd_batch* h) {
     auto t0 = std::chrono::steady_clock::now();
-    h->count = count; h->device = p->device;
+    h->count = count;
     const int32_t nmin = p->n_sample_min > 0 ? p->n_sample_min : 30;
     for (int32_t b = 0; b < count; ++b) {
         int rc = validate_problem(&probs[b], true);
@@ -360,16 +329,13 @@ int batch_create(const desc_problem* probs, int32_t count, const desc_params* p,
     h->st.assign((size_t)count, nullptr);
     hvec<int32_t> rcs((size_t)count, DESC_OK);
     std::vector<std::string> msgs((size_t)count);
-    const int T = std::max(1, std::min(count, 16));
-    run_threads(T, [&](int t) {
+    for_each_problem(count, [&](int32_t b) {
         struct Serial { bool was; Serial(bool on) : was(g_structure_serial) { g_structure_serial = on; } ~Serial() { g_structure_serial = was; } };
-        Serial serial(T > 1);                    // T builders side by side: none of them starts threads of its own (16 host threads at most)
-        for (int32_t b = t; b < count; b += T) {
-            desc_structure* s = new desc_structure();
-            h->st[(size_t)b] = s;
-            rcs[(size_t)b] = build_structure_host(&probs[b], nmin, seeds ? seeds[b] : p->seed, s);
-            if (rcs[(size_t)b]) msgs[(size_t)b] = desc_last_error();        // the error text is per thread
-        }
+        Serial serial(count > 1);                // builders side by side: none of them starts threads of its own (16 host threads at most)
+        desc_structure* s = new desc_structure();
+        h->st[(size_t)b] = s;
+        rcs[(size_t)b] = build_structure_host(&probs[b], nmin, seeds ? seeds[b] : p->seed, s);
+        if (rcs[(size_t)b]) msgs[(size_t)b] = desc_last_error();            // the error text is per thread
     });
     for (int32_t b = 0; b < count; ++b)
         if (rcs[(size_t)b]) return fail(rcs[(size_t)b], "problem %d: %s", b, msgs[(size_t)b].c_str());
@@ -413,39 +379,29 @@ int batch_create(const desc_problem* probs, int32_t count, const desc_params* p,
     h->nwg = (int32_t)wg.size();
     h->ms_structure = ms_since(t0);
 
-    // ---- device: nothing above touched it
-    int ndev = desc_device_count();
-    if (ndev < 0) return ndev;
-    if (ndev == 0) return fail(DESC_ERR_HIP, "no HIP device visible: DESC_PGD_batch has no CPU fallback");
-    if (h->device < 0 || h->device >= ndev) return fail(DESC_ERR_INVALID, "device %d out of range (0..%d)", h->device, ndev - 1);
-    hipError_t he = hipSetDevice(h->device);
-    if (he == hipSuccess) he = stream_acquire(&h->stream);
-    if (he != hipSuccess) return fail(DESC_ERR_HIP, "device %d: %s", h->device, hipGetErrorString(he));
+    if ((rc = h->open(p->device, "DESC_PGD_batch"))) return rc;           // nothing above touched the device
     auto t1 = std::chrono::steady_clock::now();
     int32_t *d_kk = nullptr, *d_ii = nullptr, *d_jj = nullptr;
     double* d_rij = nullptr;
-    if ((rc = batch_upload(h, &h->d_cum, cum.data(), MP + 1))) return rc;
-    if ((rc = batch_upload(h, &h->d_pos, pos.data(), MP))) return rc;
-    if ((rc = batch_upload(h, &h->d_ejk, ejk.data(), MC))) return rc;
-    if ((rc = batch_upload(h, &h->d_eki, eki.data(), MC))) return rc;
-    if ((rc = batch_upload(h, &h->d_ikj, ikj.data(), MC))) return rc;
-    if ((rc = batch_upload(h, &h->d_jki, jki.data(), MC))) return rc;
-    if ((rc = batch_upload(h, &d_kk, kk.data(), MC))) return rc;
-    if ((rc = batch_upload(h, &d_ii, ii.data(), M))) return rc;
-    if ((rc = batch_upload(h, &d_jj, jj.data(), M))) return rc;
-    if ((rc = batch_upload(h, &h->d_wg, wg.data(), wg.size()))) return rc;
-    if ((rc = batch_upload(h, &h->d_prob, pr.data(), pr.size()))) return rc;
-    if ((rc = batch_upload(h, &h->d_edge_off, h->edge_off.data(), h->edge_off.size()))) return rc;
-    if ((rc = batch_upload(h, &h->d_cycle_off, h->cycle_off.data(), h->cycle_off.size()))) return rc;
+    if ((rc = h->upload(&h->d_cum, cum.data(), MP + 1))) return rc;
+    if ((rc = h->upload(&h->d_pos, pos.data(), MP))) return rc;
+    if ((rc = h->upload(&h->d_ejk, ejk.data(), MC))) return rc;
+    if ((rc = h->upload(&h->d_eki, eki.data(), MC))) return rc;
+    if ((rc = h->upload(&h->d_ikj, ikj.data(), MC))) return rc;
+    if ((rc = h->upload(&h->d_jki, jki.data(), MC))) return rc;
+    if ((rc = h->upload(&d_kk, kk.data(), MC))) return rc;
+    if ((rc = h->upload(&d_ii, ii.data(), M))) return rc;
+    if ((rc = h->upload(&d_jj, jj.data(), M))) return rc;
+    if ((rc = h->upload(&h->d_wg, wg.data(), wg.size()))) return rc;
+    if ((rc = h->upload(&h->d_prob, pr.data(), pr.size()))) return rc;
+    if ((rc = h->upload(&h->d_edge_off, h->edge_off.data(), h->edge_off.size()))) return rc;
+    if ((rc = h->upload(&h->d_cycle_off, h->cycle_off.data(), h->cycle_off.size()))) return rc;
     double nv[65];
     nv[0] = 0.0;
     for (int c = 1; c <= 64; ++c) nv[c] = 1.0 / std::pow((double)c, 0.5);             // ones/(nsample^0.5), DESC_PGD.m:199
-    if ((rc = batch_upload(h, &h->d_nv, nv, 65))) return rc;
-    // all rotations in one copy: the problems' blocks behind one another in a staging vector
-    hvec<double> rij(9 * M);
-    for (int32_t b = 0; b < count; ++b)
-        if (probs[b].m) std::memcpy(rij.data() + 9 * (size_t)h->edge_off[(size_t)b], probs[b].rij, sizeof(double) * 9 * (size_t)probs[b].m);
-    if ((rc = batch_upload(h, &d_rij, rij.data(), 9 * M))) return rc;
+    if ((rc = h->upload(&h->d_nv, nv, 65))) return rc;
+    const hvec<double> rij = stage_rotations(probs, count, h->edge_off);
+    if ((rc = h->upload(&d_rij, rij.data(), 9 * M))) return rc;
     if ((rc = h->mem.alloc(&h->d_S0, MC))) return rc;
     for (int q = 0; q < 2; ++q) {
         if ((rc = h->mem.alloc(&h->d_w[q], MC))) return rc;
@@ -522,10 +478,7 @@ int batch_run(desc_pgd_batch* h, const desc_params* pin, desc_batch_result* r) {
     DESC_HIP(hipGetLastError());
 
     // ---- loop (:182-261): per iteration one sweep of the whole batch + one bookkeeping wave per problem
-    hipEvent_t e0, e1;
-    DESC_HIP(hipEventCreate(&e0)); DESC_HIP(hipEventCreate(&e1));
-    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } guard{e0, e1};
-    DESC_HIP(hipEventRecord(e0, h->stream));
+    if ((rc = h->timer_begin())) return rc;
     const int chunk = p.check_every > 0 ? p.check_every : 32;
     BatchFinArgs f{h->d_partials, h->d_state, h->d_prob, h->d_obj, h->d_avg, h->d_running, p.stop_tol, cap, 0, p.patience, 0};
     int T = 0;
@@ -563,7 +516,7 @@ int batch_run(desc_pgd_batch* h, const desc_params* pin, desc_batch_result* r) {
         f.t = T; f.last_only = 1;
         hipLaunchKernelGGL(k_batch_finalize, dim3(count), dim3(64), 0, h->stream, f);
     }
-    DESC_HIP(hipEventRecord(e1, h->stream));
+    if ((rc = h->timer_end())) return rc;
     // ---- every problem's final iterate into buffer 0
     const dim3 gE(count, std::max(1, std::min<int>(64, (int)((M / (size_t)count + 255) / 256))));
     const dim3 gC(count, std::max(1, std::min<int>(64, (int)((MC / (size_t)count + 255) / 256))));
@@ -576,7 +529,8 @@ int batch_run(desc_pgd_batch* h, const desc_params* pin, desc_batch_result* r) {
     }
     DESC_HIP(hipGetLastError());
     DESC_HIP(hipStreamSynchronize(h->stream));
-    float ms = 0; DESC_HIP(hipEventElapsedTime(&ms, e0, e1));
+    float ms = 0;
+    if ((rc = h->timer_ms(&ms))) return rc;
     r->ms_pgd = ms;
     // ---- download
     hvec<BatchState> st((size_t)count);
@@ -614,18 +568,8 @@ int batch_run(desc_pgd_batch* h, const desc_params* pin, desc_batch_result* r) {
 extern "C" {
 
 int desc_pgd_batch_create(const desc_problem* probs, int32_t count, const desc_params* p, const uint64_t* seeds, desc_pgd_batch** out) {
-    return no_throw("desc_pgd_batch_create", [&]() -> int {
-        if (!out) return fail(DESC_ERR_INVALID, "out is NULL");
-        *out = nullptr;
-        if (!p || count < 0 || (count > 0 && !probs)) return fail(DESC_ERR_INVALID, "NULL argument or negative count");
-        desc_pgd_batch* h = new desc_pgd_batch();
-        int rc;
-        try { rc = batch_create(probs, count, p, seeds, h); }
-        catch (...) { batch_free(h); throw; }
-        if (rc) { const std::string msg = desc_last_error(); batch_free(h); return fail(rc, "%s", msg.c_str()); }
-        *out = h;
-        return DESC_OK;
-    });
+    return batch_create_guarded("desc_pgd_batch_create", out, probs, count,
+                                [&](desc_pgd_batch* h) { return batch_create(probs, count, p, seeds, h); }, p != nullptr);
 }
 
 int desc_pgd_batch_sizes(const desc_pgd_batch* h, int32_t* count, int64_t* edge_off, int64_t* cycle_off, int32_t* n_sample) {
@@ -659,7 +603,7 @@ int desc_pgd_batch_run(desc_pgd_batch* h, const desc_params* p, desc_batch_resul
     });
 }
 
-void desc_pgd_batch_destroy(desc_pgd_batch* h) { batch_free(h); }
+void desc_pgd_batch_destroy(desc_pgd_batch* h) { delete h; }
 
 int desc_pgd_batch_concat(const desc_structure* const* s, int32_t count, int64_t* edge_off, int64_t* cycle_off, int64_t* seg_off,
                           int32_t* pos_edge, int32_t* cum, int32_t* e_jk, int32_t* e_ki, int32_t* ikj, int32_t* jki) {

@@ -34,7 +34,7 @@
 
 #include "batch_csr.h"
 #include "cemp_math.h"
-#include "device_utils.h"
+#include "batch_device.h"
 
 namespace desc {
 namespace {
@@ -149,37 +149,17 @@ __global__ __launch_bounds__(256) void k_cemp_batch_round(const int32_t* e_jk, c
 
 using namespace desc;
 
-struct desc_cemp_batch : desc::BatchCsr {
-    int device = 0;
+struct desc_cemp_batch : desc::BatchCsr, desc::BatchDevice {
     int32_t nsample = 0, max_deg = 0, grid = 1;
-    hipStream_t stream = nullptr;
-    DevArena mem;
     CbArgs a{};
-    double ms_structure = 0, ms_upload = 0, ms_build = 0;
+    double ms_build = 0;
 };
 
 namespace {
 
-void cb_free(desc_cemp_batch* h) {
-    if (!h) return;
-    if (h->stream) { (void)hipSetDevice(h->device); (void)hipStreamSynchronize(h->stream); }
-    h->mem.release();
-    if (h->stream) stream_release(h->stream);
-    delete h;
-}
-
-template <class T>
-int cb_upload(desc_cemp_batch* h, const T** dst, const T* src, size_t n) {
-    T* d = nullptr;
-    int rc = h->mem.alloc(&d, n); if (rc) return rc;
-    if (n) DESC_HIP(hipMemcpyAsync(d, src, sizeof(T) * n, hipMemcpyHostToDevice, h->stream));
-    *dst = d;
-    return DESC_OK;
-}
-
 int cb_create(const desc_problem* probs, int32_t count, int32_t nsample, uint64_t seed, const uint64_t* seeds, int32_t device, desc_cemp_batch* h) {
     auto t0 = std::chrono::steady_clock::now();
-    h->device = device; h->nsample = nsample;
+    h->nsample = nsample;
     if (nsample < 1) return fail(DESC_ERR_INVALID, "need nsample >= 1");
     // ---- host: validation, the per-problem CSR, the degree maxima
     int rc = batch_csr_host(probs, count, nullptr, h);
@@ -199,30 +179,22 @@ int cb_create(const desc_problem* probs, int32_t count, int32_t nsample, uint64_
     h->ms_structure = ms_since(t0);
     if (count == 0) return DESC_OK;
 
-    // ---- device: nothing above touched it
-    int ndev = desc_device_count();
-    if (ndev < 0) return ndev;
-    if (ndev == 0) return fail(DESC_ERR_HIP, "no HIP device visible: the batched CEMP has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(DESC_ERR_INVALID, "device %d out of range (0..%d)", device, ndev - 1);
-    hipError_t he = hipSetDevice(device);
-    if (he == hipSuccess) he = stream_acquire(&h->stream);
-    if (he != hipSuccess) return fail(DESC_ERR_HIP, "device %d: %s", device, hipGetErrorString(he));
+    if ((rc = h->open(device, "the batched CEMP"))) return rc;             // nothing above touched the device
     auto t1 = std::chrono::steady_clock::now();
     const size_t M = (size_t)h->M, MC = M * (size_t)nsample;
     hvec<CbProb> pr((size_t)count);
     hvec<int32_t> eprob(M);
-    hvec<double> rij(9 * M);                           // all rotations in one copy
     for (int32_t b = 0; b < count; ++b) {
         const size_t eo = (size_t)h->edge_off[(size_t)b], m = (size_t)probs[b].m;
         pr[(size_t)b] = CbProb{(int32_t)probs[b].n, (int32_t)m, (int32_t)h->node_off[(size_t)b], (int32_t)eo, seeds ? seeds[b] : seed};
         std::fill(eprob.begin() + eo, eprob.begin() + eo + m, b);
-        std::memcpy(rij.data() + 9 * eo, probs[b].rij, sizeof(double) * 9 * m);
     }
+    const hvec<double> rij = stage_rotations(probs, count, h->edge_off);
     CbArgs& a = h->a;
-    if ((rc = cb_upload(h, &a.prob, pr.data(), pr.size())) || (rc = cb_upload(h, &a.eprob, eprob.data(), M)) ||
-        (rc = cb_upload(h, &a.ii, h->ii.data(), M)) || (rc = cb_upload(h, &a.jj, h->jj.data(), M)) ||
-        (rc = cb_upload(h, &a.rowptr, h->rowptr.data(), h->rowptr.size())) || (rc = cb_upload(h, &a.adj, h->adj.data(), 2 * M)) ||
-        (rc = cb_upload(h, &a.adj_eid, h->adj_eid.data(), 2 * M)) || (rc = cb_upload(h, &a.rij, rij.data(), 9 * M))) return rc;
+    if ((rc = h->upload(&a.prob, pr.data(), pr.size())) || (rc = h->upload(&a.eprob, eprob.data(), M)) ||
+        (rc = h->upload(&a.ii, h->ii.data(), M)) || (rc = h->upload(&a.jj, h->jj.data(), M)) ||
+        (rc = h->upload(&a.rowptr, h->rowptr.data(), h->rowptr.size())) || (rc = h->upload(&a.adj, h->adj.data(), 2 * M)) ||
+        (rc = h->upload(&a.adj_eid, h->adj_eid.data(), 2 * M)) || (rc = h->upload(&a.rij, rij.data(), 9 * M))) return rc;
     if ((rc = h->mem.alloc(&a.e_jk, MC)) || (rc = h->mem.alloc(&a.e_ki, MC)) || (rc = h->mem.alloc(&a.S0, MC)) || (rc = h->mem.alloc(&a.S_init, M)) ||
         (rc = h->mem.alloc(&a.S_a, M)) || (rc = h->mem.alloc(&a.S_b, M)) || (rc = h->mem.alloc(&a.has_cycle, M))) return rc;
     DESC_HIP(hipStreamSynchronize(h->stream));         // the staging vectors go out of scope below
@@ -275,26 +247,13 @@ int32_t desc_cemp_batch_max_degree(void) { return CEMP_BATCH_MAX_DEGREE; }
 
 int desc_cemp_batch_create(const desc_problem* probs, int32_t count, int32_t nsample, uint64_t seed, const uint64_t* seeds, int32_t device,
                            desc_cemp_batch** out) {
-    return no_throw("desc_cemp_batch_create", [&]() -> int {
-        if (!out) return fail(DESC_ERR_INVALID, "out is NULL");
-        *out = nullptr;
-        if (count < 0 || (count > 0 && !probs)) return fail(DESC_ERR_INVALID, "NULL argument or negative count");
-        desc_cemp_batch* h = new desc_cemp_batch();
-        int rc;
-        try { rc = cb_create(probs, count, nsample, seed, seeds, device, h); }
-        catch (...) { cb_free(h); throw; }
-        if (rc) { const std::string msg = desc_last_error(); cb_free(h); return fail(rc, "%s", msg.c_str()); }
-        *out = h;
-        return DESC_OK;
-    });
+    return batch_create_guarded("desc_cemp_batch_create", out, probs, count,
+                                [&](desc_cemp_batch* h) { return cb_create(probs, count, nsample, seed, seeds, device, h); });
 }
 
 int desc_cemp_batch_sizes(const desc_cemp_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off) {
     if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
-    if (count) *count = h->count;
-    if (node_off) std::copy(h->node_off.begin(), h->node_off.end(), node_off);
-    if (edge_off) std::copy(h->edge_off.begin(), h->edge_off.end(), edge_off);
-    return DESC_OK;
+    return batch_sizes(*h, count, node_off, edge_off);
 }
 
 int desc_cemp_batch_get_samples(desc_cemp_batch* h, int32_t* e_jk, int32_t* e_ki, double* s0, uint8_t* has_cycle) {
@@ -324,6 +283,6 @@ int desc_cemp_batch_run(desc_cemp_batch* h, const double* beta, int32_t n_beta, 
     });
 }
 
-void desc_cemp_batch_destroy(desc_cemp_batch* h) { cb_free(h); }
+void desc_cemp_batch_destroy(desc_cemp_batch* h) { delete h; }
 
 }  // extern "C"

@@ -35,7 +35,7 @@
 #include <vector>
 
 #include "batch_csr.h"
-#include "device_utils.h"
+#include "batch_device.h"
 #include "small_dense.h"
 
 namespace desc {
@@ -359,18 +359,15 @@ int batch_csr_host(const desc_problem* probs, int32_t count, const std::function
         return fail(DESC_ERR_TOO_LARGE, "the batch holds %lld edges in total: the 2^30 index budget is exceeded, split the batch", (long long)h->M);
     h->ii.resize((size_t)h->M); h->jj.resize((size_t)h->M);
     h->rowptr.resize((size_t)h->N + (size_t)count); h->adj.resize(2 * (size_t)h->M); h->adj_eid.resize(2 * (size_t)h->M);
-    const int T = std::max(1, std::min(count, 16));
-    run_threads(T, [&](int t) {
+    for_each_problem(count, [&](int32_t b) {
         hvec<int32_t> rp, ad, ae;
-        for (int32_t b = t; b < count; b += T) {
-            const int64_t n = probs[b].n, m = probs[b].m, eo = h->edge_off[(size_t)b];
-            std::memcpy(h->ii.data() + eo, probs[b].ind_i, sizeof(int32_t) * (size_t)m);
-            std::memcpy(h->jj.data() + eo, probs[b].ind_j, sizeof(int32_t) * (size_t)m);
-            build_csr(n, m, probs[b].ind_i, probs[b].ind_j, rp, ad, ae);
-            std::memcpy(h->rowptr.data() + h->node_off[(size_t)b] + b, rp.data(), sizeof(int32_t) * (size_t)(n + 1));
-            std::memcpy(h->adj.data() + 2 * eo, ad.data(), sizeof(int32_t) * 2 * (size_t)m);
-            std::memcpy(h->adj_eid.data() + 2 * eo, ae.data(), sizeof(int32_t) * 2 * (size_t)m);
-        }
+        const int64_t n = probs[b].n, m = probs[b].m, eo = h->edge_off[(size_t)b];
+        std::memcpy(h->ii.data() + eo, probs[b].ind_i, sizeof(int32_t) * (size_t)m);
+        std::memcpy(h->jj.data() + eo, probs[b].ind_j, sizeof(int32_t) * (size_t)m);
+        build_csr(n, m, probs[b].ind_i, probs[b].ind_j, rp, ad, ae);
+        std::memcpy(h->rowptr.data() + h->node_off[(size_t)b] + b, rp.data(), sizeof(int32_t) * (size_t)(n + 1));
+        std::memcpy(h->adj.data() + 2 * eo, ad.data(), sizeof(int32_t) * 2 * (size_t)m);
+        std::memcpy(h->adj_eid.data() + 2 * eo, ae.data(), sizeof(int32_t) * 2 * (size_t)m);
     });
     return DESC_OK;
 }
@@ -379,33 +376,14 @@ int batch_csr_host(const desc_problem* probs, int32_t count, const std::function
 
 using namespace desc;
 
-struct desc_gcw_batch : desc::BatchCsr {     // offsets and the per-problem CSR (local ids): batch_csr.h
-    int device = 0;
-    hipStream_t stream = nullptr;
-    DevArena mem;
+struct desc_gcw_batch : desc::BatchCsr, desc::BatchDevice {     // offsets and the per-problem CSR (local ids); device, stream, arena, events
     GbProb* d_prob = nullptr;
     int32_t *d_rowptr = nullptr, *d_adj = nullptr, *d_adj_eid = nullptr;
     double *d_rij = nullptr, *d_in = nullptr, *d_w = nullptr, *d_dinv = nullptr, *d_blocks = nullptr, *d_V = nullptr;
     GbInfo* d_info = nullptr;
-    double ms_structure = 0, ms_upload = 0;
 };
 
 namespace {
-
-void gb_free(desc_gcw_batch* h) {
-    if (!h) return;
-    if (h->stream) { (void)hipSetDevice(h->device); (void)hipStreamSynchronize(h->stream); }
-    h->mem.release();
-    if (h->stream) stream_release(h->stream);
-    delete h;
-}
-
-template <class T>
-int gb_upload(desc_gcw_batch* h, T** dst, const T* src, size_t n) {
-    int rc = h->mem.alloc(dst, n); if (rc) return rc;
-    if (n) DESC_HIP(hipMemcpyAsync(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice, h->stream));
-    return DESC_OK;
-}
 
 // validation, offsets and the per-problem CSR: no device
 int gb_host_part(const desc_problem* probs, int32_t count, desc_gcw_batch* h) {
@@ -419,31 +397,22 @@ int gb_host_part(const desc_problem* probs, int32_t count, desc_gcw_batch* h) {
 
 int gb_create(const desc_problem* probs, int32_t count, int32_t device, desc_gcw_batch* h) {
     auto t0 = std::chrono::steady_clock::now();
-    h->device = device;
     int rc = gb_host_part(probs, count, h);
     if (rc) return rc;
     h->ms_structure = ms_since(t0);
     if (count == 0) return DESC_OK;
 
-    // ---- device: nothing above touched it
-    int ndev = desc_device_count();
-    if (ndev < 0) return ndev;
-    if (ndev == 0) return fail(DESC_ERR_HIP, "no HIP device visible: the batched eigen-solve has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(DESC_ERR_INVALID, "device %d out of range (0..%d)", device, ndev - 1);
-    hipError_t he = hipSetDevice(device);
-    if (he == hipSuccess) he = stream_acquire(&h->stream);
-    if (he != hipSuccess) return fail(DESC_ERR_HIP, "device %d: %s", device, hipGetErrorString(he));
+    if ((rc = h->open(device, "the batched eigen-solve"))) return rc;      // nothing above touched the device
     auto t1 = std::chrono::steady_clock::now();
     const size_t M = (size_t)h->M, N = (size_t)h->N;
     hvec<GbProb> pr((size_t)count);
     for (int32_t b = 0; b < count; ++b) pr[(size_t)b] = GbProb{(int32_t)probs[b].n, (int32_t)probs[b].m, h->node_off[(size_t)b], h->edge_off[(size_t)b]};
-    hvec<double> rij(9 * M);                           // all rotations in one copy
-    for (int32_t b = 0; b < count; ++b) std::memcpy(rij.data() + 9 * (size_t)h->edge_off[(size_t)b], probs[b].rij, sizeof(double) * 9 * (size_t)probs[b].m);
-    if ((rc = gb_upload(h, &h->d_prob, pr.data(), pr.size()))) return rc;
-    if ((rc = gb_upload(h, &h->d_rowptr, h->rowptr.data(), h->rowptr.size()))) return rc;
-    if ((rc = gb_upload(h, &h->d_adj, h->adj.data(), 2 * M))) return rc;
-    if ((rc = gb_upload(h, &h->d_adj_eid, h->adj_eid.data(), 2 * M))) return rc;
-    if ((rc = gb_upload(h, &h->d_rij, rij.data(), 9 * M))) return rc;
+    const hvec<double> rij = stage_rotations(probs, count, h->edge_off);
+    if ((rc = h->upload(&h->d_prob, pr.data(), pr.size()))) return rc;
+    if ((rc = h->upload(&h->d_rowptr, h->rowptr.data(), h->rowptr.size()))) return rc;
+    if ((rc = h->upload(&h->d_adj, h->adj.data(), 2 * M))) return rc;
+    if ((rc = h->upload(&h->d_adj_eid, h->adj_eid.data(), 2 * M))) return rc;
+    if ((rc = h->upload(&h->d_rij, rij.data(), 9 * M))) return rc;
     if ((rc = h->mem.alloc(&h->d_in, M)) || (rc = h->mem.alloc(&h->d_w, M)) || (rc = h->mem.alloc(&h->d_dinv, N)) ||
         (rc = h->mem.alloc(&h->d_blocks, 18 * M)) || (rc = h->mem.alloc(&h->d_V, 9 * N)) || (rc = h->mem.alloc(&h->d_info, (size_t)count))) return rc;
     DESC_HIP(hipStreamSynchronize(h->stream));         // the staging vectors go out of scope below
@@ -459,17 +428,15 @@ int gb_run(desc_gcw_batch* h, const double* s_vec, const double* weights, int32_
     if (count == 0) { if (tm) tm->ms_total = ms_since(t0); return DESC_OK; }
     if (!R_out || !infos) return fail(DESC_ERR_INVALID, "R_out or infos is NULL");
     if (s_vec && weights) return fail(DESC_ERR_INVALID, "s_vec and weights are both set: pass one of them");
-    // the single call refuses what makes a weighted degree non-finite, naming the node; here the entries themselves are checked
     const double* in = s_vec ? s_vec : weights;
-    if (in)
-        for (int32_t b = 0; b < count; ++b)
-            for (int64_t e = h->edge_off[(size_t)b]; e < h->edge_off[(size_t)b + 1]; ++e) {
-                const double x = in[e];
-                if (!(x >= 0) || !std::isfinite(x)) {
-                    if (s_vec) return fail(DESC_ERR_INVALID, "problem %d: S_vec holds a negative or non-finite entry (node %d)", b, (int)h->ii[(size_t)e]);
+    int rc;
+    for (int32_t b = 0; b < count; ++b) {
+        if (s_vec && (rc = check_s_vec_nonneg(*h, b, s_vec))) return rc;
+        if (weights)
+            for (int64_t e = h->edge_off[(size_t)b]; e < h->edge_off[(size_t)b + 1]; ++e)
+                if (!(weights[e] >= 0) || !std::isfinite(weights[e]))
                     return fail(DESC_ERR_INVALID, "problem %d: weight %lld is not a finite non-negative number", b, (long long)(e - h->edge_off[(size_t)b]));
-                }
-            }
+    }
     DESC_HIP(hipSetDevice(h->device));
     const size_t M = (size_t)h->M, N = (size_t)h->N;
     if (in) DESC_HIP(hipMemcpyAsync(h->d_in, in, sizeof(double) * M, hipMemcpyHostToDevice, h->stream));
@@ -481,34 +448,29 @@ int gb_run(desc_gcw_batch* h, const double* s_vec, const double* weights, int32_
     const size_t lds = gb_lds_bytes(h->max_n);
     if (lds > (size_t)GB_LDS_BYTES) return fail(DESC_ERR_STATE, "LDS budget exceeded (%zu bytes)", lds);
     if (lds > 64 * 1024) DESC_HIP(hipFuncSetAttribute((const void*)k_gcw_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipEvent_t e0, e1;
-    DESC_HIP(hipEventCreate(&e0)); DESC_HIP(hipEventCreate(&e1));
-    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } guard{e0, e1};
-    DESC_HIP(hipEventRecord(e0, h->stream));
+    if ((rc = h->timer_begin())) return rc;
     hipLaunchKernelGGL(k_gcw_batch, dim3((unsigned)count), dim3(256), lds, h->stream, a);
     DESC_HIP(hipGetLastError());
-    DESC_HIP(hipEventRecord(e1, h->stream));
+    if ((rc = h->timer_end())) return rc;
     hvec<GbInfo> inf((size_t)count);
     hvec<double> V(9 * N), dinv(N);
     DESC_HIP(hipMemcpyAsync(inf.data(), h->d_info, sizeof(GbInfo) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
     DESC_HIP(hipMemcpyAsync(V.data(), h->d_V, sizeof(double) * 9 * N, hipMemcpyDeviceToHost, h->stream));
     DESC_HIP(hipMemcpyAsync(dinv.data(), h->d_dinv, sizeof(double) * N, hipMemcpyDeviceToHost, h->stream));
     DESC_HIP(hipStreamSynchronize(h->stream));
-    float ms = 0; DESC_HIP(hipEventElapsedTime(&ms, e0, e1));
+    float ms = 0;
+    if ((rc = h->timer_ms(&ms))) return rc;
     for (int32_t b = 0; b < count; ++b) {
         if (inf[(size_t)b].status == 1) return fail(DESC_ERR_INVALID, "problem %d: degenerate start basis", b);
         if (inf[(size_t)b].status) return fail(DESC_ERR_INVALID, "problem %d: subspace iteration broke down (rank-deficient block)", b);
     }
     // ---- the tail of spectral_impl per problem on host threads
     auto t1 = std::chrono::steady_clock::now();
-    const int T = std::max(1, std::min(count, 16));
-    run_threads(T, [&](int t) {
-        for (int32_t b = t; b < count; b += T) {
-            const int64_t no = h->node_off[(size_t)b], n = h->node_off[(size_t)b + 1] - no;
-            double* Vb = V.data() + 9 * (size_t)no;
-            ritz_scale_sign(Vb, a.normalize ? dinv.data() + no : nullptr, n);
-            project_nodes(Vb, 0, n, R_out + 9 * (size_t)no);
-        }
+    for_each_problem(count, [&](int32_t b) {
+        const int64_t no = h->node_off[(size_t)b], n = h->node_off[(size_t)b + 1] - no;
+        double* Vb = V.data() + 9 * (size_t)no;
+        ritz_scale_sign(Vb, a.normalize ? dinv.data() + no : nullptr, n);
+        project_nodes(Vb, 0, n, R_out + 9 * (size_t)no);
     });
     const double ms_project = ms_since(t1), ms_total = ms_since(t0);
     for (int32_t b = 0; b < count; ++b) {
@@ -529,26 +491,12 @@ extern "C" {
 int32_t desc_gcw_batch_max_n(void) { return GCW_BATCH_MAX_N; }
 
 int desc_gcw_batch_create(const desc_problem* probs, int32_t count, int32_t device, desc_gcw_batch** out) {
-    return no_throw("desc_gcw_batch_create", [&]() -> int {
-        if (!out) return fail(DESC_ERR_INVALID, "out is NULL");
-        *out = nullptr;
-        if (count < 0 || (count > 0 && !probs)) return fail(DESC_ERR_INVALID, "NULL argument or negative count");
-        desc_gcw_batch* h = new desc_gcw_batch();
-        int rc;
-        try { rc = gb_create(probs, count, device, h); }
-        catch (...) { gb_free(h); throw; }
-        if (rc) { const std::string msg = desc_last_error(); gb_free(h); return fail(rc, "%s", msg.c_str()); }
-        *out = h;
-        return DESC_OK;
-    });
+    return batch_create_guarded("desc_gcw_batch_create", out, probs, count, [&](desc_gcw_batch* h) { return gb_create(probs, count, device, h); });
 }
 
 int desc_gcw_batch_sizes(const desc_gcw_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off) {
     if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
-    if (count) *count = h->count;
-    if (node_off) std::copy(h->node_off.begin(), h->node_off.end(), node_off);
-    if (edge_off) std::copy(h->edge_off.begin(), h->edge_off.end(), edge_off);
-    return DESC_OK;
+    return batch_sizes(*h, count, node_off, edge_off);
 }
 
 int desc_gcw_batch_csr(const desc_problem* probs, int32_t count, int64_t* node_off, int64_t* edge_off, int32_t* rowptr, int32_t* adj, int32_t* adj_eid) {
@@ -557,8 +505,7 @@ int desc_gcw_batch_csr(const desc_problem* probs, int32_t count, int64_t* node_o
         desc_gcw_batch h;
         int rc = gb_host_part(probs, count, &h);
         if (rc) return rc;
-        std::copy(h.node_off.begin(), h.node_off.end(), node_off);
-        std::copy(h.edge_off.begin(), h.edge_off.end(), edge_off);
+        batch_sizes(h, nullptr, node_off, edge_off);
         if (rowptr) std::copy(h.rowptr.begin(), h.rowptr.end(), rowptr);
         if (adj) std::copy(h.adj.begin(), h.adj.end(), adj);
         if (adj_eid) std::copy(h.adj_eid.begin(), h.adj_eid.end(), adj_eid);
@@ -574,6 +521,6 @@ int desc_gcw_batch_run(desc_gcw_batch* h, const double* s_vec, const double* wei
     });
 }
 
-void desc_gcw_batch_destroy(desc_gcw_batch* h) { gb_free(h); }
+void desc_gcw_batch_destroy(desc_gcw_batch* h) { delete h; }
 
 }  // extern "C"

@@ -23,7 +23,7 @@
 #include <vector>
 
 #include "batch_csr.h"
-#include "device_utils.h"
+#include "batch_device.h"
 #include "mst_key.h"
 
 namespace desc {
@@ -127,18 +127,6 @@ int mb_host_part(const desc_problem* probs, int32_t count, const double* s_vec, 
     return DESC_OK;
 }
 
-template <class T>
-int mb_upload(DevArena& mem, hipStream_t st, T** dst, const T* src, size_t n) {
-    int rc = mem.alloc(dst, n); if (rc) return rc;
-    if (n) DESC_HIP(hipMemcpyAsync(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice, st));
-    return DESC_OK;
-}
-
-struct StreamGuard {
-    hipStream_t s = nullptr;
-    ~StreamGuard() { if (s) { (void)hipStreamSynchronize(s); stream_release(s); } }
-};
-
 int mb_run(const desc_problem* probs, int32_t count, const double* s_vec, int32_t device, double* R_out, int32_t* tree_edges, desc_mst_batch_timings* tm) {
     auto t0 = std::chrono::steady_clock::now();
     if (tm) { tm->ms_structure = 0; tm->ms_upload = 0; tm->ms_tree = 0; tm->ms_propagate = 0; tm->ms_total = 0; }
@@ -149,37 +137,29 @@ int mb_run(const desc_problem* probs, int32_t count, const double* s_vec, int32_
     if (rc) return rc;
     const double ms_structure = ms_since(t0);
 
-    // ---- device: nothing above touched it
-    int ndev = desc_device_count();
-    if (ndev < 0) return ndev;
-    if (ndev == 0) return fail(DESC_ERR_HIP, "no HIP device visible: the batched tree step has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(DESC_ERR_INVALID, "device %d out of range (0..%d)", device, ndev - 1);
-    StreamGuard sg;
-    DevArena mem;                                      // released before the stream (declared after it)
-    hipError_t he = hipSetDevice(device);
-    if (he == hipSuccess) he = stream_acquire(&sg.s);
-    if (he != hipSuccess) return fail(DESC_ERR_HIP, "device %d: %s", device, hipGetErrorString(he));
+    BatchDevice dev;                                   // this call's own: gone, stream drained, at every return below
+    if ((rc = dev.open(device, "the batched tree step"))) return rc;        // nothing above touched the device
     auto t1 = std::chrono::steady_clock::now();
     const size_t M = (size_t)h.M, N = (size_t)h.N;
     hvec<MbProb> pr((size_t)count);
     for (int32_t b = 0; b < count; ++b) pr[(size_t)b] = MbProb{(int32_t)probs[b].n, (int32_t)probs[b].m, (int32_t)h.node_off[(size_t)b], (int32_t)h.edge_off[(size_t)b]};
     MbProb* d_prob; int32_t *d_rowptr, *d_adj, *d_eid, *d_tree, *d_status; double* d_s;
-    if ((rc = mb_upload(mem, sg.s, &d_prob, (const MbProb*)pr.data(), pr.size())) || (rc = mb_upload(mem, sg.s, &d_rowptr, (const int32_t*)h.rowptr.data(), h.rowptr.size())) ||
-        (rc = mb_upload(mem, sg.s, &d_adj, (const int32_t*)h.adj.data(), 2 * M)) || (rc = mb_upload(mem, sg.s, &d_eid, (const int32_t*)h.adj_eid.data(), 2 * M)) ||
-        (rc = mb_upload(mem, sg.s, &d_s, s_vec, M)) || (rc = mem.alloc(&d_tree, N)) || (rc = mem.alloc(&d_status, (size_t)count))) return rc;
-    DESC_HIP(hipMemsetAsync(d_status, 0xFF, sizeof(int32_t) * (size_t)count, sg.s));       // -1: the workgroup never finished
-    DESC_HIP(hipStreamSynchronize(sg.s));
+    if ((rc = dev.upload(&d_prob, pr.data(), pr.size())) || (rc = dev.upload(&d_rowptr, h.rowptr.data(), h.rowptr.size())) ||
+        (rc = dev.upload(&d_adj, h.adj.data(), 2 * M)) || (rc = dev.upload(&d_eid, h.adj_eid.data(), 2 * M)) ||
+        (rc = dev.upload(&d_s, s_vec, M)) || (rc = dev.mem.alloc(&d_tree, N)) || (rc = dev.mem.alloc(&d_status, (size_t)count))) return rc;
+    DESC_HIP(hipMemsetAsync(d_status, 0xFF, sizeof(int32_t) * (size_t)count, dev.stream));       // -1: the workgroup never finished
+    DESC_HIP(hipStreamSynchronize(dev.stream));
     const double ms_upload = ms_since(t1);
 
     auto t2 = std::chrono::steady_clock::now();
     const size_t lds = (size_t)16 * (size_t)h.max_n;
     if (lds > 64 * 1024) return fail(DESC_ERR_STATE, "LDS budget exceeded (%zu bytes)", lds);
-    hipLaunchKernelGGL(k_mst_batch, dim3((unsigned)count), dim3(256), lds, sg.s, d_prob, d_rowptr, d_adj, d_eid, d_s, d_tree, d_status);
+    hipLaunchKernelGGL(k_mst_batch, dim3((unsigned)count), dim3(256), lds, dev.stream, d_prob, d_rowptr, d_adj, d_eid, d_s, d_tree, d_status);
     DESC_HIP(hipGetLastError());
     hvec<int32_t> tree(std::max<size_t>(N, 1)), status((size_t)count);
-    DESC_HIP(hipMemcpyAsync(status.data(), d_status, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, sg.s));
-    if (N > (size_t)count) DESC_HIP(hipMemcpyAsync(tree.data(), d_tree, sizeof(int32_t) * (N - (size_t)count), hipMemcpyDeviceToHost, sg.s));
-    DESC_HIP(hipStreamSynchronize(sg.s));
+    DESC_HIP(hipMemcpyAsync(status.data(), d_status, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, dev.stream));
+    if (N > (size_t)count) DESC_HIP(hipMemcpyAsync(tree.data(), d_tree, sizeof(int32_t) * (N - (size_t)count), hipMemcpyDeviceToHost, dev.stream));
+    DESC_HIP(hipStreamSynchronize(dev.stream));
     const double ms_tree = ms_since(t2);
     for (int32_t b = 0; b < count; ++b)
         if (status[(size_t)b] != 0)
@@ -188,23 +168,19 @@ int mb_run(const desc_problem* probs, int32_t count, const double* s_vec, int32_
     // ---- rooting and propagation (MPLS.m:171-193) per problem on host threads: the tail of mst_device
     auto t3 = std::chrono::steady_clock::now();
     hvec<int32_t> prc((size_t)count, DESC_OK);
-    const int T = std::max(1, std::min(count, 16));
-    run_threads(T, [&](int t) {
-        hvec<double> blk;
-        for (int32_t b = t; b < count; b += T) {
-            const int64_t no = h.node_off[(size_t)b], n = probs[b].n;
-            int32_t* ids = tree.data() + no - b;
-            const int cnt = (int)(n - 1);
-            bool ok = true;
-            for (int q = 0; q < cnt; ++q) ok = ok && ids[q] >= 0 && ids[q] < probs[b].m;
-            if (!ok) { prc[(size_t)b] = DESC_ERR_STATE; continue; }
-            blk.resize((size_t)9 * (size_t)std::max(cnt, 1));
-            for (int q = 0; q < cnt; ++q) std::memcpy(&blk[9 * (size_t)q], probs[b].rij + 9 * (size_t)ids[q], 72);
-            prc[(size_t)b] = mst_propagate(n, probs[b].ind_i, probs[b].ind_j, ids, cnt, blk.data(), R_out + 9 * (size_t)no);
-            if (tree_edges && prc[(size_t)b] == DESC_OK) {
-                std::sort(ids, ids + cnt);
-                std::copy(ids, ids + cnt, tree_edges + no - b);
-            }
+    for_each_problem(count, [&](int32_t b) {
+        const int64_t no = h.node_off[(size_t)b], n = probs[b].n;
+        int32_t* ids = tree.data() + no - b;
+        const int cnt = (int)(n - 1);
+        bool ok = true;
+        for (int q = 0; q < cnt; ++q) ok = ok && ids[q] >= 0 && ids[q] < probs[b].m;
+        if (!ok) { prc[(size_t)b] = DESC_ERR_STATE; return; }
+        hvec<double> blk((size_t)9 * (size_t)std::max(cnt, 1));
+        for (int q = 0; q < cnt; ++q) std::memcpy(&blk[9 * (size_t)q], probs[b].rij + 9 * (size_t)ids[q], 72);
+        prc[(size_t)b] = mst_propagate(n, probs[b].ind_i, probs[b].ind_j, ids, cnt, blk.data(), R_out + 9 * (size_t)no);
+        if (tree_edges && prc[(size_t)b] == DESC_OK) {
+            std::sort(ids, ids + cnt);
+            std::copy(ids, ids + cnt, tree_edges + no - b);
         }
     });
     for (int32_t b = 0; b < count; ++b)

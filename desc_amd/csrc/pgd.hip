@@ -2177,21 +2177,7 @@ StepArgs make_step(desc_pgd* h, bool* adam, int rd, int wr) {
     StepArgs s{};
     s.adam_m = h->d_adam_m[rd]; s.adam_v = h->d_adam_v[rd]; s.adam_m_out = h->d_adam_m[wr]; s.adam_v_out = h->d_adam_v[wr];
     // one GetStep call per iteration (DESC_PGD.m:207): the plugin counter advances first
-    const int tp = ++h->t_plugin;
-    s.lr = p.lr; s.beta1 = p.beta1; s.beta2 = p.beta2; s.bc1 = 1.0; s.bc2 = 1.0;
-    s.step = p.lr;
-    *adam = false;
-    if (p.step_kind == DESC_STEP_PIECEWISE) {
-        s.step = p.lr / (std::trunc((double)tp / p.decay_interval) + 1.0);            // PiecewiseStepSize.m:16
-    } else if (p.step_kind == DESC_STEP_HYBRID) {
-        if (p.hybrid_strategy == 0) {
-            *adam = true;
-            s.bc1 = 1.0 - std::pow(p.beta1, (double)tp);                             // HybridGradient.m:32-33
-            s.bc2 = 1.0 - std::pow(p.beta2, (double)tp);
-        } else {
-            s.step = 100.0 * (p.lr / (std::trunc((double)tp / p.decay_interval) + 1.0));   // HybridGradient.m:39
-        }
-    }
+    *adam = plugin_step(p, ++h->t_plugin, s);
     return s;
 }
 

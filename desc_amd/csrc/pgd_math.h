@@ -17,6 +17,24 @@ struct StepArgs {
     double lr, beta1, beta2, bc1, bc2;    // Adam (HybridGradient.m:28-35)
 };
 
+// The built-in plugins' GetStep call number tp (host): step size and Adam bias corrections into s, whose moment pointers are the
+// caller's.  Returns whether the sweep runs the Adam update (HybridGradient, strategy 0).
+inline bool plugin_step(const desc_params& p, int tp, StepArgs& s) {
+    s.lr = p.lr; s.beta1 = p.beta1; s.beta2 = p.beta2; s.bc1 = 1.0; s.bc2 = 1.0;
+    s.step = p.lr;
+    if (p.step_kind == DESC_STEP_PIECEWISE) {
+        s.step = p.lr / (std::trunc((double)tp / p.decay_interval) + 1.0);            // PiecewiseStepSize.m:16
+    } else if (p.step_kind == DESC_STEP_HYBRID) {
+        if (p.hybrid_strategy == 0) {
+            s.bc1 = 1.0 - std::pow(p.beta1, (double)tp);                             // HybridGradient.m:32-33
+            s.bc2 = 1.0 - std::pow(p.beta2, (double)tp);
+            return true;
+        }
+        s.step = 100.0 * (p.lr / (std::trunc((double)tp / p.decay_interval) + 1.0));   // HybridGradient.m:39
+    }
+    return false;
+}
+
 __device__ __forceinline__ double abs_acos_ext(double x) {
     // MATLAB abs(acos(x)) with the complex extension outside [-1,1] (DESC_PGD.m:147)
     if (x > 1.0) return acosh(x);

@@ -34,7 +34,7 @@
 #include <vector>
 
 #include "batch_csr.h"
-#include "device_utils.h"
+#include "batch_device.h"
 #include "laa_math.h"
 #include "mst_key.h"
 
@@ -302,38 +302,16 @@ __global__ __launch_bounds__(256) void k_refine_batch(RbArgs a) {
 
 using namespace desc;
 
-struct desc_refine_batch : desc::BatchCsr {  // offsets and the per-problem CSR (local ids): batch_csr.h
-    int device = 0;
-    hipStream_t stream = nullptr;
-    DevArena mem;
+struct desc_refine_batch : desc::BatchCsr, desc::BatchDevice {  // offsets and the per-problem CSR (local ids); device, stream, arena, events
     RbProb* d_prob = nullptr;
     int32_t *d_rowptr = nullptr, *d_adj = nullptr, *d_adj_eid = nullptr, *d_ii = nullptr, *d_jj = nullptr;
     int8_t* d_sgn = nullptr;
     double *d_rij = nullptr, *d_S = nullptr, *d_thresh0 = nullptr, *d_Rinit = nullptr, *d_Rout = nullptr, *d_B = nullptr, *d_w = nullptr, *d_RS = nullptr;
     Quat* d_QQ = nullptr;
     RbInfo* d_info = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;        // around the launch of a run; made once in create
-    double ms_structure = 0, ms_upload = 0;
 };
 
 namespace {
-
-void rb_free(desc_refine_batch* h) {
-    if (!h) return;
-    if (h->stream) { (void)hipSetDevice(h->device); (void)hipStreamSynchronize(h->stream); }
-    h->mem.release();
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) stream_release(h->stream);
-    delete h;
-}
-
-template <class T>
-int rb_upload(desc_refine_batch* h, T** dst, const T* src, size_t n) {
-    int rc = h->mem.alloc(dst, n); if (rc) return rc;
-    if (n) DESC_HIP(hipMemcpyAsync(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice, h->stream));
-    return DESC_OK;
-}
 
 // validation, offsets and the per-problem CSR: no device
 int rb_host_part(const desc_problem* probs, int32_t count, desc_refine_batch* h) {
@@ -347,7 +325,6 @@ int rb_host_part(const desc_problem* probs, int32_t count, desc_refine_batch* h)
 
 int rb_create(const desc_problem* probs, int32_t count, int32_t device, desc_refine_batch* h) {
     auto t0 = std::chrono::steady_clock::now();
-    h->device = device;
     int rc = rb_host_part(probs, count, h);
     if (rc) return rc;
     const size_t M = (size_t)h->M, N = (size_t)h->N;
@@ -361,29 +338,20 @@ int rb_create(const desc_problem* probs, int32_t count, int32_t device, desc_ref
     h->ms_structure = ms_since(t0);
     if (count == 0) return DESC_OK;
 
-    // ---- device: nothing above touched it
-    int ndev = desc_device_count();
-    if (ndev < 0) return ndev;
-    if (ndev == 0) return fail(DESC_ERR_HIP, "no HIP device visible: the batched refinement has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(DESC_ERR_INVALID, "device %d out of range (0..%d)", device, ndev - 1);
-    hipError_t he = hipSetDevice(device);
-    if (he == hipSuccess) he = stream_acquire(&h->stream);
-    if (he != hipSuccess) return fail(DESC_ERR_HIP, "device %d: %s", device, hipGetErrorString(he));
+    if ((rc = h->open(device, "the batched refinement"))) return rc;       // nothing above touched the device
     auto t1 = std::chrono::steady_clock::now();
     hvec<RbProb> pr((size_t)count);
     for (int32_t b = 0; b < count; ++b) pr[(size_t)b] = RbProb{(int32_t)probs[b].n, (int32_t)probs[b].m, h->node_off[(size_t)b], h->edge_off[(size_t)b]};
-    hvec<double> rij(9 * M);                           // all rotations in one copy
-    for (int32_t b = 0; b < count; ++b) std::memcpy(rij.data() + 9 * (size_t)h->edge_off[(size_t)b], probs[b].rij, sizeof(double) * 9 * (size_t)probs[b].m);
-    if ((rc = rb_upload(h, &h->d_prob, (const RbProb*)pr.data(), pr.size())) || (rc = rb_upload(h, &h->d_rowptr, (const int32_t*)h->rowptr.data(), h->rowptr.size())) ||
-        (rc = rb_upload(h, &h->d_adj, (const int32_t*)h->adj.data(), 2 * M)) || (rc = rb_upload(h, &h->d_adj_eid, (const int32_t*)h->adj_eid.data(), 2 * M)) ||
-        (rc = rb_upload(h, &h->d_sgn, (const int8_t*)sgn.data(), 2 * M)) || (rc = rb_upload(h, &h->d_ii, (const int32_t*)h->ii.data(), M)) ||
-        (rc = rb_upload(h, &h->d_jj, (const int32_t*)h->jj.data(), M)) || (rc = rb_upload(h, &h->d_rij, (const double*)rij.data(), 9 * M)))
+    const hvec<double> rij = stage_rotations(probs, count, h->edge_off);
+    if ((rc = h->upload(&h->d_prob, pr.data(), pr.size())) || (rc = h->upload(&h->d_rowptr, h->rowptr.data(), h->rowptr.size())) ||
+        (rc = h->upload(&h->d_adj, h->adj.data(), 2 * M)) || (rc = h->upload(&h->d_adj_eid, h->adj_eid.data(), 2 * M)) ||
+        (rc = h->upload(&h->d_sgn, sgn.data(), 2 * M)) || (rc = h->upload(&h->d_ii, h->ii.data(), M)) ||
+        (rc = h->upload(&h->d_jj, h->jj.data(), M)) || (rc = h->upload(&h->d_rij, rij.data(), 9 * M)))
         return rc;
     if ((rc = h->mem.alloc(&h->d_S, M)) || (rc = h->mem.alloc(&h->d_thresh0, (size_t)count)) || (rc = h->mem.alloc(&h->d_Rinit, 9 * N)) ||
         (rc = h->mem.alloc(&h->d_Rout, 9 * N)) || (rc = h->mem.alloc(&h->d_QQ, M)) || (rc = h->mem.alloc(&h->d_B, 3 * M)) ||
         (rc = h->mem.alloc(&h->d_w, M)) || (rc = h->mem.alloc(&h->d_RS, M)) || (rc = h->mem.alloc(&h->d_info, (size_t)count)))
         return rc;
-    DESC_HIP(hipEventCreate(&h->ev0)); DESC_HIP(hipEventCreate(&h->ev1));      // rb_free destroys whichever exists
     // the largest dynamic LDS any handle may ask for: the attribute belongs to the kernel, not to a handle, so it is never lowered
     DESC_HIP(hipFuncSetAttribute((const void*)k_refine_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rb_lds_bytes(REFINE_BATCH_MAX_N)));
     DESC_HIP(hipStreamSynchronize(h->stream));         // the staging vectors go out of scope below
@@ -401,15 +369,10 @@ int rb_run(desc_refine_batch* h, const double* s_vec, const double* R_init, doub
     if (stop_threshold <= 0) stop_threshold = 1e-3;     // DESC.m:272
     if (max_iters <= 0) max_iters = 100;
     hvec<double> thresh0((size_t)count);                // DESC.m:274-282: quantile(S_vec, 1) = max
+    int rc;
     for (int32_t b = 0; b < count; ++b) {
-        double mx = -INFINITY;
-        for (int64_t e = h->edge_off[(size_t)b]; e < h->edge_off[(size_t)b + 1]; ++e) {
-            const double x = s_vec[e];
-            if (!(x >= 0) || !std::isfinite(x))
-                return fail(DESC_ERR_INVALID, "problem %d: S_vec holds a negative or non-finite entry (node %d)", b, (int)h->ii[(size_t)e]);
-            mx = std::max(mx, x);
-        }
-        thresh0[(size_t)b] = mx;
+        if ((rc = check_s_vec_nonneg(*h, b, s_vec))) return rc;
+        thresh0[(size_t)b] = *std::max_element(s_vec + h->edge_off[(size_t)b], s_vec + h->edge_off[(size_t)b + 1]);      // no problem is without edges
         for (int64_t v = h->node_off[(size_t)b]; v < h->node_off[(size_t)b + 1]; ++v)
             for (int c = 0; c < 9; ++c)
                 if (!std::isfinite(R_init[9 * v + c]))
@@ -435,17 +398,17 @@ int rb_run(desc_refine_batch* h, const double* s_vec, const double* R_init, doub
     }
     const size_t lds = rb_lds_bytes(h->max_n);
     if (lds + RB_STATIC_BYTES > (size_t)RB_LDS_BYTES) return fail(DESC_ERR_STATE, "LDS budget exceeded (%zu bytes)", lds);
-    const hipEvent_t e0 = h->ev0, e1 = h->ev1;
-    DESC_HIP(hipEventRecord(e0, h->stream));
+    if ((rc = h->timer_begin())) return rc;
     hipLaunchKernelGGL(k_refine_batch, dim3((unsigned)count), dim3(256), lds, h->stream, a);
     DESC_HIP(hipGetLastError());
-    DESC_HIP(hipEventRecord(e1, h->stream));
+    if ((rc = h->timer_end())) return rc;
     hvec<RbInfo> inf((size_t)count);
     hvec<double> R(9 * N);
     DESC_HIP(hipMemcpyAsync(inf.data(), h->d_info, sizeof(RbInfo) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
     DESC_HIP(hipMemcpyAsync(R.data(), h->d_Rout, sizeof(double) * 9 * N, hipMemcpyDeviceToHost, h->stream));
     DESC_HIP(hipStreamSynchronize(h->stream));
-    float ms = 0; DESC_HIP(hipEventElapsedTime(&ms, e0, e1));
+    float ms = 0;
+    if ((rc = h->timer_ms(&ms))) return rc;
     for (int32_t b = 0; b < count; ++b) {
         const RbInfo& g = inf[(size_t)b];
         if (g.status == 1) return fail(DESC_ERR_STATE, "problem %d: the quantile selection found no candidate (step %d)", b, (int)g.iters + 1);
@@ -471,26 +434,12 @@ extern "C" {
 int32_t desc_refine_batch_max_n(void) { return REFINE_BATCH_MAX_N; }
 
 int desc_refine_batch_create(const desc_problem* probs, int32_t count, int32_t device, desc_refine_batch** out) {
-    return no_throw("desc_refine_batch_create", [&]() -> int {
-        if (!out) return fail(DESC_ERR_INVALID, "out is NULL");
-        *out = nullptr;
-        if (count < 0 || (count > 0 && !probs)) return fail(DESC_ERR_INVALID, "NULL argument or negative count");
-        desc_refine_batch* h = new desc_refine_batch();
-        int rc;
-        try { rc = rb_create(probs, count, device, h); }
-        catch (...) { rb_free(h); throw; }
-        if (rc) { const std::string msg = desc_last_error(); rb_free(h); return fail(rc, "%s", msg.c_str()); }
-        *out = h;
-        return DESC_OK;
-    });
+    return batch_create_guarded("desc_refine_batch_create", out, probs, count, [&](desc_refine_batch* h) { return rb_create(probs, count, device, h); });
 }
 
 int desc_refine_batch_sizes(const desc_refine_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off) {
     if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
-    if (count) *count = h->count;
-    if (node_off) std::copy(h->node_off.begin(), h->node_off.end(), node_off);
-    if (edge_off) std::copy(h->edge_off.begin(), h->edge_off.end(), edge_off);
-    return DESC_OK;
+    return batch_sizes(*h, count, node_off, edge_off);
 }
 
 int desc_refine_batch_run(desc_refine_batch* h, const double* s_vec, const double* R_init, double stop_threshold, int32_t max_iters,
@@ -501,6 +450,6 @@ int desc_refine_batch_run(desc_refine_batch* h, const double* s_vec, const doubl
     });
 }
 
-void desc_refine_batch_destroy(desc_refine_batch* h) { rb_free(h); }
+void desc_refine_batch_destroy(desc_refine_batch* h) { delete h; }
 
 }  // extern "C"
