@@ -40,6 +40,7 @@ EXPORTS = [
     "desc_cemp_batch_max_degree", "desc_cemp_batch_create", "desc_cemp_batch_sizes", "desc_cemp_batch_get_samples", "desc_cemp_batch_run",
     "desc_cemp_batch_destroy", "desc_mst_batch_max_n", "desc_mst_batch_check", "desc_mst_batch_run",
     "desc_refine_batch_max_n", "desc_refine_batch_create", "desc_refine_batch_sizes", "desc_refine_batch_run", "desc_refine_batch_destroy",
+    "desc_mpls_batch_max_n", "desc_mpls_batch_run",
     "desc_test_laa_r2q", "desc_test_laa_q2r", "desc_test_laa_edge_log", "desc_test_laa_rhs", "desc_test_laa_pcg", "desc_test_laa_node_update",
     "desc_test_irls_node_update", "desc_test_laa_weights", "desc_test_irls_weights", "desc_test_laa_quantile", "desc_test_irls_project",
 ]
@@ -127,6 +128,11 @@ class MstBatchTimings(C.Structure):
 
 class RefineBatchTimings(C.Structure):
     _fields_ = [("ms_structure", C.c_double), ("ms_upload", C.c_double), ("ms_input", C.c_double), ("ms_refine", C.c_double),
+                ("ms_total", C.c_double)]
+
+
+class MplsBatchTimings(C.Structure):
+    _fields_ = [("ms_setup", C.c_double), ("ms_input", C.c_double), ("ms_loop", C.c_double), ("ms_download", C.c_double),
                 ("ms_total", C.c_double)]
 
 
@@ -323,6 +329,10 @@ def load():
     L.desc_refine_batch_run.argtypes = [C.c_void_p, F64P, F64P, C.c_double, C.c_int32, F64P, C.POINTER(RefineInfo), C.POINTER(RefineBatchTimings)]
     L.desc_refine_batch_destroy.argtypes = [C.c_void_p]
     L.desc_refine_batch_destroy.restype = None
+    L.desc_mpls_batch_max_n.restype = C.c_int32
+    L.desc_mpls_batch_max_n.argtypes = []
+    L.desc_mpls_batch_run.argtypes = [C.c_void_p, F64P, F64P, C.c_double, C.c_int32, F64P, C.c_int32, F64P, C.c_int32, F64P, C.c_int32, F64P,
+                                      C.POINTER(MplsInfo), C.POINTER(MplsBatchTimings)]
     L.desc_test_laa_r2q.argtypes = [F64P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, F64P]
     L.desc_test_laa_q2r.argtypes = [F64P, C.c_int64, C.c_int32, F64P]
     L.desc_test_laa_edge_log.argtypes = [C.c_void_p, F64P, F64P, C.c_int64, F64P]
@@ -685,6 +695,30 @@ class CempBatch(_BatchHandle):
         outs = [S[int(self.edge_off[k]):int(self.edge_off[k + 1])] for k in range(self.count)]
         return outs, _timings(tm)
 
+    def mpls_run(self, s_vec, R_init, stop_threshold, max_iter, beta, tau, alpha):
+        """The MPLS loop (MPLS.m:196-254) of every problem in one launch, on the handle's samples (desc_mpls_batch_run).  s_vec: the
+        concatenated SVec (library's edge order, what ``run`` returned); R_init: the concatenated 9 n_b doubles per problem (3 x 3 x n_b
+        column-major); beta / tau / alpha: MPLS_parameters.reweighting / .thresholding / .cycle_info_ratio.  Returns a list of per-problem
+        (R_est (3,3,n_b) Fortran-ordered, info dict with mpls_run's keys) and the call's timings."""
+        B = self.count
+        S = np.ascontiguousarray(s_vec, dtype=np.float64).reshape(-1)
+        Ri = np.ascontiguousarray(R_init, dtype=np.float64).reshape(-1)
+        if S.size != self.m:
+            raise ValueError(f"s_vec must hold {self.m} entries (all problems' edges behind one another), not {S.size}")
+        if Ri.size != 9 * self.n:
+            raise ValueError(f"R_init must hold {9 * self.n} entries (all problems' 3 x 3 x n blocks behind one another), not {Ri.size}")
+        vec = [np.ascontiguousarray(np.atleast_1d(np.asarray(v, dtype=np.float64)).reshape(-1)) for v in (beta, tau, alpha)]
+        R = out_buffer(9 * self.n)
+        infos = (MplsInfo * max(B, 1))()
+        tm = MplsBatchTimings()
+        check(load().desc_mpls_batch_run(self.handle, ptr(S, F64P), ptr(Ri, F64P), float(stop_threshold), int(max_iter),
+                                         ptr(vec[0], F64P), vec[0].size, ptr(vec[1], F64P), vec[1].size, ptr(vec[2], F64P), vec[2].size,
+                                         ptr(R, F64P), infos, C.byref(tm)))
+        outs = [(Rb, dict(iters=i.iters, cg_iters=i.cg_iters, cg_unconverged=i.cg_unconverged, m_pos=i.m_pos, score=i.score,
+                          cg_residual=i.cg_residual, ms_loop=i.ms_loop, ms_total=i.ms_total))
+                for Rb, i in zip(_split_R(R, self.node_off), infos)]
+        return outs, _timings(tm)
+
 
 def mst_batch_max_n():
     """desc_mst_batch_max_n: the largest problem (nodes) the batched tree kernel takes."""
@@ -718,6 +752,11 @@ def mst_batch_run(probs, s_vec, device=0):
 def refine_batch_max_n():
     """desc_refine_batch_max_n: the largest problem (nodes) the batched refinement takes."""
     return int(load().desc_refine_batch_max_n())
+
+
+def mpls_batch_max_n():
+    """desc_mpls_batch_max_n: the largest problem (nodes) the batched MPLS loop takes (the batched refinement's cap)."""
+    return int(load().desc_mpls_batch_max_n())
 
 
 class RefineBatch(_BatchHandle):

@@ -652,6 +652,59 @@ def CEMP_MST_batch(problems, CEMP_parameters, seeds=None, return_info=False):
     return [R for R, _ in mst]
 
 
+def _mpls_batch_params(MPLS_parameters):
+    """The fields the MPLS loop reads, checked once for the whole batch -> (stop_threshold, max_iter, beta, tau, alpha)."""
+    beta = _param_vec(MPLS_parameters, "reweighting", "MPLS_parameters")
+    tau = _param_vec(MPLS_parameters, "thresholding", "MPLS_parameters")
+    alpha = _param_vec(MPLS_parameters, "cycle_info_ratio", "MPLS_parameters")
+    stop_threshold, max_iter = _get(MPLS_parameters, "stop_threshold"), _get(MPLS_parameters, "max_iter")
+    if stop_threshold is None:
+        raise ValueError("MPLS_parameters.stop_threshold is required")
+    if max_iter is None:
+        raise ValueError("MPLS_parameters.max_iter is required")
+    return float(stop_threshold), int(max_iter), beta, tau, alpha
+
+
+def MPLS_batch(problems, CEMP_parameters, MPLS_parameters, seeds=None, return_info=False):
+    """MPLS (Algorithms/MPLS.m:31, the "MPLS" row of Demo/compare_algorithms.m) on B independent small problems: ONE batched CEMP handle
+    runs the rounds, the batched tree kernel turns their SVec into R_init, and the MPLS loop of every problem runs in one launch on the
+    same handle, whose sampled cycles stay resident (desc_cemp_batch_*, desc_mst_batch_run, desc_mpls_batch_run; the reference has no
+    such call).
+
+    ``problems`` as for DESC_PGD_batch; one ``CEMP_parameters`` and one ``MPLS_parameters`` for the whole batch, with the fields MPLS()
+    reads; ``seeds`` an optional sequence of per-problem sampling seeds.  Returns a list of (R_est, R_init): entry b is bit for bit
+    ``MPLS(Ind_b, RijMat_b, dict(CEMP_parameters, seed=seed_b), MPLS_parameters)``, and no bit of it depends on the batch around it.
+    With ``return_info`` a list of (R_est, R_init, dict(SVec=..., cemp=..., mst=..., mpls=...)): CEMP's SVec in the caller's edge
+    order, the timings of the first two passes, and the loop's record (``iters``, ``score``, ``cg_iters``, ``cg_unconverged``,
+    ``cg_residual``, ``m_pos``, ``timings``).  The batch prints nothing: ``verbose`` is ignored.
+
+    Refused (ValueError, before the device is touched, naming the problem): what CEMP_MST_batch refuses; a missing or empty
+    ``MPLS_parameters.reweighting``, ``.thresholding`` or ``.cycle_info_ratio``; a missing ``stop_threshold`` or ``max_iter``; a problem
+    of more than ``_lib.mpls_batch_max_n()`` nodes (solve it with MPLS)."""
+    _check_sequence(problems)
+    cemp_beta, cemp_max_iter, nsample, seed, device, seeds = _cemp_batch_params(CEMP_parameters, len(problems), seeds)
+    stop_threshold, max_iter, beta, tau, alpha = _mpls_batch_params(MPLS_parameters)
+    probs, perms = _marshal_problems(problems)
+    if not probs:
+        return []
+    _check_cemp_batch_degrees(probs)
+    _check_mst_batch(probs)
+    _check_batch_sizes(probs, _lib.mpls_batch_max_n(), "per-node state of the MPLS loop", "MPLS")
+    with _batch_handle(_lib.CempBatch, probs, nsample, seed, seeds, device) as batch:
+        S_list, cemp_tm = batch.run(cemp_beta, cemp_max_iter)
+        S = np.concatenate(S_list)                                   # the library's edge order, as both later passes take it
+        with _invalid_as_value_error():
+            mst, mst_tm = _lib.mst_batch_run(probs, S, device)
+            R0 = np.concatenate([R.reshape(-1, order="F") for R, _ in mst])
+            outs, mpls_tm = batch.mpls_run(S, R0, stop_threshold, max_iter, beta, tau, alpha)
+    if not return_info:
+        return [(R, R_init) for (R, _), (R_init, _) in zip(outs, mst)]
+    return [(R, R_init, dict(SVec=_unsort(S_b.copy(), perm), cemp=dict(timings=cemp_tm),
+                             mst=dict(tree_edges=tree if perm is None else np.sort(perm[tree]), timings=mst_tm),
+                             mpls=dict(info, timings=mpls_tm)))
+            for (R, info), (R_init, tree), S_b, perm in zip(outs, mst, S_list, perms)]
+
+
 def _run_with_plots(solver, p, params, prob, dprob, perm, verbose, adam=None):
     """params.make_plots = true (DESC_PGD.m:235-239): after every iteration the error of S_vec against params.ErrVec and
     the rotation error of GCW(S_vec) against params.R_orig (GlobalSOdCorrectRight = the alignment of Rotation_Alignment).

@@ -32,9 +32,8 @@
 #include <new>
 #include <vector>
 
-#include "batch_csr.h"
+#include "cemp_batch.h"
 #include "cemp_math.h"
-#include "batch_device.h"
 
 namespace desc {
 namespace {
@@ -42,27 +41,6 @@ namespace {
 constexpr int CEMP_BATCH_MAX_DEGREE = 4096;            // longest CSR row: 4 waves x 4096 staged positions x 4 B = the 64 KiB every launch may declare
 static_assert(CEMP_BATCH_MAX_DEGREE >= 512 && CEMP_BATCH_MAX_DEGREE <= 65536, "row positions are packed in 16 bits each");
 static_assert(4 * CEMP_BATCH_MAX_DEGREE * 4 <= 64 * 1024, "LDS budget");
-
-struct CbProb { int32_t n, m, node_off, edge_off; uint64_t seed; };
-
-struct CbArgs {
-    const CbProb* prob;
-    const int32_t* eprob;       // batch-global edge id -> problem
-    const int32_t* ii;          // local endpoints of every edge
-    const int32_t* jj;
-    const int32_t* rowptr;      // problem b's n_b + 1 row starts at node_off[b] + b, counted inside the problem
-    const int32_t* adj;         // 2 m_b local neighbour ids at 2 edge_off[b]
-    const int32_t* adj_eid;     // 2 m_b local edge ids
-    const double* rij;          // 9 per edge
-    int32_t* e_jk;              // M * nsample batch-global edge ids (-1: the edge has no cycle)
-    int32_t* e_ki;
-    double* S0;                 // M * nsample
-    double* S_init;             // M: the initial means (:102-103), kept for the next run of the handle
-    double* S_a;                // M: the ping-pong buffers of the rounds
-    double* S_b;
-    uint8_t* has_cycle;         // M
-    int32_t M, nsample, lds_cap;
-};
 
 __global__ __launch_bounds__(256) void k_cemp_batch_build(CbArgs a) {
     extern __shared__ uint32_t cb_stage[];             // per wave: lds_cap packed positions (in row i | in row j << 16) of the common neighbours
@@ -148,12 +126,6 @@ __global__ __launch_bounds__(256) void k_cemp_batch_round(const int32_t* e_jk, c
 }  // namespace desc
 
 using namespace desc;
-
-struct desc_cemp_batch : desc::BatchCsr, desc::BatchDevice {
-    int32_t nsample = 0, max_deg = 0, grid = 1;
-    CbArgs a{};
-    double ms_build = 0;
-};
 
 namespace {
 

@@ -11,7 +11,8 @@
 // depends on that size.  The per-edge arrays (QQ, B, w, RS and the inputs S, ii, jj, rij) lie in global memory at the problem's edge
 // offset; the CSR (local ids) and the incidence sign per slot come from the host (batch_csr.h).
 //
-// Arithmetic and summation orders.  Every per-element expression is the text of laa_math.h, which the kernels of the single path call
+// Arithmetic and summation orders.  The Weighted-LAA step and the quantile are the workgroup-level functions of laa_wg.h, which
+// k_mpls_batch (mpls_batch.hip) calls too.  Every per-element expression is the text of laa_math.h, which the kernels of the single path call
 // too.  The single path's reductions all fit one workgroup and are reproduced in their orders: a CSR row by the 16 lanes of a DPP row
 // (rhs_row16 / lap_row16), the PCG's dot products by k_cg_dot's loop and block_reduce<3, 0>, the score in 256-row chunks
 // (score_chunk_sum) added in ascending order from 0.0.  The quantile's two order statistics are found exactly by a radix select over
@@ -35,21 +36,12 @@
 
 #include "batch_csr.h"
 #include "batch_device.h"
-#include "laa_math.h"
-#include "mst_key.h"
+#include "laa_wg.h"
 
 namespace desc {
 namespace {
 
-constexpr int RB_LDS_BYTES = 160 * 1024;               // what one workgroup may declare on gfx950
-constexpr int RB_NODE_DOUBLES = 4 + 6 * 3 + 1 + 3;     // Q; x r z p q rhs; diag; Wv
-constexpr int RB_STATIC_BYTES = 8 * 1024;              // set aside for the kernel's fixed LDS: block_reduce's tree (6 KiB), the histogram (1 KiB), scalars
-constexpr int REFINE_BATCH_MAX_N = (RB_LDS_BYTES - RB_STATIC_BYTES) / (8 * RB_NODE_DOUBLES);    // 748
-static_assert(REFINE_BATCH_MAX_N >= 278, "the cap of DESC_batch is the eigen-solve's");
-constexpr int RB_PROBE = 25;                           // laa_step's probe interval
 constexpr int RB_QR = 8;                               // entries of the quant_ratio table (the recurrence is constant after five steps)
-
-inline size_t rb_lds_bytes(int n) { return sizeof(double) * (size_t)RB_NODE_DOUBLES * (size_t)n; }
 
 struct RbProb { int32_t n, m; int64_t node_off, edge_off; };
 // status: 0 done, 1 the selection found no candidate, 2 a score that is not finite, -1 the workgroup never finished
@@ -75,33 +67,11 @@ struct RbArgs {
     double qr[RB_QR];           // quant_ratio of step 1, 2, ...: the host's recurrence max(0.8, q - 0.05)
 };
 
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ double key_value(unsigned long long k) {
-    return __longlong_as_double((long long)((k >> 63) ? (k & ~(1ull << 63)) : ~k));
-}
-
-// k_cg_dot in place: column-wise dot products of two n x 3 arrays into out3 (LDS).  Ends with a barrier.
-__device__ __forceinline__ void rb_dot(const double* a, const double* b, int n, double* out3) {
-    double s[3] = {0, 0, 0};
-    for (int v = threadIdx.x; v < n; v += 256) for (int c = 0; c < 3; ++c) s[c] += a[3 * v + c] * b[3 * v + c];
-    block_reduce<3, 0>(s, out3);
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(256) void k_refine_batch(RbArgs a) {
     extern __shared__ double rb_lds[];
-    __shared__ double cgs[15];                          // rz, rz_new, pq, bnorm, rnorm: CgScal's doubles
-    __shared__ double sh4[4], mm[8];
-    __shared__ unsigned hist[256];
-    __shared__ unsigned cnt_le;
-    __shared__ unsigned long long key_gt;
-    const int b = blockIdx.x, tid = threadIdx.x, l16 = tid & 15, row = tid >> 4;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const RbProb pd = a.prob[b];
     const int n = uni(pd.n), m = uni(pd.m);
-    const int32_t* rowptr = a.rowptr + pd.node_off + b;
-    const int32_t* adj = a.adj + 2 * pd.edge_off;
-    const int32_t* eid = a.adj_eid + 2 * pd.edge_off;
-    const int8_t* sgn = a.sgn + 2 * pd.edge_off;
     const int32_t* ii = a.ii + pd.edge_off;
     const int32_t* jj = a.jj + pd.edge_off;
     const double* S = a.S + pd.edge_off;
@@ -109,16 +79,16 @@ __global__ __launch_bounds__(256) void k_refine_batch(RbArgs a) {
     double* B = a.B + 3 * pd.edge_off;
     double* w = a.w + pd.edge_off;
     double* RS = a.RS + pd.edge_off;
-    Quat* Q = (Quat*)rb_lds;
-    double* x = rb_lds + 4 * n;
-    double* r = x + 3 * n;
-    double* z = r + 3 * n;
-    double* p = z + 3 * n;
-    double* q = p + 3 * n;
-    double* rhs = q + 3 * n;
-    double* diag = rhs + 3 * n;
-    double* Wv = diag + n;
-    double *rz = cgs, *rz_new = cgs + 3, *pq = cgs + 6, *bnorm = cgs + 9, *rnorm = cgs + 12;
+    WgLaa st;                                           // laa_wg.h: the problem's state and the step on it
+    st.n = n; st.m = m;
+    st.rowptr = a.rowptr + pd.node_off + b;
+    st.adj = a.adj + 2 * pd.edge_off;
+    st.eid = a.adj_eid + 2 * pd.edge_off;
+    st.sgn = a.sgn + 2 * pd.edge_off;
+    st.ii = ii; st.jj = jj; st.QQ = QQ; st.B = B; st.w = w;
+    wg_laa_views(rb_lds, n, st);
+    Quat* Q = st.Q;
+    const double* Wv = st.Wv;
 
     // ---- laa_setup: Q = R2Q(R_init), QQ = R2Q(permute(RijMat, [2,1,3])); the initial weights (DESC.m:274-282)
     for (int v = tid; v < n; v += 256) Q[v] = r2q(a.R_init + 9 * (pd.node_off + v), false);
@@ -132,85 +102,12 @@ __global__ __launch_bounds__(256) void k_refine_batch(RbArgs a) {
     const double stop = a.stop_threshold;
     const int max_iters = a.max_iters;
     const int cg_max = min(20000, 20 * n + 200);
-    double score = INFINITY, worst_sq = 0.0;
-    int it = 1, cg_total = 0, cg_unconverged = 0, status = 0;
+    double score = INFINITY;
+    WgCg cg;
+    int it = 1, status = 0;
     while (uni(score > stop && it < max_iters)) {                                           // DESC.m:287
         const double lam = 1.0 / (it + 1);
-        // ---- Weighted_LAA: the edge log map, the normal equations
-        for (int e = tid; e < m; e += 256) edge_log(QQ[e], Q[ii[e]], Q[jj[e]], B + 3 * (int64_t)e);
-        __syncthreads();
-        for (int vb = 0; vb < n; vb += 16) {
-            const int v = vb + row;
-            const bool on = v < n;
-            double s3[3], dg;
-            rhs_row16(eid, sgn, w, B, on ? rowptr[v] : 0, on ? rowptr[v + 1] : 0, l16, s3, &dg);
-            if (on && l16 == 0) { rhs[3 * v] = s3[0]; rhs[3 * v + 1] = s3[1]; rhs[3 * v + 2] = s3[2]; diag[v] = dg; }
-        }
-        __syncthreads();
-        // ---- laa_pcg<false, false>: x = 0, r = rhs (node 0 zeroed), z = r / diag, p = z
-        for (int v = tid; v < n; v += 256)
-            for (int c = 0; c < 3; ++c) {
-                const double rv = v > 0 ? rhs[3 * v + c] : 0.0;
-                const double zv = jacobi<false>(diag, v, c, rv);
-                x[3 * v + c] = 0.0; r[3 * v + c] = rv; z[3 * v + c] = zv; p[3 * v + c] = zv;
-            }
-        __syncthreads();
-        rb_dot(r, z, n, rz);
-        rb_dot(r, r, n, bnorm);
-        int done = 0, k = 0;
-        for (k = 1; k <= cg_max; ++k) {
-            for (int vb = 0; vb < n; vb += 16) {
-                const int v = vb + row;
-                const bool on = v < n && v > 0;
-                double s3[3];
-                lap_row16<false>(adj, eid, w, p, v, on ? rowptr[v] : 0, on ? rowptr[v + 1] : 0, l16, s3);
-                if (v < n && l16 == 0) { q[3 * v] = s3[0]; q[3 * v + 1] = s3[1]; q[3 * v + 2] = s3[2]; }
-            }
-            __syncthreads();
-            rb_dot(p, q, n, pq);
-            double al[3];
-            for (int c = 0; c < 3; ++c) al[c] = cg_alpha(rz[c], pq[c]);
-            for (int v = tid; v < n; v += 256)
-                for (int c = 0; c < 3; ++c) {
-                    const double xv = x[3 * v + c] + al[c] * p[3 * v + c];
-                    const double rv = r[3 * v + c] - al[c] * q[3 * v + c];
-                    x[3 * v + c] = xv; r[3 * v + c] = rv;
-                    z[3 * v + c] = jacobi<false>(diag, v, c, rv);
-                }
-            __syncthreads();
-            rb_dot(r, z, n, rz_new);
-            double be[3];
-            for (int c = 0; c < 3; ++c) be[c] = cg_beta(rz[c], rz_new[c]);
-            for (int v = tid; v < n; v += 256)
-                for (int c = 0; c < 3; ++c) p[3 * v + c] = z[3 * v + c] + be[c] * p[3 * v + c];
-            __syncthreads();                                                                // every thread has read rz
-            if (tid < 3) rz[tid] = rz_new[tid];
-            if (k % RB_PROBE == 0 || k == cg_max) {                                          // convergence probe: |r| <= 1e-13 |b|
-                rb_dot(r, r, n, rnorm);
-                int fin = 1;
-                for (int c = 0; c < 3; ++c) if (cg_unfinished(rnorm[c], bnorm[c])) fin = 0;
-                done = uni(fin);
-                if (done || k == cg_max) break;
-            }
-        }
-        __syncthreads();                                                                    // the last roll of rz is behind every thread
-        cg_total += min(k, cg_max);                                                         // the true count rounded up to the probe interval
-        for (int c = 0; c < 3; ++c)
-            if (bnorm[c] > 0) { const double ratio = rnorm[c] / bnorm[c]; if (worst_sq < ratio) worst_sq = ratio; }
-        if (!done) ++cg_unconverged;
-        // ---- Weighted_LAA.m:40-50: exp map, Q <- Q * W, the score in chunks of 256 rows
-        double tot = 0.0;
-        for (int base = 0; base < n; base += 256) {
-            const int v = base + tid;
-            double sc = 0.0;
-            if (v < n) {
-                const double theta = node_update(x + 3 * v, Q + v, Wv + 3 * v);
-                if (v > 0) sc += theta;
-            }
-            tot += score_chunk_sum(sc, sh4);
-            __syncthreads();
-        }
-        score = tot / (double)n;
+        score = wg_laa_step(st, cg_max, cg);                                                // Weighted_LAA
         if (uni(!isfinite(score))) { status = 2; break; }
         // ---- residuals and new weights (DESC.m:289-303)
         double lo = INFINITY, hi = -INFINITY;
@@ -218,67 +115,14 @@ __global__ __launch_bounds__(256) void k_refine_batch(RbArgs a) {
             const double v = rsvec_value(Wv, B, ii, jj, S, e, lam);
             RS[e] = v; lo = fmin(lo, v); hi = fmax(hi, v);
         }
-        for (int off = 32; off >= 1; off >>= 1) { lo = fmin(lo, __shfl_xor(lo, off)); hi = fmax(hi, __shfl_xor(hi, off)); }
-        if ((tid & 63) == 0) { mm[tid >> 6] = lo; mm[4 + (tid >> 6)] = hi; }
-        __syncthreads();                                                                    // RS, the wave extrema
-        lo = fmin(fmin(mm[0], mm[1]), fmin(mm[2], mm[3])); hi = fmax(fmax(mm[4], mm[5]), fmax(mm[6], mm[7]));
-        const double qratio = a.qr[min(it - 1, RB_QR - 1)];
-        int64_t k0 = 0; double fr = 0.0, thresh;
-        const int where = uni(hazen_position((int64_t)m, qratio, &k0, &fr));
-        if (where == HAZEN_MIN) thresh = lo;
-        else if (where == HAZEN_MAX) thresh = hi;
-        else if (uni(hazen_flat(lo, hi))) thresh = lo;
-        else {
-            // the order statistic of rank k0: radix select over the order key, most significant digit first
-            unsigned long long prefix = 0;
-            unsigned rank = (unsigned)k0;
-            int found = 1;
-            for (int pass = 7; pass >= 0; --pass) {
-                const int shift = 8 * pass;
-                hist[tid] = 0;
-                __syncthreads();
-                for (int e = tid; e < m; e += 256) {
-                    const unsigned long long key = order_key(RS[e]);
-                    if (pass == 7 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(unsigned)(key >> shift) & 255u], 1u);
-                }
-                __syncthreads();
-                unsigned acc = 0; int d = -1;
-                for (int bin = 0; bin < 256; ++bin) {
-                    const unsigned hcount = hist[bin];
-                    if (d < 0) { if (acc + hcount > rank) d = bin; else acc += hcount; }
-                }
-                d = uni(d);
-                __syncthreads();                                                            // hist is free again
-                if (d < 0) { found = 0; break; }
-                rank -= uni((int)acc);
-                prefix |= (unsigned long long)d << shift;
-            }
-            if (!found) { status = 1; break; }
-            // rank k0 + 1: the same value if more than k0 + 1 keys are <= it, else the smallest key above it
-            if (tid == 0) { cnt_le = 0; key_gt = ~0ull; }
-            __syncthreads();
-            unsigned c_le = 0; unsigned long long k_gt = ~0ull;
-            for (int e = tid; e < m; e += 256) {
-                const unsigned long long key = order_key(RS[e]);
-                if (key <= prefix) ++c_le; else if (key < k_gt) k_gt = key;
-            }
-            atomicAdd(&cnt_le, c_le);
-            atomicMin(&key_gt, k_gt);
-            __syncthreads();
-            const unsigned le = cnt_le;
-            const unsigned long long next = key_gt;
-            __syncthreads();                                                                // cnt_le, key_gt are free again
-            unsigned long long upper = prefix;
-            if (!uni(le >= (unsigned)k0 + 2u)) {
-                if (uni(next == ~0ull)) { status = 1; break; }
-                upper = next;
-            }
-            thresh = hazen_interp(key_value(prefix), key_value(upper), fr);
-        }
+        double thresh = 0.0;
+        if (uni(wg_quantile(RS, m, a.qr[min(it - 1, RB_QR - 1)], lo, hi, &thresh))) { status = 1; break; }
         for (int e = tid; e < m; e += 256) w[e] = laa_weight(RS[e], thresh, 1e4, 1e-4);
         __syncthreads();
         ++it;
     }
+    const int cg_total = cg.total, cg_unconverged = cg.unconverged;
+    const double worst_sq = cg.worst_sq;
     if (status) {                                                                           // the same in every thread
         if (tid == 0) { RbInfo o{}; o.status = status; o.iters = it - 1; o.score = score; a.info[b] = o; }
         return;

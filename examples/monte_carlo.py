@@ -2,7 +2,7 @@
 """A small Monte-Carlo study in ONE batched call: mean |S_vec - ErrVec| against the corruption level q, averaged over a few trials
 of Uniform_Topology(100, 0.5, q, 0.1) -- the shape of the figures the DESC paper draws (error against q on graphs of 100-200 nodes).
 
-    python examples/monte_carlo.py [--trials 5] [--n 100] [--iters 100] [--rotations] [--refined] [--baselines]
+    python examples/monte_carlo.py [--trials 5] [--n 100] [--iters 100] [--rotations] [--refined] [--baselines] [--mpls]
 
 --rotations: the demo's own metric next to it -- one DESC_init_batch call (the PGD pass, then the batched GCW eigen-solve) and the mean
 rotation error in degrees (Rotation_Alignment against the ground truth), the column of Demo/compare_algorithms.m.
@@ -10,6 +10,8 @@ rotation error in degrees (Rotation_Alignment against the ground truth), the col
 refinement) and the mean rotation error of R_est next to that of its initialisation R_init.
 --baselines: the curves DESC is drawn against, one batched call per curve -- CEMP's SVec error (CEMP_batch) and the rotation errors of
 CEMP+GCW (CEMP_GCW_batch) and CEMP+MST (CEMP_MST_batch), with the demo's CEMP parameters (compare_algorithms.m:26-29).
+--mpls: the MPLS curve from one MPLS_batch call (CEMP's rounds, the tree, then the MPLS loop of every problem in one launch), with the
+demo's CEMP and MPLS parameters (compare_algorithms.m:26-36): the mean rotation error of R_est next to that of its CEMP+MST start.
 """
 import argparse
 import os
@@ -21,7 +23,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from desc_amd import (CEMP_GCW_batch, CEMP_MST_batch, CEMP_batch, ConstantStepSize, DESC_PGD_batch, DESC_batch,  # noqa: E402
-                      DESC_init_batch, Rotation_Alignment, Uniform_Topology)
+                      DESC_init_batch, MPLS_batch, Rotation_Alignment, Uniform_Topology)
 
 
 def baselines(models, qs, trials):
@@ -45,6 +47,24 @@ def baselines(models, qs, trials):
         print(f" {q:4.2f}   {a.mean():.4f}                     {b.mean():8.4f}                           {c.mean():8.4f}")
 
 
+def mpls_curve(models, qs, trials):
+    """One MPLS_batch call: the MPLS curve of the demo."""
+    cemp = dict(max_iter=6, reweighting=[2.0 ** k for k in range(6)], nsample=50, seed=0)
+    mpls = dict(stop_threshold=1e-3, max_iter=100, reweighting=cemp["reweighting"][-1], thresholding=[0.95, 0.9, 0.85, 0.8],
+                cycle_info_ratio=1.0 / (np.arange(1, 101) + 1))
+    t0 = time.perf_counter()
+    out = MPLS_batch(models, cemp, mpls, return_info=True)
+    ms = (time.perf_counter() - t0) * 1e3
+    print(f"MPLS, {len(models)} problems in one MPLS_batch call: {ms:.1f} ms (the loop's launch {out[0][2]['mpls']['timings']['ms_loop']:.1f} ms)")
+    shape = (len(qs), trials)
+    est = np.array([Rotation_Alignment(R, mo.R_orig)[2] for (R, _, _), mo in zip(out, models)]).reshape(shape)
+    ini = np.array([Rotation_Alignment(R, mo.R_orig)[2] for (_, R, _), mo in zip(out, models)]).reshape(shape)
+    its = np.array([info["mpls"]["iters"] for _, _, info in out]).reshape(shape)
+    print("    q   MPLS rotation error, degrees   (min .. max)          its initialisation's (CEMP+MST)   iterations (min .. max)")
+    for q, re, ri, ni in zip(qs, est, ini, its):
+        print(f" {q:4.2f}   {re.mean():8.4f}                       ({re.min():.4f} .. {re.max():.4f})      {ri.mean():8.4f}                          {ni.min()} .. {ni.max()}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--trials", type=int, default=5)
@@ -53,6 +73,7 @@ def main():
     ap.add_argument("--rotations", action="store_true", help="one DESC_init_batch call: the mean rotation error next to the S_vec error")
     ap.add_argument("--refined", action="store_true", help="one DESC_batch call: the rotation error of DESC() next to its initialisation's")
     ap.add_argument("--baselines", action="store_true", help="CEMP, CEMP+GCW and CEMP+MST next to DESC: one batched call per curve")
+    ap.add_argument("--mpls", action="store_true", help="the MPLS curve: one MPLS_batch call")
     a = ap.parse_args()
     qs = [0.0, 0.1, 0.2, 0.3, 0.4, 0.5]
     models = [Uniform_Topology(a.n, 0.5, q, 0.1, "uniform", seed=1000 * k + t) for k, q in enumerate(qs) for t in range(a.trials)]
@@ -71,6 +92,8 @@ def main():
             print(f" {q:4.2f}   {row.mean():.4f}                {re.mean():8.4f}                       ({re.min():.4f} .. {re.max():.4f})      {ri.mean():8.4f}")
         if a.baselines:
             baselines(models, qs, a.trials)
+        if a.mpls:
+            mpls_curve(models, qs, a.trials)
         return
     t0 = time.perf_counter()
     if a.rotations:
@@ -89,12 +112,16 @@ def main():
                   f"                      ({rr.min():.4f} .. {rr.max():.4f})")
         if a.baselines:
             baselines(models, qs, a.trials)
+        if a.mpls:
+            mpls_curve(models, qs, a.trials)
         return
     print("    q   mean |S_vec - ErrVec|   (min .. max over the trials)")
     for q, row in zip(qs, err):
         print(f" {q:4.2f}   {row.mean():.4f}                ({row.min():.4f} .. {row.max():.4f})")
     if a.baselines:
         baselines(models, qs, a.trials)
+    if a.mpls:
+        mpls_curve(models, qs, a.trials)
 
 
 if __name__ == "__main__":

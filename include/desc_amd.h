@@ -707,6 +707,37 @@ int desc_refine_batch_run(desc_refine_batch* h, const double* s_vec, const doubl
                           double* R_out, desc_refine_info* infos, desc_refine_batch_timings* timings /* nullable */);
 void desc_refine_batch_destroy(desc_refine_batch* h);
 
+/* The MPLS loop (Algorithms/MPLS.m:196-254, the loop of desc_mpls_run) for B independent small problems in ONE launch, on a CEMP batch
+ * handle: the last stage of MPLS() behind desc_cemp_batch_run (SVec) and desc_mst_batch_run (R_init).  The handle already owns the CSR,
+ * the rotations and the sampled cycles; one workgroup per problem runs the whole loop on the chip -- the Weighted-LAA step exactly as
+ * desc_refine_batch_run runs it (one text: csrc/laa_wg.h), the residuals, the H step through CEMP's samples (csrc/cemp_math.h; an edge
+ * without a 3-cycle takes the reference's 2/3 rule), the convex combination, the quantile under the iteration's tau by an exact
+ * selection, the new weights -- with the per-node state (26 doubles) in LDS and no host round trip.  Problem b's R_est and record are bit
+ * for bit what desc_mpls_run's loop gives for it from the same s_vec and R_init, and no bit of them depends on the batch around it.
+ * desc_mpls_batch_max_n: the largest problem (nodes) the loop takes: desc_refine_batch_max_n() (748).
+ * desc_mpls_batch_run: s_vec = the edge_off[count] concatenated SVec in the library's edge order (what desc_cemp_batch_run returned);
+ * R_init / R_est: problem b's 3x3xn_b column-major blocks at 9 * node_off[b]; beta / tau / alpha: MPLS_parameters.reweighting /
+ * .thresholding / .cycle_info_ratio, each padded by repeating its last entry (MPLS.m:47-63); stop_threshold and max_iter as
+ * desc_mpls_params (max_iter <= 1: no iteration, R_est = q2R(R2Q(R_init))).  infos: count entries with desc_mpls_info's meaning (m_pos =
+ * the problem's edges with a 3-cycle; ms_loop / ms_total = the call's, ms_cemp = ms_mst = 0).  At its first call the handle allocates the
+ * loop's arrays and uploads the incidence signs (ms_setup; 0 afterwards).  The handle may be run any number of times, and
+ * desc_cemp_batch_run and desc_mpls_batch_run may alternate on it.  The call prints nothing.  Refused before any device work
+ * (DESC_ERR_INVALID), naming the problem: NULL arguments; n_beta, n_tau or n_alpha < 1; a problem of more than desc_mpls_batch_max_n()
+ * nodes (solve it with MPLS); a negative or non-finite s_vec entry; a non-finite R_init entry.  An empty batch returns DESC_OK.  A
+ * problem whose selection finds no candidate or whose score is not finite is DESC_ERR_STATE naming the problem and the step (there
+ * desc_mpls_run returns DESC_OK, leaving its loop on a NaN score: "bit for bit" holds for every problem whose scores are finite). */
+typedef struct desc_mpls_batch_timings {
+    double ms_setup;          /* first call: the loop's arrays, the incidence signs, the cycle counts; 0 afterwards */
+    double ms_input;          /* the checks of s_vec / R_init and their copy to HBM                                */
+    double ms_loop;           /* the loop's launch, device time (HIP events)                                       */
+    double ms_download;       /* R_est and the records back to the host                                            */
+    double ms_total;          /* wall clock of desc_mpls_batch_run                                                 */
+} desc_mpls_batch_timings;    /* 40 bytes */
+int32_t desc_mpls_batch_max_n(void);
+int desc_mpls_batch_run(desc_cemp_batch* h, const double* s_vec, const double* R_init, double stop_threshold, int32_t max_iter,
+                        const double* beta, int32_t n_beta, const double* tau, int32_t n_tau, const double* alpha, int32_t n_alpha,
+                        double* R_est, desc_mpls_info* infos, desc_mpls_batch_timings* timings /* nullable */);
+
 /* One-shot: what the MEX shim calls.  Builds the structure (p->build_where),
  * uploads, runs, downloads, frees. */
 int desc_pgd_solve(const desc_problem* prob, const desc_params* p, desc_result* r);
