@@ -41,6 +41,7 @@ EXPORTS = [
     "desc_cemp_batch_destroy", "desc_mst_batch_max_n", "desc_mst_batch_check", "desc_mst_batch_run",
     "desc_refine_batch_max_n", "desc_refine_batch_create", "desc_refine_batch_sizes", "desc_refine_batch_run", "desc_refine_batch_destroy",
     "desc_mpls_batch_max_n", "desc_mpls_batch_run",
+    "desc_lp_batch_plan", "desc_lp_batch_create", "desc_lp_batch_sizes", "desc_lp_batch_get_samples", "desc_lp_batch_run", "desc_lp_batch_destroy",
     "desc_test_laa_r2q", "desc_test_laa_q2r", "desc_test_laa_edge_log", "desc_test_laa_rhs", "desc_test_laa_pcg", "desc_test_laa_node_update",
     "desc_test_irls_node_update", "desc_test_laa_weights", "desc_test_irls_weights", "desc_test_laa_quantile", "desc_test_irls_project",
 ]
@@ -133,6 +134,11 @@ class RefineBatchTimings(C.Structure):
 
 class MplsBatchTimings(C.Structure):
     _fields_ = [("ms_setup", C.c_double), ("ms_input", C.c_double), ("ms_loop", C.c_double), ("ms_download", C.c_double),
+                ("ms_total", C.c_double)]
+
+
+class LpBatchTimings(C.Structure):
+    _fields_ = [("ms_structure", C.c_double), ("ms_upload", C.c_double), ("ms_build", C.c_double), ("ms_loop", C.c_double),
                 ("ms_total", C.c_double)]
 
 
@@ -333,6 +339,13 @@ def load():
     L.desc_mpls_batch_max_n.argtypes = []
     L.desc_mpls_batch_run.argtypes = [C.c_void_p, F64P, F64P, C.c_double, C.c_int32, F64P, C.c_int32, F64P, C.c_int32, F64P, C.c_int32, F64P,
                                       C.POINTER(MplsInfo), C.POINTER(MplsBatchTimings)]
+    L.desc_lp_batch_plan.argtypes = [C.POINTER(Problem), C.c_int32, I32P, I32P, I64P, I64P, I64P, I32P, I32P]
+    L.desc_lp_batch_create.argtypes = [C.POINTER(Problem), C.c_int32, I32P, C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_void_p)]
+    L.desc_lp_batch_sizes.argtypes = [C.c_void_p, I32P, I64P, I64P, I32P, I64P, I64P, I64P]
+    L.desc_lp_batch_get_samples.argtypes = [C.c_void_p, I32P, I32P]
+    L.desc_lp_batch_run.argtypes = [C.c_void_p, C.POINTER(LpParams), F64P, F64P, C.POINTER(LpInfo), C.POINTER(LpBatchTimings)]
+    L.desc_lp_batch_destroy.argtypes = [C.c_void_p]
+    L.desc_lp_batch_destroy.restype = None
     L.desc_test_laa_r2q.argtypes = [F64P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, F64P]
     L.desc_test_laa_q2r.argtypes = [F64P, C.c_int64, C.c_int32, F64P]
     L.desc_test_laa_edge_log.argtypes = [C.c_void_p, F64P, F64P, C.c_int64, F64P]
@@ -786,6 +799,87 @@ class RefineBatch(_BatchHandle):
                                            C.byref(tm)))
         outs = [(Rb, dict(iters=i.iters, cg_iters=i.cg_iters, score=i.score, ms_total=i.ms_total, cg_unconverged=i.cg_unconverged,
                           cg_residual=i.cg_residual)) for Rb, i in zip(_split_R(R, self.node_off), infos)]
+        return outs, _timings(tm)
+
+
+def _nsample_array(nsample, B):
+    """``nsample`` of a batched LP call -- None (the rule for every problem), one int or a sequence of B ints -- as an int32 array, or
+    None."""
+    if nsample is None:
+        return None
+    if np.ndim(nsample) == 0:
+        nsample = [nsample] * B
+    if len(nsample) != B:
+        raise ValueError(f"nsample must hold one entry per problem ({B}), not {len(nsample)}")
+    return np.ascontiguousarray([0 if v is None else int(v) for v in nsample], dtype=np.int32).reshape(-1)
+
+
+def lp_batch_plan(probs, nsample=None):
+    """desc_lp_batch_plan on a sequence of ProblemArrays: what desc_lp_batch_create decides on the host (no device; raises DescError with
+    create's refusals) -> dict of nsample, m_pos, ncol, nrow (B entries) and var_off, row_off (B + 1)."""
+    probs = list(probs)
+    B = len(probs)
+    ns = _nsample_array(nsample, B)
+    i32 = lambda k: np.zeros(max(k, 1), dtype=np.int32)
+    i64 = lambda k: np.zeros(max(k, 1), dtype=np.int64)
+    out = dict(nsample=i32(B), m_pos=i64(B), var_off=i64(B + 1), row_off=i64(B + 1), ncol=i32(B), nrow=i32(B))
+    check(load().desc_lp_batch_plan(_problem_array(probs), B, ptr(ns, I32P), ptr(out["nsample"], I32P), ptr(out["m_pos"], I64P),
+                                    ptr(out["var_off"], I64P), ptr(out["row_off"], I64P), ptr(out["ncol"], I32P), ptr(out["nrow"], I32P)))
+    return {k: v[:B + 1 if k.endswith("_off") else B] for k, v in out.items()}
+
+
+class LpBatch(_BatchHandle):
+    """Owner of a desc_lp_batch*: the LP of linprog_sij for B small problems at once (desc_lp_batch_*).  ``probs`` is a sequence of
+    ProblemArrays; ``nsample`` None (the rule of linprog_sij.m:43, per problem), one int or a sequence of B ints; ``seeds`` an optional
+    sequence of per-problem sampling seeds.  Samples, S0Mat and the transposed incidence are built here; the handle may be run any
+    number of times with other parameters."""
+
+    _kind = "lp"
+
+    def __init__(self, probs, nsample=None, seeds=None, device=0):
+        probs = list(probs)
+        self._open(probs, ptr(_nsample_array(nsample, len(probs)), I32P), _seeds_array(seeds, len(probs)), int(device))
+
+    def _read_sizes(self, B):
+        no, eo, vo, ro = (np.zeros(B + 1, dtype=np.int64) for _ in range(4))
+        ns, mp = np.zeros(max(B, 1), dtype=np.int32), np.zeros(max(B, 1), dtype=np.int64)
+        check(self._export("sizes")(self.handle, None, ptr(no, I64P), ptr(eo, I64P), ptr(ns, I32P), ptr(mp, I64P), ptr(vo, I64P), ptr(ro, I64P)))
+        self.node_off, self.edge_off, self.var_off, self.row_off, self.nsample, self.m_pos = no, eo, vo, ro, ns[:B], mp[:B]
+        self.n, self.m = int(no[B]), int(eo[B])
+
+    def sizes(self):
+        """Per problem: nsample, m_pos, the offset of its variables and of its cycles in the batch's arrays."""
+        return [dict(nsample=int(self.nsample[b]), m_pos=int(self.m_pos[b]), var_off=int(self.var_off[b]), row_off=int(self.row_off[b]))
+                for b in range(self.count)]
+
+    def samples(self):
+        """What create sampled, per problem: a list of dicts pos_edges (m_pos 0-based sorted edge ids: the LP's variables) and k
+        (m_pos x nsample sampled third nodes, 1-based), as lp_sij_run returns them."""
+        MP, MC = int(self.var_off[self.count]), int(self.row_off[self.count])
+        pos, k = out_buffer(MP, np.int32), out_buffer(MC, np.int32)
+        check(load().desc_lp_batch_get_samples(self.handle, ptr(pos, I32P), ptr(k, I32P)))
+        return [dict(pos_edges=pos[int(self.var_off[b]):int(self.var_off[b + 1])].copy(),
+                     k=k[int(self.row_off[b]):int(self.row_off[b + 1])].reshape(int(self.m_pos[b]), int(self.nsample[b])))
+                for b in range(self.count)]
+
+    def run(self, params=None, want_y=False):
+        """One batched run of the loop.  params: LpParams (tol, max_iter, check_every and restart are read; None: the defaults).
+        Returns a list of per-problem (S_vec (m_b,) in sorted edge order, y (m_pos, nsample, 2) or None, info dict with lp_sij_run's
+        keys) and the call's timings."""
+        B = self.count
+        MC = int(self.row_off[B])
+        p = params if params is not None else default_lp_params()
+        S = out_buffer(self.m)
+        y = out_buffer(2 * MC) if want_y else None
+        infos = (LpInfo * max(B, 1))()
+        tm = LpBatchTimings()
+        check(load().desc_lp_batch_run(self.handle, C.byref(p), ptr(S, F64P), ptr(y, F64P), infos, C.byref(tm)))
+        outs = []
+        for b in range(B):
+            yb = None
+            if want_y:
+                yb = y[2 * int(self.row_off[b]):2 * int(self.row_off[b + 1])].reshape(int(self.m_pos[b]), int(self.nsample[b]), 2)
+            outs.append((S[int(self.edge_off[b]):int(self.edge_off[b + 1])], yb, {name: getattr(infos[b], name) for name, _ in LpInfo._fields_}))
         return outs, _timings(tm)
 
 

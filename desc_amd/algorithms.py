@@ -705,6 +705,80 @@ def MPLS_batch(problems, CEMP_parameters, MPLS_parameters, seeds=None, return_in
             for (R, info), (R_init, tree), S_b, perm in zip(outs, mst, S_list, perms)]
 
 
+def linprog_sij_batch(problems, params=None, seeds=None, rotations=True, return_info=False):
+    """linprog_sij (Algorithms/linprog_sij.m:16) on B independent small problems: the LP of every problem in one batched PDHG loop
+    (desc_lp_batch_*: two launches per step and one 4-byte read-back per check for the whole batch), then the row-normalised weighted
+    spectral step with weights exp(-5 S_vec) on the batched eigen-solve and the refinement with maxIters = 200 on the batched
+    refinement -- three batched handles (the reference has no such call).
+
+    ``problems`` as for DESC_PGD_batch; one ``params`` for the whole batch with the fields of linprog_sij: ``seed``, ``device``, ``tol``,
+    ``max_iter``, ``check_every``, ``restart``, ``return_dual`` and ``nsample`` -- None (the rule of :43, evaluated per problem), one int,
+    or a sequence of B ints; ``seeds`` an optional sequence of per-problem sampling seeds (default: ``params.seed`` for every problem).
+    Returns a list of (R_est, S_vec), S_vec in the caller's edge order: entry b's S_vec is bit for bit
+    ``linprog_sij(Ind_b, RijMat_b, dict(params, seed=seed_b, nsample=nsample_b))``'s, each problem stops at its own step, and no bit of
+    it depends on the batch around it.  With ``return_info`` a list of (R_est, S_vec, info) with linprog_sij's keys ``lp``,
+    ``pos_edges``, ``k``, ``R_gcw``, ``spectral``, ``refine`` and, with ``return_dual``, ``y``.  ``rotations=False`` runs the LP only and
+    returns a list of S_vec, or of (S_vec, info).  The batch prints nothing: ``verbose`` is ignored.
+
+    Refused (ValueError, before the device is touched, naming the problem): not a sequence, an empty edge list, ``nsample < 0``, a
+    ``seeds`` or ``nsample`` sequence of the wrong length, a node of more neighbours than ``_lib.cemp_batch_max_degree()`` (the batched
+    sampler's cap; solve it with linprog_sij), a batch whose LP rows reach 2^31 (split the batch), and with ``rotations=True`` a problem
+    of more than ``_lib.gcw_batch_max_n()`` nodes (solve it with linprog_sij, or pass rotations=False for S_vec alone)."""
+    _check_sequence(problems)
+    params = {} if params is None else params
+    B = len(problems)
+    seeds = _check_seeds(seeds, B)
+    nsample = _get(params, "nsample")
+    if nsample is not None and np.ndim(nsample) != 0 and len(nsample) != B:
+        raise ValueError(f"nsample must hold one entry per problem ({B}), not {len(nsample)}")
+    p = _lib.default_lp_params()
+    for name, cast in (("tol", float), ("max_iter", int), ("check_every", int), ("restart", int)):
+        if _get(params, name) is not None:
+            setattr(p, name, cast(_get(params, name)))
+    p.verbose = 0
+    want_y, device = bool(_get(params, "return_dual", False)), int(_get(params, "device", 0))
+    if seeds is None:
+        seeds = [int(_get(params, "seed", 0))] * B
+    if B == 0:
+        return []
+    probs, perms = _marshal_problems(problems)
+    try:
+        _lib.lp_batch_plan(probs, nsample)                               # create's refusals, on the host
+    except _lib.DescError as e:
+        if e.code in (_lib.ERR_INVALID, _lib.ERR_TOO_LARGE):
+            raise ValueError(str(e).split(": ", 1)[-1]) from None
+        raise
+    if rotations:
+        cap = _lib.gcw_batch_max_n()
+        for b, q in enumerate(probs):
+            if q.n > cap:
+                raise ValueError(f"problem {b}: n = {q.n} exceeds {cap} (the 3n x 6 blocks of the eigen-solve must fit the LDS of one workgroup): "
+                                 "solve it with linprog_sij, or pass rotations=False for S_vec alone")
+    with _batch_handle(_lib.LpBatch, probs, nsample, seeds, device) as batch:
+        outs, lp_tm = batch.run(p, want_y=want_y)
+        samples = batch.samples() if return_info else None
+    S_list = [_unsort(S, perm) for (S, _, _), perm in zip(outs, perms)]
+    infos = None
+    if return_info:
+        infos = []
+        for (S, y, lp), smp, perm in zip(outs, samples, perms):
+            info = dict(lp=dict(lp, timings=lp_tm), pos_edges=smp["pos_edges"] if perm is None else perm[smp["pos_edges"]], k=smp["k"])
+            if want_y:
+                info["y"] = y
+            infos.append(info)
+    if not rotations:
+        return [(S, info) for S, info in zip(S_list, infos)] if return_info else S_list
+    S = np.concatenate([S for S, _, _ in outs])                          # the library's edge order, as both later passes take it
+    gcw, gcw_tm = _gcw_batch_run(probs, device, weights=np.exp(-5.0 * S), normalize_rows=True)              # :154-174, beta_T = 5
+    R0 = np.concatenate([R.reshape(-1, order="F") for R, _ in gcw])
+    ref, ref_tm = _refine_batch_run(probs, device, S, R0, 1e-3, 200)                                        # :176-351
+    if not return_info:
+        return [(R, S_b) for (R, _), S_b in zip(ref, S_list)]
+    for info, (R_gcw, sinfo), (_, rinfo) in zip(infos, gcw, ref):
+        info.update(R_gcw=R_gcw, spectral=dict(sinfo, timings=gcw_tm), refine=dict(rinfo, timings=ref_tm))
+    return [(R, S_b, info) for (R, _), S_b, info in zip(ref, S_list, infos)]
+
+
 def _run_with_plots(solver, p, params, prob, dprob, perm, verbose, adam=None):
     """params.make_plots = true (DESC_PGD.m:235-239): after every iteration the error of S_vec against params.ErrVec and
     the rotation error of GCW(S_vec) against params.R_orig (GlobalSOdCorrectRight = the alignment of Rotation_Alignment).

@@ -28,6 +28,38 @@ struct CbArgs {
     int32_t M, nsample, lds_cap;
 };
 
+constexpr int CEMP_BATCH_MAX_DEGREE = 4096;            // longest CSR row: 4 waves x 4096 staged positions x 4 B = the 64 KiB every launch may declare
+static_assert(CEMP_BATCH_MAX_DEGREE >= 512 && CEMP_BATCH_MAX_DEGREE <= 65536, "row positions are packed in 16 bits each");
+static_assert(4 * CEMP_BATCH_MAX_DEGREE * 4 <= 64 * 1024, "LDS budget");
+
+// The common neighbours of i and j in ascending k (CEMP.m:48-56), by one wave: lanes stride over the shorter of the two CSR rows (ri, di /
+// rj, dj: start and length in adj) and binary-search the longer one, hits are ranked by ballot / popcount.  st[0 .. min(cd, lds_cap)) gets
+// the positions of the hits in the two rows, packed (in row i | in row j << 16); returns the codegree cd, the same in every lane.  Ends
+// with a wave barrier: st is the wave's own staging area.
+__device__ __forceinline__ int cb_common_neighbours(const int32_t* adj, int ri, int di, int rj, int dj, int lane, int lds_cap, uint32_t* st) {
+    const bool i_short = di <= dj;
+    const int rs = i_short ? ri : rj, ds = i_short ? di : dj, rl = i_short ? rj : ri, dl = i_short ? dj : di;
+    int cd = 0;
+    for (int t0 = 0; t0 < ds; t0 += 64) {
+        const int t = t0 + lane;
+        bool hit = false;
+        int lo = 0;
+        if (t < ds) {
+            const int k = adj[rs + t];
+            int hi = dl;
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (adj[rl + mid] < k) lo = mid + 1; else hi = mid; }
+            hit = lo < dl && adj[rl + lo] == k;
+        }
+        const unsigned long long mk = __ballot(hit);
+        const int pos = cd + __popcll(mk & ((1ull << lane) - 1ull));
+        if (hit && pos < lds_cap) st[pos] = i_short ? ((uint32_t)t | (uint32_t)lo << 16) : ((uint32_t)lo | (uint32_t)t << 16);
+        cd += __popcll(mk);
+    }
+    cd = __builtin_amdgcn_readfirstlane(cd);
+    __builtin_amdgcn_wave_barrier();
+    return cd;
+}
+
 // status: 0 done, 1 the selection found no candidate, 2 a score that is not finite, -1 the workgroup never finished
 struct MbInfo { int32_t iters, cg_total, cg_unconverged, status; double score, worst_sq; };
 

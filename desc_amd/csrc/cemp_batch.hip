@@ -38,10 +38,6 @@
 namespace desc {
 namespace {
 
-constexpr int CEMP_BATCH_MAX_DEGREE = 4096;            // longest CSR row: 4 waves x 4096 staged positions x 4 B = the 64 KiB every launch may declare
-static_assert(CEMP_BATCH_MAX_DEGREE >= 512 && CEMP_BATCH_MAX_DEGREE <= 65536, "row positions are packed in 16 bits each");
-static_assert(4 * CEMP_BATCH_MAX_DEGREE * 4 <= 64 * 1024, "LDS budget");
-
 __global__ __launch_bounds__(256) void k_cemp_batch_build(CbArgs a) {
     extern __shared__ uint32_t cb_stage[];             // per wave: lds_cap packed positions (in row i | in row j << 16) of the common neighbours
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -59,27 +55,7 @@ __global__ __launch_bounds__(256) void k_cemp_batch_build(CbArgs a) {
         const int32_t* eid = a.adj_eid + 2 * (int64_t)pd.edge_off;
         const int ri = uniform_load(rp, i), di = uniform_load(rp, i + 1) - ri;
         const int rj = uniform_load(rp, j), dj = uniform_load(rp, j + 1) - rj;
-        // ---- the common neighbours in ascending k (:48-56): stride over the shorter row, search the longer one
-        const bool i_short = di <= dj;
-        const int rs = i_short ? ri : rj, ds = i_short ? di : dj, rl = i_short ? rj : ri, dl = i_short ? dj : di;
-        int cd = 0;
-        for (int t0 = 0; t0 < ds; t0 += 64) {
-            const int t = t0 + lane;
-            bool hit = false;
-            int lo = 0;
-            if (t < ds) {
-                const int k = adj[rs + t];
-                int hi = dl;
-                while (lo < hi) { const int mid = (lo + hi) >> 1; if (adj[rl + mid] < k) lo = mid + 1; else hi = mid; }
-                hit = lo < dl && adj[rl + lo] == k;
-            }
-            const unsigned long long mk = __ballot(hit);
-            const int pos = cd + __popcll(mk & ((1ull << lane) - 1ull));
-            if (hit && pos < a.lds_cap) st[pos] = i_short ? ((uint32_t)t | (uint32_t)lo << 16) : ((uint32_t)lo | (uint32_t)t << 16);
-            cd += __popcll(mk);
-        }
-        cd = __builtin_amdgcn_readfirstlane(cd);
-        __builtin_amdgcn_wave_barrier();
+        const int cd = cb_common_neighbours(adj, ri, di, rj, dj, lane, a.lds_cap, st);      // :48-56, staged in ascending k
         const int64_t base = (int64_t)g * nsample;
         if (cd == 0) {                                                   // :103 SVec(~IndPosbin) = 1
             for (int t = lane; t < nsample; t += 64) { a.e_jk[base + t] = -1; a.e_ki[base + t] = -1; a.S0[base + t] = 0.0; }

@@ -29,180 +29,49 @@
 // (the gap then lags the violation).  Defaults: tol 1e-4, max_iter 200000, check_every 64.  restart = 0 keeps no averages; with tol = 0
 // besides, exactly max_iter plain steps run from x = 0, y = 0.
 // Two runs on the same input return the same bits: no atomics on doubles, fixed reduction trees, grids that depend on the sizes only.
+// The kernels' arithmetic and the rule the host applies after a check (lp_decide) are lp_math.h's: lp_batch.hip runs the same text for many
+// small problems at once, and a problem gets the same bits from either.
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
 
 #include "cemp_state.h"
+#include "lp_math.h"
 
 namespace desc {
 namespace {
-
-struct LpRec { double viol, bty, P, dbox; double pad[4]; };      // what the host reads per check
 
 // variable (pos index) of the two other edges of every cycle
 __global__ __launch_bounds__(256) void k_lp_vars(const int32_t* e_ki, const int32_t* e_jk, const int32_t* poe, int32_t* va, int32_t* vb, int64_t mc) {
     for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < mc; c += (int64_t)gridDim.x * 256) { va[c] = poe[e_ki[c]]; vb[c] = poe[e_jk[c]]; }
 }
-__global__ __launch_bounds__(256) void k_lp_count(const int32_t* va, const int32_t* vb, int32_t* cnt, int64_t mc) {
-    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < mc; c += (int64_t)gridDim.x * 256) { atomicAdd(&cnt[va[c]], 1); atomicAdd(&cnt[vb[c]], 1); }
-}
-// exclusive scan of cnt[0 .. mp) into ptr[0 .. mp] by one workgroup (a contiguous chunk per thread); tau0 = 1 / (2 nsample + 2 cnt); cnt is zeroed
-__global__ __launch_bounds__(1024) void k_lp_scan(int32_t* cnt, int32_t* ptr, double* tau0, int64_t mp, int nsample) {
-    __shared__ int64_t s_sum[1024];
-    const int64_t chunk = (mp + 1023) / 1024, lo0 = chunk * threadIdx.x, lo = lo0 < mp ? lo0 : mp, hi = lo + chunk < mp ? lo + chunk : mp;
-    int64_t s = 0;
-    for (int64_t l = lo; l < hi; ++l) s += cnt[l];
-    s_sum[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) { int64_t acc = 0; for (int t = 0; t < 1024; ++t) { const int64_t v = s_sum[t]; s_sum[t] = acc; acc += v; } ptr[mp] = (int32_t)acc; }
-    __syncthreads();
-    int64_t acc = s_sum[threadIdx.x];
-    for (int64_t l = lo; l < hi; ++l) {
-        const int c = cnt[l];
-        ptr[l] = (int32_t)acc; acc += c;
-        tau0[l] = 1.0 / (2.0 * (double)nsample + 2.0 * (double)c);
-        cnt[l] = 0;
-    }
-}
-__global__ __launch_bounds__(256) void k_lp_fill(const int32_t* va, const int32_t* vb, const int32_t* ptr, int32_t* cur, int32_t* list, int64_t mc) {
-    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < mc; c += (int64_t)gridDim.x * 256) {
-        const int a = va[c], b = vb[c];
-        list[ptr[a] + atomicAdd(&cur[a], 1)] = (int32_t)c;
-        list[ptr[b] + atomicAdd(&cur[b], 1)] = (int32_t)c;
-    }
-}
-// every list ascending (the fill's order is arrival order): rank sort by one wave per list, the list in the LDS when it fits.  The ids of
-// one list are distinct (a cycle holds an edge once).
-constexpr int LP_SORT_LDS = 2048;
-__global__ __launch_bounds__(64) void k_lp_sort(const int32_t* ptr, const int32_t* in, int32_t* out, int64_t mp) {
-    __shared__ int32_t s_v[LP_SORT_LDS];
-    for (int64_t l = blockIdx.x; l < mp; l += gridDim.x) {
-        const int p0 = ptr[l], len = ptr[l + 1] - p0;
-        const bool lds = len <= LP_SORT_LDS;
-        __syncthreads();
-        if (lds) for (int t = threadIdx.x; t < len; t += 64) s_v[t] = in[p0 + t];
-        __syncthreads();
-        for (int t = threadIdx.x; t < len; t += 64) {
-            const int v = lds ? s_v[t] : in[p0 + t];
-            int rank = 0;
-            if (lds) for (int u = 0; u < len; ++u) rank += s_v[u] < v;
-            else for (int u = 0; u < len; ++u) rank += in[p0 + u] < v;
-            out[p0 + rank] = v;
-        }
-    }
-}
+__global__ __launch_bounds__(1024) void k_lp_scan(int32_t* cnt, int32_t* ptr, double* tau0, int64_t mp, int nsample) { lp_scan_block(cnt, ptr, tau0, mp, nsample, 0, true); }
 
-// reduced cost of variable l from z and own: 1 + (K'y)_l, the incidence list summed by the 16 lanes in a fixed order
-__device__ __forceinline__ double lp_reduced_cost(const int32_t* ptr, const int32_t* list, const double* z, const double* own, int64_t l, int sub) {
-    const int p0 = ptr[l], p1 = ptr[l + 1];
-    double acc = 0.0;
-    for (int p = p0 + sub; p < p1; p += 16) acc += z[list[p]];
-    acc = group_sum<16>(acc);
-    return 1.0 + own[l] - acc;
-}
-
+// the kernels of the loop: the passes of lp_math.h over the launch grid, the problem at variable 0 and cycle 0 of its arrays
 template <bool AVG>
 __global__ __launch_bounds__(256) void k_lp_col(const int32_t* ptr, const int32_t* list, const double* z, const double* own, const double* tau0,
                                                 double* x, double* xbar, double* xsum, int64_t mp) {
-    const int sub = threadIdx.x & 15;
-    const int64_t gid = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4, ng = ((int64_t)gridDim.x * 256) >> 4;
-    for (int64_t l0 = 0; l0 < mp; l0 += ng) {                   // whole waves stay in the loop: the DPP sums need every lane
-        const int64_t l = l0 + gid;
-        const bool on = l < mp;
-        const double rc = lp_reduced_cost(ptr, list, z, own, on ? l : mp - 1, sub);
-        if (on && sub == 0) {
-            const double xo = x[l];
-            const double xn = fmin(fmax(xo - tau0[l] * rc, 0.0), 1.0);
-            x[l] = xn; xbar[l] = 2.0 * xn - xo;
-            if (AVG) xsum[l] += xn;
-        }
-    }
+    lp_col_pass<AVG>(ptr, list, z, own, tau0, x, xbar, xsum, mp, blockIdx.x, gridDim.x, 0);
 }
-
 template <int G, bool AVG>
 __global__ __launch_bounds__(256) void k_lp_row(const int32_t* va, const int32_t* vb, const double* S0, const double* xbar, double2* y, double2* ysum, double* z,
                                                 double* own, double sigma, int64_t mp, int nsample) {
-    const int sub = threadIdx.x & (G - 1);
-    const int64_t gid = ((int64_t)blockIdx.x * 256 + threadIdx.x) / G, ng = ((int64_t)gridDim.x * 256) / G;
-    for (int64_t l0 = 0; l0 < mp; l0 += ng) {
-        const int64_t l = l0 + gid;
-        const bool on = l < mp;
-        const double xl = on ? xbar[l] : 0.0;
-        double acc = 0.0;
-        if (on) for (int t = sub; t < nsample; t += G) {
-            const int64_t c = l * nsample + t;
-            const double s = xbar[va[c]] + xbar[vb[c]], d = S0[c];
-            const double2 yo = y[c];
-            double2 yn;
-            yn.x = fmax(yo.x + sigma * ((xl - s) - d), 0.0);       // row  s_l - s_a - s_b <= d
-            yn.y = fmax(yo.y + sigma * ((-xl - s) + d), 0.0);      // row -s_l - s_a - s_b <= -d
-            y[c] = yn;
-            z[c] = yn.x + yn.y;
-            if (AVG) { double2 ys = ysum[c]; ys.x += yn.x; ys.y += yn.y; ysum[c] = ys; }
-            acc += yn.x - yn.y;
-        }
-        acc = group_sum<G>(acc);
-        if (on && sub == 0) own[l] = acc;
-    }
+    lp_row_pass<G, AVG>(va, vb, S0, xbar, y, ysum, z, own, sigma, mp, nsample, blockIdx.x, gridDim.x, 0, 0);
 }
-
-// certificates of (x, y), first half: z and own of y, block partials of max violation and b'y
 template <int G>
 __global__ __launch_bounds__(256) void k_lp_eval_row(const int32_t* va, const int32_t* vb, const double* S0, const double* x, const double2* y, double* z, double* own,
                                                      double* part, int64_t mp, int nsample) {
-    const int sub = threadIdx.x & (G - 1);
-    const int64_t gid = ((int64_t)blockIdx.x * 256 + threadIdx.x) / G, ng = ((int64_t)gridDim.x * 256) / G;
-    double viol[1] = {0.0}, bty[1] = {0.0};
-    for (int64_t l0 = 0; l0 < mp; l0 += ng) {
-        const int64_t l = l0 + gid;
-        const bool on = l < mp;
-        const double xl = on ? x[l] : 0.0;
-        double acc = 0.0;
-        if (on) for (int t = sub; t < nsample; t += G) {
-            const int64_t c = l * nsample + t;
-            const double s = x[va[c]] + x[vb[c]], d = S0[c];
-            const double2 yc = y[c];
-            viol[0] = fmax(viol[0], fmax((xl - s) - d, (-xl - s) + d));
-            bty[0] += d * (yc.x - yc.y);
-            z[c] = yc.x + yc.y;
-            acc += yc.x - yc.y;
-        }
-        acc = group_sum<G>(acc);
-        if (on && sub == 0) own[l] = acc;
-    }
-    block_reduce<1, 2>(viol, part + 2 * blockIdx.x);
-    __syncthreads();
-    block_reduce<1, 0>(bty, part + 2 * blockIdx.x + 1);
+    lp_eval_row_pass<G>(va, vb, S0, x, y, z, own, part + 2 * blockIdx.x, mp, nsample, blockIdx.x, gridDim.x, 0, 0);
 }
-// second half: block partials of sum x and sum min(0, reduced cost)
 __global__ __launch_bounds__(256) void k_lp_eval_col(const int32_t* ptr, const int32_t* list, const double* z, const double* own, const double* x, double* part, int64_t mp) {
-    const int sub = threadIdx.x & 15;
-    const int64_t gid = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4, ng = ((int64_t)gridDim.x * 256) >> 4;
-    double v[2] = {0.0, 0.0};
-    for (int64_t l0 = 0; l0 < mp; l0 += ng) {
-        const int64_t l = l0 + gid;
-        const bool on = l < mp;
-        const double rc = lp_reduced_cost(ptr, list, z, own, on ? l : mp - 1, sub);
-        if (on && sub == 0) { v[0] += x[l]; v[1] += fmin(rc, 0.0); }
-    }
-    block_reduce<2, 0>(v, part + 2 * blockIdx.x);
+    lp_eval_col_pass(ptr, list, z, own, x, part + 2 * blockIdx.x, mp, blockIdx.x, gridDim.x, 0);
 }
-// the partials of both halves in block order -> the record
 __global__ __launch_bounds__(256) void k_lp_eval_final(const double* part_row, int nb_row, const double* part_col, int nb_col, LpRec* rec) {
-    double a[1] = {0.0}, b[3] = {0.0, 0.0, 0.0};
-    for (int t = threadIdx.x; t < nb_row; t += 256) { a[0] = fmax(a[0], part_row[2 * t]); b[0] += part_row[2 * t + 1]; }
-    for (int t = threadIdx.x; t < nb_col; t += 256) { b[1] += part_col[2 * t]; b[2] += part_col[2 * t + 1]; }
-    __shared__ double o[4];
-    block_reduce<1, 2>(a, o);
-    __syncthreads();
-    block_reduce<3, 0>(b, o + 1);
-    __syncthreads();
-    if (threadIdx.x == 0) { rec->viol = o[0]; rec->bty = o[1]; rec->P = o[2]; rec->dbox = o[3]; }
+    lp_eval_final(part_row, nb_row, part_col, nb_col, rec);
 }
 
 __global__ __launch_bounds__(256) void k_lp_average(const double* sum, double* out, double cnt, int64_t count) {
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < count; t += (int64_t)gridDim.x * 256) out[t] = sum[t] / cnt;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < count; t += (int64_t)gridDim.x * 256) out[t] = lp_average(sum[t], cnt);
 }
 // restart: v <- src, the running sum cleared
 __global__ __launch_bounds__(256) void k_lp_restart(const double* src, double* v, double* sum, int64_t count) {
@@ -213,7 +82,7 @@ __global__ __launch_bounds__(256) void k_lp_set(double* p, int64_t count, double
 }
 // S_vec: 1 without a cycle (:104), the variable clipped to the box otherwise
 __global__ __launch_bounds__(256) void k_lp_out(const int32_t* pos, const double* x, double* s_vec, int64_t mp) {
-    for (int64_t l = (int64_t)blockIdx.x * 256 + threadIdx.x; l < mp; l += (int64_t)gridDim.x * 256) s_vec[pos[l]] = fmin(fmax(x[l], 0.0), 1.0);
+    for (int64_t l = (int64_t)blockIdx.x * 256 + threadIdx.x; l < mp; l += (int64_t)gridDim.x * 256) s_vec[pos[l]] = lp_clip(x[l]);
 }
 
 struct LpTimer {                                        // hipEvent laps of the loop's two kernels (verbose >= 2: tools/lp_stages.py)
@@ -324,12 +193,9 @@ extern "C" int desc_lp_sij_run_dev(const desc_device_problem* dp, const desc_lp_
         DESC_HIP(hipMemcpy(out, d_rec, sizeof(LpRec), hipMemcpyDeviceToHost));
         return DESC_OK;
     };
-    auto dual_obj = [](const LpRec& r) { return -r.bty + r.dbox; };
-    auto error_of = [&](const LpRec& r) { const double Dv = dual_obj(r); return std::max(r.viol, std::fabs(r.P - Dv) / (1.0 + std::fabs(r.P) + std::fabs(Dv))); };
-    auto passes = [&](const LpRec& r) { const double Dv = dual_obj(r); return r.viol <= P.tol && r.P - Dv <= P.tol * (1.0 + std::fabs(r.P) + std::fabs(Dv)); };
-    double e_restart = INFINITY, e_prev = INFINITY;
+    LpLoop loop;                                           // the restart rule's memory (lp_math.h: lp_decide)
     int64_t cnt = 0;
-    int it = 0, restarts = 0;
+    int it = 0;
     bool converged = false;
     const double *x_fin = d_x, *y_fin = d_y;
     LpRec fin{};
@@ -357,33 +223,31 @@ extern "C" int desc_lp_sij_run_dev(const desc_device_problem* dp, const desc_lp_
         }
         ++cnt;
         if (!checks || (it % P.check_every != 0 && it != P.max_iter)) continue;
-        LpRec rc_cur, rc_avg;
+        LpRec rc_cur, rc_avg{};
         if ((rc = evaluate(d_x, d_y, &rc_cur))) return rc;
         bool use_avg = false;
         if (restart) {
             hipLaunchKernelGGL(k_lp_average, dim3(grid_for(mp, 1024)), dim3(256), 0, 0, d_xs, d_xa, (double)cnt, mp);
             hipLaunchKernelGGL(k_lp_average, dim3(grid_for(2 * mc, 1024)), dim3(256), 0, 0, d_ys, d_ya, (double)cnt, 2 * mc);
             if ((rc = evaluate(d_xa, d_ya, &rc_avg))) return rc;                                       // last: d_zt / d_ownt belong to the average
-            use_avg = error_of(rc_avg) <= error_of(rc_cur);
         }
+        const int act = lp_decide(loop, rc_cur, rc_avg, restart, P.tol, cnt, it, P.max_iter, &use_avg);
         const LpRec& cand = use_avg ? rc_avg : rc_cur;
-        const double e = error_of(cand);
-        if (P.verbose) printf("lp iter %d: viol %.3e  P %.9g  D %.9g  err %.3e  %s  restarts %d\n", it, cand.viol, cand.P, dual_obj(cand), e, use_avg ? "avg" : "cur", restarts);
+        if (P.verbose) printf("lp iter %d: viol %.3e  P %.9g  D %.9g  err %.3e  %s  restarts %d\n", it, cand.viol, cand.P, lp_dual_obj(cand), lp_error_of(cand), use_avg ? "avg" : "cur",
+                              loop.restarts - (act == LP_RESTART_AVG || act == LP_RESTART_CUR ? 1 : 0));
         fin = cand; have_fin = true; x_fin = use_avg ? d_xa : d_x; y_fin = use_avg ? d_ya : d_y;
-        if (P.tol > 0.0 && passes(cand)) { converged = true; break; }
-        if (!restart || it == P.max_iter) continue;
-        if (e <= 0.2 * e_restart || (e <= 0.8 * e_restart && e > e_prev) || (double)cnt >= 0.36 * (double)it) {
-            if (use_avg) {
-                hipLaunchKernelGGL(k_lp_restart, dim3(grid_for(mp, 1024)), dim3(256), 0, 0, d_xa, d_x, d_xs, mp);
-                hipLaunchKernelGGL(k_lp_restart, dim3(grid_for(2 * mc, 1024)), dim3(256), 0, 0, d_ya, d_y, d_ys, 2 * mc);
-                std::swap(d_z, d_zt); std::swap(d_own, d_ownt);                                          // z / own of the new y
-            } else {
-                DESC_HIP(hipMemsetAsync(d_xs, 0, sizeof(double) * mp, 0));
-                DESC_HIP(hipMemsetAsync(d_ys, 0, sizeof(double) * 2 * mc, 0));
-            }
-            x_fin = d_x; y_fin = d_y;
-            e_restart = e; e_prev = INFINITY; cnt = 0; ++restarts;
-        } else e_prev = e;
+        if (act == LP_CONVERGED) { converged = true; break; }
+        if (act == LP_CONTINUE) continue;
+        if (act == LP_RESTART_AVG) {
+            hipLaunchKernelGGL(k_lp_restart, dim3(grid_for(mp, 1024)), dim3(256), 0, 0, d_xa, d_x, d_xs, mp);
+            hipLaunchKernelGGL(k_lp_restart, dim3(grid_for(2 * mc, 1024)), dim3(256), 0, 0, d_ya, d_y, d_ys, 2 * mc);
+            std::swap(d_z, d_zt); std::swap(d_own, d_ownt);                                          // z / own of the new y
+        } else {
+            DESC_HIP(hipMemsetAsync(d_xs, 0, sizeof(double) * mp, 0));
+            DESC_HIP(hipMemsetAsync(d_ys, 0, sizeof(double) * 2 * mc, 0));
+        }
+        x_fin = d_x; y_fin = d_y;
+        cnt = 0;
     }
     if (!have_fin) { if ((rc = evaluate(d_x, d_y, &fin))) return rc; x_fin = d_x; y_fin = d_y; }
     hipLaunchKernelGGL(k_lp_out, dim3(grid_for(mp, 1024)), dim3(256), 0, 0, cs.d_pos, x_fin, d_svec, mp);
@@ -396,13 +260,13 @@ extern "C" int desc_lp_sij_run_dev(const desc_device_problem* dp, const desc_lp_
         DESC_HIP(hipMemcpy(k_out, cs.d_k, sizeof(int32_t) * mc, hipMemcpyDeviceToHost));
         for (int64_t c = 0; c < mc; ++c) k_out[c] += 1;                                                // 1-based, as CoIndMat
     }
-    I.iters = it; I.restarts = restarts; I.converged = converged ? 1 : 0;
-    I.viol = fin.viol; I.pobj = fin.P; I.dobj = dual_obj(fin);
+    I.iters = it; I.restarts = loop.restarts; I.converged = converged ? 1 : 0;
+    I.viol = fin.viol; I.pobj = fin.P; I.dobj = lp_dual_obj(fin);
     I.ms_loop = ms_since(t2); I.ms_total = ms_since(t0);
     if (tm.laps) { I.ms_col = tm.ms_col / tm.laps; I.ms_row = tm.ms_row / tm.laps; }
     if (!converged && P.tol > 0.0)
         fprintf(stderr, "[desc_amd] linprog_sij: the LP solver stopped at max_iter = %d with viol %.3e, P %.9g, D %.9g (tol %.1e): S_vec is the better of the last iterate and the running average\n",
-                P.max_iter, fin.viol, fin.P, dual_obj(fin), P.tol);
+                P.max_iter, fin.viol, fin.P, lp_dual_obj(fin), P.tol);
     if (P.verbose) fflush(stdout);
     if (info) *info = I;
     return DESC_OK;

@@ -2,7 +2,7 @@
 """A small Monte-Carlo study in ONE batched call: mean |S_vec - ErrVec| against the corruption level q, averaged over a few trials
 of Uniform_Topology(100, 0.5, q, 0.1) -- the shape of the figures the DESC paper draws (error against q on graphs of 100-200 nodes).
 
-    python examples/monte_carlo.py [--trials 5] [--n 100] [--iters 100] [--rotations] [--refined] [--baselines] [--mpls]
+    python examples/monte_carlo.py [--trials 5] [--n 100] [--iters 100] [--rotations] [--refined] [--baselines] [--mpls] [--lp]
 
 --rotations: the demo's own metric next to it -- one DESC_init_batch call (the PGD pass, then the batched GCW eigen-solve) and the mean
 rotation error in degrees (Rotation_Alignment against the ground truth), the column of Demo/compare_algorithms.m.
@@ -12,6 +12,9 @@ refinement) and the mean rotation error of R_est next to that of its initialisat
 CEMP+GCW (CEMP_GCW_batch) and CEMP+MST (CEMP_MST_batch), with the demo's CEMP parameters (compare_algorithms.m:26-29).
 --mpls: the MPLS curve from one MPLS_batch call (CEMP's rounds, the tree, then the MPLS loop of every problem in one launch), with the
 demo's CEMP and MPLS parameters (compare_algorithms.m:26-36): the mean rotation error of R_est next to that of its CEMP+MST start.
+--lp: the linprog_sij curve from one linprog_sij_batch call (the LP of every problem in one batched PDHG loop, then the batched weighted
+spectral step and refinement): mean |S_vec - ErrVec|, the mean rotation error of R_est next to that of its spectral start, and the
+PDHG steps of the fastest and the slowest problem per q.
 """
 import argparse
 import os
@@ -23,7 +26,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from desc_amd import (CEMP_GCW_batch, CEMP_MST_batch, CEMP_batch, ConstantStepSize, DESC_PGD_batch, DESC_batch,  # noqa: E402
-                      DESC_init_batch, MPLS_batch, Rotation_Alignment, Uniform_Topology)
+                      DESC_init_batch, MPLS_batch, Rotation_Alignment, Uniform_Topology, linprog_sij_batch)
 
 
 def baselines(models, qs, trials):
@@ -65,6 +68,22 @@ def mpls_curve(models, qs, trials):
         print(f" {q:4.2f}   {re.mean():8.4f}                       ({re.min():.4f} .. {re.max():.4f})      {ri.mean():8.4f}                          {ni.min()} .. {ni.max()}")
 
 
+def lp_curve(models, qs, trials):
+    """One linprog_sij_batch call: the LP relaxation of the problem DESC solves as a QP."""
+    t0 = time.perf_counter()
+    out = linprog_sij_batch(models, dict(seed=0), return_info=True)
+    ms = (time.perf_counter() - t0) * 1e3
+    print(f"linprog_sij, {len(models)} problems in one linprog_sij_batch call: {ms:.1f} ms (the LP loop {out[0][2]['lp']['timings']['ms_loop']:.1f} ms)")
+    shape = (len(qs), trials)
+    err = np.array([np.abs(s - mo.ErrVec).mean() for (_, s, _), mo in zip(out, models)]).reshape(shape)
+    est = np.array([Rotation_Alignment(R, mo.R_orig)[2] for (R, _, _), mo in zip(out, models)]).reshape(shape)
+    ini = np.array([Rotation_Alignment(info["R_gcw"], mo.R_orig)[2] for (_, _, info), mo in zip(out, models)]).reshape(shape)
+    its = np.array([info["lp"]["iters"] for _, _, info in out]).reshape(shape)
+    print("    q   mean |S_vec - ErrVec|   linprog_sij rotation error, degrees   its spectral start's (R_gcw)   PDHG steps (min .. max)")
+    for q, e, re, ri, ni in zip(qs, err, est, ini, its):
+        print(f" {q:4.2f}   {e.mean():.4f}                  {re.mean():8.4f}                              {ri.mean():8.4f}                       {ni.min()} .. {ni.max()}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--trials", type=int, default=5)
@@ -74,6 +93,7 @@ def main():
     ap.add_argument("--refined", action="store_true", help="one DESC_batch call: the rotation error of DESC() next to its initialisation's")
     ap.add_argument("--baselines", action="store_true", help="CEMP, CEMP+GCW and CEMP+MST next to DESC: one batched call per curve")
     ap.add_argument("--mpls", action="store_true", help="the MPLS curve: one MPLS_batch call")
+    ap.add_argument("--lp", action="store_true", help="the linprog_sij curve: one linprog_sij_batch call")
     a = ap.parse_args()
     qs = [0.0, 0.1, 0.2, 0.3, 0.4, 0.5]
     models = [Uniform_Topology(a.n, 0.5, q, 0.1, "uniform", seed=1000 * k + t) for k, q in enumerate(qs) for t in range(a.trials)]
@@ -94,6 +114,8 @@ def main():
             baselines(models, qs, a.trials)
         if a.mpls:
             mpls_curve(models, qs, a.trials)
+        if a.lp:
+            lp_curve(models, qs, a.trials)
         return
     t0 = time.perf_counter()
     if a.rotations:
@@ -114,6 +136,8 @@ def main():
             baselines(models, qs, a.trials)
         if a.mpls:
             mpls_curve(models, qs, a.trials)
+        if a.lp:
+            lp_curve(models, qs, a.trials)
         return
     print("    q   mean |S_vec - ErrVec|   (min .. max over the trials)")
     for q, row in zip(qs, err):
@@ -122,6 +146,8 @@ def main():
         baselines(models, qs, a.trials)
     if a.mpls:
         mpls_curve(models, qs, a.trials)
+    if a.lp:
+        lp_curve(models, qs, a.trials)
 
 
 if __name__ == "__main__":

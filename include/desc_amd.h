@@ -738,6 +738,50 @@ int desc_mpls_batch_run(desc_cemp_batch* h, const double* s_vec, const double* R
                         const double* beta, int32_t n_beta, const double* tau, int32_t n_tau, const double* alpha, int32_t n_alpha,
                         double* R_est, desc_mpls_info* infos, desc_mpls_batch_timings* timings /* nullable */);
 
+/* The LP of linprog_sij (desc_lp_sij_run_dev's samples, incidence and PDHG loop) for B independent small problems at once: the variables
+ * and cycles of all problems lie behind one another and every launch of the loop -- two per step, about ten per check -- is shared by the
+ * batch (csrc/lp_batch.hip; the arithmetic and the decision rule are csrc/lp_math.h, one text with the single call).  Problem b's s_vec,
+ * y, k and record are bit for bit what desc_lp_sij_run_dev returns for it alone with the same seed, nsample and parameters, and no bit of
+ * them depends on the batch around it: every sum of a problem runs over that problem's own virtual grid (the grid the single call
+ * launches for it), and after a check one kernel takes each problem's decisions (restart, stop, returned point) on the device from the
+ * records the host reads in the single call.  The host reads one int32 per check: the number of problems still running.  A problem that
+ * stopped is frozen while the others run on; its iters is the step of its stop.
+ * desc_lp_batch_plan: the host half of create without a device, for sizing and tests: per problem nsample, m_pos, the offsets of its
+ * variables and of its cycles (count + 1 entries each) and the blocks of its two virtual grids; every array nullable.
+ * desc_lp_batch_create: everything that does not depend on tol, max_iter, check_every or restart.  nsample (nullable): count entries, 0 =
+ * the rule of linprog_sij.m:43 evaluated for that problem alone (NULL: the rule for all); seeds (nullable: 0 for all): count sampling
+ * keys.  Variable l of problem b is the batch's variable var_off[b] + l, cycle t of it the batch's cycle row_off[b] + l * nsample_b + t.
+ * Refused before any device work, naming the problem: what desc_problem validation refuses, an empty edge list, nsample < 0
+ * (DESC_ERR_INVALID); a node of more neighbours than desc_cemp_batch_max_degree() = 4096, the cap of the batched sampler, shared with
+ * desc_cemp_batch_create (DESC_ERR_INVALID: solve it with linprog_sij); a batch whose LP rows 2 * sum(m_pos_b * nsample_b) reach 2^31
+ * (DESC_ERR_TOO_LARGE: split the batch).  A problem without a triangle is the empty LP: s_vec = 1, iters = 0, converged = 1.
+ * desc_lp_batch_sizes: node_off / edge_off / var_off / row_off: count + 1 entries; nsample / m_pos: count entries; each nullable.
+ * desc_lp_batch_get_samples: pos_edges: var_off[count] 0-based edge ids (sorted order, local to the problem), the LP's variables; k:
+ * row_off[count] sampled third nodes, 1-based; what params->pos_out and k_out of the single call receive.  Each nullable.
+ * desc_lp_batch_run: params (NULL: the defaults): tol, max_iter, check_every and restart are read, nsample and seed belong to create,
+ * verbose is ignored (the call prints nothing).  s_vec: edge_off[count] doubles; y (nullable): 2 row_off[count] doubles, each problem's
+ * duals of its returned point; infos: count records (ms_loop = ms_total = the call's; the other stage times are 0).  max_iter = 0 returns
+ * the start x = 0, y = 0 and its record.  Problems that stop at max_iter with tol > 0 are named in one warning line on stderr.  The handle
+ * may be run any number of times with other parameters; two handles may be alive at once.  An empty batch returns DESC_OK. */
+typedef struct desc_lp_batch desc_lp_batch;   /* opaque */
+typedef struct desc_lp_batch_timings {
+    double ms_structure;      /* host: validation, CSR, codegrees, nsample, offsets, workgroup tables (create)      */
+    double ms_upload;         /* host -> device copies and allocations (create)                                    */
+    double ms_build;          /* samples, S0Mat and the transposed incidence (create), wall clock                  */
+    double ms_loop;           /* the loop and the downloads (desc_lp_batch_run), wall clock                        */
+    double ms_total;          /* wall clock of desc_lp_batch_run                                                   */
+} desc_lp_batch_timings;      /* 40 bytes */
+int desc_lp_batch_plan(const desc_problem* probs, int32_t count, const int32_t* nsample /* nullable */, int32_t* nsample_out, int64_t* m_pos,
+                       int64_t* var_off, int64_t* row_off, int32_t* ncol, int32_t* nrow);
+int desc_lp_batch_create(const desc_problem* probs, int32_t count, const int32_t* nsample /* nullable */, const uint64_t* seeds /* nullable */,
+                         int32_t device, desc_lp_batch** out);
+int desc_lp_batch_sizes(const desc_lp_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off, int32_t* nsample, int64_t* m_pos,
+                        int64_t* var_off, int64_t* row_off);
+int desc_lp_batch_get_samples(desc_lp_batch* h, int32_t* pos_edges, int32_t* k);
+int desc_lp_batch_run(desc_lp_batch* h, const desc_lp_params* params, double* s_vec, double* y /* nullable */, desc_lp_info* infos,
+                      desc_lp_batch_timings* timings /* nullable */);
+void desc_lp_batch_destroy(desc_lp_batch* h);
+
 /* One-shot: what the MEX shim calls.  Builds the structure (p->build_where),
  * uploads, runs, downloads, frees. */
 int desc_pgd_solve(const desc_problem* prob, const desc_params* p, desc_result* r);
