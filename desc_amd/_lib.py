@@ -41,6 +41,8 @@ EXPORTS = [
     "desc_cemp_batch_destroy", "desc_mst_batch_max_n", "desc_mst_batch_check", "desc_mst_batch_run",
     "desc_refine_batch_max_n", "desc_refine_batch_create", "desc_refine_batch_sizes", "desc_refine_batch_run", "desc_refine_batch_destroy",
     "desc_mpls_batch_max_n", "desc_mpls_batch_run",
+    "desc_irls_batch_max_n", "desc_irls_batch_create", "desc_irls_batch_sizes", "desc_irls_batch_run", "desc_irls_batch_destroy",
+    "desc_irls_tree_sequence",
     "desc_lp_batch_plan", "desc_lp_batch_create", "desc_lp_batch_sizes", "desc_lp_batch_get_samples", "desc_lp_batch_run", "desc_lp_batch_destroy",
     "desc_test_laa_r2q", "desc_test_laa_q2r", "desc_test_laa_edge_log", "desc_test_laa_rhs", "desc_test_laa_pcg", "desc_test_laa_node_update",
     "desc_test_irls_node_update", "desc_test_laa_weights", "desc_test_irls_weights", "desc_test_laa_quantile", "desc_test_irls_project",
@@ -134,6 +136,11 @@ class RefineBatchTimings(C.Structure):
 
 class MplsBatchTimings(C.Structure):
     _fields_ = [("ms_setup", C.c_double), ("ms_input", C.c_double), ("ms_loop", C.c_double), ("ms_download", C.c_double),
+                ("ms_total", C.c_double)]
+
+
+class IrlsBatchTimings(C.Structure):
+    _fields_ = [("ms_structure", C.c_double), ("ms_upload", C.c_double), ("ms_project", C.c_double), ("ms_solve", C.c_double),
                 ("ms_total", C.c_double)]
 
 
@@ -339,6 +346,15 @@ def load():
     L.desc_mpls_batch_max_n.argtypes = []
     L.desc_mpls_batch_run.argtypes = [C.c_void_p, F64P, F64P, C.c_double, C.c_int32, F64P, C.c_int32, F64P, C.c_int32, F64P, C.c_int32, F64P,
                                       C.POINTER(MplsInfo), C.POINTER(MplsBatchTimings)]
+    L.desc_irls_batch_max_n.restype = C.c_int32
+    L.desc_irls_batch_max_n.argtypes = []
+    L.desc_irls_batch_create.argtypes = [C.POINTER(Problem), C.c_int32, C.POINTER(I32P), C.c_int32, C.POINTER(C.c_void_p)]
+    L.desc_irls_batch_sizes.argtypes = [C.c_void_p, I32P, I64P, I64P]
+    L.desc_irls_batch_run.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_int32, F64P, F64P, C.POINTER(IrlsInfo),
+                                      C.POINTER(IrlsBatchTimings)]
+    L.desc_irls_batch_destroy.argtypes = [C.c_void_p]
+    L.desc_irls_batch_destroy.restype = None
+    L.desc_irls_tree_sequence.argtypes = [C.POINTER(Problem), I32P, I32P, I64P]
     L.desc_lp_batch_plan.argtypes = [C.POINTER(Problem), C.c_int32, I32P, I32P, I64P, I64P, I64P, I32P, I32P]
     L.desc_lp_batch_create.argtypes = [C.POINTER(Problem), C.c_int32, I32P, C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_void_p)]
     L.desc_lp_batch_sizes.argtypes = [C.c_void_p, I32P, I64P, I64P, I32P, I64P, I64P, I64P]
@@ -799,6 +815,60 @@ class RefineBatch(_BatchHandle):
                                            C.byref(tm)))
         outs = [(Rb, dict(iters=i.iters, cg_iters=i.cg_iters, score=i.score, ms_total=i.ms_total, cg_unconverged=i.cg_unconverged,
                           cg_residual=i.cg_residual)) for Rb, i in zip(_split_R(R, self.node_off), infos)]
+        return outs, _timings(tm)
+
+
+def irls_batch_max_n():
+    """desc_irls_batch_max_n: the largest problem (nodes) the batched IRLS takes."""
+    return int(load().desc_irls_batch_max_n())
+
+
+def irls_tree_sequence(prob, order=None):
+    """desc_irls_tree_sequence (host only): the spanning-tree start of BoxMedianSO3Graph.m:79-114 over the edges of ``prob`` in the
+    caller's row order (``order``: marshal_edges' perm, or None) -> (edges, dirs, reached): per reached node, in the order the
+    reference sets them, the sorted edge id and 0 (Q(j) from Q(i)) or 1 (Q(i) from Q(j)); ``reached`` == n iff the graph is connected."""
+    od = None if order is None else np.ascontiguousarray(order, dtype=np.int32)
+    if od is not None and od.size != prob.m:
+        raise ValueError("order must have m entries")
+    seq = out_buffer(max(prob.n - 1, 1), np.int32)
+    reached = C.c_int64(0)
+    check(load().desc_irls_tree_sequence(C.byref(prob.c), ptr(od, I32P), ptr(seq, I32P), C.byref(reached)))
+    seq = seq[:max(int(reached.value) - 1, 0)]
+    return seq >> 1, seq & 1, int(reached.value)
+
+
+class IrlsBatch(_BatchHandle):
+    """Owner of a desc_irls_batch*: IRLS_GM / IRLS_L12 of B small connected problems in two launches (desc_irls_batch_*).  ``probs`` is a
+    sequence of ProblemArrays, ``orders`` an optional sequence of per-problem row orders (marshal_edges' perm, or None).  The handle may
+    be run any number of times, in either mode."""
+
+    _kind = "irls"
+
+    def __init__(self, probs, orders=None, device=0):
+        probs = list(probs)
+        B = len(probs)
+        arr = None
+        if orders is not None:
+            if len(orders) != B:
+                raise ValueError(f"orders must hold one entry per problem ({B}), not {len(orders)}")
+            self._orders = [None if o is None else np.ascontiguousarray(o, dtype=np.int32) for o in orders]     # kept alive over create
+            for q, o in zip(probs, self._orders):
+                if o is not None and o.size != q.m:
+                    raise ValueError("an order must have one entry per edge of its problem")
+            arr = (I32P * max(B, 1))(*[ptr(o, I32P) for o in self._orders])
+        self._open(probs, arr, int(device))
+
+    def run(self, mode, sigma_deg=5.0, max_iter_l1=10, max_iter_irls=100):
+        """One batched run -> a list of per-problem (R, R_l1 (3,3,n_b) Fortran-ordered, info dict with irls_run's keys) and the call's
+        timings."""
+        B = self.count
+        R, R1 = out_buffer(9 * self.n), out_buffer(9 * self.n)
+        infos = (IrlsInfo * max(B, 1))()
+        tm = IrlsBatchTimings()
+        check(load().desc_irls_batch_run(self.handle, int(mode), float(sigma_deg), int(max_iter_l1), int(max_iter_irls), ptr(R, F64P),
+                                         ptr(R1, F64P), infos, C.byref(tm)))
+        outs = [(Rb, R1b, {k: getattr(i, k) for k, _ in IrlsInfo._fields_})
+                for Rb, R1b, i in zip(_split_R(R, self.node_off), _split_R(R1, self.node_off), infos)]
         return outs, _timings(tm)
 
 

@@ -705,6 +705,76 @@ def MPLS_batch(problems, CEMP_parameters, MPLS_parameters, seeds=None, return_in
             for (R, info), (R_init, tree), S_b, perm in zip(outs, mst, S_list, perms)]
 
 
+def _irls_batch(mode, name, problems, SIGMA, MaxIterations, device, return_info):
+    _check_sequence(problems)
+    mi = np.atleast_1d(np.asarray(MaxIterations, dtype=np.float64)).reshape(-1)
+    if mi.size != 2:
+        raise ValueError("MaxIterations must have two entries [L1, IRLS]")
+    sigma = 5.0 if SIGMA is None or np.size(SIGMA) == 0 else float(SIGMA)
+    for b, item in enumerate(problems):
+        if isinstance(item, _Marshalled):
+            continue
+        try:
+            R = np.asarray(item.RijMat if hasattr(item, "RijMat") else item[1])
+        except (TypeError, IndexError, KeyError):
+            continue                                                 # _marshal_problems has the words for it
+        if R.ndim == 2 and R.shape[0] == 4:
+            raise ValueError(f"problem {b}: the quaternion form of RR (4 x m) is not supported: pass RijMat as 3 x 3 x m rotation matrices")
+    probs, perms = _marshal_problems(problems)
+    if not probs:
+        return []
+    single = "IRLS_GM / IRLS_L12"
+    _check_batch_sizes(probs, _lib.irls_batch_max_n(), "per-node state of the L1 stage", single)
+    for b, (q, perm) in enumerate(zip(probs, perms)):                # connectivity: the host half of the spanning-tree start
+        with _invalid_as_value_error():
+            reached = _lib.irls_tree_sequence(q, perm)[2]
+        if reached < q.n:
+            raise ValueError(f"problem {b}: the graph is not connected ({reached} of {q.n} nodes reached from node 1): solve it with {single}")
+    with _batch_handle(_lib.IrlsBatch, probs, perms, int(device)) as batch:
+        outs, timings = batch.run(mode, sigma, int(mi[0]), int(mi[1]))
+    warned = [b for b, (_, _, info) in enumerate(outs) if info["warned_edges"]]
+    if warned:
+        import warnings
+        warnings.warn(f"{name}: edge rotations with all three singular values off 1 by >= 0.01 were projected to SO(3) in problems "
+                      + ", ".join(f"{b} ({outs[b][2]['warned_edges']})" for b in warned), RuntimeWarning, stacklevel=3)
+    if not return_info:
+        return [R for R, _, _ in outs]
+    result = []
+    for R, R_l1, info in outs:
+        info = {k: v for k, v in info.items() if not k.startswith("ms_")}
+        info["R_l1"] = R_l1
+        info["timings"] = timings
+        result.append((R, info))
+    return result
+
+
+def IRLS_GM_batch(problems, SIGMA=5, MaxIterations=(10, 100), device=0, return_info=False):
+    """IRLS_GM (Algorithms/IRLS_GM.m, the "IRLS-GM" row of Demo/compare_algorithms.m) on B independent small, connected problems in two
+    GPU launches (desc_irls_batch_*; the reference has no such call): one projects the edges of all problems, one runs a workgroup per
+    problem from the spanning-tree start through the L1 loop and the reweighted loop.
+
+    ``problems`` as for DESC_PGD_batch; one ``SIGMA`` (degrees) and one ``MaxIterations`` = (L1, IRLS) for the whole batch.  Returns a
+    list of R (3 x 3 x n_b).  With ``return_info`` a list of (R, info): ``info`` has the keys of ``IRLS_GM(..., return_info=True)``
+    -- ``R_l1``, the iteration counts and scores, the primal-dual and PCG counts, ``warned_edges``, ``comp_nodes`` / ``comp_edges`` --
+    except the per-stage milliseconds, which are the batch's, under ``timings``.  Entry b is bit for bit
+    ``IRLS_GM(RijMat_b, Ind_b, SIGMA=..., MaxIterations=..., return_info=True)`` in all of them, and no bit of it depends on the
+    batch around it.  The call prints nothing; projected ("warned") edges are reported in one RuntimeWarning naming the problems.
+
+    Refused (ValueError, before the device is touched, naming the problem): not a sequence, an empty edge list, ``MaxIterations``
+    without two entries, the 4 x m quaternion form of RijMat, a problem that is not connected or has more than
+    ``_lib.irls_batch_max_n()`` nodes (solve it with IRLS_GM / IRLS_L12; component extraction stays with the single call).  There is no
+    ``Rinit``.  An edge rotation with det <= 0, or with all three singular values off 1 by >= 0.1, raises DescError naming the problem
+    and the 1-based row of its ``Ind`` (the lowest problem, the smallest row in it)."""
+    return _irls_batch(_lib.IRLS_GM, "IRLS_GM_batch", problems, SIGMA, MaxIterations, device, return_info)
+
+
+def IRLS_L12_batch(problems, SIGMA=5, MaxIterations=(10, 100), device=0, return_info=False):
+    """IRLS_L12 (Algorithms/IRLS_L12.m, the "IRLS-L0.5" row) on B independent small, connected problems: as IRLS_GM_batch with
+    Utils/L12.m's weights in the reweighted stage (SIGMA is accepted and unused, as in the reference); entry b is bit for bit
+    ``IRLS_L12(RijMat_b, Ind_b, ...)``."""
+    return _irls_batch(_lib.IRLS_L12, "IRLS_L12_batch", problems, SIGMA, MaxIterations, device, return_info)
+
+
 def linprog_sij_batch(problems, params=None, seeds=None, rotations=True, return_info=False):
     """linprog_sij (Algorithms/linprog_sij.m:16) on B independent small problems: the LP of every problem in one batched PDHG loop
     (desc_lp_batch_*: two launches per step and one 4-byte read-back per check for the whole batch), then the row-normalised weighted

@@ -1,4 +1,4 @@
-// Host part shared by the batched calls that walk per-problem CSR rows (gcw_batch.hip, cemp_batch.hip, mpls_batch.hip, mst_batch.hip, refine_batch.hip, lp_batch.hip):
+// Host part shared by the batched calls that walk per-problem CSR rows (gcw_batch.hip, cemp_batch.hip, mpls_batch.hip, mst_batch.hip, refine_batch.hip, irls_batch.hip, lp_batch.hip):
 // validation, offsets and the CSR of every problem with LOCAL node and edge ids -- what desc_gcw_batch_csr returns -- and the host
 // loops every batched call repeats.  No device: the device half of a handle is BatchDevice (batch_device.h).
 #pragma once

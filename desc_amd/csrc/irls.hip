@@ -16,58 +16,23 @@
 //   * The primal-dual step scalars (tau, sdg, resnorm, step length) are formed on the host from fixed-order device partials, one
 //     read-back per backtracking trial; the CG keeps its scalars on the device and is probed every PD_PROBE = 5 steps.
 // Reductions are fixed-order partials (no float atomics): results are bitwise reproducible from run to run.
+// The per-element arithmetic of the kernels below and the scalar rules of pd_solve and the two outer loops are the text of irls_math.h,
+// which the batched call (irls_batch.hip) runs too: a change there changes both paths together.
 #include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
+#include "irls_math.h"
 #include "laa.h"
 
 namespace desc {
 namespace {
 
-constexpr int RG = 256;            // blocks of the partial-reduction kernels: partials are [RG][K], summed on the host in block order
-// The Newton-system CG is probed every PD_PROBE steps (one dot and one read-back): the reported step count is the solve's true count
-// rounded up to a multiple of PD_PROBE.  At C4 a CG step costs ~0.1 ms and a probe a few microseconds.
-constexpr int PD_PROBE = 5;
+constexpr int RG = PD_RG;         // blocks of the partial-reduction kernels: partials are [RG][K], summed on the host in block order
 
-// ---- stage 3: per-edge checks and projection ---------------------------------------------------------------------------------------
-// one-sided Jacobi SVD of a 3x3 column-major matrix: A V = U S; a[] ends as U S (columns), v[] as V; s sorted descending
-__device__ void svd3(double a[9], double v[9], double s[3]) {
-    for (int k = 0; k < 9; ++k) v[k] = (k % 4 == 0) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 40; ++sweep) {
-        bool rotated = false;
-        for (int pr = 0; pr < 3; ++pr) {
-            const int p = pr == 2 ? 1 : 0, q = pr == 0 ? 1 : 2;
-            double al = 0, be = 0, ga = 0;
-            for (int r = 0; r < 3; ++r) { al += a[3 * p + r] * a[3 * p + r]; be += a[3 * q + r] * a[3 * q + r]; ga += a[3 * p + r] * a[3 * q + r]; }
-            if (!(fabs(ga) > 1e-300 && fabs(ga) > 1e-17 * sqrt(al * be))) continue;
-            rotated = true;
-            const double zeta = (be - al) / (2.0 * ga);
-            const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-            const double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
-            for (int r = 0; r < 3; ++r) {
-                const double ap = a[3 * p + r], aq = a[3 * q + r];
-                a[3 * p + r] = c * ap - sn * aq; a[3 * q + r] = sn * ap + c * aq;
-                const double vp = v[3 * p + r], vq = v[3 * q + r];
-                v[3 * p + r] = c * vp - sn * vq; v[3 * q + r] = sn * vp + c * vq;
-            }
-        }
-        if (!rotated) break;
-    }
-    for (int k = 0; k < 3; ++k) s[k] = sqrt(a[3 * k] * a[3 * k] + a[3 * k + 1] * a[3 * k + 1] + a[3 * k + 2] * a[3 * k + 2]);
-    for (int i = 0; i < 2; ++i)                                               // descending, as MATLAB's svd
-        for (int k = 0; k < 2 - i; ++k)
-            if (s[k] < s[k + 1]) {
-                double t = s[k]; s[k] = s[k + 1]; s[k + 1] = t;
-                for (int r = 0; r < 3; ++r) {
-                    t = a[3 * k + r]; a[3 * k + r] = a[3 * k + 3 + r]; a[3 * k + 3 + r] = t;
-                    t = v[3 * k + r]; v[3 * k + r] = v[3 * k + 3 + r]; v[3 * k + 3 + r] = t;
-                }
-            }
-}
-
+// ---- stage 3: per-edge checks and projection (the per-edge text: irls_math.h) -------------------------------------------------------
 // IRLS_GM.m:82-93 for every edge: P = U round(S) V' of RR = Rij' (column-major, RR orientation).  status: 3 det <= 0, 2 all three
 // |s - 1| >= 0.1, 1 all three >= 0.01 (warning), 0 fine.  The smallest failing caller row goes to *bad_row (integer atomicMin),
 // warnings are counted.  only >= 0: that edge alone, its status / det / s into info[5].
@@ -75,14 +40,8 @@ __global__ __launch_bounds__(256) void k_irls_project(const double* rij, const i
                                                       int32_t* warn, int64_t only, double* info) {
     const int64_t lo = only >= 0 ? only : 0, hi = only >= 0 ? only + 1 : m;
     for (int64_t e = lo + (int64_t)blockIdx.x * 256 + threadIdx.x; e < hi; e += (int64_t)gridDim.x * 256) {
-        double a[9], v[9], s[3];
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) a[r + 3 * c] = rij[9 * e + c + 3 * r];          // RR(r, c) = Rij(c, r)
-        const double det = a[0] * (a[4] * a[8] - a[7] * a[5]) - a[3] * (a[1] * a[8] - a[7] * a[2]) + a[6] * (a[1] * a[5] - a[4] * a[2]);
-        svd3(a, v, s);
-        bool all10 = true, all01 = true;
-        for (int k = 0; k < 3; ++k) { const double d = fabs(s[k] - 1.0); all10 = all10 && d >= 0.1; all01 = all01 && d >= 0.01; }
-        const int status = det <= 0.0 ? 3 : (all10 ? 2 : (all01 ? 1 : 0));
+        double a[9], v[9], s[3], det;
+        const int status = irls_edge_status(rij + 9 * e, a, v, s, &det);
         if (only >= 0) {
             info[0] = status; info[1] = det; info[2] = s[0]; info[3] = s[1]; info[4] = s[2];
             continue;
@@ -90,23 +49,11 @@ __global__ __launch_bounds__(256) void k_irls_project(const double* rij, const i
         const int32_t row = order ? order[e] : (int32_t)e;
         if (status >= 2) atomicMin(bad_row, row);
         else if (status == 1) atomicAdd(warn, 1);
-        double out[9];
-        for (int k = 0; k < 9; ++k) out[k] = 0.0;
-        for (int k = 0; k < 3; ++k) {                                                  // U * round(S) * V'
-            if (!(s[k] > 0.0)) continue;
-            const double rs = round(s[k]);
-            for (int r = 0; r < 3; ++r) {
-                const double ur = (a[3 * k + r] / s[k]) * rs;
-                for (int c = 0; c < 3; ++c) out[r + 3 * c] += ur * v[3 * k + c];
-            }
-        }
-        for (int k = 0; k < 9; ++k) P[9 * e + k] = out[k];
+        irls_edge_project(a, v, s, P + 9 * e);
     }
 }
 
-// ---- stage 4: l1decode_pd, three coordinates batched ---------------------------------------------------------------------------------
-struct Pd3 { double tau[3], s[3], ymax[3]; int act[3]; };      // per-coordinate scalars of one launch (act: 1 = this coordinate takes part)
-
+// ---- stage 4: l1decode_pd, three coordinates batched (the per-element text: irls_math.h) ---------------------------------------------
 // max |y - Ax| with Ax = 0 (:271): MATLAB's max, per coordinate
 __global__ __launch_bounds__(256) void k_pd_absmax(const double* y, int64_t m, double* part) {
     double v[3] = {0, 0, 0};
@@ -118,14 +65,7 @@ __global__ __launch_bounds__(256) void k_pd_absmax(const double* y, int64_t m, d
 __global__ __launch_bounds__(256) void k_pd_init(const double* y, int64_t m, Pd3 a, double* Ax, double* u, double* f1, double* f2, double* l1,
                                                  double* l2, double* ev) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256)
-        for (int c = 0; c < 3; ++c) {
-            const int64_t k = 3 * e + c;
-            const double ax = 0.0, yy = y[k];
-            const double uu = 0.95 * fabs(yy - ax) + 0.10 * a.ymax[c];
-            const double g1 = (ax - yy) - uu, g2 = (-ax + yy) - uu;
-            const double m1 = -1.0 / g1, m2 = -1.0 / g2;
-            Ax[k] = ax; u[k] = uu; f1[k] = g1; f2[k] = g2; l1[k] = m1; l2[k] = m2; ev[k] = m1 - m2;
-        }
+        for (int c = 0; c < 3; ++c) pd_init_at(y, a.ymax[c], 3 * e + c, Ax, u, f1, f2, l1, l2, ev);
 }
 // A' v over the CSR rows (16 lanes per row, as k_rhs): MODE 0 out = A' ev1; MODE 1 out = coef .* (A' ev1) - A' ev2 (w1p, :303-304);
 // MODE 2 out = sum of ev1 over the row (the Jacobi diagonal of A' diag(ev1) A).  Row 0 (node 1, grounded) is 0.
@@ -136,19 +76,11 @@ __global__ __launch_bounds__(256) void k_pd_gather(const int32_t* rowptr, const 
     const int row0 = (blockIdx.x * 256 + threadIdx.x) >> 4, nrows = (gridDim.x * 256) >> 4;
     for (int vb = row0 - (row0 % 4); vb < n; vb += nrows) {
         const int v = vb + (row0 % 4);
-        double g[3] = {0, 0, 0}, h[3] = {0, 0, 0};
-        if (v < n && v > 0)
-            for (int t = rowptr[v] + l16; t < rowptr[v + 1]; t += 16) {
-                const int64_t e = eid[t];
-                const double sg = MODE == 2 ? 1.0 : (double)sgn[t];
-                for (int c = 0; c < 3; ++c) {
-                    g[c] += sg * ev1[3 * e + c];
-                    if (MODE == 1) h[c] += sg * ev2[3 * e + c];
-                }
-            }
-        for (int c = 0; c < 3; ++c) { g[c] = group16_sum(g[c]); if (MODE == 1) h[c] = group16_sum(h[c]); }
+        const bool on = v < n && v > 0;
+        double g[3], h[3];
+        pd_gather_row16<MODE>(eid, sgn, ev1, ev2, on ? rowptr[v] : 0, on ? rowptr[v + 1] : 0, l16, g, h);
         if (v < n && l16 == 0)
-            for (int c = 0; c < 3; ++c) out[3 * v + c] = MODE == 1 ? a.tau[c] * g[c] - h[c] : g[c];
+            for (int c = 0; c < 3; ++c) out[3 * v + c] = pd_gather_out<MODE>(a.tau[c], g[c], h[c]);
     }
 }
 // :296-304 per edge: w2, sig1, sig2, sigx; ev1 = -1./fu1 + 1./fu2 (w1), ev2 = (sig2./sig1).*w2 (w1p).  Coordinates not taking part get
@@ -156,46 +88,22 @@ __global__ __launch_bounds__(256) void k_pd_gather(const int32_t* rowptr, const 
 __global__ __launch_bounds__(256) void k_pd_pre(int64_t m, Pd3 a, const double* f1, const double* f2, const double* l1, const double* l2,
                                                 double* w2, double* s1, double* s2, double* sx, double* ev1, double* ev2) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256)
-        for (int c = 0; c < 3; ++c) {
-            const int64_t k = 3 * e + c;
-            if (!a.act[c]) { sx[k] = 1.0; ev1[k] = 0.0; ev2[k] = 0.0; continue; }
-            const double g1 = f1[k], g2 = f2[k], m1 = l1[k], m2 = l2[k], it = 1.0 / a.tau[c];
-            const double ww = -1.0 - it * (1.0 / g1 + 1.0 / g2);                     // :296
-            const double a1 = -m1 / g1 - m2 / g2;                                    // :298
-            const double a2 = m1 / g1 - m2 / g2;                                     // :299
-            const double ax = a1 - a2 * a2 / a1;                                     // :300
-            w2[k] = ww; s1[k] = a1; s2[k] = a2; sx[k] = ax;
-            ev1[k] = -1.0 / g1 + 1.0 / g2;                                           // :303
-            ev2[k] = (a2 / a1) * ww;                                                 // :304
-        }
+        for (int c = 0; c < 3; ++c) pd_pre_at(a, c, 3 * e + c, f1, f2, l1, l2, w2, s1, s2, sx, ev1, ev2);
 }
-// :315-324: Adx, du, dlamu1, dlamu2; ev = dlamu1 - dlamu2 (Atdv); the two step-length minima (:327-330; MATLAB's min skips NaN, so
-// does fmin) as block partials [RG][6]: lamu bound per coordinate, then fu bound per coordinate
+// :315-324: Adx, du, dlamu1, dlamu2; ev = dlamu1 - dlamu2 (Atdv); the two step-length minima (:327-330) as block partials [RG][6]: lamu
+// bound per coordinate, then fu bound per coordinate
 __global__ __launch_bounds__(256) void k_pd_dir(const int32_t* ii, const int32_t* jj, int64_t m, Pd3 a, const double* dx, const double* f1,
                                                 const double* f2, const double* l1, const double* l2, const double* w2, const double* s1,
                                                 const double* s2, double* Adx, double* du, double* d1, double* d2, double* ev, double* part) {
     double mn[6] = {INFINITY, INFINITY, INFINITY, INFINITY, INFINITY, INFINITY};
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256) {
         const int i = ii[e], j = jj[e];
-        for (int c = 0; c < 3; ++c) {
-            const int64_t k = 3 * e + c;
-            if (!a.act[c]) { ev[k] = 0.0; continue; }
-            const double adx = (j > 0 ? dx[3 * j + c] : 0.0) - (i > 0 ? dx[3 * i + c] : 0.0);
-            const double it = 1.0 / a.tau[c], g1 = f1[k], g2 = f2[k], m1 = l1[k], m2 = l2[k];
-            const double dd = (w2[k] - s2[k] * adx) / s1[k];                                 // :318
-            const double q1 = -(m1 / g1) * (adx - dd) - m1 - it * 1.0 / g1;                   // :320
-            const double q2 = (m2 / g2) * (adx + dd) - m2 - it * 1.0 / g2;                    // :321
-            Adx[k] = adx; du[k] = dd; d1[k] = q1; d2[k] = q2; ev[k] = q1 - q2;
-            if (q1 < 0) mn[c] = fmin(mn[c], -m1 / q1);                                        // :325-326
-            if (q2 < 0) mn[c] = fmin(mn[c], -m2 / q2);
-            if ((adx - dd) > 0) mn[3 + c] = fmin(mn[3 + c], -g1 / (adx - dd));               // :327-328
-            if ((-adx - dd) > 0) mn[3 + c] = fmin(mn[3 + c], -g2 / (-adx - dd));
-        }
+        for (int c = 0; c < 3; ++c) pd_dir_at(a, c, e, i, j, dx, f1, f2, l1, l2, w2, s1, s2, Adx, du, d1, d2, ev, mn);
     }
     block_reduce<6, 1>(mn, part + 6 * blockIdx.x);
 }
 // |[rdual; rcent]|^2 per coordinate as block partials [RG][3] (:280-283, :334-336, :347-349).  TRIAL: of the trial point at step a.s
-// (state + s * direction); else of the state itself.  rdual = gradf0 + [Atv; -lamu1 - lamu2], rcent = [-lamu1.*fu1; -lamu2.*fu2] - 1/tau.
+// (state + s * direction); else of the state itself.
 template <bool TRIAL>
 __global__ __launch_bounds__(256) void k_pd_resid(int64_t m, int n, Pd3 a, const double* y, const double* Ax, const double* u, const double* l1,
                                                   const double* l2, const double* Atv, const double* Adx, const double* du, const double* d1,
@@ -204,21 +112,13 @@ __global__ __launch_bounds__(256) void k_pd_resid(int64_t m, int n, Pd3 a, const
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256)
         for (int c = 0; c < 3; ++c) {
             if (!a.act[c]) continue;
-            const int64_t k = 3 * e + c;
-            double ax = Ax[k], uu = u[k], m1 = l1[k], m2 = l2[k];
-            if (TRIAL) { const double s = a.s[c]; uu = u[k] + s * du[k]; ax = Ax[k] + s * Adx[k]; m1 = l1[k] + s * d1[k]; m2 = l2[k] + s * d2[k]; }
-            const double g1 = (ax - y[k]) - uu, g2 = (-ax + y[k]) - uu;
-            const double it = 1.0 / a.tau[c];
-            const double rd = 1.0 + (-m1 - m2);
-            const double r1 = -m1 * g1 - it, r2 = -m2 * g2 - it;
-            acc[c] += rd * rd + r1 * r1 + r2 * r2;
+            acc[c] += pd_resid_edge<TRIAL>(a, c, 3 * e + c, y, Ax, u, l1, l2, Adx, du, d1, d2);
         }
     for (int v = blockIdx.x * 256 + threadIdx.x; v < n; v += gridDim.x * 256) {
         if (v == 0) continue;
         for (int c = 0; c < 3; ++c) {
             if (!a.act[c]) continue;
-            const double t = TRIAL ? Atv[3 * v + c] + a.s[c] * Atdv[3 * v + c] : Atv[3 * v + c];
-            acc[c] += t * t;
+            acc[c] += pd_resid_node<TRIAL>(a, c, v, Atv, Atdv);
         }
     }
     block_reduce<3, 0>(acc, part + 3 * blockIdx.x);
@@ -231,17 +131,12 @@ __global__ __launch_bounds__(256) void k_pd_accept(int64_t m, int n, Pd3 a, cons
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256)
         for (int c = 0; c < 3; ++c) {
             const int64_t k = 3 * e + c;
-            if (a.act[c]) {
-                const double s = a.s[c];
-                const double uu = u[k] + s * du[k], ax = Ax[k] + s * Adx[k], m1 = l1[k] + s * d1[k], m2 = l2[k] + s * d2[k];
-                const double g1 = (ax - y[k]) - uu, g2 = (-ax + y[k]) - uu;
-                u[k] = uu; Ax[k] = ax; l1[k] = m1; l2[k] = m2; f1[k] = g1; f2[k] = g2;
-            }
+            if (a.act[c]) pd_accept_at(a, c, k, y, Ax, u, l1, l2, f1, f2, Adx, du, d1, d2);
             acc[c] += f1[k] * l1[k]; acc[3 + c] += f2[k] * l2[k];
         }
     for (int v = blockIdx.x * 256 + threadIdx.x; v < n; v += gridDim.x * 256)
         for (int c = 0; c < 3; ++c)
-            if (a.act[c]) { x[3 * v + c] = x[3 * v + c] + a.s[c] * dx[3 * v + c]; Atv[3 * v + c] = Atv[3 * v + c] + a.s[c] * Atdv[3 * v + c]; }
+            if (a.act[c]) pd_accept_node(a, c, v, x, Atv, dx, Atdv);
     block_reduce<6, 0>(acc, part + 6 * blockIdx.x);
 }
 
@@ -249,10 +144,8 @@ __global__ __launch_bounds__(256) void k_pd_accept(int64_t m, int n, Pd3 a, cons
 __global__ __launch_bounds__(256) void k_l1_node_update(const double* x, Quat* Q, int n, double* part) {
     double sc[1] = {0.0};
     for (int v = blockIdx.x * 256 + threadIdx.x; v < n; v += gridDim.x * 256) {
-        double theta;
-        const Quat w = qexp(x[3 * v], x[3 * v + 1], x[3 * v + 2], &theta);
+        const double theta = l1_node_update(x + 3 * v, Q + v);
         if (v > 0) sc[0] = fmax(sc[0], theta);
-        Q[v] = qmul(Q[v], w);
     }
     block_reduce<1, 2>(sc, part + blockIdx.x);
 }
@@ -260,13 +153,8 @@ __global__ __launch_bounds__(256) void k_l1_node_update(const double* x, Quat* Q
 // ---- stage 5: residuals and weights (RobustMeanSO3Graph.m:169-170, L12.m:169-171) from the solved W (before the exp map) --------------
 __global__ __launch_bounds__(256) void k_irls_weights(const double* x, const double* B, const int32_t* ii, const int32_t* jj, int64_t m, int mode,
                                                       double sigma, double* w) {
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256) {
-        const double s = edge_residual_sq(x, B, ii, jj, e);
-        double wt;
-        if (mode == DESC_IRLS_GM) wt = sigma / (s + sigma * sigma);
-        else { wt = 1.0 / pow(sqrt(s), 0.75); if (wt > 1e4) wt = 1e4; }
-        w[e] = wt;
-    }
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256)
+        w[e] = irls_weight(edge_residual_sq(x, B, ii, jj, e), mode, sigma);
 }
 __global__ void k_fill(double* p, int64_t count, double v) {
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (int64_t)gridDim.x * blockDim.x) p[t] = v;
@@ -332,7 +220,6 @@ int pd_solve(PdState& S, const double* d_B, int pdmaxiter) {
     const desc_device_problem* dp = L.dp;
     const int64_t m = S.m;
     const int n = (int)S.n;
-    const double pdtol = 2.220446049250313e-16, alpha = 0.01, beta = 0.5, mu = 10.0;   // :262-266
     const double M = (double)m;
     DESC_HIP(hipMemcpyAsync(S.y, d_B, sizeof(double) * 3 * m, hipMemcpyDeviceToDevice, 0));
     DESC_HIP(hipMemsetAsync(S.x, 0, sizeof(double) * 3 * n, 0));
@@ -354,15 +241,15 @@ int pd_solve(PdState& S, const double* d_B, int pdmaxiter) {
         if (rc2) return rc2;
         for (int c = 0; c < 3; ++c) {
             if (!act[c]) continue;
-            sdg[c] = -(dots[c] + dots[3 + c]);
-            tau[c] = mu * 2.0 * M / sdg[c];
+            sdg[c] = pd_sdg(dots[c], dots[3 + c]);
+            tau[c] = pd_tau(M, sdg[c]);
             b.act[c] = 1; b.tau[c] = tau[c];
         }
         hipLaunchKernelGGL(k_pd_resid<false>, dim3(RG), dim3(256), 0, 0, m, n, b, S.y, S.Ax, S.u, S.l1, S.l2, S.Atv, S.Adx, S.du, S.d1, S.d2,
                            S.Atdv, S.part);
         double rr[3];
         if ((rc2 = read_part(S, 3, rr, false))) return rc2;
-        for (int c = 0; c < 3; ++c) if (act[c]) resnorm[c] = std::sqrt(rr[c]);
+        for (int c = 0; c < 3; ++c) if (act[c]) resnorm[c] = pd_resnorm(rr[c]);
         return DESC_OK;
     };
     int run[3] = {1, 1, 1};
@@ -373,14 +260,14 @@ int pd_solve(PdState& S, const double* d_B, int pdmaxiter) {
     }
     if ((rc = scalars(run))) return rc;
     int pditer = 0;
-    for (int c = 0; c < 3; ++c) run[c] = !((sdg[c] < pdtol) | (pditer >= pdmaxiter));         // :287
+    for (int c = 0; c < 3; ++c) run[c] = pd_goes_on(sdg[c], pditer, pdmaxiter);                // :287
     while (run[0] || run[1] || run[2]) {
         ++pditer;
         for (int c = 0; c < 3; ++c) { a.act[c] = run[c]; a.tau[c] = tau[c]; }
         // ---- Newton system (:296-312)
         hipLaunchKernelGGL(k_pd_pre, dim3(S.egrid), dim3(256), 0, 0, m, a, S.f1, S.f2, S.l1, S.l2, S.w2, S.s1, S.s2, S.sx, S.ev1, S.ev2);
         Pd3 g = a;
-        for (int c = 0; c < 3; ++c) g.tau[c] = run[c] ? -1.0 / tau[c] : 0.0;                 // w1 = -1/tau * (A' ...)
+        for (int c = 0; c < 3; ++c) g.tau[c] = pd_gather_coef(run[c], tau[c]);                // w1 = -1/tau * (A' ...)
         hipLaunchKernelGGL(k_pd_gather<1>, dim3(S.rgrid), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj_eid, L.d_sgn, S.ev1, S.ev2, g, S.w1p, n);
         DESC_HIP(hipDeviceSynchronize());
         auto tp = std::chrono::steady_clock::now();
@@ -402,7 +289,7 @@ int pd_solve(PdState& S, const double* d_B, int pdmaxiter) {
         hipLaunchKernelGGL(k_pd_gather<0>, dim3(S.rgrid), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj_eid, L.d_sgn, S.ev1, nullptr, a, S.Atdv, n);
         double s[3] = {0, 0, 0};
         for (int c = 0; c < 3; ++c)
-            if (run[c]) { s[c] = std::fmin(1.0, mins[c]); s[c] = 0.99 * std::fmin(s[c], mins[3 + c]); }
+            if (run[c]) s[c] = pd_step_length(mins[c], mins[3 + c]);
         // ---- backtracking (:332-346): one trial of every searching coordinate per launch
         int search[3], backiter[3] = {0, 0, 0}, accept[3] = {0, 0, 0};
         double s_acc[3] = {0, 0, 0};
@@ -416,14 +303,12 @@ int pd_solve(PdState& S, const double* d_B, int pdmaxiter) {
             if ((rc = read_part(S, 3, rr, false))) return rc;
             for (int c = 0; c < 3; ++c) {
                 if (!search[c]) continue;
-                const bool suffdec = std::sqrt(rr[c]) <= (1.0 - alpha * s[c]) * resnorm[c];
-                const double s_tried = s[c];
-                s[c] = beta * s[c];
-                ++backiter[c];
-                if (backiter[c] > 32) {                                                      // :339-343
+                double s_tried;
+                const int verdict = pd_trial(rr[c], resnorm[c], &s[c], &backiter[c], &s_tried);
+                if (verdict == PD_TRIAL_STUCK) {                                             // :339-343
                     if (S.verbose) printf("Stuck backtracking, returning last iterate.  (See Section 4 of notes for more information.)\n");
                     ++S.stuck; search[c] = 0; run[c] = 0;
-                } else if (suffdec) { search[c] = 0; accept[c] = 1; s_acc[c] = s_tried; }
+                } else if (verdict == PD_TRIAL_ACCEPT) { search[c] = 0; accept[c] = 1; s_acc[c] = s_tried; }
             }
         }
         // ---- next iterate (:348-356)
@@ -433,7 +318,7 @@ int pd_solve(PdState& S, const double* d_B, int pdmaxiter) {
                            S.d1, S.d2, S.Atdv, S.part);
         if ((rc = scalars(accept))) return rc;
         for (int c = 0; c < 3; ++c)
-            if (accept[c]) run[c] = !((sdg[c] < pdtol) | (pditer >= pdmaxiter));
+            if (accept[c]) run[c] = pd_goes_on(sdg[c], pditer, pdmaxiter);
     }
     DESC_HIP(hipGetLastError());
     return DESC_OK;
@@ -443,20 +328,11 @@ int pd_solve(PdState& S, const double* d_B, int pdmaxiter) {
 int tree_start(const desc_device_problem* sp, const hvec<int32_t>& visit, const Quat* d_QQ, hvec<Quat>& Q) {
     const int64_t n = sp->n;
     const int32_t *ii = sp->ii.data(), *jj = sp->jj.data();
-    hvec<uint8_t> done((size_t)n, 0);
-    hvec<int32_t> seq_e, seq_dir;
-    seq_e.reserve((size_t)n); seq_dir.reserve((size_t)n);
-    done[0] = 1;                                                                            // :86-87 (a = 1)
-    int64_t count = 1;
-    while (count < n) {
-        bool span = false;
-        for (const int32_t e : visit) {
-            const int i = ii[e], j = jj[e];
-            if (done[i] && !done[j]) { seq_e.push_back(e); seq_dir.push_back(0); done[j] = 1; ++count; span = true; }
-            if (!done[i] && done[j]) { seq_e.push_back(e); seq_dir.push_back(1); done[i] = 1; ++count; span = true; }
-        }
-        if (!span && count < n) return fail(DESC_ERR_STATE, "spanning-tree start: %lld of %lld nodes reached", (long long)count, (long long)n);
-    }
+    hvec<int32_t> seq, seq_e;
+    seq.reserve((size_t)n);
+    const int64_t count = irls_tree_sequence(n, ii, jj, visit.data(), (int64_t)visit.size(), seq);
+    if (count < n) return fail(DESC_ERR_STATE, "spanning-tree start: %lld of %lld nodes reached", (long long)count, (long long)n);
+    for (const int32_t en : seq) seq_e.push_back(en >> 1);
     const int cnt = (int)seq_e.size();
     hvec<Quat> qq((size_t)std::max(cnt, 1));
     if (cnt) {
@@ -469,12 +345,8 @@ int tree_start(const desc_device_problem* sp, const hvec<int32_t>& visit, const 
         DESC_HIP(hipMemcpy(qq.data(), d_out, sizeof(Quat) * cnt, hipMemcpyDeviceToHost));
     }
     Q.assign((size_t)n, Quat{1.0, 0.0, 0.0, 0.0});                                          // :78
-    for (int t = 0; t < cnt; ++t) {
-        const Quat g = qq[t];
-        const int e = seq_e[t];
-        if (seq_dir[t] == 0) Q[jj[e]] = qmul(g, Q[ii[e]]);                                  // :93-95: Q(j) = QQ * Q(i)
-        else Q[ii[e]] = qmul(Quat{-g.a, g.x, g.y, g.z}, Q[jj[e]]);                          // :101-103: Q(i) from Q(j)
-    }
+    for (int t = 0; t < cnt; ++t)
+        irls_tree_step(seq[t], qq[t], ii, jj, Q.data());                                    // :93-95, :101-103
     return DESC_OK;
 }
 
@@ -615,8 +487,8 @@ extern "C" int desc_irls_run_dev(const desc_device_problem* dp, const desc_irls_
         double changeThreshold = .001, score = INFINITY;                                     // :56, :134
         int Iteration = 0, L1Step = 2;
         if (verbose) printf("Itr\tMaxChange\tTime\n%d  NaN  %g\n", 0, ms_since(t2) / 1e3);  // :136-137
-        while (((score >= changeThreshold) || (L1Step < 2)) && (Iteration < max_l1)) {     // :138
-            if (score < changeThreshold) { L1Step = L1Step * 4; changeThreshold = changeThreshold / 100; }   // :139
+        while (l1_goes_on(score, changeThreshold, L1Step, Iteration, max_l1)) {             // :138
+            l1_step_rule(score, &changeThreshold, &L1Step);                                 // :139
             laa_edge_log(L);                                                                // :141-160
             if ((rc = pd_solve(S, L.d_B, L1Step))) return rc;                               // :162-168
             hipLaunchKernelGGL(k_l1_node_update, dim3(L.sgrid), dim3(256), 0, 0, S.x, L.d_Q, (int)nc, d_smax);   // :173-185
@@ -647,7 +519,7 @@ extern "C" int desc_irls_run_dev(const desc_device_problem* dp, const desc_irls_
         double score = INFINITY;
         int Iteration = 0;
         if (verbose) printf("%d  NaN  %g\n", 0, ms_since(t3) / 1e3);                        // :129
-        while ((score > 1e-3) && (Iteration < max_irls)) {                                  // :130
+        while (irls_goes_on(score, Iteration, max_irls)) {                                  // :130
             if ((rc = laa_step(L, &score))) return rc;                                      // :132-186
             hipLaunchKernelGGL(k_irls_weights, dim3(L.egrid), dim3(256), 0, 0, L.d_x, L.d_B, sp->d_ii, sp->d_jj, mc, P->mode, sigma, L.d_w);   // :169-171
             DESC_HIP(hipGetLastError());

@@ -81,7 +81,6 @@ __global__ __launch_bounds__(256) void k_cg_dot(const double* a, const double* b
     for (int v = threadIdx.x; v < n; v += 256) for (int c = 0; c < 3; ++c) s[c] += a[3 * v + c] * b[3 * v + c];
     block_reduce<3, 0>(s, out3);
 }
-__device__ __forceinline__ bool cg_breaks(double pq, double rz) { return !isfinite(pq) || !isfinite(rz) || (pq <= 0.0 && rz > 0.0); }
 // x = 0, r = rhs (node 0 zeroed), z = r/diag, p = z
 template <bool W3>
 __global__ void k_cg_init(CgScal* sc, const double* rhs, const double* diag, double* x, double* r, double* z, double* p, int n) {

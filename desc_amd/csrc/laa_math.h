@@ -132,6 +132,8 @@ __device__ __forceinline__ double jacobi(const double* diag, int v, int c, doubl
 // the PCG's step lengths from its scalars: alpha = r'z / p'Hp (0 unless p'Hp > 0), beta = r'z_new / r'z (0 unless r'z > 0)
 __device__ __forceinline__ double cg_alpha(double rz, double pq) { return pq > 0 ? rz / pq : 0.0; }
 __device__ __forceinline__ double cg_beta(double rz, double rz_new) { return rz > 0 ? rz_new / rz : 0.0; }
+// a breakdown of the PCG (tracked only for the primal-dual Newton systems): a non-finite p'Hp or r'z, or p'Hp <= 0 while r'z > 0
+__device__ __forceinline__ bool cg_breaks(double pq, double rz) { return !isfinite(pq) || !isfinite(rz) || (pq <= 0.0 && rz > 0.0); }
 // the probe's test on one coordinate: not yet at |r| <= 1e-13 |b|
 __host__ __device__ __forceinline__ bool cg_unfinished(double rnorm, double bnorm) { return rnorm > 1e-26 * bnorm && rnorm > 1e-300; }
 

@@ -1,9 +1,11 @@
-// The Weighted-LAA loop of ONE problem inside ONE workgroup of 256 threads, shared by k_refine_batch (refine_batch.hip) and k_mpls_batch
-// (mpls_batch.hip): one text, so a problem gets the same bits whichever of them steps it (as laa_math.h, cemp_math.h and small_dense.h
+// The Weighted-LAA loop of ONE problem inside ONE workgroup of 256 threads, shared by k_refine_batch (refine_batch.hip), k_mpls_batch
+// (mpls_batch.hip) and k_irls_batch (irls_batch.hip): one text, so a problem gets the same bits whichever of them steps it (as laa_math.h, cemp_math.h and small_dense.h
 // for their callers).
 //   WgLaa / wg_laa_views   the per-node state in dynamic LDS, 26 doubles per node (Q; x r z p q rhs; diag; Wv), addressed with the
 //                          problem's own n, and the problem's views of the per-edge arrays in global memory
-//   wg_laa_step            Weighted_LAA.m: the edge log map, the normal equations, laa_pcg<false, false> with its probe every 25 steps,
+//   wg_pcg<W3, TRACK>      laa_pcg of laa.h: the Jacobi-PCG of three right-hand sides with its probe; <true, true> serves the primal-dual
+//                          Newton systems of k_irls_batch (irls_batch.hip)
+//   wg_laa_step            Weighted_LAA.m: the edge log map, the normal equations, wg_pcg<false, false> with its probe every 25 steps,
 //                          the exp map, Q <- Q * W, the score in chunks of 256 rows
 //   wg_quantile            MATLAB's quantile of a per-edge array: the extrema, the Hazen position, the two order statistics by an exact
 //                          radix select over the 64-bit order key (8-bit digits, integer histogram in LDS), their interpolation
@@ -69,34 +71,25 @@ __device__ __forceinline__ void rb_dot(const double* a, const double* b, int n, 
     __syncthreads();
 }
 
-// One Weighted-LAA step on the state s with the weights s.w; returns the score (the same in every thread; the caller looks at
-// isfinite).  Expects a barrier behind the last write of Q and w; ends with one.
-__device__ __forceinline__ double wg_laa_step(const WgLaa& s, int cg_max, WgCg& cg) {
+// laa_pcg<W3, TRACK> (laa.h) inside the workgroup: x_c = (A' diag(w_c) A) \ rhs_c for the three coordinates, x r z p q rhs diag in LDS,
+// the weights in global memory (W3: w[3 e + c] and diag[3 v + c], else w[e] * w[e] and diag[v]), the probe |r| <= 1e-13 |b| every `probe`
+// steps over the coordinates in act.  TRACK: a breakdown freezes its coordinate, takes it out of the probe and comes back in
+// bad_out[c]; else bad_out[] comes back 0.  The bookkeeping of the solve is added to cg.  Expects a barrier behind the last write of
+// rhs, diag and w; ends with one.
+template <bool W3, bool TRACK>
+__device__ __forceinline__ void wg_pcg(int n, const int32_t* rowptr, const int32_t* adj, const int32_t* eid, const double* w, const double* rhs,
+                                       const double* diag, double* x, double* r, double* z, double* p, double* q, const int act[3], int probe,
+                                       int cg_max, WgCg& cg, int bad_out[3]) {
     __shared__ double cgs[15];                          // rz, rz_new, pq, bnorm, rnorm: CgScal's doubles
-    __shared__ double sh4[4];
+    __shared__ int cg_bad[3];                           // CgScal's bad
     const int tid = threadIdx.x, l16 = tid & 15, row = tid >> 4;
-    const int n = s.n, m = s.m;
-    const int32_t *rowptr = s.rowptr, *adj = s.adj, *eid = s.eid, *ii = s.ii, *jj = s.jj;
-    const int8_t* sgn = s.sgn;
-    Quat *QQ = s.QQ, *Q = s.Q;
-    double *B = s.B, *w = s.w, *x = s.x, *r = s.r, *z = s.z, *p = s.p, *q = s.q, *rhs = s.rhs, *diag = s.diag, *Wv = s.Wv;
     double *rz = cgs, *rz_new = cgs + 3, *pq = cgs + 6, *bnorm = cgs + 9, *rnorm = cgs + 12;
-    // ---- Weighted_LAA: the edge log map, the normal equations
-    for (int e = tid; e < m; e += 256) edge_log(QQ[e], Q[ii[e]], Q[jj[e]], B + 3 * (int64_t)e);
-    __syncthreads();
-    for (int vb = 0; vb < n; vb += 16) {
-        const int v = vb + row;
-        const bool on = v < n;
-        double s3[3], dg;
-        rhs_row16(eid, sgn, w, B, on ? rowptr[v] : 0, on ? rowptr[v + 1] : 0, l16, s3, &dg);
-        if (on && l16 == 0) { rhs[3 * v] = s3[0]; rhs[3 * v + 1] = s3[1]; rhs[3 * v + 2] = s3[2]; diag[v] = dg; }
-    }
-    __syncthreads();
-    // ---- laa_pcg<false, false>: x = 0, r = rhs (node 0 zeroed), z = r / diag, p = z
+    // ---- x = 0, r = rhs (node 0 zeroed), z = r / diag, p = z
+    if (TRACK && tid < 3) cg_bad[tid] = 0;
     for (int v = tid; v < n; v += 256)
         for (int c = 0; c < 3; ++c) {
             const double rv = v > 0 ? rhs[3 * v + c] : 0.0;
-            const double zv = jacobi<false>(diag, v, c, rv);
+            const double zv = jacobi<W3>(diag, v, c, rv);
             x[3 * v + c] = 0.0; r[3 * v + c] = rv; z[3 * v + c] = zv; p[3 * v + c] = zv;
         }
     __syncthreads();
@@ -108,19 +101,26 @@ __device__ __forceinline__ double wg_laa_step(const WgLaa& s, int cg_max, WgCg& 
             const int v = vb + row;
             const bool on = v < n && v > 0;
             double s3[3];
-            lap_row16<false>(adj, eid, w, p, v, on ? rowptr[v] : 0, on ? rowptr[v + 1] : 0, l16, s3);
+            lap_row16<W3>(adj, eid, w, p, v, on ? rowptr[v] : 0, on ? rowptr[v + 1] : 0, l16, s3);
             if (v < n && l16 == 0) { q[3 * v] = s3[0]; q[3 * v + 1] = s3[1]; q[3 * v + 2] = s3[2]; }
         }
         __syncthreads();
         rb_dot(p, q, n, pq);
         double al[3];
-        for (int c = 0; c < 3; ++c) al[c] = cg_alpha(rz[c], pq[c]);
+        for (int c = 0; c < 3; ++c) {
+            const bool brk = TRACK && (cg_bad[c] || cg_breaks(pq[c], rz[c]));
+            al[c] = brk ? 0.0 : cg_alpha(rz[c], pq[c]);
+        }
+        if (TRACK) {
+            __syncthreads();                                                            // every thread has read cg_bad
+            if (tid < 3 && cg_breaks(pq[tid], rz[tid])) cg_bad[tid] = 1;
+        }
         for (int v = tid; v < n; v += 256)
             for (int c = 0; c < 3; ++c) {
                 const double xv = x[3 * v + c] + al[c] * p[3 * v + c];
                 const double rv = r[3 * v + c] - al[c] * q[3 * v + c];
                 x[3 * v + c] = xv; r[3 * v + c] = rv;
-                z[3 * v + c] = jacobi<false>(diag, v, c, rv);
+                z[3 * v + c] = jacobi<W3>(diag, v, c, rv);
             }
         __syncthreads();
         rb_dot(r, z, n, rz_new);
@@ -129,20 +129,54 @@ __device__ __forceinline__ double wg_laa_step(const WgLaa& s, int cg_max, WgCg& 
         for (int v = tid; v < n; v += 256)
             for (int c = 0; c < 3; ++c) p[3 * v + c] = z[3 * v + c] + be[c] * p[3 * v + c];
         __syncthreads();                                                                // every thread has read rz
-        if (tid < 3) rz[tid] = rz_new[tid];
-        if (k % RB_PROBE == 0 || k == cg_max) {                                          // convergence probe: |r| <= 1e-13 |b|
+        if (tid < 3) {
+            if (TRACK && !isfinite(rz_new[tid])) cg_bad[tid] = 1;
+            rz[tid] = rz_new[tid];
+        }
+        if (k % probe == 0 || k == cg_max) {                                             // convergence probe: |r| <= 1e-13 |b|
             rb_dot(r, r, n, rnorm);
             int fin = 1;
-            for (int c = 0; c < 3; ++c) if (cg_unfinished(rnorm[c], bnorm[c])) fin = 0;
+            for (int c = 0; c < 3; ++c) if (act[c] && !(TRACK && cg_bad[c]) && cg_unfinished(rnorm[c], bnorm[c])) fin = 0;
             done = uni(fin);
             if (done || k == cg_max) break;
         }
     }
     __syncthreads();                                                                    // the last roll of rz is behind every thread
     cg.total += min(k, cg_max);                                                         // the true count rounded up to the probe interval
-    for (int c = 0; c < 3; ++c)
-        if (bnorm[c] > 0) { const double ratio = rnorm[c] / bnorm[c]; if (cg.worst_sq < ratio) cg.worst_sq = ratio; }
+    for (int c = 0; c < 3; ++c) {
+        const int bd = TRACK && cg_bad[c];
+        bad_out[c] = act[c] && bd;
+        if (act[c] && !bd && bnorm[c] > 0) { const double ratio = rnorm[c] / bnorm[c]; if (cg.worst_sq < ratio) cg.worst_sq = ratio; }
+    }
     if (!done) ++cg.unconverged;
+    __syncthreads();                                                                    // cgs and cg_bad are free again
+}
+
+// One Weighted-LAA step on the state s with the weights s.w; returns the score (the same in every thread; the caller looks at
+// isfinite).  Expects a barrier behind the last write of Q and w; ends with one.
+__device__ __forceinline__ double wg_laa_step(const WgLaa& s, int cg_max, WgCg& cg) {
+    __shared__ double sh4[4];
+    const int tid = threadIdx.x, l16 = tid & 15, row = tid >> 4;
+    const int n = s.n, m = s.m;
+    const int32_t *rowptr = s.rowptr, *eid = s.eid, *ii = s.ii, *jj = s.jj;
+    const int8_t* sgn = s.sgn;
+    Quat *QQ = s.QQ, *Q = s.Q;
+    double *B = s.B, *w = s.w, *x = s.x, *rhs = s.rhs, *diag = s.diag, *Wv = s.Wv;
+    // ---- Weighted_LAA: the edge log map, the normal equations
+    for (int e = tid; e < m; e += 256) edge_log(QQ[e], Q[ii[e]], Q[jj[e]], B + 3 * (int64_t)e);
+    __syncthreads();
+    for (int vb = 0; vb < n; vb += 16) {
+        const int v = vb + row;
+        const bool on = v < n;
+        double s3[3], dg;
+        rhs_row16(eid, sgn, w, B, on ? rowptr[v] : 0, on ? rowptr[v + 1] : 0, l16, s3, &dg);
+        if (on && l16 == 0) { rhs[3 * v] = s3[0]; rhs[3 * v + 1] = s3[1]; rhs[3 * v + 2] = s3[2]; diag[v] = dg; }
+    }
+    __syncthreads();
+    // ---- laa_pcg<false, false> with laa_step's probe interval
+    const int all[3] = {1, 1, 1};
+    int bad[3];
+    wg_pcg<false, false>(n, rowptr, s.adj, eid, w, rhs, diag, x, s.r, s.z, s.p, s.q, all, RB_PROBE, cg_max, cg, bad);
     // ---- Weighted_LAA.m:40-50: exp map, Q <- Q * W, the score in chunks of 256 rows
     double tot = 0.0;
     for (int base = 0; base < n; base += 256) {

@@ -2,7 +2,7 @@
 """A small Monte-Carlo study in ONE batched call: mean |S_vec - ErrVec| against the corruption level q, averaged over a few trials
 of Uniform_Topology(100, 0.5, q, 0.1) -- the shape of the figures the DESC paper draws (error against q on graphs of 100-200 nodes).
 
-    python examples/monte_carlo.py [--trials 5] [--n 100] [--iters 100] [--rotations] [--refined] [--baselines] [--mpls] [--lp]
+    python examples/monte_carlo.py [--trials 5] [--n 100] [--iters 100] [--rotations] [--refined] [--baselines] [--mpls] [--lp] [--irls]
 
 --rotations: the demo's own metric next to it -- one DESC_init_batch call (the PGD pass, then the batched GCW eigen-solve) and the mean
 rotation error in degrees (Rotation_Alignment against the ground truth), the column of Demo/compare_algorithms.m.
@@ -15,6 +15,8 @@ demo's CEMP and MPLS parameters (compare_algorithms.m:26-36): the mean rotation 
 --lp: the linprog_sij curve from one linprog_sij_batch call (the LP of every problem in one batched PDHG loop, then the batched weighted
 spectral step and refinement): mean |S_vec - ErrVec|, the mean rotation error of R_est next to that of its spectral start, and the
 PDHG steps of the fastest and the slowest problem per q.
+--irls: the IRLS-GM and IRLS-L0.5 curves, one IRLS_GM_batch and one IRLS_L12_batch call (a workgroup per problem runs the L1 stage and
+the reweighted stage in one launch): the mean rotation error of each next to that of the L1 stage they share, and the IRLS steps.
 """
 import argparse
 import os
@@ -26,7 +28,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from desc_amd import (CEMP_GCW_batch, CEMP_MST_batch, CEMP_batch, ConstantStepSize, DESC_PGD_batch, DESC_batch,  # noqa: E402
-                      DESC_init_batch, MPLS_batch, Rotation_Alignment, Uniform_Topology, linprog_sij_batch)
+                      DESC_init_batch, IRLS_GM_batch, IRLS_L12_batch, MPLS_batch, Rotation_Alignment, Uniform_Topology, linprog_sij_batch)
 
 
 def baselines(models, qs, trials):
@@ -84,6 +86,27 @@ def lp_curve(models, qs, trials):
         print(f" {q:4.2f}   {e.mean():.4f}                  {re.mean():8.4f}                              {ri.mean():8.4f}                       {ni.min()} .. {ni.max()}")
 
 
+def irls_curves(models, qs, trials):
+    """One call per curve: IRLS_GM_batch, IRLS_L12_batch (the demo's defaults: SIGMA = 5 degrees, MaxIterations = [10, 100])."""
+    t0 = time.perf_counter()
+    gm = IRLS_GM_batch(models, return_info=True)
+    t1 = time.perf_counter()
+    l12 = IRLS_L12_batch(models, return_info=True)
+    t2 = time.perf_counter()
+    print(f"IRLS, {len(models)} problems, one call per curve: IRLS_GM_batch {(t1 - t0) * 1e3:.1f} ms (its solve launch "
+          f"{gm[0][1]['timings']['ms_solve']:.1f} ms), IRLS_L12_batch {(t2 - t1) * 1e3:.1f} ms")
+    shape = (len(qs), trials)
+    e_gm = np.array([Rotation_Alignment(R, mo.R_orig)[2] for (R, _), mo in zip(gm, models)]).reshape(shape)
+    e_l12 = np.array([Rotation_Alignment(R, mo.R_orig)[2] for (R, _), mo in zip(l12, models)]).reshape(shape)
+    e_l1 = np.array([Rotation_Alignment(info["R_l1"], mo.R_orig)[2] for (_, info), mo in zip(gm, models)]).reshape(shape)
+    n_gm = np.array([info["irls_iters"] for _, info in gm]).reshape(shape)
+    n_l12 = np.array([info["irls_iters"] for _, info in l12]).reshape(shape)
+    print("    q   IRLS-GM rotation error, degrees   IRLS-L0.5 rotation error, degrees   their L1 start's (R_l1)   IRLS steps GM / L0.5 (min .. max)")
+    for q, a, b, c, na, nb in zip(qs, e_gm, e_l12, e_l1, n_gm, n_l12):
+        print(f" {q:4.2f}   {a.mean():8.4f}                          {b.mean():8.4f}                            {c.mean():8.4f}"
+              f"                  {na.min()} .. {na.max()} / {nb.min()} .. {nb.max()}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--trials", type=int, default=5)
@@ -94,6 +117,7 @@ def main():
     ap.add_argument("--baselines", action="store_true", help="CEMP, CEMP+GCW and CEMP+MST next to DESC: one batched call per curve")
     ap.add_argument("--mpls", action="store_true", help="the MPLS curve: one MPLS_batch call")
     ap.add_argument("--lp", action="store_true", help="the linprog_sij curve: one linprog_sij_batch call")
+    ap.add_argument("--irls", action="store_true", help="the IRLS-GM and IRLS-L0.5 curves: one IRLS_GM_batch and one IRLS_L12_batch call")
     a = ap.parse_args()
     qs = [0.0, 0.1, 0.2, 0.3, 0.4, 0.5]
     models = [Uniform_Topology(a.n, 0.5, q, 0.1, "uniform", seed=1000 * k + t) for k, q in enumerate(qs) for t in range(a.trials)]
@@ -116,6 +140,8 @@ def main():
             mpls_curve(models, qs, a.trials)
         if a.lp:
             lp_curve(models, qs, a.trials)
+        if a.irls:
+            irls_curves(models, qs, a.trials)
         return
     t0 = time.perf_counter()
     if a.rotations:
@@ -138,6 +164,8 @@ def main():
             mpls_curve(models, qs, a.trials)
         if a.lp:
             lp_curve(models, qs, a.trials)
+        if a.irls:
+            irls_curves(models, qs, a.trials)
         return
     print("    q   mean |S_vec - ErrVec|   (min .. max over the trials)")
     for q, row in zip(qs, err):
@@ -148,6 +176,8 @@ def main():
         mpls_curve(models, qs, a.trials)
     if a.lp:
         lp_curve(models, qs, a.trials)
+    if a.irls:
+        irls_curves(models, qs, a.trials)
 
 
 if __name__ == "__main__":

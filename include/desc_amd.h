@@ -738,6 +738,53 @@ int desc_mpls_batch_run(desc_cemp_batch* h, const double* s_vec, const double* R
                         const double* beta, int32_t n_beta, const double* tau, int32_t n_tau, const double* alpha, int32_t n_alpha,
                         double* R_est, desc_mpls_info* infos, desc_mpls_batch_timings* timings /* nullable */);
 
+/* IRLS_GM / IRLS_L12 (desc_irls_run) for B independent small, connected problems in TWO launches (csrc/irls_batch.hip): the last two rows
+ * of Demo/compare_algorithms.m for a Monte-Carlo batch.  Launch A checks and projects the edges of all problems (IRLS_GM.m:82-93) and
+ * leaves per problem the smallest failing caller row and a warning count; launch B runs one workgroup per problem through stages 4 and
+ * 5 of desc_irls_run_dev -- the spanning-tree start, the L1 loop with its primal-dual steps, their Newton systems by the PCG with
+ * per-coordinate weights and breakdown tracking, Q = R2Q(R_l1), the reweighted loop -- with the per-node state (34 doubles) in LDS and
+ * no host round trip.  The per-element arithmetic and the scalar rules are one text with the single call (csrc/irls_math.h,
+ * csrc/laa_math.h, csrc/laa_wg.h) and every sum is taken in the single call's order (the 256 virtual blocks of its partial-reduction
+ * kernels included): problem b's R_out, R_l1 and record (every field of desc_irls_info but the ms_*) are bit for bit what desc_irls_run
+ * gives for it with the same order, and no bit of them depends on the batch around it.
+ * desc_irls_batch_max_n: the largest n whose per-node state fits the 160 KiB of LDS a workgroup may declare next to the kernel's fixed
+ * LDS (557; at least the eigen-solve's 278).
+ * desc_irls_batch_create: orders (nullable, and each entry nullable) = per problem desc_irls_params.order, the caller's 0-based row of
+ * every edge: the row order of the spanning-tree start and of the error message.  Validates every problem and refuses -- before any
+ * device work, naming the problem -- an empty edge list, an order that is no permutation, n > desc_irls_batch_max_n() and a graph that
+ * is not connected (DESC_ERR_INVALID: solve it with IRLS_GM / IRLS_L12; component extraction stays with the single call).  Builds the
+ * per-problem CSR, the incidence signs and the tree sequences (the graph part of BoxMedianSO3Graph.m:79-114, in the caller's row
+ * order) on the host, checks the kernel's fixed LDS (hipFuncGetAttributes) plus the launch's dynamic LDS against 160 KiB, uploads.
+ * count == 0 is legal and touches no device.  Without a device: DESC_ERR_HIP and *out = NULL.  The handle may be run any number of
+ * times, in either mode.
+ * desc_irls_batch_sizes: node_off[count+1], edge_off[count+1] (each nullable).
+ * desc_irls_batch_run: mode DESC_IRLS_GM / DESC_IRLS_L12; sigma_deg, max_iter_l1, max_iter_irls as desc_irls_params (<= 0: 5, 10, 100),
+ * one set for the whole batch; there is no R_init.  R_out / R_l1 (nullable): problem b's 3x3xn_b column-major blocks at 9 * node_off[b];
+ * infos: count entries (comp_nodes / comp_edges = the problem's n and m; ms_total = the call's, the other ms_* 0: the stage times are
+ * the batch's, in timings).  The call prints nothing: warned_edges and cg_unconverged say what the single call warns about.  An edge
+ * block with det <= 0 or with all three singular values off 1 by >= 0.1 is DESC_ERR_INVALID naming the problem and the 1-based caller
+ * row with the single call's numbers -- the lowest problem first, the smallest caller row within it. */
+typedef struct desc_irls_batch desc_irls_batch;   /* opaque */
+typedef struct desc_irls_batch_timings {
+    double ms_structure;      /* validation + per-problem CSR + incidence signs + tree sequences (create's host part) */
+    double ms_upload;         /* host -> HBM (create)                                                                */
+    double ms_project;        /* run: launch A and the read-back of its flags (wall clock)                            */
+    double ms_solve;          /* launch B, device time (HIP events)                                                  */
+    double ms_total;          /* wall clock of desc_irls_batch_run                                                   */
+} desc_irls_batch_timings;    /* 40 bytes */
+int32_t desc_irls_batch_max_n(void);
+int desc_irls_batch_create(const desc_problem* probs, int32_t count, const int32_t* const* orders /* nullable */, int32_t device,
+                           desc_irls_batch** out);
+int desc_irls_batch_sizes(const desc_irls_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off);
+int desc_irls_batch_run(desc_irls_batch* h, int32_t mode, double sigma_deg, int32_t max_iter_l1, int32_t max_iter_irls, double* R_out,
+                        double* R_l1 /* nullable */, desc_irls_info* infos, desc_irls_batch_timings* timings /* nullable */);
+void desc_irls_batch_destroy(desc_irls_batch* h);
+/* The host half of the spanning-tree start alone (no device; tests and the batched call's refusals): the passes of
+ * BoxMedianSO3Graph.m:79-114 over the edges in the caller's row order (order nullable: the edge order) from node 1.  seq (nullable,
+ * n - 1 entries): one entry 2 e + dir per reached node in the order the reference sets them (dir 0: Q(j) from Q(i) of edge e, dir 1:
+ * Q(i) from Q(j)); *reached: the nodes reached, n exactly when the graph is connected. */
+int desc_irls_tree_sequence(const desc_problem* prob, const int32_t* order, int32_t* seq, int64_t* reached);
+
 /* The LP of linprog_sij (desc_lp_sij_run_dev's samples, incidence and PDHG loop) for B independent small problems at once: the variables
  * and cycles of all problems lie behind one another and every launch of the loop -- two per step, about ten per check -- is shared by the
  * batch (csrc/lp_batch.hip; the arithmetic and the decision rule are csrc/lp_math.h, one text with the single call).  Problem b's s_vec,
