@@ -115,7 +115,7 @@ def propagate(Ind, RijMat, tree):
 
 
 def mpls_oracle(Ind, RijMat, CEMP_parameters, MPLS_parameters, seed=0, svec_for_tree=None):
-    """MPLS.m:31-257 -> dict(R_est, R_init, SVec, iters, score, tree).  ``svec_for_tree``: build the tree from this SVec (the
+    """MPLS.m:31-257 -> dict(R_est, R_init, SVec, iters, score, tree, scores: every step's score).  ``svec_for_tree``: build the tree from this SVec (the
     device's) instead of the oracle's own -- two keys within round-off of each other could otherwise pick different trees."""
     Ind = np.asarray(Ind, dtype=np.int64)
     RijMat = np.asarray(RijMat, dtype=np.float64)
@@ -134,8 +134,10 @@ def mpls_oracle(Ind, RijMat, CEMP_parameters, MPLS_parameters, seed=0, svec_for_
     score = np.inf; Iteration = 1
     Weights = 1.0 / (SVec ** 0.75)                                                        # :210
     Weights[Weights > 1e4] = 1e4                                                          # :211-213
+    scores = []
     while score > MPLS_parameters["stop_threshold"] and Iteration < maxIters:            # :218
         Q, W, B, score = Weighted_LAA(Ind_T, Q, QQ, Amatrix, Weights)                     # :220
+        scores.append(float(score))
         E = Amatrix @ W[1:, 1:4] - B                                                      # :221
         ResVec = np.sqrt(np.sum(E ** 2, axis=1)) / np.pi                                  # :222
         HVec = h_step(st, ResVec, beta[Iteration - 1])                                    # :223-237
@@ -148,4 +150,4 @@ def mpls_oracle(Ind, RijMat, CEMP_parameters, MPLS_parameters, seed=0, svec_for_
     R_est = np.zeros((3, 3, n))
     for i in range(n):
         R_est[:, :, i] = q2R(Q[i])                                                        # :251-254
-    return dict(R_est=R_est, R_init=R_init, SVec=SVec, iters=Iteration - 1, score=score, tree=tree, state=st)
+    return dict(R_est=R_est, R_init=R_init, SVec=SVec, iters=Iteration - 1, score=score, tree=tree, state=st, scores=scores)
