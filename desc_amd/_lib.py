@@ -46,6 +46,7 @@ EXPORTS = [
     "desc_lp_batch_plan", "desc_lp_batch_create", "desc_lp_batch_sizes", "desc_lp_batch_get_samples", "desc_lp_batch_run", "desc_lp_batch_destroy",
     "desc_test_laa_r2q", "desc_test_laa_q2r", "desc_test_laa_edge_log", "desc_test_laa_rhs", "desc_test_laa_pcg", "desc_test_laa_node_update",
     "desc_test_irls_node_update", "desc_test_laa_weights", "desc_test_irls_weights", "desc_test_laa_quantile", "desc_test_irls_project",
+    "desc_test_irls_pd_stage", "desc_test_irls_pd_solve",
 ]
 
 I32P = C.POINTER(C.c_int32)
@@ -373,6 +374,8 @@ def load():
     L.desc_test_irls_weights.argtypes = [C.c_void_p, F64P, F64P, C.c_int64, C.c_int32, C.c_double, F64P]
     L.desc_test_laa_quantile.argtypes = [F64P, C.c_int64, C.c_double, C.c_int64, C.c_int32, F64P]
     L.desc_test_irls_project.argtypes = [F64P, I32P, C.c_int64, C.c_int64, C.c_int32, F64P, I32P, I32P, F64P]
+    L.desc_test_irls_pd_stage.argtypes = [C.c_void_p, C.c_int32, F64P, F64P, F64P, I32P, C.c_int64, C.c_int64, F64P, F64P, F64P]
+    L.desc_test_irls_pd_solve.argtypes = [C.c_void_p, F64P, C.c_int64, C.c_int64, C.c_int32, F64P, F64P, I32P, F64P, C.c_int32, I32P]
     _lib = L
     return L
 
@@ -1602,3 +1605,47 @@ def hook_project(rij, order=None, only=-1, device=0):
     check(load().desc_test_irls_project(ptr(rij, F64P), ptr(od, I32P), m, int(only), device, ptr(P, F64P), ptr(bad, I32P), ptr(warn, I32P),
                                         ptr(info, F64P)))
     return dict(P=P[:9 * m].reshape(m, 9), bad_row=int(bad[0]), warn=int(warn[0]), info=info[:5].copy())
+
+
+# ---- test hooks into the primal-dual L1 solver (desc_test_irls_pd_*, include/desc_amd.h).  Used by tests/test_gpu_pd_kernels.py and
+# tests/test_gpu_pd_solver.py only.
+PD_STAGES = ("absmax", "init", "gather0", "gather1", "gather2", "pre", "dir", "resid", "resid_trial", "accept")      # DESC_TEST_PD_*
+PD_EDGE = ("y", "Ax", "u", "f1", "f2", "l1", "l2", "w2", "s1", "s2", "sx", "ev1", "ev2", "Adx", "du", "d1", "d2")    # m x 3 each
+PD_NODE = ("x", "Atv", "w1p", "dg", "dx", "Atdv")                                                                    # n x 3 each
+PD_RG = 256                                                                                                          # irls_math.h
+PD_TRACE = ("part", "bad", "s", "trials", "verdict", "sdg", "tau", "resnorm")
+
+
+def hook_pd_stage(dprob: DeviceProblem, stage, state, part, tau=(1, 1, 1), s=(0, 0, 0), ymax=(0, 0, 0), act=(1, 1, 1)):
+    """One kernel of the primal-dual solver on a snapshot.  state: dict of the PD_EDGE (m, 3) and PD_NODE (n, 3) arrays; part: (PD_RG, 6)
+    as the launch finds it.  -> (dict of all arrays after the launch, part (PD_RG * 6,) raw: [PD_RG][K] from its start)."""
+    n, m = dprob.n, dprob.m
+    edge = np.concatenate([_f64(state[k], 3 * m) for k in PD_EDGE])
+    node = np.concatenate([_f64(state[k], 3 * n) for k in PD_NODE])
+    eb, nb, pb = out_buffer(edge.size), out_buffer(node.size), out_buffer(6 * PD_RG)
+    eb[:] = edge; nb[:] = node; pb[:] = _f64(part, 6 * PD_RG)
+    sc = [np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (tau, s, ymax)]
+    act = np.ascontiguousarray(act, dtype=np.int32).reshape(3)
+    check(load().desc_test_irls_pd_stage(dprob.handle, PD_STAGES.index(stage), ptr(sc[0], F64P), ptr(sc[1], F64P), ptr(sc[2], F64P),
+                                         ptr(act, I32P), m, n, ptr(eb, F64P), ptr(nb, F64P), ptr(pb, F64P)))
+    out = {k: eb[3 * m * t:3 * m * (t + 1)].reshape(m, 3).copy() for t, k in enumerate(PD_EDGE)}
+    out.update({k: nb[3 * n * t:3 * n * (t + 1)].reshape(n, 3).copy() for t, k in enumerate(PD_NODE)})
+    return out, pb[:6 * PD_RG].copy()
+
+
+def hook_pd_solve(dprob: DeviceProblem, B, pdmaxiter):
+    """The whole primal-dual solve of B (m, 3) -> dict(x, u, l1, l2, Ax, Atv, steps, ill, stuck, solves, cg_total, cg_unconverged,
+    trace (records, 3, 8): the fields of PD_TRACE per step (record 0: the start) and coordinate)."""
+    n, m = dprob.n, dprob.m
+    B = _f64(B, 3 * m)
+    cap = int(pdmaxiter) + 1
+    x, st, cnt = out_buffer(3 * n), out_buffer(12 * m + 3 * n), out_buffer(6, np.int32)
+    tr, tl = out_buffer(24 * max(cap, 1)), out_buffer(1, np.int32)
+    check(load().desc_test_irls_pd_solve(dprob.handle, ptr(B, F64P), m, n, int(pdmaxiter), ptr(x, F64P), ptr(st, F64P), ptr(cnt, I32P),
+                                         ptr(tr, F64P), max(cap, 0), ptr(tl, I32P)))
+    out = dict(x=x[:3 * n].reshape(n, 3).copy(), Atv=st[12 * m:12 * m + 3 * n].reshape(n, 3).copy())
+    for t, k in enumerate(("u", "l1", "l2", "Ax")):
+        out[k] = st[3 * m * t:3 * m * (t + 1)].reshape(m, 3).copy()
+    out.update(zip(("steps", "ill", "stuck", "solves", "cg_total", "cg_unconverged"), (int(v) for v in cnt[:6])))
+    out["trace"] = tr[:24 * int(tl[0])].reshape(-1, 3, 8).copy()
+    return out

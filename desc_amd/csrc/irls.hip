@@ -123,7 +123,8 @@ __global__ __launch_bounds__(256) void k_pd_resid(int64_t m, int n, Pd3 a, const
     }
     block_reduce<3, 0>(acc, part + 3 * blockIdx.x);
 }
-// the accepted step (:340-344) for the coordinates with act set, then fu1'*lamu1 and fu2'*lamu2 of the new point as partials [RG][6]
+// the accepted step (:340-344) for the coordinates with act set (row 0 of x and Atv, the grounded node, is not written), then fu1'*lamu1
+// and fu2'*lamu2 of the new point as partials [RG][6]
 __global__ __launch_bounds__(256) void k_pd_accept(int64_t m, int n, Pd3 a, const double* y, double* Ax, double* u, double* l1, double* l2,
                                                    double* f1, double* f2, double* x, double* Atv, const double* dx, const double* Adx,
                                                    const double* du, const double* d1, const double* d2, const double* Atdv, double* part) {
@@ -134,9 +135,11 @@ __global__ __launch_bounds__(256) void k_pd_accept(int64_t m, int n, Pd3 a, cons
             if (a.act[c]) pd_accept_at(a, c, k, y, Ax, u, l1, l2, f1, f2, Adx, du, d1, d2);
             acc[c] += f1[k] * l1[k]; acc[3 + c] += f2[k] * l2[k];
         }
-    for (int v = blockIdx.x * 256 + threadIdx.x; v < n; v += gridDim.x * 256)
+    for (int v = blockIdx.x * 256 + threadIdx.x; v < n; v += gridDim.x * 256) {
+        if (v == 0) continue;                                                 // the grounded node: x and Atv stay 0
         for (int c = 0; c < 3; ++c)
             if (a.act[c]) pd_accept_node(a, c, v, x, Atv, dx, Atdv);
+    }
     block_reduce<6, 0>(acc, part + 6 * blockIdx.x);
 }
 
@@ -179,14 +182,21 @@ struct PdState {
     bool verbose = false;
 };
 
+// the state arrays in their fixed order (pd_alloc; the snapshot of desc_test_irls_pd_stage): PD_EDGE_ARRAYS of m x 3, PD_NODE_ARRAYS of n x 3
+constexpr int PD_EDGE_ARRAYS = 17, PD_NODE_ARRAYS = 6;
+struct PdArrays { double** em[PD_EDGE_ARRAYS]; double** nm[PD_NODE_ARRAYS]; };
+PdArrays pd_arrays(PdState& S) {
+    return {{&S.y, &S.Ax, &S.u, &S.f1, &S.f2, &S.l1, &S.l2, &S.w2, &S.s1, &S.s2, &S.sx, &S.ev1, &S.ev2, &S.Adx, &S.du, &S.d1, &S.d2},
+            {&S.x, &S.Atv, &S.w1p, &S.dg, &S.dx, &S.Atdv}};
+}
+
 int pd_alloc(PdState& S, LaaSolver& L) {
     int rc = DESC_OK;
     S.L = &L; S.n = L.n; S.m = L.m;
     const int64_t m3 = 3 * S.m, n3 = 3 * S.n;
-    double** em[] = {&S.y, &S.Ax, &S.u, &S.f1, &S.f2, &S.l1, &S.l2, &S.w2, &S.s1, &S.s2, &S.sx, &S.ev1, &S.ev2, &S.Adx, &S.du, &S.d1, &S.d2};
-    double** nm[] = {&S.x, &S.Atv, &S.w1p, &S.dg, &S.dx, &S.Atdv};
-    for (auto* a : em) if ((rc = L.alloc(a, m3))) return rc;
-    for (auto* a : nm) if ((rc = L.alloc(a, n3))) return rc;
+    const PdArrays arr = pd_arrays(S);
+    for (auto* a : arr.em) if ((rc = L.alloc(a, m3))) return rc;
+    for (auto* a : arr.nm) if ((rc = L.alloc(a, n3))) return rc;
     if ((rc = L.alloc(&S.part, 6 * RG))) return rc;
     S.hpart.resize(6 * RG);
     S.egrid = L.egrid; S.ngrid = L.ngrid; S.rgrid = L.rgrid;
@@ -213,8 +223,14 @@ int pd_pcg(PdState& S, const int act[3], int bad[3]) {
     return laa_pcg<true, true>(L, S.sx, S.w1p, S.dg, S.dx, act, PD_PROBE, S.cg, bad);
 }
 
+// What pd_solve decided, for desc_test_irls_pd_solve: record 0 is the start, record k step k; a record holds PD_TRACE_FIELDS doubles per
+// coordinate: takes part, the CG's bad, the first trial step s, the number of trials, the verdict (0 none, PD_TRIAL_ACCEPT, PD_TRIAL_STUCK),
+// then sdg, tau, resnorm as they stand after the step.  Filled from values the loop has on the host anyway.
+constexpr int PD_TRACE_FIELDS = 8;
+struct PdTrace { double* rec = nullptr; int cap = 0, len = 0; };
+
 // W(2:end, 2:4) = [l1decode_pd(0, A, [], B(:,c), eps, pdmaxiter, AtA) for c = 1..3] (BoxMedianSO3Graph.m:166-168) into S.x
-int pd_solve(PdState& S, const double* d_B, int pdmaxiter) {
+int pd_solve(PdState& S, const double* d_B, int pdmaxiter, PdTrace* tr = nullptr) {
     int rc = DESC_OK;
     const LaaSolver& L = *S.L;
     const desc_device_problem* dp = L.dp;
@@ -260,9 +276,28 @@ int pd_solve(PdState& S, const double* d_B, int pdmaxiter) {
     }
     if ((rc = scalars(run))) return rc;
     int pditer = 0;
+    // the trace record of step `pditer` (nullptr: none kept), and its closing fields
+    auto record = [&]() -> double* {
+        if (!tr || pditer >= tr->cap) return nullptr;
+        double* r = tr->rec + (size_t)3 * PD_TRACE_FIELDS * pditer;
+        std::fill(r, r + 3 * PD_TRACE_FIELDS, 0.0);
+        return r;
+    };
+    auto close_record = [&](double* r) {
+        if (!r) return;
+        for (int c = 0; c < 3; ++c) { r[PD_TRACE_FIELDS * c + 5] = sdg[c]; r[PD_TRACE_FIELDS * c + 6] = tau[c]; r[PD_TRACE_FIELDS * c + 7] = resnorm[c]; }
+        tr->len = pditer + 1;
+    };
+    {
+        double* r = record();
+        if (r) for (int c = 0; c < 3; ++c) r[PD_TRACE_FIELDS * c] = 1.0;
+        close_record(r);
+    }
     for (int c = 0; c < 3; ++c) run[c] = pd_goes_on(sdg[c], pditer, pdmaxiter);                // :287
     while (run[0] || run[1] || run[2]) {
         ++pditer;
+        double* const rec = record();
+        if (rec) for (int c = 0; c < 3; ++c) rec[PD_TRACE_FIELDS * c] = run[c];
         for (int c = 0; c < 3; ++c) { a.act[c] = run[c]; a.tau[c] = tau[c]; }
         // ---- Newton system (:296-312)
         hipLaunchKernelGGL(k_pd_pre, dim3(S.egrid), dim3(256), 0, 0, m, a, S.f1, S.f2, S.l1, S.l2, S.w2, S.s1, S.s2, S.sx, S.ev1, S.ev2);
@@ -278,8 +313,9 @@ int pd_solve(PdState& S, const double* d_B, int pdmaxiter) {
             if (bad[c]) {                                                                    // :308-312
                 if (S.verbose) printf("Matrix ill-conditioned.  Returning previous iterate.  (See Section 4 of notes for more information.)\n");
                 ++S.ill; run[c] = 0; a.act[c] = 0;
+                if (rec) rec[PD_TRACE_FIELDS * c + 1] = 1.0;
             }
-        if (!(run[0] || run[1] || run[2])) break;
+        if (!(run[0] || run[1] || run[2])) { close_record(rec); break; }
         for (int c = 0; c < 3; ++c) if (run[c]) ++S.steps;
         // ---- direction and step length (:315-330)
         hipLaunchKernelGGL(k_pd_dir, dim3(RG), dim3(256), 0, 0, dp->d_ii, dp->d_jj, m, a, S.dx, S.f1, S.f2, S.l1, S.l2, S.w2, S.s1, S.s2, S.Adx, S.du,
@@ -289,7 +325,7 @@ int pd_solve(PdState& S, const double* d_B, int pdmaxiter) {
         hipLaunchKernelGGL(k_pd_gather<0>, dim3(S.rgrid), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj_eid, L.d_sgn, S.ev1, nullptr, a, S.Atdv, n);
         double s[3] = {0, 0, 0};
         for (int c = 0; c < 3; ++c)
-            if (run[c]) s[c] = pd_step_length(mins[c], mins[3 + c]);
+            if (run[c]) { s[c] = pd_step_length(mins[c], mins[3 + c]); if (rec) rec[PD_TRACE_FIELDS * c + 2] = s[c]; }
         // ---- backtracking (:332-346): one trial of every searching coordinate per launch
         int search[3], backiter[3] = {0, 0, 0}, accept[3] = {0, 0, 0};
         double s_acc[3] = {0, 0, 0};
@@ -309,6 +345,7 @@ int pd_solve(PdState& S, const double* d_B, int pdmaxiter) {
                     if (S.verbose) printf("Stuck backtracking, returning last iterate.  (See Section 4 of notes for more information.)\n");
                     ++S.stuck; search[c] = 0; run[c] = 0;
                 } else if (verdict == PD_TRIAL_ACCEPT) { search[c] = 0; accept[c] = 1; s_acc[c] = s_tried; }
+                if (rec) { rec[PD_TRACE_FIELDS * c + 3] = backiter[c]; rec[PD_TRACE_FIELDS * c + 4] = verdict; }
             }
         }
         // ---- next iterate (:348-356)
@@ -319,6 +356,7 @@ int pd_solve(PdState& S, const double* d_B, int pdmaxiter) {
         if ((rc = scalars(accept))) return rc;
         for (int c = 0; c < 3; ++c)
             if (accept[c]) run[c] = pd_goes_on(sdg[c], pditer, pdmaxiter);
+        close_record(rec);
     }
     DESC_HIP(hipGetLastError());
     return DESC_OK;
@@ -603,5 +641,90 @@ extern "C" int desc_test_irls_weights(const desc_device_problem* dp, const doubl
     if ((rc = hook_upload(A, x, 3 * dp->n, &d_x)) || (rc = hook_upload(A, B, 3 * m, &d_B)) || (rc = A.alloc(&d_w, (size_t)m))) return rc;
     if (m) hipLaunchKernelGGL(k_irls_weights, dim3(grid_for(m, 2048)), dim3(256), 0, 0, d_x, d_B, dp->d_ii, dp->d_jj, m, mode, sigma, d_w);
     return hook_download(w, d_w, m);
+    });
+}
+
+// ---- test hooks into the primal-dual solver (tests/test_gpu_pd_kernels.py, tests/test_gpu_pd_solver.py)
+// One kernel of pd_solve on a snapshot of the whole state, launched as pd_solve (pd_pcg for gather2) launches it.  edge: the
+// PD_EDGE_ARRAYS m x 3 arrays, node: the PD_NODE_ARRAYS n x 3 arrays (the order of pd_arrays), part: the 6 * RG partials; all three are
+// uploaded, and come back whole after the launch.
+extern "C" int desc_test_irls_pd_stage(const desc_device_problem* dp, int32_t stage, const double* tau, const double* s, const double* ymax,
+                                       const int32_t* act, int64_t m, int64_t n, double* edge, double* node, double* part) {
+    return no_throw("desc_test_irls_pd_stage", [&]() -> int {
+    if (!dp || !tau || !s || !ymax || !act || !edge || !node || !part) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (m != dp->m || n != dp->n) return fail(DESC_ERR_INVALID, "m or n does not match the device problem");
+    if (stage < 0 || stage >= DESC_TEST_PD_STAGES) return fail(DESC_ERR_INVALID, "unknown stage");
+    DESC_HIP(hipSetDevice(dp->device));
+    LaaSolver L; PdState S; int rc;
+    if ((rc = hook_solver(dp, L)) || (rc = pd_alloc(S, L))) return rc;
+    const PdArrays arr = pd_arrays(S);
+    for (int k = 0; k < PD_EDGE_ARRAYS; ++k) DESC_HIP(hipMemcpy(*arr.em[k], edge + (size_t)k * 3 * m, sizeof(double) * 3 * m, hipMemcpyHostToDevice));
+    for (int k = 0; k < PD_NODE_ARRAYS; ++k) DESC_HIP(hipMemcpy(*arr.nm[k], node + (size_t)k * 3 * n, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
+    DESC_HIP(hipMemcpy(S.part, part, sizeof(double) * 6 * RG, hipMemcpyHostToDevice));
+    Pd3 a{};
+    for (int c = 0; c < 3; ++c) { a.tau[c] = tau[c]; a.s[c] = s[c]; a.ymax[c] = ymax[c]; a.act[c] = act[c] != 0; }
+    const int ni = (int)n;
+    switch (stage) {
+    case DESC_TEST_PD_ABSMAX: hipLaunchKernelGGL(k_pd_absmax, dim3(RG), dim3(256), 0, 0, S.y, m, S.part); break;
+    case DESC_TEST_PD_INIT:
+        hipLaunchKernelGGL(k_pd_init, dim3(S.egrid), dim3(256), 0, 0, S.y, m, a, S.Ax, S.u, S.f1, S.f2, S.l1, S.l2, S.ev1); break;
+    case DESC_TEST_PD_GATHER0:
+        hipLaunchKernelGGL(k_pd_gather<0>, dim3(S.rgrid), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj_eid, L.d_sgn, S.ev1, nullptr, a, S.Atv, ni); break;
+    case DESC_TEST_PD_GATHER1: {
+        Pd3 g = a;
+        for (int c = 0; c < 3; ++c) g.tau[c] = pd_gather_coef(a.act[c], a.tau[c]);
+        hipLaunchKernelGGL(k_pd_gather<1>, dim3(S.rgrid), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj_eid, L.d_sgn, S.ev1, S.ev2, g, S.w1p, ni);
+        break;
+    }
+    case DESC_TEST_PD_GATHER2: {
+        Pd3 none{}; none.act[0] = none.act[1] = none.act[2] = 1;
+        hipLaunchKernelGGL(k_pd_gather<2>, dim3(S.rgrid), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj_eid, L.d_sgn, S.sx, nullptr, none, S.dg, ni);
+        break;
+    }
+    case DESC_TEST_PD_PRE:
+        hipLaunchKernelGGL(k_pd_pre, dim3(S.egrid), dim3(256), 0, 0, m, a, S.f1, S.f2, S.l1, S.l2, S.w2, S.s1, S.s2, S.sx, S.ev1, S.ev2); break;
+    case DESC_TEST_PD_DIR:
+        hipLaunchKernelGGL(k_pd_dir, dim3(RG), dim3(256), 0, 0, dp->d_ii, dp->d_jj, m, a, S.dx, S.f1, S.f2, S.l1, S.l2, S.w2, S.s1, S.s2, S.Adx, S.du,
+                           S.d1, S.d2, S.ev1, S.part);
+        break;
+    case DESC_TEST_PD_RESID:
+        hipLaunchKernelGGL(k_pd_resid<false>, dim3(RG), dim3(256), 0, 0, m, ni, a, S.y, S.Ax, S.u, S.l1, S.l2, S.Atv, S.Adx, S.du, S.d1, S.d2,
+                           S.Atdv, S.part);
+        break;
+    case DESC_TEST_PD_RESID_TRIAL:
+        hipLaunchKernelGGL(k_pd_resid<true>, dim3(RG), dim3(256), 0, 0, m, ni, a, S.y, S.Ax, S.u, S.l1, S.l2, S.Atv, S.Adx, S.du, S.d1, S.d2,
+                           S.Atdv, S.part);
+        break;
+    default:
+        hipLaunchKernelGGL(k_pd_accept, dim3(RG), dim3(256), 0, 0, m, ni, a, S.y, S.Ax, S.u, S.l1, S.l2, S.f1, S.f2, S.x, S.Atv, S.dx, S.Adx, S.du,
+                           S.d1, S.d2, S.Atdv, S.part);
+    }
+    for (int k = 0; k < PD_EDGE_ARRAYS; ++k) if ((rc = hook_download(edge + (size_t)k * 3 * m, *arr.em[k], 3 * m))) return rc;
+    for (int k = 0; k < PD_NODE_ARRAYS; ++k) if ((rc = hook_download(node + (size_t)k * 3 * n, *arr.nm[k], 3 * n))) return rc;
+    return hook_download(part, S.part, 6 * RG);
+    });
+}
+
+// pd_alloc + pd_solve on B (m x 3) from x = 0.  Out: x (n x 3); state: u, lamu1, lamu2, Ax (m x 3 each) then Atv (n x 3); counters[6]:
+// steps, ill, stuck, solves, CG steps, CG solves stopped at the cap; trace: trace_cap records of 3 x 8 doubles (PdTrace), *trace_len
+// the number written (the start and every step begun).
+extern "C" int desc_test_irls_pd_solve(const desc_device_problem* dp, const double* B, int64_t m, int64_t n, int32_t pdmaxiter, double* x,
+                                       double* state, int32_t* counters, double* trace, int32_t trace_cap, int32_t* trace_len) {
+    return no_throw("desc_test_irls_pd_solve", [&]() -> int {
+    if (!dp || !B || !x || !state || !counters || !trace || !trace_len) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (m != dp->m || n != dp->n) return fail(DESC_ERR_INVALID, "m or n does not match the device problem");
+    if (pdmaxiter < 0) return fail(DESC_ERR_INVALID, "pdmaxiter must not be negative");
+    if (trace_cap < 0) return fail(DESC_ERR_INVALID, "negative trace capacity");
+    DESC_HIP(hipSetDevice(dp->device));
+    LaaSolver L; PdState S; int rc; double* d_B;
+    if ((rc = hook_solver(dp, L)) || (rc = pd_alloc(S, L)) || (rc = hook_upload(L, B, 3 * m, &d_B))) return rc;
+    PdTrace tr; tr.rec = trace; tr.cap = trace_cap;
+    if ((rc = pd_solve(S, d_B, pdmaxiter, &tr))) return rc;
+    *trace_len = tr.len;
+    counters[0] = S.steps; counters[1] = S.ill; counters[2] = S.stuck; counters[3] = S.solves; counters[4] = S.cg.total; counters[5] = S.cg.unconverged;
+    double* const em[4] = {S.u, S.l1, S.l2, S.Ax};
+    for (int k = 0; k < 4; ++k) if ((rc = hook_download(state + (size_t)k * 3 * m, em[k], 3 * m))) return rc;
+    if ((rc = hook_download(state + (size_t)12 * m, S.Atv, 3 * n))) return rc;
+    return hook_download(x, S.x, 3 * n);
     });
 }

@@ -65,6 +65,8 @@ int hook_upload(DevArena& A, const T* host, int64_t count, T** out) {
     if (count) DESC_HIP(hipMemcpy(*out, host, sizeof(T) * count, hipMemcpyHostToDevice));
     return DESC_OK;
 }
+// the solver state of laa_setup on dp with identity R_init, for the hooks: grids, incidence signs, work arrays (laa.hip)
+int hook_solver(const desc_device_problem* dp, LaaSolver& L);
 template <class T>
 int hook_download(T* host, const T* dev, int64_t count) {
     DESC_HIP(hipDeviceSynchronize());

@@ -357,7 +357,7 @@ int laa_finish(LaaSolver& L, int iterations, double* R_out) {
 // and the grid rule of the product path (laa_setup's egrid / ngrid / rgrid / sgrid).  Nothing in the library calls them.
 using namespace desc;
 
-namespace {
+namespace desc {
 
 // the solver state of laa_setup on dp (identity R_init): grids, incidence signs, work arrays
 int hook_solver(const desc_device_problem* dp, LaaSolver& L) {
@@ -367,7 +367,7 @@ int hook_solver(const desc_device_problem* dp, LaaSolver& L) {
     return laa_setup(dp, eye.data(), L);
 }
 
-}  // namespace
+}  // namespace desc
 
 extern "C" int desc_test_laa_r2q(const double* R, int64_t count, int32_t transpose, int32_t edge_grid, int32_t device, double* Q) {
     return no_throw("desc_test_laa_r2q", [&]() -> int {

@@ -930,6 +930,27 @@ int desc_test_laa_quantile(const double* x, int64_t m, double p, int64_t cap, in
 int desc_test_irls_project(const double* rij, const int32_t* order, int64_t m, int64_t only, int32_t device, double* P,
                            int32_t* bad_row, int32_t* warn, double* info);
 
+/* Test hooks (tests/test_gpu_pd_kernels.py, tests/test_gpu_pd_solver.py): the L1 stage's primal-dual solver (l1decode_pd, three
+ * coordinates batched; irls.hip).  A NULL pointer, an m or n that is not the device problem's, an unknown stage or a negative pdmaxiter
+ * returns DESC_ERR_INVALID before any device work.
+ *   pd_stage  one kernel on a snapshot of the solver's whole state, launched as the solver launches it.  tau, s, ymax, act: the three
+ *             coordinates' scalars of the launch (gather1 forms its coefficient -1 / tau, 0 for act = 0, as the solver does; gather2
+ *             ignores them).  edge: 17 arrays of m x 3 in the order y Ax u fu1 fu2 lamu1 lamu2 w2 sig1 sig2 sigx ev1 ev2 Adx du dlamu1
+ *             dlamu2; node: 6 arrays of n x 3 in the order x Atv w1p diag dx Atdv; part: 6 * 256 doubles, the block partials [256][K]
+ *             (K = 3 absmax / resid, 6 dir / accept).  All three are uploaded, and every array comes back after the launch: what the
+ *             kernel does not write returns with the bits it came with.
+ *   pd_solve  the whole solver on B (m x 3) from x = 0.  x (n x 3); state: the final u, lamu1, lamu2, Ax (m x 3 each) and Atv (n x 3),
+ *             12 m + 3 n doubles; counters[6]: steps, ill-conditioned returns, stuck returns, Newton solves, CG steps, CG solves stopped
+ *             at the cap.  trace: trace_cap records of 3 x 8 doubles, record 0 the start, record k step k, per coordinate {takes
+ *             part, the CG broke down, first trial step, trials, verdict (0 none, 1 accepted, 2 stuck), sdg, tau, resnorm after the
+ *             step}; *trace_len: records written. */
+enum { DESC_TEST_PD_ABSMAX = 0, DESC_TEST_PD_INIT, DESC_TEST_PD_GATHER0, DESC_TEST_PD_GATHER1, DESC_TEST_PD_GATHER2, DESC_TEST_PD_PRE,
+       DESC_TEST_PD_DIR, DESC_TEST_PD_RESID, DESC_TEST_PD_RESID_TRIAL, DESC_TEST_PD_ACCEPT, DESC_TEST_PD_STAGES };
+int desc_test_irls_pd_stage(const desc_device_problem* dp, int32_t stage, const double* tau, const double* s, const double* ymax,
+                            const int32_t* act, int64_t m, int64_t n, double* edge, double* node, double* part);
+int desc_test_irls_pd_solve(const desc_device_problem* dp, const double* B, int64_t m, int64_t n, int32_t pdmaxiter, double* x,
+                            double* state, int32_t* counters, double* trace, int32_t trace_cap, int32_t* trace_len);
+
 #ifdef __cplusplus
 }
 #endif

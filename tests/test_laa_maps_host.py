@@ -297,6 +297,70 @@ def test_hooks_refuse_bad_arguments_before_any_device_work(lib):
         L.desc_test_laa_quantile(p, -1, 0.5, 8, 0, p), L.desc_test_laa_quantile(p, 4, 0.5, 0, 0, p), L.desc_test_laa_quantile(None, 4, 0.5, 8, 0, p),
         L.desc_test_irls_project(None, None, 1, -1, 0, p, pi, pi, p), L.desc_test_irls_project(p, None, -1, -1, 0, p, pi, pi, p),
         L.desc_test_irls_project(p, None, 1, 1, 0, p, pi, pi, p),
+        L.desc_test_irls_pd_stage(None, 0, p, p, p, pi, 1, 2, p, p, p), L.desc_test_irls_pd_solve(None, p, 1, 2, 2, p, p, pi, p, 3, pi),
     ]
     assert all(rc == lib.ERR_INVALID for rc in calls), calls
     assert L.desc_last_error()
+
+
+PD_CHILD = r"""
+import json, sys
+sys.path.insert(0, sys.argv[1])
+import numpy as np
+from desc_amd import _lib as lib
+from tests import laa_maps_cases as K
+L = lib.load()
+assert hasattr(L, "hipmock_launch_count"), "must run against the mock build"
+n, ii, jj = K.path_graph(4)
+dp = lib.DeviceProblem(lib.ProblemArrays(n, ii, jj, K.identity_rij(len(ii))))
+m = dp.m
+d = np.zeros(17 * 3 * m + 6 * 256); p = lib.ptr(d, lib.F64P)
+i32 = np.zeros(8, dtype=np.int32); pi = lib.ptr(i32, lib.I32P)
+h = dp.handle
+stage = lambda *a: L.desc_test_irls_pd_stage(*a)
+solve = lambda *a: L.desc_test_irls_pd_solve(*a)
+c0 = L.hipmock_launch_count()
+out = dict(
+    stage_null=[stage(h, 0, *[None if k == t else (pi if k == 3 else p) for k in range(4)], m, n, p, p, p) for t in range(4)] +
+               [stage(h, 0, p, p, p, pi, m, n, *[None if k == t else p for k in range(3)]) for t in range(3)],
+    stage_size=[stage(h, 0, p, p, p, pi, m + 1, n, p, p, p), stage(h, 0, p, p, p, pi, m, n - 1, p, p, p), stage(h, 0, p, p, p, pi, -1, n, p, p, p)],
+    stage_id=[stage(h, -1, p, p, p, pi, m, n, p, p, p), stage(h, len(lib.PD_STAGES), p, p, p, pi, m, n, p, p, p)],
+    solve_null=[solve(h, None, m, n, 2, p, p, pi, p, 3, pi), solve(h, p, m, n, 2, None, p, pi, p, 3, pi), solve(h, p, m, n, 2, p, None, pi, p, 3, pi),
+                solve(h, p, m, n, 2, p, p, None, p, 3, pi), solve(h, p, m, n, 2, p, p, pi, None, 3, pi), solve(h, p, m, n, 2, p, p, pi, p, 3, None)],
+    solve_size=[solve(h, p, m - 1, n, 2, p, p, pi, p, 3, pi), solve(h, p, m, n + 1, 2, p, p, pi, p, 3, pi)],
+    solve_iter=[solve(h, p, m, n, -1, p, p, pi, p, 3, pi)],
+)
+out["refused_launches"] = L.hipmock_launch_count() - c0
+out["invalid"] = lib.ERR_INVALID
+before = L.hipmock_launch_count()
+# the wrappers end to end (no kernel runs: device blocks read back as zeros): sizes, guard words, the stage names
+st = {k: np.zeros((m, 3)) for k in lib.PD_EDGE}; st.update({k: np.zeros((n, 3)) for k in lib.PD_NODE})
+for s in lib.PD_STAGES:
+    got, part = lib.hook_pd_stage(dp, s, st, np.zeros((lib.PD_RG, 6)))
+    assert set(got) == set(lib.PD_EDGE) | set(lib.PD_NODE) and part.shape == (6 * lib.PD_RG,)
+r = lib.hook_pd_solve(dp, np.zeros((m, 3)), 2)
+assert r["x"].shape == (n, 3) and r["trace"].shape[1:] == (3, 8) and r["steps"] == 0
+out["ok_launches"] = L.hipmock_launch_count() - before
+print("RESULT " + json.dumps(out))
+"""
+
+
+def test_pd_hooks_refuse_bad_arguments_on_the_mock_runtime():
+    """desc_test_irls_pd_stage / desc_test_irls_pd_solve on a device problem of the mock HIP runtime (tests/hipmock: no GPU): a NULL
+    pointer, an m or n that is not the problem's, an unknown stage and pdmaxiter < 0 are refused with DESC_ERR_INVALID before anything
+    is launched; the host build still links, and the Python wrappers run end to end."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tests", "hipmock"))
+    import build_host
+    so = build_host.build(root, "none")
+    env = dict(os.environ, DESC_AMD_LIB=so, OPENBLAS_NUM_THREADS="1")
+    r = subprocess.run([sys.executable, "-c", PD_CHILD, root], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][len("RESULT "):])
+    for key in ("stage_null", "stage_size", "stage_id", "solve_null", "solve_size", "solve_iter"):
+        assert out[key] and all(rc == out["invalid"] for rc in out[key]), (key, out[key])
+    assert out["refused_launches"] == 0 and out["ok_launches"] > 0
