@@ -36,6 +36,7 @@ EXPORTS = [
     "desc_pgd_ext_begin", "desc_pgd_ext_grad", "desc_pgd_ext_apply", "desc_pgd_ext_laps",
     "desc_pgd_batch_create", "desc_pgd_batch_sizes", "desc_pgd_batch_get_structure", "desc_pgd_batch_get_s0", "desc_pgd_batch_run",
     "desc_pgd_batch_destroy", "desc_pgd_batch_concat",
+    "desc_pgd_batch_create_where", "desc_pgd_batch_built_where", "desc_pgd_batch_max_codeg", "desc_pgd_batch_build_laps", "desc_test_batch_plan",
     "desc_gcw_batch_max_n", "desc_gcw_batch_create", "desc_gcw_batch_sizes", "desc_gcw_batch_csr", "desc_gcw_batch_run", "desc_gcw_batch_destroy",
     "desc_cemp_batch_max_degree", "desc_cemp_batch_create", "desc_cemp_batch_sizes", "desc_cemp_batch_get_samples", "desc_cemp_batch_run",
     "desc_cemp_batch_destroy", "desc_mst_batch_max_n", "desc_mst_batch_check", "desc_mst_batch_run",
@@ -307,6 +308,13 @@ def load():
     L.desc_lp_sij_run.argtypes = [C.POINTER(Problem), C.POINTER(LpParams), C.c_int32, F64P, F64P, I32P, C.POINTER(LpInfo)]
     L.desc_lp_sij_run_dev.argtypes = [C.c_void_p, C.POINTER(LpParams), F64P, F64P, I32P, C.POINTER(LpInfo)]
     L.desc_pgd_batch_create.argtypes = [C.POINTER(Problem), C.c_int32, C.POINTER(Params), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p)]
+    L.desc_pgd_batch_create_where.argtypes = [C.POINTER(Problem), C.c_int32, C.POINTER(Params), C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_void_p)]
+    L.desc_pgd_batch_built_where.argtypes = [C.c_void_p]
+    L.desc_pgd_batch_built_where.restype = C.c_int32
+    L.desc_pgd_batch_max_codeg.argtypes = []
+    L.desc_pgd_batch_max_codeg.restype = C.c_int32
+    L.desc_pgd_batch_build_laps.argtypes = [C.c_void_p, F64P]
+    L.desc_test_batch_plan.argtypes = [I32P, C.c_int32, C.c_int32, I64P]
     L.desc_pgd_batch_sizes.argtypes = [C.c_void_p, I32P, I64P, I64P, I32P]
     L.desc_pgd_batch_get_structure.argtypes = [C.c_void_p, C.c_int32, C.POINTER(StructureView)]
     L.desc_pgd_batch_get_s0.argtypes = [C.c_void_p, F64P]
@@ -557,8 +565,10 @@ def _timings(tm):
 
 class _BatchHandle:
     """Base of the owners of a batched handle desc_<_kind>_batch*.  A subclass's constructor calls _open with the arguments of its
-    create call that stand between ``count`` and ``out``; Batch, whose offsets are others, also overrides _read_sizes."""
+    create call that stand between ``count`` and ``out``; Batch, whose offsets are others, also overrides _read_sizes, and names
+    another create call."""
     _kind = None
+    _create = "create"
     handle = None
 
     def _export(self, name):
@@ -568,7 +578,7 @@ class _BatchHandle:
         self.probs = list(probs)                     # keeps the NumPy buffers alive
         self.count = B = len(self.probs)
         h = C.c_void_p()
-        check(self._export("create")(_problem_array(self.probs), B, *create_args, C.byref(h)))
+        check(self._export(self._create)(_problem_array(self.probs), B, *create_args, C.byref(h)))
         self.handle = h
         self._read_sizes(B)
 
@@ -592,13 +602,24 @@ class _BatchHandle:
 
 class Batch(_BatchHandle):
     """Owner of a desc_pgd_batch*: B independent problems behind one another in one set of device arrays (desc_pgd_batch_*).
-    ``probs`` is a sequence of ProblemArrays; ``seeds`` an optional sequence of per-problem sampling seeds."""
+    ``probs`` is a sequence of ProblemArrays; ``seeds`` an optional sequence of per-problem sampling seeds; ``where`` the builder
+    of the cycle structure (BUILD_HOST, or BUILD_DEVICE: desc_pgd_batch_create_where).  ``built_where`` is the builder that made the
+    handle: BUILD_HOST also where a batch outside the device builder's staging caps fell back to the host."""
 
     _kind = "pgd"
+    _create = "create_where"
+    BUILD_LAPS = ("codeg", "plan", "compact", "sample", "mirror")
 
-    def __init__(self, probs, params: Params, seeds=None):
+    def __init__(self, probs, params: Params, seeds=None, where=BUILD_HOST):
         probs = list(probs)
-        self._open(probs, C.byref(params), _seeds_array(seeds, len(probs)))
+        self._open(probs, C.byref(params), _seeds_array(seeds, len(probs)), int(where))
+        self.built_where = int(self._export("built_where")(self.handle))
+
+    def build_laps(self):
+        """Device time (ms) of the device builder's five launches, by name; zeros for a host-built handle."""
+        out = np.zeros(len(self.BUILD_LAPS))
+        check(load().desc_pgd_batch_build_laps(self.handle, ptr(out, F64P)))
+        return dict(zip(self.BUILD_LAPS, out.tolist()))
 
     def _read_sizes(self, B):
         eo, co, ns = np.zeros(B + 1, dtype=np.int64), np.zeros(B + 1, dtype=np.int64), np.zeros(max(B, 1), dtype=np.int32)
@@ -648,6 +669,19 @@ class Batch(_BatchHandle):
                 o["adam_m"], o["adam_v"] = adam[0][c0:c1], adam[1][c0:c1]
             outs.append(o)
         return outs, _timings(r)
+
+
+def pgd_batch_max_codeg():
+    """desc_pgd_batch_max_codeg: the largest codegree the batched device structure builder stages."""
+    return int(load().desc_pgd_batch_max_codeg())
+
+
+def batch_plan(hist, n_sample_min=30):
+    """desc_test_batch_plan: the device builder's plan rule on a histogram of codegrees (hist[c], c = 0 .. n), on the host."""
+    hist = np.ascontiguousarray(hist, dtype=np.int32)
+    out = np.zeros(5, dtype=np.int64)
+    check(load().desc_test_batch_plan(ptr(hist, I32P), hist.shape[0] - 1, int(n_sample_min), ptr(out, I64P)))
+    return dict(zip(("m_pos", "max_codeg", "n_sample", "m_cycle", "max_cnt"), (int(x) for x in out)))
 
 
 def gcw_batch_max_n():

@@ -309,6 +309,16 @@ def _batch_handle(cls, *args):
         batch.destroy()
 
 
+_BUILD_WHERE = {"host": _lib.BUILD_HOST, "device": _lib.BUILD_DEVICE}
+
+
+def _check_build(build):
+    """``build`` of the batched DESC calls -> BUILD_HOST / BUILD_DEVICE."""
+    if not isinstance(build, str) or build not in _BUILD_WHERE:
+        raise ValueError(f"build must be 'host' or 'device', not {build!r}")
+    return _BUILD_WHERE[build]
+
+
 def _check_seeds(seeds, B):
     """``seeds`` as a list of B ints, or None."""
     if seeds is None:
@@ -319,21 +329,25 @@ def _check_seeds(seeds, B):
     return seeds
 
 
-def DESC_PGD_batch(problems, params, seeds=None, return_info=False):
+def DESC_PGD_batch(problems, params, seeds=None, return_info=False, build="host"):
     """DESC_PGD on B independent problems in one GPU pass (desc_pgd_batch_*; the reference has no such call).
 
     ``problems`` is a sequence of ``(Ind, RijMat)`` pairs or of model objects with ``.Ind`` / ``.RijMat``; ``params`` as for DESC_PGD,
     one for the whole batch; ``seeds`` an optional sequence of per-problem sampling seeds (default: ``params.seed`` for every problem).
     Problem b gets what ``DESC_PGD(Ind_b, RijMat_b, params)`` returns with the same seed and the host structure builder: its own
     n_sample, traces, patience rule and stop iteration; its result does not depend, in any bit, on the batch around it.
+    ``build``: ``"host"`` builds the cycle structures per problem on host threads; ``"device"`` builds the same index arrays, element
+    for element, in five launches for the whole batch (desc_pgd_batch_create_where) -- every result bit is the same.  A batch outside
+    the device builder's staging caps is built on the host without failing; ``built_where`` says which builder ran.
 
     Returns a list of S_vec arrays (caller's edge order).  With ``return_info`` a list of dicts: ``S_vec``, ``iters_run``, ``obj_vals``,
-    ``average_change``, ``n_sample``, ``w`` (cycle order of the problem sorted by (i, j)), ``t_end`` and the call's ``timings``; with a
-    HybridGradient (Adam) also ``m_t`` / ``v_t``.  The plugin object is shared by the batch and is NOT updated: its counter ``t`` is
+    ``average_change``, ``n_sample``, ``w`` (cycle order of the problem sorted by (i, j)), ``t_end``, ``built_where`` (``"host"`` or
+    ``"device"``) and the call's ``timings``; with a HybridGradient (Adam) also ``m_t`` / ``v_t``.  The plugin object is shared by the batch and is NOT updated: its counter ``t`` is
     read as the starting counter of every problem, the moments start at zero, and each problem's state comes back in its dict.
 
     Refused (ValueError): a Gradient object of the caller's own (external GetStep), ``make_plots``, a problem whose n_sample exceeds 64
-    (solve it with DESC_PGD)."""
+    (solve it with DESC_PGD), a ``build`` other than ``"host"`` / ``"device"``."""
+    where = _check_build(build)
     _check_sequence(problems)
     G = _get(params, "Gradient")
     if G is not None and is_external(G):
@@ -348,12 +362,15 @@ def DESC_PGD_batch(problems, params, seeds=None, return_info=False):
     if B == 0:
         return []
     probs, perms = _marshal_problems(problems)
-    with _batch_handle(_lib.Batch, probs, p, seeds) as batch:
+    with _batch_handle(_lib.Batch, probs, p, seeds, where) as batch:
+        built_where = "device" if batch.built_where == _lib.BUILD_DEVICE else "host"
         hybrid = isinstance(G, HybridGradient) and G.strategy == 0
         adam = (np.zeros(max(batch.m_cycle, 1)), np.zeros(max(batch.m_cycle, 1))) if hybrid else None
         if adam is not None:
             adam = (adam[0][:batch.m_cycle], adam[1][:batch.m_cycle])
         outs, timings = batch.run(p, want_w=return_info, adam=adam)
+        if batch.built_where == _lib.BUILD_DEVICE:       # device time of the builder's five launches
+            timings.update({"ms_build_" + name: ms for name, ms in batch.build_laps().items()})
     result = []
     for o, perm in zip(outs, perms):
         S_vec = o["S_vec"]
@@ -364,7 +381,7 @@ def DESC_PGD_batch(problems, params, seeds=None, return_info=False):
             result.append(S_vec)
             continue
         d = dict(S_vec=S_vec, iters_run=o["iters_run"], obj_vals=o["obj"], average_change=o["avg"], n_sample=o["n_sample"], w=o["w"],
-                 t_end=o["t_end"], timings=timings)
+                 t_end=o["t_end"], built_where=built_where, timings=timings)
         if hybrid:
             d["m_t"], d["v_t"] = o["adam_m"], o["adam_v"]
         result.append(d)
@@ -437,12 +454,14 @@ def GCW_batch(problems, S_list, device=0, return_info=False):
     return [(R, dict(info, timings=timings)) for R, info in outs] if return_info else [R for R, _ in outs]
 
 
-def DESC_init_batch(problems, params, seeds=None, return_info=False):
+def DESC_init_batch(problems, params, seeds=None, return_info=False, build="host"):
     """DESC_init (Algorithms/DESC_init.m: DESC_PGD, then GCW) on B independent small problems: DESC_PGD_batch's pass, then the batched
     eigen-solve on the resulting S_vec -- two GPU passes for the whole batch.  Returns a list of (R_est, S_vec); problem b's S_vec is
     bit for bit what DESC_PGD_batch returns for it.  With ``return_info`` a list of (R_est, S_vec, dict(pgd=..., gcw=...)).
+    ``build`` is DESC_PGD_batch's (``dict["pgd"]["built_where"]`` says which builder ran).
     Refused (ValueError, before the device is touched): what DESC_PGD_batch refuses, and a problem of more than
     ``_lib.gcw_batch_max_n()`` nodes (solve it with DESC_init)."""
+    _check_build(build)
     _check_sequence(problems)
     G = _get(params, "Gradient")
     if G is not None and is_external(G):
@@ -453,7 +472,7 @@ def DESC_init_batch(problems, params, seeds=None, return_info=False):
     seeds = _check_seeds(seeds, len(problems))
     probs, perms = _marshal_problems(problems)
     _check_gcw_batch_sizes(probs)
-    pgd = DESC_PGD_batch([_Marshalled(q, perm) for q, perm in zip(probs, perms)], params, seeds=seeds, return_info=True)
+    pgd = DESC_PGD_batch([_Marshalled(q, perm) for q, perm in zip(probs, perms)], params, seeds=seeds, return_info=True, build=build)
     if not probs:
         return []
     # DESC_PGD_batch gave S_vec in the caller's order; the eigen-solve takes the library's
@@ -510,15 +529,17 @@ def DESC_refine_batch(problems, S_list, R_init_list, stop_threshold=1e-3, max_it
     return [(R, dict(info, timings=timings)) for R, info in outs] if return_info else [R for R, _ in outs]
 
 
-def DESC_batch(problems, params, seeds=None, return_info=False):
+def DESC_batch(problems, params, seeds=None, return_info=False, build="host"):
     """DESC (Algorithms/DESC.m:14: DESC_PGD, then GCW, then the reweighted Lie-algebraic refinement) on B independent small problems:
     DESC_init_batch's two passes, then the batched refinement on their S_vec and R_init -- three GPU passes for the whole batch.
     Returns a list of (R_est, R_init, S_vec); S_vec and R_init are bit for bit DESC_init_batch's.  With ``return_info`` a list of
     (R_est, R_init, S_vec, dict(pgd=..., gcw=..., refine=...)).  The batch prints nothing: ``params.verbose`` is ignored.
+    ``build`` is DESC_PGD_batch's.
     Refused (ValueError, before the device is touched): what DESC_init_batch refuses."""
+    _check_build(build)
     _check_sequence(problems)
     probs, perms = _marshal_problems(problems)
-    init = DESC_init_batch([_Marshalled(q, perm) for q, perm in zip(probs, perms)], params, seeds=seeds, return_info=True)
+    init = DESC_init_batch([_Marshalled(q, perm) for q, perm in zip(probs, perms)], params, seeds=seeds, return_info=True, build=build)
     if not init:
         return []
     S = np.concatenate([S_vec if perm is None else S_vec[perm] for (_, S_vec, _), perm in zip(init, perms)])

@@ -5,7 +5,9 @@
 // arrays and every iteration is ONE sweep launch plus one bookkeeping launch for the whole batch.
 //
 // Layout.  The structures are built per problem by the host builder (local ids: bit-exact with a solve of the problem alone) and
-// concatenated with per-problem edge / cycle offsets added (batch_concat).  The sweep is the gather sweep of pgd.hip (k_sweep<G, STEP>):
+// concatenated with per-problem edge / cycle offsets added (batch_concat) -- or, with desc_pgd_batch_create_where(DESC_BUILD_DEVICE),
+// the same arrays, element for element, are made for the whole batch on the device (batch_structure.hip); batch_finish and the run
+// see no difference.  The sweep is the gather sweep of pgd.hip (k_sweep<G, STEP>):
 // a group of G lanes per segment, mirror sums from direct gathers of w_old[ikj] / w_old[jki], tangent projection, plugin step, simplex
 // projection, new S -- the arithmetic comes from pgd_math.h, shared with pgd.hip.
 //
@@ -31,6 +33,7 @@
 
 #include "batch_csr.h"
 #include "batch_device.h"
+#include "batch_structure.h"
 #include "pgd_math.h"
 
 namespace desc {
@@ -266,6 +269,14 @@ struct desc_pgd_batch : desc::BatchDevice {     // device, stream, arena, events
     int64_t *d_edge_off = nullptr, *d_cycle_off = nullptr;
     int32_t* d_running = nullptr;
     double ms_cycle_d = 0;
+    // a handle whose index arrays were made by the device builder (batch_structure.hip): st[b] is filled at the first
+    // desc_pgd_batch_get_structure from the arrays below (blocks of the arena); the plain run never downloads them
+    int32_t built_where = DESC_BUILD_HOST;
+    hvec<desc::BatchPlan> plan;
+    hvec<int64_t> prob_n;
+    int32_t *d_kk = nullptr, *d_codeg = nullptr;
+    bool st_ready = true;
+    double ms_lap[desc::BATCH_BUILD_LAPS] = {0, 0, 0, 0, 0};
     ~desc_pgd_batch() {
         close();                                  // the device first, as ever
         for (desc_structure* s : st) if (s) { structure_free_device(s); delete s; }
@@ -317,9 +328,11 @@ StepArgs batch_step(const desc_pgd_batch* h, const desc_params& p, int t, int rd
     return s;
 }
 
+int batch_finish(const desc_problem* probs, desc_pgd_batch* h, const int32_t* d_kk, const int32_t* d_ii, const int32_t* d_jj);
+
 int batch_create(const desc_problem* probs, int32_t count, const desc_params* p, const uint64_t* seeds, desc_pgd_batch* h) {
     auto t0 = std::chrono::steady_clock::now();
-    h->count = count;
+    h->count = count; h->built_where = DESC_BUILD_HOST; h->st_ready = true;
     const int32_t nmin = p->n_sample_min > 0 ? p->n_sample_min : 30;
     for (int32_t b = 0; b < count; ++b) {
         int rc = validate_problem(&probs[b], true);
@@ -364,25 +377,15 @@ int batch_create(const desc_problem* probs, int32_t count, const desc_params* p,
             std::memcpy(jj.data() + h->edge_off[(size_t)b], probs[b].ind_j, sizeof(int32_t) * (size_t)s->m);
         }
     }
-    // the workgroup table: a problem's segments in runs of BATCH_PASSES x 4 waves x 64/G, counted from its own first segment
-    hvec<BatchWg> wg;
-    hvec<BatchProb> pr((size_t)count);
+    h->plan.resize((size_t)count);                   // what the workgroup table is cut from
     for (int32_t b = 0; b < count; ++b) {
         const desc_structure* s = h->st[(size_t)b];
-        const int G = s->max_cnt <= 16 ? 16 : s->max_cnt <= 32 ? 32 : 64;
-        const int64_t per = (int64_t)BATCH_PASSES * 4 * (64 / G);
-        pr[(size_t)b].wg0 = (int32_t)wg.size(); pr[(size_t)b].m = s->m;
-        for (int64_t l = 0; l < s->m_pos; l += per)
-            wg.push_back(BatchWg{b, (int32_t)(h->seg_off[(size_t)b] + l), (int32_t)std::min<int64_t>(per, s->m_pos - l), G});
-        pr[(size_t)b].nwg = (int32_t)wg.size() - pr[(size_t)b].wg0;
+        BatchPlan& q = h->plan[(size_t)b];
+        q = BatchPlan{};
+        q.m_pos = s->m_pos; q.m_cycle = s->m_cycle; q.n_sample = s->n_sample; q.max_cnt = s->max_cnt;
     }
-    h->nwg = (int32_t)wg.size();
-    h->ms_structure = ms_since(t0);
-
     if ((rc = h->open(p->device, "DESC_PGD_batch"))) return rc;           // nothing above touched the device
-    auto t1 = std::chrono::steady_clock::now();
     int32_t *d_kk = nullptr, *d_ii = nullptr, *d_jj = nullptr;
-    double* d_rij = nullptr;
     if ((rc = h->upload(&h->d_cum, cum.data(), MP + 1))) return rc;
     if ((rc = h->upload(&h->d_pos, pos.data(), MP))) return rc;
     if ((rc = h->upload(&h->d_ejk, ejk.data(), MC))) return rc;
@@ -392,6 +395,32 @@ int batch_create(const desc_problem* probs, int32_t count, const desc_params* p,
     if ((rc = h->upload(&d_kk, kk.data(), MC))) return rc;
     if ((rc = h->upload(&d_ii, ii.data(), M))) return rc;
     if ((rc = h->upload(&d_jj, jj.data(), M))) return rc;
+    DESC_HIP(hipStreamSynchronize(h->stream));         // the index arrays are on the device: the staging vectors go out of scope below
+    h->ms_structure = ms_since(t0);
+    return batch_finish(probs, h, d_kk, d_ii, d_jj);
+}
+
+// Behind either builder, once the index arrays are on the device: the workgroup table, the small tables, the rotations, the state
+// buffers, and S0_long of the whole batch in one launch.
+int batch_finish(const desc_problem* probs, desc_pgd_batch* h, const int32_t* d_kk, const int32_t* d_ii, const int32_t* d_jj) {
+    auto t1 = std::chrono::steady_clock::now();
+    const int32_t count = h->count;
+    const size_t M = (size_t)h->M, MC = (size_t)h->MC, MP = (size_t)h->MP;
+    int rc;
+    // the workgroup table: a problem's segments in runs of BATCH_PASSES x 4 waves x 64/G, counted from its own first segment
+    hvec<BatchWg> wg;
+    hvec<BatchProb> pr((size_t)count);
+    for (int32_t b = 0; b < count; ++b) {
+        const BatchPlan& s = h->plan[(size_t)b];
+        const int G = s.max_cnt <= 16 ? 16 : s.max_cnt <= 32 ? 32 : 64;
+        const int64_t per = (int64_t)BATCH_PASSES * 4 * (64 / G);
+        pr[(size_t)b].wg0 = (int32_t)wg.size(); pr[(size_t)b].m = probs[b].m;
+        for (int64_t l = 0; l < s.m_pos; l += per)
+            wg.push_back(BatchWg{b, (int32_t)(h->seg_off[(size_t)b] + l), (int32_t)std::min<int64_t>(per, s.m_pos - l), G});
+        pr[(size_t)b].nwg = (int32_t)wg.size() - pr[(size_t)b].wg0;
+    }
+    h->nwg = (int32_t)wg.size();
+    double* d_rij = nullptr;
     if ((rc = h->upload(&h->d_wg, wg.data(), wg.size()))) return rc;
     if ((rc = h->upload(&h->d_prob, pr.data(), pr.size()))) return rc;
     if ((rc = h->upload(&h->d_edge_off, h->edge_off.data(), h->edge_off.size()))) return rc;
@@ -422,6 +451,66 @@ int batch_create(const desc_problem* probs, int32_t count, const desc_params* p,
     }
     DESC_HIP(hipStreamSynchronize(h->stream));
     h->ms_cycle_d = ms_since(t2);
+    return DESC_OK;
+}
+
+// The device builder (batch_structure.hip) in place of the per-problem host builds, the concatenation and the seven uploads.  May
+// return BATCH_BUILD_FALLBACK: the caller then builds the same handle on the host.
+int batch_create_device(const desc_problem* probs, int32_t count, const desc_params* p, const uint64_t* seeds, desc_pgd_batch* h) {
+    auto t0 = std::chrono::steady_clock::now();
+    h->count = count; h->built_where = DESC_BUILD_DEVICE;
+    const int32_t nmin = p->n_sample_min > 0 ? p->n_sample_min : 30;
+    BatchBuilt bb;
+    int rc = batch_structure_device(h, probs, count, nmin, p->seed, seeds, p->device, &bb);
+    if (rc) return rc;
+    h->st.assign((size_t)count, nullptr);
+    h->st_ready = count == 0;
+    h->prob_n.resize((size_t)count);
+    h->n_sample.resize((size_t)count);
+    for (int32_t b = 0; b < count; ++b) { h->prob_n[(size_t)b] = probs[b].n; h->n_sample[(size_t)b] = bb.plan[(size_t)b].n_sample; }
+    h->plan = bb.plan; h->edge_off = bb.edge_off; h->cycle_off = bb.cycle_off; h->seg_off = bb.seg_off;
+    h->M = h->edge_off[(size_t)count]; h->MC = h->cycle_off[(size_t)count]; h->MP = h->seg_off[(size_t)count];
+    if (count == 0) return DESC_OK;
+    h->d_cum = bb.d_cum; h->d_pos = bb.d_pos; h->d_ejk = bb.d_ejk; h->d_eki = bb.d_eki; h->d_ikj = bb.d_ikj; h->d_jki = bb.d_jki;
+    h->d_kk = bb.d_kk; h->d_codeg = bb.d_codeg;
+    for (int t = 0; t < BATCH_BUILD_LAPS; ++t) h->ms_lap[t] = bb.ms_lap[t];
+    h->ms_structure = ms_since(t0);                    // batch_structure_device returned with the stream drained
+    return batch_finish(probs, h, bb.d_kk, bb.d_ii, bb.d_jj);
+}
+
+// desc_pgd_batch_get_structure on a device-built handle, first request: the index arrays come down once, every problem's share less
+// its offsets becomes a host-resident desc_structure.
+int batch_structures_to_host(desc_pgd_batch* h) {
+    if (h->st_ready) return DESC_OK;
+    const size_t M = (size_t)h->M, MC = (size_t)h->MC, MP = (size_t)h->MP;
+    hvec<int32_t> pos(MP), cum(MP + 1), ejk(MC), eki(MC), ikj(MC), jki(MC), kk(MC), cdg(M);
+    DESC_HIP(hipSetDevice(h->device));
+    DESC_HIP(hipStreamSynchronize(h->stream));
+    const struct { int32_t* dst; const int32_t* src; size_t n; } copies[] = {
+        {pos.data(), h->d_pos, MP}, {cum.data(), h->d_cum, MP + 1}, {ejk.data(), h->d_ejk, MC}, {eki.data(), h->d_eki, MC},
+        {ikj.data(), h->d_ikj, MC}, {jki.data(), h->d_jki, MC}, {kk.data(), h->d_kk, MC}, {cdg.data(), h->d_codeg, M}};
+    for (const auto& c : copies)
+        if (c.n) DESC_HIP(hipMemcpy(c.dst, c.src, sizeof(int32_t) * c.n, hipMemcpyDeviceToHost));
+    for (int32_t b = 0; b < h->count; ++b) {
+        desc_structure* s = new desc_structure();
+        h->st[(size_t)b] = s;
+        const BatchPlan& q = h->plan[(size_t)b];
+        const int64_t eo = h->edge_off[(size_t)b], co = h->cycle_off[(size_t)b], so = h->seg_off[(size_t)b];
+        s->n = h->prob_n[(size_t)b]; s->m = h->edge_off[(size_t)b + 1] - eo; s->m_pos = q.m_pos; s->m_cycle = q.m_cycle;
+        s->n_sample = q.n_sample; s->max_cnt = q.max_cnt; s->host_cycles = true;
+        s->codeg.assign(cdg.begin() + eo, cdg.begin() + eo + s->m);
+        s->pos_edge.resize((size_t)q.m_pos); s->cum_ind.resize((size_t)q.m_pos + 1);
+        for (int64_t l = 0; l < q.m_pos; ++l) s->pos_edge[(size_t)l] = pos[(size_t)(so + l)] - (int32_t)eo;
+        for (int64_t l = 0; l <= q.m_pos; ++l) s->cum_ind[(size_t)l] = (int64_t)cum[(size_t)(so + l)] - co;
+        s->k.assign(kk.begin() + co, kk.begin() + co + q.m_cycle);
+        s->e_jk.resize((size_t)q.m_cycle); s->e_ki.resize((size_t)q.m_cycle); s->ikj.resize((size_t)q.m_cycle); s->jki.resize((size_t)q.m_cycle);
+        for (int64_t c = 0; c < q.m_cycle; ++c) {
+            const size_t g = (size_t)(co + c);
+            s->e_jk[(size_t)c] = ejk[g] - (int32_t)eo; s->e_ki[(size_t)c] = eki[g] - (int32_t)eo;
+            s->ikj[(size_t)c] = ikj[g] < 0 ? -1 : ikj[g] - (int32_t)co; s->jki[(size_t)c] = jki[g] < 0 ? -1 : jki[g] - (int32_t)co;
+        }
+    }
+    h->st_ready = true;
     return DESC_OK;
 }
 
@@ -572,6 +661,30 @@ int desc_pgd_batch_create(const desc_problem* probs, int32_t count, const desc_p
                                 [&](desc_pgd_batch* h) { return batch_create(probs, count, p, seeds, h); }, p != nullptr);
 }
 
+int desc_pgd_batch_create_where(const desc_problem* probs, int32_t count, const desc_params* p, const uint64_t* seeds, int32_t where,
+                                desc_pgd_batch** out) {
+    if (where != DESC_BUILD_HOST && where != DESC_BUILD_DEVICE) {
+        if (out) *out = nullptr;
+        return fail(DESC_ERR_INVALID, "where = %d: need DESC_BUILD_HOST or DESC_BUILD_DEVICE", (int)where);
+    }
+    return batch_create_guarded("desc_pgd_batch_create_where", out, probs, count, [&](desc_pgd_batch* h) {
+        if (where == DESC_BUILD_DEVICE) {
+            const int rc = batch_create_device(probs, count, p, seeds, h);
+            if (rc != BATCH_BUILD_FALLBACK) return rc;
+            h->close();                                // outside what the device builder stages: the same handle, built on the host
+        }
+        return batch_create(probs, count, p, seeds, h);
+    }, p != nullptr);
+}
+
+int32_t desc_pgd_batch_built_where(const desc_pgd_batch* h) { return h ? h->built_where : (int32_t)fail(DESC_ERR_INVALID, "NULL handle"); }
+
+int desc_pgd_batch_build_laps(const desc_pgd_batch* h, double* ms) {
+    if (!h || !ms) return fail(DESC_ERR_INVALID, "NULL argument");
+    for (int t = 0; t < BATCH_BUILD_LAPS; ++t) ms[t] = h->ms_lap[t];
+    return DESC_OK;
+}
+
 int desc_pgd_batch_sizes(const desc_pgd_batch* h, int32_t* count, int64_t* edge_off, int64_t* cycle_off, int32_t* n_sample) {
     if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
     if (count) *count = h->count;
@@ -584,6 +697,8 @@ int desc_pgd_batch_sizes(const desc_pgd_batch* h, int32_t* count, int64_t* edge_
 int desc_pgd_batch_get_structure(const desc_pgd_batch* h, int32_t b, desc_structure_view* view) {
     if (!h || !view) return fail(DESC_ERR_INVALID, "NULL argument");
     if (b < 0 || b >= h->count) return fail(DESC_ERR_INVALID, "problem %d out of range (the batch holds %d)", b, h->count);
+    const int rc = no_throw("desc_pgd_batch_get_structure", [&]() -> int { return batch_structures_to_host(const_cast<desc_pgd_batch*>(h)); });
+    if (rc) return rc;
     return desc_structure_get(h->st[(size_t)b], view);
 }
 

@@ -1,4 +1,4 @@
-// Host part shared by the batched calls that walk per-problem CSR rows (gcw_batch.hip, cemp_batch.hip, mpls_batch.hip, mst_batch.hip, refine_batch.hip, irls_batch.hip, lp_batch.hip):
+// Host part shared by the batched calls that walk per-problem CSR rows (gcw_batch.hip, cemp_batch.hip, mpls_batch.hip, mst_batch.hip, refine_batch.hip, irls_batch.hip, lp_batch.hip, batch_structure.hip):
 // validation, offsets and the CSR of every problem with LOCAL node and edge ids -- what desc_gcw_batch_csr returns -- and the host
 // loops every batched call repeats.  No device: the device half of a handle is BatchDevice (batch_device.h).
 #pragma once
@@ -19,8 +19,10 @@ struct BatchCsr {
 };
 
 // Refuses -- naming the problem -- what validate_problem refuses, an empty edge list, what `extra` (nullable: the caller's own caps,
-// called per problem after those two) refuses, and a batch of 2^30 edges or more.  Defined in gcw_batch.hip.
-int batch_csr_host(const desc_problem* probs, int32_t count, const std::function<int(int32_t, const desc_problem&)>& extra, BatchCsr* h);
+// called per problem after those two) refuses, and a batch of 2^30 edges or more.  allow_empty: a problem without an edge is taken
+// (rows of length 0), for the caller whose host path takes it (batch_structure.hip).  Defined in gcw_batch.hip.
+int batch_csr_host(const desc_problem* probs, int32_t count, const std::function<int(int32_t, const desc_problem&)>& extra, BatchCsr* h,
+                   bool allow_empty = false);
 
 // fn(b) for every problem, the problems dealt round-robin to 16 host threads at most (run_threads: exceptions reach the caller)
 template <class F>

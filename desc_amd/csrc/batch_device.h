@@ -1,4 +1,4 @@
-// Device half of a batched handle, shared by batch.hip, gcw_batch.hip, cemp_batch.hip (with mpls_batch.hip on its handle), mst_batch.hip, refine_batch.hip, irls_batch.hip and lp_batch.hip: the device,
+// Device half of a batched handle, shared by batch.hip (with batch_structure.hip on its handle), gcw_batch.hip, cemp_batch.hip (with mpls_batch.hip on its handle), mst_batch.hip, refine_batch.hip, irls_batch.hip and lp_batch.hip: the device,
 // one pooled stream, the arena of device blocks, the event pair around a timed launch, and the create wrapper of the C entry points.
 // Host code only.  A batched call supplies its host validation, its kernels and its words for the refusals; the order of the
 // refusals (nothing touches the device before open) and of the teardown is decided here.

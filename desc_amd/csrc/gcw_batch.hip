@@ -342,13 +342,14 @@ __global__ __launch_bounds__(256, 2) void k_gcw_batch(GbArgs a) {
 
 namespace desc {
 
-int batch_csr_host(const desc_problem* probs, int32_t count, const std::function<int(int32_t, const desc_problem&)>& extra, BatchCsr* h) {
+int batch_csr_host(const desc_problem* probs, int32_t count, const std::function<int(int32_t, const desc_problem&)>& extra, BatchCsr* h,
+                   bool allow_empty) {
     h->count = count;
     h->node_off.assign((size_t)count + 1, 0); h->edge_off.assign((size_t)count + 1, 0);
     for (int32_t b = 0; b < count; ++b) {
         int rc = validate_problem(&probs[b], true);
         if (rc) { const std::string msg = desc_last_error(); return fail(rc, "problem %d: %s", b, msg.c_str()); }
-        if (probs[b].m == 0) return fail(DESC_ERR_INVALID, "problem %d: empty edge list", b);
+        if (probs[b].m == 0 && !allow_empty) return fail(DESC_ERR_INVALID, "problem %d: empty edge list", b);
         if (extra && (rc = extra(b, probs[b]))) return rc;
         h->node_off[(size_t)b + 1] = h->node_off[(size_t)b] + probs[b].n;
         h->edge_off[(size_t)b + 1] = h->edge_off[(size_t)b] + probs[b].m;

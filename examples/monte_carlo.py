@@ -2,7 +2,11 @@
 """A small Monte-Carlo study in ONE batched call: mean |S_vec - ErrVec| against the corruption level q, averaged over a few trials
 of Uniform_Topology(100, 0.5, q, 0.1) -- the shape of the figures the DESC paper draws (error against q on graphs of 100-200 nodes).
 
-    python examples/monte_carlo.py [--trials 5] [--n 100] [--iters 100] [--rotations] [--refined] [--baselines] [--mpls] [--lp] [--irls]
+    python examples/monte_carlo.py [--trials 5] [--n 100] [--iters 100] [--build host|device] [--rotations] [--refined] [--baselines]
+                                   [--mpls] [--lp] [--irls]
+
+--build: the builder of the cycle structures behind DESC_PGD_batch / DESC_init_batch / DESC_batch: per problem on host threads (the
+default) or for the whole batch on the device; the curves are the same to the last bit.
 
 --rotations: the demo's own metric next to it -- one DESC_init_batch call (the PGD pass, then the batched GCW eigen-solve) and the mean
 rotation error in degrees (Rotation_Alignment against the ground truth), the column of Demo/compare_algorithms.m.
@@ -112,6 +116,7 @@ def main():
     ap.add_argument("--trials", type=int, default=5)
     ap.add_argument("--n", type=int, default=100)
     ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--build", choices=("host", "device"), default="host", help="where the batch's cycle structures are built")
     ap.add_argument("--rotations", action="store_true", help="one DESC_init_batch call: the mean rotation error next to the S_vec error")
     ap.add_argument("--refined", action="store_true", help="one DESC_batch call: the rotation error of DESC() next to its initialisation's")
     ap.add_argument("--baselines", action="store_true", help="CEMP, CEMP+GCW and CEMP+MST next to DESC: one batched call per curve")
@@ -124,7 +129,7 @@ def main():
     params = dict(iters=a.iters, Gradient=ConstantStepSize(0.01), seed=0, verbose=False)
     if a.refined:
         t0 = time.perf_counter()
-        out = DESC_batch(models, params)
+        out = DESC_batch(models, params, build=a.build)
         ms = (time.perf_counter() - t0) * 1e3
         shape = (len(qs), a.trials)
         err = np.array([np.abs(s - mo.ErrVec).mean() for (_, _, s), mo in zip(out, models)]).reshape(shape)
@@ -145,10 +150,10 @@ def main():
         return
     t0 = time.perf_counter()
     if a.rotations:
-        out = DESC_init_batch(models, params)
+        out = DESC_init_batch(models, params, build=a.build)
         S = [s for _, s in out]
     else:
-        S = DESC_PGD_batch(models, params)
+        S = DESC_PGD_batch(models, params, build=a.build)
     ms = (time.perf_counter() - t0) * 1e3
     err = np.array([np.abs(s - mo.ErrVec).mean() for s, mo in zip(S, models)]).reshape(len(qs), a.trials)
     print(f"{len(models)} problems (n = {a.n}, {a.trials} trials per q) in one {'DESC_init_batch' if a.rotations else 'DESC_PGD_batch'} call: {ms:.1f} ms")

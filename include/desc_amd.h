@@ -541,8 +541,20 @@ int desc_lp_sij_run_dev(const desc_device_problem* dp, const desc_lp_params* par
  * its cycles at cycle_off[b] .. cycle_off[b+1] of every per-cycle vector (the problem's own cycle order).
  * desc_pgd_batch_create: validates, builds the structures on min(count, 16) host threads, refuses -- all before any device work, naming
  * the problem -- a problem whose n_sample exceeds 64 (DESC_ERR_INVALID: solve it with desc_pgd_solve) and totals of m_cycle >= 2^31 - 1
- * or m >= 2^30 (DESC_ERR_TOO_LARGE); then uploads and evaluates S0_long of the whole batch.  p: n_sample_min, seed and device are read.
- * count == 0 is legal.  Step rules: DESC_STEP_CONSTANT / PIECEWISE / HYBRID, one desc_params for the whole batch. */
+ * or m >= 2^30 (DESC_ERR_TOO_LARGE); then uploads and evaluates S0_long of the whole batch.  p: n_sample_min, seed and device are read
+ * (p->build_where is NOT: the builder of a batch is chosen by desc_pgd_batch_create_where).
+ * count == 0 is legal.  Step rules: DESC_STEP_CONSTANT / PIECEWISE / HYBRID, one desc_params for the whole batch.
+ *
+ * desc_pgd_batch_create_where(.., where, ..): where = DESC_BUILD_HOST is desc_pgd_batch_create.  where = DESC_BUILD_DEVICE makes the
+ * same index arrays, element for element, on the device: the host validates and builds the CSR of every problem (O(m); no triangle
+ * is touched on the host), five launches for the whole batch count the codegrees, plan, compact, sample and mirror, and the only
+ * read-back is one record per problem.  Everything downstream (S0_long, the sweep, the stop rule, S_vec, w, the traces) is bit for bit
+ * what the host builder gives.  It refuses what the host builder refuses, with the same code and the same "problem b"; n_sample > 64
+ * and the 2^31 - 1 total are known only after that read-back and are refused there, after device work: the handle is then closed and
+ * nothing is left allocated.  Two cases make the whole batch fall back to the host builder, silently and without failing: a problem
+ * with a CSR row above desc_cemp_batch_max_degree(), and a problem with a codegree above desc_pgd_batch_max_codeg() (what the sampling
+ * kernel stages in the 64 KiB of LDS a launch may declare).  desc_pgd_batch_built_where tells which builder made the handle.  Any other
+ * value of where: DESC_ERR_INVALID.  DESC_DEBUG_EXACT_SELECT=1 (read at create) forces the tie-safe exact ranking for every edge. */
 typedef struct desc_pgd_batch desc_pgd_batch;   /* opaque */
 typedef struct desc_batch_result {
     double* s_vec;            /* edge_off[count]   out: S_vec of every problem                                  */
@@ -554,17 +566,28 @@ typedef struct desc_batch_result {
     double* adam_v;           /* cycle_off[count]  in/out or NULL: HybridGradient.v_t                           */
     int32_t* iters_run;       /* count             out: iterations problem b executed                           */
     int32_t* t_end;           /* count             out or NULL: plugin counter of problem b after the run       */
-    double ms_structure;      /* host structure builds + concatenation (wall clock of desc_pgd_batch_create's host part) */
-    double ms_upload;         /* host -> HBM                                                                    */
+    double ms_structure;      /* wall clock of create up to the point where the index arrays are on the device (either builder) */
+    double ms_upload;         /* the remainder of the set-up: the rotations, the small tables, the state buffers  */
     double ms_cycle_d;        /* S0_long kernel                                                                 */
     double ms_pgd;            /* PGD loop, device time (HIP events)                                             */
     double ms_total;          /* wall clock of desc_pgd_batch_run                                               */
 } desc_batch_result;          /* 104 bytes */
 int desc_pgd_batch_create(const desc_problem* probs, int32_t count, const desc_params* p, const uint64_t* seeds /* count, nullable */,
                           desc_pgd_batch** out);
+int desc_pgd_batch_create_where(const desc_problem* probs, int32_t count, const desc_params* p, const uint64_t* seeds /* count, nullable */,
+                                int32_t where /* DESC_BUILD_HOST | DESC_BUILD_DEVICE */, desc_pgd_batch** out);
+int32_t desc_pgd_batch_built_where(const desc_pgd_batch* h);      /* DESC_BUILD_HOST | DESC_BUILD_DEVICE: the builder that made the handle */
+int32_t desc_pgd_batch_max_codeg(void);                           /* the largest codegree the device builder's sampling kernel stages */
+/* device time (ms, HIP events) of the device builder's five launches: codegrees, plan, compaction, sampling, mirror maps; zeros for a
+ * host-built handle */
+int desc_pgd_batch_build_laps(const desc_pgd_batch* h, double* ms /* 5 */);
+/* the plan rule of the device builder on a histogram of codegrees (hist[c], c = 0 .. n), for tests; no device.
+ * out: m_pos, max_codeg, n_sample, m_cycle, max_cnt */
+int desc_test_batch_plan(const int32_t* hist, int32_t n, int32_t n_sample_min, int64_t* out /* 5 */);
 /* count (nullable), edge_off[count+1], cycle_off[count+1], n_sample[count] (each nullable): what a binding needs to size its buffers */
 int desc_pgd_batch_sizes(const desc_pgd_batch* h, int32_t* count, int64_t* edge_off, int64_t* cycle_off, int32_t* n_sample);
-/* the structure of problem b, local ids (parity tests); the view stays valid until desc_pgd_batch_destroy */
+/* the structure of problem b, local ids (parity tests); the view stays valid until desc_pgd_batch_destroy.  On a device-built handle the
+ * first request downloads the index arrays once and fills a host-resident structure per problem; the plain run never does. */
 int desc_pgd_batch_get_structure(const desc_pgd_batch* h, int32_t b, desc_structure_view* view);
 int desc_pgd_batch_get_s0(desc_pgd_batch* h, double* s0 /* cycle_off[count] */);
 /* init + loop + download.  p->check_every: the host reads one "problems still running" word every this many iterations (0: 32);
