@@ -2021,8 +2021,6 @@ struct desc_pgd {
     int64_t n = 0, m = 0, m_pos = 0, m_cycle = 0;
     int32_t max_cnt = 0, n_sample = 0, max_deg = 0;
     int variant = VARIANT_GATHER;
-    int G = 64;                 // gather variant: lanes per segment (0 = big fallback); node variant: cycles per lane
-    int lps = 16;               // node variant: lanes per segment
     bool band_jmajor = false;   // band sweep: j-block-major units (large graphs) instead of contiguous ranges
     int grid = 0;               // sweep grid (multiple of 8)
     int obj_grid = 0;
@@ -2035,7 +2033,7 @@ struct desc_pgd {
     int band = 0;
     bool band_ok = false;       // k_sweep_band applies (segments <= 64 cycles, rows fit the LDS)
     bool small_ok = false;      // k_sweep_small: one rank, < 2 M cycles, segments of at most 64 cycles (the reference's demo sizes)
-    int small_grid = 0, small_g = 64;
+    int small_grid = 0;
     int band_grid = 0, band_rows = 0;
     size_t band_lds = 0;
     PieceDesc* d_pieces = nullptr;
@@ -2181,32 +2179,56 @@ StepArgs make_step(desc_pgd* h, bool* adam, int rd, int wr) {
     return s;
 }
 
-template <int STEP>
-void launch_gather(desc_pgd* h, const SweepArgs& a) {
-    dim3 grid(h->grid), block(256);
-    { char nm[64]; if (h->G) snprintf(nm, sizeof nm, "k_sweep<%d,%d>", h->G, STEP); else snprintf(nm, sizeof nm, "k_sweep_big<%d>", STEP); h->last_sweep = nm; }
-    switch (h->G) {
-        case 16: hipLaunchKernelGGL((k_sweep<16, STEP>), grid, block, 0, h->stream, a); break;
-        case 32: hipLaunchKernelGGL((k_sweep<32, STEP>), grid, block, 0, h->stream, a); break;
-        case 64: hipLaunchKernelGGL((k_sweep<64, STEP>), grid, block, 0, h->stream, a); break;
-        default: hipLaunchKernelGGL((k_sweep_big<STEP>), grid, block, 0, h->stream, a); break;
-    }
+// ------------------------------------------------------------ sweep instances --
+// Every instance of a sweep kernel that can be launched is written once, as an entry of its family's table.  The launch, the kernel's address
+// (hipFuncSetAttribute, the occupancy query) and the names desc_debug_last_sweep and desc_pgd_kernel_name return all come from that entry; the
+// rule from the longest segment to an entry's shape is one function per family.
+struct SweepShape { int lps, E; };      // lanes per segment x cycles per lane (gather layout and k_sweep_small: E = 0)
+template <class... A>
+struct SweepInst {
+    SweepShape sh;
+    int NT;                             // threads per workgroup
+    void (*kern[2])(A...);              // {constant step, Adam}; band sweep: {one rank, XT}
+};
+constexpr int STEP_OF[2] = {DESC_STEP_CONSTANT, DESC_STEP_HYBRID};      // the STEP argument of kern[adam]
+template <class I, size_t N>
+const I* sweep_inst(const I (&table)[N], SweepShape sh) {
+    for (const I& i : table) if (i.sh.lps == sh.lps && i.sh.E == sh.E) return &i;
+    fail(DESC_ERR_STATE, "no sweep instance of %d lanes per segment x %d cycles per lane", sh.lps, sh.E);
+    return nullptr;
 }
-template <int STEP>
-void launch_node(desc_pgd* h, const NodeSweepArgs& a) {
-    dim3 grid(h->grid), block(SWEEP_THREADS);
-    {
-        int L = h->lps, E = h->G;
-        if (!((L == 16 && (E == 1 || E == 2)) || (L == 32 && (E == 2 || E == 4)))) { L = 64; E = 4; }      // the switch's default
-        char nm[64]; snprintf(nm, sizeof nm, "k_sweep_node<%d,%d,%d>%s", L, E, STEP, a.xt ? " sharded" : ""); h->last_sweep = nm;
-    }
-    switch (h->lps * 8 + h->G) {              // lps lanes per segment, G = cycles per lane (E)
-        case 16 * 8 + 1: hipLaunchKernelGGL((k_sweep_node<16, 1, STEP>), grid, block, 0, h->stream, a); break;
-        case 16 * 8 + 2: hipLaunchKernelGGL((k_sweep_node<16, 2, STEP>), grid, block, 0, h->stream, a); break;
-        case 32 * 8 + 2: hipLaunchKernelGGL((k_sweep_node<32, 2, STEP>), grid, block, 0, h->stream, a); break;
-        case 32 * 8 + 4: hipLaunchKernelGGL((k_sweep_node<32, 4, STEP>), grid, block, 0, h->stream, a); break;
-        default: hipLaunchKernelGGL((k_sweep_node<64, 4, STEP>), grid, block, 0, h->stream, a); break;
-    }
+template <class... V>
+std::string inst_name(const char* fmt, V... v) { char nm[64]; snprintf(nm, sizeof nm, fmt, v...); return nm; }
+
+// gather layout: G lanes per segment; above 64 cycles (G = 0) k_sweep_big, the multi-pass wave-per-edge kernel
+template <int G>
+constexpr SweepInst<SweepArgs> gather_inst() { return {{G, 0}, 256, {k_sweep<G, DESC_STEP_CONSTANT>, k_sweep<G, DESC_STEP_HYBRID>}}; }
+constexpr SweepInst<SweepArgs> big_inst() { return {{0, 0}, 256, {k_sweep_big<DESC_STEP_CONSTANT>, k_sweep_big<DESC_STEP_HYBRID>}}; }
+const SweepInst<SweepArgs> GATHER_INSTS[] = {gather_inst<16>(), gather_inst<32>(), gather_inst<64>(), big_inst()};
+SweepShape gather_shape(int c) { return {c <= 16 ? 16 : c <= 32 ? 32 : c <= 64 ? 64 : 0, 0}; }      // 16, 32, 64 or 0: each has its entry
+std::string gather_prefix(SweepShape sh) { return sh.lps ? inst_name("k_sweep<%d,", sh.lps) : std::string("k_sweep_big<"); }
+int launch_gather(desc_pgd* h, const SweepArgs& a, bool adam) {
+    const auto* k = sweep_inst(GATHER_INSTS, gather_shape(h->max_cnt));
+    if (!k) return DESC_ERR_STATE;
+    h->last_sweep = gather_prefix(k->sh) + inst_name("%d>", STEP_OF[adam]);
+    hipLaunchKernelGGL(k->kern[adam], dim3(h->grid), dim3(k->NT), 0, h->stream, a);
+    return DESC_OK;
+}
+
+// node layout: lanes per segment x cycles per lane >= longest segment
+// (33..64 cycles: 32 lanes x 2 cycles keeps all 8 waves of the workgroup busy in the arithmetic --
+//  measured 2 % faster than 16 lanes x 4 cycles at C2 and C4)
+template <int LPS, int E>
+constexpr SweepInst<NodeSweepArgs> node_inst() { return {{LPS, E}, SWEEP_THREADS, {k_sweep_node<LPS, E, DESC_STEP_CONSTANT>, k_sweep_node<LPS, E, DESC_STEP_HYBRID>}}; }
+const SweepInst<NodeSweepArgs> NODE_INSTS[] = {node_inst<16, 1>(), node_inst<16, 2>(), node_inst<32, 2>(), node_inst<32, 4>(), node_inst<64, 4>()};
+SweepShape node_shape(int c) { return {c <= 32 ? 16 : c <= 128 ? 32 : 64, c <= 16 ? 1 : c <= 64 ? 2 : 4}; }      // 16 x 1, 16 x 2, 32 x 2, 32 x 4 or 64 x 4: each has its entry
+std::string node_prefix(SweepShape sh) { return inst_name("k_sweep_node<%d,%d,", sh.lps, sh.E); }
+int launch_node(desc_pgd* h, const NodeSweepArgs& a, bool adam) {
+    const auto* k = sweep_inst(NODE_INSTS, node_shape(h->max_cnt));
+    if (!k) return DESC_ERR_STATE;
+    h->last_sweep = node_prefix(k->sh) + inst_name("%d>%s", STEP_OF[adam], a.xt ? " sharded" : "");
+    hipLaunchKernelGGL(k->kern[adam], dim3(h->grid), dim3(k->NT), 0, h->stream, a);
+    return DESC_OK;
 }
 
 // Band sweep instances by the longest segment: lanes per segment x cycles per lane, threads per workgroup.
@@ -2217,81 +2239,51 @@ void launch_node(desc_pgd* h, const NodeSweepArgs& a) {
 //  the same shape on 16 waves by 2-4 % (12 waves: 1 %; 4 waves lose 7-22 % everywhere): fewer waves keep more of the j rows in the caches --
 //  the PMC traffic of the C4 sweep fell from 6.2 to 5.6 GB with the 8-wave shape.)
 // The Adam plugin: 512-thread instances (the moments ride in the stream sets) up to 64 cycles: 16 x 1, 16 x 2, 32 x 2.
-struct BandShape { int lps, E; };
-BandShape band_shape(const desc_pgd* h, bool adam) {
-    const int c = h->max_cnt;
-    if (adam) return c <= 16 ? BandShape{16, 1} : c <= 32 ? BandShape{16, 2} : BandShape{32, 2};
-    if (c > 16 && c <= 32 && !h->band_jmajor) return BandShape{8, 4};      // graphs whose S stays in the L2 (contiguous ranges)
-    return c <= 16 ? BandShape{16, 1} : c <= 32 ? BandShape{16, 2} : c <= 64 ? BandShape{16, 4} : c <= 128 ? BandShape{32, 4} : BandShape{64, 4};
-}
-bool band_adam_ok(const desc_pgd* h) { return h->band_ok && h->max_cnt <= 64; }
-template <int STEP, bool XT>
-const void* band_kernel(const desc_pgd* h) {
-    const BandShape sh = band_shape(h, STEP == DESC_STEP_HYBRID);
-    if constexpr (STEP == DESC_STEP_HYBRID) {
-        if (h->max_cnt > 64) return nullptr;           // 4 cycles per lane + the moments do not fit the registers: k_sweep_node (band_adam_ok)
-        switch (sh.lps * 8 + sh.E) {
-            case 16 * 8 + 1: return (const void*)k_sweep_band<16, 1, STEP, 512, XT>;
-            case 16 * 8 + 2: return (const void*)k_sweep_band<16, 2, STEP, 512, XT>;
-            default: return (const void*)k_sweep_band<32, 2, STEP, 512, XT>;
-        }
-    } else {
-        switch (sh.lps * 8 + sh.E) {
-            case 16 * 8 + 1: return (const void*)k_sweep_band<16, 1, STEP, 1024, XT>;
-            case 16 * 8 + 2: return (const void*)k_sweep_band<16, 2, STEP, 512, XT>;
-            case 16 * 8 + 4: return (const void*)k_sweep_band<16, 4, STEP, 512, XT>;
-            case 8 * 8 + 4: return (const void*)k_sweep_band<8, 4, STEP, 512, XT>;
-            case 32 * 8 + 4: return (const void*)k_sweep_band<32, 4, STEP, 512, XT>;
-            default: return (const void*)k_sweep_band<64, 4, STEP, 512, XT>;
-        }
-    }
-}
 template <int LPS, int E, int STEP, int NT>
-void launch_band_shape(desc_pgd* h, const BandSweepArgs& b) {
-    { char nm[64]; snprintf(nm, sizeof nm, "k_sweep_band<%d,%d,%d,%d,%s>", LPS, E, STEP, NT, b.n.xt ? "XT" : "one-rank"); h->last_sweep = nm; }
-    if (b.n.xt) hipLaunchKernelGGL((k_sweep_band<LPS, E, STEP, NT, true>), dim3(h->band_grid), dim3(NT), h->band_lds, h->stream, b);
-    else hipLaunchKernelGGL((k_sweep_band<LPS, E, STEP, NT, false>), dim3(h->band_grid), dim3(NT), h->band_lds, h->stream, b);
+constexpr SweepInst<BandSweepArgs> band_inst() { return {{LPS, E}, NT, {k_sweep_band<LPS, E, STEP, NT, false>, k_sweep_band<LPS, E, STEP, NT, true>}}; }
+const SweepInst<BandSweepArgs> BAND_INSTS[] = {band_inst<16, 1, DESC_STEP_CONSTANT, 1024>(), band_inst<16, 2, DESC_STEP_CONSTANT, 512>(), band_inst<8, 4, DESC_STEP_CONSTANT, 512>(),
+                                               band_inst<16, 4, DESC_STEP_CONSTANT, 512>(), band_inst<32, 4, DESC_STEP_CONSTANT, 512>(), band_inst<64, 4, DESC_STEP_CONSTANT, 512>()};
+const SweepInst<BandSweepArgs> BAND_ADAM_INSTS[] = {band_inst<16, 1, DESC_STEP_HYBRID, 512>(), band_inst<16, 2, DESC_STEP_HYBRID, 512>(), band_inst<32, 2, DESC_STEP_HYBRID, 512>()};
+// Adam above 64 cycles: 4 cycles per lane + the moments do not fit the registers -- no band instance, k_sweep_node sweeps
+bool band_adam_ok(const desc_pgd* h) { return h->band_ok && h->max_cnt <= 64; }
+SweepShape band_shape(const desc_pgd* h, bool adam) {      // constant step: the six shapes of BAND_INSTS; Adam (at most 64 cycles): the three of BAND_ADAM_INSTS
+    const int c = h->max_cnt;
+    if (adam) return c <= 16 ? SweepShape{16, 1} : c <= 32 ? SweepShape{16, 2} : SweepShape{32, 2};
+    if (c > 16 && c <= 32 && !h->band_jmajor) return SweepShape{8, 4};      // graphs whose S stays in the L2 (contiguous ranges)
+    return c <= 16 ? SweepShape{16, 1} : c <= 32 ? SweepShape{16, 2} : c <= 64 ? SweepShape{16, 4} : c <= 128 ? SweepShape{32, 4} : SweepShape{64, 4};
 }
-template <int STEP>
-void launch_band(desc_pgd* h, const NodeSweepArgs& a, int part = 0) {
-    const BandShape sh = band_shape(h, STEP == DESC_STEP_HYBRID);
+const SweepInst<BandSweepArgs>* band_inst_of(const desc_pgd* h, bool adam) {
+    return adam ? sweep_inst(BAND_ADAM_INSTS, band_shape(h, true)) : sweep_inst(BAND_INSTS, band_shape(h, false));
+}
+std::string band_prefix(SweepShape sh) { return inst_name("k_sweep_band<%d,%d,", sh.lps, sh.E); }
+int launch_band(desc_pgd* h, const NodeSweepArgs& a, bool adam, int part) {
+    const auto* k = band_inst_of(h, adam);
+    if (!k) return DESC_ERR_STATE;
     // the plan of exchange part `part` (one-rank handles: the only one)
     BandSweepArgs b{a, h->d_pieces + h->xpiece_base[part], h->d_piece_ptr + h->xpiece_ptr_base[part], h->band_rows, h->d_wg_clock, h->xtail_first[part], h->xntail[part],
                     h->d_ticket + part};
-    if constexpr (STEP == DESC_STEP_HYBRID) {
-        switch (sh.lps * 8 + sh.E) {
-            case 16 * 8 + 1: launch_band_shape<16, 1, STEP, 512>(h, b); break;
-            case 16 * 8 + 2: launch_band_shape<16, 2, STEP, 512>(h, b); break;
-            default: launch_band_shape<32, 2, STEP, 512>(h, b); break;
-        }
-    } else {
-        switch (sh.lps * 8 + sh.E) {
-            case 16 * 8 + 1: launch_band_shape<16, 1, STEP, 1024>(h, b); break;
-            case 16 * 8 + 2: launch_band_shape<16, 2, STEP, 512>(h, b); break;
-            case 16 * 8 + 4: launch_band_shape<16, 4, STEP, 512>(h, b); break;
-            case 8 * 8 + 4: launch_band_shape<8, 4, STEP, 512>(h, b); break;
-            case 32 * 8 + 4: launch_band_shape<32, 4, STEP, 512>(h, b); break;
-            default: launch_band_shape<64, 4, STEP, 512>(h, b); break;
-        }
-    }
+    h->last_sweep = band_prefix(k->sh) + inst_name("%d,%d,%s>", STEP_OF[adam], k->NT, a.xt ? "XT" : "one-rank");
+    hipLaunchKernelGGL(k->kern[a.xt != nullptr], dim3(h->band_grid), dim3(k->NT), h->band_lds, h->stream, b);
+    return DESC_OK;
 }
-template <int STEP>
-void launch_small(desc_pgd* h, const NodeSweepArgs& a) {
-    const dim3 grid(h->small_grid), block(256);
-    { char nm[64]; snprintf(nm, sizeof nm, "k_sweep_small<%d,%d>", h->small_g, STEP); h->last_sweep = nm; }
-    const int ns = (int)(h->seg_hi - h->seg_lo);
-    switch (h->small_g) {
-        case 16: hipLaunchKernelGGL((k_sweep_small<16, STEP>), grid, block, 0, h->stream, a, ns); break;
-        case 32: hipLaunchKernelGGL((k_sweep_small<32, STEP>), grid, block, 0, h->stream, a, ns); break;
-        default: hipLaunchKernelGGL((k_sweep_small<64, STEP>), grid, block, 0, h->stream, a, ns); break;
-    }
+
+// k_sweep_small: G lanes per segment (small_ok: segments of at most 64 cycles)
+template <int G>
+constexpr SweepInst<NodeSweepArgs, int> small_inst() { return {{G, 0}, 256, {k_sweep_small<G, DESC_STEP_CONSTANT>, k_sweep_small<G, DESC_STEP_HYBRID>}}; }
+const SweepInst<NodeSweepArgs, int> SMALL_INSTS[] = {small_inst<16>(), small_inst<32>(), small_inst<64>()};
+SweepShape small_shape(int c) { return {c <= 16 ? 16 : c <= 32 ? 32 : 64, 0}; }      // 16, 32 or 64: each has its entry
+std::string small_prefix(SweepShape sh) { return inst_name("k_sweep_small<%d,", sh.lps); }
+int launch_small(desc_pgd* h, const NodeSweepArgs& a, bool adam) {
+    const auto* k = sweep_inst(SMALL_INSTS, small_shape(h->max_cnt));
+    if (!k) return DESC_ERR_STATE;
+    h->last_sweep = small_prefix(k->sh) + inst_name("%d>", STEP_OF[adam]);
+    hipLaunchKernelGGL(k->kern[adam], dim3(h->small_grid), dim3(k->NT), 0, h->stream, a, (int)(h->seg_hi - h->seg_lo));
+    return DESC_OK;
 }
-void launch_sweep_node_layout(desc_pgd* h, const NodeSweepArgs& a, bool adam, int part = 0) {
-    if (h->small_ok && a.partials == h->d_partials) { if (adam) launch_small<DESC_STEP_HYBRID>(h, a); else launch_small<DESC_STEP_CONSTANT>(h, a); }      // the plain one-rank path only
-    else if (h->band_ok && !adam) launch_band<DESC_STEP_CONSTANT>(h, a, part);
-    else if (adam && band_adam_ok(h)) launch_band<DESC_STEP_HYBRID>(h, a, part);
-    else if (adam) launch_node<DESC_STEP_HYBRID>(h, a);
-    else launch_node<DESC_STEP_CONSTANT>(h, a);
+int launch_sweep_node_layout(desc_pgd* h, const NodeSweepArgs& a, bool adam, int part = 0) {
+    if (h->small_ok && a.partials == h->d_partials) return launch_small(h, a, adam);      // the plain one-rank path only
+    if (adam ? band_adam_ok(h) : h->band_ok) return launch_band(h, a, adam, part);
+    return launch_node(h, a, adam);
 }
 // workgroups (= partial pairs) of the sweep kernel that serves this step kind
 int sweep_parts(const desc_pgd* h, bool adam, bool plain_path = false) {
@@ -2330,29 +2322,37 @@ void launch_colsum(desc_pgd* h, hipStream_t st, const double* w, double* T, cons
                            xpos, fin, h->d_ticket, h->d_node_order, h->d_node_run, h->colsum_long, copies, fx_scale);
 }
 
+// what every sweep on the node layout is given, one rank or sharded; the caller adds Tfull, xt, s_slice, partials, t_bytes, slice_bytes and the step
+NodeSweepArgs node_sweep_args(const desc_pgd* h, int rd, int wr) {
+    NodeSweepArgs a{};
+    a.cum = h->d_cum; a.einfo = h->d_einfo; a.pk = h->d_pk; a.S0 = h->d_S0; a.w_old = h->d_w[rd]; a.w_new = h->d_w[wr];
+    a.S_old = h->d_S[rd]; a.S_new = h->d_S[wr]; a.nv_tab = h->d_nv;
+    a.state = h->d_state; a.chunk_desc = h->d_chunk_desc + h->ch_lo; a.nchunks = h->nchunks; a.max_cnt = h->max_cnt;
+    a.csr_bytes = (uint32_t)(16 * h->m); a.seg_count = (uint32_t)h->m_pos; a.fx_inv = std::ldexp(1.0, -h->colsum_fx_bits);
+    return a;
+}
+
 // enqueue sweep number t (1-based) and its finalize; ev0/ev1 bracket the kernels of the sweep proper
 int enqueue_sweep(desc_pgd* h, int t, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
     const int rd = (t - 1) & 1, wr = t & 1;
     bool adam = false;
     const StepArgs st = make_step(h, &adam, rd, wr);
+    int rc;
     if (ev0) (void)hipEventRecord(ev0, h->stream);
     if (h->variant == VARIANT_NODE) {
         const FinArgs fin = fin_args(h, h->d_partials, h->pending_parts, h->pending_fin, 0);      // the previous sweep's bookkeeping rides on this launch
         launch_colsum(h, h->stream, h->d_w[rd], h->d_T, nullptr, fin);
         h->pending_fin = 0;
-        NodeSweepArgs a{};
-        a.cum = h->d_cum; a.einfo = h->d_einfo; a.pk = h->d_pk; a.S0 = h->d_S0; a.w_old = h->d_w[rd]; a.w_new = h->d_w[wr];
-        a.S_old = h->d_S[rd]; a.S_new = h->d_S[wr]; a.Tfull = h->d_T; a.xt = nullptr; a.nv_tab = h->d_nv; a.partials = h->d_partials;
-        a.state = h->d_state; a.st = st; a.chunk_desc = h->d_chunk_desc + h->ch_lo; a.nchunks = h->nchunks; a.max_cnt = h->max_cnt;
-        a.csr_bytes = (uint32_t)(16 * h->m); a.t_bytes = a.csr_bytes; a.slice_bytes = 0; a.seg_count = (uint32_t)h->m_pos; a.fx_inv = std::ldexp(1.0, -h->colsum_fx_bits);
-        launch_sweep_node_layout(h, a, adam);
+        NodeSweepArgs a = node_sweep_args(h, rd, wr);
+        a.Tfull = h->d_T; a.partials = h->d_partials; a.st = st; a.t_bytes = a.csr_bytes;       // xt, s_slice: NULL, slice_bytes: 0
+        if ((rc = launch_sweep_node_layout(h, a, adam))) return rc;
     } else {
         SweepArgs a{};
         a.cum = h->d_cum; a.pos_edge = h->d_pos_edge; a.e_jk = h->d_ejk; a.e_ki = h->d_eki; a.ikj = h->d_ikj; a.jki = h->d_jki;
         a.S0 = h->d_S0; a.w_old = h->d_w[rd]; a.w_new = h->d_w[wr]; a.S_old = h->d_S[rd]; a.S_new = h->d_S[wr];
         a.nv_tab = h->d_nv; a.partials = h->d_partials; a.state = h->d_state; a.st = st;
         a.m_pos = (int32_t)h->m_pos;
-        if (adam) launch_gather<DESC_STEP_HYBRID>(h, a); else launch_gather<DESC_STEP_CONSTANT>(h, a);
+        if ((rc = launch_gather(h, a, adam))) return rc;
     }
     if (ev1) (void)hipEventRecord(ev1, h->stream);
     h->pending_fin = t; h->pending_parts = sweep_parts(h, adam, true);
@@ -2370,7 +2370,7 @@ int enqueue_iterations(desc_pgd* h, int n) {
 }
 
 int choose_grid(desc_pgd* h) {
-    const int epw = h->G ? 64 / h->G : 1;
+    const int G = gather_shape(h->max_cnt).lps, epw = G ? 64 / G : 1;
     int64_t want = (h->m_pos + 4 * epw - 1) / (4 * epw);
     want = std::min<int64_t>(want, 2048);
     want = std::max<int64_t>(want, 8);
@@ -2390,12 +2390,9 @@ int setup_gather(desc_pgd* h, const desc_problem* prob, const desc_structure* s,
     if ((rc = dalloc(h, &h->d_jki, mc))) return rc;
     if ((rc = dalloc(h, &h->d_S[0], m))) return rc;
     if ((rc = dalloc(h, &h->d_S[1], m))) return rc;
-    h->G = h->max_cnt <= 16 ? 16 : h->max_cnt <= 32 ? 32 : h->max_cnt <= 64 ? 64 : 0;
     choose_grid(h);
     h->obj_grid = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (mc + 255) / 256));
-    char nm[64];
-    if (h->G) snprintf(nm, sizeof nm, "k_sweep<%d,", h->G); else snprintf(nm, sizeof nm, "k_sweep_big<");
-    h->kname = nm;
+    h->kname = gather_prefix(gather_shape(h->max_cnt));
 
     auto t0 = std::chrono::steady_clock::now();
     hvec<int32_t> cum32((size_t)mp + 1);
@@ -2744,15 +2741,11 @@ int setup_node(desc_pgd* h, const desc_problem* prob, const desc_structure* s, c
     h->ms_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     lap("upload");
 
-    // lanes per segment x cycles per lane >= longest segment
-    // (33..64 cycles: 32 lanes x 2 cycles keeps all 8 waves of the workgroup busy in the arithmetic --
-    //  measured 2 % faster than 16 lanes x 4 cycles at C2 and C4)
-    h->lps = h->max_cnt <= 32 ? 16 : h->max_cnt <= 128 ? 32 : 64;
-    h->G = h->max_cnt <= 16 ? 1 : h->max_cnt <= 64 ? 2 : 4;
     {   // persistent grid: exactly the workgroups that are co-resident (registers / LDS decide)
         int per_cu = 0;
-        const void* kfn = (const void*)k_sweep_node<32, 4, DESC_STEP_CONSTANT>;    // the largest-register instance
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, SWEEP_THREADS, 0) != hipSuccess || per_cu < 1) per_cu = 2;
+        const auto* big = sweep_inst(NODE_INSTS, {32, 4});                          // the largest-register instance (constant step)
+        if (!big) return DESC_ERR_STATE;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)big->kern[0], big->NT, 0) != hipSuccess || per_cu < 1) per_cu = 2;
         int64_t want = std::min<int64_t>(std::max(h->nchunks, 1), (int64_t)ncu * per_cu);
         h->grid = (int)(std::max<int64_t>(want, 8) + 7) / 8 * 8;
     }
@@ -2810,18 +2803,18 @@ int setup_node(desc_pgd* h, const desc_problem* prob, const desc_structure* s, c
     }
     if (h->band_ok) {      // the band rows + the nv table in dynamic LDS: more than the 64 KiB default
         h->band_lds = ((size_t)h->band_rows + MAX_SEG_CYCLES + 1) * sizeof(double);
-        for (const void* kb : {band_kernel<DESC_STEP_CONSTANT, false>(h), band_kernel<DESC_STEP_HYBRID, false>(h), band_kernel<DESC_STEP_CONSTANT, true>(h), band_kernel<DESC_STEP_HYBRID, true>(h)})
-            if (kb && hipFuncSetAttribute(kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->band_lds) != hipSuccess) { (void)hipGetLastError(); h->band_ok = false; }
+        for (int adam = 0; adam < (h->max_cnt <= 64 ? 2 : 1); ++adam) {      // every instance this handle can launch (band_adam_ok)
+            const auto* k = band_inst_of(h, adam);
+            if (!k) return DESC_ERR_STATE;
+            for (auto kern : k->kern)
+                if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->band_lds) != hipSuccess) { (void)hipGetLastError(); h->band_ok = false; }
+        }
     }
     // the reference's demo sizes: the latency-lean sweep (DESC_DEBUG_VARIANT = 2 / 3 keep k_sweep_node / the band sweep for the cross-checks)
     h->small_ok = force_band == 0 && !h->band_ok && h->world == 1 && h->max_cnt <= 64 && h->m_cycle < (2 << 20) && env_int("DESC_DEBUG_SMALL", 1) != 0;
-    h->small_g = h->max_cnt <= 16 ? 16 : h->max_cnt <= 32 ? 32 : 64;
-    h->small_grid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (nsl + 4 * (64 / h->small_g) - 1) / (4 * (64 / h->small_g))));
-    char nm[64];
-    if (h->small_ok) snprintf(nm, sizeof nm, "k_sweep_small<%d,", h->small_g);
-    else if (h->band_ok) { const BandShape sh = band_shape(h, false); snprintf(nm, sizeof nm, "k_sweep_band<%d,%d,", sh.lps, sh.E); }
-    else snprintf(nm, sizeof nm, "k_sweep_node<%d,%d,", h->lps, h->G);
-    h->kname = nm;
+    const SweepShape small = small_shape(h->max_cnt);
+    h->small_grid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (nsl + 4 * (64 / small.lps) - 1) / (4 * (64 / small.lps))));
+    h->kname = h->small_ok ? small_prefix(small) : h->band_ok ? band_prefix(band_shape(h, false)) : node_prefix(node_shape(h->max_cnt));
 
     lap("occupancy/attrs");
     hipEvent_t e0, e1;
@@ -3114,22 +3107,26 @@ int desc_pgd_reset(desc_pgd* h, const desc_params* p) {
     return DESC_OK;
 }
 
-int desc_pgd_iterate(desc_pgd* h, int32_t n_iters) {
+namespace {
+int shard_unpack_pending(desc_pgd* h);
+// what desc_pgd_iterate and desc_pgd_iterate_timed refuse; then the handle's device is current
+int iterate_begin(const desc_pgd* h, int32_t n_iters) {
     if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
     if (!h->armed) return fail(DESC_ERR_STATE, "desc_pgd_reset must be called first");
     if (h->ext_phase) return fail(DESC_ERR_STATE, "the handle runs a caller-supplied step rule (desc_pgd_ext_begin): iterate with desc_pgd_ext_grad / desc_pgd_ext_apply");
     if (n_iters < 0 || h->t_done + n_iters > h->iters_cap) return fail(DESC_ERR_INVALID, "iterating past params.iters = %d", h->p.iters);
-    int rc = set_device(h); if (rc) return rc;
+    return set_device(h);
+}
+}  // namespace
+
+int desc_pgd_iterate(desc_pgd* h, int32_t n_iters) {
+    int rc = iterate_begin(h, n_iters); if (rc) return rc;
     if (h->m_pos == 0) { h->t_done += n_iters; h->t_plugin += n_iters; return DESC_OK; }
     return enqueue_iterations(h, n_iters);
 }
 
 int desc_pgd_iterate_timed(desc_pgd* h, int32_t n_iters, float* ms_total, float* ms_main_kernel_avg) {
-    if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
-    if (!h->armed) return fail(DESC_ERR_STATE, "desc_pgd_reset must be called first");
-    if (h->ext_phase) return fail(DESC_ERR_STATE, "the handle runs a caller-supplied step rule (desc_pgd_ext_begin): iterate with desc_pgd_ext_grad / desc_pgd_ext_apply");
-    if (n_iters < 0 || h->t_done + n_iters > h->iters_cap) return fail(DESC_ERR_INVALID, "iterating past params.iters = %d", h->p.iters);
-    int rc = set_device(h); if (rc) return rc;
+    int rc = iterate_begin(h, n_iters); if (rc) return rc;
     hipEvent_t e0, e1;
     DESC_HIP(hipEventCreate(&e0)); DESC_HIP(hipEventCreate(&e1));
     hvec<hipEvent_t> ev;
@@ -3158,8 +3155,6 @@ int desc_pgd_iterate_timed(desc_pgd* h, int32_t n_iters, float* ms_total, float*
     return DESC_OK;
 }
 
-namespace { int shard_unpack_pending(desc_pgd* h); }
-
 int desc_pgd_sync(desc_pgd* h) {
     if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
     int rc = set_device(h); if (rc) return rc;
@@ -3169,8 +3164,6 @@ int desc_pgd_sync(desc_pgd* h) {
     DESC_HIP(hipGetLastError());
     return DESC_OK;
 }
-
-namespace { int shard_unpack_pending(desc_pgd* h); }
 
 int desc_pgd_download(desc_pgd* h, desc_result* r) {
     if (!h || !r) return fail(DESC_ERR_INVALID, "NULL argument");
@@ -3400,21 +3393,18 @@ int shard_enqueue_sweep(desc_pgd* h, hipStream_t st, int part_lo = 0, int part_h
     const bool by_parts = adam ? band_adam_ok(h) : h->band_ok;
     for (int c = part_lo; c < part_hi; ++c) {
         if (!by_parts && c > 0) break;
-        NodeSweepArgs a{};
-        a.cum = h->d_cum; a.einfo = h->d_einfo; a.pk = h->d_pk; a.S0 = h->d_S0; a.w_old = h->d_w[rd]; a.w_new = h->d_w[wr];
-        a.S_old = h->d_S[rd]; a.S_new = h->d_S[wr]; a.xt = h->d_xt; a.nv_tab = h->d_nv;
+        NodeSweepArgs a = node_sweep_args(h, rd, wr);
+        a.st = h->cur_step; a.xt = h->d_xt;
         a.Tfull = h->x_Trecv + (int64_t)c * h->t_part;
         // S and the workgroup partials go straight into the slice: the part's S behind the parts before it, its partials in its share of the partial area
         a.s_slice = my_slice(h) + h->xslice_off[c];
         a.partials = my_slice(h) + h->slice_S + 2 * (int64_t)c * (SHARD_PARTS / h->xparts);
-        a.csr_bytes = (uint32_t)(16 * h->m); a.t_bytes = (uint32_t)(8 * h->t_part); a.slice_bytes = (uint32_t)(8 * (h->slice_S - h->xslice_off[c]));
-        a.seg_count = (uint32_t)h->m_pos; a.fx_inv = std::ldexp(1.0, -h->colsum_fx_bits);
+        a.t_bytes = (uint32_t)(8 * h->t_part); a.slice_bytes = (uint32_t)(8 * (h->slice_S - h->xslice_off[c]));
         if (shard_direct(h)) { a.Tfull = h->d_T; a.xt = nullptr; a.s_slice = nullptr; a.t_bytes = a.csr_bytes; }
-        a.state = h->d_state; a.st = h->cur_step; a.chunk_desc = h->d_chunk_desc + h->ch_lo; a.nchunks = h->nchunks;
-        a.max_cnt = h->max_cnt;
         const hipStream_t keep = h->stream; h->stream = st;
-        launch_sweep_node_layout(h, a, adam, c);
+        const int rc = launch_sweep_node_layout(h, a, adam, c);
         h->stream = keep;
+        if (rc) return rc;
     }
     h->last_parts = sweep_parts(h, adam);
     DESC_HIP(hipGetLastError());

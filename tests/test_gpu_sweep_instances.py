@@ -145,13 +145,9 @@ def _reference(O, T, step):
 
 
 # ------------------------------------------------------------------------------------------------------------------ CPU guard
-def _body(src, head):
-    a = src.index(head)
-    return src[a:src.index("\n}\n", a)]
-
-
 def _instances():
-    """Every sweep instance the dispatch of pgd.hip can launch, named as desc_debug_last_sweep names them."""
+    """Every sweep instance the dispatch of pgd.hip can launch, named as desc_debug_last_sweep names them: the entries <family>_inst<...>()
+    of the instance tables, each standing for its two step kinds (band sweep: for one rank and XT)."""
     with open(os.path.join(ROOT, "desc_amd", "csrc", "pgd.hip")) as f:
         src = f.read()
     steps = {"DESC_STEP_CONSTANT": 0, "DESC_STEP_HYBRID": 2}
@@ -159,31 +155,28 @@ def _instances():
         hdr = f.read()
     for k, v in steps.items():
         assert re.search(r"#define\s+%s\s+%d\b" % (k, v), hdr), k
-    # the step kinds every launcher is instantiated with
-    used = set(re.findall(r"launch_(?:gather|node|small|band)<(DESC_STEP_\w+)>", src))
-    assert used == set(steps), used
-    launched = re.compile(r"hipLaunchKernelGGL\(\((k_sweep\w*)<([^>]*)>\)")
+    code = [ln.split("//")[0] for ln in src.splitlines()]
+    host = code[code.index("struct desc_pgd {"):]
+    # a sweep kernel is named only where an entry is made, and launched only through an entry's pointer
+    naming = [ln for ln in host if re.search(r"\bk_sweep(_node|_small|_band|_big)?<[^%\"]", ln)]          # ("k_sweep<%d,": a name's format)
+    assert len(naming) == 5 and all(re.search(r"^constexpr SweepInst<.*> \w+_inst\(\) \{ return ", ln) for ln in naming), naming
+    assert not [ln for ln in code if re.search(r"hipLaunchKernelGGL\(\(*k_sweep", ln)]
+    entries = re.findall(r"\b(gather|big|small|node|band)_inst(?:<([^>]*)>)?\(\)(?! \{)", "\n".join(host))
+    assert len(entries) == len(set(entries)), entries          # every argument tuple in exactly one table entry
     names = set()
-    for head, kinds in (("void launch_gather(", ("",)), ("void launch_small(", ("",)), ("void launch_node(", ("", " sharded"))):
-        found = launched.findall(_body(src, head))
-        assert found, head
-        for kern, args in found:
-            args = [a.strip() for a in args.split(",")]
-            for s in steps.values():
-                for suffix in kinds:
-                    names.add("%s<%s>%s" % (kern, ",".join(str(s) if a == "STEP" else a for a in args), suffix))
-    band = _body(src, "const void* band_kernel(")
-    adam_part, const_part = band.split("} else {")
-    for part, s in ((adam_part, 2), (const_part, 0)):
-        found = re.findall(r"return \(const void\*\)k_sweep_band<(\d+), (\d+), STEP, (\d+), XT>", part)
-        assert found
-        for lps, e, nt in found:
-            for xt in ("one-rank", "XT"):
-                names.add("k_sweep_band<%s,%s,%d,%s,%s>" % (lps, e, s, nt, xt))
-    # launch_band must dispatch the same shapes band_kernel reports (its 1024-thread instance included)
-    shapes = set(re.findall(r"launch_band_shape<(\d+), (\d+), STEP, (\d+)>", _body(src, "void launch_band(")))
-    kshapes = set(re.findall(r"k_sweep_band<(\d+), (\d+), STEP, (\d+), XT>", band))
-    assert shapes == kshapes, (shapes, kshapes)
+    for family, args in entries:
+        a = [str(steps.get(x.strip(), x.strip())) for x in args.split(",")]
+        for s in steps.values():
+            if family == "gather":
+                names.add("k_sweep<%s,%d>" % (a[0], s))
+            elif family == "big":
+                names.add("k_sweep_big<%d>" % s)
+            elif family == "small":
+                names.add("k_sweep_small<%s,%d>" % (a[0], s))
+            elif family == "node":
+                names.update("k_sweep_node<%s,%s,%d>%s" % (a[0], a[1], s, suffix) for suffix in ("", " sharded"))
+        if family == "band":
+            names.update("k_sweep_band<%s,%s,%s,%s,%s>" % (*a, xt) for xt in ("one-rank", "XT"))
     return names
 
 
