@@ -48,6 +48,9 @@ EXPORTS = [
     "desc_test_laa_r2q", "desc_test_laa_q2r", "desc_test_laa_edge_log", "desc_test_laa_rhs", "desc_test_laa_pcg", "desc_test_laa_node_update",
     "desc_test_irls_node_update", "desc_test_laa_weights", "desc_test_irls_weights", "desc_test_laa_quantile", "desc_test_irls_project",
     "desc_test_irls_pd_stage", "desc_test_irls_pd_solve",
+    "desc_test_spectral_weights", "desc_test_spectral_row_wsum", "desc_test_spectral_assemble", "desc_test_spectral_spmm", "desc_test_spectral_gram",
+    "desc_test_spectral_residual", "desc_test_spectral_combine", "desc_test_small_jacobi", "desc_test_small_ortho", "desc_test_small_project",
+    "desc_test_small_ritz_tail",
 ]
 
 I32P = C.POINTER(C.c_int32)
@@ -384,6 +387,17 @@ def load():
     L.desc_test_irls_project.argtypes = [F64P, I32P, C.c_int64, C.c_int64, C.c_int32, F64P, I32P, I32P, F64P]
     L.desc_test_irls_pd_stage.argtypes = [C.c_void_p, C.c_int32, F64P, F64P, F64P, I32P, C.c_int64, C.c_int64, F64P, F64P, F64P]
     L.desc_test_irls_pd_solve.argtypes = [C.c_void_p, F64P, C.c_int64, C.c_int64, C.c_int32, F64P, F64P, I32P, F64P, C.c_int32, I32P]
+    L.desc_test_spectral_weights.argtypes = [F64P, C.c_int64, C.c_int32, F64P]
+    L.desc_test_spectral_row_wsum.argtypes = [C.c_void_p, F64P, C.c_int64, C.c_int32, F64P]
+    L.desc_test_spectral_assemble.argtypes = [C.c_void_p, F64P, F64P, C.c_int64, C.c_int32, F64P]
+    L.desc_test_spectral_spmm.argtypes = [C.c_void_p, F64P, F64P, F64P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, F64P]
+    L.desc_test_spectral_gram.argtypes = [F64P, F64P, C.c_int64, C.c_int32, C.c_int32, F64P, F64P]
+    L.desc_test_spectral_residual.argtypes = [F64P, F64P, C.c_int64, F64P, F64P, C.c_int32, C.c_int32, F64P]
+    L.desc_test_spectral_combine.argtypes = [F64P, C.c_int64, F64P, C.c_int32, C.c_int32, F64P]
+    L.desc_test_small_jacobi.argtypes = [C.c_int32, F64P, F64P, F64P]
+    L.desc_test_small_ortho.argtypes = [F64P, F64P, F64P, I32P]
+    L.desc_test_small_project.argtypes = [F64P, C.c_int64, F64P]
+    L.desc_test_small_ritz_tail.argtypes = [F64P, F64P, C.c_int64, F64P]
     _lib = L
     return L
 
@@ -1683,3 +1697,105 @@ def hook_pd_solve(dprob: DeviceProblem, B, pdmaxiter):
     out.update(zip(("steps", "ill", "stuck", "solves", "cg_total", "cg_unconverged"), (int(v) for v in cnt[:6])))
     out["trace"] = tr[:24 * int(tl[0])].reshape(-1, 3, 8).copy()
     return out
+
+
+# ---- test hooks into the Spectral / GCW eigen-solve (desc_test_spectral_* / desc_test_small_*, include/desc_amd.h).  Used by
+# tests/test_gpu_spectral_kernels.py and tests/test_spectral_host.py only.  grid = 0: the product path's grid rule.
+SPECTRAL_BW = 6          # spectral.hip's BW: columns of the iterated block
+
+
+def hook_spectral_weights(S, device=0):
+    S = _f64(S); m = S.size
+    w = out_buffer(m)
+    check(load().desc_test_spectral_weights(ptr(S, F64P), m, device, ptr(w, F64P)))
+    return w[:m].copy()
+
+
+def hook_spectral_row_wsum(dprob: DeviceProblem, w=None, grid=0):
+    w = None if w is None else _f64(w, dprob.m)
+    deg = out_buffer(dprob.n)
+    check(load().desc_test_spectral_row_wsum(dprob.handle, ptr(w, F64P), dprob.m, int(grid), ptr(deg, F64P)))
+    return deg[:dprob.n].copy()
+
+
+def hook_spectral_assemble(dprob: DeviceProblem, w=None, dinv=None, grid=0):
+    """-> (9, 2m): component q = r + 3k of CSR slot t at [q, t], as the library stores the blocks."""
+    m = dprob.m
+    w = None if w is None else _f64(w, m)
+    dinv = None if dinv is None else _f64(dinv, dprob.n)
+    blocks = out_buffer(18 * m)
+    check(load().desc_test_spectral_assemble(dprob.handle, ptr(w, F64P), ptr(dinv, F64P), m, int(grid), ptr(blocks, F64P)))
+    return blocks[:18 * m].reshape(9, 2 * m).copy()
+
+
+def hook_spectral_spmm(dprob: DeviceProblem, blocks, x, z, alpha, s1, s2, z_is_y=False, form=0, grid=0):
+    """y = alpha A x + s1 x + s2 z -> (3n, 6); blocks as hook_spectral_assemble returns them."""
+    rows = 3 * dprob.n
+    blocks, x, z = _f64(blocks, 18 * dprob.m), _f64(x, rows * SPECTRAL_BW), _f64(z, rows * SPECTRAL_BW)
+    if blocks.size == 0:
+        blocks = np.zeros(1)
+    y = out_buffer(rows * SPECTRAL_BW)
+    check(load().desc_test_spectral_spmm(dprob.handle, ptr(blocks, F64P), ptr(x, F64P), ptr(z, F64P), int(bool(z_is_y)), int(form), int(grid),
+                                         float(alpha), float(s1), float(s2), ptr(y, F64P)))
+    return y[:rows * SPECTRAL_BW].reshape(rows, SPECTRAL_BW).copy()
+
+
+def hook_spectral_gram(X, Y, grid=0, device=0):
+    """-> (X'Y, Y'Y), 6 x 6 each."""
+    X = _f64(X); rows = X.size // SPECTRAL_BW
+    Y = _f64(Y, X.size)
+    G1, G2 = out_buffer(36), out_buffer(36)
+    check(load().desc_test_spectral_gram(ptr(X, F64P), ptr(Y, F64P), rows, int(grid), device, ptr(G1, F64P), ptr(G2, F64P)))
+    return G1[:36].reshape(6, 6).copy(), G2[:36].reshape(6, 6).copy()
+
+
+def hook_spectral_residual(X, Y, Z3, theta, grid=0, device=0):
+    """-> r2 (3,): |Y z_c - theta_c X z_c|^2 for the columns z_c of Z3 (6 x 3)."""
+    X = _f64(X); rows = X.size // SPECTRAL_BW
+    Y, Z3, theta = _f64(Y, X.size), _f64(Z3, 18), _f64(theta, 3)
+    r2 = out_buffer(3)
+    check(load().desc_test_spectral_residual(ptr(X, F64P), ptr(Y, F64P), rows, ptr(Z3, F64P), ptr(theta, F64P), int(grid), device, ptr(r2, F64P)))
+    return r2[:3].copy()
+
+
+def hook_spectral_combine(Y, Cm, grid=0, device=0):
+    Y = _f64(Y); rows = Y.size // SPECTRAL_BW
+    Cm = _f64(Cm, 36)
+    Xn = out_buffer(Y.size)
+    check(load().desc_test_spectral_combine(ptr(Y, F64P), rows, ptr(Cm, F64P), int(grid), device, ptr(Xn, F64P)))
+    return Xn[:Y.size].reshape(rows, SPECTRAL_BW).copy()
+
+
+def hook_small_jacobi(A):
+    """-> (w descending, V with the eigenvectors in its columns)."""
+    A = np.asarray(A, dtype=np.float64); N = A.shape[0]
+    a = _f64(A, N * N)
+    w, V = out_buffer(N), out_buffer(N * N)
+    check(load().desc_test_small_jacobi(N, ptr(a, F64P), ptr(w, F64P), ptr(V, F64P)))
+    return w[:N].copy(), V[:N * N].reshape(N, N).copy()
+
+
+def hook_small_ortho(G, Z=None):
+    """-> (ok, C 6 x 6)."""
+    G = _f64(G, 36)
+    Z = None if Z is None else _f64(Z, 36)
+    Cm, ok = out_buffer(36), out_buffer(1, np.int32)
+    check(load().desc_test_small_ortho(ptr(G, F64P), ptr(Z, F64P), ptr(Cm, F64P), ptr(ok, I32P)))
+    return bool(ok[0]), Cm[:36].reshape(6, 6).copy()
+
+
+def hook_small_project(M):
+    """M: (count, 3, 3) -> their projections onto SO(3), (count, 3, 3)."""
+    M = _f64(M); count = M.size // 9
+    R = out_buffer(9 * count)
+    check(load().desc_test_small_project(ptr(M, F64P), count, ptr(R, F64P)))
+    return R[:9 * count].reshape(count, 3, 3).copy()
+
+
+def hook_small_ritz_tail(V, dinv=None):
+    """V: (3n, 3) -> R (3, 3, n) Fortran-ordered."""
+    V = _f64(V); n = V.size // 9
+    dinv = None if dinv is None else _f64(dinv, n)
+    R = out_buffer(9 * n)
+    check(load().desc_test_small_ritz_tail(ptr(V, F64P), ptr(dinv, F64P), n, ptr(R, F64P)))
+    return R[:9 * n].reshape((3, 3, n), order="F").copy()

@@ -63,40 +63,69 @@ __host__ __device__ inline bool ortho_coeffs(const double* G, const double* Z, d
     return true;
 }
 
-// R = U*diag(1,1,det(U*V'))*V' for the 3x3 block M (row-major)  (Spectral.m:43-45); host only
+// R = U*diag(1,1,det(U*V'))*V' for the 3x3 block M (row-major)  (Spectral.m:43-45); host only.
+// One-sided (Hestenes) Jacobi SVD of M itself: column rotations make the columns of G = M V orthogonal, their norms are the singular
+// values.  M'M is never formed, so a small singular value is not lost under the square of the largest (U = M v / sqrt(eig(M'M)) left
+// RR' - I at eps * cond(M)^2 and never saw a rank-deficient block as one).  The third left vector does not need sigma_3:
+// R = u1 v1' + u2 v2' + det(V) (u1 x u2) v3', with u2 re-orthogonalised against u1; a block of rank 1 gets a u2 completed from the
+// coordinate axis farthest from u1, the zero block the identity (svd(0): U = V = I).
 inline void project_so3(const double* M, double* R) {
-    // eigen-decomposition of M'M gives V and the singular values; U = M V / sigma
-    double MtM[9], w[3], V[9];
-    for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) { double s = 0; for (int k = 0; k < 3; ++k) s += M[k * 3 + a] * M[k * 3 + b]; MtM[a * 3 + b] = s; }
-    jacobi_eig<3>(MtM, w, V);
-    double U[9];
-    const double s0 = std::sqrt(std::max(w[0], 0.0));
-    int good = 0;
+    double big = 0.0;
+    for (int t = 0; t < 9; ++t) big = std::max(big, std::fabs(M[t]));
+    if (!(big > 0.0)) { for (int t = 0; t < 9; ++t) R[t] = (t % 4 == 0); return; }
+    int ex = 0;
+    (void)std::frexp(big, &ex);                                   // entries scaled by a power of two into [-1, 1]: no overflow at 1e+-100
+    double G[3][3], V[3][3];
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) { G[r][c] = std::ldexp(M[r * 3 + c], -ex); V[r][c] = r == c; }
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        bool rotated = false;
+        for (int p = 0; p < 3; ++p)
+            for (int q = p + 1; q < 3; ++q) {
+                double al = 0, be = 0, ga = 0;
+                for (int k = 0; k < 3; ++k) { al += G[k][p] * G[k][p]; be += G[k][q] * G[k][q]; ga += G[k][p] * G[k][q]; }
+                if (!(std::fabs(ga) > 1.1102230246251565e-16 * std::sqrt(al) * std::sqrt(be))) continue;
+                rotated = true;
+                const double zeta = (be - al) / (2.0 * ga);
+                const double t = (zeta >= 0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(zeta * zeta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < 3; ++k) {
+                    const double gp = G[k][p], gq = G[k][q]; G[k][p] = c * gp - s * gq; G[k][q] = s * gp + c * gq;
+                    const double vp = V[k][p], vq = V[k][q]; V[k][p] = c * vp - s * vq; V[k][q] = s * vp + c * vq;
+                }
+            }
+        if (!rotated) break;
+    }
+    double sv[3];
+    for (int c = 0; c < 3; ++c) sv[c] = std::sqrt(G[0][c] * G[0][c] + G[1][c] * G[1][c] + G[2][c] * G[2][c]);
+    int idx[3];                                                   // descending, equal values keep their index order
+    for (int i = 0; i < 3; ++i) { int j = i; for (; j > 0 && sv[i] > sv[idx[j - 1]]; --j) idx[j] = idx[j - 1]; idx[j] = i; }
+    auto unit = [](double* a) { const double nr = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); for (int k = 0; k < 3; ++k) a[k] /= nr; return nr; };
+    double u1[3], u2[3], u3[3], v[3][3];                          // v[c]: right vector c
     for (int c = 0; c < 3; ++c) {
-        const double sc = std::sqrt(std::max(w[c], 0.0));
-        if (sc > 1e-12 * std::max(s0, 1e-300) && sc > 1e-300) {
-            for (int r = 0; r < 3; ++r) { double s = 0; for (int k = 0; k < 3; ++k) s += M[r * 3 + k] * V[k * 3 + c]; U[r * 3 + c] = s / sc; }
-            good = c + 1;
-        } else break;
+        for (int k = 0; k < 3; ++k) v[c][k] = V[k][idx[c]];
+        unit(v[c]);                                               // the accumulated rotations leave a few eps
     }
-    if (good == 0) { for (int i = 0; i < 9; ++i) { U[i] = (i % 4 == 0); V[i] = (i % 4 == 0); } good = 3; }   // svd(0): U = V = I
-    if (good == 1) {      // complete an orthonormal basis
-        double a[3] = {U[0], U[3], U[6]}; int k = std::fabs(a[0]) < std::fabs(a[1]) ? (std::fabs(a[0]) < std::fabs(a[2]) ? 0 : 2) : (std::fabs(a[1]) < std::fabs(a[2]) ? 1 : 2);
+    for (int k = 0; k < 3; ++k) { u1[k] = G[k][idx[0]]; u2[k] = G[k][idx[1]]; }
+    unit(u1);
+    bool have2 = sv[idx[1]] > 0.0;
+    if (have2) {
+        unit(u2);
+        const double d = u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2];
+        for (int k = 0; k < 3; ++k) u2[k] -= d * u1[k];
+        have2 = unit(u2) > 0.5;
+    }
+    if (!have2) {                                                 // rank 1: complete an orthonormal basis
+        const int k = std::fabs(u1[0]) < std::fabs(u1[1]) ? (std::fabs(u1[0]) < std::fabs(u1[2]) ? 0 : 2) : (std::fabs(u1[1]) < std::fabs(u1[2]) ? 1 : 2);
         double e[3] = {0, 0, 0}; e[k] = 1;
-        double b[3] = {a[1] * e[2] - a[2] * e[1], a[2] * e[0] - a[0] * e[2], a[0] * e[1] - a[1] * e[0]};
-        const double nb = std::sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
-        for (int r = 0; r < 3; ++r) U[r * 3 + 1] = b[r] / nb;
-        good = 2;
+        u2[0] = u1[1] * e[2] - u1[2] * e[1]; u2[1] = u1[2] * e[0] - u1[0] * e[2]; u2[2] = u1[0] * e[1] - u1[1] * e[0];
+        unit(u2);
     }
-    if (good == 2) {
-        const double a[3] = {U[0], U[3], U[6]}, b[3] = {U[1], U[4], U[7]};
-        U[2] = a[1] * b[2] - a[2] * b[1]; U[5] = a[2] * b[0] - a[0] * b[2]; U[8] = a[0] * b[1] - a[1] * b[0];
-    }
-    auto det3 = [](const double* A) { return A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6]) + A[2] * (A[3] * A[7] - A[4] * A[6]); };
-    double UVt[9];
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) { double s = 0; for (int k = 0; k < 3; ++k) s += U[r * 3 + k] * V[c * 3 + k]; UVt[r * 3 + c] = s; }
-    const double d = det3(UVt) < 0 ? -1.0 : 1.0;
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) R[r * 3 + c] = U[r * 3 + 0] * V[c * 3 + 0] + U[r * 3 + 1] * V[c * 3 + 1] + d * U[r * 3 + 2] * V[c * 3 + 2];
+    u3[0] = u1[1] * u2[2] - u1[2] * u2[1]; u3[1] = u1[2] * u2[0] - u1[0] * u2[2]; u3[2] = u1[0] * u2[1] - u1[1] * u2[0];
+    unit(u3);
+    const double detV = v[0][0] * (v[1][1] * v[2][2] - v[1][2] * v[2][1]) - v[0][1] * (v[1][0] * v[2][2] - v[1][2] * v[2][0]) +
+                        v[0][2] * (v[1][0] * v[2][1] - v[1][1] * v[2][0]);
+    const double d = detV < 0 ? -1.0 : 1.0;
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) R[r * 3 + c] = u1[r] * v[0][c] + u2[r] * v[1][c] + d * u3[r] * v[2][c];
 }
 
 // The tail of the eigen-solve for one problem on the host, the arithmetic of spectral.hip's (Spectral.m:39-46 / GCW.m:21,27-36).

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "device_utils.h"
+#include "laa.h"
 #include "small_dense.h"
 
 namespace desc {
@@ -281,6 +282,86 @@ __global__ void k_combine(const double* Y, double* Xn, int64_t rows, SmallMat C)
 
 // the small dense helpers (jacobi_eig, ortho_coeffs, project_so3) live in small_dense.h, shared with gcw_batch.hip
 
+// ---- launches of the product path, with its grid rules.  spectral_impl passes grid = 0; the test hooks (desc_test_spectral_*) may
+// force one, so that the stride loops turn at small sizes.
+constexpr int GGRID = 256;          // workgroups of k_gram / k_residual; the host adds that many partial sums
+constexpr int COMBINE_GRID = 512;
+constexpr int HOOK_GRID_MAX = 65535;
+inline int weights_grid(int64_t m) { return (int)std::min<int64_t>(2048, (m + 255) / 256); }
+inline int row_wsum_grid(int64_t n) { return grid_for(n * 16, 2048); }
+inline int assemble_grid(int64_t n) { return (int)std::min<int64_t>(4096, (n + 3) / 4); }
+inline bool wide_rows_rule(int64_t n, int64_t m) {
+    const bool wide_rows = 2 * m >= 192 * n;                   // average row of >= 192 slots: a workgroup per row, else a wave
+    return wide_rows;
+}
+inline int spmm_grid(bool wide, int64_t n) { return (int)std::min<int64_t>(8192, wide ? n : (n + 3) / 4); }
+
+void launch_weights(const double* d_s, double* d_w, int64_t m, int grid) {
+    if (m) hipLaunchKernelGGL(k_gcw_weights, dim3((unsigned)(grid ? grid : weights_grid(m))), dim3(256), 0, 0, d_s, d_w, m);
+}
+void launch_row_wsum(const desc_device_problem* dp, const double* d_w, double* d_deg, int grid) {
+    hipLaunchKernelGGL(k_row_wsum, dim3(grid ? grid : row_wsum_grid(dp->n)), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj_eid, d_w, d_deg, (int)dp->n);
+}
+void launch_assemble(const desc_device_problem* dp, const double* d_w, const double* d_dinv, double* d_blocks, int grid) {
+    hipLaunchKernelGGL(k_assemble_blocks, dim3((unsigned)(grid ? grid : assemble_grid(dp->n))), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj, dp->d_adj_eid,
+                       dp->d_rij, d_w, d_dinv, d_blocks, (int64_t)2 * dp->m, (int)dp->n);
+}
+// y = alpha A x + s1 x + s2 z with A = the assembled blocks of dp; wide: k_bsr_spmm<256>, else <64>
+void launch_spmm(const desc_device_problem* dp, const double* d_blocks, bool wide, int grid, const double* x, const double* z, double* y, double alpha,
+                 double s1, double s2) {
+    const int g = grid ? grid : spmm_grid(wide, dp->n);
+    if (wide) hipLaunchKernelGGL(k_bsr_spmm<256>, dim3(g), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj, d_blocks, (int64_t)2 * dp->m, x, z, y, (int)dp->n, alpha, s1, s2);
+    else hipLaunchKernelGGL(k_bsr_spmm<64>, dim3(g), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj, d_blocks, (int64_t)2 * dp->m, x, z, y, (int)dp->n, alpha, s1, s2);
+}
+void launch_spmm_mfma(const desc_device_problem* dp, const double* d_blocks, int grid, const double* x, const double* z, double* y, double alpha,
+                      double s1, double s2) {
+    hipLaunchKernelGGL(k_bsr_spmm_mfma, dim3((unsigned)(grid ? grid : std::min<int64_t>(8192, dp->n))), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj, d_blocks,
+                       (int64_t)2 * dp->m, x, z, y, (int)dp->n, alpha, s1, s2);
+}
+void launch_combine(const double* Y, double* Xn, int64_t rows, const SmallMat& C, int grid) {
+    hipLaunchKernelGGL(k_combine, dim3(grid ? grid : COMBINE_GRID), dim3(256), 0, 0, Y, Xn, rows, C);
+}
+// G1 = A'B, G2 = B'B (BW x BW row-major): k_gram's partials per workgroup (d_part: grid * 2 BW^2 doubles), added on the host in index order
+int gram_sums(const double* A, const double* B, int64_t rows, int grid, double* d_part, hvec<double>& part, double* G1, double* G2) {
+    const int g = grid ? grid : GGRID;
+    hipLaunchKernelGGL(k_gram, dim3(g), dim3(256), 0, 0, A, B, rows, d_part);
+    DESC_HIP(hipMemcpy(part.data(), d_part, sizeof(double) * (size_t)g * 2 * BW * BW, hipMemcpyDeviceToHost));
+    for (int t = 0; t < BW * BW; ++t) { double s1 = 0, s2 = 0; for (int b = 0; b < g; ++b) { s1 += part[(size_t)b * 2 * BW * BW + t]; s2 += part[(size_t)b * 2 * BW * BW + BW * BW + t]; } G1[t] = s1; G2[t] = s2; }
+    return DESC_OK;
+}
+// r2[c] = |Y z_c - theta_c X z_c|^2 of the three wanted Ritz pairs: k_residual's partials (d_part: grid * 3 doubles) added on the host
+int residual_sums(const double* X, const double* Y, int64_t rows, int grid, const ResArgs& ra, double* d_part, hvec<double>& part, double* r2) {
+    const int g = grid ? grid : GGRID;
+    hipLaunchKernelGGL(k_residual, dim3(g), dim3(256), 0, 0, X, Y, rows, ra, d_part);
+    DESC_HIP(hipMemcpy(part.data(), d_part, sizeof(double) * 3 * g, hipMemcpyDeviceToHost));
+    for (int c = 0; c < 3; ++c) { double s = 0; for (int bb = 0; bb < g; ++bb) s += part[(size_t)3 * bb + c]; r2[c] = s; }
+    return DESC_OK;
+}
+// operand layout of v_mfma_f64_4x4x4: the unit-vector probes must show exactly the layout k_bsr_spmm_mfma is written for --
+// A's lane (x, y, r) reaches D's lanes (*, y, x), B's lane (x, y, r) reaches D's lanes (x, y, *), with lane = 16 r + 4 y + x,
+// and an A lane meets a B lane iff they share the tile y and the summation index r
+int mfma_layout_probe(DevArena& D, int& lay_ok) {
+    int rc;
+    lay_ok = 1;
+    unsigned long long* d_rm; unsigned long long* d_cm; unsigned char* d_cp;
+    if ((rc = D.alloc(&d_rm, 64)) || (rc = D.alloc(&d_cm, 64)) || (rc = D.alloc(&d_cp, 4096))) return rc;
+    hipLaunchKernelGGL(k_mfma_layout_probe, dim3(1), dim3(64), 0, 0, d_rm, d_cm, d_cp);
+    unsigned long long rm[64], cm[64]; unsigned char cp[4096];
+    DESC_HIP(hipMemcpy(rm, d_rm, sizeof rm, hipMemcpyDeviceToHost));
+    DESC_HIP(hipMemcpy(cm, d_cm, sizeof cm, hipMemcpyDeviceToHost));
+    DESC_HIP(hipMemcpy(cp, d_cp, sizeof cp, hipMemcpyDeviceToHost));
+    if (std::getenv("DESC_DEBUG_TIMING"))                  // diagnostics: the raw footprints
+        for (int q = 0; q < 64; ++q) fprintf(stderr, "[desc_amd] mfma probe lane %2d: A -> D %016llx   B -> D %016llx\n", q, rm[q], cm[q]);
+    for (int l = 0; l < 64; ++l) {
+        const int lx = l & 3, ly = (l >> 2) & 3;
+        if (rm[l] != 0xFull << (16 * lx + 4 * ly)) lay_ok = 0;
+        if (cm[l] != 0x0001000100010001ull << (4 * ly + lx)) lay_ok = 0;
+        for (int l2 = 0; l2 < 64; ++l2)
+            if ((cp[l * 64 + l2] != 0) != (((l >> 2) & 3) == ((l2 >> 2) & 3) && (l >> 4) == (l2 >> 4))) lay_ok = 0;
+    }
+    return DESC_OK;
+}
+
 }  // namespace
 }  // namespace desc
 
@@ -320,6 +401,13 @@ static int spectral_impl(const desc_device_problem* dp, const double* weights, c
     int rc = DESC_OK;
     const int64_t n = dp->n, m = dp->m;
     if (n == 0) return DESC_OK;
+    if (n == 1) {
+        // one node has no edges: the matrix is the 3 x 3 zero, and the 3 x 6 start block cannot have full rank (what its Cholesky made of it
+        // depended on rounding).  Every rotation is a solution; the answer is the identity, with no product taken.
+        for (int t = 0; t < 9; ++t) R_out[t] = (t % 4 == 0);
+        if (info) { *info = desc_spectral_info{}; info->converged = 1; }
+        return DESC_OK;
+    }
     DESC_HIP(hipSetDevice(dp->device));
     auto t0 = std::chrono::steady_clock::now();
     auto t_lap = t0;
@@ -345,9 +433,8 @@ static int spectral_impl(const desc_device_problem* dp, const double* weights, c
         DevArena Tmp;
         if ((rc = W.alloc(&d_w, m)) || (rc = Tmp.alloc(&d_s, m)) || (rc = Tmp.alloc(&d_deg, n))) return rc;
         if (m) DESC_HIP(hipMemcpy(d_s, gcw_svec, sizeof(double) * m, hipMemcpyHostToDevice));
-        if (m) hipLaunchKernelGGL(k_gcw_weights, dim3((unsigned)std::min<int64_t>(2048, (m + 255) / 256)), dim3(256), 0, 0, d_s, d_w, m);
-        hipLaunchKernelGGL(k_row_wsum, dim3(grid_for(n * 16, 2048)), dim3(256), 0, 0,
-                           dp->d_rowptr, dp->d_adj_eid, d_w, d_deg, (int)n);
+        launch_weights(d_s, d_w, m, 0);
+        launch_row_wsum(dp, d_w, d_deg, 0);
         DESC_HIP(hipMemcpy(deg.data(), d_deg, sizeof(double) * n, hipMemcpyDeviceToHost));
         for (int64_t v = 0; v < n; ++v) if (!std::isfinite(deg[v])) return fail(DESC_ERR_INVALID, "S_vec holds a negative or non-finite entry (node %lld)", (long long)v);
     } else {
@@ -379,17 +466,16 @@ static int spectral_impl(const desc_device_problem* dp, const double* weights, c
     for (size_t t = 0; t < X0.size(); ++t) X0[t] = (double)(int64_t)(mix64(0xC0FFEEull + t) >> 11) / 4503599627370496.0 - 1.0;
 
     DevArena D;
-    const int32_t *d_rowptr = dp->d_rowptr, *d_adj = dp->d_adj; double *d_blocks, *d_X, *d_Y, *d_part;
-    const int ggrid = 256;
+    double *d_blocks, *d_X, *d_Y, *d_part;
+    const int ggrid = GGRID;
     if ((rc = D.alloc(&d_blocks, 18 * m)) ||
         (rc = D.alloc(&d_X, rows * BW)) || (rc = D.alloc(&d_Y, rows * BW)) || (rc = D.alloc(&d_part, (size_t)ggrid * 2 * BW * BW))) return rc;
     if (m) {
         DevArena T;                                               // assembly inputs, released before the iteration starts
-        const int32_t* d_eid = dp->d_adj_eid; const double* d_rij = dp->d_rij; double* d_dinv;
+        double* d_dinv;
         if ((rc = T.alloc(&d_dinv, n))) return rc;
         DESC_HIP(hipMemcpy(d_dinv, dinv.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_assemble_blocks, dim3((unsigned)std::min<int64_t>(4096, (n + 3) / 4)), dim3(256), 0, 0, d_rowptr, d_adj, d_eid, d_rij, d_w,
-                           d_dinv, d_blocks, (int64_t)2 * m, (int)n);
+        launch_assemble(dp, d_w, d_dinv, d_blocks, 0);
         DESC_HIP(hipGetLastError());
         DESC_HIP(hipDeviceSynchronize());
     }
@@ -398,12 +484,7 @@ static int spectral_impl(const desc_device_problem* dp, const double* weights, c
 
     hvec<double> part((size_t)ggrid * 2 * BW * BW);
     double G1[BW * BW], G2[BW * BW];
-    auto grams = [&](const double* A, const double* B) -> int {
-        hipLaunchKernelGGL(k_gram, dim3(ggrid), dim3(256), 0, 0, A, B, rows, d_part);
-        DESC_HIP(hipMemcpy(part.data(), d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost));
-        for (int t = 0; t < BW * BW; ++t) { double s1 = 0, s2 = 0; for (int b = 0; b < ggrid; ++b) { s1 += part[(size_t)b * 2 * BW * BW + t]; s2 += part[(size_t)b * 2 * BW * BW + BW * BW + t]; } G1[t] = s1; G2[t] = s2; }
-        return DESC_OK;
-    };
+    auto grams = [&](const double* A, const double* B) -> int { return gram_sums(A, B, rows, 0, d_part, part, G1, G2); };
     // C = Z * L^-T where K = Z' G Z = L L'  (columns of Y*C are orthonormal): small_dense.h
     auto ortho_coeffs = [&](const double* G, const double* Z, SmallMat& C) -> bool { return desc::ortho_coeffs<BW>(G, Z, C.c); };
     double Ident[BW * BW];
@@ -412,7 +493,7 @@ static int spectral_impl(const desc_device_problem* dp, const double* weights, c
     SmallMat C;
     if ((rc = grams(d_Y, d_Y))) return rc;
     if (!ortho_coeffs(G2, Ident, C)) return fail(DESC_ERR_INVALID, "degenerate start basis");
-    hipLaunchKernelGGL(k_combine, dim3(512), dim3(256), 0, 0, d_Y, d_X, rows, C);
+    launch_combine(d_Y, d_X, rows, C, 0);
 
     // Chebyshev-filtered subspace iteration (Zhou & Saad): each outer step damps the unwanted
     // part of the spectrum [lo, cut] with a degree-CHEB_DEG Chebyshev polynomial of A, then
@@ -447,11 +528,9 @@ static int spectral_impl(const desc_device_problem* dp, const double* weights, c
     double theta[BW] = {}, Z[BW * BW], res = 1e300;
     int it = 0, products = 0;
     bool converged = false;
-    const bool wide_rows = 2 * m >= 192 * n;                   // average row of >= 192 slots: a workgroup per row, else a wave
-    const int sgrid = (int)std::min<int64_t>(8192, wide_rows ? n : (n + 3) / 4);
+    const bool wide_rows = wide_rows_rule(n, m);
     auto spmm = [&](const double* x, const double* z, double* y, double alpha, double s1, double s2) {
-        if (wide_rows) hipLaunchKernelGGL(k_bsr_spmm<256>, dim3(sgrid), dim3(256), 0, 0, d_rowptr, d_adj, d_blocks, (int64_t)2 * m, x, z, y, (int)n, alpha, s1, s2);
-        else hipLaunchKernelGGL(k_bsr_spmm<64>, dim3(sgrid), dim3(256), 0, 0, d_rowptr, d_adj, d_blocks, (int64_t)2 * m, x, z, y, (int)n, alpha, s1, s2);
+        launch_spmm(dp, d_blocks, wide_rows, 0, x, z, y, alpha, s1, s2);
         ++products;
     };
     double lo = -sigma;
@@ -465,11 +544,11 @@ static int spectral_impl(const desc_device_problem* dp, const double* weights, c
             ResArgs ra;
             for (int k = 0; k < BW; ++k) for (int c = 0; c < 3; ++c) ra.z[k * 3 + c] = Z[k * BW + c];
             for (int c = 0; c < 3; ++c) ra.theta[c] = theta[c];
-            hipLaunchKernelGGL(k_residual, dim3(ggrid), dim3(256), 0, 0, d_X, d_Y, rows, ra, d_part);
-            DESC_HIP(hipMemcpy(part.data(), d_part, sizeof(double) * 3 * ggrid, hipMemcpyDeviceToHost));
+            double r2[3];
+            if ((rc = residual_sums(d_X, d_Y, rows, 0, ra, d_part, part, r2))) return rc;
             res = 0.0;
             const double scale = std::max(std::fabs(theta[0]), sigma);
-            for (int c = 0; c < 3; ++c) { double r2 = 0; for (int bb = 0; bb < ggrid; ++bb) r2 += part[(size_t)3 * bb + c]; res = std::max(res, std::sqrt(r2) / std::max(scale, 1e-300)); }
+            for (int c = 0; c < 3; ++c) res = std::max(res, std::sqrt(r2[c]) / std::max(scale, 1e-300));
         }
         if (timing) fprintf(stderr, "[desc_amd] spectral  outer %d: residual %.3e after %d products (last pass: degree %d)\n", it, res, products, deg_prev);
         if (res <= tol) { converged = true; break; }
@@ -522,7 +601,7 @@ static int spectral_impl(const desc_device_problem* dp, const double* weights, c
                 continue;
             }
             double* Xn = (Pp == d_X) ? (Xp == d_P ? d_Q : d_P) : d_X;       // a buffer that is not Pp
-            hipLaunchKernelGGL(k_combine, dim3(512), dim3(256), 0, 0, Pp, Xn, rows, Co);
+            launch_combine(Pp, Xn, rows, Co, 0);
             if (Xn != d_X) DESC_HIP(hipMemcpyAsync(d_X, Xn, sizeof(double) * rows * BW, hipMemcpyDeviceToDevice, 0));
             break;
         }
@@ -537,36 +616,19 @@ static int spectral_impl(const desc_device_problem* dp, const double* weights, c
     }
     lap("subspace iteration");
     SmallMat CZ; std::memcpy(CZ.c, Z, sizeof Z);
-    hipLaunchKernelGGL(k_combine, dim3(512), dim3(256), 0, 0, d_X, d_Y, rows, CZ);
+    launch_combine(d_X, d_Y, rows, CZ, 0);
     DESC_HIP(hipGetLastError());
     hvec<double> Vh((size_t)rows * BW);
     DESC_HIP(hipMemcpy(Vh.data(), d_Y, sizeof(double) * rows * BW, hipMemcpyDeviceToHost));
 
-    // back to the eigenvectors of D^-1 A, unit 2-norm columns (what eigs returns)   (GCW.m:21,27)
+    // back to the eigenvectors of D^-1 A, unit 2-norm columns (what eigs returns), sign fix   (GCW.m:21,27-28 / Spectral.m:39): small_dense.h
     hvec<double> V((size_t)rows * 3);
-    double nrm[3] = {0, 0, 0};
-    for (int64_t v = 0; v < n; ++v) for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) {
-        const double x = Vh[((size_t)3 * v + r) * BW + c] * (normalize_rows ? dinv[v] : 1.0);
-        V[((size_t)3 * v + r) * 3 + c] = x; nrm[c] += x * x;
-    }
-    for (size_t t = 0; t < V.size(); ++t) V[t] /= std::sqrt(nrm[t % 3]);
-    // V(:,1) = V(:,1)*sign(det(V(1:3,:)))   (Spectral.m:39 / GCW.m:28)
-    {
-        const double* A = V.data();
-        const double det = A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6]) + A[2] * (A[3] * A[7] - A[4] * A[6]);
-        const double sg = det > 0 ? 1.0 : (det < 0 ? -1.0 : 0.0);
-        for (int64_t r = 0; r < rows; ++r) V[(size_t)r * 3] *= sg;
-    }
+    for (int64_t r = 0; r < rows; ++r) for (int c = 0; c < 3; ++c) V[(size_t)r * 3 + c] = Vh[(size_t)r * BW + c];
+    ritz_scale_sign(V.data(), normalize_rows ? dinv.data() : nullptr, n);
     {   // per-node SVD projection (Spectral.m:41-46): independent 3x3 problems, host threads for large n
         unsigned hw = std::thread::hardware_concurrency();
         const int T = (int)std::min<int64_t>(std::max(1u, std::min(hw, 16u)), std::max<int64_t>(1, n / 512));
-        run_threads(T, [&](int t) {
-            for (int64_t v = n * t / T; v < n * (t + 1) / T; ++v) {
-                double R[9];
-                project_so3(&V[(size_t)9 * v], R);           // rows 3v..3v+2 of V = the node's 3x3 block, row-major
-                for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) R_out[9 * v + r + 3 * c] = R[r * 3 + c];   // MATLAB column-major 3x3xn
-            }
-        });
+        run_threads(T, [&](int t) { project_nodes(V.data(), n * t / T, n * (t + 1) / T, R_out); });
     }
     lap("normalise + project");
     if (info) {
@@ -600,43 +662,18 @@ extern "C" int desc_debug_spmm_variants(const desc_device_problem* dp, int32_t r
     for (size_t t = 0; t < X0.size(); ++t) X0[t] = (double)(int64_t)(mix64(0xC0FFEEull + t) >> 11) / 4503599627370496.0 - 1.0;
     DESC_HIP(hipMemcpy(d_dinv, ones.data(), sizeof(double) * n, hipMemcpyHostToDevice));
     DESC_HIP(hipMemcpy(d_X, X0.data(), sizeof(double) * rows * BW, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_assemble_blocks, dim3((unsigned)std::min<int64_t>(4096, (n + 3) / 4)), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj, dp->d_adj_eid, dp->d_rij,
-                       (const double*)nullptr, d_dinv, d_blocks, (int64_t)2 * m, (int)n);
-    // operand layout of v_mfma_f64_4x4x4: the unit-vector probes must show exactly the layout k_bsr_spmm_mfma is written for --
-    // A's lane (x, y, r) reaches D's lanes (*, y, x), B's lane (x, y, r) reaches D's lanes (x, y, *), with lane = 16 r + 4 y + x,
-    // and an A lane meets a B lane iff they share the tile y and the summation index r
+    launch_assemble(dp, nullptr, d_dinv, d_blocks, 0);
     int lay_ok = 1;
-    {
-        unsigned long long* d_rm; unsigned long long* d_cm; unsigned char* d_cp;
-        if ((rc = D.alloc(&d_rm, 64)) || (rc = D.alloc(&d_cm, 64)) || (rc = D.alloc(&d_cp, 4096))) return rc;
-        hipLaunchKernelGGL(k_mfma_layout_probe, dim3(1), dim3(64), 0, 0, d_rm, d_cm, d_cp);
-        unsigned long long rm[64], cm[64]; unsigned char cp[4096];
-        DESC_HIP(hipMemcpy(rm, d_rm, sizeof rm, hipMemcpyDeviceToHost));
-        DESC_HIP(hipMemcpy(cm, d_cm, sizeof cm, hipMemcpyDeviceToHost));
-        DESC_HIP(hipMemcpy(cp, d_cp, sizeof cp, hipMemcpyDeviceToHost));
-        if (std::getenv("DESC_DEBUG_TIMING"))                  // diagnostics: the raw footprints
-            for (int q = 0; q < 64; ++q) fprintf(stderr, "[desc_amd] mfma probe lane %2d: A -> D %016llx   B -> D %016llx\n", q, rm[q], cm[q]);
-        for (int l = 0; l < 64; ++l) {
-            const int lx = l & 3, ly = (l >> 2) & 3;
-            if (rm[l] != 0xFull << (16 * lx + 4 * ly)) lay_ok = 0;
-            if (cm[l] != 0x0001000100010001ull << (4 * ly + lx)) lay_ok = 0;
-            for (int l2 = 0; l2 < 64; ++l2)
-                if ((cp[l * 64 + l2] != 0) != (((l >> 2) & 3) == ((l2 >> 2) & 3) && (l >> 4) == (l2 >> 4))) lay_ok = 0;
-        }
-    }
+    if ((rc = mfma_layout_probe(D, lay_ok))) return rc;
     const int lay = lay_ok ? 1 : -1;
-    const bool wide = 2 * m >= 192 * n;
-    const int sgrid = (int)std::min<int64_t>(8192, wide ? n : (n + 3) / 4);
+    const bool wide = wide_rows_rule(n, m);
     hipEvent_t e0, e1;
     DESC_HIP(hipEventCreate(&e0)); DESC_HIP(hipEventCreate(&e1));
     auto timed = [&](int which) -> double {
         for (int r = -2; r < reps; ++r) {                              // two untimed warm-up products
             if (r == 0) (void)hipEventRecord(e0, 0);
-            if (which == 0) {
-                if (wide) hipLaunchKernelGGL(k_bsr_spmm<256>, dim3(sgrid), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj, d_blocks, (int64_t)2 * m, d_X, d_X, d_Y1, (int)n, 1.0, 0.0, 0.0);
-                else hipLaunchKernelGGL(k_bsr_spmm<64>, dim3(sgrid), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj, d_blocks, (int64_t)2 * m, d_X, d_X, d_Y1, (int)n, 1.0, 0.0, 0.0);
-            } else
-                hipLaunchKernelGGL(k_bsr_spmm_mfma, dim3((unsigned)std::min<int64_t>(8192, n)), dim3(256), 0, 0, dp->d_rowptr, dp->d_adj, d_blocks, (int64_t)2 * m, d_X, d_X, d_Y2, (int)n, 1.0, 0.0, 0.0);
+            if (which == 0) launch_spmm(dp, d_blocks, wide, 0, d_X, d_X, d_Y1, 1.0, 0.0, 0.0);
+            else launch_spmm_mfma(dp, d_blocks, 0, d_X, d_X, d_Y2, 1.0, 0.0, 0.0);
         }
         (void)hipEventRecord(e1, 0);
         (void)hipEventSynchronize(e1);
@@ -654,6 +691,172 @@ extern "C" int desc_debug_spmm_variants(const desc_device_problem* dp, int32_t r
     }
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     DESC_HIP(hipGetLastError());
+    return DESC_OK;
+    });
+}
+
+
+// ---- test hooks (include/desc_amd.h, tests/test_gpu_spectral_kernels.py, tests/test_spectral_host.py): one kernel of the eigen-solve
+// on caller (host) arrays, through the launch functions spectral_impl uses; grid = 0 is the product path's rule.  Nothing in the
+// library calls them.
+namespace {
+bool grid_ok(int32_t grid) { return grid >= 0 && grid <= HOOK_GRID_MAX; }
+}  // namespace
+
+extern "C" int desc_test_spectral_weights(const double* S, int64_t m, int32_t device, double* w) {
+    return no_throw("desc_test_spectral_weights", [&]() -> int {
+    if (!S || !w) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (m < 0) return fail(DESC_ERR_INVALID, "negative count");
+    DESC_HIP(hipSetDevice(device));
+    DevArena A; int rc; double *d_s, *d_w;
+    if ((rc = hook_upload(A, S, m, &d_s)) || (rc = A.alloc(&d_w, (size_t)m))) return rc;
+    launch_weights(d_s, d_w, m, 0);
+    return hook_download(w, d_w, m);
+    });
+}
+
+extern "C" int desc_test_spectral_row_wsum(const desc_device_problem* dp, const double* w, int64_t m, int32_t grid, double* deg) {
+    return no_throw("desc_test_spectral_row_wsum", [&]() -> int {
+    if (!dp || !deg) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (m < 0 || m != dp->m) return fail(DESC_ERR_INVALID, "m does not match the device problem");
+    if (!grid_ok(grid)) return fail(DESC_ERR_INVALID, "grid must lie in [0, %d]", HOOK_GRID_MAX);
+    DESC_HIP(hipSetDevice(dp->device));
+    DevArena A; int rc; double *d_w = nullptr, *d_deg;
+    if ((w && (rc = hook_upload(A, w, m, &d_w))) || (rc = A.alloc(&d_deg, (size_t)dp->n))) return rc;
+    launch_row_wsum(dp, d_w, d_deg, grid);
+    return hook_download(deg, d_deg, dp->n);
+    });
+}
+
+extern "C" int desc_test_spectral_assemble(const desc_device_problem* dp, const double* w, const double* dinv, int64_t m, int32_t grid,
+                                           double* blocks) {
+    return no_throw("desc_test_spectral_assemble", [&]() -> int {
+    if (!dp || !blocks) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (m < 0 || m != dp->m) return fail(DESC_ERR_INVALID, "m does not match the device problem");
+    if (!grid_ok(grid)) return fail(DESC_ERR_INVALID, "grid must lie in [0, %d]", HOOK_GRID_MAX);
+    if (m && !dp->d_rij) return fail(DESC_ERR_INVALID, "the device problem holds no rotations");
+    DESC_HIP(hipSetDevice(dp->device));
+    DevArena A; int rc; double *d_w = nullptr, *d_dinv, *d_blocks;
+    hvec<double> ones;
+    if (!dinv) { ones.assign((size_t)dp->n, 1.0); dinv = ones.data(); }                       // spectral_impl without normalize_rows
+    if ((w && (rc = hook_upload(A, w, m, &d_w))) || (rc = hook_upload(A, dinv, dp->n, &d_dinv)) || (rc = A.alloc(&d_blocks, (size_t)(18 * m)))) return rc;
+    if (m) launch_assemble(dp, d_w, d_dinv, d_blocks, grid);
+    return hook_download(blocks, d_blocks, 18 * m);
+    });
+}
+
+extern "C" int desc_test_spectral_spmm(const desc_device_problem* dp, const double* blocks, const double* x, const double* z, int32_t z_is_y,
+                                       int32_t form, int32_t grid, double alpha, double s1, double s2, double* y) {
+    return no_throw("desc_test_spectral_spmm", [&]() -> int {
+    if (!dp || !blocks || !x || !z || !y) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (form != 0 && form != 64 && form != 256 && form != 2) return fail(DESC_ERR_INVALID, "form must be 0, 64, 256 or 2");
+    if (!grid_ok(grid)) return fail(DESC_ERR_INVALID, "grid must lie in [0, %d]", HOOK_GRID_MAX);
+    if (dp->n < 1) return fail(DESC_ERR_INVALID, "empty problem");
+    DESC_HIP(hipSetDevice(dp->device));
+    const int64_t len = 3 * dp->n * BW;
+    DevArena A; int rc; double *d_blocks, *d_x, *d_z, *d_y;
+    if ((rc = hook_upload(A, blocks, 18 * dp->m, &d_blocks)) || (rc = hook_upload(A, x, len, &d_x)) || (rc = hook_upload(A, z, len, &d_z))) return rc;
+    if (z_is_y) d_y = d_z;                                                                    // the recurrence's in-place form
+    else if ((rc = A.alloc(&d_y, (size_t)len))) return rc;
+    if (form == 2) {
+        int lay_ok = 0;
+        if ((rc = mfma_layout_probe(A, lay_ok))) return rc;
+        if (!lay_ok) return fail(DESC_ERR_INVALID, "v_mfma_f64_4x4x4 has another operand layout on this device");
+        launch_spmm_mfma(dp, d_blocks, grid, d_x, d_z, d_y, alpha, s1, s2);
+    } else
+        launch_spmm(dp, d_blocks, form ? form == 256 : wide_rows_rule(dp->n, dp->m), grid, d_x, d_z, d_y, alpha, s1, s2);
+    return hook_download(y, d_y, len);
+    });
+}
+
+extern "C" int desc_test_spectral_gram(const double* X, const double* Y, int64_t rows, int32_t grid, int32_t device, double* G1, double* G2) {
+    return no_throw("desc_test_spectral_gram", [&]() -> int {
+    if (!X || !Y || !G1 || !G2) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (rows < 0) return fail(DESC_ERR_INVALID, "negative count");
+    if (!grid_ok(grid)) return fail(DESC_ERR_INVALID, "grid must lie in [0, %d]", HOOK_GRID_MAX);
+    DESC_HIP(hipSetDevice(device));
+    const int g = grid ? grid : GGRID;
+    DevArena A; int rc; double *d_X, *d_Y, *d_part;
+    if ((rc = hook_upload(A, X, rows * BW, &d_X)) || (rc = hook_upload(A, Y, rows * BW, &d_Y)) || (rc = A.alloc(&d_part, (size_t)g * 2 * BW * BW))) return rc;
+    hvec<double> part((size_t)g * 2 * BW * BW);
+    if ((rc = gram_sums(d_X, d_Y, rows, grid, d_part, part, G1, G2))) return rc;
+    DESC_HIP(hipGetLastError());
+    return DESC_OK;
+    });
+}
+
+extern "C" int desc_test_spectral_residual(const double* X, const double* Y, int64_t rows, const double* Z3, const double* theta, int32_t grid,
+                                           int32_t device, double* r2) {
+    return no_throw("desc_test_spectral_residual", [&]() -> int {
+    if (!X || !Y || !Z3 || !theta || !r2) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (rows < 0) return fail(DESC_ERR_INVALID, "negative count");
+    if (!grid_ok(grid)) return fail(DESC_ERR_INVALID, "grid must lie in [0, %d]", HOOK_GRID_MAX);
+    DESC_HIP(hipSetDevice(device));
+    const int g = grid ? grid : GGRID;
+    DevArena A; int rc; double *d_X, *d_Y, *d_part;
+    if ((rc = hook_upload(A, X, rows * BW, &d_X)) || (rc = hook_upload(A, Y, rows * BW, &d_Y)) || (rc = A.alloc(&d_part, (size_t)g * 3))) return rc;
+    ResArgs ra;
+    for (int t = 0; t < BW * 3; ++t) ra.z[t] = Z3[t];
+    for (int c = 0; c < 3; ++c) ra.theta[c] = theta[c];
+    hvec<double> part((size_t)g * 3);
+    if ((rc = residual_sums(d_X, d_Y, rows, grid, ra, d_part, part, r2))) return rc;
+    DESC_HIP(hipGetLastError());
+    return DESC_OK;
+    });
+}
+
+extern "C" int desc_test_spectral_combine(const double* Y, int64_t rows, const double* C, int32_t grid, int32_t device, double* Xn) {
+    return no_throw("desc_test_spectral_combine", [&]() -> int {
+    if (!Y || !C || !Xn) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (rows < 0) return fail(DESC_ERR_INVALID, "negative count");
+    if (!grid_ok(grid)) return fail(DESC_ERR_INVALID, "grid must lie in [0, %d]", HOOK_GRID_MAX);
+    DESC_HIP(hipSetDevice(device));
+    DevArena A; int rc; double *d_Y, *d_Xn;
+    if ((rc = hook_upload(A, Y, rows * BW, &d_Y)) || (rc = A.alloc(&d_Xn, (size_t)(rows * BW)))) return rc;
+    SmallMat Cm;
+    for (int t = 0; t < BW * BW; ++t) Cm.c[t] = C[t];
+    launch_combine(d_Y, d_Xn, rows, Cm, grid);
+    return hook_download(Xn, d_Xn, rows * BW);
+    });
+}
+
+// the small dense helpers of small_dense.h on the host: no device is touched
+extern "C" int desc_test_small_jacobi(int32_t N, const double* A, double* w, double* V) {
+    return no_throw("desc_test_small_jacobi", [&]() -> int {
+    if (!A || !w || !V) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (N == 3) jacobi_eig<3>(A, w, V);
+    else if (N == BW) jacobi_eig<BW>(A, w, V);
+    else return fail(DESC_ERR_INVALID, "N must be 3 or %d", BW);
+    return DESC_OK;
+    });
+}
+
+extern "C" int desc_test_small_ortho(const double* G, const double* Z, double* C, int32_t* ok) {
+    return no_throw("desc_test_small_ortho", [&]() -> int {
+    if (!G || !C || !ok) return fail(DESC_ERR_INVALID, "NULL argument");
+    double Ident[BW * BW];
+    for (int t = 0; t < BW * BW; ++t) Ident[t] = (t % (BW + 1) == 0);
+    *ok = ortho_coeffs<BW>(G, Z ? Z : Ident, C) ? 1 : 0;
+    return DESC_OK;
+    });
+}
+
+extern "C" int desc_test_small_project(const double* M, int64_t count, double* R) {
+    return no_throw("desc_test_small_project", [&]() -> int {
+    if (!M || !R) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (count < 0) return fail(DESC_ERR_INVALID, "negative count");
+    for (int64_t k = 0; k < count; ++k) project_so3(M + 9 * k, R + 9 * k);
+    return DESC_OK;
+    });
+}
+
+extern "C" int desc_test_small_ritz_tail(const double* V, const double* dinv, int64_t n, double* R_out) {
+    return no_throw("desc_test_small_ritz_tail", [&]() -> int {
+    if (!V || !R_out) return fail(DESC_ERR_INVALID, "NULL argument");
+    if (n < 1) return fail(DESC_ERR_INVALID, "n must be positive");
+    hvec<double> W(V, V + 9 * n);
+    ritz_scale_sign(W.data(), dinv, n);
+    project_nodes(W.data(), 0, n, R_out);
     return DESC_OK;
     });
 }

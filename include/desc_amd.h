@@ -974,6 +974,40 @@ int desc_test_irls_pd_stage(const desc_device_problem* dp, int32_t stage, const 
 int desc_test_irls_pd_solve(const desc_device_problem* dp, const double* B, int64_t m, int64_t n, int32_t pdmaxiter, double* x,
                             double* state, int32_t* counters, double* trace, int32_t trace_cap, int32_t* trace_len);
 
+/* Test hooks (tests/test_gpu_spectral_kernels.py, tests/test_spectral_host.py): the kernels of the Spectral / GCW eigen-solve
+ * (spectral.hip) one at a time on caller (host) arrays, and the small dense helpers it shares with the batched solve (small_dense.h).
+ * Each launches through the function the product path launches with; grid = 0 is the product path's grid rule, another value forces
+ * that many workgroups (so that the stride loops turn at small sizes).  A NULL pointer, a negative count, an m that is not the device
+ * problem's, an unknown form or a grid outside [0, 65535] returns DESC_ERR_INVALID before any device work.
+ *   weights    S (m) -> 1 / (S^1.5 + 1e-8)  (GCW.m:20)
+ *   row_wsum   w (m; NULL: ones) -> the weighted degree of every node (n)
+ *   assemble   w (m; NULL: ones), dinv (n; NULL: ones) -> the 2m blocks as stored: 18 m doubles, component-major
+ *              (blocks[q * 2m + t], q = r + 3k of CSR slot t)
+ *   spmm       y = alpha A x + s1 x + s2 z for the given blocks; x, z, y: 3n x 6 row-major.  form 0: the product path's choice between
+ *              the wave-per-row (64) and workgroup-per-row (256) kernels, 64 / 256: that one, 2: the v_mfma_f64_4x4x4 form (refused
+ *              unless the operand layout probe agrees).  z_is_y: launched with z aliasing y
+ *   gram       X, Y (rows x 6) -> G1 = X'Y, G2 = Y'Y (6 x 6 row-major), the host sum over the workgroups' partials included
+ *   residual   X, Y (rows x 6), Z3 (6 x 3 row-major: the three Ritz vectors' coefficients), theta (3) -> r2[c] = |Y z_c - theta_c X z_c|^2
+ *   combine    Y (rows x 6), C (6 x 6 row-major) -> Y C
+ *   small_jacobi   N = 3 or 6: symmetric A (N x N) -> eigenvalues w descending, eigenvectors in the columns of V
+ *   small_ortho    G, Z (6 x 6; Z NULL: identity) -> C = Z L^-T with Z'GZ = L L'; *ok = 0 where that is not positive definite
+ *   small_project  count 3x3 blocks M (row-major) -> their projections onto SO(3) (row-major)
+ *   small_ritz_tail  V (3n x 3 Ritz vectors), dinv (n; NULL: none) -> scaling, sign fix and per-node projection, R_out 3x3xn column-major
+ * The small_* hooks are host code only. */
+int desc_test_spectral_weights(const double* S, int64_t m, int32_t device, double* w);
+int desc_test_spectral_row_wsum(const desc_device_problem* dp, const double* w, int64_t m, int32_t grid, double* deg);
+int desc_test_spectral_assemble(const desc_device_problem* dp, const double* w, const double* dinv, int64_t m, int32_t grid, double* blocks);
+int desc_test_spectral_spmm(const desc_device_problem* dp, const double* blocks, const double* x, const double* z, int32_t z_is_y,
+                            int32_t form, int32_t grid, double alpha, double s1, double s2, double* y);
+int desc_test_spectral_gram(const double* X, const double* Y, int64_t rows, int32_t grid, int32_t device, double* G1, double* G2);
+int desc_test_spectral_residual(const double* X, const double* Y, int64_t rows, const double* Z3, const double* theta, int32_t grid,
+                                int32_t device, double* r2);
+int desc_test_spectral_combine(const double* Y, int64_t rows, const double* C, int32_t grid, int32_t device, double* Xn);
+int desc_test_small_jacobi(int32_t N, const double* A, double* w, double* V);
+int desc_test_small_ortho(const double* G, const double* Z, double* C, int32_t* ok);
+int desc_test_small_project(const double* M, int64_t count, double* R);
+int desc_test_small_ritz_tail(const double* V, const double* dinv, int64_t n, double* R_out);
+
 #ifdef __cplusplus
 }
 #endif
