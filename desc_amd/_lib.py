@@ -45,6 +45,8 @@ EXPORTS = [
     "desc_irls_batch_max_n", "desc_irls_batch_create", "desc_irls_batch_sizes", "desc_irls_batch_run", "desc_irls_batch_destroy",
     "desc_irls_tree_sequence",
     "desc_lp_batch_plan", "desc_lp_batch_create", "desc_lp_batch_sizes", "desc_lp_batch_get_samples", "desc_lp_batch_run", "desc_lp_batch_destroy",
+    "desc_models_key", "desc_models_batch_max_n", "desc_models_batch_create", "desc_models_batch_sizes", "desc_models_batch_fetch",
+    "desc_models_batch_destroy", "desc_test_models_uniform", "desc_test_models_normal",
     "desc_test_laa_r2q", "desc_test_laa_q2r", "desc_test_laa_edge_log", "desc_test_laa_rhs", "desc_test_laa_pcg", "desc_test_laa_node_update",
     "desc_test_irls_node_update", "desc_test_laa_weights", "desc_test_irls_weights", "desc_test_laa_quantile", "desc_test_irls_project",
     "desc_test_irls_pd_stage", "desc_test_irls_pd_solve",
@@ -151,6 +153,17 @@ class IrlsBatchTimings(C.Structure):
 
 class LpBatchTimings(C.Structure):
     _fields_ = [("ms_structure", C.c_double), ("ms_upload", C.c_double), ("ms_build", C.c_double), ("ms_loop", C.c_double),
+                ("ms_total", C.c_double)]
+
+
+class ModelSpec(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("n", C.c_int32), ("p", C.c_double), ("q", C.c_double), ("p_node_crpt", C.c_double),
+                ("p_edge_crpt", C.c_double), ("sigma", C.c_double), ("sigma_in", C.c_double), ("sigma_out", C.c_double),
+                ("mode", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
+class ModelsBatchTimings(C.Structure):
+    _fields_ = [("ms_graph", C.c_double), ("ms_nodes", C.c_double), ("ms_edges", C.c_double), ("ms_copy", C.c_double),
                 ("ms_total", C.c_double)]
 
 
@@ -374,6 +387,17 @@ def load():
     L.desc_lp_batch_run.argtypes = [C.c_void_p, C.POINTER(LpParams), F64P, F64P, C.POINTER(LpInfo), C.POINTER(LpBatchTimings)]
     L.desc_lp_batch_destroy.argtypes = [C.c_void_p]
     L.desc_lp_batch_destroy.restype = None
+    L.desc_models_key.restype = C.c_uint64
+    L.desc_models_key.argtypes = [C.c_uint64] * 5
+    L.desc_models_batch_max_n.restype = C.c_int32
+    L.desc_models_batch_max_n.argtypes = []
+    L.desc_models_batch_create.argtypes = [C.POINTER(ModelSpec), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.desc_models_batch_sizes.argtypes = [C.c_void_p, I64P]
+    L.desc_models_batch_fetch.argtypes = [C.c_void_p, I32P, I32P, F64P, F64P, F64P, F64P, C.POINTER(C.c_uint8), C.POINTER(ModelsBatchTimings)]
+    L.desc_models_batch_destroy.argtypes = [C.c_void_p]
+    L.desc_models_batch_destroy.restype = None
+    L.desc_test_models_uniform.argtypes = [C.c_uint64] * 4 + [C.c_int64, C.c_uint64, C.c_int32, F64P]
+    L.desc_test_models_normal.argtypes = [C.c_uint64] * 4 + [C.c_int64, C.c_uint64, C.c_int32, F64P]
     L.desc_test_laa_r2q.argtypes = [F64P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, F64P]
     L.desc_test_laa_q2r.argtypes = [F64P, C.c_int64, C.c_int32, F64P]
     L.desc_test_laa_edge_log.argtypes = [C.c_void_p, F64P, F64P, C.c_int64, F64P]
@@ -1002,6 +1026,65 @@ class LpBatch(_BatchHandle):
                 yb = y[2 * int(self.row_off[b]):2 * int(self.row_off[b + 1])].reshape(int(self.m_pos[b]), int(self.nsample[b]), 2)
             outs.append((S[int(self.edge_off[b]):int(self.edge_off[b + 1])], yb, {name: getattr(infos[b], name) for name, _ in LpInfo._fields_}))
         return outs, _timings(tm)
+
+
+MODELS_KIND_UNIFORM, MODELS_KIND_NONUNIFORM = 0, 1
+MODELS_UNIFORM, MODELS_SELF_CONSISTENT, MODELS_ADV = 0, 1, 2
+# DESC_MODELS_STREAM_*
+MODELS_STREAMS = dict(edge=1, rorig=2, rcorr=3, corrupt=4, noise=5, haar=6, node=7, select=8, r0=9)
+
+
+def models_batch_max_n():
+    """desc_models_batch_max_n: the largest n the batched generator draws."""
+    return int(load().desc_models_batch_max_n())
+
+
+def models_key(seed, stream, sub, id, c):
+    """desc_models_key: the generator's 64-bit key of (seed, stream, sub, id, component)."""
+    return int(load().desc_models_key(int(seed), int(stream), int(sub), int(id), int(c)))
+
+
+class ModelsBatch(_BatchHandle):
+    """Owner of a desc_models_batch*: B synthetic problems drawn on the GPU (desc_models_batch_*).  ``specs`` is a sequence of
+    ModelSpec.  Create runs the graph pass: ``m_per`` holds the problems' edge counts, ``node_off`` / ``edge_off`` their offsets in the
+    concatenated arrays ``fetch`` returns."""
+
+    _kind = "models"
+
+    def __init__(self, specs, device=0):
+        self.specs = list(specs)
+        self.count = B = len(self.specs)
+        arr = (ModelSpec * max(B, 1))(*self.specs)
+        h = C.c_void_p()
+        check(load().desc_models_batch_create(arr, B, int(device), C.byref(h)))
+        self.handle = h
+        m_per = np.zeros(max(B, 1), dtype=np.int64)
+        check(load().desc_models_batch_sizes(self.handle, ptr(m_per, I64P)))
+        self.m_per = m_per[:B]
+        self.node_off = np.concatenate([[0], np.cumsum([s.n for s in self.specs], dtype=np.int64)]).astype(np.int64)
+        self.edge_off = np.concatenate([[0], np.cumsum(self.m_per, dtype=np.int64)]).astype(np.int64)
+        self.n, self.m = int(self.node_off[B]), int(self.edge_off[B])
+
+    def fetch(self):
+        """The node, selection and edge passes and the copy-back: a dict of the concatenated arrays ind_i / ind_j (int32, 0-based), rij /
+        rij_orig (9 m), r_orig (9 n), err_vec (m), corrupted (m, uint8) -- and the call's timings."""
+        N, M = self.n, self.m
+        out = dict(ind_i=out_buffer(M, np.int32), ind_j=out_buffer(M, np.int32), rij=out_buffer(9 * M), rij_orig=out_buffer(9 * M),
+                   r_orig=out_buffer(9 * N), err_vec=out_buffer(M), corrupted=out_buffer(M, np.uint8))
+        tm = ModelsBatchTimings()
+        check(load().desc_models_batch_fetch(self.handle, ptr(out["ind_i"], I32P), ptr(out["ind_j"], I32P), ptr(out["rij"], F64P),
+                                             ptr(out["rij_orig"], F64P), ptr(out["r_orig"], F64P), ptr(out["err_vec"], F64P),
+                                             ptr(out["corrupted"], C.POINTER(C.c_uint8)), C.byref(tm)))
+        sizes = dict(ind_i=M, ind_j=M, rij=9 * M, rij_orig=9 * M, r_orig=9 * N, err_vec=M, corrupted=M)
+        return {k: v[:sizes[k]] for k, v in out.items()}, _timings(tm)
+
+
+def hook_models_draws(seed, stream, sub, id0, count, c, normal=False, device=0):
+    """desc_test_models_uniform / _normal: the device's draws of component c for ids id0 .. id0 + count - 1."""
+    out = out_buffer(count)
+    fn = load().desc_test_models_normal if normal else load().desc_test_models_uniform
+    check(fn(int(seed), int(stream), int(sub), int(id0), int(count), int(c), int(device), ptr(out, F64P)))
+    return out[:int(count)]
 
 
 def gcw_batch_csr(probs):

@@ -146,3 +146,141 @@ def Nonuniform_Topology(n, p, p_node_crpt, p_edge_crpt, sigma_in, sigma_out, crp
     if m:
         Rm = _project_so3(Rm)                                                  # :133-137
     return _finish(n, Ind_i, Ind_j, Rm, Rij_orig, R_orig, dict(corrupted=crptInd))
+
+
+# ---- the batched generators: B problems drawn on the GPU in one pass (desc_models_batch_*, csrc/models_batch.hip) -------------------
+# A third seeded restatement of the same distributions, defined in include/desc_amd.h: counter-based keys on (seed, stream, id,
+# component).  For the same seed it does NOT produce the draws of the NumPy generators above.
+_CRPT_MODES = {"uniform": 0, "self-consistent": 1, "adv": 2}
+
+
+def _per_problem(name, value, B):
+    """A scalar or a sequence of B values -> a list of B values."""
+    if isinstance(value, str) or np.ndim(value) == 0:
+        return [value] * B
+    seq = list(value)
+    if len(seq) != B:
+        raise ValueError(f"{name} must be a scalar or hold one entry per problem ({B}), not {len(seq)}")
+    return seq
+
+
+def _batch_seeds(seeds):
+    if seeds is None or isinstance(seeds, str) or np.ndim(seeds) != 1:
+        raise ValueError("seeds must be a sequence of integers, one per problem")
+    out = []
+    for b, s in enumerate(seeds):
+        if not isinstance(s, (int, np.integer)) or isinstance(s, bool) or not 0 <= int(s) < 2 ** 64:
+            raise ValueError(f"problem {b}: the seed must be an integer in [0, 2^64)")
+        out.append(int(s))
+    return out
+
+
+def _check_probability(b, name, x):
+    x = float(x)
+    if not (np.isfinite(x) and 0.0 <= x <= 1.0):
+        raise ValueError(f"problem {b}: {name} must be a probability in [0, 1]")
+    return x
+
+
+def _check_sigma(b, name, x):
+    x = float(x)
+    if not (np.isfinite(x) and x >= 0.0):
+        raise ValueError(f"problem {b}: {name} must be finite and >= 0")
+    return x
+
+
+def _check_n(b, n, cap):
+    if not isinstance(n, (int, np.integer)) or isinstance(n, bool):
+        raise ValueError(f"problem {b}: n must be an integer")
+    n = int(n)
+    if n < 2:
+        raise ValueError(f"problem {b}: n = {n}, need n >= 2")
+    if n > cap:
+        raise ValueError(f"problem {b}: n = {n} exceeds {cap}")
+    return n
+
+
+def _check_totals(specs):
+    """The batch-wide refusals of desc_models_batch_create."""
+    N, expected = 0, 0.0
+    for b, s in enumerate(specs):
+        N += s.n
+        expected += s.p * (0.5 * float(s.n) * float(s.n - 1))
+        if N >= 2 ** 31:
+            raise ValueError(f"the batch holds 2^31 nodes or more at problem {b}: split the batch")
+        if expected >= float(2 ** 30):
+            raise ValueError(f"the batch is expected to draw 2^30 edges or more at problem {b} (152 bytes each): split the batch")
+
+
+def _draw_batch(specs, device, return_info):
+    from . import _lib
+    _check_totals(specs)
+    if not isinstance(device, (int, np.integer)) or isinstance(device, bool) or device < 0:
+        raise ValueError("device must be a non-negative integer")
+    if not specs:                                    # the empty batch touches no device
+        timings = {name: 0.0 for name, _ in _lib.ModelsBatchTimings._fields_}
+        return ([], timings) if return_info else []
+    batch = _lib.ModelsBatch(specs, device=int(device))
+    try:
+        arrays, timings = batch.fetch()
+    finally:
+        batch.destroy()
+    models = []
+    for b, s in enumerate(specs):
+        e0, e1 = int(batch.edge_off[b]), int(batch.edge_off[b + 1])
+        v0, v1 = int(batch.node_off[b]), int(batch.node_off[b + 1])
+        m = e1 - e0
+        Ind = np.stack([arrays["ind_i"][e0:e1].astype(np.int64) + 1, arrays["ind_j"][e0:e1].astype(np.int64) + 1], axis=1)
+        models.append(_Model(n=s.n, Ind=Ind,
+                             RijMat=arrays["rij"][9 * e0:9 * e1].reshape((3, 3, m), order="F"),
+                             Rij_orig=arrays["rij_orig"][9 * e0:9 * e1].reshape((3, 3, m), order="F"),
+                             R_orig=arrays["r_orig"][9 * v0:9 * v1].reshape((3, 3, s.n), order="F"),
+                             ErrVec=arrays["err_vec"][e0:e1], corrupted=arrays["corrupted"][e0:e1].astype(bool), seed=int(s.seed)))
+    return (models, timings) if return_info else models
+
+
+def Uniform_Topology_batch(n, p, q, sigma, model="uniform", *, seeds, device=0, return_info=False):
+    """B = len(seeds) problems of Models/Uniform_Topology.m:24-101 drawn on the GPU in one pass.
+
+    ``seeds``: a sequence of B integers; every other argument a scalar or a sequence of B values.  ``model``: 'uniform', any other
+    string the self-consistent branch (as ``Uniform_Topology``).  Returns a list of B models with the fields and layouts of
+    ``Uniform_Topology`` plus ``seed``; every ``*_batch`` solver takes them unchanged.  Problem b depends on its own arguments and seed
+    only.  The draws are those of the definition in include/desc_amd.h, not the NumPy generator's for the same seed.  With
+    ``return_info`` the call returns ``(models, timings)``: ms_graph, ms_nodes, ms_edges, ms_copy, ms_total."""
+    from . import _lib
+    seeds = _batch_seeds(seeds)
+    B = len(seeds)
+    cols = [_per_problem(name, v, B) for name, v in (("n", n), ("p", p), ("q", q), ("sigma", sigma), ("model", model))]
+    cap = _lib.models_batch_max_n()
+    specs = []
+    for b, (nb, pb, qb, sb, mb) in enumerate(zip(*cols)):
+        if not isinstance(mb, str):
+            raise ValueError(f"problem {b}: model must be a string")
+        specs.append(_lib.ModelSpec(kind=_lib.MODELS_KIND_UNIFORM, n=_check_n(b, nb, cap), p=_check_probability(b, "p", pb),
+                                    q=_check_probability(b, "q", qb), sigma=_check_sigma(b, "sigma", sb),
+                                    mode=_lib.MODELS_UNIFORM if mb == "uniform" else _lib.MODELS_SELF_CONSISTENT, seed=seeds[b]))
+    return _draw_batch(specs, device, return_info)
+
+
+def Nonuniform_Topology_batch(n, p, p_node_crpt, p_edge_crpt, sigma_in, sigma_out, crpt_type="uniform", *, seeds, device=0,
+                              return_info=False):
+    """B = len(seeds) problems of Models/Nonuniform_Topology.m:26-147 drawn on the GPU in one pass; arguments and result as
+    ``Uniform_Topology_batch``.  ``crpt_type``: 'uniform' | 'self-consistent' | 'adv'.  The two ``randperm``s are keyed selections: the
+    corrupted nodes are the floor(n p_node_crpt) nodes with the smallest node keys, node i corrupts the floor(p_edge_crpt deg_i)
+    incident edges with the smallest (i, edge) keys, and an edge both endpoints selected belongs to the endpoint with the larger
+    node key."""
+    from . import _lib
+    seeds = _batch_seeds(seeds)
+    B = len(seeds)
+    cols = [_per_problem(name, v, B) for name, v in (("n", n), ("p", p), ("p_node_crpt", p_node_crpt), ("p_edge_crpt", p_edge_crpt),
+                                                     ("sigma_in", sigma_in), ("sigma_out", sigma_out), ("crpt_type", crpt_type))]
+    cap = _lib.models_batch_max_n()
+    specs = []
+    for b, (nb, pb, pn, pe, si, so, ct) in enumerate(zip(*cols)):
+        if not isinstance(ct, str) or ct not in _CRPT_MODES:
+            raise ValueError(f"problem {b}: unknown crpt_type {ct!r} (uniform | self-consistent | adv)")
+        specs.append(_lib.ModelSpec(kind=_lib.MODELS_KIND_NONUNIFORM, n=_check_n(b, nb, cap), p=_check_probability(b, "p", pb),
+                                    p_node_crpt=_check_probability(b, "p_node_crpt", pn),
+                                    p_edge_crpt=_check_probability(b, "p_edge_crpt", pe), sigma_in=_check_sigma(b, "sigma_in", si),
+                                    sigma_out=_check_sigma(b, "sigma_out", so), mode=_CRPT_MODES[ct], seed=seeds[b]))
+    return _draw_batch(specs, device, return_info)

@@ -3,7 +3,11 @@
 of Uniform_Topology(100, 0.5, q, 0.1) -- the shape of the figures the DESC paper draws (error against q on graphs of 100-200 nodes).
 
     python examples/monte_carlo.py [--trials 5] [--n 100] [--iters 100] [--build host|device] [--rotations] [--refined] [--baselines]
-                                   [--mpls] [--lp] [--irls]
+                                   [--mpls] [--lp] [--irls] [--device-models]
+
+--device-models: the trials are drawn on the GPU by one Uniform_Topology_batch call instead of one Uniform_Topology call per trial on the
+host.  The batched generator has streams of its own: the curves differ from an unflagged run in their draws, not in their distribution.
+The time the generation took is printed in both modes.
 
 --build: the builder of the cycle structures behind DESC_PGD_batch / DESC_init_batch / DESC_batch: per problem on host threads (the
 default) or for the whole batch on the device; the curves are the same to the last bit.
@@ -32,7 +36,8 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from desc_amd import (CEMP_GCW_batch, CEMP_MST_batch, CEMP_batch, ConstantStepSize, DESC_PGD_batch, DESC_batch,  # noqa: E402
-                      DESC_init_batch, IRLS_GM_batch, IRLS_L12_batch, MPLS_batch, Rotation_Alignment, Uniform_Topology, linprog_sij_batch)
+                      DESC_init_batch, IRLS_GM_batch, IRLS_L12_batch, MPLS_batch, Rotation_Alignment, Uniform_Topology, Uniform_Topology_batch,
+                      linprog_sij_batch)
 
 
 def baselines(models, qs, trials):
@@ -123,9 +128,17 @@ def main():
     ap.add_argument("--mpls", action="store_true", help="the MPLS curve: one MPLS_batch call")
     ap.add_argument("--lp", action="store_true", help="the linprog_sij curve: one linprog_sij_batch call")
     ap.add_argument("--irls", action="store_true", help="the IRLS-GM and IRLS-L0.5 curves: one IRLS_GM_batch and one IRLS_L12_batch call")
+    ap.add_argument("--device-models", action="store_true", help="draw the trials on the GPU: one Uniform_Topology_batch call")
     a = ap.parse_args()
     qs = [0.0, 0.1, 0.2, 0.3, 0.4, 0.5]
-    models = [Uniform_Topology(a.n, 0.5, q, 0.1, "uniform", seed=1000 * k + t) for k, q in enumerate(qs) for t in range(a.trials)]
+    t0 = time.perf_counter()
+    if a.device_models:
+        models = Uniform_Topology_batch(a.n, 0.5, [q for q in qs for _ in range(a.trials)], 0.1, "uniform",
+                                        seeds=[1000 * k + t for k in range(len(qs)) for t in range(a.trials)])
+    else:
+        models = [Uniform_Topology(a.n, 0.5, q, 0.1, "uniform", seed=1000 * k + t) for k, q in enumerate(qs) for t in range(a.trials)]
+    print(f"{len(models)} problems drawn by " + ("one Uniform_Topology_batch call" if a.device_models else f"{len(models)} Uniform_Topology calls on the host")
+          + f": {(time.perf_counter() - t0) * 1e3:.1f} ms")
     params = dict(iters=a.iters, Gradient=ConstantStepSize(0.01), seed=0, verbose=False)
     if a.refined:
         t0 = time.perf_counter()

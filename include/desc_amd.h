@@ -852,6 +852,95 @@ int desc_lp_batch_run(desc_lp_batch* h, const desc_lp_params* params, double* s_
                       desc_lp_batch_timings* timings /* nullable */);
 void desc_lp_batch_destroy(desc_lp_batch* h);
 
+/* ------------------------------------------------- batched problem generator -- */
+/* Models/Uniform_Topology.m:24-101 and Models/Nonuniform_Topology.m:26-147 for B problems in one GPU pass (csrc/models_batch.hip): what
+ * a Monte-Carlo study draws in front of the *_batch solvers.  MATLAB's RNG streams cannot be matched; this is a seeded restatement of
+ * the same distributions -- a third one, next to MATLAB's and to desc_amd/models.py's NumPy streams, whose draws it does NOT reproduce
+ * for the same seed.  tests/models_batch_oracle.py restates the definition below in NumPy.
+ *
+ * Keys.  Every random number of problem b is a pure function of (seed_b, stream, sub, id, c):
+ *     desc_models_key(seed, stream, sub, id, c) = desc_sample_key(desc_sample_key(seed, stream, sub), id, c)
+ * with ids counted inside the problem (0-based node v, 0-based edge e in the (i, j)-sorted list, pair index t = i n - i (i + 1) / 2 +
+ * (j - i - 1) of the 0-based pair i < j), so that no bit of a problem depends on the batch around it.
+ *   uniform draw   u = (key >> 11) * 2^-53, an exact double in [0, 1)
+ *   normal draw c  z = sqrt(-2 log(u1)) * cos(6.283185307179586 * u2) with u1 = ((key(.., 2c) >> 12) + 0.5) * 2^-52 in (0, 1) and
+ *                  u2 = (key(.., 2c + 1) >> 11) * 2^-53
+ *   normal block   nine normals c = 0..8; c is entry (c mod 3, c div 3): the block's column-major memory order, as randn(3) fills it
+ *   projection     P(Q) = U diag(1, 1, det(U V')) V' of Q = U S V' (Uniform_Topology.m:41-44, :61-65); a Haar rotation is P(normal block)
+ * Streams (sub = 0 unless stated):
+ *   DESC_MODELS_STREAM_EDGE    id = t, c = 0: the pair is an edge iff u < p                       (Uniform_Topology.m:29)
+ *   DESC_MODELS_STREAM_RORIG   id = v: the normal block of R_orig(:,:,v)                          (:40-45)
+ *   DESC_MODELS_STREAM_RCORR   id = v: the normal block of R_corr / R_crpt(:,:,v)                 (:69-74; Nonuniform_Topology.m:66-71)
+ *   DESC_MODELS_STREAM_CORRUPT id = e, c = 0: a noise edge iff u >= q, else corrupted             (Uniform_Topology.m:53)
+ *   DESC_MODELS_STREAM_NOISE   id = e: the normal block N_e of the additive noise                 (:58-59, :86; Nonuniform_Topology.m:121-127)
+ *   DESC_MODELS_STREAM_HAAR    id = e: the normal block of a 'uniform' corrupted edge             (Uniform_Topology.m:77-82)
+ *   DESC_MODELS_STREAM_NODE    id = v, c = 0: the node key.  The node order is ascending (key, v); the corrupted nodes are the first
+ *                              floor(n * p_node_crpt) of it                                       (Nonuniform_Topology.m:60-62)
+ *   DESC_MODELS_STREAM_SELECT  sub = v, id = e, c = 0: node v corrupts the floor(p_edge_crpt * deg_v) incident edges with the smallest
+ *                              (key, e)                                                           (:77-82)
+ *   DESC_MODELS_STREAM_R0      sub = w, id = e: the normal block of R0 drawn by the winning node w for edge e   (:88-91)
+ * Uniform (mode DESC_MODELS_UNIFORM, any other value: self-consistent, as :76,83): a noise edge gets P(Rij_orig + sigma N_e); a
+ * corrupted edge P(Haar block) or, self-consistent, P(R_corr_i R_corr_j' + sigma N_e).
+ * Nonuniform (modes UNIFORM | SELF_CONSISTENT | ADV): an edge selected by both endpoints belongs to the endpoint later in the node
+ * order (the later iteration of :76 overwrites).  With w the winner and x the other endpoint, M = R0 | R_crpt_w R_crpt_x' | R_crpt_w
+ * R_orig_x'; the edge's block becomes M if w is the edge's first node (IndMat > 0, :86) and M' otherwise; an edge nobody selected keeps
+ * Rij_orig.  Then every edge gets P(block + s N_e), s = sigma_out on a corrupted edge and sigma_in elsewhere (:121-137).
+ * ErrVec = |acos((trace(Rij_orig' RijMat) - 1) / 2)| / pi with the extended |acos| of the cycle kernels for an argument a rounding error
+ * outside [-1, 1].  Operand order on the device: Rij_orig(r, c) = sum_k Ri(r, k) Rj(c, k) in ascending k from 0.0; Q = block + s * N.
+ *
+ * desc_models_batch_max_n: the largest n (65536): n (n - 1) / 2 edges stay below 2^31.
+ * desc_models_batch_create: validates on the host and refuses -- before the device is touched, naming the problem -- n < 2 or above the
+ * cap, a probability (p, q, p_node_crpt, p_edge_crpt) outside [0, 1] or not finite, a negative or non-finite sigma, an unknown kind, an
+ * unknown mode of a Nonuniform problem (DESC_ERR_INVALID); a batch of 2^31 nodes or more or whose expected edge count sum(p_b n_b (n_b -
+ * 1) / 2) reaches 2^30 (DESC_ERR_TOO_LARGE).  Then the graph pass runs: one wave per (problem, row) counts the row's edges (ballot +
+ * popcount), a scan per problem gives the row offsets, the host reads the count edge totals, and a second pass writes the sorted edge
+ * list.  No n x n array exists.  A problem that draws no edge is legal (m = 0).  count == 0 is legal and touches no device.  Without a
+ * device: DESC_ERR_HIP and *out = NULL.
+ * desc_models_batch_sizes: m_per_problem[count].
+ * desc_models_batch_fetch: the node, selection and edge passes, and the copy of the concatenated arrays (problem after problem) into
+ * the caller's buffers, each nullable: ind_i / ind_j (M, 0-based, as desc_problem), rij / rij_orig (M x 9, column-major blocks),
+ * r_orig (N x 9), err_vec (M), corrupted (M).  May be called again; the result is the same. */
+#define DESC_MODELS_KIND_UNIFORM      0
+#define DESC_MODELS_KIND_NONUNIFORM   1
+#define DESC_MODELS_UNIFORM           0
+#define DESC_MODELS_SELF_CONSISTENT   1
+#define DESC_MODELS_ADV               2
+enum { DESC_MODELS_STREAM_EDGE = 1, DESC_MODELS_STREAM_RORIG, DESC_MODELS_STREAM_RCORR, DESC_MODELS_STREAM_CORRUPT,
+       DESC_MODELS_STREAM_NOISE, DESC_MODELS_STREAM_HAAR, DESC_MODELS_STREAM_NODE, DESC_MODELS_STREAM_SELECT, DESC_MODELS_STREAM_R0 };
+typedef struct desc_model_spec {
+    int32_t kind;             /* DESC_MODELS_KIND_*                                                           */
+    int32_t n;
+    double p;                 /* edge probability                                                             */
+    double q;                 /* Uniform: corruption probability                                              */
+    double p_node_crpt;       /* Nonuniform                                                                   */
+    double p_edge_crpt;       /* Nonuniform                                                                   */
+    double sigma;             /* Uniform                                                                      */
+    double sigma_in;          /* Nonuniform: noise of the edges nobody corrupted                              */
+    double sigma_out;         /* Nonuniform: noise of the corrupted edges                                     */
+    int32_t mode;             /* DESC_MODELS_UNIFORM | _SELF_CONSISTENT | _ADV (Nonuniform only)              */
+    int32_t reserved;
+    uint64_t seed;
+} desc_model_spec;            /* 80 bytes */
+typedef struct desc_models_batch desc_models_batch;   /* opaque */
+typedef struct desc_models_batch_timings {
+    double ms_graph;          /* validation, upload and the graph pass (create), wall clock                   */
+    double ms_nodes;          /* the node pass and, with a Nonuniform problem, marking and selection          */
+    double ms_edges;          /* the edge pass                                                                */
+    double ms_copy;           /* device -> host copies into the caller's buffers                              */
+    double ms_total;          /* ms_graph + wall clock of desc_models_batch_fetch                             */
+} desc_models_batch_timings;  /* 40 bytes */
+uint64_t desc_models_key(uint64_t seed, uint64_t stream, uint64_t sub, uint64_t id, uint64_t c);
+int32_t desc_models_batch_max_n(void);
+int desc_models_batch_create(const desc_model_spec* specs, int32_t count, int32_t device, desc_models_batch** out);
+int desc_models_batch_sizes(const desc_models_batch* h, int64_t* m_per_problem);
+int desc_models_batch_fetch(desc_models_batch* h, int32_t* ind_i, int32_t* ind_j, double* rij, double* rij_orig, double* r_orig,
+                            double* err_vec, uint8_t* corrupted, desc_models_batch_timings* timings /* nullable */);
+void desc_models_batch_destroy(desc_models_batch* h);
+/* Test hooks (tests/test_gpu_models_batch.py): the device's draws for ids id0 .. id0 + count - 1 of (seed, stream, sub): the uniform
+ * draw of component c, and the normal draw c.  out: count doubles.  NULL out or a negative count: DESC_ERR_INVALID. */
+int desc_test_models_uniform(uint64_t seed, uint64_t stream, uint64_t sub, uint64_t id0, int64_t count, uint64_t c, int32_t device, double* out);
+int desc_test_models_normal(uint64_t seed, uint64_t stream, uint64_t sub, uint64_t id0, int64_t count, uint64_t c, int32_t device, double* out);
+
 /* One-shot: what the MEX shim calls.  Builds the structure (p->build_where),
  * uploads, runs, downloads, frees. */
 int desc_pgd_solve(const desc_problem* prob, const desc_params* p, desc_result* r);
