@@ -47,6 +47,7 @@ EXPORTS = [
     "desc_lp_batch_plan", "desc_lp_batch_create", "desc_lp_batch_sizes", "desc_lp_batch_get_samples", "desc_lp_batch_run", "desc_lp_batch_destroy",
     "desc_models_key", "desc_models_batch_max_n", "desc_models_batch_create", "desc_models_batch_sizes", "desc_models_batch_fetch",
     "desc_models_batch_destroy", "desc_test_models_uniform", "desc_test_models_normal",
+    "desc_align_batch_create", "desc_align_batch_sizes", "desc_align_batch_run", "desc_align_batch_destroy", "desc_test_align_project",
     "desc_test_laa_r2q", "desc_test_laa_q2r", "desc_test_laa_edge_log", "desc_test_laa_rhs", "desc_test_laa_pcg", "desc_test_laa_node_update",
     "desc_test_irls_node_update", "desc_test_laa_weights", "desc_test_irls_weights", "desc_test_laa_quantile", "desc_test_irls_project",
     "desc_test_irls_pd_stage", "desc_test_irls_pd_solve",
@@ -165,6 +166,10 @@ class ModelSpec(C.Structure):
 class ModelsBatchTimings(C.Structure):
     _fields_ = [("ms_graph", C.c_double), ("ms_nodes", C.c_double), ("ms_edges", C.c_double), ("ms_copy", C.c_double),
                 ("ms_total", C.c_double)]
+
+
+class AlignBatchTimings(C.Structure):
+    _fields_ = [("ms_upload", C.c_double), ("ms_align", C.c_double), ("ms_copy", C.c_double), ("ms_total", C.c_double)]
 
 
 class RefineInfo(C.Structure):
@@ -398,6 +403,12 @@ def load():
     L.desc_models_batch_destroy.restype = None
     L.desc_test_models_uniform.argtypes = [C.c_uint64] * 4 + [C.c_int64, C.c_uint64, C.c_int32, F64P]
     L.desc_test_models_normal.argtypes = [C.c_uint64] * 4 + [C.c_int64, C.c_uint64, C.c_int32, F64P]
+    L.desc_align_batch_create.argtypes = [I32P, F64P, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.desc_align_batch_sizes.argtypes = [C.c_void_p, I32P, I64P]
+    L.desc_align_batch_run.argtypes = [C.c_void_p, F64P, F64P, F64P, F64P, F64P, F64P, C.POINTER(AlignBatchTimings)]
+    L.desc_align_batch_destroy.argtypes = [C.c_void_p]
+    L.desc_align_batch_destroy.restype = None
+    L.desc_test_align_project.argtypes = [F64P, C.c_int64, C.c_int32, F64P]
     L.desc_test_laa_r2q.argtypes = [F64P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, F64P]
     L.desc_test_laa_q2r.argtypes = [F64P, C.c_int64, C.c_int32, F64P]
     L.desc_test_laa_edge_log.argtypes = [C.c_void_p, F64P, F64P, C.c_int64, F64P]
@@ -1085,6 +1096,52 @@ def hook_models_draws(seed, stream, sub, id0, count, c, normal=False, device=0):
     fn = load().desc_test_models_normal if normal else load().desc_test_models_uniform
     check(fn(int(seed), int(stream), int(sub), int(id0), int(count), int(c), int(device), ptr(out, F64P)))
     return out[:int(count)]
+
+
+class AlignBatch(_BatchHandle):
+    """Owner of a desc_align_batch*: the ground-truth rotations of B problems resident on the GPU (desc_align_batch_*).  ``n`` holds the
+    problems' node counts, ``R_gt`` their 3x3xn_b column-major blocks behind one another (9 * sum(n) doubles).  ``run`` scores one set of
+    estimates against them and may be called any number of times."""
+
+    _kind = "align"
+
+    def __init__(self, n, R_gt, device=0):
+        self.n_per = np.ascontiguousarray(n, dtype=np.int32).reshape(-1)
+        self.count = B = int(self.n_per.shape[0])
+        self.R_gt = np.ascontiguousarray(R_gt, dtype=np.float64).reshape(-1)
+        if self.R_gt.shape[0] != 9 * int(np.maximum(self.n_per, 0).sum(dtype=np.int64)):
+            raise ValueError("R_gt must hold 9 * sum(n) doubles")
+        n_arr = self.n_per if B else np.zeros(1, dtype=np.int32)
+        gt = self.R_gt if self.R_gt.shape[0] else np.zeros(1)
+        h = C.c_void_p()
+        check(load().desc_align_batch_create(ptr(n_arr, I32P), ptr(gt, F64P), B, int(device), C.byref(h)))
+        self.handle = h
+        no, cnt = np.zeros(B + 1, dtype=np.int64), C.c_int32()
+        check(load().desc_align_batch_sizes(self.handle, C.byref(cnt), ptr(no, I64P)))
+        self.node_off, self.n = no, int(no[B])
+
+    def run(self, R_est, rotations=True):
+        """One batched alignment of R_est (9 * n doubles, the problems behind one another).  Returns a dict of the concatenated arrays
+        R_out (9 n; None without ``rotations``), R_align (9 B), err (n, degrees), mean_error and median_error (B) -- and the call's timings."""
+        B, N = self.count, self.n
+        est = np.ascontiguousarray(R_est, dtype=np.float64).reshape(-1)
+        if est.shape[0] != 9 * N:
+            raise ValueError(f"R_est must hold 9 * {N} doubles, not {est.shape[0]}")
+        out = dict(R_out=out_buffer(9 * N) if rotations else None, R_align=out_buffer(9 * B), err=out_buffer(N), mean_error=out_buffer(B),
+                   median_error=out_buffer(B))
+        tm = AlignBatchTimings()
+        check(load().desc_align_batch_run(self.handle, ptr(est if N else np.zeros(1), F64P), ptr(out["R_out"], F64P), ptr(out["R_align"], F64P),
+                                          ptr(out["err"], F64P), ptr(out["mean_error"], F64P), ptr(out["median_error"], F64P), C.byref(tm)))
+        sizes = dict(R_out=9 * N, R_align=9 * B, err=N, mean_error=B, median_error=B)
+        return {k: (None if v is None else v[:sizes[k]]) for k, v in out.items()}, _timings(tm)
+
+
+def hook_align_project(A, device=0):
+    """desc_test_align_project: the projection behind R_align of count column-major blocks (count x 9) -> count x 9."""
+    A = np.ascontiguousarray(A, dtype=np.float64).reshape(-1, 9)
+    out = out_buffer(A.size)
+    check(load().desc_test_align_project(ptr(A if A.size else np.zeros(9), F64P), A.shape[0], int(device), ptr(out, F64P)))
+    return out[:A.size].reshape(-1, 9)
 
 
 def gcw_batch_csr(probs):

@@ -1277,3 +1277,58 @@ def Rotation_Alignment(R_est, R_gt):
     x = (tr - 1.0) / 2.0
     err = np.where(np.abs(x) <= 1, np.arccos(np.clip(x, -1, 1)), np.abs(np.arccos(x.astype(complex)))) / np.pi * 180
     return R_out, R_align, float(np.mean(err)), float(np.median(err))
+
+
+def _alignment_blocks(x, b, name):
+    """One entry of Rotation_Alignment_batch's lists as the 9 n doubles of its column-major 3x3xn blocks."""
+    if name == "R_gt" and not isinstance(x, np.ndarray) and hasattr(x, "R_orig"):
+        x = x.R_orig                                         # a model object
+    try:
+        x = np.asarray(x, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"problem {b}: {name} must be a 3x3xn array") from None
+    if x.ndim != 3 or x.shape[0] != 3 or x.shape[1] != 3 or x.shape[2] < 1:
+        raise ValueError(f"problem {b}: {name} must be 3x3xn with n >= 1, not of shape {x.shape}")
+    flat = x.reshape(-1, order="F")                          # any memory order in, the ABI's out
+    if not np.isfinite(flat).all():
+        k = int(np.flatnonzero(~np.isfinite(flat))[0]) // 9
+        raise ValueError(f"problem {b}: {name} of node {k + 1} is not finite")
+    return flat
+
+
+def Rotation_Alignment_batch(R_est_list, R_gt_list, rotations=True, device=0, return_info=False):
+    """Rotation_Alignment (Utils/Rotation_Alignment.m:13-38) of many problems in one GPU pass: a list of the tuples (R_out, R_align,
+    mean_error, median_error) Rotation_Alignment returns, one per problem.  R_out is Fortran-ordered 3x3xn, or None with
+    ``rotations=False`` (it is three quarters of what comes back).  An entry of ``R_gt_list`` is a 3x3xn array or a model object, whose
+    R_orig is used; arrays may be in any memory order.  With ``return_info`` every tuple gets a fifth member dict(err=..., timings=...),
+    err the per-node errors in degrees.  Non-finite entries are refused: the nodes IRLS_GM leaves NaN outside the largest component must
+    be masked by the caller.  Two empty lists give []."""
+    for name, lst in (("R_est_list", R_est_list), ("R_gt_list", R_gt_list)):
+        if isinstance(lst, (str, bytes, np.ndarray)) or not hasattr(lst, "__len__") or not hasattr(lst, "__getitem__"):
+            raise ValueError(f"{name} must be a sequence of 3x3xn arrays")
+    if len(R_est_list) != len(R_gt_list):
+        raise ValueError(f"R_est_list holds {len(R_est_list)} problems, R_gt_list {len(R_gt_list)}")
+    if not isinstance(device, (int, np.integer)) or isinstance(device, bool) or device < 0:
+        raise ValueError("device must be a non-negative integer")
+    est, gt = [], []
+    for b, (e, g) in enumerate(zip(R_est_list, R_gt_list)):
+        est.append(_alignment_blocks(e, b, "R_est"))
+        gt.append(_alignment_blocks(g, b, "R_gt"))
+        if est[-1].shape[0] != gt[-1].shape[0]:
+            raise ValueError(f"problem {b}: R_est has n = {est[-1].shape[0] // 9}, R_gt n = {gt[-1].shape[0] // 9}")
+    if not est:                                              # the empty batch touches no device
+        return []
+    if sum(x.shape[0] for x in gt) >= 2 ** 31:
+        raise ValueError("the batch holds 2^31 / 9 nodes or more: split the batch")
+    batch = _lib.AlignBatch([x.shape[0] // 9 for x in gt], np.concatenate(gt), device=int(device))
+    try:
+        out, timings = batch.run(np.concatenate(est), rotations=bool(rotations))
+    finally:
+        batch.destroy()
+    R_out = _lib._split_R(out["R_out"], batch.node_off) if rotations else [None] * batch.count
+    res = []
+    for b in range(batch.count):
+        n0, n1 = int(batch.node_off[b]), int(batch.node_off[b + 1])
+        t = (R_out[b], out["R_align"][9 * b:9 * b + 9].reshape((3, 3), order="F"), float(out["mean_error"][b]), float(out["median_error"][b]))
+        res.append(t + (dict(err=out["err"][n0:n1], timings=timings),) if return_info else t)
+    return res

@@ -1,4 +1,4 @@
-// Device half of a batched handle, shared by batch.hip (with batch_structure.hip on its handle), gcw_batch.hip, cemp_batch.hip (with mpls_batch.hip on its handle), mst_batch.hip, refine_batch.hip, irls_batch.hip, lp_batch.hip and models_batch.hip: the device,
+// Device half of a batched handle, shared by batch.hip (with batch_structure.hip on its handle), gcw_batch.hip, cemp_batch.hip (with mpls_batch.hip on its handle), mst_batch.hip, refine_batch.hip, irls_batch.hip, lp_batch.hip, models_batch.hip and align_batch.hip: the device,
 // one pooled stream, the arena of device blocks, the event pair around a timed launch, and the create wrapper of the C entry points.
 // Host code only.  A batched call supplies its host validation, its kernels and its words for the refusals; the order of the
 // refusals (nothing touches the device before open) and of the teardown is decided here.
@@ -68,7 +68,7 @@ struct BatchDevice {
 // The body of desc_*_batch_create: argument checks, a fresh handle H, body(h); *out gets the handle only if body returned DESC_OK.
 // Otherwise the handle is destroyed -- after an exception too -- and body's message is raised again, the teardown having HIP calls
 // of its own.  args_ok: what the call needs besides probs.
-// P: desc_problem, or the record a generator takes in its place (desc_model_spec).
+// P: desc_problem, or the record a generator takes in its place (desc_model_spec), or the node counts of desc_align_batch_create.
 template <class H, class P, class Body>
 int batch_create_guarded(const char* name, H** out, const P* probs, int32_t count, Body&& body, bool args_ok = true) {
     return no_throw(name, [&]() -> int {

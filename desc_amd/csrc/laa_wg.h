@@ -9,6 +9,7 @@
 //                          the exp map, Q <- Q * W, the score in chunks of 256 rows
 //   wg_quantile            MATLAB's quantile of a per-edge array: the extrema, the Hazen position, the two order statistics by an exact
 //                          radix select over the 64-bit order key (8-bit digits, integer histogram in LDS), their interpolation
+//   wg_select              that radix select alone: the order statistics of two neighbouring ranks (also the median of align_batch.hip)
 // Reductions keep the single path's orders: a CSR row by the 16 lanes of a DPP row (rhs_row16 / lap_row16), the PCG's dot products by
 // k_cg_dot's loop and block_reduce<3, 0>, the score by score_chunk_sum added in ascending order from 0.0.
 //
@@ -192,24 +193,16 @@ __device__ __forceinline__ double wg_laa_step(const WgLaa& s, int cg_max, WgCg& 
     return tot / (double)n;
 }
 
-// quantile(RS[0..m), p) into *thresh.  lo / hi: the extrema of this thread's entries (e = tid, tid + 256, ...); RS may have been
-// written just before the call without a barrier in between: the first barrier below orders it.  Returns 0, or 1 where the selection
-// found no candidate (the same in every thread; *thresh is then not written).  Every barrier it holds is passed by all threads or none.
-__device__ __forceinline__ int wg_quantile(const double* RS, int m, double p, double lo, double hi, double* thresh) {
-    __shared__ double mm[8];
+// The order statistics of the 0-based ranks k0 and, with next_too, k0 + 1 of RS[0..m) as order keys (key_value gives the doubles): an
+// exact radix select, shared by wg_quantile below and k_align_batch's median (align_batch.hip).  k0 and next_too are the same in every
+// thread; without next_too *key_hi = *key_lo.  RS may have been written just before the call without a barrier in between: the first
+// barrier below orders it.  Returns 0, or 1 where the selection found no candidate (the same in every thread; the keys are then not
+// written).  Every barrier it holds is passed by all threads or none.
+__device__ __forceinline__ int wg_select(const double* RS, int m, int64_t k0, bool next_too, unsigned long long* key_lo, unsigned long long* key_hi) {
     __shared__ unsigned hist[256];
     __shared__ unsigned cnt_le;
     __shared__ unsigned long long key_gt;
     const int tid = threadIdx.x;
-    for (int off = 32; off >= 1; off >>= 1) { lo = fmin(lo, __shfl_xor(lo, off)); hi = fmax(hi, __shfl_xor(hi, off)); }
-    if ((tid & 63) == 0) { mm[tid >> 6] = lo; mm[4 + (tid >> 6)] = hi; }
-    __syncthreads();                                                                    // RS, the wave extrema
-    lo = fmin(fmin(mm[0], mm[1]), fmin(mm[2], mm[3])); hi = fmax(fmax(mm[4], mm[5]), fmax(mm[6], mm[7]));
-    int64_t k0 = 0; double fr = 0.0;
-    const int where = uni(hazen_position((int64_t)m, p, &k0, &fr));
-    if (where == HAZEN_MIN) { *thresh = lo; return 0; }
-    if (where == HAZEN_MAX) { *thresh = hi; return 0; }
-    if (uni(hazen_flat(lo, hi))) { *thresh = lo; return 0; }
     // the order statistic of rank k0: radix select over the order key, most significant digit first
     unsigned long long prefix = 0;
     unsigned rank = (unsigned)k0;
@@ -233,6 +226,7 @@ __device__ __forceinline__ int wg_quantile(const double* RS, int m, double p, do
         rank -= uni((int)acc);
         prefix |= (unsigned long long)d << shift;
     }
+    if (!next_too) { *key_lo = prefix; *key_hi = prefix; return 0; }
     // rank k0 + 1: the same value if more than k0 + 1 keys are <= it, else the smallest key above it
     if (tid == 0) { cnt_le = 0; key_gt = ~0ull; }
     __syncthreads();
@@ -252,6 +246,27 @@ __device__ __forceinline__ int wg_quantile(const double* RS, int m, double p, do
         if (uni(next == ~0ull)) return 1;
         upper = next;
     }
+    *key_lo = prefix; *key_hi = upper;
+    return 0;
+}
+
+// quantile(RS[0..m), p) into *thresh.  lo / hi: the extrema of this thread's entries (e = tid, tid + 256, ...); RS may have been
+// written just before the call without a barrier in between: the first barrier below orders it.  Returns 0, or 1 where the selection
+// found no candidate (the same in every thread; *thresh is then not written).  Every barrier it holds is passed by all threads or none.
+__device__ __forceinline__ int wg_quantile(const double* RS, int m, double p, double lo, double hi, double* thresh) {
+    __shared__ double mm[8];
+    const int tid = threadIdx.x;
+    for (int off = 32; off >= 1; off >>= 1) { lo = fmin(lo, __shfl_xor(lo, off)); hi = fmax(hi, __shfl_xor(hi, off)); }
+    if ((tid & 63) == 0) { mm[tid >> 6] = lo; mm[4 + (tid >> 6)] = hi; }
+    __syncthreads();                                                                    // RS, the wave extrema
+    lo = fmin(fmin(mm[0], mm[1]), fmin(mm[2], mm[3])); hi = fmax(fmax(mm[4], mm[5]), fmax(mm[6], mm[7]));
+    int64_t k0 = 0; double fr = 0.0;
+    const int where = uni(hazen_position((int64_t)m, p, &k0, &fr));
+    if (where == HAZEN_MIN) { *thresh = lo; return 0; }
+    if (where == HAZEN_MAX) { *thresh = hi; return 0; }
+    if (uni(hazen_flat(lo, hi))) { *thresh = lo; return 0; }
+    unsigned long long prefix = 0, upper = 0;
+    if (wg_select(RS, m, k0, true, &prefix, &upper)) return 1;
     *thresh = hazen_interp(key_value(prefix), key_value(upper), fr);
     return 0;
 }

@@ -14,6 +14,8 @@ default) or for the whole batch on the device; the curves are the same to the la
 
 --rotations: the demo's own metric next to it -- one DESC_init_batch call (the PGD pass, then the batched GCW eigen-solve) and the mean
 rotation error in degrees (Rotation_Alignment against the ground truth), the column of Demo/compare_algorithms.m.
+Every rotation curve is scored by Rotation_Alignment_batch: the curves that share the ground truth go into one call, whose time is
+printed next to the solver's.
 --refined: the headline row, DESC() itself -- one DESC_batch call (the two passes of DESC_init_batch, then the batched reweighted
 refinement) and the mean rotation error of R_est next to that of its initialisation R_init.
 --baselines: the curves DESC is drawn against, one batched call per curve -- CEMP's SVec error (CEMP_batch) and the rotation errors of
@@ -36,8 +38,25 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from desc_amd import (CEMP_GCW_batch, CEMP_MST_batch, CEMP_batch, ConstantStepSize, DESC_PGD_batch, DESC_batch,  # noqa: E402
-                      DESC_init_batch, IRLS_GM_batch, IRLS_L12_batch, MPLS_batch, Rotation_Alignment, Uniform_Topology, Uniform_Topology_batch,
+                      DESC_init_batch, IRLS_GM_batch, IRLS_L12_batch, MPLS_batch, Rotation_Alignment_batch, Uniform_Topology, Uniform_Topology_batch,
                       linprog_sij_batch)
+
+
+def score(curves, models, shape):
+    """The mean rotation errors (degrees) of several curves against one ground truth in ONE Rotation_Alignment_batch call: the curves'
+    estimates behind one another, the models repeated.  Nodes a solver left NaN (IRLS, outside the largest component) are masked here,
+    as the call requires.  Returns the curves' errors, each reshaped to (q, trial), and the call's time in ms."""
+    est, gt = [], []
+    for curve in curves:
+        for R, mo in zip(curve, models):
+            keep = np.isfinite(R).all(axis=(0, 1))
+            est.append(R if keep.all() else R[:, :, keep])
+            gt.append(mo if keep.all() else mo.R_orig[:, :, keep])
+    t0 = time.perf_counter()
+    out = Rotation_Alignment_batch(est, gt, rotations=False)
+    ms = (time.perf_counter() - t0) * 1e3
+    B = len(models)
+    return [np.array([t[2] for t in out[k * B:(k + 1) * B]]).reshape(shape) for k in range(len(curves))], ms
 
 
 def baselines(models, qs, trials):
@@ -50,12 +69,11 @@ def baselines(models, qs, trials):
     t2 = time.perf_counter()
     R_mst = CEMP_MST_batch(models, cemp)
     t3 = time.perf_counter()
-    print(f"baselines, one call per curve: CEMP_batch {(t1 - t0) * 1e3:.1f} ms, CEMP_GCW_batch {(t2 - t1) * 1e3:.1f} ms, "
-          f"CEMP_MST_batch {(t3 - t2) * 1e3:.1f} ms")
     shape = (len(qs), trials)
     err = np.array([np.abs(s - mo.ErrVec).mean() for s, mo in zip(S, models)]).reshape(shape)
-    gcw = np.array([Rotation_Alignment(R, mo.R_orig)[2] for R, mo in zip(R_gcw, models)]).reshape(shape)
-    mst = np.array([Rotation_Alignment(R, mo.R_orig)[2] for R, mo in zip(R_mst, models)]).reshape(shape)
+    (gcw, mst), ms_score = score([R_gcw, R_mst], models, shape)
+    print(f"baselines, one call per curve: CEMP_batch {(t1 - t0) * 1e3:.1f} ms, CEMP_GCW_batch {(t2 - t1) * 1e3:.1f} ms, "
+          f"CEMP_MST_batch {(t3 - t2) * 1e3:.1f} ms; scoring both rotation curves in one Rotation_Alignment_batch call {ms_score:.1f} ms")
     print("    q   CEMP mean |SVec - ErrVec|   CEMP+GCW rotation error, degrees   CEMP+MST rotation error, degrees   (means over the trials)")
     for q, a, b, c in zip(qs, err, gcw, mst):
         print(f" {q:4.2f}   {a.mean():.4f}                     {b.mean():8.4f}                           {c.mean():8.4f}")
@@ -69,10 +87,10 @@ def mpls_curve(models, qs, trials):
     t0 = time.perf_counter()
     out = MPLS_batch(models, cemp, mpls, return_info=True)
     ms = (time.perf_counter() - t0) * 1e3
-    print(f"MPLS, {len(models)} problems in one MPLS_batch call: {ms:.1f} ms (the loop's launch {out[0][2]['mpls']['timings']['ms_loop']:.1f} ms)")
     shape = (len(qs), trials)
-    est = np.array([Rotation_Alignment(R, mo.R_orig)[2] for (R, _, _), mo in zip(out, models)]).reshape(shape)
-    ini = np.array([Rotation_Alignment(R, mo.R_orig)[2] for (_, R, _), mo in zip(out, models)]).reshape(shape)
+    (est, ini), ms_score = score([[R for R, _, _ in out], [R for _, R, _ in out]], models, shape)
+    print(f"MPLS, {len(models)} problems in one MPLS_batch call: {ms:.1f} ms (the loop's launch {out[0][2]['mpls']['timings']['ms_loop']:.1f} ms); "
+          f"scoring in one Rotation_Alignment_batch call {ms_score:.1f} ms")
     its = np.array([info["mpls"]["iters"] for _, _, info in out]).reshape(shape)
     print("    q   MPLS rotation error, degrees   (min .. max)          its initialisation's (CEMP+MST)   iterations (min .. max)")
     for q, re, ri, ni in zip(qs, est, ini, its):
@@ -84,11 +102,11 @@ def lp_curve(models, qs, trials):
     t0 = time.perf_counter()
     out = linprog_sij_batch(models, dict(seed=0), return_info=True)
     ms = (time.perf_counter() - t0) * 1e3
-    print(f"linprog_sij, {len(models)} problems in one linprog_sij_batch call: {ms:.1f} ms (the LP loop {out[0][2]['lp']['timings']['ms_loop']:.1f} ms)")
     shape = (len(qs), trials)
     err = np.array([np.abs(s - mo.ErrVec).mean() for (_, s, _), mo in zip(out, models)]).reshape(shape)
-    est = np.array([Rotation_Alignment(R, mo.R_orig)[2] for (R, _, _), mo in zip(out, models)]).reshape(shape)
-    ini = np.array([Rotation_Alignment(info["R_gcw"], mo.R_orig)[2] for (_, _, info), mo in zip(out, models)]).reshape(shape)
+    (est, ini), ms_score = score([[R for R, _, _ in out], [info["R_gcw"] for _, _, info in out]], models, shape)
+    print(f"linprog_sij, {len(models)} problems in one linprog_sij_batch call: {ms:.1f} ms (the LP loop {out[0][2]['lp']['timings']['ms_loop']:.1f} ms); "
+          f"scoring in one Rotation_Alignment_batch call {ms_score:.1f} ms")
     its = np.array([info["lp"]["iters"] for _, _, info in out]).reshape(shape)
     print("    q   mean |S_vec - ErrVec|   linprog_sij rotation error, degrees   its spectral start's (R_gcw)   PDHG steps (min .. max)")
     for q, e, re, ri, ni in zip(qs, err, est, ini, its):
@@ -102,12 +120,11 @@ def irls_curves(models, qs, trials):
     t1 = time.perf_counter()
     l12 = IRLS_L12_batch(models, return_info=True)
     t2 = time.perf_counter()
-    print(f"IRLS, {len(models)} problems, one call per curve: IRLS_GM_batch {(t1 - t0) * 1e3:.1f} ms (its solve launch "
-          f"{gm[0][1]['timings']['ms_solve']:.1f} ms), IRLS_L12_batch {(t2 - t1) * 1e3:.1f} ms")
     shape = (len(qs), trials)
-    e_gm = np.array([Rotation_Alignment(R, mo.R_orig)[2] for (R, _), mo in zip(gm, models)]).reshape(shape)
-    e_l12 = np.array([Rotation_Alignment(R, mo.R_orig)[2] for (R, _), mo in zip(l12, models)]).reshape(shape)
-    e_l1 = np.array([Rotation_Alignment(info["R_l1"], mo.R_orig)[2] for (_, info), mo in zip(gm, models)]).reshape(shape)
+    (e_gm, e_l12, e_l1), ms_score = score([[R for R, _ in gm], [R for R, _ in l12], [info["R_l1"] for _, info in gm]], models, shape)
+    print(f"IRLS, {len(models)} problems, one call per curve: IRLS_GM_batch {(t1 - t0) * 1e3:.1f} ms (its solve launch "
+          f"{gm[0][1]['timings']['ms_solve']:.1f} ms), IRLS_L12_batch {(t2 - t1) * 1e3:.1f} ms; scoring the three curves in one "
+          f"Rotation_Alignment_batch call {ms_score:.1f} ms")
     n_gm = np.array([info["irls_iters"] for _, info in gm]).reshape(shape)
     n_l12 = np.array([info["irls_iters"] for _, info in l12]).reshape(shape)
     print("    q   IRLS-GM rotation error, degrees   IRLS-L0.5 rotation error, degrees   their L1 start's (R_l1)   IRLS steps GM / L0.5 (min .. max)")
@@ -146,9 +163,9 @@ def main():
         ms = (time.perf_counter() - t0) * 1e3
         shape = (len(qs), a.trials)
         err = np.array([np.abs(s - mo.ErrVec).mean() for (_, _, s), mo in zip(out, models)]).reshape(shape)
-        est = np.array([Rotation_Alignment(R, mo.R_orig)[2] for (R, _, _), mo in zip(out, models)]).reshape(shape)
-        ini = np.array([Rotation_Alignment(R, mo.R_orig)[2] for (_, R, _), mo in zip(out, models)]).reshape(shape)
-        print(f"{len(models)} problems (n = {a.n}, {a.trials} trials per q) in one DESC_batch call: {ms:.1f} ms")
+        (est, ini), ms_score = score([[R for R, _, _ in out], [R for _, R, _ in out]], models, shape)
+        print(f"{len(models)} problems (n = {a.n}, {a.trials} trials per q) in one DESC_batch call: {ms:.1f} ms; "
+              f"scoring in one Rotation_Alignment_batch call {ms_score:.1f} ms")
         print("    q   mean |S_vec - ErrVec|   DESC rotation error, degrees   (min .. max)          its initialisation's (R_init)")
         for q, row, re, ri in zip(qs, err, est, ini):
             print(f" {q:4.2f}   {row.mean():.4f}                {re.mean():8.4f}                       ({re.min():.4f} .. {re.max():.4f})      {ri.mean():8.4f}")
@@ -171,7 +188,8 @@ def main():
     err = np.array([np.abs(s - mo.ErrVec).mean() for s, mo in zip(S, models)]).reshape(len(qs), a.trials)
     print(f"{len(models)} problems (n = {a.n}, {a.trials} trials per q) in one {'DESC_init_batch' if a.rotations else 'DESC_PGD_batch'} call: {ms:.1f} ms")
     if a.rotations:
-        rot = np.array([Rotation_Alignment(R, mo.R_orig)[2] for (R, _), mo in zip(out, models)]).reshape(len(qs), a.trials)
+        (rot,), ms_score = score([[R for R, _ in out]], models, (len(qs), a.trials))
+        print(f"scoring in one Rotation_Alignment_batch call: {ms_score:.1f} ms")
         print("    q   mean |S_vec - ErrVec|   (min .. max)          mean rotation error, degrees   (min .. max over the trials)")
         for q, row, rr in zip(qs, err, rot):
             print(f" {q:4.2f}   {row.mean():.4f}                ({row.min():.4f} .. {row.max():.4f})      {rr.mean():8.4f}"

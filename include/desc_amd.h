@@ -941,6 +941,54 @@ void desc_models_batch_destroy(desc_models_batch* h);
 int desc_test_models_uniform(uint64_t seed, uint64_t stream, uint64_t sub, uint64_t id0, int64_t count, uint64_t c, int32_t device, double* out);
 int desc_test_models_normal(uint64_t seed, uint64_t stream, uint64_t sub, uint64_t id0, int64_t count, uint64_t c, int32_t device, double* out);
 
+/* ------------------------------------------------- batched rotation alignment -- */
+/* Utils/Rotation_Alignment.m:13-38 for B problems in one GPU pass (csrc/align_batch.hip): the scoring behind the *_batch solvers of a
+ * Monte-Carlo study.  One launch, one workgroup of 256 threads per problem.  The problems' 3 x 3 x n_b column-major blocks lie behind
+ * one another, problem b's from 9 * node_off[b] (as R_out of desc_gcw_batch_run); N = sum(n).  tests/align_batch_oracle.py restates
+ * the orders below in NumPy.
+ *
+ * Operand orders on the device (the library is built without contraction; they are part of the interface):
+ *   A (:18-22)        thread t of the workgroup takes the nodes t, t + 256, ... in ascending order; per node the entry (r, c) is
+ *                     sum_a R_est(a, r) R_gt(a, c) in ascending a from 0.0, added to the thread's running sum of that entry.  The 256
+ *                     partials: the 64 lanes of a wave by the fixed butterfly desc_selftest_group_sum exposes (G = 64), then
+ *                     ((wave 0 + wave 1) + wave 2) + wave 3.
+ *   R_align (:24-25)  U1 diag(1, 1, det(U1 V1')) V1' of A by a one-sided Jacobi SVD (A V = U S; pairs (0,1), (0,2), (1,2), at most 40
+ *                     sweeps, a pair is skipped when |g| <= 1e-17 sqrt(a b)), the singular values sorted descending; u1 = a1 / |a1|,
+ *                     u2 = (a2 - (u1'a2) u1) normalised, the third left vector det(V) (u1 x u2):
+ *                     R_align(r, c) = (u1(r) v1(c) + u2(r) v2(c)) + u3(r) v3(c).  Ill-defined as (s2 + sign(det A) s3) / s1 -> 0.
+ *   R_out (:30-32)    R_out_k(r, c) = sum_j R_est_k(r, j) R_align(j, c) in ascending j from 0.0.
+ *   err (:33-34)      tr = sum of R_gt_k .* R_out_k over the nine entries in column-major order from 0.0;
+ *                     err_k = |acos((tr - 1) / 2)| / pi * 180 (degrees), with the extended |acos| of the cycle kernels for an
+ *                     argument a rounding error outside [-1, 1].
+ *   mean_error (:35)  thread t adds err_t, err_(t + 256), ... from 0.0; the 256 partials as for A; the total / n.
+ *   median_error (:36) MATLAB's median by an exact selection: n odd, the order statistic of rank (n + 1) / 2; n even, a + (b - a) / 2
+ *                     of the two middle order statistics a <= b.
+ * No bit of a problem depends on the batch around it or on its position.
+ *
+ * desc_align_batch_create: n[count], R_gt: 9 N doubles.  Validates on the host and refuses -- before the device is touched, naming the
+ * problem -- n_b < 1, a non-finite entry of R_gt (naming the 1-based node as well) (DESC_ERR_INVALID); 9 N >= 2^31, i.e. 2^31 / 9 nodes
+ * or more (DESC_ERR_TOO_LARGE, before R_gt is read).  The handle keeps the ground truth on the device.  count == 0 is legal and touches no
+ * device.  Without a device: DESC_ERR_HIP and *out = NULL.
+ * desc_align_batch_sizes: *count and node_off[count + 1], each nullable.
+ * desc_align_batch_run: scores R_est (9 N) against the handle's ground truth; may be called any number of times.  A non-finite entry of
+ * R_est is refused as in create, before this call touches the device.  R_out (9 N) and err (N) are nullable -- R_out is three quarters
+ * of the bytes that come back --; R_align (9 count), mean_error and median_error (count) are required. */
+typedef struct desc_align_batch desc_align_batch;   /* opaque */
+typedef struct desc_align_batch_timings {
+    double ms_upload;         /* the finite check of R_est and its upload, wall clock                        */
+    double ms_align;          /* the launch, wall clock to the drained stream                                 */
+    double ms_copy;           /* device -> host copies into the caller's buffers                              */
+    double ms_total;          /* wall clock of desc_align_batch_run                                           */
+} desc_align_batch_timings;   /* 32 bytes */
+int desc_align_batch_create(const int32_t* n, const double* R_gt, int32_t count, int32_t device, desc_align_batch** out);
+int desc_align_batch_sizes(const desc_align_batch* h, int32_t* count, int64_t* node_off);
+int desc_align_batch_run(desc_align_batch* h, const double* R_est, double* R_out /* nullable */, double* R_align, double* err /* nullable */,
+                         double* mean_error, double* median_error, desc_align_batch_timings* timings /* nullable */);
+void desc_align_batch_destroy(desc_align_batch* h);
+/* Test hook (tests/test_gpu_align_batch.py): the projection of R_align alone on count column-major blocks A (destroyed on the device
+ * only), one thread per block.  NULL A or R, or a negative count: DESC_ERR_INVALID. */
+int desc_test_align_project(const double* A, int64_t count, int32_t device, double* R);
+
 /* One-shot: what the MEX shim calls.  Builds the structure (p->build_where),
  * uploads, runs, downloads, frees. */
 int desc_pgd_solve(const desc_problem* prob, const desc_params* p, desc_result* r);
