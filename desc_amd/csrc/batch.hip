@@ -7,7 +7,7 @@
 // Layout.  The structures are built per problem by the host builder (local ids: bit-exact with a solve of the problem alone) and
 // concatenated with per-problem edge / cycle offsets added (batch_concat) -- or, with desc_pgd_batch_create_where(DESC_BUILD_DEVICE),
 // the same arrays, element for element, are made for the whole batch on the device (batch_structure.hip); batch_finish and the run
-// see no difference.  The sweep is the gather sweep of pgd.hip (k_sweep<G, STEP>):
+// see no difference.  The sweep is the gather sweep of sweep_gather.hip (k_sweep<G, STEP>):
 // a group of G lanes per segment, mirror sums from direct gathers of w_old[ikj] / w_old[jki], tangent projection, plugin step, simplex
 // projection, new S -- the arithmetic comes from pgd_math.h, shared with pgd.hip.
 //
@@ -69,7 +69,7 @@ struct BatchArgs {
     StepArgs st;
 };
 
-// the loop of k_sweep<G, STEP> (pgd.hip) over the segments lo .. hi of one problem
+// the loop of k_sweep<G, STEP> (sweep_gather.hip) over the segments lo .. hi of one problem
 template <int G, int STEP>
 __device__ __forceinline__ void batch_sweep_run(const BatchArgs& a, int lo, int hi, double& obj_acc, double& chg_acc) {
     constexpr int EPW = 64 / G;

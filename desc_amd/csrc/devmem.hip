@@ -4,6 +4,7 @@
 // handed out again (best fit, at most 25 % larger than asked) instead of going back to the driver, up to DESC_CACHE_MB
 // (default 8192, at most a quarter of the device memory; 0 = off) per process; desc_trim_memory() returns everything parked to the driver
 // (the MEX shims register it with mexAtExit).
+// Also here: the plain device exports (device count, synchronise, host <-> device copies) and the self-test of the group reductions.
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
@@ -209,6 +210,13 @@ size_t host_block_trim() {
     return freed;
 }
 
+// self-test kernel for the group reductions (tests/test_gpu_parity.py)
+__global__ void k_selftest_group_sum(const double* in, double* out, int G) {
+    const int t = threadIdx.x + blockIdx.x * blockDim.x;
+    const double v = in[t];
+    out[t] = (G == 16) ? group_sum<16>(v) : (G == 32) ? group_sum<32>(v) : group_sum<64>(v);
+}
+
 }  // namespace desc
 
 extern "C" int64_t desc_trim_memory(void) {
@@ -238,3 +246,46 @@ extern "C" int64_t desc_trim_memory(void) {
     (void)hipSetDevice(cur);
     return freed;
 }
+
+using namespace desc;
+
+extern "C" {
+
+int desc_device_count(void) {
+    int c = 0;
+    hipError_t e = hipGetDeviceCount(&c);
+    if (e != hipSuccess) return fail(DESC_ERR_HIP, "hipGetDeviceCount: %s", hipGetErrorString(e));
+    return c;
+}
+
+int desc_device_synchronize(int32_t device) {
+    DESC_HIP(hipSetDevice(device));
+    DESC_HIP(hipDeviceSynchronize());
+    return DESC_OK;
+}
+int desc_memcpy_d2h(void* host_dst, const void* dev_src, size_t bytes) {
+    if (bytes) DESC_HIP(hipMemcpy(host_dst, dev_src, bytes, hipMemcpyDeviceToHost));
+    return DESC_OK;
+}
+int desc_memcpy_h2d(void* dev_dst, const void* host_src, size_t bytes) {
+    if (bytes) DESC_HIP(hipMemcpy(dev_dst, host_src, bytes, hipMemcpyHostToDevice));
+    return DESC_OK;
+}
+
+// test hook: group_sum over a buffer of 64*k doubles
+int desc_selftest_group_sum(const double* in, double* out, int32_t count, int32_t G, int32_t device) {
+    if (!in || !out || count <= 0 || count % 64) return fail(DESC_ERR_INVALID, "count must be a positive multiple of 64");
+    if (G != 16 && G != 32 && G != 64) return fail(DESC_ERR_INVALID, "G must be 16, 32 or 64");
+    DESC_HIP(hipSetDevice(device));
+    double *di = nullptr, *dout = nullptr;
+    DESC_HIP(hipMalloc((void**)&di, sizeof(double) * count));
+    DESC_HIP(hipMalloc((void**)&dout, sizeof(double) * count));
+    DESC_HIP(hipMemcpy(di, in, sizeof(double) * count, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_selftest_group_sum, dim3(count / 64), dim3(64), 0, 0, di, dout, G);
+    DESC_HIP(hipDeviceSynchronize());
+    DESC_HIP(hipMemcpy(out, dout, sizeof(double) * count, hipMemcpyDeviceToHost));
+    (void)hipFree(di); (void)hipFree(dout);
+    return DESC_OK;
+}
+
+}  // extern "C"

@@ -45,6 +45,10 @@
 // sweep.  The early-stop test of iteration t is therefore evaluated on the device
 // during sweep t+1; when it fires, sweep t+1's output is discarded (the Jacobi double
 // buffers still hold iteration t) and later launches return at once.
+//
+// Units: the three sweep families -- kernels, instance table and launcher each -- are sweep_gather.hip, sweep_node.hip and sweep_band.hip;
+// struct desc_pgd and what they share with this file are in pgd_handle.h (host) and pgd_device.h (device).  k_objective and k_init of the
+// gather layout stay here, with the entry points that launch them.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -54,24 +58,9 @@
 #include <thread>
 #include <vector>
 
-#include "device_utils.h"
-#include "node_plan.h"
-#include "pgd_math.h"
+#include "pgd_handle.h"
 
 namespace desc {
-
-struct DevState {
-    int32_t stop;          // 1 once the patience rule fired
-    int32_t misses;        // DESC_PGD.m:181
-    int32_t iters_run;     // iteration at which the loop broke
-    int32_t final_parity;  // which double buffer holds the final iterate
-    int32_t last_tested;   // last iteration whose stop test (:243-256) has been applied: a download between
-                           // iterations evaluates the objective early, the next sweep must not count it again
-};
-
-// The mirror-weight sums travel as 64-bit fixed-point integers (k_colsum_node: order-independent adds; sharded runs reduce-scatter them as
-// ncclInt64, so the totals -- and with them S_vec and the weights -- are bitwise the same for every number of ranks).  `t` holds the bits.
-__device__ __forceinline__ double fx_to_double(double t, double fx_inv) { return (double)__double_as_longlong(t) * fx_inv; }
 
 // the same with the third factor already loaded (k_layout_node_dev<.., STAGED>: node i's blocks sit in the LDS)
 __device__ __forceinline__ double cycle_trace_regs(const double* A, const double* pb, bool tb, const double* Cm, bool tc) {
@@ -97,169 +86,6 @@ __device__ __forceinline__ double cycle_trace_regs(const double* A, const double
     return tr;
 }
 
-// deterministic workgroup partials (blockDim 256 or 512)
-__device__ __forceinline__ void block_partials(double obj_acc, double chg_acc, double* partials, int lb) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    obj_acc = group_sum<64>(obj_acc);
-    chg_acc = group_sum<64>(chg_acc);
-    __shared__ double sh[16];
-    if (lane == 0) { sh[wv] = obj_acc; sh[8 + wv] = chg_acc; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double o = 0.0, c = 0.0;
-        for (int k = 0; k < nw; ++k) { o += sh[k]; c += sh[8 + k]; }
-        partials[2 * lb] = o;
-        partials[2 * lb + 1] = c;
-    }
-}
-
-// ===========================================================================
-// GATHER variant
-// ===========================================================================
-struct SweepArgs {
-    const int32_t* cum;       // m_pos+1
-    const int32_t* pos_edge;  // m_pos
-    const int32_t* e_jk;
-    const int32_t* e_ki;
-    const int32_t* ikj;
-    const int32_t* jki;
-    const double* S0;
-    const double* w_old;
-    double* w_new;
-    const double* S_old;
-    double* S_new;
-    const double* nv_tab;     // nv_tab[c] = 1/sqrt(c)   (DESC_PGD.m:199)
-    double* partials;         // [grid][2]: objective of the old iterate, sum |dS|
-    const DevState* state;
-    StepArgs st;
-    int32_t m_pos;
-};
-
-template <int G, int STEP>
-__global__ __launch_bounds__(256) void k_sweep(SweepArgs a) {
-    if (a.state->stop) return;
-    constexpr int EPW = 64 / G;
-    const int lane = threadIdx.x & 63;
-    const int wv = threadIdx.x >> 6;
-    const int sub = lane / G, gl = lane % G;
-    const int nb = gridDim.x;
-    const int lb = xcd_logical_block(blockIdx.x, nb);
-    const int per_block = (a.m_pos + nb - 1) / nb;
-    const int lo_edge = lb * per_block;
-    const int hi_edge = min(a.m_pos, lo_edge + per_block);
-
-    double obj_acc = 0.0, chg_acc = 0.0;
-    for (int l0 = lo_edge + wv * EPW; l0 < hi_edge; l0 += 4 * EPW) {
-        const int l = l0 + sub;
-        const bool edge_ok = l < hi_edge;
-        int base = 0, cnt = 0;
-        if (edge_ok) { base = a.cum[l]; cnt = a.cum[l + 1] - base; }
-        const bool act0 = gl < cnt;
-        const int64_t c = (int64_t)base + gl;
-
-        double w = 0.0, d = 0.0, ssum = 0.0, wa = 0.0, wb = 0.0;
-        int ia = -1, ib = -1;
-        if (act0) {
-            const int ejk = a.e_jk[c], eki = a.e_ki[c];
-            ia = a.ikj[c]; ib = a.jki[c];
-            w = a.w_old[c]; d = a.S0[c];
-            ssum = a.S_old[ejk] + a.S_old[eki];
-            if (ia >= 0) wa = a.w_old[ia];
-            if (ib >= 0) wb = a.w_old[ib];
-        }
-        obj_acc += w * ssum;                       // objective of the iterate being read (:233, one sweep late)
-        // mirror-weight sums: one scalar per edge, applied to masked positions only (:189-190)
-        const double T1 = group_sum<G>(wa), T2 = group_sum<G>(wb);
-        double g = ssum + ((ia >= 0 ? T1 : 0.0) + (ib >= 0 ? T2 : 0.0)) * d;          // :193
-        // tangent projection grad - (grad*nv')*nv, nv = ones/sqrt(cnt)  (:199-201)
-        const double nv = act0 ? a.nv_tab[cnt] : 0.0;
-        const double dot = group_sum<G>(act0 ? g * nv : 0.0);
-        g = g - dot * nv;
-        const double ws = act0 ? apply_step<STEP>(a.st, w, g, c) : 0.0;               // :207
-        const double T = simplex_threshold<G>(ws, act0, lane);          // :215-223
-        const double wn = act0 ? fmax(ws - T, 0.0) : 0.0;                             // :224
-        const double snew = group_sum<G>(wn * d);                                     // :229
-        if (act0) a.w_new[c] = wn;
-        if (edge_ok && gl == 0) {
-            const int e = a.pos_edge[l];
-            chg_acc += fabs(snew - a.S_old[e]);                                       // :232
-            a.S_new[e] = snew;
-        }
-    }
-    block_partials(obj_acc, chg_acc, a.partials, lb);
-}
-
-// Segments longer than 64 cycles: one wave per edge, several passes over the segment;
-// w_new doubles as scratch (each lane re-reads only what it wrote itself).
-template <int STEP>
-__global__ __launch_bounds__(256) void k_sweep_big(SweepArgs a) {
-    if (a.state->stop) return;
-    const int lane = threadIdx.x & 63;
-    const int wv = threadIdx.x >> 6;
-    const int nb = gridDim.x;
-    const int lb = xcd_logical_block(blockIdx.x, nb);
-    const int per_block = (a.m_pos + nb - 1) / nb;
-    const int lo_edge = lb * per_block;
-    const int hi_edge = min(a.m_pos, lo_edge + per_block);
-
-    double obj_acc = 0.0, chg_acc = 0.0;
-    for (int l = lo_edge + wv; l < hi_edge; l += 4) {
-        const int base = a.cum[l], cnt = a.cum[l + 1] - base;
-        double t1 = 0.0, t2 = 0.0;
-        for (int t = lane; t < cnt; t += 64) {
-            const int64_t c = (int64_t)base + t;
-            const int ia = a.ikj[c], ib = a.jki[c];
-            if (ia >= 0) t1 += a.w_old[ia];
-            if (ib >= 0) t2 += a.w_old[ib];
-        }
-        const double T1 = group_sum<64>(t1), T2 = group_sum<64>(t2);
-        const double nv = a.nv_tab[cnt];
-        double dotp = 0.0;
-        for (int t = lane; t < cnt; t += 64) {
-            const int64_t c = (int64_t)base + t;
-            const double ssum = a.S_old[a.e_jk[c]] + a.S_old[a.e_ki[c]];
-            obj_acc += a.w_old[c] * ssum;
-            const double g = ssum + ((a.ikj[c] >= 0 ? T1 : 0.0) + (a.jki[c] >= 0 ? T2 : 0.0)) * a.S0[c];
-            a.w_new[c] = g;
-            dotp += g * nv;
-        }
-        const double dot = group_sum<64>(dotp);
-        for (int t = lane; t < cnt; t += 64) {
-            const int64_t c = (int64_t)base + t;
-            const double g = a.w_new[c] - dot * nv;
-            a.w_new[c] = apply_step<STEP>(a.st, a.w_old[c], g, c);
-        }
-        double T = -INFINITY;
-        int prev_n = -1;
-        for (;;) {
-            double s = 0.0; int na = 0;
-            for (int t = lane; t < cnt; t += 64) {
-                const double x = a.w_new[(int64_t)base + t];
-                if (x > T) { s += x; ++na; }
-            }
-            s = group_sum<64>(s);
-            na = (int)group_sum<64>((double)na);
-            if (na == prev_n) break;
-            prev_n = na;
-            T = (s - 1.0) / (double)max(na, 1);
-        }
-        double sn = 0.0;
-        for (int t = lane; t < cnt; t += 64) {
-            const int64_t c = (int64_t)base + t;
-            const double wn = fmax(a.w_new[c] - T, 0.0);
-            a.w_new[c] = wn;
-            sn += wn * a.S0[c];
-        }
-        const double snew = group_sum<64>(sn);
-        if (lane == 0) {
-            const int e = a.pos_edge[l];
-            chg_acc += fabs(snew - a.S_old[e]);
-            a.S_new[e] = snew;
-        }
-    }
-    block_partials(obj_acc, chg_acc, a.partials, lb);
-}
-
 __global__ __launch_bounds__(256) void k_objective(const double* w, const double* S, const int32_t* e_jk,
                                                    const int32_t* e_ki, int64_t m_cycle, double* partials,
                                                    const DevState* st) {
@@ -283,783 +109,6 @@ __global__ __launch_bounds__(256) void k_init(const int32_t* cum, const int32_t*
         for (int t = lane; t < cnt; t += 64) { w[(int64_t)base + t] = w0; s += w0 * S0[(int64_t)base + t]; }
         s = group_sum<64>(s);
         if (lane == 0) { S_a[pos_edge[l]] = s; S_b[pos_edge[l]] = s; }
-    }
-}
-
-// Cycle inconsistency (DESC_PGD.m:129-147): one wave per edge, lanes over its cycles.
-// R_jk = RijMat4d(:,:,j,k) is the stored block of edge {j,k} if j<k, its transpose
-// otherwise; likewise R_ki (:65-66,89-91).
-__global__ __launch_bounds__(256) void k_cycle_d(const int32_t* cum, const int32_t* pos_edge, const int32_t* ind_i,
-                                                 const int32_t* ind_j, const int32_t* kk, const int32_t* e_jk,
-                                                 const int32_t* e_ki, const double* rij, double* S0, int m_pos) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wid = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
-    const int64_t nw = ((int64_t)gridDim.x * 256) >> 6;
-    for (int64_t l = wid; l < m_pos; l += nw) {
-        const int base = cum[l], cnt = cum[l + 1] - base;
-        const int e = pos_edge[l], i = ind_i[e], j = ind_j[e];
-        double A[9];
-        for (int t = 0; t < 9; ++t) A[t] = rij[9 * (int64_t)e + t];
-        for (int q = lane; q < cnt; q += 64) {
-            const int64_t c = (int64_t)base + q;
-            const int k = kk[c];
-            const double tr = cycle_trace(A, rij + 9 * (int64_t)e_jk[c], !(j < k), rij + 9 * (int64_t)e_ki[c], !(k < i));
-            S0[c] = abs_acos_ext((tr - 1.0) / 2.0) / M_PI;
-        }
-    }
-}
-
-// ===========================================================================
-// NODE variant
-// ===========================================================================
-// per edge-with-cycles, in device (band-major) order
-struct EdgeInfo {
-    int32_t rb_i;     // rowptr[i]
-    int32_t rb_j;     // rowptr[j]
-    int32_t slot_a;   // rowptr[i] + idx_i(j): this edge's slot in row i of Sfull / Tfull
-    int32_t slot_b;   // rowptr[j] + idx_j(i): this edge's slot in row j
-};
-// packed per-cycle word: bits 0-14 idx_i(k), bit 15 cycle (ik;j) sampled (IKJ_appears, :113),
-//                        bits 16-30 idx_j(k), bit 31 cycle (jk;i) sampled (JKI_appears, :124)
-
-
-constexpr int SWEEP_THREADS = 512;
-
-// first / end cycle and first / end segment of a chunk, one 16-byte scalar load
-struct alignas(16) ChunkDesc { int32_t c0, c1, l0, l1; };
-__device__ __forceinline__ ChunkDesc uniform_load_desc(const ChunkDesc* p, int i) {
-    typedef int v4i __attribute__((ext_vector_type(4)));
-    typedef const v4i __attribute__((address_space(4)))* cptr_t;
-    const v4i v = ((cptr_t)(unsigned long long)p)[i];
-    return ChunkDesc{v.x, v.y, v.z, v.w};
-}
-
-struct NodeSweepArgs {
-    const int32_t* cum;        // m_pos+1, device order
-    const EdgeInfo* einfo;     // m_pos
-    const uint32_t* pk;        // m_cycle
-    const double* S0;
-    const double* w_old;
-    double* w_new;
-    const double* S_old;       // Sfull, 2m
-    double* S_new;
-    const double* Tfull;       // 2m: Tfull[rowptr[v]+t] = sum_k w(v,k; nbr_t), masked; sharded runs: T1, T2 per owned segment
-    const int2* xt;            // sharded runs (else NULL): per device-order segment {ta, tb}: Tfull (= the reduce-scattered sums of this rank) holds
-                               // T1 of the segment at ta, T2 at tb (exchange layout: see k_xpos); ta is also its place in the all-gather slice
-    double* s_slice;           // sharded runs: the new S of segment l goes to s_slice[ta] (this rank's all-gather slice)
-    const double* nv_tab;
-    double* partials;
-    const DevState* state;
-    const ChunkDesc* chunk_desc;   // nchunks: {c0, c1, l0, l1}
-    StepArgs st;
-    int32_t nchunks;
-    int32_t max_cnt;
-    uint32_t csr_bytes;        // bytes of the CSR-aligned arrays (S_old, S_new, Tfull of a one-rank run: 2m doubles) -- num_records of their buffer descriptors
-    uint32_t t_bytes;          // bytes of Tfull (sharded runs: this rank's part of the reduce-scattered sums)
-    uint32_t slice_bytes;      // bytes of s_slice (sharded runs)
-    uint32_t seg_count;        // segments in cum / einfo / xt (device order, all ranks): cum has seg_count + 1 entries
-    double fx_inv;             // 2^-fx_bits: Tfull holds fixed-point integers (fx_to_double)
-};
-
-struct StreamRegs { uint4 pk; double2 w, d; };   // one 16-byte vector of each streamed array
-
-// LDS image of one chunk.  Entry q' = (cycle - a0) where a0 = c0 & ~3 is the chunk's first
-// cycle rounded down to a 16-byte boundary of the packed-word array, so that every
-// streaming load is a 16-byte access.
-struct alignas(16) ChunkBuf {
-    double w[CHUNK_LDS], d[CHUNK_LDS];
-    uint32_t pk[CHUNK_LDS];
-};
-
-// The sweep (dominant kernel).  512-thread persistent workgroups take chunks of consecutive
-// segments (<= CHUNK_CAP cycles, <= 8 * 64/LPS segments) round-robin: at any moment the
-// resident workgroups read one contiguous window of the streamed arrays (DRAM row-buffer
-// locality; disjoint far-apart streams per workgroup measured ~half the bandwidth).
-// pk, w and S0 of a chunk arrive with 16-byte loads, two chunks ahead, and are parked in a
-// triple-buffered LDS image.  Everything per segment lives in the registers of the 16 lanes
-// that own the segment (LPS lanes x E cycles per lane = 16x1, 16x2, 32x2, 32x4, 64x4 for segments of up to 16, 32, 64, 128, 256 cycles; a
-// chunk = one pass of the 8 waves x 64/LPS lane groups): the lane group
-// that will compute segment t of chunk c+1 loads its records, issues its row gathers
-// (addresses from the packed words already parked in LDS) and keeps their sums until the
-// arithmetic of chunk c+1; E cycles per lane, reductions = E in-lane adds + 4 DPP steps
-// shared by the 4 segments of a wave; simplex threshold by Michelot's fixed point with a
-// division-free comparison (same active set as the reference's sort-and-scan, :215-223);
-// weights and S leave with 8-byte stores straight from registers (16 lanes x 8 B = 128
-// contiguous bytes).  One workgroup barrier per chunk.
-//   iteration c:  park stream(c+1) -> LDS[(c+1)%3] | barrier | gathers(c+1) | records(c+2),
-//                 stream(c+3) | arithmetic(c) out of LDS[c%3] + registers | land gathers and
-//                 records | stores(c)
-// gfx950 retires loads AND stores through one in-order counter (vmcnt): every pipelined
-// load is unconditional (clamped index instead of a branch) so the compiler can count
-// them, and a load that is waited for after a store point would make the wave wait for the
-// stores too, so gathers and records are consumed (landed) after the arithmetic but before
-// the stores of the iteration that issued them.  Chunk descriptors are prefetched four
-// chunks ahead with one scalar 16-byte load (constant cache: off vmcnt).
-// (the Adam variant carries two more streamed values per cycle through the arithmetic: it gets the
-//  register budget of 3 waves per SIMD instead of spilling)
-template <int LPS, int E, int STEP>
-__global__ __launch_bounds__(SWEEP_THREADS, STEP == DESC_STEP_HYBRID ? 3 : 4) void k_sweep_node(NodeSweepArgs a) {
-    __shared__ ChunkBuf X[3];
-    __shared__ double s_nv[MAX_SEG_CYCLES + 1];
-    if (a.state->stop) return;
-    constexpr int NT = SWEEP_THREADS;
-    static_assert(NT == 512 && (LPS == 16 || LPS == 32 || LPS == 64) && LPS * E <= MAX_SEG_CYCLES, "8 waves x 64/LPS lane groups per chunk");
-    static_assert(CHUNK_LDS / 2 <= NT, "one 16-byte vector of w per thread");
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wv = tid >> 6;
-    constexpr int SPW = 64 / LPS;                      // segments per wave: a chunk holds at most 8 * SPW segments
-    const int grp = lane / LPS, r16 = lane % LPS;      // LPS lanes per segment, E cycles per lane
-    const int ts = wv * SPW + grp;                     // segment slot of this lane group
-    const int nb = gridDim.x, lb = blockIdx.x;         // chunks dealt round-robin (see k_sweep_node)
-    const int nk = lb < a.nchunks ? (a.nchunks - lb + nb - 1) / nb : 0;
-    double obj_acc = 0.0, chg_acc = 0.0;
-    if (nk == 0) { block_partials(obj_acc, chg_acc, a.partials, lb); return; }
-    if (tid <= MAX_SEG_CYCLES) s_nv[tid] = tid <= a.max_cnt ? a.nv_tab[tid] : 0.0;
-
-    struct RecRaw { int b0, b1; EdgeInfo ei; int2 x; };
-    struct Rec { int qb, cnt, rbi, rbj, sa, sb, seg; };   // qb: image entry of the segment's first cycle; sharded runs: seg = ta, sb = tb
-    struct Gat { double sjk[E], ski[E], T1, T2, So; };
-    struct Landed { double ss[E], T1, T2, So; };       // S(jk)+S(ki) per cycle, mirror sums, old S of the segment
-    struct Carry { StreamRegs s; Landed g; Rec r; };
-
-    // past the end every load is redirected to this workgroup's last chunk: harmless and branch-free
-    auto desc_of = [&](int k) -> ChunkDesc { return uniform_load_desc(a.chunk_desc, lb + min(k, nk - 1) * nb); };
-    auto load_rec = [&](const ChunkDesc d) -> RecRaw {
-        const int t = d.l0 + min(ts, d.l1 - d.l0 - 1);
-        RecRaw r;
-        r.b0 = a.cum[t]; r.b1 = a.cum[t + 1]; r.ei = a.einfo[t];
-        r.x = a.xt ? a.xt[t] : int2{0, 0};
-        return r;
-    };
-    auto land_rec = [&](const ChunkDesc d, const RecRaw q) -> Rec {
-        Rec r;
-        r.qb = q.b0 - (d.c0 & ~3);
-        r.cnt = ts < d.l1 - d.l0 ? q.b1 - q.b0 : 0;
-        r.rbi = q.ei.rb_i; r.rbj = q.ei.rb_j; r.sa = q.ei.slot_a; r.sb = a.xt ? q.x.y : q.ei.slot_b;
-        r.seg = q.x.x;
-        return r;
-    };
-    auto load_stream = [&](const ChunkDesc d) -> StreamRegs {   // 16-byte loads; image entry 0 = cycle a0 = c0 & ~3
-        const int a0 = d.c0 & ~3, last = d.c1 - 1 - a0;
-        const int v2 = min(tid, last >> 1), v4 = min(tid, last >> 2);
-        StreamRegs sr;
-        sr.w = *reinterpret_cast<const double2*>(a.w_old + a0 + 2 * (int64_t)v2);
-        sr.d = *reinterpret_cast<const double2*>(a.S0 + a0 + 2 * (int64_t)v2);
-        sr.pk = *reinterpret_cast<const uint4*>(a.pk + a0 + 4 * (int64_t)v4);
-        return sr;
-    };
-    auto park = [&](const ChunkDesc d, const StreamRegs sr, ChunkBuf& xb) {
-        const int last = d.c1 - 1 - (d.c0 & ~3);
-        if (tid <= (last >> 1)) { *reinterpret_cast<double2*>(&xb.w[2 * tid]) = sr.w; *reinterpret_cast<double2*>(&xb.d[2 * tid]) = sr.d; }
-        if (tid <= (last >> 2)) *reinterpret_cast<uint4*>(&xb.pk[4 * tid]) = sr.pk;
-    };
-    auto issue_gathers = [&](const Rec r, const ChunkBuf& xb) -> Gat {
-        Gat g;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {                // unconditional: idle lanes repeat the segment's first cycle
-            const int idx = r16 + LPS * e;
-            const uint32_t p = xb.pk[r.qb + (idx < r.cnt ? idx : 0)];
-            const int si = r.rbi + (int)(p & 0x7FFFu), sj = r.rbj + (int)((p >> 16) & 0x7FFFu);
-            g.sjk[e] = a.S_old[sj]; g.ski[e] = a.S_old[si];
-        }
-        const int ta = a.xt ? r.seg : r.sa, tb = r.sb;
-        g.T1 = a.Tfull[ta];                      // column j of node i = sum(wijk(IKJ(mask)))  (:189)
-        g.T2 = a.Tfull[tb];                      // column i of node j = sum(wijk(JKI(mask)))  (:190)
-        g.So = a.S_old[r.sa];
-        return g;
-    };
-
-    // one pipeline iteration: chunk k of this workgroup is computed; c.s = stream registers of
-    // chunk k+1, c.g = gathers of chunk k, c.r = records of chunk k+1; r0 = records of chunk k
-    auto iterate = [&](int k, const Carry c, const Rec r0, const ChunkDesc d0, const ChunkDesc d1, const ChunkDesc d2,
-                       const ChunkDesc d3) -> Carry {
-        Carry o;
-        Gat gn;
-        ChunkBuf& xc = X[k % 3];
-        ChunkBuf& xn = X[(k + 1) % 3];
-        park(d1, c.s, xn);
-        __syncthreads();
-        gn = issue_gathers(c.r, xn);
-        const RecRaw q2 = load_rec(d2);
-        o.s = load_stream(d3);
-        // ---- arithmetic of chunk k
-        const int a0 = d0.c0 & ~3;
-        const int cnt = r0.cnt;
-        const double T1 = fx_to_double(c.g.T1, a.fx_inv), T2 = fx_to_double(c.g.T2, a.fx_inv), nv = cnt > 0 ? s_nv[cnt] : 0.0;
-        double ws[E];
-        uint32_t okm = 0;
-        double part = 0.0;
-        // waves whose four lane groups own no segment of this chunk skip the arithmetic (wave-uniform)
-        if (__ballot(cnt > 0) != 0ull) {
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const int idx = r16 + LPS * e;
-                const bool ok = idx < cnt;
-                const int q = r0.qb + idx;
-                uint32_t p = 0; double w = 0.0, d = 0.0;
-                if (ok) { p = xc.pk[q]; w = xc.w[q]; d = xc.d[q]; okm |= 1u << e; }
-                const double ss = c.g.ss[e];                                                         // S(jk)+S(ki)
-                obj_acc += w * ss;                                                                   // :233, one sweep late
-                const double g = ss + (((p & 0x8000u) ? T1 : 0.0) + ((p & 0x80000000u) ? T2 : 0.0)) * d;   // :193
-                ws[e] = g;
-                part += ok ? g * nv : 0.0;
-            }
-            const double dot = group_sum<LPS>(part);                                                    // :199-201
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const int q = r0.qb + r16 + LPS * e;
-                const double g = ws[e] - dot * nv;
-                ws[e] = ((okm >> e) & 1u) ? apply_step<STEP>(a.st, xc.w[q], g, (int64_t)a0 + q) : 0.0;   // :207
-            }
-            // simplex projection threshold (:215-223), Michelot fixed point; the comparison
-            // ws*na > s-1 is ws > (s-1)/na without a division per pass
-            uint32_t act = okm;
-            double s1v = 0.0; int na = 1;
-            for (;;) {
-                double sp = 0.0;
-#pragma unroll
-                for (int e = 0; e < E; ++e) sp += ((act >> e) & 1u) ? ws[e] : 0.0;
-                s1v = group_sum<LPS>(sp) - 1.0;
-                if (LPS == 16) na = max(group16_sum((int)__popc(act)), 1);
-                else {                                 // wider groups: count by ballots (scalar popcounts)
-                    na = 0;
-#pragma unroll
-                    for (int e = 0; e < E; ++e) na += group_count<LPS>((act >> e) & 1u, lane);
-                    na = max(na, 1);
-                }
-                const double nad = (double)na;
-                uint32_t keep = 0;
-#pragma unroll
-                for (int e = 0; e < E; ++e) keep |= (((act >> e) & 1u) && ws[e] * nad > s1v) ? 1u << e : 0u;
-                const bool changed = keep != act;
-                act = keep;
-                if (!__any(changed)) break;
-            }
-            const double T = s1v / (double)na;
-            double sn = 0.0;
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const double wn = fmax(ws[e] - T, 0.0);                                              // :224
-                ws[e] = wn;
-                if ((okm >> e) & 1u) sn += wn * xc.d[r0.qb + r16 + LPS * e];
-            }
-            part = group_sum<LPS>(sn);                                                                  // :229
-        }
-        // gathers of chunk k+1 and records of chunk k+2 are consumed before this iteration's stores
-        // (see the header); the gathers shrink to their sums
-#pragma unroll
-        for (int e = 0; e < E; ++e) o.g.ss[e] = gn.sjk[e] + gn.ski[e];
-        o.g.T1 = gn.T1; o.g.T2 = gn.T2; o.g.So = gn.So;
-        o.r = land_rec(d2, q2);
-        // pin the landing here: without it the scheduler sinks these adds below the stores
-#pragma unroll
-        for (int e = 0; e < E; ++e) asm volatile("" : "+v"(o.g.ss[e]));
-        asm volatile("" : "+v"(o.g.T1), "+v"(o.g.T2), "+v"(o.g.So));
-        asm volatile("" : "+v"(o.r.qb), "+v"(o.r.cnt), "+v"(o.r.rbi), "+v"(o.r.rbj), "+v"(o.r.sa), "+v"(o.r.sb), "+v"(o.r.seg));
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int e = 0; e < E; ++e)
-            if ((okm >> e) & 1u) a.w_new[(int64_t)a0 + r0.qb + r16 + LPS * e] = ws[e];
-        if (cnt > 0 && r16 == 0) {
-            chg_acc += fabs(part - c.g.So);                                                      // :232
-            // sharded runs: only the all-gather slice is written; k_unpack_S scatters S of every edge, this rank's included
-            if (a.s_slice) a.s_slice[r0.seg] = part;
-            else { a.S_new[r0.sa] = part; a.S_new[r0.sb] = part; }
-        }
-        return o;
-    };
-
-    // ---- prologue: chunk 0 parked and its gathers in flight, streams of chunks 1 and 2 in flight
-    ChunkDesc D0 = desc_of(0), D1 = desc_of(1), D2 = desc_of(2), D3 = desc_of(3);
-    Rec R0;
-    Carry CA, CB;
-    {
-        const RecRaw q0 = load_rec(D0);
-        const StreamRegs s0 = load_stream(D0);
-        const RecRaw q1 = load_rec(D1);
-        CA.s = load_stream(D1);                  // CA: consumed by even iterations
-        CB.s = load_stream(D2);
-        R0 = land_rec(D0, q0);
-        park(D0, s0, X[0]);
-        __syncthreads();
-        const Gat g0 = issue_gathers(R0, X[0]);
-#pragma unroll
-        for (int e = 0; e < E; ++e) CA.g.ss[e] = g0.sjk[e] + g0.ski[e];
-        CA.g.T1 = g0.T1; CA.g.T2 = g0.T2; CA.g.So = g0.So;
-        CA.r = land_rec(D1, q1);
-    }
-    // Two iterations per trip (the register sets alternate).  The second one always runs -- with
-    // an odd number of chunks it computes nothing (cnt = 0) -- so that the compiler sees one
-    // straight-line loop body and can count the loads in flight across the back edge.
-    for (int k = 0; k < nk; k += 2) {
-        {
-            const ChunkDesc Dn = desc_of(k + 4);
-            const Carry o = iterate(k, CA, R0, D0, D1, D2, D3);       // parks CA.s (chunk k+1), consumes CA.g (chunk k)
-            R0 = CA.r; CB.g = o.g; CB.r = o.r; CA.s = o.s;            // CA.s now streams chunk k+3
-            D0 = D1; D1 = D2; D2 = D3; D3 = Dn;
-        }
-        {
-            if (k + 1 >= nk) R0.cnt = 0;
-            const ChunkDesc Dn = desc_of(k + 5);
-            const Carry o = iterate(k + 1, Carry{CB.s, CB.g, CB.r}, R0, D0, D1, D2, D3);
-            R0 = CB.r; CA.g = o.g; CA.r = o.r; CB.s = o.s;
-            D0 = D1; D1 = D2; D2 = D3; D3 = Dn;
-        }
-    }
-    block_partials(obj_acc, chg_acc, a.partials, lb);
-}
-
-// SMALL graphs (round 4; the reference's own demo sizes, Demo/compare_algorithms.m:10: n = 100-200, configs[0]): an iteration of a few hundred
-// thousand cycles is not bandwidth- but latency-bound -- k_sweep_node's staged chunk pipeline is a chain of ~6 dependent memory round trips for one
-// chunk per workgroup (C1: 11.7 us per sweep for ~1 us of traffic).  Here a lane group of G lanes takes a whole segment (one cycle per lane) straight
-// from global memory: records -> packed words / weights / S0 -> the gathers of S and the mirror sums -> arithmetic -> stores, three dependent round
-// trips.  Same per-segment arithmetic as the gather layout's k_sweep (group reductions over G lanes, Michelot threshold), on the node layout's arrays.
-template <int G, int STEP>
-__global__ __launch_bounds__(256) void k_sweep_small(NodeSweepArgs a, int n_seg) {
-    if (a.state->stop) return;
-    constexpr int EPW = 64 / G;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int sub = lane / G, gl = lane % G;
-    double obj_acc = 0.0, chg_acc = 0.0;
-    for (int l0 = ((int)blockIdx.x * 4 + wv) * EPW; l0 < n_seg; l0 += (int)gridDim.x * 4 * EPW) {
-        const int l = l0 + sub;
-        const bool seg_ok = l < n_seg;
-        int base = 0, cnt = 0;
-        EdgeInfo ei{0, 0, 0, 0};
-        if (seg_ok) { base = a.cum[l]; cnt = a.cum[l + 1] - base; ei = a.einfo[l]; }
-        const bool act0 = gl < cnt;
-        const int64_t c = (int64_t)base + gl;
-        uint32_t p = 0; double w = 0.0, d = 0.0, ssum = 0.0;
-        if (act0) {
-            p = a.pk[c]; w = a.w_old[c]; d = a.S0[c];
-            ssum = a.S_old[ei.rb_j + (int)((p >> 16) & 0x7FFFu)] + a.S_old[ei.rb_i + (int)(p & 0x7FFFu)];          // S(jk) + S(ki)
-        }
-        double T1 = 0.0, T2 = 0.0, So = 0.0;
-        if (seg_ok) { T1 = fx_to_double(a.Tfull[ei.slot_a], a.fx_inv); T2 = fx_to_double(a.Tfull[ei.slot_b], a.fx_inv); So = a.S_old[ei.slot_a]; }
-        obj_acc += w * ssum;                                                                                     // :233, one sweep late
-        double g = ssum + (((p & 0x8000u) ? T1 : 0.0) + ((p & 0x80000000u) ? T2 : 0.0)) * d;                     // :193
-        const double nv = act0 ? a.nv_tab[cnt] : 0.0;
-        const double dot = group_sum<G>(act0 ? g * nv : 0.0);                                                    // :199-201
-        g = g - dot * nv;
-        const double ws = act0 ? apply_step<STEP>(a.st, w, g, c) : 0.0;                                          // :207
-        const double T = simplex_threshold<G>(ws, act0, lane);                                                   // :215-223
-        const double wn = act0 ? fmax(ws - T, 0.0) : 0.0;                                                        // :224
-        const double snew = group_sum<G>(wn * d);                                                                // :229
-        if (act0) a.w_new[c] = wn;
-        if (seg_ok && cnt > 0 && gl == 0) {
-            chg_acc += fabs(snew - So);                                                                          // :232
-            a.S_new[ei.slot_a] = snew; a.S_new[ei.slot_b] = snew;
-        }
-    }
-    block_partials(obj_acc, chg_acc, a.partials, blockIdx.x);
-}
-
-// ===========================================================================
-// BAND sweep: the same arithmetic with the i-rows of S in the LDS
-// ===========================================================================
-// k_sweep_node is bound by L1-miss sector traffic: every segment gathers ~cnt values out of row i of Sfull
-// (8 useful bytes per 64-byte sector, a different row for every segment of a chunk).  Here the nodes are cut
-// into bands whose CSR rows fit the LDS of one CU together (<= row_cap doubles: 36 rows at C2, 18 at C4 / C5);
-// the edges keep the (band(i), j, i) order, every workgroup owns ONE contiguous range of segments (equal cycle
-// counts; pure streaming measured no penalty for contiguous ranges -- tools/probes/stream_probe.hip), split into
-// "pieces" at band boundaries, loads the piece's band rows once (coalesced) and serves S({k,i}) and the segment's
-// old S from the LDS.  S({j,k}) stays a gather through L1: consecutive segments of a band share j.
-// 1024 threads = 16 waves per workgroup (one workgroup per CU); no barrier inside a piece.  A wave takes
-// SPW = 64/LPS consecutive segments per iteration; its software pipeline keeps, per lane group,
-//   records (cum, EdgeInfo: scalar loads, off vmcnt)  4 iterations ahead,
-//   the streamed pk / w / S0 of its cycles            3 iterations ahead (registers, 4 rotating sets),
-//   the gathers of S({j,k}), T1, T2 (+ LDS reads)     1 iteration ahead (2 sets),
-// issued in the order gathers -> stream -> arithmetic -> stores: loads and stores retire through one in-order
-// counter on gfx950, so everything an iteration waits for was issued before the previous iteration's stores.
-// BUFFER instructions (round 3).  The band sweep and the column sums address global memory as `descriptor in SGPRs + 32-bit byte offset per
-// lane` (buffer_load / buffer_store ... offen) instead of a 64-bit address per lane (global_load / global_store): half the address data per
-// instruction on the way to the address unit -- the busiest unit of the CU in this kernel (TA_BUSY 76 % at C4, section 5 of DESIGN.md) -- and no
-// 64-bit address arithmetic (v_lshl_add_u64, sign extensions: 12 % of the VALU instructions of an iteration).  Measured, rocprofv3 averages in
-// one call (profiles/r03_buffer_instructions.txt): only the S({j,k}) gathers C4 1171 -> 1119 us; + T1/T2 and the S stores 1122; + the three
-// streams and the weight stores 1084-1091 (-7.2 %); C5 1737 -> 1670-1682, C3 105.0 -> 100.4, C2 110.8 -> 107.8.  Cache-policy bits on the
-// gathers (same file): nt 1873 us, sc1 / sc0 sc1 1253 us -- no.  Offsets are 32 bits: the descriptors of the per-cycle arrays are rebuilt per
-// piece with the piece's first cycle as base (any m_cycle), the CSR-aligned arrays (2m doubles) must stay below 4 GiB (setup_node: else no band sweep).
-// Out-of-range offsets read 0 and store nothing (num_records) instead of faulting.  (The round-2 global-load forms are in the history, tree ca0abdf.)
-typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
-template <class T> __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const T* p, uint32_t bytes = 0xFFFFFFFFu) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, bytes, 0x00020000);          // raw buffer (stride 0), 32-bit data format
-}
-__device__ __forceinline__ double buf_load_f64(__amdgpu_buffer_rsrc_t rs, uint32_t off) {
-    const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)off, 0, 0);
-    double d; __builtin_memcpy(&d, &v, 8); return d;
-}
-__device__ __forceinline__ uint32_t buf_load_u32(__amdgpu_buffer_rsrc_t rs, uint32_t off) { return __builtin_amdgcn_raw_buffer_load_b32(rs, (int)off, 0, 0); }
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void buf_load_f64x2(__amdgpu_buffer_rsrc_t rs, uint32_t off, double& a0, double& a1) {      // 16 bytes, 8-byte aligned
-    const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0);
-    const u32x2_t lo = {v.x, v.y}, hi = {v.z, v.w};
-    __builtin_memcpy(&a0, &lo, 8); __builtin_memcpy(&a1, &hi, 8);
-}
-__device__ __forceinline__ void buf_load_u32x2(__amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t& a0, uint32_t& a1) {
-    const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)off, 0, 0);
-    a0 = v.x; a1 = v.y;
-}
-__device__ __forceinline__ void buf_store_f64x2(__amdgpu_buffer_rsrc_t rs, uint32_t off, double d0, double d1) {
-    u32x2_t lo, hi; __builtin_memcpy(&lo, &d0, 8); __builtin_memcpy(&hi, &d1, 8);
-    const u32x4_t v = {lo.x, lo.y, hi.x, hi.y};
-    __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)off, 0, 0);
-}
-__device__ __forceinline__ void buf_store_f64(__amdgpu_buffer_rsrc_t rs, uint32_t off, double d) {
-    u32x2_t v; __builtin_memcpy(&v, &d, 8);
-    __builtin_amdgcn_raw_buffer_store_b64(v, rs, (int)off, 0, 0);
-}
-
-struct BandSweepArgs {
-    NodeSweepArgs n;
-    const PieceDesc* pieces;
-    const int32_t* piece_ptr;      // grid + 1
-    int32_t row_cap;
-    unsigned long long* wg_clock;  // diagnostics (DESC_DEBUG_WGCLOCK=1; else NULL): per workgroup {start, end} of the constant 100 MHz clock
-    // Dynamic tail (round 3): the last few per cent of the sweep's work are not in any workgroup's list but in a shared queue of small pieces
-    // pieces[tail_first .. tail_first + n_tail), handed out by tickets to whichever workgroup has finished its list (the lists are balanced by
-    // a cost model; the workgroups' real times differ by +-5 %).  Every tail piece has its own pair of partials (slot gridDim.x + ticket), so
-    // the objective and |dS| sums do not depend on who took which piece.  *ticket is zeroed by the column-sum launch that precedes a sweep.
-    int32_t tail_first, n_tail;
-    int32_t* ticket;
-};
-
-__device__ __forceinline__ PieceDesc uniform_load_piece(const PieceDesc* p, int i) {
-    typedef int v4i __attribute__((ext_vector_type(4)));
-    typedef const v4i __attribute__((address_space(4)))* cptr_t;
-    const v4i v = ((cptr_t)(unsigned long long)p)[i];
-    return PieceDesc{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ EdgeInfo uniform_load_einfo(const EdgeInfo* p, int i) {
-    typedef int v4i __attribute__((ext_vector_type(4)));
-    typedef const v4i __attribute__((address_space(4)))* cptr_t;
-    const v4i v = ((cptr_t)(unsigned long long)p)[i];
-    return EdgeInfo{v.x, v.y, v.z, v.w};
-}
-
-template <int LPS, int E, int STEP, int NT, bool XT = false>      // XT: sharded run (exchange positions {ta, tb} per segment; its own instances keep
-__global__ __launch_bounds__(NT, 1) void k_sweep_band(BandSweepArgs b) {     // the extra records out of the one-GPU kernels' scalar registers)
-    extern __shared__ double s_dyn[];                  // [row_cap] band rows of S_old, then the nv table
-    const NodeSweepArgs& a = b.n;
-    double* s_rows = s_dyn;
-    double* s_nv = s_dyn + b.row_cap;
-    __shared__ double s_part[2][NT / 64];
-    // segments of up to 64 cycles: 1024 threads (16 waves, <= 128 VGPRs each); up to 256 cycles (4 cycles per lane: twice the
-    // registers per pipeline stage) and the Adam plugin (its two moments are two more streams in and out): 512 threads (8 waves, <= 256 VGPRs).
-    static_assert((LPS == 8 || LPS == 16 || LPS == 32 || LPS == 64) && LPS * E <= MAX_SEG_CYCLES && (NT == 512 || NT == 1024) && (STEP != DESC_STEP_HYBRID || NT == 512), "band sweep instances");
-    constexpr bool ADAM = STEP == DESC_STEP_HYBRID;
-    constexpr int EA = ADAM ? E : 1;
-    if (a.state->stop) return;
-    constexpr int NW = NT / 64, SPW = 64 / LPS;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = lane / LPS, rr = lane % LPS;
-    if (tid <= MAX_SEG_CYCLES) s_nv[tid] = tid <= a.max_cnt ? a.nv_tab[tid] : 0.0;
-    double obj_acc = 0.0, chg_acc = 0.0;
-
-    constexpr bool VREC = SPW > 4;         // (for every shape, as buffer loads: C4 +4.7 %, C5 +3.6 %, C2 +2 % -- the scalar loads keep the records out of the address unit) eight segments per wave: their records would not fit the SGPRs -- per-lane vector loads instead
-    struct RecRaw { int c0[VREC ? 1 : SPW], c1[VREC ? 1 : SPW]; EdgeInfo ei[VREC ? 1 : SPW]; int xa[XT ? (VREC ? 1 : SPW) : 1], xb[XT ? (VREC ? 1 : SPW) : 1]; int t0; };      // wave-uniform (SGPRs); VREC: this lane group's record (VGPRs)
-    struct Rec { int c0, cnt, rbi, rbj, sa, sb, seg; };                   // this lane group's segment; sharded runs: seg = ta, sb = tb (exchange positions)
-    // Which cycles of its segment a lane owns.  Round 2: rr + LPS * e (every stream instruction reads one contiguous run of 8-byte words).
-    // Round 3 (PAIR): the adjacent pairs 2 rr + 2 LPS * (e / 2) + {0, 1}, so that the 8-byte streams (old weights, S0, Adam moments) are read
-    // 16 bytes per lane: the CU's address unit takes 16.4 cycles for a contiguous 8-byte-per-lane load and 16.3 for a 16-byte one
-    // (tools/probes/gather_probe.hip, profiles/r03_gather_probe.txt), i.e. half the cycles per byte.  The packed words become 8-byte loads
-    // (16.4 cycles for two cycles' worth instead of 2 x 6.2), the weight stores 16-byte stores (43.6 = 2 x 21.9: no change).
-    // Only the constant / piecewise-step shapes for segments of up to 64 cycles (LPS <= 16: what the BASELINE workloads run).  Measured on the others:
-    // unsampled C5 (<64,4>) 8.05 -> 7.89 ms; the Adam instances (<32,2> at C2 / C4) no gain (2.19 -> 2.27 ms at C4, 0.251 -> 0.267 at C2) -- both
-    // keep the round-2 map, and with it results bitwise equal to k_sweep_node's (which two tests assert).
-    constexpr bool PAIR = (E % 2 == 0) && LPS <= 16 && !ADAM;
-    // (four adjacent cycles per lane -- the packed words as ONE 16-byte load -- measured on top: C4 1025-1054 vs 989-1034 us, C2 +3 %: not adopted)
-    auto cidx = [&](int e) { return PAIR ? 2 * rr + (e & 1) + 2 * LPS * (e >> 1) : rr + LPS * e; };
-    struct Str { uint32_t pk[E]; double w[E], d[E], am[EA], av[EA]; };     // am / av: HybridGradient.m_t / v_t (Adam only)
-    struct Gat { double sj[E], si[E], T1, T2, So; };
-
-    const int p0 = uniform_load(b.piece_ptr, blockIdx.x), p1 = uniform_load(b.piece_ptr, blockIdx.x + 1);
-    unsigned long long wg_c0 = 0;
-    if (b.wg_clock && tid == 0) { b.wg_clock[2 * blockIdx.x] = wall_clock64(); wg_c0 = clock64(); }
-    __shared__ int s_ticket;
-    // deterministic workgroup partials of what has been accumulated since the last flush -> pair `slot`
-    auto flush_partials = [&](int slot) {
-        const double o1 = group_sum<64>(obj_acc), c1 = group_sum<64>(chg_acc);
-        __syncthreads();
-        if (lane == 0) { s_part[0][wv] = o1; s_part[1][wv] = c1; }
-        __syncthreads();
-        if (tid == 0) {
-            double o = 0.0, c = 0.0;
-            for (int k = 0; k < NW; ++k) { o += s_part[0][k]; c += s_part[1][k]; }
-            a.partials[2 * slot] = o;
-            a.partials[2 * slot + 1] = c;
-        }
-        obj_acc = 0.0; chg_acc = 0.0;
-    };
-    // num_records = the arrays' real lengths: an offset past the end reads 0 / stores nothing instead of touching a neighbouring block
-#ifndef DESC_RSRC_UNBOUNDED          // A/B builds only: 1 = the round-3 descriptors (num_records 0xFFFFFFFF)
-#define DESC_RSRC_UNBOUNDED 0
-#endif
-    const uint32_t nb_csr = DESC_RSRC_UNBOUNDED ? 0xFFFFFFFFu : a.csr_bytes, nb_t = DESC_RSRC_UNBOUNDED ? 0xFFFFFFFFu : a.t_bytes, nb_sl = DESC_RSRC_UNBOUNDED ? 0xFFFFFFFFu : a.slice_bytes;
-    const __amdgpu_buffer_rsrc_t rs_S = make_rsrc(a.S_old, nb_csr), rs_T = make_rsrc(a.Tfull, nb_t), rs_Sn = make_rsrc(a.S_new, nb_csr);      // CSR-aligned: 2m doubles < 4 GiB
-    const __amdgpu_buffer_rsrc_t rs_sl = XT ? make_rsrc(a.s_slice, nb_sl) : rs_Sn;                        // sharded runs: this rank's all-gather slice
-    const __amdgpu_buffer_rsrc_t rs_cum = make_rsrc(a.cum, (a.seg_count + 1u) * 4u), rs_ei = make_rsrc(a.einfo, a.seg_count * 16u);          // per-lane records (VREC shapes only; C3 -1 %)
-    int pc = p0, ticket = -1;
-    for (;;) {
-        if (ticket < 0 && pc >= p1) {                      // own list done: its partials, then the shared tail
-            flush_partials(blockIdx.x);
-            if (b.n_tail == 0) break;
-            ticket = 0;
-        }
-        if (ticket >= 0) {
-            if (tid == 0) s_ticket = atomicAdd(b.ticket, 1);
-            __syncthreads();
-            ticket = __builtin_amdgcn_readfirstlane(s_ticket);
-            __syncthreads();
-            if (ticket >= b.n_tail) break;
-            pc = b.tail_first + ticket;
-        }
-        const PieceDesc pd = uniform_load_piece(b.pieces, pc);
-        __syncthreads();                                   // every wave is done with the previous band's rows
-        const int nit = (pd.seg_hi - pd.seg_lo + NW * SPW - 1) / (NW * SPW);
-        // the piece's cycles are one contiguous range of the per-cycle arrays: Rec::c0 counts from its start
-        const int c_lo = uniform_load(a.cum, pd.seg_lo);
-        const uint32_t c_len = (uint32_t)(uniform_load(a.cum, pd.seg_hi) - c_lo) + 8u;           // + the 16-byte tail the arrays are padded by
-        const __amdgpu_buffer_rsrc_t rs_pk = make_rsrc(a.pk + c_lo, c_len * 4u), rs_w = make_rsrc(a.w_old + c_lo, c_len * 8u),
-                                     rs_d = make_rsrc(a.S0 + c_lo, c_len * 8u), rs_wn = make_rsrc(a.w_new + c_lo, c_len * 8u);
-        __amdgpu_buffer_rsrc_t rs_am = rs_w, rs_av = rs_w, rs_amo = rs_wn, rs_avo = rs_wn;       // Adam moments (HybridGradient.m:28-35), read and written per cycle
-        if constexpr (ADAM) {
-            rs_am = make_rsrc(a.st.adam_m + c_lo, c_len * 8u); rs_av = make_rsrc(a.st.adam_v + c_lo, c_len * 8u);
-            rs_amo = make_rsrc(a.st.adam_m_out + c_lo, c_len * 8u); rs_avo = make_rsrc(a.st.adam_v_out + c_lo, c_len * 8u);
-        }
-
-        auto load_raw = [&](int it) -> RecRaw {            // past the end: the piece's last segment, cnt = 0
-            RecRaw q;
-            q.t0 = pd.seg_lo + (it * NW + wv) * SPW;
-            if constexpr (VREC) {
-                const int t = min(q.t0 + grp, pd.seg_hi - 1);
-                {
-                    const u32x2_t cc = __builtin_amdgcn_raw_buffer_load_b64(rs_cum, t * 4, 0, 0);
-                    const u32x4_t ee = __builtin_amdgcn_raw_buffer_load_b128(rs_ei, t * 16, 0, 0);
-                    q.c0[0] = (int)cc.x; q.c1[0] = (int)cc.y;
-                    q.ei[0].rb_i = (int)ee.x; q.ei[0].rb_j = (int)ee.y; q.ei[0].slot_a = (int)ee.z; q.ei[0].slot_b = (int)ee.w;
-                }
-                if constexpr (XT) { const int2 x = a.xt[t]; q.xa[0] = x.x; q.xb[0] = x.y; }
-                return q;
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < SPW; ++s2) {
-                const int t = min(q.t0 + s2, pd.seg_hi - 1);
-                q.c0[s2] = uniform_load(a.cum, t); q.c1[s2] = uniform_load(a.cum, t + 1);
-                q.ei[s2] = uniform_load_einfo(a.einfo, t);
-                if constexpr (XT) { q.xa[s2] = uniform_load((const int32_t*)a.xt, 2 * t); q.xb[s2] = uniform_load((const int32_t*)a.xt, 2 * t + 1); }
-            }
-            return q;
-        };
-        auto land = [&](const RecRaw& q) -> Rec {
-            Rec r{};
-            if constexpr (VREC) {
-                r.c0 = q.c0[0] - c_lo; r.cnt = q.t0 + grp < pd.seg_hi ? q.c1[0] - q.c0[0] : 0;
-                r.rbi = q.ei[0].rb_i - pd.row_lo; r.rbj = q.ei[0].rb_j; r.sa = q.ei[0].slot_a; r.sb = XT ? q.xb[0] : q.ei[0].slot_b;
-                r.seg = XT ? q.xa[0] : 0;
-                return r;
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < SPW; ++s2)
-                if (grp == s2) {
-                    r.c0 = q.c0[s2] - c_lo; r.cnt = q.t0 + s2 < pd.seg_hi ? q.c1[s2] - q.c0[s2] : 0;
-                    r.rbi = q.ei[s2].rb_i - pd.row_lo; r.rbj = q.ei[s2].rb_j; r.sa = q.ei[s2].slot_a; r.sb = XT ? q.xb[s2] : q.ei[s2].slot_b;
-                    r.seg = XT ? q.xa[s2] : 0;
-                }
-            return r;
-        };
-        auto load_stream = [&](const Rec& r) -> Str {      // unconditional: idle lanes repeat a valid cycle of the segment
-            Str x;
-            if constexpr (PAIR) {
-#pragma unroll
-                for (int h = 0; h < E / 2; ++h) {
-                    // the pair's first cycle, clamped into the segment; its second one may lie past the segment's end (an odd count, idle lanes):
-                    // that is the next segment's first cycle or the arrays' padding -- readable, masked in compute; its packed word is replaced by
-                    // the first one's, so that the gathers formed from it stay inside rows i and j
-                    const int first = min(2 * rr + 2 * LPS * h, max(r.cnt, 1) - 1);
-                    const uint32_t cr = (uint32_t)(r.c0 + first);
-                    buf_load_u32x2(rs_pk, cr * 4u, x.pk[2 * h], x.pk[2 * h + 1]);
-                    buf_load_f64x2(rs_w, cr * 8u, x.w[2 * h], x.w[2 * h + 1]);
-                    buf_load_f64x2(rs_d, cr * 8u, x.d[2 * h], x.d[2 * h + 1]);
-                    if (ADAM) { buf_load_f64x2(rs_am, cr * 8u, x.am[(2 * h) % EA], x.am[(2 * h + 1) % EA]); buf_load_f64x2(rs_av, cr * 8u, x.av[(2 * h) % EA], x.av[(2 * h + 1) % EA]); }
-                    if (first + 1 >= r.cnt) x.pk[2 * h + 1] = x.pk[2 * h];
-                }
-                return x;
-            }
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const int cr = r.c0 + min(rr + LPS * e, max(r.cnt, 1) - 1);
-                x.pk[e] = buf_load_u32(rs_pk, (uint32_t)cr * 4u); x.w[e] = buf_load_f64(rs_w, (uint32_t)cr * 8u); x.d[e] = buf_load_f64(rs_d, (uint32_t)cr * 8u);
-                if (ADAM) { x.am[e % EA] = buf_load_f64(rs_am, (uint32_t)cr * 8u); x.av[e % EA] = buf_load_f64(rs_av, (uint32_t)cr * 8u); }
-            }
-            return x;
-        };
-        auto issue_gathers = [&](const Rec& r, const Str& x) -> Gat {
-            Gat g;
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const uint32_t p = x.pk[e];
-                g.sj[e] = buf_load_f64(rs_S, (uint32_t)(r.rbj + (int)((p >> 16) & 0x7FFFu)) * 8u);      // S({j,k}): a gather inside row j (L1 / L2)
-                g.si[e] = s_rows[r.rbi + (int)(p & 0x7FFFu)];                                              // S({k,i}): the band's rows in the LDS
-            }
-            const int ta = XT ? r.seg : r.sa, tb = r.sb;
-                        // this and the single S store: C4 1059.5 -> 1045.8 / 1083 -> 1059 us, C2 within noise (profiles/r03_buffer_instructions.txt)
-            g.T1 = buf_load_f64(rs_T, (uint32_t)((lane & 1) ? tb : ta) * 8u);
-            g.T2 = 0.0;
-            g.So = s_rows[r.sa - pd.row_lo];
-            return g;
-        };
-        // arithmetic + stores of one segment group (DESC_PGD.m:193-233), everything in registers
-        auto compute = [&](const Rec& r, const Str& x, const Gat& g0) {
-            const int cnt = r.cnt;
-            Gat g = g0;
-            const double tconv = fx_to_double(g0.T1, a.fx_inv);       // this lane's load: T1 (even lanes) or T2 (odd lanes)
-            g.T1 = dpp_mov_f64<0xA0>(tconv);        // quad_perm:[0,0,2,2]: the even lane's value = T1
-            g.T2 = dpp_mov_f64<0xF5>(tconv);        // quad_perm:[1,1,3,3]: the odd lane's value = T2
-            double ws[E], mo[EA], vo[EA];
-            uint32_t okm = 0;
-            double part = 0.0;
-            if (__ballot(cnt > 0) != 0ull) {               // wave-uniform; no memory operation inside
-                const double nv = cnt > 0 ? s_nv[cnt] : 0.0;
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    // idle lanes (ok false) hold a copy of the segment's last cycle (load_stream clamps): what they compute from it is finite and
-                    // discarded below (ws[e] = 0, no part in any sum), so only the sums mask them
-                    const bool ok = cidx(e) < cnt;
-                    const uint32_t p = x.pk[e];
-                    const double w = ok ? x.w[e] : 0.0, d = x.d[e];
-                    if (ok) okm |= 1u << e;
-                    const double ss = g.sj[e] + g.si[e];                                                 // S(jk)+S(ki)
-                    obj_acc += w * ss;                                                                   // :233, one sweep late
-                    const double gr = ss + (((p & 0x8000u) ? g.T1 : 0.0) + ((p & 0x80000000u) ? g.T2 : 0.0)) * d;   // :193
-                    ws[e] = gr;
-                    part += ok ? gr * nv : 0.0;
-                }
-                const double dot = group_sum<LPS>(part);                                                 // :199-201
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const double gr = ws[e] - dot * nv;
-                    if (ADAM) {                            // HybridGradient.m:28-35 (strategy 0): apply_step with the moments in registers
-                        const double mt = (a.st.beta1 * x.am[e % EA]) + (1.0 - a.st.beta1) * gr;
-                        const double vt = (a.st.beta2 * x.av[e % EA]) + (1.0 - a.st.beta2) * (gr * gr);
-                        mo[e % EA] = mt; vo[e % EA] = vt;
-                        const double cm = mt / a.st.bc1, cv = vt / a.st.bc2;
-                        ws[e] = ((okm >> e) & 1u) ? x.w[e] + (-a.st.lr * cm / (sqrt(cv) + 1e-8)) : 0.0;
-                    } else
-                    ws[e] = ((okm >> e) & 1u) ? apply_step<STEP>(a.st, x.w[e], gr, 0) : 0.0;             // :207
-                }
-                uint32_t act = okm;                        // simplex threshold (:215-223), Michelot fixed point
-                double s1v = 0.0; int na = 1;
-                for (;;) {
-                    double sp = 0.0;
-#pragma unroll
-                    for (int e = 0; e < E; ++e) sp += ((act >> e) & 1u) ? ws[e] : 0.0;
-                    s1v = group_sum<LPS>(sp) - 1.0;
-                    if (LPS == 8) na = max(group8_sum((int)__popc(act)), 1);
-                    else if (LPS == 16) na = max(group16_sum((int)__popc(act)), 1);
-                    else {
-                        na = 0;
-#pragma unroll
-                        for (int e = 0; e < E; ++e) na += group_count<LPS>((act >> e) & 1u, lane);
-                        na = max(na, 1);
-                    }
-                    const double nad = (double)na;
-                    uint32_t keep = 0;
-#pragma unroll
-                    for (int e = 0; e < E; ++e) keep |= (((act >> e) & 1u) && ws[e] * nad > s1v) ? 1u << e : 0u;
-                    const bool changed = keep != act;
-                    act = keep;
-                    if (!__any(changed)) break;
-                }
-                const double T = s1v / (double)na;
-                double sn = 0.0;
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const double wn = fmax(ws[e] - T, 0.0);                                              // :224
-                    ws[e] = wn;
-                    if ((okm >> e) & 1u) sn += wn * x.d[e];
-                }
-                part = group_sum<LPS>(sn);                                                               // :229
-            }
-            if constexpr (PAIR) {                      // 16-byte stores of the pairs; the last pair of an odd segment: its first cycle alone
-#pragma unroll
-                for (int h = 0; h < E / 2; ++h) {
-                    const uint32_t off = (uint32_t)(r.c0 + cidx(2 * h)) * 8u;
-                    const bool ok0 = (okm >> (2 * h)) & 1u, ok1 = (okm >> (2 * h + 1)) & 1u;
-                    if (ok1) {
-                        buf_store_f64x2(rs_wn, off, ws[2 * h], ws[2 * h + 1]);
-                        if (ADAM) { buf_store_f64x2(rs_amo, off, mo[(2 * h) % EA], mo[(2 * h + 1) % EA]); buf_store_f64x2(rs_avo, off, vo[(2 * h) % EA], vo[(2 * h + 1) % EA]); }
-                    } else if (ok0) {
-                        buf_store_f64(rs_wn, off, ws[2 * h]);
-                        if (ADAM) { buf_store_f64(rs_amo, off, mo[(2 * h) % EA]); buf_store_f64(rs_avo, off, vo[(2 * h) % EA]); }
-                    }
-                }
-            } else
-#pragma unroll
-            for (int e = 0; e < E; ++e)
-                if ((okm >> e) & 1u) {
-                    buf_store_f64(rs_wn, (uint32_t)(r.c0 + rr + LPS * e) * 8u, ws[e]);
-                    if (ADAM) { buf_store_f64(rs_amo, (uint32_t)(r.c0 + rr + LPS * e) * 8u, mo[e % EA]); buf_store_f64(rs_avo, (uint32_t)(r.c0 + rr + LPS * e) * 8u, vo[e % EA]); }
-                }
-            if (!XT && cnt > 0 && rr < 2) buf_store_f64(rs_Sn, (uint32_t)(rr == 0 ? r.sa : r.sb) * 8u, part);
-            if (cnt > 0 && rr == 0) {
-                chg_acc += fabs(part - g.So);                                                            // :232
-                if constexpr (XT) buf_store_f64(rs_sl, (uint32_t)r.seg * 8u, part);       // sharded: k_unpack_S copies it into the CSR-aligned replica
-            }
-        };
-
-        // ---- prologue: records 0..3, streams 0..2, gathers 0
-        Rec R0, R1, R2, R3; Str S0, S1, S2, S3; Gat G0, G1;
-        RecRaw Q;
-        { const RecRaw q = load_raw(0); R0 = land(q); S0 = load_stream(R0); }
-        { const RecRaw q = load_raw(1); R1 = land(q); S1 = load_stream(R1); }
-        { const RecRaw q = load_raw(2); R2 = land(q); S2 = load_stream(R2); }
-        Q = load_raw(3);
-        // the band's rows of S_old -> LDS, while the first streams are in flight
-        {
-            // up to 19 loads in flight per thread: one batch for 1024 threads, two for 512 (38 at once cost the 64 x 4 instance 3.5 %)
-            constexpr int RL = (BAND_ROW_CAP + 1023) / 1024;
-            // 16 bytes per lane (half the address-unit cycles per byte, see PAIR): thread t takes the doubles 2 t, 2 t + 1 of every batch of 2 NT.
-            // The clamped load of a one-entry band would end one double past the rows -- such a band (one node of degree 1, no triangle) never has a
-            // segment and therefore never a piece; all the same rs_S carries the array's real length (the read returns 0) and the CSR-aligned arrays
-            // are allocated two doubles longer.
-            constexpr int RL2 = (RL + 1) / 2;
-            for (int base = 0; base < pd.row_len; base += 2 * RL2 * NT) {
-                double v0[RL2], v1[RL2];
-#pragma unroll
-                for (int u = 0; u < RL2; ++u)
-                    buf_load_f64x2(rs_S, (uint32_t)(pd.row_lo + min(base + 2 * (u * NT + tid), max(pd.row_len - 2, 0))) * 8u, v0[u], v1[u]);
-#pragma unroll
-                for (int u = 0; u < RL2; ++u) {
-                    const int t0 = base + 2 * (u * NT + tid);
-                    if (t0 + 1 < pd.row_len) { s_rows[t0] = v0[u]; s_rows[t0 + 1] = v1[u]; }
-                    else if (t0 < pd.row_len) s_rows[t0] = pd.row_len >= 2 ? v1[u] : v0[u];      // the row's last double: the clamped load ended on it
-                }
-            }
-        }
-        __syncthreads();
-        G0 = issue_gathers(R0, S0);
-        // one iteration: Ra/Sa/Ga = group g (computed), Rb/Sb = g+1 (gathers issued into Gb), Rd/Sd <- g+3
-        auto step = [&](int g, const Rec& Ra, const Str& Sa, const Gat& Ga, const Rec& Rb, const Str& Sb, Gat& Gb, Rec& Rd, Str& Sd) {
-            const RecRaw qn = load_raw(g + 4);
-            Gb = issue_gathers(Rb, Sb);
-            Rd = land(Q);
-            Sd = load_stream(Rd);
-            compute(Ra, Sa, Ga);
-            Q = qn;
-        };
-        for (int g = 0; g < nit; g += 4) {                 // the tail iterations past nit compute nothing (cnt = 0)
-            step(g,     R0, S0, G0, R1, S1, G1, R3, S3);
-            step(g + 1, R1, S1, G1, R2, S2, G0, R0, S0);
-            step(g + 2, R2, S2, G0, R3, S3, G1, R1, S1);
-            step(g + 3, R3, S3, G1, R0, S0, G0, R2, S2);
-        }
-        if (ticket >= 0) flush_partials((int)gridDim.x + ticket);      // a tail piece: its own pair of partials
-        else ++pc;
-    }
-    if (b.wg_clock && tid == 0) {
-        b.wg_clock[2 * blockIdx.x + 1] = wall_clock64();
-        b.wg_clock[2 * gridDim.x + blockIdx.x] = clock64() - wg_c0;          // shader-clock cycles of the same interval: the clock the box ran at
     }
 }
 
@@ -1762,17 +811,10 @@ __global__ void k_fill(double* p, int64_t n, double v) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = v;
 }
 
-// self-test kernel for the group reductions (tests/test_gpu_parity.py)
-__global__ void k_selftest_group_sum(const double* in, double* out, int G) {
-    const int t = threadIdx.x + blockIdx.x * blockDim.x;
-    const double v = in[t];
-    out[t] = (G == 16) ? group_sum<16>(v) : (G == 32) ? group_sum<32>(v) : group_sum<64>(v);
-}
-
 // ===========================================================================
 // TWO-PHASE iteration: the cut at DESC_PGD.m:207 for a caller-supplied step rule
 // ===========================================================================
-// params.Gradient may be any object with a GetStep method (:207).  The sweeps above fuse :185-230 into one pass around one of the three known
+// params.Gradient may be any object with a GetStep method (:207).  The sweeps (sweep_*.hip) fuse :185-230 into one pass around one of the three known
 // rules; here the same iteration is two kernels with the caller between them:
 //   gradient pass (:185-204)  mirror-weight sums (node layout: k_colsum_node's fixed-point totals; gather layout: in the kernel), grad_long,
 //                             tangent projection -> ONE double per cycle, nothing else written
@@ -2010,146 +1052,7 @@ __global__ __launch_bounds__(64) void k_ext_finalize(FinArgs fc, FinArgs fo, dou
 
 }  // namespace desc
 
-using namespace desc;
-
-// ------------------------------------------------------------------- handle --
-enum { VARIANT_GATHER = 1, VARIANT_NODE = 2 };
-
-struct desc_pgd {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int64_t n = 0, m = 0, m_pos = 0, m_cycle = 0;
-    int32_t max_cnt = 0, n_sample = 0, max_deg = 0;
-    int variant = VARIANT_GATHER;
-    bool band_jmajor = false;   // band sweep: j-block-major units (large graphs) instead of contiguous ranges
-    int grid = 0;               // sweep grid (multiple of 8)
-    int obj_grid = 0;
-    int colsum_grid = 0, colsum_stride = 0, colsum_cl = 16;     // colsum_cl: lanes per segment in k_colsum_node (8 when the runs are short)
-    int colsum_fx_bits = 47;                                     // fixed-point position of the column sums: 62 - ceil(log2(max degree + 1))
-    int colsum_nodes = 0;                                        // nodes k_colsum_node visits (sharded: those with segments of this rank in their row)
-    int colsum_long = 0;                                         // nodes that get a whole workgroup in k_colsum_node (the rest: a wave each, sharded runs)
-    int64_t colsum_entries = 0;                                  // (cycle, endpoint) pairs the column sums read: cycles whose mirror was sampled, per endpoint
-    int64_t n_pieces = 0, n_bands = 0, piece_row_entries = 0;    // band sweep plan: pieces, bands, CSR entries of band rows loaded per sweep
-    int band = 0;
-    bool band_ok = false;       // k_sweep_band applies (segments <= 64 cycles, rows fit the LDS)
-    bool small_ok = false;      // k_sweep_small: one rank, < 2 M cycles, segments of at most 64 cycles (the reference's demo sizes)
-    int small_grid = 0;
-    int band_grid = 0, band_rows = 0;
-    size_t band_lds = 0;
-    PieceDesc* d_pieces = nullptr;
-    int32_t* d_piece_ptr = nullptr;
-    unsigned long long* d_wg_clock = nullptr;   // diagnostics: DESC_DEBUG_WGCLOCK
-    int band_tail_first = 0, band_ntail = 0;    // shared tail of the band sweep (BandSweepArgs)
-    int32_t* d_ticket = nullptr;
-    int32_t* d_node_order = nullptr;            // column sums: the nodes gone through (one workgroup each, dispatched in index order); sharded: only those with owned segments
-    int2* d_node_run = nullptr;                 // sharded runs: per node the run [x, y) of its row's CSR slots whose segments this rank owns (NULL: whole rows)
-    hvec<void*> allocs;
-    int uc_default = 0;         // which streamed arrays go to uncached memory (dalloc_stream)
-    // common
-    int32_t* d_cum = nullptr;
-    double *d_S0 = nullptr, *d_w[2] = {nullptr, nullptr}, *d_S[2] = {nullptr, nullptr};
-    double *d_adam_m[2] = {nullptr, nullptr}, *d_adam_v[2] = {nullptr, nullptr}, *d_nv = nullptr, *d_partials = nullptr;
-    double *d_obj = nullptr, *d_avg = nullptr, *d_scratch = nullptr;
-    DevState* d_state = nullptr;
-    // gather variant
-    int32_t *d_pos_edge = nullptr, *d_ejk = nullptr, *d_eki = nullptr, *d_ikj = nullptr, *d_jki = nullptr;
-    // node variant
-    EdgeInfo* d_einfo = nullptr;
-    uint32_t* d_pk = nullptr;
-    uint32_t* d_moff = nullptr;  // per CSR slot: start of its run in d_midx
-    uint16_t* d_midx = nullptr;  // column index of every contributing cycle, in the order the column-sum pass reads them
-    int2* d_adj_seg = nullptr;   // per CSR slot: slot_record() = {first contributing cycle of the incident segment, their number | (row node is the smaller endpoint) << 31}
-    int32_t *d_rowptr = nullptr, *d_src_start = nullptr, *d_eslot = nullptr;
-    ChunkDesc* d_chunk_desc = nullptr;
-    int nchunks = 0;
-    double *d_T = nullptr, *d_Svec = nullptr;
-    uint8_t* d_seg_perm = nullptr;     // natural in-segment offset of every device-order cycle
-    // sharding (world == 1: the whole problem)
-    int rank = 0, world = 1;
-    int64_t seg_lo = 0, seg_hi = 0;     // device-order range of segments owned by this rank
-    int64_t cyc_lo = 0, cyc_hi = 0;     // their cycles
-    int ch_lo = 0;                      // first chunk owned
-    int64_t slice_len = 0;              // doubles per rank in the S exchange buffer
-    int64_t slice_S = 0;                // ... of which S values (the rest: SHARD_PARTS pairs of partials)
-    desc_collectives coll{};            // fused protocol: the caller's collectives (RCCL entry points + communicator)
-    hipStream_t comm_stream = nullptr;  // second stream: exchange + unpack overlap the next column-sum pass
-    hipEvent_t ev_col = nullptr, ev_rs = nullptr, ev_sw = nullptr, ev_ag = nullptr;
-    StepArgs cur_step{}; bool cur_adam = false;      // sharded sweeps: the step of the sweep in progress (its exchange parts are separate launches)
-    int unpack_pending = 0;             // fused protocol: sweep whose all-gathered S still has to be unpacked (on the compute stream, behind ev_ag)
-    bool own_xbuf = false, force_coll = false;
-    hvec<int64_t> rank_seg;      // world+1 segment boundaries
-    double* x_T = nullptr;              // caller-bound exchange buffers (device): owner-sorted partial mirror sums (send)
-    double* x_Trecv = nullptr;          // reduce-scattered mirror sums of the owned segments
-    int32_t* d_xpos = nullptr;          // 2m: CSR slot -> position of its column sum in x_T (k_xpos)
-    int32_t* d_spos = nullptr;          // 2m: CSR slot -> position of its edge's S in the gathered slices x_sall
-    int2* d_xt = nullptr;               // m_pos (device order; owned segments filled): {ta, tb} = places of T1 / T2 in x_Trecv, ta also in the slice
-    int64_t t_part = 0;                 // words per block of the exchange layout (one block per virtual owner = (rank, part))
-    int xparts = 1;                     // exchange parts per rank (NodePlan::xparts): one reduce-scatter and one sweep launch each
-    hvec<int64_t> xseg;                 // xparts + 1: device-order segment boundaries of this rank's parts
-    hvec<int64_t> xslice_off;           // xparts: first edge of the part - first edge of the rank (offset of the part's S in the rank's slice)
-    hvec<int> xpiece_base, xpiece_ptr_base, xtail_first, xntail;      // per part: where its pieces / piece_ptr start in d_pieces / d_piece_ptr, its shared tail
-    hipEvent_t ev_rsx[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // fused protocol: reduce-scatter of part c done
-    double* x_sall = nullptr;           //   world * slice_len
-    bool borrowed_stream = false, objective_done = false;
-    int last_parts = 0;                 // workgroup partials the last sharded sweep wrote
-    int final_obj_T = -1;               // sweep count for which download already evaluated the objective
-    int pending_fin = 0, pending_parts = 0;   // sweep whose bookkeeping (k_finalize) rides on the next column-sum launch
-    int32_t* d_rank_seg = nullptr;
-    int trace_cap = 0;          // allocated length of d_obj / d_avg (the largest budget this handle has seen)
-    int iters_cap = 0;          // max(1, params.iters) of the last reset: what the caller's trace buffers hold
-    // run state
-    desc_params p{};
-    bool armed = false;
-    int t_done = 0;             // sweeps enqueued since reset
-    int t_plugin = 0;           // plugin counter (PiecewiseStepSize.t / HybridGradient.t)
-    double ms_upload = 0, ms_cycle_d = 0, ms_pgd = 0;
-    std::string kname;
-    std::string last_sweep;     // the sweep instance launched last, with its template arguments (desc_debug_last_sweep: tests assert which kernel ran)
-    // caller-supplied step rule (desc_pgd_ext_*): the iteration cut at DESC_PGD.m:207
-    int ext_phase = 0;          // 0 not begun | EXT_GRAD_DUE | EXT_STEP_DUE | EXT_STOPPED
-    double* d_ext_io = nullptr; // m_cycle doubles in the reference's cycle order: host-mode staging of grad_long and of the step
-    double* d_ext_out = nullptr;        // {average_change, objective, stop flag} of the iteration just applied
-    hipEvent_t ev_ext[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // gradient pass [0,1]; apply pass [2,3]; objective + stop rule [3,4]
-    double ext_ms[3] = {0, 0, 0};       // device time of the last gradient pass, apply pass, objective (desc_pgd_ext_laps)
-};
-
 namespace {
-
-template <class T>
-int dalloc(desc_pgd* h, T** p, size_t count) {
-    *p = nullptr;
-    void* q = nullptr;
-    DESC_HIP(dev_alloc(&q, sizeof(T) * (count > 0 ? count : 1)));
-    h->allocs.push_back(q);
-    *p = (T*)q;
-    return DESC_OK;
-}
-// The arrays the band sweep streams through exactly once per launch and never writes -- S0 (8 B per cycle) and the packed words (4 B) --
-// live in UNCACHED device memory (MTYPE UC; devmem.hip): their lines do not stay in the L2, where the rows of S the sweep gathers from then
-// keep their place.  Measured (profiles/r03_uncached_streams.txt, rocprofv3 sweep averages in one call): C4 1170 -> 1130 us (-3.4 %); the
-// weights too (read, written, read again by the column sums): +17 %, not done; C5 / C2 / C3: see the file.  DESC_DEBUG_UNCACHED overrides
-// the mask (1 weights, 2 S0, 4 packed words, 8 the column-index stream of the column sums, 16 their slot records; default 6 on graphs
-// whose S does not fit the L2s, else 0).
-template <class T>
-int dalloc_stream(desc_pgd* h, T** p, size_t count, int bit) {
-    const char* ev = std::getenv("DESC_DEBUG_UNCACHED");
-    const int mask = ev ? std::atoi(ev) : h->uc_default;
-    if (!(mask & bit)) return dalloc(h, p, count);
-    *p = nullptr;
-    void* q = nullptr;
-    DESC_HIP(dev_alloc_uncached(&q, sizeof(T) * (count > 0 ? count : 1)));
-    h->allocs.push_back(q);
-    *p = (T*)q;
-    return DESC_OK;
-}
-void dfree(desc_pgd* h, void* q) {
-    if (!q) return;
-    for (auto& x : h->allocs) if (x == q) { x = nullptr; break; }
-    dev_free(q);
-}
-
-int set_device(const desc_pgd* h) { DESC_HIP(hipSetDevice(h->device)); return DESC_OK; }
-int64_t local_cycles(const desc_pgd* h) { return h->variant == VARIANT_NODE ? h->cyc_hi - h->cyc_lo : h->m_cycle; }
 
 void free_all(desc_pgd* h) {
     if (!h) return;
@@ -2164,12 +1067,6 @@ void free_all(desc_pgd* h) {
     delete h;
 }
 
-template <class T>
-int upload(desc_pgd* h, T* dst, const T* src, size_t count) {
-    if (count) DESC_HIP(hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyHostToDevice, h->stream));
-    return DESC_OK;
-}
-
 StepArgs make_step(desc_pgd* h, bool* adam, int rd, int wr) {
     const desc_params& p = h->p;
     StepArgs s{};
@@ -2177,118 +1074,6 @@ StepArgs make_step(desc_pgd* h, bool* adam, int rd, int wr) {
     // one GetStep call per iteration (DESC_PGD.m:207): the plugin counter advances first
     *adam = plugin_step(p, ++h->t_plugin, s);
     return s;
-}
-
-// ------------------------------------------------------------ sweep instances --
-// Every instance of a sweep kernel that can be launched is written once, as an entry of its family's table.  The launch, the kernel's address
-// (hipFuncSetAttribute, the occupancy query) and the names desc_debug_last_sweep and desc_pgd_kernel_name return all come from that entry; the
-// rule from the longest segment to an entry's shape is one function per family.
-struct SweepShape { int lps, E; };      // lanes per segment x cycles per lane (gather layout and k_sweep_small: E = 0)
-template <class... A>
-struct SweepInst {
-    SweepShape sh;
-    int NT;                             // threads per workgroup
-    void (*kern[2])(A...);              // {constant step, Adam}; band sweep: {one rank, XT}
-};
-constexpr int STEP_OF[2] = {DESC_STEP_CONSTANT, DESC_STEP_HYBRID};      // the STEP argument of kern[adam]
-template <class I, size_t N>
-const I* sweep_inst(const I (&table)[N], SweepShape sh) {
-    for (const I& i : table) if (i.sh.lps == sh.lps && i.sh.E == sh.E) return &i;
-    fail(DESC_ERR_STATE, "no sweep instance of %d lanes per segment x %d cycles per lane", sh.lps, sh.E);
-    return nullptr;
-}
-template <class... V>
-std::string inst_name(const char* fmt, V... v) { char nm[64]; snprintf(nm, sizeof nm, fmt, v...); return nm; }
-
-// gather layout: G lanes per segment; above 64 cycles (G = 0) k_sweep_big, the multi-pass wave-per-edge kernel
-template <int G>
-constexpr SweepInst<SweepArgs> gather_inst() { return {{G, 0}, 256, {k_sweep<G, DESC_STEP_CONSTANT>, k_sweep<G, DESC_STEP_HYBRID>}}; }
-constexpr SweepInst<SweepArgs> big_inst() { return {{0, 0}, 256, {k_sweep_big<DESC_STEP_CONSTANT>, k_sweep_big<DESC_STEP_HYBRID>}}; }
-const SweepInst<SweepArgs> GATHER_INSTS[] = {gather_inst<16>(), gather_inst<32>(), gather_inst<64>(), big_inst()};
-SweepShape gather_shape(int c) { return {c <= 16 ? 16 : c <= 32 ? 32 : c <= 64 ? 64 : 0, 0}; }      // 16, 32, 64 or 0: each has its entry
-std::string gather_prefix(SweepShape sh) { return sh.lps ? inst_name("k_sweep<%d,", sh.lps) : std::string("k_sweep_big<"); }
-int launch_gather(desc_pgd* h, const SweepArgs& a, bool adam) {
-    const auto* k = sweep_inst(GATHER_INSTS, gather_shape(h->max_cnt));
-    if (!k) return DESC_ERR_STATE;
-    h->last_sweep = gather_prefix(k->sh) + inst_name("%d>", STEP_OF[adam]);
-    hipLaunchKernelGGL(k->kern[adam], dim3(h->grid), dim3(k->NT), 0, h->stream, a);
-    return DESC_OK;
-}
-
-// node layout: lanes per segment x cycles per lane >= longest segment
-// (33..64 cycles: 32 lanes x 2 cycles keeps all 8 waves of the workgroup busy in the arithmetic --
-//  measured 2 % faster than 16 lanes x 4 cycles at C2 and C4)
-template <int LPS, int E>
-constexpr SweepInst<NodeSweepArgs> node_inst() { return {{LPS, E}, SWEEP_THREADS, {k_sweep_node<LPS, E, DESC_STEP_CONSTANT>, k_sweep_node<LPS, E, DESC_STEP_HYBRID>}}; }
-const SweepInst<NodeSweepArgs> NODE_INSTS[] = {node_inst<16, 1>(), node_inst<16, 2>(), node_inst<32, 2>(), node_inst<32, 4>(), node_inst<64, 4>()};
-SweepShape node_shape(int c) { return {c <= 32 ? 16 : c <= 128 ? 32 : 64, c <= 16 ? 1 : c <= 64 ? 2 : 4}; }      // 16 x 1, 16 x 2, 32 x 2, 32 x 4 or 64 x 4: each has its entry
-std::string node_prefix(SweepShape sh) { return inst_name("k_sweep_node<%d,%d,", sh.lps, sh.E); }
-int launch_node(desc_pgd* h, const NodeSweepArgs& a, bool adam) {
-    const auto* k = sweep_inst(NODE_INSTS, node_shape(h->max_cnt));
-    if (!k) return DESC_ERR_STATE;
-    h->last_sweep = node_prefix(k->sh) + inst_name("%d>%s", STEP_OF[adam], a.xt ? " sharded" : "");
-    hipLaunchKernelGGL(k->kern[adam], dim3(h->grid), dim3(k->NT), 0, h->stream, a);
-    return DESC_OK;
-}
-
-// Band sweep instances by the longest segment: lanes per segment x cycles per lane, threads per workgroup.
-//   <= 16 cycles: 16 x 1, 1024     <= 32: 16 x 2, 512 (8 x 4, 512 on small graphs)     <= 64: 16 x 4, 512     <= 128: 32 x 4, 512     <= 256: 64 x 4, 512
-// (33..64 cycles: 8 waves with 4 cycles per lane beat 16 waves of 32 x 2 by 5 % at C2 and C4 -- the DPP reductions are shared by four
-//  segments per wave instead of two.  17..32 cycles: 8 lanes x 4 cycles, eight segments per wave with their records in per-lane vector
-//  loads (they would spill the SGPRs), gains 4-5 % where S stays in the L2 (C3) and loses 1-2 % at C5; there 16 x 2 on 8 waves beats
-//  the same shape on 16 waves by 2-4 % (12 waves: 1 %; 4 waves lose 7-22 % everywhere): fewer waves keep more of the j rows in the caches --
-//  the PMC traffic of the C4 sweep fell from 6.2 to 5.6 GB with the 8-wave shape.)
-// The Adam plugin: 512-thread instances (the moments ride in the stream sets) up to 64 cycles: 16 x 1, 16 x 2, 32 x 2.
-template <int LPS, int E, int STEP, int NT>
-constexpr SweepInst<BandSweepArgs> band_inst() { return {{LPS, E}, NT, {k_sweep_band<LPS, E, STEP, NT, false>, k_sweep_band<LPS, E, STEP, NT, true>}}; }
-const SweepInst<BandSweepArgs> BAND_INSTS[] = {band_inst<16, 1, DESC_STEP_CONSTANT, 1024>(), band_inst<16, 2, DESC_STEP_CONSTANT, 512>(), band_inst<8, 4, DESC_STEP_CONSTANT, 512>(),
-                                               band_inst<16, 4, DESC_STEP_CONSTANT, 512>(), band_inst<32, 4, DESC_STEP_CONSTANT, 512>(), band_inst<64, 4, DESC_STEP_CONSTANT, 512>()};
-const SweepInst<BandSweepArgs> BAND_ADAM_INSTS[] = {band_inst<16, 1, DESC_STEP_HYBRID, 512>(), band_inst<16, 2, DESC_STEP_HYBRID, 512>(), band_inst<32, 2, DESC_STEP_HYBRID, 512>()};
-// Adam above 64 cycles: 4 cycles per lane + the moments do not fit the registers -- no band instance, k_sweep_node sweeps
-bool band_adam_ok(const desc_pgd* h) { return h->band_ok && h->max_cnt <= 64; }
-SweepShape band_shape(const desc_pgd* h, bool adam) {      // constant step: the six shapes of BAND_INSTS; Adam (at most 64 cycles): the three of BAND_ADAM_INSTS
-    const int c = h->max_cnt;
-    if (adam) return c <= 16 ? SweepShape{16, 1} : c <= 32 ? SweepShape{16, 2} : SweepShape{32, 2};
-    if (c > 16 && c <= 32 && !h->band_jmajor) return SweepShape{8, 4};      // graphs whose S stays in the L2 (contiguous ranges)
-    return c <= 16 ? SweepShape{16, 1} : c <= 32 ? SweepShape{16, 2} : c <= 64 ? SweepShape{16, 4} : c <= 128 ? SweepShape{32, 4} : SweepShape{64, 4};
-}
-const SweepInst<BandSweepArgs>* band_inst_of(const desc_pgd* h, bool adam) {
-    return adam ? sweep_inst(BAND_ADAM_INSTS, band_shape(h, true)) : sweep_inst(BAND_INSTS, band_shape(h, false));
-}
-std::string band_prefix(SweepShape sh) { return inst_name("k_sweep_band<%d,%d,", sh.lps, sh.E); }
-int launch_band(desc_pgd* h, const NodeSweepArgs& a, bool adam, int part) {
-    const auto* k = band_inst_of(h, adam);
-    if (!k) return DESC_ERR_STATE;
-    // the plan of exchange part `part` (one-rank handles: the only one)
-    BandSweepArgs b{a, h->d_pieces + h->xpiece_base[part], h->d_piece_ptr + h->xpiece_ptr_base[part], h->band_rows, h->d_wg_clock, h->xtail_first[part], h->xntail[part],
-                    h->d_ticket + part};
-    h->last_sweep = band_prefix(k->sh) + inst_name("%d,%d,%s>", STEP_OF[adam], k->NT, a.xt ? "XT" : "one-rank");
-    hipLaunchKernelGGL(k->kern[a.xt != nullptr], dim3(h->band_grid), dim3(k->NT), h->band_lds, h->stream, b);
-    return DESC_OK;
-}
-
-// k_sweep_small: G lanes per segment (small_ok: segments of at most 64 cycles)
-template <int G>
-constexpr SweepInst<NodeSweepArgs, int> small_inst() { return {{G, 0}, 256, {k_sweep_small<G, DESC_STEP_CONSTANT>, k_sweep_small<G, DESC_STEP_HYBRID>}}; }
-const SweepInst<NodeSweepArgs, int> SMALL_INSTS[] = {small_inst<16>(), small_inst<32>(), small_inst<64>()};
-SweepShape small_shape(int c) { return {c <= 16 ? 16 : c <= 32 ? 32 : 64, 0}; }      // 16, 32 or 64: each has its entry
-std::string small_prefix(SweepShape sh) { return inst_name("k_sweep_small<%d,", sh.lps); }
-int launch_small(desc_pgd* h, const NodeSweepArgs& a, bool adam) {
-    const auto* k = sweep_inst(SMALL_INSTS, small_shape(h->max_cnt));
-    if (!k) return DESC_ERR_STATE;
-    h->last_sweep = small_prefix(k->sh) + inst_name("%d>", STEP_OF[adam]);
-    hipLaunchKernelGGL(k->kern[adam], dim3(h->small_grid), dim3(k->NT), 0, h->stream, a, (int)(h->seg_hi - h->seg_lo));
-    return DESC_OK;
-}
-int launch_sweep_node_layout(desc_pgd* h, const NodeSweepArgs& a, bool adam, int part = 0) {
-    if (h->small_ok && a.partials == h->d_partials) return launch_small(h, a, adam);      // the plain one-rank path only
-    if (adam ? band_adam_ok(h) : h->band_ok) return launch_band(h, a, adam, part);
-    return launch_node(h, a, adam);
-}
-// workgroups (= partial pairs) of the sweep kernel that serves this step kind
-int sweep_parts(const desc_pgd* h, bool adam, bool plain_path = false) {
-    if (plain_path && h->variant == VARIANT_NODE && h->small_ok) return h->small_grid;
-    return h->variant == VARIANT_NODE && (adam ? band_adam_ok(h) : h->band_ok) ? h->band_grid + h->band_ntail : h->grid;
 }
 
 // second half of d_partials: the objective kernel of a download writes there, so the partials of the last sweep stay intact and
@@ -2366,72 +1151,6 @@ int enqueue_sweep(desc_pgd* h, int t, hipEvent_t ev0 = nullptr, hipEvent_t ev1 =
 // what an iteration waits for -- and removed in round 4.)
 int enqueue_iterations(desc_pgd* h, int n) {
     for (; n > 0; --n) { const int rc = enqueue_sweep(h, ++h->t_done); if (rc) return rc; }
-    return DESC_OK;
-}
-
-int choose_grid(desc_pgd* h) {
-    const int G = gather_shape(h->max_cnt).lps, epw = G ? 64 / G : 1;
-    int64_t want = (h->m_pos + 4 * epw - 1) / (4 * epw);
-    want = std::min<int64_t>(want, 2048);
-    want = std::max<int64_t>(want, 8);
-    h->grid = (int)((want + 7) / 8 * 8);
-    return DESC_OK;
-}
-
-// ---------------------------------------------------------------- GATHER setup
-int setup_gather(desc_pgd* h, const desc_problem* prob, const desc_structure* s, const double* shared_rij) {
-    const int64_t m = h->m, mp = h->m_pos, mc = h->m_cycle;
-    int rc;
-    if ((rc = structure_ensure_host(const_cast<desc_structure*>(s)))) return rc;
-    if ((rc = dalloc(h, &h->d_pos_edge, mp))) return rc;
-    if ((rc = dalloc(h, &h->d_ejk, mc))) return rc;
-    if ((rc = dalloc(h, &h->d_eki, mc))) return rc;
-    if ((rc = dalloc(h, &h->d_ikj, mc))) return rc;
-    if ((rc = dalloc(h, &h->d_jki, mc))) return rc;
-    if ((rc = dalloc(h, &h->d_S[0], m))) return rc;
-    if ((rc = dalloc(h, &h->d_S[1], m))) return rc;
-    choose_grid(h);
-    h->obj_grid = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (mc + 255) / 256));
-    h->kname = gather_prefix(gather_shape(h->max_cnt));
-
-    auto t0 = std::chrono::steady_clock::now();
-    hvec<int32_t> cum32((size_t)mp + 1);
-    for (int64_t l = 0; l <= mp; ++l) cum32[l] = (int32_t)s->cum_ind[l];
-    int32_t *d_k = nullptr, *d_ii = nullptr, *d_jj = nullptr; double* d_rij = nullptr;
-    if ((rc = dalloc(h, &d_k, mc))) return rc;
-    if ((rc = dalloc(h, &d_ii, m))) return rc;
-    if ((rc = dalloc(h, &d_jj, m))) return rc;
-    if (shared_rij) d_rij = const_cast<double*>(shared_rij);
-    else if ((rc = dalloc(h, &d_rij, 9 * (size_t)m))) return rc;
-    if ((rc = upload(h, h->d_cum, cum32.data(), (size_t)mp + 1))) return rc;
-    if ((rc = upload(h, h->d_pos_edge, s->pos_edge.data(), (size_t)mp))) return rc;
-    if ((rc = upload(h, h->d_ejk, s->e_jk.data(), (size_t)mc))) return rc;
-    if ((rc = upload(h, h->d_eki, s->e_ki.data(), (size_t)mc))) return rc;
-    if ((rc = upload(h, h->d_ikj, s->ikj.data(), (size_t)mc))) return rc;
-    if ((rc = upload(h, h->d_jki, s->jki.data(), (size_t)mc))) return rc;
-    if ((rc = upload(h, d_k, s->k.data(), (size_t)mc))) return rc;
-    if ((rc = upload(h, d_ii, prob->ind_i, (size_t)m))) return rc;
-    if ((rc = upload(h, d_jj, prob->ind_j, (size_t)m))) return rc;
-    if (!shared_rij && (rc = upload(h, d_rij, prob->rij, 9 * (size_t)m))) return rc;
-    DESC_HIP(hipStreamSynchronize(h->stream));
-    h->ms_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-
-    hipEvent_t e0, e1;
-    DESC_HIP(hipEventCreate(&e0)); DESC_HIP(hipEventCreate(&e1));
-    (void)hipEventRecord(e0, h->stream);
-    if (mp > 0) {
-        int g = (int)std::min<int64_t>(4096, (mp + 3) / 4);
-        hipLaunchKernelGGL(k_cycle_d, dim3(g), dim3(256), 0, h->stream, h->d_cum, h->d_pos_edge, d_ii, d_jj, d_k,
-                           h->d_ejk, h->d_eki, d_rij, h->d_S0, (int)mp);
-    }
-    (void)hipEventRecord(e1, h->stream);
-    hipError_t e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = hipGetLastError();
-    float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
-    h->ms_cycle_d = ms;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    dfree(h, d_k); dfree(h, d_ii); dfree(h, d_jj); if (!shared_rij) dfree(h, d_rij);
-    if (e != hipSuccess) return fail(DESC_ERR_HIP, "k_cycle_d: %s", hipGetErrorString(e));
     return DESC_OK;
 }
 
@@ -2922,13 +1641,6 @@ int ensure_scratch(desc_pgd* h) {
 }  // namespace
 
 extern "C" {
-
-int desc_device_count(void) {
-    int c = 0;
-    hipError_t e = hipGetDeviceCount(&c);
-    if (e != hipSuccess) return fail(DESC_ERR_HIP, "hipGetDeviceCount: %s", hipGetErrorString(e));
-    return c;
-}
 
 int desc_pgd_create(const desc_problem* prob, const desc_structure* s, int32_t device, desc_pgd** out) {
     return desc_pgd_create_shard(prob, s, device, 0, 1, out);
@@ -3684,21 +2396,6 @@ int desc_pgd_stopped(desc_pgd* h, int32_t* stopped) {
     return DESC_OK;
 }
 
-
-int desc_device_synchronize(int32_t device) {
-    DESC_HIP(hipSetDevice(device));
-    DESC_HIP(hipDeviceSynchronize());
-    return DESC_OK;
-}
-int desc_memcpy_d2h(void* host_dst, const void* dev_src, size_t bytes) {
-    if (bytes) DESC_HIP(hipMemcpy(host_dst, dev_src, bytes, hipMemcpyDeviceToHost));
-    return DESC_OK;
-}
-int desc_memcpy_h2d(void* dev_dst, const void* host_src, size_t bytes) {
-    if (bytes) DESC_HIP(hipMemcpy(dev_dst, host_src, bytes, hipMemcpyHostToDevice));
-    return DESC_OK;
-}
-
 // Test hook, host only (no device call): the band-sweep work plan of `rank` of `world` for `grid` workgroups -- bands, ranks' segment
 // ranges, pieces -- checked for its invariants (every owned segment in exactly one piece, a piece inside one band, band rows within
 // the LDS budget).  stats[8] = {bands, pieces, largest band's row entries, max / min cycles per workgroup, j-block-major?, seg_lo, seg_hi}.
@@ -3744,22 +2441,6 @@ int desc_debug_band_plan(const desc_problem* prob, const desc_structure* s, int3
     for (size_t q = 0; q < seen.size(); ++q) if (!seen[q]) return fail(DESC_ERR_STATE, "segment %lld is in no piece", (long long)(q + seg_lo));
     stats[0] = nbands; stats[1] = (int64_t)pieces.size(); stats[2] = band_rows; stats[3] = wmax; stats[4] = wmin; stats[5] = jmajor ? 1 : 0;
     stats[6] = seg_lo; stats[7] = seg_hi;
-    return DESC_OK;
-}
-
-// test hook: group_sum over a buffer of 64*k doubles
-int desc_selftest_group_sum(const double* in, double* out, int32_t count, int32_t G, int32_t device) {
-    if (!in || !out || count <= 0 || count % 64) return fail(DESC_ERR_INVALID, "count must be a positive multiple of 64");
-    if (G != 16 && G != 32 && G != 64) return fail(DESC_ERR_INVALID, "G must be 16, 32 or 64");
-    DESC_HIP(hipSetDevice(device));
-    double *di = nullptr, *dout = nullptr;
-    DESC_HIP(hipMalloc((void**)&di, sizeof(double) * count));
-    DESC_HIP(hipMalloc((void**)&dout, sizeof(double) * count));
-    DESC_HIP(hipMemcpy(di, in, sizeof(double) * count, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_selftest_group_sum, dim3(count / 64), dim3(64), 0, 0, di, dout, G);
-    DESC_HIP(hipDeviceSynchronize());
-    DESC_HIP(hipMemcpy(out, dout, sizeof(double) * count, hipMemcpyDeviceToHost));
-    (void)hipFree(di); (void)hipFree(dout);
     return DESC_OK;
 }
 

@@ -1,4 +1,4 @@
-// Device arithmetic shared by the sweep kernels of pgd.hip (one problem per handle) and batch.hip (many small problems per launch):
+// Device arithmetic shared by the sweep kernels of sweep_gather.hip, sweep_node.hip and sweep_band.hip (one problem per handle) and batch.hip (many small problems per launch):
 // the plugin step, the simplex projection threshold and the cycle-inconsistency trace.  Both files must produce the same bits
 // from the same inputs, so the text lives here once.
 #pragma once

@@ -6,8 +6,9 @@ rank or a shard.  max_cnt is pinned by n_sample_min = T: n_sample = max(ceil(med
 dense graph whose median codegree is at most 4 T and whose largest is at least T the longest segment has exactly T cycles.
 
 One table: the graph, T, the layout forced, the step kind, the world (1, or 2 / 3 / 8 ranks emulated on one card) and the exact
-instance the case must launch.  test_table_covers_every_instance (CPU) parses the instance set out of pgd.hip and checks that T is what
-the oracle's structure gives; the GPU cases then only have to confirm the dispatch and the numbers."""
+instance the case must launch.  test_table_covers_every_instance (CPU) parses the instance set out of the sweep units (sweep_gather.hip,
+sweep_node.hip, sweep_band.hip) and checks that T is what the oracle's structure gives; the GPU cases then only have to confirm the
+dispatch and the numbers."""
 import functools
 import os
 import re
@@ -146,22 +147,26 @@ def _reference(O, T, step):
 
 # ------------------------------------------------------------------------------------------------------------------ CPU guard
 def _instances():
-    """Every sweep instance the dispatch of pgd.hip can launch, named as desc_debug_last_sweep names them: the entries <family>_inst<...>()
-    of the instance tables, each standing for its two step kinds (band sweep: for one rank and XT)."""
-    with open(os.path.join(ROOT, "desc_amd", "csrc", "pgd.hip")) as f:
-        src = f.read()
+    """Every sweep instance the dispatch can launch, named as desc_debug_last_sweep names them: the entries <family>_inst<...>() of the
+    instance tables (sweep_gather.hip, sweep_node.hip, sweep_band.hip), each standing for its two step kinds (band sweep: for one rank
+    and XT)."""
+    csrc = os.path.join(ROOT, "desc_amd", "csrc")
+    units = sorted(nm for nm in os.listdir(csrc) if nm.endswith((".hip", ".cpp", ".h")))          # every unit of the library
+    assert {"pgd.hip", "pgd_handle.h", "sweep_gather.hip", "sweep_node.hip", "sweep_band.hip"} <= set(units)
+    code = []
+    for nm in units:
+        with open(os.path.join(csrc, nm)) as f:
+            code += [ln.split("//")[0] for ln in f.read().splitlines()]
     steps = {"DESC_STEP_CONSTANT": 0, "DESC_STEP_HYBRID": 2}
     with open(os.path.join(ROOT, "include", "desc_amd.h")) as f:
         hdr = f.read()
     for k, v in steps.items():
         assert re.search(r"#define\s+%s\s+%d\b" % (k, v), hdr), k
-    code = [ln.split("//")[0] for ln in src.splitlines()]
-    host = code[code.index("struct desc_pgd {"):]
     # a sweep kernel is named only where an entry is made, and launched only through an entry's pointer
-    naming = [ln for ln in host if re.search(r"\bk_sweep(_node|_small|_band|_big)?<[^%\"]", ln)]          # ("k_sweep<%d,": a name's format)
+    naming = [ln for ln in code if re.search(r"\bk_sweep(_node|_small|_band|_big)?<[^%\"]", ln)]          # ("k_sweep<%d,": a name's format)
     assert len(naming) == 5 and all(re.search(r"^constexpr SweepInst<.*> \w+_inst\(\) \{ return ", ln) for ln in naming), naming
     assert not [ln for ln in code if re.search(r"hipLaunchKernelGGL\(\(*k_sweep", ln)]
-    entries = re.findall(r"\b(gather|big|small|node|band)_inst(?:<([^>]*)>)?\(\)(?! \{)", "\n".join(host))
+    entries = re.findall(r"\b(gather|big|small|node|band)_inst(?:<([^>]*)>)?\(\)(?! \{)", "\n".join(code))
     assert len(entries) == len(set(entries)), entries          # every argument tuple in exactly one table entry
     names = set()
     for family, args in entries:
@@ -181,7 +186,7 @@ def _instances():
 
 
 def test_table_covers_every_instance(oracle):
-    """The case table names every sweep instance pgd.hip can launch, and nothing else; every case's graph gives exactly T cycles
+    """The case table names every sweep instance the sweep units can launch, and nothing else; every case's graph gives exactly T cycles
     in its longest segment (oracle structure)."""
     names = _instances()
     assert len(names) == 52, sorted(names)
