@@ -38,6 +38,7 @@ EXPORTS = [
     "desc_pgd_batch_destroy", "desc_pgd_batch_concat",
     "desc_pgd_batch_create_where", "desc_pgd_batch_built_where", "desc_pgd_batch_max_codeg", "desc_pgd_batch_build_laps", "desc_test_batch_plan",
     "desc_gcw_batch_max_n", "desc_gcw_batch_create", "desc_gcw_batch_sizes", "desc_gcw_batch_csr", "desc_gcw_batch_run", "desc_gcw_batch_destroy",
+    "desc_gcw_batch_create_where", "desc_gcw_batch_streamed_max_n",
     "desc_cemp_batch_max_degree", "desc_cemp_batch_create", "desc_cemp_batch_sizes", "desc_cemp_batch_get_samples", "desc_cemp_batch_run",
     "desc_cemp_batch_destroy", "desc_mst_batch_max_n", "desc_mst_batch_check", "desc_mst_batch_run",
     "desc_refine_batch_max_n", "desc_refine_batch_create", "desc_refine_batch_sizes", "desc_refine_batch_run", "desc_refine_batch_destroy",
@@ -346,6 +347,9 @@ def load():
     L.desc_gcw_batch_max_n.restype = C.c_int32
     L.desc_gcw_batch_max_n.argtypes = []
     L.desc_gcw_batch_create.argtypes = [C.POINTER(Problem), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.desc_gcw_batch_streamed_max_n.restype = C.c_int32
+    L.desc_gcw_batch_streamed_max_n.argtypes = []
+    L.desc_gcw_batch_create_where.argtypes = [C.POINTER(Problem), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
     L.desc_gcw_batch_sizes.argtypes = [C.c_void_p, I32P, I64P, I64P]
     L.desc_gcw_batch_csr.argtypes = [C.POINTER(Problem), C.c_int32, I64P, I64P, I32P, I32P, I32P]
     L.desc_gcw_batch_run.argtypes = [C.c_void_p, F64P, F64P, C.c_int32, C.c_double, C.c_int32, F64P, C.POINTER(SpectralInfo),
@@ -738,14 +742,33 @@ def gcw_batch_max_n():
     return int(load().desc_gcw_batch_max_n())
 
 
+def gcw_batch_streamed_max_n():
+    """desc_gcw_batch_streamed_max_n: the largest problem (nodes) the batched eigen-solve takes with its blocks streamed through LDS."""
+    return int(load().desc_gcw_batch_streamed_max_n())
+
+
+GCW_EIG = {"lds": 0, "streamed": 1, "auto": 2}       # DESC_GCW_EIG_*
+GCW_EIG_RAN = ("lds", "streamed")                    # desc_spectral_info.reserved of a batched run
+
+
+def gcw_eig_mode(eig):
+    """The DESC_GCW_EIG_* value of ``eig``; ValueError naming the three values for anything else."""
+    if not isinstance(eig, str) or eig not in GCW_EIG:
+        raise ValueError(f'eig must be "lds", "streamed" or "auto", not {eig!r}')
+    return GCW_EIG[eig]
+
+
 class GcwBatch(_BatchHandle):
     """Owner of a desc_gcw_batch*: the Spectral / GCW eigen-solve of B small problems in one launch (desc_gcw_batch_*).
-    ``probs`` is a sequence of ProblemArrays.  The handle may be run any number of times."""
+    ``probs`` is a sequence of ProblemArrays.  ``eig``: ``"lds"`` (the four blocks in LDS, up to gcw_batch_max_n() nodes),
+    ``"streamed"`` (the blocks in global memory, one staging block in LDS, up to gcw_batch_streamed_max_n() nodes) or ``"auto"``
+    (each problem by its own n: at most two launches).  The handle may be run any number of times."""
 
     _kind = "gcw"
+    _create = "create_where"
 
-    def __init__(self, probs, device=0):
-        self._open(probs, int(device))
+    def __init__(self, probs, device=0, eig="lds"):
+        self._open(probs, int(device), gcw_eig_mode(eig))
 
     def run(self, s_vec=None, weights=None, normalize_rows=False, tol=1e-13, max_iters=500):
         """One batched eigen-solve.  s_vec: the concatenated S_vec (GCW mode); weights: concatenated host weights; neither: Spectral.
@@ -765,7 +788,8 @@ class GcwBatch(_BatchHandle):
                                         ptr(vec, F64P) if s_vec is None and weights is not None else None, 1 if normalize_rows else 0,
                                         tol, max_iters, ptr(R, F64P), infos, C.byref(tm)))
         outs = [(Rb, dict(iters=i.iters, products=i.products, converged=bool(i.converged), residual=i.residual,
-                          eigenvalues=list(i.eigenvalues), ms_total=i.ms_total)) for Rb, i in zip(_split_R(R, self.node_off), infos)]
+                          eigenvalues=list(i.eigenvalues), ms_total=i.ms_total, eig=GCW_EIG_RAN[i.reserved]))
+                for Rb, i in zip(_split_R(R, self.node_off), infos)]
         return outs, _timings(tm)
 
 

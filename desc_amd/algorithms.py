@@ -395,8 +395,18 @@ def _check_batch_sizes(probs, cap, what, instead):
             raise ValueError(f"problem {b}: n = {q.n} exceeds {cap} (the {what} must fit the LDS of one workgroup): solve it with {instead}")
 
 
-def _check_gcw_batch_sizes(probs):
-    _check_batch_sizes(probs, _lib.gcw_batch_max_n(), "3n x 6 blocks of the eigen-solve", "GCW / DESC_init")
+def _check_eig(eig):
+    """``eig`` of the calls built on the batched eigen-solve: ``"lds"`` (the default: the four blocks in LDS), ``"streamed"`` (the
+    blocks in global memory, one staging block in LDS) or ``"auto"`` (each problem by its own n)."""
+    _lib.gcw_eig_mode(eig)
+    return eig
+
+
+def _check_gcw_batch_sizes(probs, eig="lds", instead="GCW / DESC_init"):
+    if eig == "lds":
+        _check_batch_sizes(probs, _lib.gcw_batch_max_n(), "3n x 6 blocks of the eigen-solve", instead)
+    else:
+        _check_batch_sizes(probs, _lib.gcw_batch_streamed_max_n(), "one 3n x 6 block of the streamed eigen-solve", instead)
 
 
 def _sorted_s_list(probs, perms, S_list, noun="S_vec", ok=lambda S: np.isfinite(S) & (S >= 0),
@@ -420,47 +430,58 @@ def _sorted_s_list(probs, perms, S_list, noun="S_vec", ok=lambda S: np.isfinite(
     return np.concatenate(parts) if parts else np.zeros(0)
 
 
-def _gcw_batch_run(probs, device, **run_args):
-    with _batch_handle(_lib.GcwBatch, probs, device) as batch:
+def _gcw_batch_run(probs, device, eig="lds", **run_args):
+    with _batch_handle(_lib.GcwBatch, probs, device, eig) as batch:
         return batch.run(**run_args)
 
 
-def Spectral_batch(problems, device=0, return_info=False):
+def Spectral_batch(problems, device=0, return_info=False, eig="lds"):
     """Spectral (Algorithms/Spectral.m:15) on B independent small problems in one GPU launch (desc_gcw_batch_*; the reference has no such
     call).  ``problems`` as for DESC_PGD_batch.  Returns a list of R (3 x 3 x n_b); with ``return_info`` a list of (R, info) with the
     record Spectral() gives plus the call's ``timings``.  Problem b's result does not depend, in any bit, on the batch around it.
-    Refused (ValueError): an empty edge list, a problem of more than ``_lib.gcw_batch_max_n()`` nodes (solve it with Spectral)."""
+
+    ``eig`` says where the kernel keeps its four 3n x 6 blocks.  ``"lds"`` (the default) keeps them in LDS and takes
+    ``_lib.gcw_batch_max_n()`` (278) nodes.  ``"streamed"`` keeps them in global memory and stages the source of each product in LDS:
+    ``_lib.gcw_batch_streamed_max_n()`` (1112) nodes, the same bits, slower where both apply.  ``"auto"`` solves a problem of at most 278
+    nodes in LDS and a larger one streamed (at most two launches); ``info["eig"]`` says which kernel solved a problem.
+
+    Refused (ValueError): an empty edge list, an ``eig`` other than the three, a problem of more nodes than the cap of ``eig`` (solve
+    it with Spectral)."""
+    _check_eig(eig)
     _check_sequence(problems)
     probs, perms = _marshal_problems(problems)
     if not probs:
         return []
-    _check_gcw_batch_sizes(probs)
-    outs, timings = _gcw_batch_run(probs, device, normalize_rows=False)
+    _check_gcw_batch_sizes(probs, eig)
+    outs, timings = _gcw_batch_run(probs, device, eig, normalize_rows=False)
     return [(R, dict(info, timings=timings)) for R, info in outs] if return_info else [R for R, _ in outs]
 
 
-def GCW_batch(problems, S_list, device=0, return_info=False):
+def GCW_batch(problems, S_list, device=0, return_info=False, eig="lds"):
     """GCW (Utils/GCW.m) on B independent small problems in one GPU launch: ``S_list[b]`` is problem b's S_vec in the caller's edge
     order; the weights 1/(S^1.5 + 1e-8) are formed on the device.  Returns a list of R (3 x 3 x n_b); with ``return_info`` a list of
-    (R, info).  Refused (ValueError, before the device is touched): S_list of the wrong length or an entry of the wrong size, a negative
-    or non-finite S entry, an empty edge list, a problem of more than ``_lib.gcw_batch_max_n()`` nodes (solve it with GCW)."""
+    (R, info).  ``eig`` as for Spectral_batch.  Refused (ValueError, before the device is touched): S_list of the wrong length or an
+    entry of the wrong size, a negative or non-finite S entry, an empty edge list, an ``eig`` other than ``"lds"`` / ``"streamed"`` /
+    ``"auto"``, a problem of more nodes than the cap of ``eig`` (``_lib.gcw_batch_max_n()`` by default; solve it with GCW)."""
+    _check_eig(eig)
     _check_sequence(problems)
     probs, perms = _marshal_problems(problems)
     S = _sorted_s_list(probs, perms, S_list)
     if not probs:
         return []
-    _check_gcw_batch_sizes(probs)
-    outs, timings = _gcw_batch_run(probs, device, s_vec=S)
+    _check_gcw_batch_sizes(probs, eig)
+    outs, timings = _gcw_batch_run(probs, device, eig, s_vec=S)
     return [(R, dict(info, timings=timings)) for R, info in outs] if return_info else [R for R, _ in outs]
 
 
-def DESC_init_batch(problems, params, seeds=None, return_info=False, build="host"):
+def DESC_init_batch(problems, params, seeds=None, return_info=False, build="host", eig="lds"):
     """DESC_init (Algorithms/DESC_init.m: DESC_PGD, then GCW) on B independent small problems: DESC_PGD_batch's pass, then the batched
     eigen-solve on the resulting S_vec -- two GPU passes for the whole batch.  Returns a list of (R_est, S_vec); problem b's S_vec is
     bit for bit what DESC_PGD_batch returns for it.  With ``return_info`` a list of (R_est, S_vec, dict(pgd=..., gcw=...)).
-    ``build`` is DESC_PGD_batch's (``dict["pgd"]["built_where"]`` says which builder ran).
-    Refused (ValueError, before the device is touched): what DESC_PGD_batch refuses, and a problem of more than
-    ``_lib.gcw_batch_max_n()`` nodes (solve it with DESC_init)."""
+    ``build`` is DESC_PGD_batch's (``dict["pgd"]["built_where"]`` says which builder ran); ``eig`` is Spectral_batch's.
+    Refused (ValueError, before the device is touched): what DESC_PGD_batch refuses, an ``eig`` other than ``"lds"`` / ``"streamed"`` /
+    ``"auto"``, and a problem of more nodes than the cap of ``eig`` (``_lib.gcw_batch_max_n()`` by default; solve it with DESC_init)."""
+    _check_eig(eig)
     _check_build(build)
     _check_sequence(problems)
     G = _get(params, "Gradient")
@@ -471,13 +492,13 @@ def DESC_init_batch(problems, params, seeds=None, return_info=False, build="host
         raise ValueError("DESC_init_batch does not support params.make_plots: use DESC_init for the traced run of one problem")
     seeds = _check_seeds(seeds, len(problems))
     probs, perms = _marshal_problems(problems)
-    _check_gcw_batch_sizes(probs)
+    _check_gcw_batch_sizes(probs, eig)
     pgd = DESC_PGD_batch([_Marshalled(q, perm) for q, perm in zip(probs, perms)], params, seeds=seeds, return_info=True, build=build)
     if not probs:
         return []
     # DESC_PGD_batch gave S_vec in the caller's order; the eigen-solve takes the library's
     S_sorted = [d["S_vec"] if perm is None else d["S_vec"][perm] for d, perm in zip(pgd, perms)]
-    outs, timings = _gcw_batch_run(probs, int(_get(params, "device", 0)), s_vec=np.concatenate(S_sorted))
+    outs, timings = _gcw_batch_run(probs, int(_get(params, "device", 0)), eig, s_vec=np.concatenate(S_sorted))
     if return_info:
         return [(R, d["S_vec"], dict(pgd=d, gcw=dict(info, timings=timings))) for (R, info), d in zip(outs, pgd)]
     return [(R, d["S_vec"]) for (R, _), d in zip(outs, pgd)]
@@ -529,17 +550,24 @@ def DESC_refine_batch(problems, S_list, R_init_list, stop_threshold=1e-3, max_it
     return [(R, dict(info, timings=timings)) for R, info in outs] if return_info else [R for R, _ in outs]
 
 
-def DESC_batch(problems, params, seeds=None, return_info=False, build="host"):
+def DESC_batch(problems, params, seeds=None, return_info=False, build="host", eig="lds"):
     """DESC (Algorithms/DESC.m:14: DESC_PGD, then GCW, then the reweighted Lie-algebraic refinement) on B independent small problems:
     DESC_init_batch's two passes, then the batched refinement on their S_vec and R_init -- three GPU passes for the whole batch.
     Returns a list of (R_est, R_init, S_vec); S_vec and R_init are bit for bit DESC_init_batch's.  With ``return_info`` a list of
     (R_est, R_init, S_vec, dict(pgd=..., gcw=..., refine=...)).  The batch prints nothing: ``params.verbose`` is ignored.
-    ``build`` is DESC_PGD_batch's.
-    Refused (ValueError, before the device is touched): what DESC_init_batch refuses."""
+    ``build`` is DESC_PGD_batch's; ``eig`` is Spectral_batch's: with ``"streamed"`` or ``"auto"`` the cap of the call is the
+    refinement's, ``_lib.refine_batch_max_n()`` (748) nodes.
+    Refused (ValueError, before the device is touched): what DESC_init_batch refuses, and with an ``eig`` other than the default a
+    problem of more than ``_lib.refine_batch_max_n()`` nodes (solve it with DESC)."""
+    _check_eig(eig)
     _check_build(build)
     _check_sequence(problems)
     probs, perms = _marshal_problems(problems)
-    init = DESC_init_batch([_Marshalled(q, perm) for q, perm in zip(probs, perms)], params, seeds=seeds, return_info=True, build=build)
+    if eig != "lds":                                 # the default's cap lies below the refinement's: nothing to check there
+        _check_gcw_batch_sizes(probs, eig)
+        _check_refine_batch_sizes(probs)
+    init = DESC_init_batch([_Marshalled(q, perm) for q, perm in zip(probs, perms)], params, seeds=seeds, return_info=True, build=build,
+                           eig=eig)
     if not init:
         return []
     S = np.concatenate([S_vec if perm is None else S_vec[perm] for (_, S_vec, _), perm in zip(init, perms)])
@@ -610,23 +638,25 @@ def CEMP_batch(problems, CEMP_parameters, seeds=None, return_info=False):
     return [(s, dict(timings=timings)) for s in S] if return_info else S
 
 
-def CEMP_GCW_batch(problems, CEMP_parameters, seeds=None, return_info=False):
+def CEMP_GCW_batch(problems, CEMP_parameters, seeds=None, return_info=False, eig="lds"):
     """CEMP_GCW (Algorithms/CEMP_GCW.m) on B independent small problems: CEMP_batch's pass, then the batched eigen-solve with the host
     weights 1/(SVec + 1e-8) and normalised rows (CEMP_GCW.m:144-146) -- two GPU passes for the whole batch.  Returns a list of R_est
     (3 x 3 x n_b); with ``return_info`` a list of (R_est, SVec, dict(cemp=..., gcw=...)), SVec bit for bit CEMP_batch's.
-    Refused (ValueError, before the device is touched): what CEMP_batch refuses, and a problem of more than
-    ``_lib.gcw_batch_max_n()`` nodes (solve it with CEMP_GCW)."""
+    ``eig`` is Spectral_batch's.
+    Refused (ValueError, before the device is touched): what CEMP_batch refuses, an ``eig`` other than ``"lds"`` / ``"streamed"`` /
+    ``"auto"``, and a problem of more nodes than the cap of ``eig`` (``_lib.gcw_batch_max_n()`` by default; solve it with CEMP_GCW)."""
+    _check_eig(eig)
     _check_sequence(problems)
     _cemp_batch_params(CEMP_parameters, len(problems), seeds)
     probs, perms = _marshal_problems(problems)
     if not probs:
         return []
     _check_cemp_batch_degrees(probs)
-    _check_gcw_batch_sizes(probs)
+    _check_gcw_batch_sizes(probs, eig)
     cemp = CEMP_batch([_Marshalled(q, perm) for q, perm in zip(probs, perms)], CEMP_parameters, seeds=seeds, return_info=True)
     # CEMP_batch gave SVec in the caller's order; the eigen-solve takes the library's
     w = np.concatenate([1.0 / ((S if perm is None else S[perm]) + 1e-8) for (S, _), perm in zip(cemp, perms)])      # CEMP_GCW.m:144
-    outs, timings = _gcw_batch_run(probs, int(_get(CEMP_parameters, "device", 0)), weights=w, normalize_rows=True)
+    outs, timings = _gcw_batch_run(probs, int(_get(CEMP_parameters, "device", 0)), eig, weights=w, normalize_rows=True)
     if return_info:
         return [(R, S, dict(cemp=ci, gcw=dict(info, timings=timings))) for (R, info), (S, ci) in zip(outs, cemp)]
     return [R for R, _ in outs]
@@ -796,7 +826,7 @@ def IRLS_L12_batch(problems, SIGMA=5, MaxIterations=(10, 100), device=0, return_
     return _irls_batch(_lib.IRLS_L12, "IRLS_L12_batch", problems, SIGMA, MaxIterations, device, return_info)
 
 
-def linprog_sij_batch(problems, params=None, seeds=None, rotations=True, return_info=False):
+def linprog_sij_batch(problems, params=None, seeds=None, rotations=True, return_info=False, eig="lds"):
     """linprog_sij (Algorithms/linprog_sij.m:16) on B independent small problems: the LP of every problem in one batched PDHG loop
     (desc_lp_batch_*: two launches per step and one 4-byte read-back per check for the whole batch), then the row-normalised weighted
     spectral step with weights exp(-5 S_vec) on the batched eigen-solve and the refinement with maxIters = 200 on the batched
@@ -813,8 +843,11 @@ def linprog_sij_batch(problems, params=None, seeds=None, rotations=True, return_
 
     Refused (ValueError, before the device is touched, naming the problem): not a sequence, an empty edge list, ``nsample < 0``, a
     ``seeds`` or ``nsample`` sequence of the wrong length, a node of more neighbours than ``_lib.cemp_batch_max_degree()`` (the batched
-    sampler's cap; solve it with linprog_sij), a batch whose LP rows reach 2^31 (split the batch), and with ``rotations=True`` a problem
-    of more than ``_lib.gcw_batch_max_n()`` nodes (solve it with linprog_sij, or pass rotations=False for S_vec alone)."""
+    sampler's cap; solve it with linprog_sij), a batch whose LP rows reach 2^31 (split the batch), an ``eig`` other than ``"lds"`` /
+    ``"streamed"`` / ``"auto"``, and with ``rotations=True`` a problem of more than ``_lib.gcw_batch_max_n()`` nodes (solve it with
+    linprog_sij, or pass rotations=False for S_vec alone).  ``eig`` is Spectral_batch's: with ``"streamed"`` or ``"auto"`` the cap of
+    the rotations is the refinement's, ``_lib.refine_batch_max_n()`` (748) nodes."""
+    _check_eig(eig)
     _check_sequence(problems)
     params = {} if params is None else params
     B = len(problems)
@@ -840,11 +873,10 @@ def linprog_sij_batch(problems, params=None, seeds=None, rotations=True, return_
             raise ValueError(str(e).split(": ", 1)[-1]) from None
         raise
     if rotations:
-        cap = _lib.gcw_batch_max_n()
-        for b, q in enumerate(probs):
-            if q.n > cap:
-                raise ValueError(f"problem {b}: n = {q.n} exceeds {cap} (the 3n x 6 blocks of the eigen-solve must fit the LDS of one workgroup): "
-                                 "solve it with linprog_sij, or pass rotations=False for S_vec alone")
+        instead = "linprog_sij, or pass rotations=False for S_vec alone"
+        _check_gcw_batch_sizes(probs, eig, instead)
+        if eig != "lds":                             # the default's cap lies below the refinement's: nothing to check there
+            _check_batch_sizes(probs, _lib.refine_batch_max_n(), "per-node state of the refinement", instead)
     with _batch_handle(_lib.LpBatch, probs, nsample, seeds, device) as batch:
         outs, lp_tm = batch.run(p, want_y=want_y)
         samples = batch.samples() if return_info else None
@@ -860,7 +892,7 @@ def linprog_sij_batch(problems, params=None, seeds=None, rotations=True, return_
     if not rotations:
         return [(S, info) for S, info in zip(S_list, infos)] if return_info else S_list
     S = np.concatenate([S for S, _, _ in outs])                          # the library's edge order, as both later passes take it
-    gcw, gcw_tm = _gcw_batch_run(probs, device, weights=np.exp(-5.0 * S), normalize_rows=True)              # :154-174, beta_T = 5
+    gcw, gcw_tm = _gcw_batch_run(probs, device, eig, weights=np.exp(-5.0 * S), normalize_rows=True)         # :154-174, beta_T = 5
     R0 = np.concatenate([R.reshape(-1, order="F") for R, _ in gcw])
     ref, ref_tm = _refine_batch_run(probs, device, S, R0, 1e-3, 200)                                        # :176-351
     if not return_info:

@@ -27,6 +27,14 @@
 // Composition independence.  Problem b's workgroup reads b's arrays and writes b's ranges; thread roles, loop bounds and summation
 // orders are functions of b's n and CSR alone.  The tail (back-scaling by D^-1/2, unit columns, det sign, per-node projection onto
 // SO(3)) runs per problem on host threads with the arithmetic of spectral.hip's tail (small_dense.h).
+//
+// Streamed blocks (k_gcw_batch<true>, opt-in: desc_gcw_batch_create_where).  Only the source block of a product is ever gathered from
+// (x at adj[t]); y and z are touched at the thread's own elements, and Grams, combinations and residuals are straight row sweeps.  The
+// streamed kernel therefore keeps the four blocks in a per-problem global workspace (72 n doubles at 72 node_off[b], L2-resident at these
+// sizes) and LDS holds ONE staging block of 18 n doubles: a product first copies its source block there, takes a barrier, and gathers
+// from LDS as before.  Operations, orders and reductions are those of the LDS kernel -- the same text on other pointers -- so a problem
+// gets the same bits from either kernel, up to GCW_BATCH_STREAMED_MAX_N nodes.  A launch may cover a subset of the batch (GbArgs::list):
+// with DESC_GCW_EIG_AUTO the problems that fit go to the LDS kernel and the others to the streamed one, two launches on one stream.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -36,6 +44,7 @@
 
 #include "batch_csr.h"
 #include "batch_device.h"
+#include "laa_wg.h"
 #include "small_dense.h"
 
 namespace desc {
@@ -48,7 +57,13 @@ constexpr int GCW_BATCH_MAX_N = (GB_LDS_BYTES / 8 - GB_SCRATCH) / (4 * 3 * BW); 
 static_assert(GCW_BATCH_MAX_N >= 200, "the Monte-Carlo sizes of the README must fit");
 static_assert((4 * 3 * BW * GCW_BATCH_MAX_N + GB_SCRATCH) * 8 <= GB_LDS_BYTES, "LDS budget");
 
+constexpr int GCW_BATCH_STREAMED_MAX_N = (GB_LDS_BYTES / 8 - GB_SCRATCH) / (3 * BW);      // 1112: one staging block in LDS
+static_assert((3 * BW * GCW_BATCH_STREAMED_MAX_N + GB_SCRATCH) * 8 <= GB_LDS_BYTES, "LDS budget");
+static_assert(GCW_BATCH_STREAMED_MAX_N >= REFINE_BATCH_MAX_N, "the streamed eigen-solve must start every problem the refinement takes");
+
 inline size_t gb_lds_bytes(int n) { return sizeof(double) * ((size_t)4 * 3 * BW * (size_t)n + GB_SCRATCH); }
+
+inline size_t gb_streamed_lds_bytes(int n) { return sizeof(double) * ((size_t)3 * BW * (size_t)n + GB_SCRATCH); }
 
 struct GbProb { int32_t n, m; int64_t node_off, edge_off; };
 struct GbInfo { int32_t iters, products, converged, status; double residual, eig[3]; };       // status: 1 degenerate start basis, 2 breakdown
@@ -66,14 +81,26 @@ struct GbArgs {
     double* blocks;             // 18 m_b at 18 edge_off[b]: slot t of the problem at 9 t
     double* V;                  // 9 n_b at 9 node_off[b]: the three Ritz vectors, (3n x 3) row-major
     GbInfo* info;
+    double* work;               // streamed kernel: X, Y, P, Q of problem b, 18 n_b doubles each, at 72 node_off[b]; else NULL
+    const int32_t* list;        // the problems of this launch, one per workgroup; NULL: blockIdx.x is the problem
     double tol;
     int32_t normalize, max_iters;
 };
 
 // y[v] = alpha * sum_t blocks[t] * x[adj[t]] + s1 * x[v] + s2 * z[v]; x, y, z: (3n x BW) row-major in LDS, x != y (z may alias y: a
 // thread reads exactly the elements it writes).  Thread (v, c) owns column c of node row v.  Ends with a barrier.
+// STREAM: x, y, z are in global memory; x is first copied into the staging block `stage` (LDS, 18 n doubles; consecutive lanes take
+// consecutive 16-byte pairs, every range being 16-byte aligned) and read from there.  The closing barrier also keeps the next product's
+// copy off a staging block that is still being gathered from.
+template <bool STREAM>
 __device__ __forceinline__ void gb_spmm(const int32_t* rowptr, const int32_t* adj, const double* blocks, const double* x, const double* z, double* y,
-                                        int n, double alpha, double s1, double s2) {
+                                        double* stage, int n, double alpha, double s1, double s2) {
+    if (STREAM) {
+        const double2* src = reinterpret_cast<const double2*>(x);
+        for (int i = threadIdx.x; i < 3 * (BW / 2) * n; i += 256) { const double2 d = src[i]; stage[2 * i] = d.x; stage[2 * i + 1] = d.y; }
+        __syncthreads();
+        x = stage;
+    }
     for (int i = threadIdx.x; i < BW * n; i += 256) {
         const int v = i / BW, c = i - v * BW;
         double acc[3] = {0.0, 0.0, 0.0};
@@ -181,9 +208,10 @@ __device__ __forceinline__ double gb_residual(const double* X, const double* Y, 
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+template <bool STREAM>
 __global__ __launch_bounds__(256, 2) void k_gcw_batch(GbArgs a) {
     extern __shared__ double gb_lds[];
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int b = a.list ? a.list[blockIdx.x] : (int)blockIdx.x, tid = threadIdx.x;
     const GbProb pd = a.prob[b];
     const int n = pd.n, m = pd.m, rows = 3 * n;
     const int32_t* rowptr = a.rowptr + pd.node_off + b;
@@ -193,11 +221,13 @@ __global__ __launch_bounds__(256, 2) void k_gcw_batch(GbArgs a) {
     double* blocks = a.blocks + 18 * pd.edge_off;
     double* dinv = a.dinv + pd.node_off;
     // LDS: four blocks of 18 n doubles, then G1[36] G2[36] Z[36] C[36] theta[6] red[288] ctl[10] = GB_SCRATCH
-    double* X = gb_lds;
+    // STREAM: the four blocks in the problem's workspace; LDS: the staging block of 18 n doubles, then the same small matrices
+    double* X = STREAM ? a.work + 4 * 3 * BW * pd.node_off : gb_lds;
     double* Y = X + 3 * BW * n;
     double* P = Y + 3 * BW * n;
     double* Q = P + 3 * BW * n;
-    double* G1 = Q + 3 * BW * n;
+    double* stage = STREAM ? gb_lds : nullptr;
+    double* G1 = STREAM ? gb_lds + 3 * BW * n : Q + 3 * BW * n;
     double* G2 = G1 + BW * BW;
     double* Z = G2 + BW * BW;
     double* Cm = Z + BW * BW;
@@ -270,7 +300,7 @@ __global__ __launch_bounds__(256, 2) void k_gcw_batch(GbArgs a) {
         double lo = -sigma, cut = 0.0;
         for (it = 1; it <= max_iters; ++it) {
             // ---- Rayleigh-Ritz on the current orthonormal basis X
-            gb_spmm(rowptr, adj, blocks, X, X, Y, n, 1.0, 0.0, 0.0); ++products;             // Y = A X
+            gb_spmm<STREAM>(rowptr, adj, blocks, X, X, Y, stage, n, 1.0, 0.0, 0.0); ++products;             // Y = A X
             gb_gram<true>(X, Y, rows, G1, G2, red);                                           // G1 = X'AX, G2 = Y'Y
             if (tid == 0) jacobi_eig<BW>(G1, theta, Z);
             __syncthreads();
@@ -298,12 +328,12 @@ __global__ __launch_bounds__(256, 2) void k_gcw_batch(GbArgs a) {
             res_prev = res;
             double s_prev = e / (top - c);
             const double s1c = s_prev;
-            gb_spmm(rowptr, adj, blocks, X, X, P, n, s_prev / e, -c * s_prev / e, 0.0); ++products;   // P = (A X - c X) * s_prev / e
+            gb_spmm<STREAM>(rowptr, adj, blocks, X, X, P, stage, n, s_prev / e, -c * s_prev / e, 0.0); ++products;   // P = (A X - c X) * s_prev / e
             double *Xp = X, *Pp = P, *Qp = Q;                                                 // X_{k-1}, X_k, scratch
             for (int k = 2; k <= cheb_deg; ++k) {
                 const double s_new = 1.0 / (2.0 / s1c - s_prev);
                 // Q = (2 s_new / e) (A P - c P) - (s_prev s_new) X_{k-1}
-                gb_spmm(rowptr, adj, blocks, Pp, Xp, Qp, n, 2.0 * s_new / e, -2.0 * s_new * c / e, -s_prev * s_new); ++products;
+                gb_spmm<STREAM>(rowptr, adj, blocks, Pp, Xp, Qp, stage, n, 2.0 * s_new / e, -2.0 * s_new * c / e, -s_prev * s_new); ++products;
                 double* t3 = Xp; Xp = Pp; Pp = Qp; Qp = t3;
                 s_prev = s_new;
             }
@@ -321,7 +351,7 @@ __global__ __launch_bounds__(256, 2) void k_gcw_batch(GbArgs a) {
             // Z belongs to the basis in X in both exits (the loop leaves right after a Rayleigh-Ritz, or after max_iters with the last
             // Ritz rotation still unapplied: redo RR once)
             if (!converged && it > max_iters) {
-                gb_spmm(rowptr, adj, blocks, X, X, Y, n, 1.0, 0.0, 0.0); ++products;
+                gb_spmm<STREAM>(rowptr, adj, blocks, X, X, Y, stage, n, 1.0, 0.0, 0.0); ++products;
                 gb_gram<true>(X, Y, rows, G1, G2, red);
                 if (tid == 0) jacobi_eig<BW>(G1, theta, Z);
                 __syncthreads();
@@ -382,23 +412,44 @@ struct desc_gcw_batch : desc::BatchCsr, desc::BatchDevice {     // offsets and t
     int32_t *d_rowptr = nullptr, *d_adj = nullptr, *d_adj_eid = nullptr;
     double *d_rij = nullptr, *d_in = nullptr, *d_w = nullptr, *d_dinv = nullptr, *d_blocks = nullptr, *d_V = nullptr;
     GbInfo* d_info = nullptr;
+    // which kernel solves which problem (a function of the problem's own n and the mode alone); the lists are uploaded only where both run
+    int32_t eig = DESC_GCW_EIG_LDS;
+    std::vector<int32_t> lds_list, streamed_list;
+    int32_t max_n_lds = 0, max_n_streamed = 0;
+    int32_t *d_lds_list = nullptr, *d_streamed_list = nullptr;
+    double* d_work = nullptr;
 };
 
 namespace {
 
-// validation, offsets and the per-problem CSR: no device
-int gb_host_part(const desc_problem* probs, int32_t count, desc_gcw_batch* h) {
-    return batch_csr_host(probs, count, [](int32_t b, const desc_problem& q) -> int {
-        if (q.n > GCW_BATCH_MAX_N)
+// validation, offsets and the per-problem CSR, the split of the batch between the two kernels: no device
+int gb_host_part(const desc_problem* probs, int32_t count, int32_t eig, desc_gcw_batch* h) {
+    if (eig != DESC_GCW_EIG_LDS && eig != DESC_GCW_EIG_STREAMED && eig != DESC_GCW_EIG_AUTO)
+        return fail(DESC_ERR_INVALID, "eig = %d is none of DESC_GCW_EIG_LDS (0), DESC_GCW_EIG_STREAMED (1), DESC_GCW_EIG_AUTO (2)", eig);
+    h->eig = eig;
+    int rc = batch_csr_host(probs, count, [eig](int32_t b, const desc_problem& q) -> int {
+        if (eig == DESC_GCW_EIG_LDS && q.n > GCW_BATCH_MAX_N)
             return fail(DESC_ERR_INVALID, "problem %d: n = %lld exceeds %d (the 3n x 6 blocks of the eigen-solve must fit the LDS of one workgroup): solve it with GCW / DESC_init",
                         b, (long long)q.n, GCW_BATCH_MAX_N);
+        if (q.n > GCW_BATCH_STREAMED_MAX_N)
+            return fail(DESC_ERR_INVALID, "problem %d: n = %lld exceeds %d (one 3n x 6 block of the streamed eigen-solve must fit the LDS of one workgroup): solve it with GCW / DESC_init",
+                        b, (long long)q.n, GCW_BATCH_STREAMED_MAX_N);
         return DESC_OK;
     }, h);
+    if (rc) return rc;
+    for (int32_t b = 0; b < count; ++b) {
+        const int32_t n = (int32_t)probs[b].n;
+        const bool streamed = eig == DESC_GCW_EIG_STREAMED || (eig == DESC_GCW_EIG_AUTO && n > GCW_BATCH_MAX_N);
+        (streamed ? h->streamed_list : h->lds_list).push_back(b);
+        int32_t& mx = streamed ? h->max_n_streamed : h->max_n_lds;
+        mx = std::max(mx, n);
+    }
+    return DESC_OK;
 }
 
-int gb_create(const desc_problem* probs, int32_t count, int32_t device, desc_gcw_batch* h) {
+int gb_create(const desc_problem* probs, int32_t count, int32_t device, int32_t eig, desc_gcw_batch* h) {
     auto t0 = std::chrono::steady_clock::now();
-    int rc = gb_host_part(probs, count, h);
+    int rc = gb_host_part(probs, count, eig, h);
     if (rc) return rc;
     h->ms_structure = ms_since(t0);
     if (count == 0) return DESC_OK;
@@ -416,6 +467,12 @@ int gb_create(const desc_problem* probs, int32_t count, int32_t device, desc_gcw
     if ((rc = h->upload(&h->d_rij, rij.data(), 9 * M))) return rc;
     if ((rc = h->mem.alloc(&h->d_in, M)) || (rc = h->mem.alloc(&h->d_w, M)) || (rc = h->mem.alloc(&h->d_dinv, N)) ||
         (rc = h->mem.alloc(&h->d_blocks, 18 * M)) || (rc = h->mem.alloc(&h->d_V, 9 * N)) || (rc = h->mem.alloc(&h->d_info, (size_t)count))) return rc;
+    if (!h->streamed_list.empty()) {
+        if ((rc = h->mem.alloc(&h->d_work, 4 * 3 * BW * N))) return rc;
+        if (!h->lds_list.empty() &&
+            ((rc = h->upload(&h->d_lds_list, h->lds_list.data(), h->lds_list.size())) ||
+             (rc = h->upload(&h->d_streamed_list, h->streamed_list.data(), h->streamed_list.size())))) return rc;
+    }
     DESC_HIP(hipStreamSynchronize(h->stream));         // the staging vectors go out of scope below
     h->ms_upload = ms_since(t1);
     return DESC_OK;
@@ -446,12 +503,25 @@ int gb_run(desc_gcw_batch* h, const double* s_vec, const double* weights, int32_
     a.s_vec = s_vec ? h->d_in : nullptr; a.wts_in = weights ? h->d_in : nullptr;
     a.w = h->d_w; a.dinv = h->d_dinv; a.blocks = h->d_blocks; a.V = h->d_V; a.info = h->d_info;
     a.tol = tol; a.normalize = (s_vec || normalize_rows) ? 1 : 0; a.max_iters = max_iters;
-    const size_t lds = gb_lds_bytes(h->max_n);
-    if (lds > (size_t)GB_LDS_BYTES) return fail(DESC_ERR_STATE, "LDS budget exceeded (%zu bytes)", lds);
-    if (lds > 64 * 1024) DESC_HIP(hipFuncSetAttribute((const void*)k_gcw_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    a.work = h->d_work;
+    // at most two launches, each sized from the largest problem it solves; one kernel for the whole batch needs no list
+    const size_t n_lds = h->lds_list.size(), n_streamed = h->streamed_list.size();
+    const size_t lds = n_lds ? gb_lds_bytes(h->max_n_lds) : 0, lds_streamed = n_streamed ? gb_streamed_lds_bytes(h->max_n_streamed) : 0;
+    if (std::max(lds, lds_streamed) > (size_t)GB_LDS_BYTES) return fail(DESC_ERR_STATE, "LDS budget exceeded (%zu bytes)", std::max(lds, lds_streamed));
+    if (lds > 64 * 1024) DESC_HIP(hipFuncSetAttribute((const void*)k_gcw_batch<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds_streamed > 64 * 1024)
+        DESC_HIP(hipFuncSetAttribute((const void*)k_gcw_batch<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_streamed));
     if ((rc = h->timer_begin())) return rc;
-    hipLaunchKernelGGL(k_gcw_batch, dim3((unsigned)count), dim3(256), lds, h->stream, a);
-    DESC_HIP(hipGetLastError());
+    if (n_lds) {
+        a.list = n_streamed ? h->d_lds_list : nullptr;
+        hipLaunchKernelGGL(k_gcw_batch<false>, dim3((unsigned)n_lds), dim3(256), lds, h->stream, a);
+        DESC_HIP(hipGetLastError());
+    }
+    if (n_streamed) {
+        a.list = n_lds ? h->d_streamed_list : nullptr;
+        hipLaunchKernelGGL(k_gcw_batch<true>, dim3((unsigned)n_streamed), dim3(256), lds_streamed, h->stream, a);
+        DESC_HIP(hipGetLastError());
+    }
     if ((rc = h->timer_end())) return rc;
     hvec<GbInfo> inf((size_t)count);
     hvec<double> V(9 * N), dinv(N);
@@ -474,10 +544,12 @@ int gb_run(desc_gcw_batch* h, const double* s_vec, const double* weights, int32_
         project_nodes(Vb, 0, n, R_out + 9 * (size_t)no);
     });
     const double ms_project = ms_since(t1), ms_total = ms_since(t0);
+    for (int32_t b : h->streamed_list) infos[b].reserved = 1;
+    for (int32_t b : h->lds_list) infos[b].reserved = 0;
     for (int32_t b = 0; b < count; ++b) {
         const GbInfo& g = inf[(size_t)b];
         desc_spectral_info& o = infos[b];
-        o.iters = g.iters; o.products = g.products; o.converged = g.converged; o.reserved = 0; o.residual = g.residual;
+        o.iters = g.iters; o.products = g.products; o.converged = g.converged; o.residual = g.residual;
         for (int c = 0; c < 3; ++c) o.eigenvalues[c] = g.eig[c];
         o.ms_total = ms_total;
     }
@@ -491,8 +563,16 @@ extern "C" {
 
 int32_t desc_gcw_batch_max_n(void) { return GCW_BATCH_MAX_N; }
 
+int32_t desc_gcw_batch_streamed_max_n(void) { return GCW_BATCH_STREAMED_MAX_N; }
+
 int desc_gcw_batch_create(const desc_problem* probs, int32_t count, int32_t device, desc_gcw_batch** out) {
-    return batch_create_guarded("desc_gcw_batch_create", out, probs, count, [&](desc_gcw_batch* h) { return gb_create(probs, count, device, h); });
+    return batch_create_guarded("desc_gcw_batch_create", out, probs, count,
+                                [&](desc_gcw_batch* h) { return gb_create(probs, count, device, DESC_GCW_EIG_LDS, h); });
+}
+
+int desc_gcw_batch_create_where(const desc_problem* probs, int32_t count, int32_t device, int32_t eig, desc_gcw_batch** out) {
+    return batch_create_guarded("desc_gcw_batch_create_where", out, probs, count,
+                                [&](desc_gcw_batch* h) { return gb_create(probs, count, device, eig, h); });
 }
 
 int desc_gcw_batch_sizes(const desc_gcw_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off) {
@@ -504,7 +584,7 @@ int desc_gcw_batch_csr(const desc_problem* probs, int32_t count, int64_t* node_o
     return no_throw("desc_gcw_batch_csr", [&]() -> int {
         if (count < 0 || (count > 0 && !probs) || !node_off || !edge_off) return fail(DESC_ERR_INVALID, "NULL argument or negative count");
         desc_gcw_batch h;
-        int rc = gb_host_part(probs, count, &h);
+        int rc = gb_host_part(probs, count, DESC_GCW_EIG_LDS, &h);
         if (rc) return rc;
         batch_sizes(h, nullptr, node_off, edge_off);
         if (rowptr) std::copy(h.rowptr.begin(), h.rowptr.end(), rowptr);

@@ -3,7 +3,7 @@
 of Uniform_Topology(100, 0.5, q, 0.1) -- the shape of the figures the DESC paper draws (error against q on graphs of 100-200 nodes).
 
     python examples/monte_carlo.py [--trials 5] [--n 100] [--iters 100] [--build host|device] [--rotations] [--refined] [--baselines]
-                                   [--mpls] [--lp] [--irls] [--device-models]
+                                   [--mpls] [--lp] [--irls] [--device-models] [--eig lds|streamed|auto]
 
 --device-models: the trials are drawn on the GPU by one Uniform_Topology_batch call instead of one Uniform_Topology call per trial on the
 host.  The batched generator has streams of its own: the curves differ from an unflagged run in their draws, not in their distribution.
@@ -11,6 +11,11 @@ The time the generation took is printed in both modes.
 
 --build: the builder of the cycle structures behind DESC_PGD_batch / DESC_init_batch / DESC_batch: per problem on host threads (the
 default) or for the whole batch on the device; the curves are the same to the last bit.
+
+--eig: where the batched eigen-solve behind --rotations, --refined, --baselines (CEMP+GCW) and --lp keeps its blocks.  The default
+"lds" takes problems of up to 278 nodes; "auto" solves larger ones with the streamed kernel, so that e.g. --n 400 --refined runs
+(DESC_batch and the LP row then take up to 748 nodes, the refinement's cap).  The curves of a size both kernels take are the same to
+the last bit.
 
 --rotations: the demo's own metric next to it -- one DESC_init_batch call (the PGD pass, then the batched GCW eigen-solve) and the mean
 rotation error in degrees (Rotation_Alignment against the ground truth), the column of Demo/compare_algorithms.m.
@@ -59,13 +64,13 @@ def score(curves, models, shape):
     return [np.array([t[2] for t in out[k * B:(k + 1) * B]]).reshape(shape) for k in range(len(curves))], ms
 
 
-def baselines(models, qs, trials):
+def baselines(models, qs, trials, eig):
     """One call per curve: CEMP_batch, CEMP_GCW_batch, CEMP_MST_batch."""
     cemp = dict(max_iter=6, reweighting=[2.0 ** k for k in range(6)], nsample=50, seed=0)
     t0 = time.perf_counter()
     S = CEMP_batch(models, cemp)
     t1 = time.perf_counter()
-    R_gcw = CEMP_GCW_batch(models, cemp)
+    R_gcw = CEMP_GCW_batch(models, cemp, eig=eig)
     t2 = time.perf_counter()
     R_mst = CEMP_MST_batch(models, cemp)
     t3 = time.perf_counter()
@@ -97,10 +102,10 @@ def mpls_curve(models, qs, trials):
         print(f" {q:4.2f}   {re.mean():8.4f}                       ({re.min():.4f} .. {re.max():.4f})      {ri.mean():8.4f}                          {ni.min()} .. {ni.max()}")
 
 
-def lp_curve(models, qs, trials):
+def lp_curve(models, qs, trials, eig):
     """One linprog_sij_batch call: the LP relaxation of the problem DESC solves as a QP."""
     t0 = time.perf_counter()
-    out = linprog_sij_batch(models, dict(seed=0), return_info=True)
+    out = linprog_sij_batch(models, dict(seed=0), return_info=True, eig=eig)
     ms = (time.perf_counter() - t0) * 1e3
     shape = (len(qs), trials)
     err = np.array([np.abs(s - mo.ErrVec).mean() for (_, s, _), mo in zip(out, models)]).reshape(shape)
@@ -146,6 +151,8 @@ def main():
     ap.add_argument("--lp", action="store_true", help="the linprog_sij curve: one linprog_sij_batch call")
     ap.add_argument("--irls", action="store_true", help="the IRLS-GM and IRLS-L0.5 curves: one IRLS_GM_batch and one IRLS_L12_batch call")
     ap.add_argument("--device-models", action="store_true", help="draw the trials on the GPU: one Uniform_Topology_batch call")
+    ap.add_argument("--eig", choices=("lds", "streamed", "auto"), default="lds",
+                    help="the batched eigen-solve's blocks: in LDS (up to 278 nodes), streamed through LDS, or by each problem's size")
     a = ap.parse_args()
     qs = [0.0, 0.1, 0.2, 0.3, 0.4, 0.5]
     t0 = time.perf_counter()
@@ -159,7 +166,7 @@ def main():
     params = dict(iters=a.iters, Gradient=ConstantStepSize(0.01), seed=0, verbose=False)
     if a.refined:
         t0 = time.perf_counter()
-        out = DESC_batch(models, params, build=a.build)
+        out = DESC_batch(models, params, build=a.build, eig=a.eig)
         ms = (time.perf_counter() - t0) * 1e3
         shape = (len(qs), a.trials)
         err = np.array([np.abs(s - mo.ErrVec).mean() for (_, _, s), mo in zip(out, models)]).reshape(shape)
@@ -170,17 +177,17 @@ def main():
         for q, row, re, ri in zip(qs, err, est, ini):
             print(f" {q:4.2f}   {row.mean():.4f}                {re.mean():8.4f}                       ({re.min():.4f} .. {re.max():.4f})      {ri.mean():8.4f}")
         if a.baselines:
-            baselines(models, qs, a.trials)
+            baselines(models, qs, a.trials, a.eig)
         if a.mpls:
             mpls_curve(models, qs, a.trials)
         if a.lp:
-            lp_curve(models, qs, a.trials)
+            lp_curve(models, qs, a.trials, a.eig)
         if a.irls:
             irls_curves(models, qs, a.trials)
         return
     t0 = time.perf_counter()
     if a.rotations:
-        out = DESC_init_batch(models, params, build=a.build)
+        out = DESC_init_batch(models, params, build=a.build, eig=a.eig)
         S = [s for _, s in out]
     else:
         S = DESC_PGD_batch(models, params, build=a.build)
@@ -195,11 +202,11 @@ def main():
             print(f" {q:4.2f}   {row.mean():.4f}                ({row.min():.4f} .. {row.max():.4f})      {rr.mean():8.4f}"
                   f"                      ({rr.min():.4f} .. {rr.max():.4f})")
         if a.baselines:
-            baselines(models, qs, a.trials)
+            baselines(models, qs, a.trials, a.eig)
         if a.mpls:
             mpls_curve(models, qs, a.trials)
         if a.lp:
-            lp_curve(models, qs, a.trials)
+            lp_curve(models, qs, a.trials, a.eig)
         if a.irls:
             irls_curves(models, qs, a.trials)
         return
@@ -207,11 +214,11 @@ def main():
     for q, row in zip(qs, err):
         print(f" {q:4.2f}   {row.mean():.4f}                ({row.min():.4f} .. {row.max():.4f})")
     if a.baselines:
-        baselines(models, qs, a.trials)
+        baselines(models, qs, a.trials, a.eig)
     if a.mpls:
         mpls_curve(models, qs, a.trials)
     if a.lp:
-        lp_curve(models, qs, a.trials)
+        lp_curve(models, qs, a.trials, a.eig)
     if a.irls:
         irls_curves(models, qs, a.trials)
 

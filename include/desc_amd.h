@@ -329,7 +329,7 @@ typedef struct desc_spectral_info {
     int32_t iters;            /* outer (filter + Rayleigh-Ritz) steps              */
     int32_t products;         /* block matrix products (3n x 6 each)               */
     int32_t converged;        /* residual <= tol reached                           */
-    int32_t reserved;
+    int32_t reserved;         /* desc_gcw_batch_run: the kernel that solved the problem (DESC_GCW_EIG_LDS or _STREAMED); else 0 */
     double  residual;         /* max relative residual of the three Ritz pairs     */
     double  eigenvalues[3];   /* the three largest eigenvalues                     */
     double  ms_total;
@@ -610,6 +610,14 @@ int desc_pgd_batch_concat(const desc_structure* const* s, int32_t count, int64_t
  * desc_gcw_batch_create: validates every problem and refuses -- before any device work, naming the problem -- an empty edge list and
  * n > desc_gcw_batch_max_n() (DESC_ERR_INVALID: solve it with GCW / DESC_init); builds the per-problem CSR (local ids) and uploads
  * rotations and indices in one copy each.  count == 0 is legal.  The handle may be run any number of times.
+ * desc_gcw_batch_create_where: create with a choice of where the four blocks live.  DESC_GCW_EIG_LDS is desc_gcw_batch_create.
+ * DESC_GCW_EIG_STREAMED solves every problem with the streamed kernel: the blocks in a per-problem global workspace (72 n doubles,
+ * allocated only where a problem streams), one staging block in LDS for the source of the current product; the cap is
+ * desc_gcw_batch_streamed_max_n() (1112).  DESC_GCW_EIG_AUTO gives a problem of n <= desc_gcw_batch_max_n() to the LDS kernel and a
+ * larger one to the streamed kernel -- by its own n alone, at most two launches on the handle's stream, both inside ms_eig.  The
+ * arithmetic is the same text in the same order: a problem gets the same bits from either kernel.  Refused before any device work
+ * (DESC_ERR_INVALID): an eig that is none of the three, and n above the cap of the mode, naming the problem.  infos[b].reserved of
+ * desc_gcw_batch_run says which kernel solved problem b.
  * desc_gcw_batch_sizes: node_off[count+1], edge_off[count+1] (each nullable).
  * desc_gcw_batch_csr: the host part of create alone (no device): rowptr (problem b's n_b + 1 entries at node_off[b] + b), adj and adj_eid
  * (its 2 m_b entries at 2 edge_off[b]; local node / edge ids); the three arrays are nullable (offsets only, to size them).
@@ -626,8 +634,13 @@ typedef struct desc_gcw_batch_timings {
     double ms_project;        /* the tail on host threads                                           */
     double ms_total;          /* wall clock of desc_gcw_batch_run                                   */
 } desc_gcw_batch_timings;     /* 40 bytes */
+#define DESC_GCW_EIG_LDS       0
+#define DESC_GCW_EIG_STREAMED  1
+#define DESC_GCW_EIG_AUTO      2
 int32_t desc_gcw_batch_max_n(void);
+int32_t desc_gcw_batch_streamed_max_n(void);
 int desc_gcw_batch_create(const desc_problem* probs, int32_t count, int32_t device, desc_gcw_batch** out);
+int desc_gcw_batch_create_where(const desc_problem* probs, int32_t count, int32_t device, int32_t eig, desc_gcw_batch** out);
 int desc_gcw_batch_sizes(const desc_gcw_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off);
 int desc_gcw_batch_csr(const desc_problem* probs, int32_t count, int64_t* node_off, int64_t* edge_off, int32_t* rowptr, int32_t* adj,
                        int32_t* adj_eid);
