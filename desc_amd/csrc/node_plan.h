@@ -14,6 +14,7 @@ constexpr int CHUNK_CAP = CHUNK_LDS - 4;   // cycles per chunk: the image starts
 constexpr int MAX_SEG_CYCLES = 256;        // longest segment the node layout takes (64 lanes x 4 cycles)
 constexpr int BAND_ROW_CAP = 19200;        // doubles of LDS for the band rows (150 KiB of the CU's 160 KiB)
 constexpr int MAX_TAIL_PIECES = 768;       // shared tail of the band sweep: at most this many queued pieces (their partials: SHARD_PARTS - grid)
+constexpr int SHARD_PARTS = 1024;           // >= band grid + tail pieces (MAX_TAIL_PIECES)
 struct alignas(16) PieceDesc { int32_t row_lo, row_len, seg_lo, seg_hi; };   // CSR slots of the band, device-order segments
 
 inline int env_int(const char* name, int dflt) {

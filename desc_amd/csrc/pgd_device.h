@@ -1,5 +1,6 @@
-// Device-side text that more than one kernel unit of the PGD solver needs (pgd.hip, sweep_gather.hip, sweep_node.hip, sweep_band.hip):
-// plain structs and __device__ __forceinline__ helpers only -- every __global__ kernel lives in exactly one .hip.
+// Device-side text that more than one kernel unit of the PGD solver needs (pgd.hip, pgd_layout.hip, pgd_shard.hip, pgd_ext.hip,
+// sweep_gather.hip, sweep_node.hip, sweep_band.hip): plain structs and __device__ __forceinline__ helpers only -- every __global__ kernel lives
+// in exactly one .hip.
 #pragma once
 
 #include "device_utils.h"
@@ -104,5 +105,84 @@ struct NodeSweepArgs {
     uint32_t seg_count;        // segments in cum / einfo / xt (device order, all ranks): cum has seg_count + 1 entries
     double fx_inv;             // 2^-fx_bits: Tfull holds fixed-point integers (fx_to_double)
 };
+
+
+// Sum the block partials in a fixed order, record the traces and run the early-stop
+// rule of DESC_PGD.m:243-256 for the iteration whose objective just became known.
+// t = 1-based index of the sweep that produced the partials.  Called by one full wave.
+struct FinArgs {
+    const double* partials; DevState* st; double* obj_trace; double* avg_trace;
+    int64_t m; double stop_tol; int32_t nparts, t, patience, last_only;      // t == 0: nothing to do
+    int64_t rank_stride; int32_t nranks;     // sharded runs: the partials of rank r start at partials + r * rank_stride (0 / 0: one rank)
+};
+// The sum of the workgroup partials is defined over 256 VIRTUAL lanes: virtual lane v adds the (rank, index) pairs v, v + 256, ... in that order, the
+// 64 virtual lanes of a quarter are combined by the fixed DPP butterfly and the four quarters are added in index order.  A 256-thread block
+// (finalize_block: the bookkeeping workgroup of the column-sum and unpack launches) gives a quarter to each of its waves; a single wave
+// (finalize_wave: k_finalize) walks the four quarters one after the other -- the SAME bits either way, and the same on every rank.  Eight pairs are
+// loaded before any is added (one at a time the 8 x 1024 pairs of a world-8 run were 128 dependent round trips for one wave: ~50 of the 85 us of
+// k_unpack_S, profiles/r04_shard_w8_c4_rocprof.txt -- 35 us in the launches that book-keep nothing).
+__device__ __forceinline__ void finalize_quarter(const FinArgs& f, int quarter, int lane, double& o, double& ch) {
+    o = 0.0; ch = 0.0;
+    const int E = max(f.nranks, 1) * f.nparts;
+    for (int base = 64 * quarter + lane; base < E; base += 256 * 8) {
+        double vo[8], vc[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int idx = base + 256 * u;
+            vo[u] = 0.0; vc[u] = 0.0;
+            if (idx < E) {
+                const double* q = f.partials + (int64_t)(idx / f.nparts) * f.rank_stride + 2 * (int64_t)(idx % f.nparts);
+                vo[u] = q[0]; vc[u] = q[1];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { o += vo[u]; ch += vc[u]; }
+    }
+    o = group_sum<64>(o); ch = group_sum<64>(ch);
+}
+__device__ __forceinline__ void finalize_book(const FinArgs& f, double o, double ch);
+// called by all 256 threads of a block
+__device__ __forceinline__ void finalize_block(const FinArgs f) {
+    __shared__ double s_fin[4][2];
+    if (f.t <= 0 || f.st->stop) return;          // t == 0: no sweep to book-keep (uniform over the block)
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double o, ch;
+    finalize_quarter(f, wv, lane, o, ch);
+    if (lane == 0) { s_fin[wv][0] = o; s_fin[wv][1] = ch; }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        finalize_book(f, ((s_fin[0][0] + s_fin[1][0]) + s_fin[2][0]) + s_fin[3][0], ((s_fin[0][1] + s_fin[1][1]) + s_fin[2][1]) + s_fin[3][1]);
+}
+// called by one full wave
+__device__ __forceinline__ void finalize_wave(const FinArgs f) {
+    if (f.t <= 0 || f.st->stop) return;
+    const int lane = threadIdx.x & 63;
+    double q0[4], q1[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) finalize_quarter(f, w, lane, q0[w], q1[w]);
+    if (lane == 0) finalize_book(f, ((q0[0] + q0[1]) + q0[2]) + q0[3], ((q1[0] + q1[1]) + q1[2]) + q1[3]);
+}
+// traces and the stop rule of DESC_PGD.m:232-257 for the iteration whose sums just became known (one thread)
+__device__ __forceinline__ void finalize_book(const FinArgs& f, double o, double ch) {
+    DevState* st = f.st;
+    // last_only: the partials come from the objective kernel after the final sweep t and
+    // hold obj(t).  Otherwise they come from sweep t: obj(t-1) and sum|dS| of sweep t.
+    const int t = f.t;
+    const int it = f.last_only ? t : t - 1;          // iteration whose objective is o
+    if (!f.last_only) f.avg_trace[t - 1] = ch / (double)f.m;                            // :232
+    if (it >= 1) {
+        f.obj_trace[it - 1] = o;                                                        // :233
+        if (it <= st->last_tested) return;          // already tested (objective evaluated early by a download)
+        st->last_tested = it;
+        if (it > 1 && f.obj_trace[it - 2] - f.obj_trace[it - 1] < f.stop_tol) {         // :243
+            st->misses += 1;
+            if (st->misses >= f.patience) {                                             // :245-246
+                st->stop = 1; st->iters_run = it; st->final_parity = it & 1;
+            }
+        } else {
+            st->misses = 0;                                                             // :255
+        }
+    }
+}
 
 }  // namespace desc

@@ -1,5 +1,5 @@
-// The PGD solver handle (struct desc_pgd), its allocation helpers, the sweep-instance types and the host functions of the sweep units
-// (sweep_gather.hip, sweep_node.hip, sweep_band.hip) that pgd.hip calls.
+// The PGD solver handle (struct desc_pgd), its allocation helpers, the sweep-instance types and the host functions that cross the units of
+// the solver: the sweep units (sweep_gather.hip, sweep_node.hip, sweep_band.hip), pgd.hip, pgd_layout.hip, pgd_shard.hip and pgd_ext.hip.
 #pragma once
 
 #include <cstdlib>
@@ -7,8 +7,6 @@
 
 #include "node_plan.h"
 #include "pgd_device.h"
-
-using namespace desc;
 
 // ------------------------------------------------------------------- handle --
 enum { VARIANT_GATHER = 1, VARIANT_NODE = 2 };
@@ -34,7 +32,7 @@ struct desc_pgd {
     int small_grid = 0;
     int band_grid = 0, band_rows = 0;
     size_t band_lds = 0;
-    PieceDesc* d_pieces = nullptr;
+    desc::PieceDesc* d_pieces = nullptr;
     int32_t* d_piece_ptr = nullptr;
     unsigned long long* d_wg_clock = nullptr;   // diagnostics: DESC_DEBUG_WGCLOCK
     int band_tail_first = 0, band_ntail = 0;    // shared tail of the band sweep (BandSweepArgs)
@@ -48,17 +46,17 @@ struct desc_pgd {
     double *d_S0 = nullptr, *d_w[2] = {nullptr, nullptr}, *d_S[2] = {nullptr, nullptr};
     double *d_adam_m[2] = {nullptr, nullptr}, *d_adam_v[2] = {nullptr, nullptr}, *d_nv = nullptr, *d_partials = nullptr;
     double *d_obj = nullptr, *d_avg = nullptr, *d_scratch = nullptr;
-    DevState* d_state = nullptr;
+    desc::DevState* d_state = nullptr;
     // gather variant
     int32_t *d_pos_edge = nullptr, *d_ejk = nullptr, *d_eki = nullptr, *d_ikj = nullptr, *d_jki = nullptr;
     // node variant
-    EdgeInfo* d_einfo = nullptr;
+    desc::EdgeInfo* d_einfo = nullptr;
     uint32_t* d_pk = nullptr;
     uint32_t* d_moff = nullptr;  // per CSR slot: start of its run in d_midx
     uint16_t* d_midx = nullptr;  // column index of every contributing cycle, in the order the column-sum pass reads them
     int2* d_adj_seg = nullptr;   // per CSR slot: slot_record() = {first contributing cycle of the incident segment, their number | (row node is the smaller endpoint) << 31}
     int32_t *d_rowptr = nullptr, *d_src_start = nullptr, *d_eslot = nullptr;
-    ChunkDesc* d_chunk_desc = nullptr;
+    desc::ChunkDesc* d_chunk_desc = nullptr;
     int nchunks = 0;
     double *d_T = nullptr, *d_Svec = nullptr;
     uint8_t* d_seg_perm = nullptr;     // natural in-segment offset of every device-order cycle
@@ -72,7 +70,7 @@ struct desc_pgd {
     desc_collectives coll{};            // fused protocol: the caller's collectives (RCCL entry points + communicator)
     hipStream_t comm_stream = nullptr;  // second stream: exchange + unpack overlap the next column-sum pass
     hipEvent_t ev_col = nullptr, ev_rs = nullptr, ev_sw = nullptr, ev_ag = nullptr;
-    StepArgs cur_step{}; bool cur_adam = false;      // sharded sweeps: the step of the sweep in progress (its exchange parts are separate launches)
+    desc::StepArgs cur_step{}; bool cur_adam = false;      // sharded sweeps: the step of the sweep in progress (its exchange parts are separate launches)
     int unpack_pending = 0;             // fused protocol: sweep whose all-gathered S still has to be unpacked (on the compute stream, behind ev_ag)
     bool own_xbuf = false, force_coll = false;
     hvec<int64_t> rank_seg;      // world+1 segment boundaries
@@ -182,7 +180,7 @@ struct BandSweepArgs;
 int launch_gather(desc_pgd* h, const SweepArgs& a, bool adam);
 int setup_gather(desc_pgd* h, const desc_problem* prob, const desc_structure* s, const double* shared_rij);
 // sweep_node.hip
-extern const SweepInst<NodeSweepArgs> NODE_INSTS[5];
+const SweepInst<NodeSweepArgs>* node_inst_of(SweepShape sh);
 SweepShape node_shape(int c);
 std::string node_prefix(SweepShape sh);
 SweepShape small_shape(int c);
@@ -195,5 +193,22 @@ SweepShape band_shape(const desc_pgd* h, bool adam);
 const SweepInst<BandSweepArgs>* band_inst_of(const desc_pgd* h, bool adam);
 std::string band_prefix(SweepShape sh);
 int launch_band(desc_pgd* h, const NodeSweepArgs& a, bool adam, int part);      // for launch_sweep_node_layout (sweep_node.hip)
+
+// -------------------------------------------------------- the other PGD units --
+// pgd.hip
+StepArgs make_step(desc_pgd* h, bool* adam, int rd, int wr);
+size_t parts_cap(const desc_pgd* h);
+double* obj_partials(const desc_pgd* h);
+FinArgs fin_args(const desc_pgd* h, const double* partials, int nparts, int t, int last_only);
+NodeSweepArgs node_sweep_args(const desc_pgd* h, int rd, int wr);
+void launch_objective(desc_pgd* h, hipStream_t st, int par, int grid, double* partials);
+void launch_unpack(desc_pgd* h, hipStream_t st, int g, double* S_a, double* S_b, const FinArgs& f);
+constexpr int COLSUM_SHORT = 128;         // sharded runs: rows whose owned run has at most this many segments are summed by ONE wave (four nodes per workgroup)
+int prepare_colsum(desc_pgd* h);
+void launch_colsum(desc_pgd* h, hipStream_t st, const double* w, double* T, const int32_t* xpos, const FinArgs& fin);
+// pgd_layout.hip
+int setup_node(desc_pgd* h, const desc_problem* prob, const desc_structure* s, const double* shared_rij);
+// pgd_shard.hip
+int shard_unpack_pending(desc_pgd* h);
 
 }  // namespace desc

@@ -316,6 +316,7 @@ const SweepInst<NodeSweepArgs, int> SMALL_INSTS[] = {small_inst<16>(), small_ins
 }  // namespace
 
 const SweepInst<NodeSweepArgs> NODE_INSTS[] = {node_inst<16, 1>(), node_inst<16, 2>(), node_inst<32, 2>(), node_inst<32, 4>(), node_inst<64, 4>()};
+const SweepInst<NodeSweepArgs>* node_inst_of(SweepShape sh) { return sweep_inst(NODE_INSTS, sh); }      // for setup_node's occupancy query (pgd_layout.hip)
 SweepShape node_shape(int c) { return {c <= 32 ? 16 : c <= 128 ? 32 : 64, c <= 16 ? 1 : c <= 64 ? 2 : 4}; }      // 16 x 1, 16 x 2, 32 x 2, 32 x 4 or 64 x 4: each has its entry
 std::string node_prefix(SweepShape sh) { return inst_name("k_sweep_node<%d,%d,", sh.lps, sh.E); }
 SweepShape small_shape(int c) { return {c <= 16 ? 16 : c <= 32 ? 32 : 64, 0}; }      // 16, 32 or 64: each has its entry

@@ -3,7 +3,7 @@ tests/test_exact_data_host.py): rotations without noise, where the cycle cosine 
 Every other GPU test keeps it strictly inside, so two of the three branches of abs_acos_ext (acosh beyond 1, hypot(pi, acosh) beyond
 -1), the ends of acos, weights tied in whole groups, S exactly 0 or 1 and an objective of exactly 0 are met only here.
 
-(a) S0 at every call site -- the PGD layouts (sweep_gather.hip: k_cycle_d; pgd.hip: k_layout_node and both instances of
+(a) S0 at every call site -- the PGD layouts (sweep_gather.hip: k_cycle_d; pgd_layout.hip: k_layout_node and both instances of
     k_layout_node_dev), batch.hip, cemp.hip (staged and not), cemp_batch.hip, models_batch.hip -- against s0_enclosure: exactly 0, or
     within 2^-52 of 1, on the four-group data; inside the interval that any correctly rounded evaluation in any summation order falls
     into on the clean and half-turn data.

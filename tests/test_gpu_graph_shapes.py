@@ -296,7 +296,7 @@ def _pgd_reference(oracle, name):
 @pytest.mark.parametrize("variant", ["1", "2", "3"])
 @pytest.mark.parametrize("name", shapes_for("pgd"))
 def test_sweep_layouts_on_a_long_row(lib, oracle, name, variant, monkeypatch):
-    """pgd.hip setup_node (band_ok), node_plan.cpp: one row far longer than the rest through the gather, node and band layouts on one rank."""
+    """pgd_layout.hip setup_node (band_ok), node_plan.cpp: one row far longer than the rest through the gather, node and band layouts on one rank."""
     monkeypatch.setenv("DESC_DEBUG_VARIANT", variant)
     nn, ii, jj, rij, st, S0, ref = _pgd_reference(oracle, name)
     prob = lib.ProblemArrays(nn, ii, jj, rij)

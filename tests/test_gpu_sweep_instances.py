@@ -152,7 +152,7 @@ def _instances():
     and XT)."""
     csrc = os.path.join(ROOT, "desc_amd", "csrc")
     units = sorted(nm for nm in os.listdir(csrc) if nm.endswith((".hip", ".cpp", ".h")))          # every unit of the library
-    assert {"pgd.hip", "pgd_handle.h", "sweep_gather.hip", "sweep_node.hip", "sweep_band.hip"} <= set(units)
+    assert {"pgd.hip", "pgd_layout.hip", "pgd_shard.hip", "pgd_ext.hip", "pgd_handle.h", "sweep_gather.hip", "sweep_node.hip", "sweep_band.hip"} <= set(units)
     code = []
     for nm in units:
         with open(os.path.join(csrc, nm)) as f:

@@ -170,8 +170,8 @@ SIDES = {
     "long_row": ("laa.hip:88", lambda f, K: f["max_deg"] >= 16 * 4 and f["max_deg"] >= 8 * np.median(f["deg"])),
     "uniform_narrow_rows": ("laa.hip:88", lambda f, K: f["max_deg"] <= 2 * 16 and f["max_deg"] <= 2 * f["min_deg"]),
     "largest_component_without_node_1": ("irls.hip", lambda f, K: not f["connected"]),
-    # pgd.hip setup_node (band_ok), node_plan.cpp: band rows up to BAND_ROW_CAP doubles
-    "one_row_far_longer": ("pgd.hip setup_node", lambda f, K: 20 * np.median(f["deg"]) <= f["max_deg"] <= K["BAND_ROW_CAP"]),
+    # pgd_layout.hip setup_node (band_ok), node_plan.cpp: band rows up to BAND_ROW_CAP doubles
+    "one_row_far_longer": ("pgd_layout.hip setup_node", lambda f, K: 20 * np.median(f["deg"]) <= f["max_deg"] <= K["BAND_ROW_CAP"]),
 }
 
 

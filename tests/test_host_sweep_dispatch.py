@@ -1,4 +1,4 @@
-"""The sweep dispatch of the PGD solver (sweep_gather.hip, sweep_node.hip, sweep_band.hip, pgd.hip) on the host side, without a GPU: the library built against the mock HIP runtime (tests/hipmock; kernels
+"""The sweep dispatch of the PGD solver (sweep_gather.hip, sweep_node.hip, sweep_band.hip, pgd.hip, pgd_layout.hip) on the host side, without a GPU: the library built against the mock HIP runtime (tests/hipmock; kernels
 do not run).  For every entry of the instance table of tests/test_gpu_sweep_instances.py the handle is created as the GPU case creates
 it, two iterations are enqueued, and the instance the dispatch chose (desc_debug_last_sweep) and the prefix the handle reports
 (desc_pgd_kernel_name) are compared with the table.  The GPU cases confirm the numbers; this confirms the choice."""
