@@ -49,6 +49,10 @@ EXPORTS = [
     "desc_models_key", "desc_models_batch_max_n", "desc_models_batch_create", "desc_models_batch_sizes", "desc_models_batch_fetch",
     "desc_models_batch_destroy", "desc_test_models_uniform", "desc_test_models_normal",
     "desc_align_batch_create", "desc_align_batch_sizes", "desc_align_batch_run", "desc_align_batch_destroy", "desc_test_align_project",
+    "desc_problem_batch_create", "desc_problem_batch_from_models", "desc_problem_batch_sizes", "desc_problem_batch_fetch",
+    "desc_problem_batch_built_where", "desc_problem_batch_bytes", "desc_problem_batch_destroy",
+    "desc_gcw_batch_create_on", "desc_refine_batch_create_on", "desc_pgd_batch_create_on",
+    "desc_gcw_batch_bytes", "desc_refine_batch_bytes", "desc_pgd_batch_bytes",
     "desc_test_laa_r2q", "desc_test_laa_q2r", "desc_test_laa_edge_log", "desc_test_laa_rhs", "desc_test_laa_pcg", "desc_test_laa_node_update",
     "desc_test_irls_node_update", "desc_test_laa_weights", "desc_test_irls_weights", "desc_test_laa_quantile", "desc_test_irls_project",
     "desc_test_irls_pd_stage", "desc_test_irls_pd_solve",
@@ -413,6 +417,19 @@ def load():
     L.desc_align_batch_destroy.argtypes = [C.c_void_p]
     L.desc_align_batch_destroy.restype = None
     L.desc_test_align_project.argtypes = [F64P, C.c_int64, C.c_int32, F64P]
+    L.desc_problem_batch_create.argtypes = [C.POINTER(Problem), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.desc_problem_batch_from_models.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.desc_problem_batch_sizes.argtypes = [C.c_void_p, I32P, I64P, I64P]
+    L.desc_problem_batch_fetch.argtypes = [C.c_void_p, I32P, I32P, F64P, I32P, I32P, I32P]
+    L.desc_problem_batch_built_where.argtypes = [C.c_void_p]
+    L.desc_problem_batch_built_where.restype = C.c_int32
+    L.desc_problem_batch_destroy.argtypes = [C.c_void_p]
+    L.desc_problem_batch_destroy.restype = None
+    L.desc_gcw_batch_create_on.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
+    L.desc_refine_batch_create_on.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.desc_pgd_batch_create_on.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_void_p)]
+    for kind in ("problem", "gcw", "refine", "pgd"):
+        getattr(L, f"desc_{kind}_batch_bytes").argtypes = [C.c_void_p, I64P, I64P]
     L.desc_test_laa_r2q.argtypes = [F64P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, F64P]
     L.desc_test_laa_q2r.argtypes = [F64P, C.c_int64, C.c_int32, F64P]
     L.desc_test_laa_edge_log.argtypes = [C.c_void_p, F64P, F64P, C.c_int64, F64P]
@@ -635,6 +652,23 @@ class _BatchHandle:
         self.handle = h
         self._read_sizes(B)
 
+    def _open_on(self, pset, *create_args):
+        """As _open on a resident ProblemBatch: desc_<_kind>_batch_create_on; the handle keeps the set's device arrays alive."""
+        if not pset.handle:
+            raise ValueError("the ProblemBatch is closed")
+        self.probs = pset.probs                      # the set's host mirror (endpoints; rotations only where they are on the host)
+        self.count = B = len(pset)
+        h = C.c_void_p()
+        check(self._export("create_on")(pset.handle, *create_args, C.byref(h)))
+        self.handle = h
+        self._read_sizes(B)
+
+    def bytes(self):
+        """(h2d, d2h): the bytes the handle's device half copied up through its create and down (desc_<_kind>_batch_bytes)."""
+        up, down = C.c_int64(), C.c_int64()
+        check(self._export("bytes")(self.handle, C.byref(up), C.byref(down)))
+        return int(up.value), int(down.value)
+
     def _read_sizes(self, B):
         no, eo = np.zeros(B + 1, dtype=np.int64), np.zeros(B + 1, dtype=np.int64)
         check(self._export("sizes")(self.handle, None, ptr(no, I64P), ptr(eo, I64P)))
@@ -663,9 +697,12 @@ class Batch(_BatchHandle):
     _create = "create_where"
     BUILD_LAPS = ("codeg", "plan", "compact", "sample", "mirror")
 
-    def __init__(self, probs, params: Params, seeds=None, where=BUILD_HOST):
-        probs = list(probs)
-        self._open(probs, C.byref(params), _seeds_array(seeds, len(probs)), int(where))
+    def __init__(self, probs, params: Params, seeds=None, where=BUILD_HOST, on=None):
+        if on is not None:                           # a resident ProblemBatch: probs is not read
+            self._open_on(on, C.byref(params), _seeds_array(seeds, len(on)), int(where))
+        else:
+            probs = list(probs)
+            self._open(probs, C.byref(params), _seeds_array(seeds, len(probs)), int(where))
         self.built_where = int(self._export("built_where")(self.handle))
 
     def build_laps(self):
@@ -767,8 +804,11 @@ class GcwBatch(_BatchHandle):
     _kind = "gcw"
     _create = "create_where"
 
-    def __init__(self, probs, device=0, eig="lds"):
-        self._open(probs, int(device), gcw_eig_mode(eig))
+    def __init__(self, probs, device=0, eig="lds", on=None):
+        if on is not None:                           # a resident ProblemBatch: probs and device are not read
+            self._open_on(on, gcw_eig_mode(eig))
+        else:
+            self._open(probs, int(device), gcw_eig_mode(eig))
 
     def run(self, s_vec=None, weights=None, normalize_rows=False, tol=1e-13, max_iters=500):
         """One batched eigen-solve.  s_vec: the concatenated S_vec (GCW mode); weights: concatenated host weights; neither: Spectral.
@@ -904,8 +944,11 @@ class RefineBatch(_BatchHandle):
 
     _kind = "refine"
 
-    def __init__(self, probs, device=0):
-        self._open(probs, int(device))
+    def __init__(self, probs, device=0, on=None):
+        if on is not None:                           # a resident ProblemBatch: probs and device are not read
+            self._open_on(on)
+        else:
+            self._open(probs, int(device))
 
     def run(self, s_vec, R_init, stop_threshold=1e-3, max_iters=100):
         """One batched refinement.  s_vec: the concatenated S_vec (library's edge order); R_init: the concatenated 9 n_b doubles per
@@ -1087,6 +1130,7 @@ class ModelsBatch(_BatchHandle):
     _kind = "models"
 
     def __init__(self, specs, device=0):
+        self.device = int(device)
         self.specs = list(specs)
         self.count = B = len(self.specs)
         arr = (ModelSpec * max(B, 1))(*self.specs)
@@ -1100,17 +1144,19 @@ class ModelsBatch(_BatchHandle):
         self.edge_off = np.concatenate([[0], np.cumsum(self.m_per, dtype=np.int64)]).astype(np.int64)
         self.n, self.m = int(self.node_off[B]), int(self.edge_off[B])
 
-    def fetch(self):
+    FIELDS = ("ind_i", "ind_j", "rij", "rij_orig", "r_orig", "err_vec", "corrupted")
+
+    def fetch(self, only=None):
         """The node, selection and edge passes and the copy-back: a dict of the concatenated arrays ind_i / ind_j (int32, 0-based), rij /
-        rij_orig (9 m), r_orig (9 n), err_vec (m), corrupted (m, uint8) -- and the call's timings."""
+        rij_orig (9 m), r_orig (9 n), err_vec (m), corrupted (m, uint8) -- and the call's timings.  ``only``: the names to copy back
+        (default: all of them)."""
         N, M = self.n, self.m
-        out = dict(ind_i=out_buffer(M, np.int32), ind_j=out_buffer(M, np.int32), rij=out_buffer(9 * M), rij_orig=out_buffer(9 * M),
-                   r_orig=out_buffer(9 * N), err_vec=out_buffer(M), corrupted=out_buffer(M, np.uint8))
-        tm = ModelsBatchTimings()
-        check(load().desc_models_batch_fetch(self.handle, ptr(out["ind_i"], I32P), ptr(out["ind_j"], I32P), ptr(out["rij"], F64P),
-                                             ptr(out["rij_orig"], F64P), ptr(out["r_orig"], F64P), ptr(out["err_vec"], F64P),
-                                             ptr(out["corrupted"], C.POINTER(C.c_uint8)), C.byref(tm)))
         sizes = dict(ind_i=M, ind_j=M, rij=9 * M, rij_orig=9 * M, r_orig=9 * N, err_vec=M, corrupted=M)
+        types = dict(ind_i=(np.int32, I32P), ind_j=(np.int32, I32P), corrupted=(np.uint8, C.POINTER(C.c_uint8)))
+        names = self.FIELDS if only is None else [k for k in self.FIELDS if k in only]
+        out = {k: out_buffer(sizes[k], types.get(k, (np.float64,))[0]) for k in names}
+        tm = ModelsBatchTimings()
+        check(load().desc_models_batch_fetch(self.handle, *[ptr(out.get(k), types.get(k, (None, F64P))[1]) for k in self.FIELDS], C.byref(tm)))
         return {k: v[:sizes[k]] for k, v in out.items()}, _timings(tm)
 
 
@@ -1166,6 +1212,76 @@ def hook_align_project(A, device=0):
     out = out_buffer(A.size)
     check(load().desc_test_align_project(ptr(A if A.size else np.zeros(9), F64P), A.shape[0], int(device), ptr(out, F64P)))
     return out[:A.size].reshape(-1, 9)
+
+
+CSR_WHERE = {"host": BUILD_HOST, "device": BUILD_DEVICE}
+
+
+class ProblemBatch(_BatchHandle):
+    """Owner of a desc_problem_batch*: the problems of B instances validated, laid out and uploaded once (desc_problem_batch_*), for
+    every batched handle created ``on=`` it.  ``probs`` is a sequence of ProblemArrays (kept: the host mirror); ``csr``: ``"host"`` or
+    ``"device"``, the builder of the per-problem CSR.  ``ProblemBatch.from_models(models_handle)`` takes a generator's problems on the
+    device; its mirror holds the endpoints, and the rotations once ``host_problems()`` has fetched them.  ``close()`` drops this
+    reference: handles created on the set keep its device arrays alive."""
+
+    _kind = "problem"
+
+    def __init__(self, probs, device=0, csr="host"):
+        if not isinstance(csr, str) or csr not in CSR_WHERE:
+            raise ValueError(f"csr must be 'host' or 'device', not {csr!r}")
+        self.device = int(device)
+        self._has_rij = True
+        self._open(probs, self.device, CSR_WHERE[csr])
+        self.built_where = int(self._export("built_where")(self.handle))
+
+    @classmethod
+    def from_models(cls, models: "ModelsBatch"):
+        self = cls.__new__(cls)
+        h = C.c_void_p()
+        check(load().desc_problem_batch_from_models(models.handle, C.byref(h)))
+        self.handle, self.device, self.count = h, int(models.device), models.count
+        self._read_sizes(self.count)
+        ii, jj = out_buffer(self.m, np.int32), out_buffer(self.m, np.int32)
+        check(load().desc_problem_batch_fetch(self.handle, ptr(ii, I32P), ptr(jj, I32P), None, None, None, None))     # the host mirror: no copy
+        self.probs = [ProblemArrays(int(self.node_off[b + 1] - self.node_off[b]), ii[self.edge_off[b]:self.edge_off[b + 1]],
+                                    jj[self.edge_off[b]:self.edge_off[b + 1]]) for b in range(self.count)]
+        self._has_rij = self.count == 0
+        self.built_where = int(self._export("built_where")(self.handle))
+        return self
+
+    def __len__(self):
+        return self.count
+
+    def fetch(self, rij=False, csr=False):
+        """The set's arrays through desc_problem_batch_fetch: dict(ind_i, ind_j[, rij][, rowptr, adj, adj_eid]), batch-long."""
+        if not self.handle:
+            raise ValueError("the ProblemBatch is closed")
+        sizes = dict(ind_i=self.m, ind_j=self.m)
+        if rij:
+            sizes["rij"] = 9 * self.m
+        if csr:
+            sizes.update(rowptr=self.n + self.count, adj=2 * self.m, adj_eid=2 * self.m)
+        out = {k: out_buffer(n, np.float64 if k == "rij" else np.int32) for k, n in sizes.items()}
+        check(load().desc_problem_batch_fetch(self.handle, *[ptr(out.get(k), F64P if k == "rij" else I32P)
+                                                             for k in ("ind_i", "ind_j", "rij", "rowptr", "adj", "adj_eid")]))
+        return {k: v[:sizes[k]] for k, v in out.items()}
+
+    def host_problems(self):
+        """The host mirror with rotations (a list of ProblemArrays); a generated set fetches them once, here."""
+        if not self._has_rij:
+            rij = self.fetch(rij=True)["rij"]
+            self.probs = [ProblemArrays(q.n, q.ind_i, q.ind_j, rij[9 * int(self.edge_off[b]):9 * int(self.edge_off[b + 1])])
+                          for b, q in enumerate(self.probs)]
+            self._has_rij = True
+        return self.probs
+
+    close = _BatchHandle.destroy
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def gcw_batch_csr(probs):

@@ -20,6 +20,7 @@ over the same ABI are in matlab/.
 """
 from __future__ import annotations
 
+import collections.abc
 import contextlib
 import ctypes as C
 
@@ -261,8 +262,12 @@ class _Marshalled:
         self.prob, self.perm = prob, perm
 
 
-def _marshal_problems(problems):
-    """The problems of a batch call -> (list of ProblemArrays, list of edge permutations); ValueError names the problem."""
+def _marshal_problems(problems, rotations=True):
+    """The problems of a batch call -> (list of ProblemArrays, list of edge permutations); ValueError names the problem.  A ProblemBatch
+    was marshalled when it was made: its host mirror comes back, with the rotations (one fetch for a generated set) unless
+    ``rotations`` is False."""
+    if isinstance(problems, ProblemBatch):
+        return (problems._host_problems() if rotations else problems._index_problems()), problems.perms
     probs, perms = [], []
     for b, item in enumerate(problems):
         if isinstance(item, _Marshalled):
@@ -286,6 +291,149 @@ def _marshal_problems(problems):
     return probs, perms
 
 
+class _SetItem:
+    """Item b of a ProblemBatch made from (Ind, RijMat) pairs."""
+
+    def __init__(self, Ind, RijMat):
+        self.Ind, self.RijMat = Ind, RijMat
+
+
+class _ResidentModel:
+    """Item b of a generated ProblemBatch: a model whose small fields are on the host and whose RijMat / Rij_orig / AdjMat are fetched
+    from the device on first access."""
+
+    def __init__(self, owner, b, **small):
+        self._owner, self._b = owner, b
+        self.__dict__.update(small)
+
+    def _blocks(self, flat):
+        e0, e1 = self._owner._edge_range(self._b)
+        return flat[9 * e0:9 * e1].reshape((3, 3, e1 - e0), order="F")
+
+    @property
+    def RijMat(self):
+        return self._owner._host_problems()[self._b].rij.reshape((3, 3, -1), order="F")
+
+    @property
+    def Rij_orig(self):
+        return self._blocks(self._owner._rij_orig())
+
+    @property
+    def AdjMat(self):
+        A = np.zeros((self.n, self.n))
+        A[self.Ind[:, 0] - 1, self.Ind[:, 1] - 1] = 1
+        return A + A.T
+
+
+class ProblemBatch(collections.abc.Sequence):
+    """The problems of a study, validated, laid out and uploaded to the GPU once (desc_problem_batch_*): every ``*_batch`` call takes a
+    ProblemBatch where it takes a list of problems, and gives the same bits.  Spectral_batch, GCW_batch, DESC_refine_batch,
+    DESC_PGD_batch, DESC_init_batch and DESC_batch create their handles ON the set -- no marshalling, no validation, no CSR build and no
+    72-byte-per-edge upload per call; the other families read the set's host mirror and save the marshalling.
+
+    ``problems`` as for DESC_PGD_batch; ``device`` the GPU the set lives on (a call whose ``device`` / ``params.device`` differs is
+    refused); ``csr``: ``"host"`` builds the per-problem CSR on host threads, ``"device"`` builds the same arrays in one launch.
+    A Sequence of B items with ``.Ind`` / ``.RijMat``; ``perms`` holds the edge permutations of the marshalling.  ``close()`` (or the
+    end of a ``with`` block) drops the set; handles that are still running on it keep its device arrays alive.
+    ``Uniform_Topology_batch(..., resident=True)`` returns a set drawn on the device; its items are models.
+
+    Refused (ValueError): what a ``*_batch`` call refuses of its problems, a ``csr`` other than the two, a negative ``device``."""
+
+    def __init__(self, problems, device=0, csr="host"):
+        _check_sequence(problems)
+        if not isinstance(csr, str) or csr not in _lib.CSR_WHERE:
+            raise ValueError(f"csr must be 'host' or 'device', not {csr!r}")
+        if not isinstance(device, (int, np.integer)) or isinstance(device, bool) or device < 0:
+            raise ValueError("device must be a non-negative integer")
+        probs, self.perms = _marshal_problems(problems)
+        self._items = [it if hasattr(it, "Ind") and hasattr(it, "RijMat") else _SetItem(*it) for it in problems]
+        self.device, self._gen, self._orig = int(device), None, None
+        with _invalid_as_value_error():
+            self._set = _lib.ProblemBatch(probs, self.device, csr)
+
+    @classmethod
+    def _from_models(cls, specs, device):
+        """The set of a generator call (models._draw_batch): no rotation reaches the host.  Returns (set, the generator's timings)."""
+        self = cls.__new__(cls)
+        self.device, self._orig = int(device), None
+        gen = _lib.ModelsBatch(specs, device=self.device)
+        try:
+            small, timings = gen.fetch(only=("r_orig", "err_vec", "corrupted"))
+            with _invalid_as_value_error():
+                self._set = _lib.ProblemBatch.from_models(gen)
+        except Exception:
+            gen.destroy()
+            raise
+        self._gen = gen                              # Rij_orig stays with the generator until somebody asks
+        self.perms = [None] * len(specs)
+        self._items = []
+        for b, (s, q) in enumerate(zip(specs, self._set.probs)):
+            e0, e1 = self._edge_range(b)
+            v0, v1 = int(gen.node_off[b]), int(gen.node_off[b + 1])
+            self._items.append(_ResidentModel(self, b, n=int(s.n), seed=int(s.seed),
+                                              Ind=np.stack([q.ind_i.astype(np.int64) + 1, q.ind_j.astype(np.int64) + 1], axis=1),
+                                              ErrVec=small["err_vec"][e0:e1], corrupted=small["corrupted"][e0:e1].astype(bool),
+                                              R_orig=small["r_orig"][9 * v0:9 * v1].reshape((3, 3, int(s.n)), order="F")))
+        return self, timings
+
+    def __len__(self):
+        return len(self._items)
+
+    def __getitem__(self, b):
+        return self._items[b]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def closed(self):
+        return not self._set.handle
+
+    @property
+    def built_where(self):
+        """``"host"`` or ``"device"``: the builder of the set's CSR."""
+        return "device" if self._set.built_where == _lib.BUILD_DEVICE else "host"
+
+    def bytes(self):
+        """(bytes copied to the device, bytes copied back) by the set so far."""
+        return self._set.bytes()
+
+    def close(self):
+        self._set.close()
+        if self._gen is not None:
+            self._gen.destroy()
+
+    def _edge_range(self, b):
+        return int(self._set.edge_off[b]), int(self._set.edge_off[b + 1])
+
+    def _index_problems(self):
+        return self._set.probs
+
+    def _host_problems(self):
+        return self._set.host_problems()
+
+    def _rij_orig(self):
+        if self._orig is None:
+            if not self._gen.handle:
+                raise ValueError("the ProblemBatch is closed")
+            self._orig = self._gen.fetch(only=("rij_orig",))[0]["rij_orig"]
+        return self._orig
+
+
+def _resident(problems, device):
+    """The _lib.ProblemBatch behind ``problems`` if that is a ProblemBatch, else None; the call's device must be the set's."""
+    if not isinstance(problems, ProblemBatch):
+        return None
+    if int(device) != problems.device:
+        raise ValueError(f"device = {int(device)} differs from the device of the ProblemBatch ({problems.device})")
+    if problems.closed:
+        raise ValueError("the ProblemBatch is closed")
+    return problems._set
+
+
 @contextlib.contextmanager
 def _invalid_as_value_error():
     """A refusal of the library (DESC_ERR_INVALID) leaves the block as ValueError, without the entry point's name in front."""
@@ -298,11 +446,11 @@ def _invalid_as_value_error():
 
 
 @contextlib.contextmanager
-def _batch_handle(cls, *args):
-    """``cls(*args)``, one of _lib's batched handles, for the length of a with block: what create refuses is a ValueError, and the
-    handle is destroyed however the block ends."""
+def _batch_handle(cls, *args, **kw):
+    """``cls(*args, **kw)``, one of _lib's batched handles, for the length of a with block: what create refuses is a ValueError, and
+    the handle is destroyed however the block ends."""
     with _invalid_as_value_error():
-        batch = cls(*args)
+        batch = cls(*args, **kw)
     try:
         yield batch
     finally:
@@ -329,7 +477,7 @@ def _check_seeds(seeds, B):
     return seeds
 
 
-def DESC_PGD_batch(problems, params, seeds=None, return_info=False, build="host"):
+def DESC_PGD_batch(problems, params, seeds=None, return_info=False, build="host", _set=None):
     """DESC_PGD on B independent problems in one GPU pass (desc_pgd_batch_*; the reference has no such call).
 
     ``problems`` is a sequence of ``(Ind, RijMat)`` pairs or of model objects with ``.Ind`` / ``.RijMat``; ``params`` as for DESC_PGD,
@@ -359,10 +507,11 @@ def DESC_PGD_batch(problems, params, seeds=None, return_info=False, build="host"
     seeds = _check_seeds(seeds, B)
     p, G = make_c_params(params)
     p.verbose = 0
+    pset = _set if _set is not None else _resident(problems, p.device)
     if B == 0:
         return []
-    probs, perms = _marshal_problems(problems)
-    with _batch_handle(_lib.Batch, probs, p, seeds, where) as batch:
+    probs, perms = _marshal_problems(problems, rotations=pset is None)
+    with _batch_handle(_lib.Batch, probs, p, seeds, where, on=pset) as batch:
         built_where = "device" if batch.built_where == _lib.BUILD_DEVICE else "host"
         hybrid = isinstance(G, HybridGradient) and G.strategy == 0
         adam = (np.zeros(max(batch.m_cycle, 1)), np.zeros(max(batch.m_cycle, 1))) if hybrid else None
@@ -430,8 +579,8 @@ def _sorted_s_list(probs, perms, S_list, noun="S_vec", ok=lambda S: np.isfinite(
     return np.concatenate(parts) if parts else np.zeros(0)
 
 
-def _gcw_batch_run(probs, device, eig="lds", **run_args):
-    with _batch_handle(_lib.GcwBatch, probs, device, eig) as batch:
+def _gcw_batch_run(probs, device, eig="lds", pset=None, **run_args):
+    with _batch_handle(_lib.GcwBatch, probs, device, eig, on=pset) as batch:
         return batch.run(**run_args)
 
 
@@ -449,11 +598,12 @@ def Spectral_batch(problems, device=0, return_info=False, eig="lds"):
     it with Spectral)."""
     _check_eig(eig)
     _check_sequence(problems)
-    probs, perms = _marshal_problems(problems)
+    pset = _resident(problems, device)
+    probs, perms = _marshal_problems(problems, rotations=pset is None)
     if not probs:
         return []
     _check_gcw_batch_sizes(probs, eig)
-    outs, timings = _gcw_batch_run(probs, device, eig, normalize_rows=False)
+    outs, timings = _gcw_batch_run(probs, device, eig, pset, normalize_rows=False)
     return [(R, dict(info, timings=timings)) for R, info in outs] if return_info else [R for R, _ in outs]
 
 
@@ -465,16 +615,17 @@ def GCW_batch(problems, S_list, device=0, return_info=False, eig="lds"):
     ``"auto"``, a problem of more nodes than the cap of ``eig`` (``_lib.gcw_batch_max_n()`` by default; solve it with GCW)."""
     _check_eig(eig)
     _check_sequence(problems)
-    probs, perms = _marshal_problems(problems)
+    pset = _resident(problems, device)
+    probs, perms = _marshal_problems(problems, rotations=pset is None)
     S = _sorted_s_list(probs, perms, S_list)
     if not probs:
         return []
     _check_gcw_batch_sizes(probs, eig)
-    outs, timings = _gcw_batch_run(probs, device, eig, s_vec=S)
+    outs, timings = _gcw_batch_run(probs, device, eig, pset, s_vec=S)
     return [(R, dict(info, timings=timings)) for R, info in outs] if return_info else [R for R, _ in outs]
 
 
-def DESC_init_batch(problems, params, seeds=None, return_info=False, build="host", eig="lds"):
+def DESC_init_batch(problems, params, seeds=None, return_info=False, build="host", eig="lds", _set=None):
     """DESC_init (Algorithms/DESC_init.m: DESC_PGD, then GCW) on B independent small problems: DESC_PGD_batch's pass, then the batched
     eigen-solve on the resulting S_vec -- two GPU passes for the whole batch.  Returns a list of (R_est, S_vec); problem b's S_vec is
     bit for bit what DESC_PGD_batch returns for it.  With ``return_info`` a list of (R_est, S_vec, dict(pgd=..., gcw=...)).
@@ -491,14 +642,16 @@ def DESC_init_batch(problems, params, seeds=None, return_info=False, build="host
     if bool(_get(params, "make_plots", False)):
         raise ValueError("DESC_init_batch does not support params.make_plots: use DESC_init for the traced run of one problem")
     seeds = _check_seeds(seeds, len(problems))
-    probs, perms = _marshal_problems(problems)
+    pset = _set if _set is not None else _resident(problems, _get(params, "device", 0))
+    probs, perms = _marshal_problems(problems, rotations=pset is None)
     _check_gcw_batch_sizes(probs, eig)
-    pgd = DESC_PGD_batch([_Marshalled(q, perm) for q, perm in zip(probs, perms)], params, seeds=seeds, return_info=True, build=build)
+    pgd = DESC_PGD_batch([_Marshalled(q, perm) for q, perm in zip(probs, perms)], params, seeds=seeds, return_info=True, build=build,
+                         _set=pset)
     if not probs:
         return []
     # DESC_PGD_batch gave S_vec in the caller's order; the eigen-solve takes the library's
     S_sorted = [d["S_vec"] if perm is None else d["S_vec"][perm] for d, perm in zip(pgd, perms)]
-    outs, timings = _gcw_batch_run(probs, int(_get(params, "device", 0)), eig, s_vec=np.concatenate(S_sorted))
+    outs, timings = _gcw_batch_run(probs, int(_get(params, "device", 0)), eig, pset, s_vec=np.concatenate(S_sorted))
     if return_info:
         return [(R, d["S_vec"], dict(pgd=d, gcw=dict(info, timings=timings))) for (R, info), d in zip(outs, pgd)]
     return [(R, d["S_vec"]) for (R, _), d in zip(outs, pgd)]
@@ -525,8 +678,8 @@ def _r_init_list(probs, R_init_list):
     return np.concatenate(parts) if parts else np.zeros(0)
 
 
-def _refine_batch_run(probs, device, S, R_init, stop_threshold, max_iters):
-    with _batch_handle(_lib.RefineBatch, probs, device) as batch:
+def _refine_batch_run(probs, device, S, R_init, stop_threshold, max_iters, pset=None):
+    with _batch_handle(_lib.RefineBatch, probs, device, on=pset) as batch:
         return batch.run(S, R_init, stop_threshold, max_iters)
 
 
@@ -540,13 +693,14 @@ def DESC_refine_batch(problems, S_list, R_init_list, stop_threshold=1e-3, max_it
     or an entry of the wrong size, a negative or non-finite S entry, a non-finite R_init entry, a problem of more than
     ``_lib.refine_batch_max_n()`` nodes (solve it with DESC)."""
     _check_sequence(problems)
-    probs, perms = _marshal_problems(problems)
+    pset = _resident(problems, device)
+    probs, perms = _marshal_problems(problems, rotations=pset is None)
     S = _sorted_s_list(probs, perms, S_list)
     R0 = _r_init_list(probs, R_init_list)
     if not probs:
         return []
     _check_refine_batch_sizes(probs)
-    outs, timings = _refine_batch_run(probs, device, S, R0, stop_threshold, max_iters)
+    outs, timings = _refine_batch_run(probs, device, S, R0, stop_threshold, max_iters, pset)
     return [(R, dict(info, timings=timings)) for R, info in outs] if return_info else [R for R, _ in outs]
 
 
@@ -562,17 +716,18 @@ def DESC_batch(problems, params, seeds=None, return_info=False, build="host", ei
     _check_eig(eig)
     _check_build(build)
     _check_sequence(problems)
-    probs, perms = _marshal_problems(problems)
+    pset = _resident(problems, _get(params, "device", 0))
+    probs, perms = _marshal_problems(problems, rotations=pset is None)
     if eig != "lds":                                 # the default's cap lies below the refinement's: nothing to check there
         _check_gcw_batch_sizes(probs, eig)
         _check_refine_batch_sizes(probs)
     init = DESC_init_batch([_Marshalled(q, perm) for q, perm in zip(probs, perms)], params, seeds=seeds, return_info=True, build=build,
-                           eig=eig)
+                           eig=eig, _set=pset)
     if not init:
         return []
     S = np.concatenate([S_vec if perm is None else S_vec[perm] for (_, S_vec, _), perm in zip(init, perms)])
     R0 = np.concatenate([R.reshape(-1, order="F") for R, _, _ in init])
-    outs, timings = _refine_batch_run(probs, int(_get(params, "device", 0)), S, R0, 1e-3, 100)
+    outs, timings = _refine_batch_run(probs, int(_get(params, "device", 0)), S, R0, 1e-3, 100, pset)
     if return_info:
         return [(R, R_init, S_vec, dict(info, refine=dict(rinfo, timings=timings))) for (R, rinfo), (R_init, S_vec, info) in zip(outs, init)]
     return [(R, R_init, S_vec) for (R, _), (R_init, S_vec, _) in zip(outs, init)]
@@ -628,6 +783,7 @@ def CEMP_batch(problems, CEMP_parameters, seeds=None, return_info=False):
     ``_lib.cemp_batch_max_degree()`` (solve that problem with CEMP)."""
     _check_sequence(problems)
     beta, max_iter, nsample, seed, device, seeds = _cemp_batch_params(CEMP_parameters, len(problems), seeds)
+    _resident(problems, device)                      # a set on another device is refused; the call reads its host mirror
     probs, perms = _marshal_problems(problems)
     if not probs:
         return []
@@ -671,6 +827,7 @@ def MST_batch(problems, S_list, device=0, return_info=False):
     the wrong size or holding a non-finite value, a problem of more than ``_lib.mst_batch_max_n()`` nodes (solve it with MST), a
     disconnected problem (a node id in 1..max(Ind) that no edge touches counts as a component)."""
     _check_sequence(problems)
+    _resident(problems, device)
     probs, perms = _marshal_problems(problems)
     S = _sorted_s_list(probs, perms, S_list, "SVec", np.isfinite,
                        lambda q, perm, t: f"SVec entry {int(t if perm is None else perm[t])} is not finite")
@@ -735,6 +892,7 @@ def MPLS_batch(problems, CEMP_parameters, MPLS_parameters, seeds=None, return_in
     _check_sequence(problems)
     cemp_beta, cemp_max_iter, nsample, seed, device, seeds = _cemp_batch_params(CEMP_parameters, len(problems), seeds)
     stop_threshold, max_iter, beta, tau, alpha = _mpls_batch_params(MPLS_parameters)
+    _resident(problems, device)
     probs, perms = _marshal_problems(problems)
     if not probs:
         return []
@@ -762,6 +920,7 @@ def _irls_batch(mode, name, problems, SIGMA, MaxIterations, device, return_info)
     if mi.size != 2:
         raise ValueError("MaxIterations must have two entries [L1, IRLS]")
     sigma = 5.0 if SIGMA is None or np.size(SIGMA) == 0 else float(SIGMA)
+    _resident(problems, device)
     for b, item in enumerate(problems):
         if isinstance(item, _Marshalled):
             continue
@@ -863,6 +1022,7 @@ def linprog_sij_batch(problems, params=None, seeds=None, rotations=True, return_
     want_y, device = bool(_get(params, "return_dual", False)), int(_get(params, "device", 0))
     if seeds is None:
         seeds = [int(_get(params, "seed", 0))] * B
+    pset = _resident(problems, device)
     if B == 0:
         return []
     probs, perms = _marshal_problems(problems)
@@ -892,9 +1052,9 @@ def linprog_sij_batch(problems, params=None, seeds=None, rotations=True, return_
     if not rotations:
         return [(S, info) for S, info in zip(S_list, infos)] if return_info else S_list
     S = np.concatenate([S for S, _, _ in outs])                          # the library's edge order, as both later passes take it
-    gcw, gcw_tm = _gcw_batch_run(probs, device, eig, weights=np.exp(-5.0 * S), normalize_rows=True)         # :154-174, beta_T = 5
+    gcw, gcw_tm = _gcw_batch_run(probs, device, eig, pset, weights=np.exp(-5.0 * S), normalize_rows=True)   # :154-174, beta_T = 5
     R0 = np.concatenate([R.reshape(-1, order="F") for R, _ in gcw])
-    ref, ref_tm = _refine_batch_run(probs, device, S, R0, 1e-3, 200)                                        # :176-351
+    ref, ref_tm = _refine_batch_run(probs, device, S, R0, 1e-3, 200, pset)                                        # :176-351
     if not return_info:
         return [(R, S_b) for (R, _), S_b in zip(ref, S_list)]
     for info, (R_gcw, sinfo), (_, rinfo) in zip(infos, gcw, ref):

@@ -246,6 +246,19 @@ __global__ __launch_bounds__(256) void k_batch_settle(double* buf0, const double
     for (int64_t i = lo + (int64_t)blockIdx.y * 256 + threadIdx.x; i < hi; i += (int64_t)gridDim.y * 256) buf0[i] = buf1[i];
 }
 
+// desc_pgd_batch_create_on: the workgroup table formed on the device from one 16-byte record per problem, entry for entry the table
+// batch_finish cuts on the host.  blockIdx.x = problem.
+struct BatchWgSeed { int32_t seg0, m_pos, G, per; };
+__global__ __launch_bounds__(256) void k_batch_wg_table(const BatchProb* prob, const BatchWgSeed* seed, BatchWg* wg) {
+    const int b = blockIdx.x;
+    const BatchProb pd = prob[b];
+    const BatchWgSeed s = seed[b];
+    for (int t = threadIdx.x; t < pd.nwg; t += 256) {
+        const int l = t * s.per;
+        wg[pd.wg0 + t] = BatchWg{b, s.seg0 + l, min(s.per, s.m_pos - l), s.G};
+    }
+}
+
 }  // namespace
 }  // namespace desc
 
@@ -277,6 +290,7 @@ struct desc_pgd_batch : desc::BatchDevice {     // device, stream, arena, events
     int32_t *d_kk = nullptr, *d_codeg = nullptr;
     bool st_ready = true;
     double ms_lap[desc::BATCH_BUILD_LAPS] = {0, 0, 0, 0, 0};
+    std::shared_ptr<desc::PbSet> set;         // desc_pgd_batch_create_on: the owner of the edge list, the CSR and the rotations
     ~desc_pgd_batch() {
         close();                                  // the device first, as ever
         for (desc_structure* s : st) if (s) { structure_free_device(s); delete s; }
@@ -328,13 +342,15 @@ StepArgs batch_step(const desc_pgd_batch* h, const desc_params& p, int t, int rd
     return s;
 }
 
-int batch_finish(const desc_problem* probs, desc_pgd_batch* h, const int32_t* d_kk, const int32_t* d_ii, const int32_t* d_jj);
+int batch_finish(const desc_problem* probs, desc_pgd_batch* h, const int32_t* d_kk, const int32_t* d_ii, const int32_t* d_jj, const PbSet* set);
 
-int batch_create(const desc_problem* probs, int32_t count, const desc_params* p, const uint64_t* seeds, desc_pgd_batch* h) {
+// set (nullable, here and below): the resident problem set a desc_pgd_batch_create_on builds on.  probs then views the set's host
+// endpoints (no rotations), nothing is validated again, and the edge list and the rotations on the device are the set's.
+int batch_create(const desc_problem* probs, int32_t count, const desc_params* p, const uint64_t* seeds, desc_pgd_batch* h, const PbSet* set = nullptr) {
     auto t0 = std::chrono::steady_clock::now();
     h->count = count; h->built_where = DESC_BUILD_HOST; h->st_ready = true;
     const int32_t nmin = p->n_sample_min > 0 ? p->n_sample_min : 30;
-    for (int32_t b = 0; b < count; ++b) {
+    for (int32_t b = 0; b < count && !set; ++b) {
         int rc = validate_problem(&probs[b], true);
         if (rc) { const std::string msg = desc_last_error(); return fail(rc, "problem %d: %s", b, msg.c_str()); }
     }
@@ -366,13 +382,13 @@ int batch_create(const desc_problem* probs, int32_t count, const desc_params* p,
     if (count == 0) return DESC_OK;
 
     const size_t M = (size_t)h->M, MC = (size_t)h->MC, MP = (size_t)h->MP;
-    hvec<int32_t> pos(MP), cum(MP + 1), ejk(MC), eki(MC), ikj(MC), jki(MC), kk(MC), ii(M), jj(M);
+    hvec<int32_t> pos(MP), cum(MP + 1), ejk(MC), eki(MC), ikj(MC), jki(MC), kk(MC), ii(set ? 0 : M), jj(set ? 0 : M);
     batch_concat_fill(h->st.data(), count, h->edge_off.data(), h->cycle_off.data(), h->seg_off.data(), pos.data(), cum.data(), ejk.data(), eki.data(),
                       ikj.data(), jki.data());
     for (int32_t b = 0; b < count; ++b) {
         const desc_structure* s = h->st[(size_t)b];
         if (s->m_cycle) std::memcpy(kk.data() + h->cycle_off[(size_t)b], s->k.data(), sizeof(int32_t) * (size_t)s->m_cycle);
-        if (s->m) {
+        if (s->m && !set) {
             std::memcpy(ii.data() + h->edge_off[(size_t)b], probs[b].ind_i, sizeof(int32_t) * (size_t)s->m);
             std::memcpy(jj.data() + h->edge_off[(size_t)b], probs[b].ind_j, sizeof(int32_t) * (size_t)s->m);
         }
@@ -384,8 +400,9 @@ int batch_create(const desc_problem* probs, int32_t count, const desc_params* p,
         q = BatchPlan{};
         q.m_pos = s->m_pos; q.m_cycle = s->m_cycle; q.n_sample = s->n_sample; q.max_cnt = s->max_cnt;
     }
-    if ((rc = h->open(p->device, "DESC_PGD_batch"))) return rc;           // nothing above touched the device
-    int32_t *d_kk = nullptr, *d_ii = nullptr, *d_jj = nullptr;
+    if ((rc = h->open(set ? set->device : p->device, "DESC_PGD_batch"))) return rc;           // nothing above touched the device
+    int32_t* d_kk = nullptr;
+    const int32_t *d_ii = set ? set->d_ii : nullptr, *d_jj = set ? set->d_jj : nullptr;
     if ((rc = h->upload(&h->d_cum, cum.data(), MP + 1))) return rc;
     if ((rc = h->upload(&h->d_pos, pos.data(), MP))) return rc;
     if ((rc = h->upload(&h->d_ejk, ejk.data(), MC))) return rc;
@@ -393,16 +410,15 @@ int batch_create(const desc_problem* probs, int32_t count, const desc_params* p,
     if ((rc = h->upload(&h->d_ikj, ikj.data(), MC))) return rc;
     if ((rc = h->upload(&h->d_jki, jki.data(), MC))) return rc;
     if ((rc = h->upload(&d_kk, kk.data(), MC))) return rc;
-    if ((rc = h->upload(&d_ii, ii.data(), M))) return rc;
-    if ((rc = h->upload(&d_jj, jj.data(), M))) return rc;
+    if (!set && ((rc = h->upload(&d_ii, ii.data(), M)) || (rc = h->upload(&d_jj, jj.data(), M)))) return rc;
     DESC_HIP(hipStreamSynchronize(h->stream));         // the index arrays are on the device: the staging vectors go out of scope below
     h->ms_structure = ms_since(t0);
-    return batch_finish(probs, h, d_kk, d_ii, d_jj);
+    return batch_finish(probs, h, d_kk, d_ii, d_jj, set);
 }
 
 // Behind either builder, once the index arrays are on the device: the workgroup table, the small tables, the rotations, the state
 // buffers, and S0_long of the whole batch in one launch.
-int batch_finish(const desc_problem* probs, desc_pgd_batch* h, const int32_t* d_kk, const int32_t* d_ii, const int32_t* d_jj) {
+int batch_finish(const desc_problem* probs, desc_pgd_batch* h, const int32_t* d_kk, const int32_t* d_ii, const int32_t* d_jj, const PbSet* set) {
     auto t1 = std::chrono::steady_clock::now();
     const int32_t count = h->count;
     const size_t M = (size_t)h->M, MC = (size_t)h->MC, MP = (size_t)h->MP;
@@ -410,27 +426,43 @@ int batch_finish(const desc_problem* probs, desc_pgd_batch* h, const int32_t* d_
     // the workgroup table: a problem's segments in runs of BATCH_PASSES x 4 waves x 64/G, counted from its own first segment
     hvec<BatchWg> wg;
     hvec<BatchProb> pr((size_t)count);
+    hvec<BatchWgSeed> seed(set ? (size_t)count : 0);   // on a resident set the table is cut on the device: O(B) bytes go up, not O(segments)
+    int64_t nwg = 0;
     for (int32_t b = 0; b < count; ++b) {
         const BatchPlan& s = h->plan[(size_t)b];
         const int G = s.max_cnt <= 16 ? 16 : s.max_cnt <= 32 ? 32 : 64;
         const int64_t per = (int64_t)BATCH_PASSES * 4 * (64 / G);
-        pr[(size_t)b].wg0 = (int32_t)wg.size(); pr[(size_t)b].m = probs[b].m;
-        for (int64_t l = 0; l < s.m_pos; l += per)
-            wg.push_back(BatchWg{b, (int32_t)(h->seg_off[(size_t)b] + l), (int32_t)std::min<int64_t>(per, s.m_pos - l), G});
-        pr[(size_t)b].nwg = (int32_t)wg.size() - pr[(size_t)b].wg0;
+        pr[(size_t)b].wg0 = (int32_t)nwg; pr[(size_t)b].m = probs[b].m;
+        if (!set)
+            for (int64_t l = 0; l < s.m_pos; l += per)
+                wg.push_back(BatchWg{b, (int32_t)(h->seg_off[(size_t)b] + l), (int32_t)std::min<int64_t>(per, s.m_pos - l), G});
+        else
+            seed[(size_t)b] = BatchWgSeed{(int32_t)h->seg_off[(size_t)b], (int32_t)s.m_pos, G, (int32_t)per};
+        nwg += (s.m_pos + per - 1) / per;
+        pr[(size_t)b].nwg = (int32_t)nwg - pr[(size_t)b].wg0;
     }
-    h->nwg = (int32_t)wg.size();
-    double* d_rij = nullptr;
-    if ((rc = h->upload(&h->d_wg, wg.data(), wg.size()))) return rc;
+    h->nwg = (int32_t)nwg;
+    const double* d_rij = set ? set->d_rij : nullptr;
     if ((rc = h->upload(&h->d_prob, pr.data(), pr.size()))) return rc;
+    if (!set) {
+        if ((rc = h->upload(&h->d_wg, wg.data(), wg.size()))) return rc;
+    } else {
+        BatchWgSeed* d_seed = nullptr;
+        if ((rc = h->upload(&d_seed, seed.data(), seed.size())) || (rc = h->mem.alloc(&h->d_wg, (size_t)nwg))) return rc;
+        hipLaunchKernelGGL(k_batch_wg_table, dim3((unsigned)count), dim3(256), 0, h->stream, h->d_prob, d_seed, h->d_wg);
+        DESC_HIP(hipGetLastError());
+    }
     if ((rc = h->upload(&h->d_edge_off, h->edge_off.data(), h->edge_off.size()))) return rc;
     if ((rc = h->upload(&h->d_cycle_off, h->cycle_off.data(), h->cycle_off.size()))) return rc;
     double nv[65];
     nv[0] = 0.0;
     for (int c = 1; c <= 64; ++c) nv[c] = 1.0 / std::pow((double)c, 0.5);             // ones/(nsample^0.5), DESC_PGD.m:199
     if ((rc = h->upload(&h->d_nv, nv, 65))) return rc;
-    const hvec<double> rij = stage_rotations(probs, count, h->edge_off);
-    if ((rc = h->upload(&d_rij, rij.data(), 9 * M))) return rc;
+    hvec<double> rij;
+    if (!set) {
+        rij = stage_rotations(probs, count, h->edge_off);
+        if ((rc = h->upload(&d_rij, rij.data(), 9 * M))) return rc;
+    }
     if ((rc = h->mem.alloc(&h->d_S0, MC))) return rc;
     for (int q = 0; q < 2; ++q) {
         if ((rc = h->mem.alloc(&h->d_w[q], MC))) return rc;
@@ -456,12 +488,13 @@ int batch_finish(const desc_problem* probs, desc_pgd_batch* h, const int32_t* d_
 
 // The device builder (batch_structure.hip) in place of the per-problem host builds, the concatenation and the seven uploads.  May
 // return BATCH_BUILD_FALLBACK: the caller then builds the same handle on the host.
-int batch_create_device(const desc_problem* probs, int32_t count, const desc_params* p, const uint64_t* seeds, desc_pgd_batch* h) {
+int batch_create_device(const desc_problem* probs, int32_t count, const desc_params* p, const uint64_t* seeds, desc_pgd_batch* h,
+                        const PbSet* set = nullptr) {
     auto t0 = std::chrono::steady_clock::now();
     h->count = count; h->built_where = DESC_BUILD_DEVICE;
     const int32_t nmin = p->n_sample_min > 0 ? p->n_sample_min : 30;
     BatchBuilt bb;
-    int rc = batch_structure_device(h, probs, count, nmin, p->seed, seeds, p->device, &bb);
+    int rc = batch_structure_device(h, probs, count, nmin, p->seed, seeds, set ? set->device : p->device, &bb, set);
     if (rc) return rc;
     h->st.assign((size_t)count, nullptr);
     h->st_ready = count == 0;
@@ -475,7 +508,7 @@ int batch_create_device(const desc_problem* probs, int32_t count, const desc_par
     h->d_kk = bb.d_kk; h->d_codeg = bb.d_codeg;
     for (int t = 0; t < BATCH_BUILD_LAPS; ++t) h->ms_lap[t] = bb.ms_lap[t];
     h->ms_structure = ms_since(t0);                    // batch_structure_device returned with the stream drained
-    return batch_finish(probs, h, bb.d_kk, bb.d_ii, bb.d_jj);
+    return batch_finish(probs, h, bb.d_kk, bb.d_ii, bb.d_jj, set);
 }
 
 // desc_pgd_batch_get_structure on a device-built handle, first request: the index arrays come down once, every problem's share less
@@ -675,6 +708,38 @@ int desc_pgd_batch_create_where(const desc_problem* probs, int32_t count, const 
         }
         return batch_create(probs, count, p, seeds, h);
     }, p != nullptr);
+}
+
+int desc_pgd_batch_create_on(desc_problem_batch* set, const desc_params* p, const uint64_t* seeds, int32_t where, desc_pgd_batch** out) {
+    if (where != DESC_BUILD_HOST && where != DESC_BUILD_DEVICE) {
+        if (out) *out = nullptr;
+        return fail(DESC_ERR_INVALID, "where = %d: need DESC_BUILD_HOST or DESC_BUILD_DEVICE", (int)where);
+    }
+    return batch_create_guarded("desc_pgd_batch_create_on", out, set, 0, [&](desc_pgd_batch* h) {
+        const PbSet* s = set->s.get();
+        const int32_t count = s->count;
+        hvec<desc_problem> probs((size_t)count);        // views of the set's host endpoints: what either builder reads of a problem
+        for (int32_t b = 0; b < count; ++b) {
+            const int64_t eo = s->edge_off[(size_t)b];
+            desc_problem& q = probs[(size_t)b];
+            q.n = s->node_off[(size_t)b + 1] - s->node_off[(size_t)b]; q.m = s->edge_off[(size_t)b + 1] - eo;
+            q.ind_i = s->ii.data() + eo; q.ind_j = s->jj.data() + eo; q.rij = nullptr;
+        }
+        h->set = set->s;                               // before the first device block of the handle: the set outlives what borrows from it
+        if (where == DESC_BUILD_DEVICE) {
+            const int rc = batch_create_device(probs.data(), count, p, seeds, h, s);
+            if (rc != BATCH_BUILD_FALLBACK) return rc;
+            h->close();                                // outside what the device builder stages: the same handle, built on the host
+        }
+        return batch_create(probs.data(), count, p, seeds, h, s);
+    }, set != nullptr && p != nullptr);
+}
+
+int desc_pgd_batch_bytes(const desc_pgd_batch* h, int64_t* h2d, int64_t* d2h) {
+    if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
+    if (h2d) *h2d = h->bytes_h2d;
+    if (d2h) *d2h = h->bytes_d2h;
+    return DESC_OK;
 }
 
 int32_t desc_pgd_batch_built_where(const desc_pgd_batch* h) { return h ? h->built_where : (int32_t)fail(DESC_ERR_INVALID, "NULL handle"); }

@@ -16,6 +16,7 @@ struct BatchDevice {
     DevArena mem;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;  // timer_begin / timer_end: made at the first timed launch, kept for the handle's life
     double ms_structure = 0, ms_upload = 0;
+    int64_t bytes_h2d = 0, bytes_d2h = 0;     // what upload copied up and download copied down (desc_*_batch_bytes): counters, no behaviour
 
     ~BatchDevice() { close(); }
 
@@ -51,7 +52,16 @@ struct BatchDevice {
         std::remove_const_t<T>* d = nullptr;
         int rc = mem.alloc(&d, n); if (rc) return rc;
         if (n) DESC_HIP(hipMemcpyAsync(d, src, sizeof(T) * n, hipMemcpyHostToDevice, stream));
+        bytes_h2d += (int64_t)(sizeof(T) * n);
         *dst = d;
+        return DESC_OK;
+    }
+
+    // dst[0..n) = the device array src once the stream has drained
+    template <class T>
+    int download(T* dst, const T* src, size_t n) {
+        if (n) DESC_HIP(hipMemcpyAsync(dst, src, sizeof(T) * n, hipMemcpyDeviceToHost, stream));
+        bytes_d2h += (int64_t)(sizeof(T) * n);
         return DESC_OK;
     }
 

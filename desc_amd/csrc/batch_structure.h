@@ -4,6 +4,7 @@
 #include "batch_csr.h"
 #include "batch_device.h"
 #include "cemp_batch.h"
+#include "problem_batch.h"
 
 namespace desc {
 
@@ -61,14 +62,18 @@ struct BatchBuilt {
     hvec<BatchPlan> plan;                      // per problem
     hvec<int64_t> edge_off, cycle_off, seg_off;
     int32_t *d_cum = nullptr, *d_pos = nullptr, *d_ejk = nullptr, *d_eki = nullptr, *d_ikj = nullptr, *d_jki = nullptr;
-    int32_t *d_kk = nullptr, *d_ii = nullptr, *d_jj = nullptr, *d_codeg = nullptr;
+    int32_t *d_kk = nullptr, *d_codeg = nullptr;
+    const int32_t *d_ii = nullptr, *d_jj = nullptr;    // the builder's own uploads, or the set's
     double ms_lap[BATCH_BUILD_LAPS] = {0, 0, 0, 0, 0};      // device time of the five launches (HIP events)
 };
 
 // validate -> batch_csr_host -> open(device) -> uploads -> codegrees, plan -> the one read-back -> refusals -> compaction, sampling,
 // mirror maps.  Returns DESC_OK, an error code (the refusals of the host path, same code and same "problem b") or BATCH_BUILD_FALLBACK
 // (a CSR row above CEMP_BATCH_MAX_DEGREE: before the device is opened; a codegree above BATCH_MAX_CODEG: after the read-back).
+// set (nullable): a resident problem set the problems come from (problem_batch.h; probs then views its host endpoints and device is the
+// set's).  Nothing is validated or laid out again, the edge list and the CSR are the set's device arrays, the edge -> problem map is
+// filled by a launch, and the uploads of the build are O(B) bytes.
 int batch_structure_device(BatchDevice* dev, const desc_problem* probs, int32_t count, int32_t n_sample_min, uint64_t seed,
-                           const uint64_t* seeds, int32_t device, BatchBuilt* out);
+                           const uint64_t* seeds, int32_t device, BatchBuilt* out, const PbSet* set = nullptr);
 
 }  // namespace desc

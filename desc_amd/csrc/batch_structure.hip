@@ -230,16 +230,33 @@ __global__ __launch_bounds__(256) void k_bs_mirror(BsArgs a) {
 
 }  // namespace
 
+// the edge -> problem map of a batch that came without a host pass over its edges: one workgroup per problem fills its range
+__global__ __launch_bounds__(256) void k_bs_eprob(const CbProb* prob, int32_t* eprob) {
+    const int b = blockIdx.x;
+    const CbProb pd = prob[b];
+    for (int e = threadIdx.x; e < pd.m; e += 256) eprob[pd.edge_off + e] = b;
+}
+
 int batch_structure_device(BatchDevice* dev, const desc_problem* probs, int32_t count, int32_t n_sample_min, uint64_t seed,
-                           const uint64_t* seeds, int32_t device, BatchBuilt* out) {
+                           const uint64_t* seeds, int32_t device, BatchBuilt* out, const PbSet* set) {
     // ---- host, O(m): validation (as the host path words it) and the per-problem CSR with local ids
-    BatchCsr csr;
-    int rc = batch_csr_host(probs, count, nullptr, &csr, true);
-    if (rc) return rc;
-    for (int32_t b = 0; b < count; ++b) {
-        const int32_t* rp = csr.rowptr.data() + csr.node_off[(size_t)b] + b;
-        for (int64_t v = 0; v < probs[b].n; ++v)
-            if (rp[v + 1] - rp[v] > CEMP_BATCH_MAX_DEGREE) return BATCH_BUILD_FALLBACK;             // row positions are packed in 16 bits
+    BatchCsr own;
+    const BatchCsr& csr = set ? static_cast<const BatchCsr&>(*set) : own;
+    int rc;
+    if (!set) {
+        if ((rc = batch_csr_host(probs, count, nullptr, &own, true))) return rc;
+        for (int32_t b = 0; b < count; ++b) {
+            const int32_t* rp = csr.rowptr.data() + csr.node_off[(size_t)b] + b;
+            for (int64_t v = 0; v < probs[b].n; ++v)
+                if (rp[v + 1] - rp[v] > CEMP_BATCH_MAX_DEGREE) return BATCH_BUILD_FALLBACK;             // row positions are packed in 16 bits
+        }
+    } else {                                           // the same rule from the set's host endpoints: its CSR may be on the device only
+        hvec<int32_t> deg;
+        for (int32_t b = 0; b < count; ++b) {
+            deg.assign((size_t)probs[b].n, 0);
+            for (int64_t e = csr.edge_off[(size_t)b]; e < csr.edge_off[(size_t)b + 1]; ++e) { ++deg[(size_t)csr.ii[(size_t)e]]; ++deg[(size_t)csr.jj[(size_t)e]]; }
+            for (int32_t d : deg) if (d > CEMP_BATCH_MAX_DEGREE) return BATCH_BUILD_FALLBACK;
+        }
     }
     out->edge_off = csr.edge_off;
     out->cycle_off.assign((size_t)count + 1, 0); out->seg_off.assign((size_t)count + 1, 0);
@@ -247,21 +264,33 @@ int batch_structure_device(BatchDevice* dev, const desc_problem* probs, int32_t 
     if (count == 0) return DESC_OK;
 
     if ((rc = dev->open(device, "DESC_PGD_batch"))) return rc;             // nothing above touched the device
-    const size_t M = (size_t)csr.M, NB = csr.rowptr.size();
+    const size_t M = (size_t)csr.M, NB = (size_t)csr.N + (size_t)count;
     hvec<CbProb> pr((size_t)count);
-    hvec<int32_t> eprob(M);
-    for (int32_t b = 0; b < count; ++b) {
-        const size_t eo = (size_t)csr.edge_off[(size_t)b], m = (size_t)probs[b].m;
-        pr[(size_t)b] = CbProb{(int32_t)probs[b].n, (int32_t)m, (int32_t)csr.node_off[(size_t)b], (int32_t)eo, seeds ? seeds[b] : seed};
-        std::fill(eprob.begin() + eo, eprob.begin() + eo + m, b);
-    }
+    for (int32_t b = 0; b < count; ++b)
+        pr[(size_t)b] = CbProb{(int32_t)probs[b].n, (int32_t)probs[b].m, (int32_t)csr.node_off[(size_t)b], (int32_t)csr.edge_off[(size_t)b],
+                               seeds ? seeds[b] : seed};
     BsArgs a{};
     BatchPlan* d_plan = nullptr;
-    int32_t *d_ii = nullptr, *d_jj = nullptr;
-    if ((rc = dev->upload(&a.prob, pr.data(), pr.size())) || (rc = dev->upload(&a.eprob, eprob.data(), M)) ||
-        (rc = dev->upload(&d_ii, csr.ii.data(), M)) || (rc = dev->upload(&d_jj, csr.jj.data(), M)) ||
-        (rc = dev->upload(&a.rowptr, csr.rowptr.data(), NB)) || (rc = dev->upload(&a.adj, csr.adj.data(), 2 * M)) ||
-        (rc = dev->upload(&a.adj_eid, csr.adj_eid.data(), 2 * M))) return rc;
+    const int32_t *d_ii = nullptr, *d_jj = nullptr;
+    hvec<int32_t> eprob;
+    if ((rc = dev->upload(&a.prob, pr.data(), pr.size()))) return rc;
+    if (!set) {
+        eprob.resize(M);
+        for (int32_t b = 0; b < count; ++b) {
+            const size_t eo = (size_t)csr.edge_off[(size_t)b], m = (size_t)probs[b].m;
+            std::fill(eprob.begin() + eo, eprob.begin() + eo + m, b);
+        }
+        if ((rc = dev->upload(&a.eprob, eprob.data(), M)) ||
+            (rc = dev->upload(&d_ii, csr.ii.data(), M)) || (rc = dev->upload(&d_jj, csr.jj.data(), M)) ||
+            (rc = dev->upload(&a.rowptr, csr.rowptr.data(), NB)) || (rc = dev->upload(&a.adj, csr.adj.data(), 2 * M)) ||
+            (rc = dev->upload(&a.adj_eid, csr.adj_eid.data(), 2 * M))) return rc;
+    } else {
+        int32_t* d_eprob = nullptr;
+        if ((rc = dev->mem.alloc(&d_eprob, M))) return rc;
+        hipLaunchKernelGGL(k_bs_eprob, dim3((unsigned)count), dim3(256), 0, dev->stream, a.prob, d_eprob);
+        DESC_HIP(hipGetLastError());
+        a.eprob = d_eprob; d_ii = set->d_ii; d_jj = set->d_jj; a.rowptr = set->d_rowptr; a.adj = set->d_adj; a.adj_eid = set->d_adj_eid;
+    }
     if ((rc = dev->mem.alloc(&a.codeg, M)) || (rc = dev->mem.alloc(&a.hist, NB)) || (rc = dev->mem.alloc(&d_plan, (size_t)count))) return rc;
     a.ii = d_ii; a.jj = d_jj; a.plan = d_plan;
     a.M = (int32_t)M; a.n_sample_min = n_sample_min;

@@ -44,6 +44,7 @@
 
 #include "batch_csr.h"
 #include "batch_device.h"
+#include "problem_batch.h"
 #include "laa_wg.h"
 #include "small_dense.h"
 
@@ -372,8 +373,10 @@ __global__ __launch_bounds__(256, 2) void k_gcw_batch(GbArgs a) {
 
 namespace desc {
 
-int batch_csr_host(const desc_problem* probs, int32_t count, const std::function<int(int32_t, const desc_problem&)>& extra, BatchCsr* h,
-                   bool allow_empty) {
+namespace {
+// the refusals and the offsets; ii and jj sized, not filled
+int batch_offsets_core(const desc_problem* probs, int32_t count, const std::function<int(int32_t, const desc_problem&)>& extra, BatchCsr* h,
+                       bool allow_empty) {
     h->count = count;
     h->node_off.assign((size_t)count + 1, 0); h->edge_off.assign((size_t)count + 1, 0);
     for (int32_t b = 0; b < count; ++b) {
@@ -389,6 +392,26 @@ int batch_csr_host(const desc_problem* probs, int32_t count, const std::function
     if (h->M >= (1ll << 30))
         return fail(DESC_ERR_TOO_LARGE, "the batch holds %lld edges in total: the 2^30 index budget is exceeded, split the batch", (long long)h->M);
     h->ii.resize((size_t)h->M); h->jj.resize((size_t)h->M);
+    return DESC_OK;
+}
+}  // namespace
+
+int batch_offsets_host(const desc_problem* probs, int32_t count, const std::function<int(int32_t, const desc_problem&)>& extra, BatchCsr* h,
+                       bool allow_empty) {
+    const int rc = batch_offsets_core(probs, count, extra, h, allow_empty);
+    if (rc) return rc;
+    for_each_problem(count, [&](int32_t b) {
+        const int64_t m = probs[b].m, eo = h->edge_off[(size_t)b];
+        std::memcpy(h->ii.data() + eo, probs[b].ind_i, sizeof(int32_t) * (size_t)m);
+        std::memcpy(h->jj.data() + eo, probs[b].ind_j, sizeof(int32_t) * (size_t)m);
+    });
+    return DESC_OK;
+}
+
+int batch_csr_host(const desc_problem* probs, int32_t count, const std::function<int(int32_t, const desc_problem&)>& extra, BatchCsr* h,
+                   bool allow_empty) {
+    const int rc = batch_offsets_core(probs, count, extra, h, allow_empty);
+    if (rc) return rc;
     h->rowptr.resize((size_t)h->N + (size_t)count); h->adj.resize(2 * (size_t)h->M); h->adj_eid.resize(2 * (size_t)h->M);
     for_each_problem(count, [&](int32_t b) {
         hvec<int32_t> rp, ad, ae;
@@ -418,32 +441,89 @@ struct desc_gcw_batch : desc::BatchCsr, desc::BatchDevice {     // offsets and t
     int32_t max_n_lds = 0, max_n_streamed = 0;
     int32_t *d_lds_list = nullptr, *d_streamed_list = nullptr;
     double* d_work = nullptr;
+    std::shared_ptr<desc::PbSet> set;         // desc_gcw_batch_create_on: the owner of d_prob, the CSR and d_rij
+    ~desc_gcw_batch() { close(); }            // the stream drains before the set may go
 };
 
 namespace {
 
-// validation, offsets and the per-problem CSR, the split of the batch between the two kernels: no device
-int gb_host_part(const desc_problem* probs, int32_t count, int32_t eig, desc_gcw_batch* h) {
+int gb_check_eig(int32_t eig) {
     if (eig != DESC_GCW_EIG_LDS && eig != DESC_GCW_EIG_STREAMED && eig != DESC_GCW_EIG_AUTO)
         return fail(DESC_ERR_INVALID, "eig = %d is none of DESC_GCW_EIG_LDS (0), DESC_GCW_EIG_STREAMED (1), DESC_GCW_EIG_AUTO (2)", eig);
-    h->eig = eig;
-    int rc = batch_csr_host(probs, count, [eig](int32_t b, const desc_problem& q) -> int {
-        if (eig == DESC_GCW_EIG_LDS && q.n > GCW_BATCH_MAX_N)
-            return fail(DESC_ERR_INVALID, "problem %d: n = %lld exceeds %d (the 3n x 6 blocks of the eigen-solve must fit the LDS of one workgroup): solve it with GCW / DESC_init",
-                        b, (long long)q.n, GCW_BATCH_MAX_N);
-        if (q.n > GCW_BATCH_STREAMED_MAX_N)
-            return fail(DESC_ERR_INVALID, "problem %d: n = %lld exceeds %d (one 3n x 6 block of the streamed eigen-solve must fit the LDS of one workgroup): solve it with GCW / DESC_init",
-                        b, (long long)q.n, GCW_BATCH_STREAMED_MAX_N);
-        return DESC_OK;
-    }, h);
-    if (rc) return rc;
-    for (int32_t b = 0; b < count; ++b) {
-        const int32_t n = (int32_t)probs[b].n;
-        const bool streamed = eig == DESC_GCW_EIG_STREAMED || (eig == DESC_GCW_EIG_AUTO && n > GCW_BATCH_MAX_N);
+    return DESC_OK;
+}
+
+// the caps of the two kernels for problem b of n nodes
+int gb_check_n(int32_t eig, int32_t b, int64_t n) {
+    if (eig == DESC_GCW_EIG_LDS && n > GCW_BATCH_MAX_N)
+        return fail(DESC_ERR_INVALID, "problem %d: n = %lld exceeds %d (the 3n x 6 blocks of the eigen-solve must fit the LDS of one workgroup): solve it with GCW / DESC_init",
+                    b, (long long)n, GCW_BATCH_MAX_N);
+    if (n > GCW_BATCH_STREAMED_MAX_N)
+        return fail(DESC_ERR_INVALID, "problem %d: n = %lld exceeds %d (one 3n x 6 block of the streamed eigen-solve must fit the LDS of one workgroup): solve it with GCW / DESC_init",
+                    b, (long long)n, GCW_BATCH_STREAMED_MAX_N);
+    return DESC_OK;
+}
+
+// which kernel solves which problem, from the offsets
+void gb_split(desc_gcw_batch* h) {
+    for (int32_t b = 0; b < h->count; ++b) {
+        const int32_t n = (int32_t)(h->node_off[(size_t)b + 1] - h->node_off[(size_t)b]);
+        const bool streamed = h->eig == DESC_GCW_EIG_STREAMED || (h->eig == DESC_GCW_EIG_AUTO && n > GCW_BATCH_MAX_N);
         (streamed ? h->streamed_list : h->lds_list).push_back(b);
         int32_t& mx = streamed ? h->max_n_streamed : h->max_n_lds;
         mx = std::max(mx, n);
     }
+}
+
+// validation, offsets and the per-problem CSR, the split of the batch between the two kernels: no device
+int gb_host_part(const desc_problem* probs, int32_t count, int32_t eig, desc_gcw_batch* h) {
+    int rc = gb_check_eig(eig);
+    if (rc) return rc;
+    h->eig = eig;
+    rc = batch_csr_host(probs, count, [eig](int32_t b, const desc_problem& q) -> int { return gb_check_n(eig, b, q.n); }, h);
+    if (rc) return rc;
+    gb_split(h);
+    return DESC_OK;
+}
+
+// the run's own buffers, the same behind either create
+int gb_alloc_work(desc_gcw_batch* h) {
+    const size_t M = (size_t)h->M, N = (size_t)h->N;
+    int rc;
+    if ((rc = h->mem.alloc(&h->d_in, M)) || (rc = h->mem.alloc(&h->d_w, M)) || (rc = h->mem.alloc(&h->d_dinv, N)) ||
+        (rc = h->mem.alloc(&h->d_blocks, 18 * M)) || (rc = h->mem.alloc(&h->d_V, 9 * N)) || (rc = h->mem.alloc(&h->d_info, (size_t)h->count))) return rc;
+    if (!h->streamed_list.empty()) {
+        if ((rc = h->mem.alloc(&h->d_work, 4 * 3 * BW * N))) return rc;
+        if (!h->lds_list.empty() &&
+            ((rc = h->upload(&h->d_lds_list, h->lds_list.data(), h->lds_list.size())) ||
+             (rc = h->upload(&h->d_streamed_list, h->streamed_list.data(), h->streamed_list.size())))) return rc;
+    }
+    return DESC_OK;
+}
+
+// On a resident set: the refusals of gb_host_part that the set has not made already, then nothing but the run's buffers -- d_prob (the
+// set's record is GbProb's), the CSR and the rotations are the set's.
+int gb_create_on(const std::shared_ptr<PbSet>& set, int32_t eig, desc_gcw_batch* h) {
+    auto t0 = std::chrono::steady_clock::now();
+    static_assert(sizeof(GbProb) == sizeof(PbProb), "the set's problem record is the eigen-solve's");
+    int rc = gb_check_eig(eig);
+    if (rc) return rc;
+    h->eig = eig;
+    for (int32_t b = 0; b < set->count; ++b)
+        if ((rc = gb_check_n(eig, b, set->node_off[(size_t)b + 1] - set->node_off[(size_t)b]))) return rc;
+    pb_share_host(*set, h);
+    gb_split(h);
+    h->ms_structure = ms_since(t0);
+    if (h->count == 0) return DESC_OK;
+
+    if ((rc = h->open(set->device, "the batched eigen-solve"))) return rc;  // nothing above touched the device
+    auto t1 = std::chrono::steady_clock::now();
+    h->set = set;
+    h->d_prob = reinterpret_cast<GbProb*>(set->d_prob);
+    h->d_rowptr = set->d_rowptr; h->d_adj = set->d_adj; h->d_adj_eid = set->d_adj_eid; h->d_rij = set->d_rij;
+    if ((rc = gb_alloc_work(h))) return rc;
+    DESC_HIP(hipStreamSynchronize(h->stream));         // the two lists may be on their way
+    h->ms_upload = ms_since(t1);
     return DESC_OK;
 }
 
@@ -456,7 +536,7 @@ int gb_create(const desc_problem* probs, int32_t count, int32_t device, int32_t 
 
     if ((rc = h->open(device, "the batched eigen-solve"))) return rc;      // nothing above touched the device
     auto t1 = std::chrono::steady_clock::now();
-    const size_t M = (size_t)h->M, N = (size_t)h->N;
+    const size_t M = (size_t)h->M;
     hvec<GbProb> pr((size_t)count);
     for (int32_t b = 0; b < count; ++b) pr[(size_t)b] = GbProb{(int32_t)probs[b].n, (int32_t)probs[b].m, h->node_off[(size_t)b], h->edge_off[(size_t)b]};
     const hvec<double> rij = stage_rotations(probs, count, h->edge_off);
@@ -465,14 +545,7 @@ int gb_create(const desc_problem* probs, int32_t count, int32_t device, int32_t 
     if ((rc = h->upload(&h->d_adj, h->adj.data(), 2 * M))) return rc;
     if ((rc = h->upload(&h->d_adj_eid, h->adj_eid.data(), 2 * M))) return rc;
     if ((rc = h->upload(&h->d_rij, rij.data(), 9 * M))) return rc;
-    if ((rc = h->mem.alloc(&h->d_in, M)) || (rc = h->mem.alloc(&h->d_w, M)) || (rc = h->mem.alloc(&h->d_dinv, N)) ||
-        (rc = h->mem.alloc(&h->d_blocks, 18 * M)) || (rc = h->mem.alloc(&h->d_V, 9 * N)) || (rc = h->mem.alloc(&h->d_info, (size_t)count))) return rc;
-    if (!h->streamed_list.empty()) {
-        if ((rc = h->mem.alloc(&h->d_work, 4 * 3 * BW * N))) return rc;
-        if (!h->lds_list.empty() &&
-            ((rc = h->upload(&h->d_lds_list, h->lds_list.data(), h->lds_list.size())) ||
-             (rc = h->upload(&h->d_streamed_list, h->streamed_list.data(), h->streamed_list.size())))) return rc;
-    }
+    if ((rc = gb_alloc_work(h))) return rc;
     DESC_HIP(hipStreamSynchronize(h->stream));         // the staging vectors go out of scope below
     h->ms_upload = ms_since(t1);
     return DESC_OK;
@@ -573,6 +646,17 @@ int desc_gcw_batch_create(const desc_problem* probs, int32_t count, int32_t devi
 int desc_gcw_batch_create_where(const desc_problem* probs, int32_t count, int32_t device, int32_t eig, desc_gcw_batch** out) {
     return batch_create_guarded("desc_gcw_batch_create_where", out, probs, count,
                                 [&](desc_gcw_batch* h) { return gb_create(probs, count, device, eig, h); });
+}
+
+int desc_gcw_batch_create_on(desc_problem_batch* set, int32_t eig, desc_gcw_batch** out) {
+    return batch_create_guarded("desc_gcw_batch_create_on", out, set, 0, [&](desc_gcw_batch* h) { return gb_create_on(set->s, eig, h); }, set != nullptr);
+}
+
+int desc_gcw_batch_bytes(const desc_gcw_batch* h, int64_t* h2d, int64_t* d2h) {
+    if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
+    if (h2d) *h2d = h->bytes_h2d;
+    if (d2h) *d2h = h->bytes_d2h;
+    return DESC_OK;
 }
 
 int desc_gcw_batch_sizes(const desc_gcw_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off) {

@@ -32,6 +32,7 @@
 
 #include "batch_device.h"
 #include "cemp_math.h"
+#include "problem_batch.h"
 #include "so3_blocks.h"
 
 namespace desc {
@@ -463,6 +464,22 @@ int mb_test_draws(const char* name, uint64_t seed, uint64_t stream, uint64_t sub
 }
 
 }  // namespace
+
+// For desc_problem_batch_from_models (problem_batch.hip): the node and edge passes run here if no fetch has run them yet; nothing is
+// copied to the host.
+int desc::models_batch_view(desc_models_batch* h, ModelsView* out) {
+    out->count = h->count; out->device = h->device; out->m_per = h->m_per.data();
+    if (h->count == 0) return DESC_OK;
+    DESC_HIP(hipSetDevice(h->device));
+    if (!h->generated) {
+        double ms_nodes = 0, ms_edges = 0;
+        const int rc = mb_generate(h, &ms_nodes, &ms_edges);
+        if (rc) return rc;
+    }
+    DESC_HIP(hipStreamSynchronize(h->stream));
+    out->d_ii = h->a.ii; out->d_jj = h->a.jj; out->d_rij = h->a.rij; out->M = h->a.M;
+    return DESC_OK;
+}
 
 extern "C" {
 

@@ -36,6 +36,7 @@
 
 #include "batch_csr.h"
 #include "batch_device.h"
+#include "problem_batch.h"
 #include "laa_wg.h"
 
 namespace desc {
@@ -141,6 +142,18 @@ __global__ __launch_bounds__(256) void k_refine_batch(RbArgs a) {
     }
 }
 
+// desc_refine_batch_create_on: the incidence sign per CSR slot from the set's CSR, as rb_create forms it on the host -- -1 where the
+// row's node is the smaller endpoint.  One workgroup per problem, a thread per row.
+__global__ __launch_bounds__(256) void k_rb_sgn(const RbProb* prob, const int32_t* rowptr_all, const int32_t* adj_all, int8_t* sgn_all) {
+    const int b = blockIdx.x;
+    const RbProb pd = prob[b];
+    const int32_t* rowptr = rowptr_all + pd.node_off + b;
+    const int32_t* adj = adj_all + 2 * pd.edge_off;
+    int8_t* sgn = sgn_all + 2 * pd.edge_off;
+    for (int v = threadIdx.x; v < pd.n; v += 256)
+        for (int t = rowptr[v]; t < rowptr[v + 1]; ++t) sgn[t] = v < adj[t] ? -1 : +1;
+}
+
 }  // namespace
 }  // namespace desc
 
@@ -153,25 +166,69 @@ struct desc_refine_batch : desc::BatchCsr, desc::BatchDevice {  // offsets and t
     double *d_rij = nullptr, *d_S = nullptr, *d_thresh0 = nullptr, *d_Rinit = nullptr, *d_Rout = nullptr, *d_B = nullptr, *d_w = nullptr, *d_RS = nullptr;
     Quat* d_QQ = nullptr;
     RbInfo* d_info = nullptr;
+    std::shared_ptr<desc::PbSet> set;         // desc_refine_batch_create_on: the owner of d_prob, the CSR, d_ii / d_jj and d_rij
+    ~desc_refine_batch() { close(); }         // the stream drains before the set may go
 };
 
 namespace {
 
+int rb_check_n(int32_t b, int64_t n) {
+    if (n > REFINE_BATCH_MAX_N)
+        return fail(DESC_ERR_INVALID, "problem %d: n = %lld exceeds %d (the per-node state of the refinement must fit the LDS of one workgroup): solve it with DESC",
+                    b, (long long)n, REFINE_BATCH_MAX_N);
+    return DESC_OK;
+}
+
 // validation, offsets and the per-problem CSR: no device
 int rb_host_part(const desc_problem* probs, int32_t count, desc_refine_batch* h) {
-    return batch_csr_host(probs, count, [](int32_t b, const desc_problem& q) -> int {
-        if (q.n > REFINE_BATCH_MAX_N)
-            return fail(DESC_ERR_INVALID, "problem %d: n = %lld exceeds %d (the per-node state of the refinement must fit the LDS of one workgroup): solve it with DESC",
-                        b, (long long)q.n, REFINE_BATCH_MAX_N);
-        return DESC_OK;
-    }, h);
+    return batch_csr_host(probs, count, [](int32_t b, const desc_problem& q) -> int { return rb_check_n(b, q.n); }, h);
+}
+
+// the run's own buffers, the same behind either create
+int rb_alloc_work(desc_refine_batch* h) {
+    const size_t M = (size_t)h->M, N = (size_t)h->N, count = (size_t)h->count;
+    int rc;
+    if ((rc = h->mem.alloc(&h->d_S, M)) || (rc = h->mem.alloc(&h->d_thresh0, count)) || (rc = h->mem.alloc(&h->d_Rinit, 9 * N)) ||
+        (rc = h->mem.alloc(&h->d_Rout, 9 * N)) || (rc = h->mem.alloc(&h->d_QQ, M)) || (rc = h->mem.alloc(&h->d_B, 3 * M)) ||
+        (rc = h->mem.alloc(&h->d_w, M)) || (rc = h->mem.alloc(&h->d_RS, M)) || (rc = h->mem.alloc(&h->d_info, count)))
+        return rc;
+    // the largest dynamic LDS any handle may ask for: the attribute belongs to the kernel, not to a handle, so it is never lowered
+    DESC_HIP(hipFuncSetAttribute((const void*)k_refine_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rb_lds_bytes(REFINE_BATCH_MAX_N)));
+    return DESC_OK;
+}
+
+// On a resident set: the cap, then the signs per slot in one launch from the set's CSR; everything else the kernel reads of the
+// problems is the set's (its record is RbProb's).
+int rb_create_on(const std::shared_ptr<PbSet>& set, desc_refine_batch* h) {
+    auto t0 = std::chrono::steady_clock::now();
+    static_assert(sizeof(RbProb) == sizeof(PbProb), "the set's problem record is the refinement's");
+    int rc;
+    for (int32_t b = 0; b < set->count; ++b)
+        if ((rc = rb_check_n(b, set->node_off[(size_t)b + 1] - set->node_off[(size_t)b]))) return rc;
+    pb_share_host(*set, h);
+    h->ms_structure = ms_since(t0);
+    if (h->count == 0) return DESC_OK;
+
+    if ((rc = h->open(set->device, "the batched refinement"))) return rc;   // nothing above touched the device
+    auto t1 = std::chrono::steady_clock::now();
+    h->set = set;
+    h->d_prob = reinterpret_cast<RbProb*>(set->d_prob);
+    h->d_rowptr = set->d_rowptr; h->d_adj = set->d_adj; h->d_adj_eid = set->d_adj_eid; h->d_ii = set->d_ii; h->d_jj = set->d_jj;
+    h->d_rij = set->d_rij;
+    if ((rc = h->mem.alloc(&h->d_sgn, 2 * (size_t)h->M))) return rc;
+    hipLaunchKernelGGL(k_rb_sgn, dim3((unsigned)h->count), dim3(256), 0, h->stream, h->d_prob, h->d_rowptr, h->d_adj, h->d_sgn);
+    DESC_HIP(hipGetLastError());
+    if ((rc = rb_alloc_work(h))) return rc;
+    DESC_HIP(hipStreamSynchronize(h->stream));
+    h->ms_upload = ms_since(t1);
+    return DESC_OK;
 }
 
 int rb_create(const desc_problem* probs, int32_t count, int32_t device, desc_refine_batch* h) {
     auto t0 = std::chrono::steady_clock::now();
     int rc = rb_host_part(probs, count, h);
     if (rc) return rc;
-    const size_t M = (size_t)h->M, N = (size_t)h->N;
+    const size_t M = (size_t)h->M;
     hvec<int8_t> sgn(2 * M);                           // Build_Amatrix.m:10 per CSR slot: -1 at the smaller endpoint i, +1 at j
     for (int32_t b = 0; b < count; ++b) {
         const int32_t* rp = h->rowptr.data() + h->node_off[(size_t)b] + b;
@@ -192,12 +249,7 @@ int rb_create(const desc_problem* probs, int32_t count, int32_t device, desc_ref
         (rc = h->upload(&h->d_sgn, sgn.data(), 2 * M)) || (rc = h->upload(&h->d_ii, h->ii.data(), M)) ||
         (rc = h->upload(&h->d_jj, h->jj.data(), M)) || (rc = h->upload(&h->d_rij, rij.data(), 9 * M)))
         return rc;
-    if ((rc = h->mem.alloc(&h->d_S, M)) || (rc = h->mem.alloc(&h->d_thresh0, (size_t)count)) || (rc = h->mem.alloc(&h->d_Rinit, 9 * N)) ||
-        (rc = h->mem.alloc(&h->d_Rout, 9 * N)) || (rc = h->mem.alloc(&h->d_QQ, M)) || (rc = h->mem.alloc(&h->d_B, 3 * M)) ||
-        (rc = h->mem.alloc(&h->d_w, M)) || (rc = h->mem.alloc(&h->d_RS, M)) || (rc = h->mem.alloc(&h->d_info, (size_t)count)))
-        return rc;
-    // the largest dynamic LDS any handle may ask for: the attribute belongs to the kernel, not to a handle, so it is never lowered
-    DESC_HIP(hipFuncSetAttribute((const void*)k_refine_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rb_lds_bytes(REFINE_BATCH_MAX_N)));
+    if ((rc = rb_alloc_work(h))) return rc;
     DESC_HIP(hipStreamSynchronize(h->stream));         // the staging vectors go out of scope below
     h->ms_upload = ms_since(t1);
     return DESC_OK;
@@ -279,6 +331,17 @@ int32_t desc_refine_batch_max_n(void) { return REFINE_BATCH_MAX_N; }
 
 int desc_refine_batch_create(const desc_problem* probs, int32_t count, int32_t device, desc_refine_batch** out) {
     return batch_create_guarded("desc_refine_batch_create", out, probs, count, [&](desc_refine_batch* h) { return rb_create(probs, count, device, h); });
+}
+
+int desc_refine_batch_create_on(desc_problem_batch* set, desc_refine_batch** out) {
+    return batch_create_guarded("desc_refine_batch_create_on", out, set, 0, [&](desc_refine_batch* h) { return rb_create_on(set->s, h); }, set != nullptr);
+}
+
+int desc_refine_batch_bytes(const desc_refine_batch* h, int64_t* h2d, int64_t* d2h) {
+    if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
+    if (h2d) *h2d = h->bytes_h2d;
+    if (d2h) *d2h = h->bytes_d2h;
+    return DESC_OK;
 }
 
 int desc_refine_batch_sizes(const desc_refine_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off) {

@@ -212,11 +212,15 @@ def _check_totals(specs):
             raise ValueError(f"the batch is expected to draw 2^30 edges or more at problem {b} (152 bytes each): split the batch")
 
 
-def _draw_batch(specs, device, return_info):
+def _draw_batch(specs, device, return_info, resident=False):
     from . import _lib
     _check_totals(specs)
     if not isinstance(device, (int, np.integer)) or isinstance(device, bool) or device < 0:
         raise ValueError("device must be a non-negative integer")
+    if resident:                                     # the problems stay on the device: no rotation is copied back
+        from .algorithms import ProblemBatch
+        pset, timings = ProblemBatch._from_models(specs, int(device))
+        return (pset, timings) if return_info else pset
     if not specs:                                    # the empty batch touches no device
         timings = {name: 0.0 for name, _ in _lib.ModelsBatchTimings._fields_}
         return ([], timings) if return_info else []
@@ -239,14 +243,19 @@ def _draw_batch(specs, device, return_info):
     return (models, timings) if return_info else models
 
 
-def Uniform_Topology_batch(n, p, q, sigma, model="uniform", *, seeds, device=0, return_info=False):
+def Uniform_Topology_batch(n, p, q, sigma, model="uniform", *, seeds, device=0, return_info=False, resident=False):
     """B = len(seeds) problems of Models/Uniform_Topology.m:24-101 drawn on the GPU in one pass.
 
     ``seeds``: a sequence of B integers; every other argument a scalar or a sequence of B values.  ``model``: 'uniform', any other
     string the self-consistent branch (as ``Uniform_Topology``).  Returns a list of B models with the fields and layouts of
     ``Uniform_Topology`` plus ``seed``; every ``*_batch`` solver takes them unchanged.  Problem b depends on its own arguments and seed
     only.  The draws are those of the definition in include/desc_amd.h, not the NumPy generator's for the same seed.  With
-    ``return_info`` the call returns ``(models, timings)``: ms_graph, ms_nodes, ms_edges, ms_copy, ms_total."""
+    ``return_info`` the call returns ``(models, timings)``: ms_graph, ms_nodes, ms_edges, ms_copy, ms_total.
+
+    ``resident=True`` returns a ``ProblemBatch`` in place of the list: the same B models as its items, the problems already on the
+    device for every ``*_batch`` call (desc_problem_batch_from_models).  ``n``, ``seed``, ``Ind``, ``ErrVec``, ``R_orig`` and
+    ``corrupted`` are fetched once; ``RijMat``, ``Rij_orig`` and ``AdjMat`` on first access.  A problem that drew no edge is refused
+    (ValueError naming it)."""
     from . import _lib
     seeds = _batch_seeds(seeds)
     B = len(seeds)
@@ -259,13 +268,13 @@ def Uniform_Topology_batch(n, p, q, sigma, model="uniform", *, seeds, device=0, 
         specs.append(_lib.ModelSpec(kind=_lib.MODELS_KIND_UNIFORM, n=_check_n(b, nb, cap), p=_check_probability(b, "p", pb),
                                     q=_check_probability(b, "q", qb), sigma=_check_sigma(b, "sigma", sb),
                                     mode=_lib.MODELS_UNIFORM if mb == "uniform" else _lib.MODELS_SELF_CONSISTENT, seed=seeds[b]))
-    return _draw_batch(specs, device, return_info)
+    return _draw_batch(specs, device, return_info, resident)
 
 
 def Nonuniform_Topology_batch(n, p, p_node_crpt, p_edge_crpt, sigma_in, sigma_out, crpt_type="uniform", *, seeds, device=0,
-                              return_info=False):
+                              return_info=False, resident=False):
     """B = len(seeds) problems of Models/Nonuniform_Topology.m:26-147 drawn on the GPU in one pass; arguments and result as
-    ``Uniform_Topology_batch``.  ``crpt_type``: 'uniform' | 'self-consistent' | 'adv'.  The two ``randperm``s are keyed selections: the
+    ``Uniform_Topology_batch`` (``resident`` included).  ``crpt_type``: 'uniform' | 'self-consistent' | 'adv'.  The two ``randperm``s are keyed selections: the
     corrupted nodes are the floor(n p_node_crpt) nodes with the smallest node keys, node i corrupts the floor(p_edge_crpt deg_i)
     incident edges with the smallest (i, edge) keys, and an edge both endpoints selected belongs to the endpoint with the larger
     node key."""
@@ -283,4 +292,4 @@ def Nonuniform_Topology_batch(n, p, p_node_crpt, p_edge_crpt, sigma_in, sigma_ou
                                     p_node_crpt=_check_probability(b, "p_node_crpt", pn),
                                     p_edge_crpt=_check_probability(b, "p_edge_crpt", pe), sigma_in=_check_sigma(b, "sigma_in", si),
                                     sigma_out=_check_sigma(b, "sigma_out", so), mode=_CRPT_MODES[ct], seed=seeds[b]))
-    return _draw_batch(specs, device, return_info)
+    return _draw_batch(specs, device, return_info, resident)

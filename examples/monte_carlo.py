@@ -3,11 +3,16 @@
 of Uniform_Topology(100, 0.5, q, 0.1) -- the shape of the figures the DESC paper draws (error against q on graphs of 100-200 nodes).
 
     python examples/monte_carlo.py [--trials 5] [--n 100] [--iters 100] [--build host|device] [--rotations] [--refined] [--baselines]
-                                   [--mpls] [--lp] [--irls] [--device-models] [--eig lds|streamed|auto]
+                                   [--mpls] [--lp] [--irls] [--device-models] [--resident] [--eig lds|streamed|auto]
 
 --device-models: the trials are drawn on the GPU by one Uniform_Topology_batch call instead of one Uniform_Topology call per trial on the
 host.  The batched generator has streams of its own: the curves differ from an unflagged run in their draws, not in their distribution.
 The time the generation took is printed in both modes.
+
+--resident: the trials become ONE ProblemBatch -- validated, laid out and uploaded once -- and every selected curve runs on it: with
+--device-models the generator hands its problems over on the device (no rotation is copied back before a curve asks for it), otherwise
+the host-drawn trials are wrapped.  The DESC curves create their handles on the set; the other curves read its host mirror.  The curves
+are the same to the last bit as without the flag.
 
 --build: the builder of the cycle structures behind DESC_PGD_batch / DESC_init_batch / DESC_batch: per problem on host threads (the
 default) or for the whole batch on the device; the curves are the same to the last bit.
@@ -43,8 +48,8 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from desc_amd import (CEMP_GCW_batch, CEMP_MST_batch, CEMP_batch, ConstantStepSize, DESC_PGD_batch, DESC_batch,  # noqa: E402
-                      DESC_init_batch, IRLS_GM_batch, IRLS_L12_batch, MPLS_batch, Rotation_Alignment_batch, Uniform_Topology, Uniform_Topology_batch,
-                      linprog_sij_batch)
+                      DESC_init_batch, IRLS_GM_batch, IRLS_L12_batch, MPLS_batch, ProblemBatch, Rotation_Alignment_batch, Uniform_Topology,
+                      Uniform_Topology_batch, linprog_sij_batch)
 
 
 def score(curves, models, shape):
@@ -151,6 +156,7 @@ def main():
     ap.add_argument("--lp", action="store_true", help="the linprog_sij curve: one linprog_sij_batch call")
     ap.add_argument("--irls", action="store_true", help="the IRLS-GM and IRLS-L0.5 curves: one IRLS_GM_batch and one IRLS_L12_batch call")
     ap.add_argument("--device-models", action="store_true", help="draw the trials on the GPU: one Uniform_Topology_batch call")
+    ap.add_argument("--resident", action="store_true", help="one ProblemBatch for every curve: the problems stay on the GPU across the calls")
     ap.add_argument("--eig", choices=("lds", "streamed", "auto"), default="lds",
                     help="the batched eigen-solve's blocks: in LDS (up to 278 nodes), streamed through LDS, or by each problem's size")
     a = ap.parse_args()
@@ -158,11 +164,18 @@ def main():
     t0 = time.perf_counter()
     if a.device_models:
         models = Uniform_Topology_batch(a.n, 0.5, [q for q in qs for _ in range(a.trials)], 0.1, "uniform",
-                                        seeds=[1000 * k + t for k in range(len(qs)) for t in range(a.trials)])
+                                        seeds=[1000 * k + t for k in range(len(qs)) for t in range(a.trials)], resident=a.resident)
     else:
         models = [Uniform_Topology(a.n, 0.5, q, 0.1, "uniform", seed=1000 * k + t) for k, q in enumerate(qs) for t in range(a.trials)]
     print(f"{len(models)} problems drawn by " + ("one Uniform_Topology_batch call" if a.device_models else f"{len(models)} Uniform_Topology calls on the host")
           + f": {(time.perf_counter() - t0) * 1e3:.1f} ms")
+    if a.resident:
+        if not a.device_models:
+            t0 = time.perf_counter()
+            models = ProblemBatch(models)
+            print(f"wrapped as one ProblemBatch (marshalled, laid out, uploaded once): {(time.perf_counter() - t0) * 1e3:.1f} ms")
+        up, down = models.bytes()
+        print(f"the resident set copied {up} bytes to the device and {down} bytes back")
     params = dict(iters=a.iters, Gradient=ConstantStepSize(0.01), seed=0, verbose=False)
     if a.refined:
         t0 = time.perf_counter()

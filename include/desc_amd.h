@@ -1002,6 +1002,46 @@ void desc_align_batch_destroy(desc_align_batch* h);
  * only), one thread per block.  NULL A or R, or a negative count: DESC_ERR_INVALID. */
 int desc_test_align_project(const double* A, int64_t count, int32_t device, double* R);
 
+/* A problem set resident on the device across calls: the problems of B independent instances validated, laid out and uploaded ONCE, for
+ * every batched handle created on it.  On the device: ii, jj (local 0-based endpoints, M entries), rowptr (problem b's n_b + 1 entries
+ * at node_off[b] + b), adj and adj_eid (problem b's 2 m_b entries at 2 edge_off[b], local ids), rij (9 M doubles, column-major blocks)
+ * -- the layout the batched handles make for themselves.  On the host: the sizes, the offsets, ii and jj; the CSR only where the host
+ * builder made it.  After create the arrays are read-only.
+ * desc_problem_batch_create: refuses what desc_gcw_batch_create refuses of a problem, in its words and order ("problem b: ...", an empty
+ * edge list, 2^30 edges in total), before any device work.  csr_where = DESC_BUILD_HOST builds the CSR on host threads and uploads it;
+ * DESC_BUILD_DEVICE uploads ii and jj and builds the same CSR, element for element, in one launch (one workgroup per problem, integer
+ * arithmetic only, no atomics; it has no size cap).  count == 0 is legal and touches no device.
+ * desc_problem_batch_from_models: the set of a generator handle without a host copy of any rotation.  Runs the generator's node and
+ * edge passes if no fetch has; copies ii, jj and rij device to device (the models handle may be destroyed first); n_b = the largest
+ * endpoint + 1 (what marshalling the fetched list gives, not the spec's n); a problem that drew no edge is refused (DESC_ERR_INVALID,
+ * "problem b: empty edge list"); the CSR is built on the device.  Device-to-host traffic: ii and jj (8 bytes per edge).
+ * desc_problem_batch_fetch: each argument nullable; ii / jj from the host mirror, rij and a device-built CSR come down.
+ * desc_problem_batch_built_where: the builder of the set's CSR.  desc_problem_batch_bytes: what the set copied up and down so far.
+ * desc_problem_batch_destroy drops the caller's reference: handles created on the set keep it alive, the memory goes with the last owner.
+ *
+ * desc_gcw_batch_create_on / desc_refine_batch_create_on / desc_pgd_batch_create_on: the handle of desc_*_batch_create(_where) on the
+ * set's device, borrowing the set's device arrays.  Each refuses what its create refuses (the caps, eig, where: same words, before any
+ * device work); what create derives from the CSR is formed on the device (the refinement's sign per slot, the device builder's edge ->
+ * problem map), so the uploads of a create_on are O(B) bytes.  desc_pgd_batch_create_on takes either builder (the host builder reads
+ * the set's host ii / jj; p->device is not read); the device builder's silent fallback is unchanged.  The run functions are unchanged
+ * and give the bits of a handle created from the host arrays.  desc_*_batch_bytes: the bytes a handle's creates copied up / down. */
+typedef struct desc_problem_batch desc_problem_batch;   /* opaque */
+int desc_problem_batch_create(const desc_problem* probs, int32_t count, int32_t device, int32_t csr_where /* DESC_BUILD_HOST | DESC_BUILD_DEVICE */,
+                              desc_problem_batch** out);
+int desc_problem_batch_from_models(desc_models_batch* m, desc_problem_batch** out);
+int desc_problem_batch_sizes(const desc_problem_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off);
+int desc_problem_batch_fetch(desc_problem_batch* h, int32_t* ind_i, int32_t* ind_j, double* rij, int32_t* rowptr, int32_t* adj, int32_t* adj_eid);
+int32_t desc_problem_batch_built_where(const desc_problem_batch* h);
+int desc_problem_batch_bytes(const desc_problem_batch* h, int64_t* h2d, int64_t* d2h);
+void desc_problem_batch_destroy(desc_problem_batch* h);
+int desc_gcw_batch_create_on(desc_problem_batch* set, int32_t eig, desc_gcw_batch** out);
+int desc_refine_batch_create_on(desc_problem_batch* set, desc_refine_batch** out);
+int desc_pgd_batch_create_on(desc_problem_batch* set, const desc_params* p, const uint64_t* seeds /* count, nullable */, int32_t where,
+                             desc_pgd_batch** out);
+int desc_gcw_batch_bytes(const desc_gcw_batch* h, int64_t* h2d, int64_t* d2h);
+int desc_refine_batch_bytes(const desc_refine_batch* h, int64_t* h2d, int64_t* d2h);
+int desc_pgd_batch_bytes(const desc_pgd_batch* h, int64_t* h2d, int64_t* d2h);
+
 /* One-shot: what the MEX shim calls.  Builds the structure (p->build_where),
  * uploads, runs, downloads, frees. */
 int desc_pgd_solve(const desc_problem* prob, const desc_params* p, desc_result* r);
