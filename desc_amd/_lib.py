@@ -53,6 +53,7 @@ EXPORTS = [
     "desc_problem_batch_built_where", "desc_problem_batch_bytes", "desc_problem_batch_destroy",
     "desc_gcw_batch_create_on", "desc_refine_batch_create_on", "desc_pgd_batch_create_on",
     "desc_gcw_batch_bytes", "desc_refine_batch_bytes", "desc_pgd_batch_bytes",
+    "desc_cemp_batch_create_on", "desc_irls_batch_create_on", "desc_mst_batch_run_on", "desc_cemp_batch_bytes", "desc_irls_batch_bytes",
     "desc_test_laa_r2q", "desc_test_laa_q2r", "desc_test_laa_edge_log", "desc_test_laa_rhs", "desc_test_laa_pcg", "desc_test_laa_node_update",
     "desc_test_irls_node_update", "desc_test_laa_weights", "desc_test_irls_weights", "desc_test_laa_quantile", "desc_test_irls_project",
     "desc_test_irls_pd_stage", "desc_test_irls_pd_solve",
@@ -428,7 +429,10 @@ def load():
     L.desc_gcw_batch_create_on.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
     L.desc_refine_batch_create_on.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.desc_pgd_batch_create_on.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_void_p)]
-    for kind in ("problem", "gcw", "refine", "pgd"):
+    L.desc_cemp_batch_create_on.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_void_p)]
+    L.desc_irls_batch_create_on.argtypes = [C.c_void_p, C.POINTER(I32P), C.POINTER(C.c_void_p)]
+    L.desc_mst_batch_run_on.argtypes = [C.c_void_p, F64P, F64P, I32P, C.POINTER(MstBatchTimings), I64P]
+    for kind in ("problem", "gcw", "refine", "pgd", "cemp", "irls"):
         getattr(L, f"desc_{kind}_batch_bytes").argtypes = [C.c_void_p, I64P, I64P]
     L.desc_test_laa_r2q.argtypes = [F64P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, F64P]
     L.desc_test_laa_q2r.argtypes = [F64P, C.c_int64, C.c_int32, F64P]
@@ -841,14 +845,17 @@ def cemp_batch_max_degree():
 class CempBatch(_BatchHandle):
     """Owner of a desc_cemp_batch*: CEMP on B small problems in one GPU pass (desc_cemp_batch_*).  ``probs`` is a sequence of
     ProblemArrays; ``seeds`` an optional sequence of per-problem sampling seeds.  Sampling, S0 and the initial means are computed here;
-    the handle may be run any number of times."""
+    the handle may be run any number of times.  ``on``: a resident ProblemBatch to create the handle on (desc_cemp_batch_create_on)."""
 
     _kind = "cemp"
 
-    def __init__(self, probs, nsample, seed=0, seeds=None, device=0):
-        probs = list(probs)
+    def __init__(self, probs, nsample, seed=0, seeds=None, device=0, on=None):
         self.nsample = int(nsample)
-        self._open(probs, self.nsample, int(seed), _seeds_array(seeds, len(probs)), int(device))
+        if on is not None:                           # a resident ProblemBatch: probs and device are not read
+            self._open_on(on, self.nsample, int(seed), _seeds_array(seeds, len(on)))
+        else:
+            probs = list(probs)
+            self._open(probs, self.nsample, int(seed), _seeds_array(seeds, len(probs)), int(device))
 
     def samples(self):
         """What create sampled, per problem: a list of dicts e_jk / e_ki (m_b x nsample local edge ids, -1 without a cycle), s0
@@ -905,7 +912,8 @@ def mst_batch_max_n():
 
 
 def mst_batch_check(probs):
-    """desc_mst_batch_check on a sequence of ProblemArrays: the size cap and connectivity of every problem (host only; raises DescError)."""
+    """desc_mst_batch_check on a sequence of ProblemArrays: the size cap and connectivity of every problem (host only; raises DescError).
+    The rotations are not read: index-only problems (a ProblemBatch's mirror) are taken."""
     probs = list(probs)
     check(load().desc_mst_batch_check(_problem_array(probs), len(probs)))
 
@@ -925,6 +933,25 @@ def mst_batch_run(probs, s_vec, device=0):
     tm = MstBatchTimings()
     check(load().desc_mst_batch_run(arr, B, ptr(S, F64P), int(device), ptr(R, F64P), ptr(T, I32P), C.byref(tm)))
     outs = [(Rb, T[int(no[b]) - b:int(no[b + 1]) - b - 1].copy()) for b, Rb in enumerate(_split_R(R, no))]
+    return outs, _timings(tm)
+
+
+def mst_batch_run_on(pset, s_vec, return_bytes=False):
+    """desc_mst_batch_run_on: mst_batch_run on a resident ProblemBatch, on its device.  ``return_bytes``: also the call's (h2d, d2h)."""
+    if not pset.handle:
+        raise ValueError("the ProblemBatch is closed")
+    B, no = len(pset), pset.node_off
+    S = np.ascontiguousarray(s_vec, dtype=np.float64).reshape(-1)
+    if S.size != pset.m:
+        raise ValueError("s_vec must hold one entry per edge of the batch")
+    R = out_buffer(9 * int(no[B]))
+    T = out_buffer(max(int(no[B]) - B, 1), np.int32)
+    tm = MstBatchTimings()
+    moved = np.zeros(2, dtype=np.int64)
+    check(load().desc_mst_batch_run_on(pset.handle, ptr(S, F64P), ptr(R, F64P), ptr(T, I32P), C.byref(tm), ptr(moved, I64P)))
+    outs = [(Rb, T[int(no[b]) - b:int(no[b + 1]) - b - 1].copy()) for b, Rb in enumerate(_split_R(R, no))]
+    if return_bytes:
+        return outs, _timings(tm), (int(moved[0]), int(moved[1]))
     return outs, _timings(tm)
 
 
@@ -993,12 +1020,12 @@ def irls_tree_sequence(prob, order=None):
 class IrlsBatch(_BatchHandle):
     """Owner of a desc_irls_batch*: IRLS_GM / IRLS_L12 of B small connected problems in two launches (desc_irls_batch_*).  ``probs`` is a
     sequence of ProblemArrays, ``orders`` an optional sequence of per-problem row orders (marshal_edges' perm, or None).  The handle may
-    be run any number of times, in either mode."""
+    be run any number of times, in either mode.  ``on``: a resident ProblemBatch to create the handle on (desc_irls_batch_create_on)."""
 
     _kind = "irls"
 
-    def __init__(self, probs, orders=None, device=0):
-        probs = list(probs)
+    def __init__(self, probs, orders=None, device=0, on=None):
+        probs = on.probs if on is not None else list(probs)          # a resident ProblemBatch: its index mirror gives the sizes
         B = len(probs)
         arr = None
         if orders is not None:
@@ -1009,7 +1036,10 @@ class IrlsBatch(_BatchHandle):
                 if o is not None and o.size != q.m:
                     raise ValueError("an order must have one entry per edge of its problem")
             arr = (I32P * max(B, 1))(*[ptr(o, I32P) for o in self._orders])
-        self._open(probs, arr, int(device))
+        if on is not None:
+            self._open_on(on, arr)
+        else:
+            self._open(probs, arr, int(device))
 
     def run(self, mode, sigma_deg=5.0, max_iter_l1=10, max_iter_irls=100):
         """One batched run -> a list of per-problem (R, R_l1 (3,3,n_b) Fortran-ordered, info dict with irls_run's keys) and the call's

@@ -328,8 +328,10 @@ class _ResidentModel:
 class ProblemBatch(collections.abc.Sequence):
     """The problems of a study, validated, laid out and uploaded to the GPU once (desc_problem_batch_*): every ``*_batch`` call takes a
     ProblemBatch where it takes a list of problems, and gives the same bits.  Spectral_batch, GCW_batch, DESC_refine_batch,
-    DESC_PGD_batch, DESC_init_batch and DESC_batch create their handles ON the set -- no marshalling, no validation, no CSR build and no
-    72-byte-per-edge upload per call; the other families read the set's host mirror and save the marshalling.
+    DESC_PGD_batch, DESC_init_batch, DESC_batch, CEMP_batch, CEMP_GCW_batch, MST_batch, CEMP_MST_batch, MPLS_batch, IRLS_GM_batch and
+    IRLS_L12_batch create their handles ON the set -- no marshalling, no validation, no CSR build and no 72-byte-per-edge upload per
+    call, and no rotation of a generated set comes down to the host (MST_batch fetches the 72-byte blocks of its n_b - 1 tree edges).
+    linprog_sij_batch alone reads the set's host mirror (its plan is a host codegree merge) and saves the marshalling.
 
     ``problems`` as for DESC_PGD_batch; ``device`` the GPU the set lives on (a call whose ``device`` / ``params.device`` differs is
     refused); ``csr``: ``"host"`` builds the per-problem CSR on host threads, ``"device"`` builds the same arrays in one launch.
@@ -762,6 +764,11 @@ def _check_mst_batch(probs):
         _lib.mst_batch_check(probs)
 
 
+def _mst_batch_run(probs, S, device, pset=None):
+    """The batched tree step on a list of ProblemArrays, or on the resident set ``pset`` they mirror."""
+    return _lib.mst_batch_run_on(pset, S) if pset is not None else _lib.mst_batch_run(probs, S, device)
+
+
 def _unsort(S, perm):
     if perm is None:
         return S
@@ -770,7 +777,7 @@ def _unsort(S, perm):
     return out
 
 
-def CEMP_batch(problems, CEMP_parameters, seeds=None, return_info=False):
+def CEMP_batch(problems, CEMP_parameters, seeds=None, return_info=False, _set=None):
     """CEMP (Algorithms/CEMP.m:24) on B independent small problems in one GPU pass (desc_cemp_batch_*; the reference has no such call).
 
     ``problems`` as for DESC_PGD_batch; one ``CEMP_parameters`` for the whole batch (``max_iter``, ``reweighting``, ``nsample``, optional
@@ -783,12 +790,12 @@ def CEMP_batch(problems, CEMP_parameters, seeds=None, return_info=False):
     ``_lib.cemp_batch_max_degree()`` (solve that problem with CEMP)."""
     _check_sequence(problems)
     beta, max_iter, nsample, seed, device, seeds = _cemp_batch_params(CEMP_parameters, len(problems), seeds)
-    _resident(problems, device)                      # a set on another device is refused; the call reads its host mirror
-    probs, perms = _marshal_problems(problems)
+    pset = _set if _set is not None else _resident(problems, device)
+    probs, perms = _marshal_problems(problems, rotations=pset is None)
     if not probs:
         return []
     _check_cemp_batch_degrees(probs)
-    with _batch_handle(_lib.CempBatch, probs, nsample, seed, seeds, device) as batch:
+    with _batch_handle(_lib.CempBatch, probs, nsample, seed, seeds, device, on=pset) as batch:
         outs, timings = batch.run(beta, max_iter)
     S = [_unsort(o, perm) for o, perm in zip(outs, perms)]
     return [(s, dict(timings=timings)) for s in S] if return_info else S
@@ -803,22 +810,23 @@ def CEMP_GCW_batch(problems, CEMP_parameters, seeds=None, return_info=False, eig
     ``"auto"``, and a problem of more nodes than the cap of ``eig`` (``_lib.gcw_batch_max_n()`` by default; solve it with CEMP_GCW)."""
     _check_eig(eig)
     _check_sequence(problems)
-    _cemp_batch_params(CEMP_parameters, len(problems), seeds)
-    probs, perms = _marshal_problems(problems)
+    device = _cemp_batch_params(CEMP_parameters, len(problems), seeds)[4]
+    pset = _resident(problems, device)
+    probs, perms = _marshal_problems(problems, rotations=pset is None)
     if not probs:
         return []
     _check_cemp_batch_degrees(probs)
     _check_gcw_batch_sizes(probs, eig)
-    cemp = CEMP_batch([_Marshalled(q, perm) for q, perm in zip(probs, perms)], CEMP_parameters, seeds=seeds, return_info=True)
+    cemp = CEMP_batch([_Marshalled(q, perm) for q, perm in zip(probs, perms)], CEMP_parameters, seeds=seeds, return_info=True, _set=pset)
     # CEMP_batch gave SVec in the caller's order; the eigen-solve takes the library's
     w = np.concatenate([1.0 / ((S if perm is None else S[perm]) + 1e-8) for (S, _), perm in zip(cemp, perms)])      # CEMP_GCW.m:144
-    outs, timings = _gcw_batch_run(probs, int(_get(CEMP_parameters, "device", 0)), eig, weights=w, normalize_rows=True)
+    outs, timings = _gcw_batch_run(probs, device, eig, pset, weights=w, normalize_rows=True)
     if return_info:
         return [(R, S, dict(cemp=ci, gcw=dict(info, timings=timings))) for (R, info), (S, ci) in zip(outs, cemp)]
     return [R for R, _ in outs]
 
 
-def MST_batch(problems, S_list, device=0, return_info=False):
+def MST_batch(problems, S_list, device=0, return_info=False, _set=None):
     """The tree step of MPLS (Algorithms/MPLS.m:160-193, as MST()) on B independent small problems in one GPU launch
     (desc_mst_batch_run): ``S_list[b]`` is problem b's SVec in the caller's edge order.  Returns a list of R (3 x 3 x n_b): entry b is
     bit for bit ``MST(Ind_b, RijMat_b, S_b)``.  With ``return_info`` a list of (R, dict(tree_edges=..., timings=...)), ``tree_edges`` the
@@ -827,15 +835,15 @@ def MST_batch(problems, S_list, device=0, return_info=False):
     the wrong size or holding a non-finite value, a problem of more than ``_lib.mst_batch_max_n()`` nodes (solve it with MST), a
     disconnected problem (a node id in 1..max(Ind) that no edge touches counts as a component)."""
     _check_sequence(problems)
-    _resident(problems, device)
-    probs, perms = _marshal_problems(problems)
+    pset = _set if _set is not None else _resident(problems, device)
+    probs, perms = _marshal_problems(problems, rotations=pset is None)
     S = _sorted_s_list(probs, perms, S_list, "SVec", np.isfinite,
                        lambda q, perm, t: f"SVec entry {int(t if perm is None else perm[t])} is not finite")
     if not probs:
         return []
     _check_mst_batch(probs)
     with _invalid_as_value_error():
-        outs, timings = _lib.mst_batch_run(probs, S, device)
+        outs, timings = _mst_batch_run(probs, S, device, pset)
     if not return_info:
         return [R for R, _ in outs]
     return [(R, dict(tree_edges=tree if perm is None else np.sort(perm[tree]), timings=timings)) for (R, tree), perm in zip(outs, perms)]
@@ -846,15 +854,16 @@ def CEMP_MST_batch(problems, CEMP_parameters, seeds=None, return_info=False):
     CEMP_batch, then MST_batch on its SVec.  Returns a list of R_init (3 x 3 x n_b); with ``return_info`` a list of
     (R_init, SVec, dict(cemp=..., mst=...)).  Refused (ValueError, before the device is touched): what CEMP_batch and MST_batch refuse."""
     _check_sequence(problems)
-    _cemp_batch_params(CEMP_parameters, len(problems), seeds)
-    probs, perms = _marshal_problems(problems)
+    device = _cemp_batch_params(CEMP_parameters, len(problems), seeds)[4]
+    pset = _resident(problems, device)
+    probs, perms = _marshal_problems(problems, rotations=pset is None)
     if not probs:
         return []
     _check_cemp_batch_degrees(probs)
     _check_mst_batch(probs)
     marshalled = [_Marshalled(q, perm) for q, perm in zip(probs, perms)]
-    cemp = CEMP_batch(marshalled, CEMP_parameters, seeds=seeds, return_info=True)
-    mst = MST_batch(marshalled, [S for S, _ in cemp], device=int(_get(CEMP_parameters, "device", 0)), return_info=True)
+    cemp = CEMP_batch(marshalled, CEMP_parameters, seeds=seeds, return_info=True, _set=pset)
+    mst = MST_batch(marshalled, [S for S, _ in cemp], device=device, return_info=True, _set=pset)
     if return_info:
         return [(R, S, dict(cemp=ci, mst=mi)) for (R, mi), (S, ci) in zip(mst, cemp)]
     return [R for R, _ in mst]
@@ -892,18 +901,18 @@ def MPLS_batch(problems, CEMP_parameters, MPLS_parameters, seeds=None, return_in
     _check_sequence(problems)
     cemp_beta, cemp_max_iter, nsample, seed, device, seeds = _cemp_batch_params(CEMP_parameters, len(problems), seeds)
     stop_threshold, max_iter, beta, tau, alpha = _mpls_batch_params(MPLS_parameters)
-    _resident(problems, device)
-    probs, perms = _marshal_problems(problems)
+    pset = _resident(problems, device)
+    probs, perms = _marshal_problems(problems, rotations=pset is None)
     if not probs:
         return []
     _check_cemp_batch_degrees(probs)
     _check_mst_batch(probs)
     _check_batch_sizes(probs, _lib.mpls_batch_max_n(), "per-node state of the MPLS loop", "MPLS")
-    with _batch_handle(_lib.CempBatch, probs, nsample, seed, seeds, device) as batch:
+    with _batch_handle(_lib.CempBatch, probs, nsample, seed, seeds, device, on=pset) as batch:
         S_list, cemp_tm = batch.run(cemp_beta, cemp_max_iter)
         S = np.concatenate(S_list)                                   # the library's edge order, as both later passes take it
         with _invalid_as_value_error():
-            mst, mst_tm = _lib.mst_batch_run(probs, S, device)
+            mst, mst_tm = _mst_batch_run(probs, S, device, pset)
             R0 = np.concatenate([R.reshape(-1, order="F") for R, _ in mst])
             outs, mpls_tm = batch.mpls_run(S, R0, stop_threshold, max_iter, beta, tau, alpha)
     if not return_info:
@@ -920,8 +929,9 @@ def _irls_batch(mode, name, problems, SIGMA, MaxIterations, device, return_info)
     if mi.size != 2:
         raise ValueError("MaxIterations must have two entries [L1, IRLS]")
     sigma = 5.0 if SIGMA is None or np.size(SIGMA) == 0 else float(SIGMA)
-    _resident(problems, device)
-    for b, item in enumerate(problems):
+    pset = _resident(problems, device)
+    # a set holds 3 x 3 x m blocks by construction: its items' RijMat (a fetch, for a generated set) is not touched
+    for b, item in enumerate(problems if pset is None else ()):
         if isinstance(item, _Marshalled):
             continue
         try:
@@ -930,7 +940,7 @@ def _irls_batch(mode, name, problems, SIGMA, MaxIterations, device, return_info)
             continue                                                 # _marshal_problems has the words for it
         if R.ndim == 2 and R.shape[0] == 4:
             raise ValueError(f"problem {b}: the quaternion form of RR (4 x m) is not supported: pass RijMat as 3 x 3 x m rotation matrices")
-    probs, perms = _marshal_problems(problems)
+    probs, perms = _marshal_problems(problems, rotations=pset is None)
     if not probs:
         return []
     single = "IRLS_GM / IRLS_L12"
@@ -940,7 +950,7 @@ def _irls_batch(mode, name, problems, SIGMA, MaxIterations, device, return_info)
             reached = _lib.irls_tree_sequence(q, perm)[2]
         if reached < q.n:
             raise ValueError(f"problem {b}: the graph is not connected ({reached} of {q.n} nodes reached from node 1): solve it with {single}")
-    with _batch_handle(_lib.IrlsBatch, probs, perms, int(device)) as batch:
+    with _batch_handle(_lib.IrlsBatch, probs, perms, int(device), on=pset) as batch:
         outs, timings = batch.run(mode, sigma, int(mi[0]), int(mi[1]))
     warned = [b for b, (_, _, info) in enumerate(outs) if info["warned_edges"]]
     if warned:

@@ -24,9 +24,10 @@ struct BatchCsr {
 int batch_csr_host(const desc_problem* probs, int32_t count, const std::function<int(int32_t, const desc_problem&)>& extra, BatchCsr* h,
                    bool allow_empty = false);
 // The first half of batch_csr_host alone -- its refusals in its order, the offsets, ii and jj -- for the caller whose CSR is built on
-// the device (problem_batch.hip).  Defined in gcw_batch.hip.
+// the device (problem_batch.hip), and, with need_rij = false, for the check that reads no rotation (desc_mst_batch_check).  Defined in
+// gcw_batch.hip.
 int batch_offsets_host(const desc_problem* probs, int32_t count, const std::function<int(int32_t, const desc_problem&)>& extra, BatchCsr* h,
-                       bool allow_empty = false);
+                       bool allow_empty = false, bool need_rij = true);
 
 // fn(b) for every problem, the problems dealt round-robin to 16 host threads at most (run_threads: exceptions reach the caller)
 template <class F>

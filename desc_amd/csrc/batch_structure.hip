@@ -31,6 +31,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "batch_kernels.h"
 #include "batch_structure.h"
 
 namespace desc {
@@ -230,13 +231,6 @@ __global__ __launch_bounds__(256) void k_bs_mirror(BsArgs a) {
 
 }  // namespace
 
-// the edge -> problem map of a batch that came without a host pass over its edges: one workgroup per problem fills its range
-__global__ __launch_bounds__(256) void k_bs_eprob(const CbProb* prob, int32_t* eprob) {
-    const int b = blockIdx.x;
-    const CbProb pd = prob[b];
-    for (int e = threadIdx.x; e < pd.m; e += 256) eprob[pd.edge_off + e] = b;
-}
-
 int batch_structure_device(BatchDevice* dev, const desc_problem* probs, int32_t count, int32_t n_sample_min, uint64_t seed,
                            const uint64_t* seeds, int32_t device, BatchBuilt* out, const PbSet* set) {
     // ---- host, O(m): validation (as the host path words it) and the per-problem CSR with local ids
@@ -287,7 +281,7 @@ int batch_structure_device(BatchDevice* dev, const desc_problem* probs, int32_t 
     } else {
         int32_t* d_eprob = nullptr;
         if ((rc = dev->mem.alloc(&d_eprob, M))) return rc;
-        hipLaunchKernelGGL(k_bs_eprob, dim3((unsigned)count), dim3(256), 0, dev->stream, a.prob, d_eprob);
+        hipLaunchKernelGGL(k_batch_eprob<CbProb>, dim3((unsigned)count), dim3(256), 0, dev->stream, a.prob, d_eprob);
         DESC_HIP(hipGetLastError());
         a.eprob = d_eprob; d_ii = set->d_ii; d_jj = set->d_jj; a.rowptr = set->d_rowptr; a.adj = set->d_adj; a.adj_eid = set->d_adj_eid;
     }

@@ -4,6 +4,7 @@
 #include "batch_csr.h"
 #include "batch_device.h"
 #include "laa_math.h"
+#include "problem_batch.h"
 
 namespace desc {
 
@@ -82,4 +83,6 @@ struct desc_cemp_batch : desc::BatchCsr, desc::BatchDevice {
     desc::CbArgs a{};
     double ms_build = 0;
     desc::MbLoop loop;
+    std::shared_ptr<desc::PbSet> set;         // desc_cemp_batch_create_on: the owner of the CSR, a.ii / a.jj and a.rij
+    ~desc_cemp_batch() { close(); }           // the stream drains before the set may go
 };

@@ -376,11 +376,11 @@ namespace desc {
 namespace {
 // the refusals and the offsets; ii and jj sized, not filled
 int batch_offsets_core(const desc_problem* probs, int32_t count, const std::function<int(int32_t, const desc_problem&)>& extra, BatchCsr* h,
-                       bool allow_empty) {
+                       bool allow_empty, bool need_rij = true) {
     h->count = count;
     h->node_off.assign((size_t)count + 1, 0); h->edge_off.assign((size_t)count + 1, 0);
     for (int32_t b = 0; b < count; ++b) {
-        int rc = validate_problem(&probs[b], true);
+        int rc = validate_problem(&probs[b], need_rij);
         if (rc) { const std::string msg = desc_last_error(); return fail(rc, "problem %d: %s", b, msg.c_str()); }
         if (probs[b].m == 0 && !allow_empty) return fail(DESC_ERR_INVALID, "problem %d: empty edge list", b);
         if (extra && (rc = extra(b, probs[b]))) return rc;
@@ -397,8 +397,8 @@ int batch_offsets_core(const desc_problem* probs, int32_t count, const std::func
 }  // namespace
 
 int batch_offsets_host(const desc_problem* probs, int32_t count, const std::function<int(int32_t, const desc_problem&)>& extra, BatchCsr* h,
-                       bool allow_empty) {
-    const int rc = batch_offsets_core(probs, count, extra, h, allow_empty);
+                       bool allow_empty, bool need_rij) {
+    const int rc = batch_offsets_core(probs, count, extra, h, allow_empty, need_rij);
     if (rc) return rc;
     for_each_problem(count, [&](int32_t b) {
         const int64_t m = probs[b].m, eo = h->edge_off[(size_t)b];

@@ -43,7 +43,9 @@
 
 #include "batch_csr.h"
 #include "batch_device.h"
+#include "batch_kernels.h"
 #include "irls_math.h"
+#include "problem_batch.h"
 #include "laa_wg.h"
 
 // A weak reference: the library loads next to a HIP runtime that lacks the call (the stand-in runtime of the host sanitizer test, which
@@ -405,6 +407,12 @@ __global__ __launch_bounds__(256) void k_irls_batch(IbArgs a) {
     }
 }
 
+// desc_irls_batch_create_on with identity orders: order[edge_off[b] + e] = e, the caller's row of every edge, without an upload
+__global__ __launch_bounds__(256) void k_irls_identity_order(const IbProb* prob, int32_t* order) {
+    const IbProb pd = prob[blockIdx.x];
+    for (int e = threadIdx.x; e < pd.m; e += 256) order[pd.edge_off + e] = e;
+}
+
 }  // namespace
 }  // namespace desc
 
@@ -421,6 +429,8 @@ struct desc_irls_batch : desc::BatchCsr, desc::BatchDevice {    // offsets and t
     double *d_rij = nullptr, *d_P = nullptr, *d_B = nullptr, *d_w = nullptr, *d_edge = nullptr, *d_Rl1 = nullptr, *d_Rout = nullptr, *d_einfo = nullptr;
     Quat* d_QQ = nullptr;
     IbInfo* d_info = nullptr;
+    std::shared_ptr<desc::PbSet> set;         // desc_irls_batch_create_on: the owner of d_prob, the CSR, d_ii / d_jj and d_rij
+    ~desc_irls_batch() { close(); }           // the stream drains before the set may go
 };
 
 namespace {
@@ -439,18 +449,20 @@ int ib_tree(const desc_problem& q, const int32_t* order, hvec<int32_t>& visit, h
     return DESC_OK;
 }
 
-// validation, offsets, the per-problem CSR and the tree sequences: no device
-int ib_host_part(const desc_problem* probs, int32_t count, const int32_t* const* orders, desc_irls_batch* h) {
-    int rc = batch_csr_host(probs, count, [](int32_t b, const desc_problem& q) -> int {
-        if (q.n > IRLS_BATCH_MAX_N)
-            return fail(DESC_ERR_INVALID, "problem %d: n = %lld exceeds %d (the per-node state of the L1 stage must fit the LDS of one workgroup): solve it with IRLS_GM / IRLS_L12",
-                        b, (long long)q.n, IRLS_BATCH_MAX_N);
-        return DESC_OK;
-    }, h);
-    if (rc) return rc;
+int ib_check_n(int32_t b, int64_t n) {
+    if (n > IRLS_BATCH_MAX_N)
+        return fail(DESC_ERR_INVALID, "problem %d: n = %lld exceeds %d (the per-node state of the L1 stage must fit the LDS of one workgroup): solve it with IRLS_GM / IRLS_L12",
+                    b, (long long)n, IRLS_BATCH_MAX_N);
+    return DESC_OK;
+}
+
+// The caller's row orders and the tree sequences of every problem into h->order / h->seq, h's offsets being set; probs[b] needs n, m and
+// the endpoints alone.  Refuses an order that is no permutation and a graph that is not connected.
+int ib_orders_and_trees(const desc_problem* probs, int32_t count, const int32_t* const* orders, desc_irls_batch* h) {
     h->order.resize((size_t)h->M);
     h->seq.assign((size_t)std::max<int64_t>(h->N - count, 1), 0);
     hvec<int32_t> visit, seq;
+    int rc;
     for (int32_t b = 0; b < count; ++b) {
         const int32_t* od = orders ? orders[b] : nullptr;
         int64_t reached = 0;
@@ -465,11 +477,96 @@ int ib_host_part(const desc_problem* probs, int32_t count, const int32_t* const*
     return DESC_OK;
 }
 
+// validation, offsets, the per-problem CSR and the tree sequences: no device
+int ib_host_part(const desc_problem* probs, int32_t count, const int32_t* const* orders, desc_irls_batch* h) {
+    int rc = batch_csr_host(probs, count, [](int32_t b, const desc_problem& q) -> int { return ib_check_n(b, q.n); }, h);
+    if (rc) return rc;
+    return ib_orders_and_trees(probs, count, orders, h);
+}
+
+void ib_flags0(desc_irls_batch* h) {
+    h->flags0.resize(2 * (size_t)h->count);
+    for (int32_t b = 0; b < h->count; ++b) { h->flags0[2 * (size_t)b] = INT_MAX; h->flags0[2 * (size_t)b + 1] = 0; }
+}
+
+// the kernel's fixed LDS against what was set aside for it: an error at create instead of a failed launch
+int ib_check_lds(const desc_irls_batch* h) {
+    hipFuncAttributes fa;
+    if (!&hipFuncGetAttributes) return fail(DESC_ERR_HIP, "the HIP runtime exports no hipFuncGetAttributes: the LDS budget of the batched IRLS cannot be checked");
+    DESC_HIP(hipFuncGetAttributes(&fa, (const void*)k_irls_batch));
+    if (fa.sharedSizeBytes > (size_t)IB_STATIC_BYTES || fa.sharedSizeBytes + ib_lds_bytes(h->max_n) > (size_t)RB_LDS_BYTES)
+        return fail(DESC_ERR_STATE, "LDS budget exceeded: %zu bytes fixed, %zu bytes for n = %d, %d allowed", (size_t)fa.sharedSizeBytes,
+                    ib_lds_bytes(h->max_n), (int)h->max_n, RB_LDS_BYTES);
+    return DESC_OK;
+}
+
+// the run's own buffers, the same behind either create; drains the stream
+int ib_alloc_work(desc_irls_batch* h) {
+    const size_t M = (size_t)h->M, N = (size_t)h->N, count = (size_t)h->count;
+    int rc;
+    if ((rc = h->mem.alloc(&h->d_P, 9 * M)) || (rc = h->mem.alloc(&h->d_QQ, M)) || (rc = h->mem.alloc(&h->d_B, 3 * M)) ||
+        (rc = h->mem.alloc(&h->d_w, M)) || (rc = h->mem.alloc(&h->d_edge, (size_t)IB_EDGE_ARRAYS * 3 * M)) || (rc = h->mem.alloc(&h->d_Rl1, 9 * N)) ||
+        (rc = h->mem.alloc(&h->d_Rout, 9 * N)) || (rc = h->mem.alloc(&h->d_info, count)) || (rc = h->mem.alloc(&h->d_flags, 2 * count)) ||
+        (rc = h->mem.alloc(&h->d_einfo, 5)))
+        return rc;
+    // the largest dynamic LDS any handle may ask for: the attribute belongs to the kernel, not to a handle, so it is never lowered
+    DESC_HIP(hipFuncSetAttribute((const void*)k_irls_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ib_lds_bytes(IRLS_BATCH_MAX_N)));
+    DESC_HIP(hipStreamSynchronize(h->stream));         // the caller's staging vectors may go
+    return DESC_OK;
+}
+
+// On a resident set: the cap, then the row orders and the tree sequences from slices of the set's host endpoints (no rotation and no CSR
+// is read).  Uploads: the tree sequences, and the row orders only where one is not the identity; the problem records, the CSR, the
+// endpoints and the rotations are the set's; the signs, the edge -> problem map and identity orders are formed by launches.
+int ib_create_on(const std::shared_ptr<PbSet>& set, const int32_t* const* orders, desc_irls_batch* h) {
+    auto t0 = std::chrono::steady_clock::now();
+    static_assert(sizeof(IbProb) == sizeof(PbProb), "the set's problem record is the batched IRLS's");
+    const int32_t count = set->count;
+    int rc;
+    for (int32_t b = 0; b < count; ++b)
+        if ((rc = ib_check_n(b, set->node_off[(size_t)b + 1] - set->node_off[(size_t)b]))) return rc;
+    pb_share_host(*set, h);
+    hvec<desc_problem> view((size_t)count);
+    for (int32_t b = 0; b < count; ++b) {
+        const size_t eo = (size_t)h->edge_off[(size_t)b];
+        view[(size_t)b] = desc_problem{h->node_off[(size_t)b + 1] - h->node_off[(size_t)b], h->edge_off[(size_t)b + 1] - h->edge_off[(size_t)b],
+                                       h->ii.data() + eo, h->jj.data() + eo, nullptr};
+    }
+    if ((rc = ib_orders_and_trees(view.data(), count, orders, h))) return rc;
+    bool identity = true;
+    for (int64_t b = 0; b < count && identity; ++b)
+        for (int64_t e = h->edge_off[(size_t)b]; e < h->edge_off[(size_t)b + 1] && identity; ++e) identity = h->order[(size_t)e] == (int32_t)(e - h->edge_off[(size_t)b]);
+    ib_flags0(h);
+    h->ms_structure = ms_since(t0);
+    if (count == 0) return DESC_OK;
+
+    if ((rc = h->open(set->device, "the batched IRLS"))) return rc;        // nothing above touched the device
+    auto t1 = std::chrono::steady_clock::now();
+    if ((rc = ib_check_lds(h))) return rc;
+    h->set = set;
+    h->d_prob = reinterpret_cast<IbProb*>(set->d_prob);
+    h->d_rowptr = set->d_rowptr; h->d_adj = set->d_adj; h->d_adj_eid = set->d_adj_eid; h->d_ii = set->d_ii; h->d_jj = set->d_jj;
+    h->d_rij = set->d_rij;
+    const size_t M = (size_t)h->M;
+    const dim3 grid((unsigned)count), block(256);
+    if ((rc = h->upload(&h->d_seq, h->seq.data(), h->seq.size())) || (rc = h->mem.alloc(&h->d_sgn, 2 * M)) || (rc = h->mem.alloc(&h->d_eprob, M))) return rc;
+    if (identity) {
+        if ((rc = h->mem.alloc(&h->d_order, M))) return rc;
+        hipLaunchKernelGGL(k_irls_identity_order, grid, block, 0, h->stream, h->d_prob, h->d_order);
+    } else if ((rc = h->upload(&h->d_order, h->order.data(), M))) return rc;
+    hipLaunchKernelGGL(k_batch_sgn<IbProb>, grid, block, 0, h->stream, h->d_prob, h->d_rowptr, h->d_adj, h->d_sgn);
+    hipLaunchKernelGGL(k_batch_eprob<IbProb>, grid, block, 0, h->stream, h->d_prob, h->d_eprob);
+    DESC_HIP(hipGetLastError());
+    if ((rc = ib_alloc_work(h))) return rc;
+    h->ms_upload = ms_since(t1);
+    return DESC_OK;
+}
+
 int ib_create(const desc_problem* probs, int32_t count, const int32_t* const* orders, int32_t device, desc_irls_batch* h) {
     auto t0 = std::chrono::steady_clock::now();
     int rc = ib_host_part(probs, count, orders, h);
     if (rc) return rc;
-    const size_t M = (size_t)h->M, N = (size_t)h->N;
+    const size_t M = (size_t)h->M;
     hvec<int8_t> sgn(2 * M);                           // Build_Amatrix.m:10 per CSR slot: -1 at the smaller endpoint i, +1 at j
     hvec<int32_t> eprob(M);
     for (int32_t b = 0; b < count; ++b) {
@@ -479,20 +576,13 @@ int ib_create(const desc_problem* probs, int32_t count, const int32_t* const* or
             for (int32_t t = rp[v]; t < rp[v + 1]; ++t) sgn[so + (size_t)t] = v < h->adj[so + (size_t)t] ? -1 : +1;
         std::fill(eprob.begin() + h->edge_off[(size_t)b], eprob.begin() + h->edge_off[(size_t)b + 1], b);
     }
-    h->flags0.resize(2 * (size_t)count);
-    for (int32_t b = 0; b < count; ++b) { h->flags0[2 * (size_t)b] = INT_MAX; h->flags0[2 * (size_t)b + 1] = 0; }
+    ib_flags0(h);
     h->ms_structure = ms_since(t0);
     if (count == 0) return DESC_OK;
 
     if ((rc = h->open(device, "the batched IRLS"))) return rc;             // nothing above touched the device
     auto t1 = std::chrono::steady_clock::now();
-    // the kernel's fixed LDS against what was set aside for it: an error here instead of a failed launch
-    hipFuncAttributes fa;
-    if (!&hipFuncGetAttributes) return fail(DESC_ERR_HIP, "the HIP runtime exports no hipFuncGetAttributes: the LDS budget of the batched IRLS cannot be checked");
-    DESC_HIP(hipFuncGetAttributes(&fa, (const void*)k_irls_batch));
-    if (fa.sharedSizeBytes > (size_t)IB_STATIC_BYTES || fa.sharedSizeBytes + ib_lds_bytes(h->max_n) > (size_t)RB_LDS_BYTES)
-        return fail(DESC_ERR_STATE, "LDS budget exceeded: %zu bytes fixed, %zu bytes for n = %d, %d allowed", (size_t)fa.sharedSizeBytes,
-                    ib_lds_bytes(h->max_n), (int)h->max_n, RB_LDS_BYTES);
+    if ((rc = ib_check_lds(h))) return rc;
     hvec<IbProb> pr((size_t)count);
     for (int32_t b = 0; b < count; ++b) pr[(size_t)b] = IbProb{(int32_t)probs[b].n, (int32_t)probs[b].m, h->node_off[(size_t)b], h->edge_off[(size_t)b]};
     const hvec<double> rij = stage_rotations(probs, count, h->edge_off);
@@ -503,14 +593,7 @@ int ib_create(const desc_problem* probs, int32_t count, const int32_t* const* or
         (rc = h->upload(&h->d_seq, h->seq.data(), h->seq.size())) || (rc = h->upload(&h->d_order, h->order.data(), M)) ||
         (rc = h->upload(&h->d_eprob, eprob.data(), M)))
         return rc;
-    if ((rc = h->mem.alloc(&h->d_P, 9 * M)) || (rc = h->mem.alloc(&h->d_QQ, M)) || (rc = h->mem.alloc(&h->d_B, 3 * M)) ||
-        (rc = h->mem.alloc(&h->d_w, M)) || (rc = h->mem.alloc(&h->d_edge, (size_t)IB_EDGE_ARRAYS * 3 * M)) || (rc = h->mem.alloc(&h->d_Rl1, 9 * N)) ||
-        (rc = h->mem.alloc(&h->d_Rout, 9 * N)) || (rc = h->mem.alloc(&h->d_info, (size_t)count)) || (rc = h->mem.alloc(&h->d_flags, 2 * (size_t)count)) ||
-        (rc = h->mem.alloc(&h->d_einfo, 5)))
-        return rc;
-    // the largest dynamic LDS any handle may ask for: the attribute belongs to the kernel, not to a handle, so it is never lowered
-    DESC_HIP(hipFuncSetAttribute((const void*)k_irls_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ib_lds_bytes(IRLS_BATCH_MAX_N)));
-    DESC_HIP(hipStreamSynchronize(h->stream));         // the staging vectors go out of scope below
+    if ((rc = ib_alloc_work(h))) return rc;             // drains the stream: the staging vectors go out of scope below
     h->ms_upload = ms_since(t1);
     return DESC_OK;
 }
@@ -601,6 +684,17 @@ int32_t desc_irls_batch_max_n(void) { return IRLS_BATCH_MAX_N; }
 
 int desc_irls_batch_create(const desc_problem* probs, int32_t count, const int32_t* const* orders, int32_t device, desc_irls_batch** out) {
     return batch_create_guarded("desc_irls_batch_create", out, probs, count, [&](desc_irls_batch* h) { return ib_create(probs, count, orders, device, h); });
+}
+
+int desc_irls_batch_create_on(desc_problem_batch* set, const int32_t* const* orders, desc_irls_batch** out) {
+    return batch_create_guarded("desc_irls_batch_create_on", out, set, 0, [&](desc_irls_batch* h) { return ib_create_on(set->s, orders, h); }, set != nullptr);
+}
+
+int desc_irls_batch_bytes(const desc_irls_batch* h, int64_t* h2d, int64_t* d2h) {
+    if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
+    if (h2d) *h2d = h->bytes_h2d;
+    if (d2h) *d2h = h->bytes_d2h;
+    return DESC_OK;
 }
 
 int desc_irls_batch_sizes(const desc_irls_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off) {

@@ -33,6 +33,7 @@
 #include <cstring>
 #include <vector>
 
+#include "batch_kernels.h"
 #include "cemp_batch.h"
 #include "cemp_math.h"
 #include "laa_wg.h"
@@ -154,16 +155,25 @@ int mb_setup(desc_cemp_batch* h) {
     MbLoop& L = h->loop;
     const int32_t count = h->count;
     const size_t M = (size_t)h->M, N = (size_t)h->N;
-    hvec<int8_t> sgn(2 * M);                           // Build_Amatrix.m:10 per CSR slot: -1 at the smaller endpoint i, +1 at j
-    for (int32_t b = 0; b < count; ++b) {
-        const int32_t* rp = h->rowptr.data() + h->node_off[(size_t)b] + b;
-        const size_t so = 2 * (size_t)h->edge_off[(size_t)b];
-        const int64_t nb = h->node_off[(size_t)b + 1] - h->node_off[(size_t)b];
-        for (int64_t v = 0; v < nb; ++v)
-            for (int32_t t = rp[v]; t < rp[v + 1]; ++t) sgn[so + (size_t)t] = v < h->adj[so + (size_t)t] ? -1 : +1;
-    }
+    hvec<int8_t> sgn;                                  // Build_Amatrix.m:10 per CSR slot: -1 at the smaller endpoint i, +1 at j
     int rc;
-    if ((rc = h->upload(&L.sgn, sgn.data(), 2 * M))) return rc;
+    if (h->set) {                                      // a handle created on a set has no host CSR: the signs by a launch from the set's (batch_kernels.h)
+        int8_t* d_sgn = nullptr;
+        if ((rc = h->mem.alloc(&d_sgn, 2 * M))) return rc;
+        hipLaunchKernelGGL(k_batch_sgn<CbProb>, dim3((unsigned)count), dim3(256), 0, h->stream, h->a.prob, h->a.rowptr, h->a.adj, d_sgn);
+        DESC_HIP(hipGetLastError());
+        L.sgn = d_sgn;
+    } else {
+        sgn.resize(2 * M);
+        for (int32_t b = 0; b < count; ++b) {
+            const int32_t* rp = h->rowptr.data() + h->node_off[(size_t)b] + b;
+            const size_t so = 2 * (size_t)h->edge_off[(size_t)b];
+            const int64_t nb = h->node_off[(size_t)b + 1] - h->node_off[(size_t)b];
+            for (int64_t v = 0; v < nb; ++v)
+                for (int32_t t = rp[v]; t < rp[v + 1]; ++t) sgn[so + (size_t)t] = v < h->adj[so + (size_t)t] ? -1 : +1;
+        }
+        if ((rc = h->upload(&L.sgn, sgn.data(), 2 * M))) return rc;
+    }
     if ((rc = h->mem.alloc(&L.S, M)) || (rc = h->mem.alloc(&L.R_init, 9 * N)) || (rc = h->mem.alloc(&L.R_out, 9 * N)) ||
         (rc = h->mem.alloc(&L.QQ, M)) || (rc = h->mem.alloc(&L.B, 3 * M)) || (rc = h->mem.alloc(&L.w, M)) || (rc = h->mem.alloc(&L.Res, M)) ||
         (rc = h->mem.alloc(&L.RH, M)) || (rc = h->mem.alloc(&L.info, (size_t)count)))

@@ -25,6 +25,7 @@
 #include "batch_csr.h"
 #include "batch_device.h"
 #include "mst_key.h"
+#include "problem_batch.h"
 
 namespace desc {
 namespace {
@@ -92,6 +93,24 @@ __global__ __launch_bounds__(256) void k_mst_batch(const MbProb* prob, const int
     if (tid == 0) status[b] = 0;
 }
 
+// desc_mst_batch_run_on: the 3 x 3 blocks of the tree's edges out of the set's rotations, for the host's rooting and propagation.  One
+// workgroup per problem; thread t copies double t, t + 256, ... of the problem's 9 (n_b - 1) output doubles, so consecutive lanes store
+// consecutive doubles (a wave's stores cover whole lines) and the nine lanes of a slot read its 72-byte block behind one another.  The
+// loop is bounded by 9 (n_b - 1); an id outside 0 .. m_b - 1 (refused on the host before the launch) reads nothing and leaves NaN.
+__global__ __launch_bounds__(256) void k_mst_gather_blocks(const MbProb* prob, const int32_t* tree_all, const double* rij_all, double* blk_all) {
+    const int b = blockIdx.x;
+    const MbProb pd = prob[b];
+    const int32_t* tree = tree_all + pd.node_off - b;
+    const double* rij = rij_all + 9 * (int64_t)pd.edge_off;
+    double* blk = blk_all + 9 * (int64_t)(pd.node_off - b);
+    const int total = 9 * (pd.n - 1);
+    for (int q = threadIdx.x; q < total; q += 256) {
+        const int slot = q / 9, c = q - 9 * slot;
+        const int e = tree[slot];
+        blk[q] = (unsigned)e < (unsigned)pd.m ? rij[9 * (int64_t)e + c] : __builtin_nan("");
+    }
+}
+
 // connected, with every node id touched by an edge: union-find over the problem's edge list; *comps = the number of components
 void mb_components(int64_t n, int64_t m, const int32_t* ii, const int32_t* jj, int64_t* comps) {
     hvec<int32_t> par((size_t)n);
@@ -105,25 +124,129 @@ void mb_components(int64_t n, int64_t m, const int32_t* ii, const int32_t* jj, i
     *comps = c;
 }
 
-// validation, the size cap, connectivity, the per-problem CSR: no device
-int mb_host_part(const desc_problem* probs, int32_t count, const double* s_vec, BatchCsr* h) {
-    int rc = batch_csr_host(probs, count, [](int32_t b, const desc_problem& q) -> int {
-        if (q.n > MST_BATCH_MAX_N)
-            return fail(DESC_ERR_INVALID, "problem %d: n = %lld exceeds %d (the per-node keys of the tree kernel must fit the LDS of one workgroup): solve it with MST / MPLS",
-                        b, (long long)q.n, MST_BATCH_MAX_N);
-        int64_t comps = 0;
-        mb_components(q.n, q.m, q.ind_i, q.ind_j, &comps);
-        if (comps != 1)                               // MPLS.m:178 would loop for ever
-            return fail(DESC_ERR_INVALID, "problem %d: the graph is disconnected: %lld components (a node id in 1..max(Ind) that no edge touches is one)",
-                        b, (long long)comps);
-        return DESC_OK;
-    }, h);
+// the size cap and connectivity of one problem, from its endpoints alone
+int mb_check_problem(int32_t b, int64_t n, int64_t m, const int32_t* ii, const int32_t* jj) {
+    if (n > MST_BATCH_MAX_N)
+        return fail(DESC_ERR_INVALID, "problem %d: n = %lld exceeds %d (the per-node keys of the tree kernel must fit the LDS of one workgroup): solve it with MST / MPLS",
+                    b, (long long)n, MST_BATCH_MAX_N);
+    int64_t comps = 0;
+    mb_components(n, m, ii, jj, &comps);
+    if (comps != 1)                                   // MPLS.m:178 would loop for ever
+        return fail(DESC_ERR_INVALID, "problem %d: the graph is disconnected: %lld components (a node id in 1..max(Ind) that no edge touches is one)",
+                    b, (long long)comps);
+    return DESC_OK;
+}
+
+int mb_check_s_vec(const BatchCsr& h, const double* s_vec) {
+    for (int32_t b = 0; b < h.count; ++b)
+        for (int64_t e = h.edge_off[(size_t)b]; e < h.edge_off[(size_t)b + 1]; ++e)
+            if (!std::isfinite(s_vec[e]))
+                return fail(DESC_ERR_INVALID, "problem %d: S_vec entry %lld is not finite", b, (long long)(e - h.edge_off[(size_t)b]));
+    return DESC_OK;
+}
+
+// validation, the size cap, connectivity, the per-problem CSR: no device.  csr = false (desc_mst_batch_check): the refusals and the
+// offsets alone, and a problem may come without rotations.
+int mb_host_part(const desc_problem* probs, int32_t count, const double* s_vec, BatchCsr* h, bool csr = true) {
+    const auto extra = [](int32_t b, const desc_problem& q) -> int { return mb_check_problem(b, q.n, q.m, q.ind_i, q.ind_j); };
+    int rc = csr ? batch_csr_host(probs, count, extra, h) : batch_offsets_host(probs, count, extra, h, false, false);
     if (rc) return rc;
-    if (s_vec)
-        for (int32_t b = 0; b < count; ++b)
-            for (int64_t e = h->edge_off[(size_t)b]; e < h->edge_off[(size_t)b + 1]; ++e)
-                if (!std::isfinite(s_vec[e]))
-                    return fail(DESC_ERR_INVALID, "problem %d: S_vec entry %lld is not finite", b, (long long)(e - h->edge_off[(size_t)b]));
+    return s_vec ? mb_check_s_vec(*h, s_vec) : DESC_OK;
+}
+
+// the launch's LDS and the read-back of its status words and edge ids (into tree, N entries at least), refusing a tree that did not close
+int mb_grow_trees(BatchDevice& dev, const BatchCsr& h, const MbProb* d_prob, const int32_t* d_rowptr, const int32_t* d_adj, const int32_t* d_eid,
+                  const double* d_s, int32_t* d_tree, int32_t* d_status, hvec<int32_t>& tree) {
+    const size_t N = (size_t)h.N, count = (size_t)h.count;
+    const size_t lds = (size_t)16 * (size_t)h.max_n;
+    if (lds > 64 * 1024) return fail(DESC_ERR_STATE, "LDS budget exceeded (%zu bytes)", lds);
+    hipLaunchKernelGGL(k_mst_batch, dim3((unsigned)count), dim3(256), lds, dev.stream, d_prob, d_rowptr, d_adj, d_eid, d_s, d_tree, d_status);
+    DESC_HIP(hipGetLastError());
+    hvec<int32_t> status(count);
+    tree.assign(std::max<size_t>(N, 1), 0);
+    int rc;
+    if ((rc = dev.download(status.data(), d_status, count))) return rc;
+    if (N > count && (rc = dev.download(tree.data(), d_tree, N - count))) return rc;
+    DESC_HIP(hipStreamSynchronize(dev.stream));
+    for (size_t b = 0; b < count; ++b)
+        if (status[b] != 0)
+            return fail(DESC_ERR_STATE, "problem %d: the tree kernel found no edge leaving the tree (status %d)", (int)b, (int)status[b]);
+    return DESC_OK;
+}
+
+// every edge id of problem b's tree lies in 0 .. m_b - 1
+bool mb_ids_ok(const BatchCsr& h, int32_t b, const int32_t* ids) {
+    const int64_t cnt = h.node_off[(size_t)b + 1] - h.node_off[(size_t)b] - 1, m = h.edge_off[(size_t)b + 1] - h.edge_off[(size_t)b];
+    bool ok = true;
+    for (int64_t q = 0; q < cnt; ++q) ok = ok && ids[q] >= 0 && ids[q] < m;
+    return ok;
+}
+
+// On a resident set: the host part on the set's endpoint mirror, s_vec up, the tree kernel on the set's CSR, the tree's blocks gathered
+// on the device (72 bytes per tree edge come down), rooting and propagation on the host as in mb_run.
+int mb_run_on(const std::shared_ptr<PbSet>& set, const double* s_vec, double* R_out, int32_t* tree_edges, desc_mst_batch_timings* tm, int64_t* bytes) {
+    auto t0 = std::chrono::steady_clock::now();
+    if (tm) { tm->ms_structure = 0; tm->ms_upload = 0; tm->ms_tree = 0; tm->ms_propagate = 0; tm->ms_total = 0; }
+    if (bytes) { bytes[0] = 0; bytes[1] = 0; }
+    const BatchCsr& h = *set;
+    const int32_t count = h.count;
+    if (count == 0) return DESC_OK;
+    if (!s_vec || !R_out) return fail(DESC_ERR_INVALID, "s_vec or R_out is NULL");
+    int rc;
+    for (int32_t b = 0; b < count; ++b) {
+        const size_t eo = (size_t)h.edge_off[(size_t)b];
+        if ((rc = mb_check_problem(b, h.node_off[(size_t)b + 1] - h.node_off[(size_t)b], h.edge_off[(size_t)b + 1] - (int64_t)eo, h.ii.data() + eo, h.jj.data() + eo)))
+            return rc;
+    }
+    if ((rc = mb_check_s_vec(h, s_vec))) return rc;
+    const double ms_structure = ms_since(t0);
+
+    BatchDevice dev;                                   // this call's own: gone, stream drained, at every return below -- before the caller's reference to the set
+    if ((rc = dev.open(set->device, "the batched tree step"))) return rc;   // nothing above touched the device
+    auto t1 = std::chrono::steady_clock::now();
+    const size_t M = (size_t)h.M, N = (size_t)h.N;
+    hvec<MbProb> pr((size_t)count);
+    for (int32_t b = 0; b < count; ++b)
+        pr[(size_t)b] = MbProb{(int32_t)(h.node_off[(size_t)b + 1] - h.node_off[(size_t)b]), (int32_t)(h.edge_off[(size_t)b + 1] - h.edge_off[(size_t)b]),
+                               (int32_t)h.node_off[(size_t)b], (int32_t)h.edge_off[(size_t)b]};
+    MbProb* d_prob; int32_t *d_tree, *d_status; double *d_s, *d_blk;
+    const size_t n_blk = 9 * (N - (size_t)count);
+    if ((rc = dev.upload(&d_prob, pr.data(), pr.size())) || (rc = dev.upload(&d_s, s_vec, M)) || (rc = dev.mem.alloc(&d_tree, N)) ||
+        (rc = dev.mem.alloc(&d_status, (size_t)count)) || (rc = dev.mem.alloc(&d_blk, std::max<size_t>(n_blk, 1)))) return rc;
+    DESC_HIP(hipMemsetAsync(d_status, 0xFF, sizeof(int32_t) * (size_t)count, dev.stream));       // -1: the workgroup never finished
+    DESC_HIP(hipStreamSynchronize(dev.stream));
+    const double ms_upload = ms_since(t1);
+
+    auto t2 = std::chrono::steady_clock::now();
+    hvec<int32_t> tree;
+    if ((rc = mb_grow_trees(dev, h, d_prob, set->d_rowptr, set->d_adj, set->d_adj_eid, d_s, d_tree, d_status, tree))) return rc;
+    for (int32_t b = 0; b < count; ++b)                // before the gather reads rotations by these ids
+        if (!mb_ids_ok(h, b, tree.data() + h.node_off[(size_t)b] - b)) return fail(DESC_ERR_STATE, "problem %d: the tree kernel's edges do not span the graph", b);
+    hvec<double> blk(std::max<size_t>(n_blk, 1));
+    hipLaunchKernelGGL(k_mst_gather_blocks, dim3((unsigned)count), dim3(256), 0, dev.stream, d_prob, d_tree, set->d_rij, d_blk);
+    DESC_HIP(hipGetLastError());
+    if ((rc = dev.download(blk.data(), d_blk, n_blk))) return rc;
+    DESC_HIP(hipStreamSynchronize(dev.stream));
+    const double ms_tree = ms_since(t2);
+
+    // ---- rooting and propagation (MPLS.m:171-193) per problem on host threads: the tail of mst_device
+    auto t3 = std::chrono::steady_clock::now();
+    hvec<int32_t> prc((size_t)count, DESC_OK);
+    for_each_problem(count, [&](int32_t b) {
+        const int64_t no = h.node_off[(size_t)b], n = h.node_off[(size_t)b + 1] - no;
+        const size_t eo = (size_t)h.edge_off[(size_t)b];
+        int32_t* ids = tree.data() + no - b;
+        const int cnt = (int)(n - 1);
+        prc[(size_t)b] = mst_propagate(n, h.ii.data() + eo, h.jj.data() + eo, ids, cnt, blk.data() + 9 * (size_t)(no - b), R_out + 9 * (size_t)no);
+        if (tree_edges && prc[(size_t)b] == DESC_OK) {
+            std::sort(ids, ids + cnt);
+            std::copy(ids, ids + cnt, tree_edges + no - b);
+        }
+    });
+    for (int32_t b = 0; b < count; ++b)
+        if (prc[(size_t)b]) return fail(DESC_ERR_STATE, "problem %d: the tree kernel's edges do not span the graph", b);
+    if (tm) { tm->ms_structure = ms_structure; tm->ms_upload = ms_upload; tm->ms_tree = ms_tree; tm->ms_propagate = ms_since(t3); tm->ms_total = ms_since(t0); }
+    if (bytes) { bytes[0] = dev.bytes_h2d; bytes[1] = dev.bytes_d2h; }
     return DESC_OK;
 }
 
@@ -152,18 +275,9 @@ int mb_run(const desc_problem* probs, int32_t count, const double* s_vec, int32_
     const double ms_upload = ms_since(t1);
 
     auto t2 = std::chrono::steady_clock::now();
-    const size_t lds = (size_t)16 * (size_t)h.max_n;
-    if (lds > 64 * 1024) return fail(DESC_ERR_STATE, "LDS budget exceeded (%zu bytes)", lds);
-    hipLaunchKernelGGL(k_mst_batch, dim3((unsigned)count), dim3(256), lds, dev.stream, d_prob, d_rowptr, d_adj, d_eid, d_s, d_tree, d_status);
-    DESC_HIP(hipGetLastError());
-    hvec<int32_t> tree(std::max<size_t>(N, 1)), status((size_t)count);
-    DESC_HIP(hipMemcpyAsync(status.data(), d_status, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, dev.stream));
-    if (N > (size_t)count) DESC_HIP(hipMemcpyAsync(tree.data(), d_tree, sizeof(int32_t) * (N - (size_t)count), hipMemcpyDeviceToHost, dev.stream));
-    DESC_HIP(hipStreamSynchronize(dev.stream));
+    hvec<int32_t> tree;
+    if ((rc = mb_grow_trees(dev, h, d_prob, d_rowptr, d_adj, d_eid, d_s, d_tree, d_status, tree))) return rc;
     const double ms_tree = ms_since(t2);
-    for (int32_t b = 0; b < count; ++b)
-        if (status[(size_t)b] != 0)
-            return fail(DESC_ERR_STATE, "problem %d: the tree kernel found no edge leaving the tree (status %d)", b, (int)status[(size_t)b]);
 
     // ---- rooting and propagation (MPLS.m:171-193) per problem on host threads: the tail of mst_device
     auto t3 = std::chrono::steady_clock::now();
@@ -202,7 +316,15 @@ int desc_mst_batch_check(const desc_problem* probs, int32_t count) {
     return no_throw("desc_mst_batch_check", [&]() -> int {
         if (count < 0 || (count > 0 && !probs)) return fail(DESC_ERR_INVALID, "NULL argument or negative count");
         BatchCsr h;
-        return mb_host_part(probs, count, nullptr, &h);
+        return mb_host_part(probs, count, nullptr, &h, false);
+    });
+}
+
+int desc_mst_batch_run_on(desc_problem_batch* set, const double* s_vec, double* R_out, int32_t* tree_edges, desc_mst_batch_timings* timings, int64_t* bytes) {
+    return no_throw("desc_mst_batch_run_on", [&]() -> int {
+        if (!set) return fail(DESC_ERR_INVALID, "NULL argument or negative count");
+        const std::shared_ptr<PbSet> keep = set->s;   // outlives the call's device half
+        return mb_run_on(keep, s_vec, R_out, tree_edges, timings, bytes);
     });
 }
 

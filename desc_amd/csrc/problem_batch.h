@@ -1,6 +1,6 @@
 // A problem set resident on the device (desc_problem_batch_*, problem_batch.hip): the problems of B independent instances, validated,
 // laid out and uploaded ONCE, for every batched handle that is created on it (desc_gcw_batch_create_on, desc_refine_batch_create_on,
-// desc_pgd_batch_create_on).  The layout is the one the batched handles make for themselves (batch_csr.h): problem b's rowptr at
+// desc_pgd_batch_create_on, desc_cemp_batch_create_on, desc_irls_batch_create_on) and for desc_mst_batch_run_on.  The layout is the one the batched handles make for themselves (batch_csr.h): problem b's rowptr at
 // node_off[b] + b, its adj / adj_eid at 2 edge_off[b], its rij at 9 edge_off[b], local ids throughout.
 //
 // Ownership.  The C handle holds a shared_ptr to the set; a handle created on the set holds another.  desc_problem_batch_destroy drops

@@ -36,6 +36,7 @@
 
 #include "batch_csr.h"
 #include "batch_device.h"
+#include "batch_kernels.h"
 #include "problem_batch.h"
 #include "laa_wg.h"
 
@@ -142,18 +143,6 @@ __global__ __launch_bounds__(256) void k_refine_batch(RbArgs a) {
     }
 }
 
-// desc_refine_batch_create_on: the incidence sign per CSR slot from the set's CSR, as rb_create forms it on the host -- -1 where the
-// row's node is the smaller endpoint.  One workgroup per problem, a thread per row.
-__global__ __launch_bounds__(256) void k_rb_sgn(const RbProb* prob, const int32_t* rowptr_all, const int32_t* adj_all, int8_t* sgn_all) {
-    const int b = blockIdx.x;
-    const RbProb pd = prob[b];
-    const int32_t* rowptr = rowptr_all + pd.node_off + b;
-    const int32_t* adj = adj_all + 2 * pd.edge_off;
-    int8_t* sgn = sgn_all + 2 * pd.edge_off;
-    for (int v = threadIdx.x; v < pd.n; v += 256)
-        for (int t = rowptr[v]; t < rowptr[v + 1]; ++t) sgn[t] = v < adj[t] ? -1 : +1;
-}
-
 }  // namespace
 }  // namespace desc
 
@@ -197,7 +186,7 @@ int rb_alloc_work(desc_refine_batch* h) {
     return DESC_OK;
 }
 
-// On a resident set: the cap, then the signs per slot in one launch from the set's CSR; everything else the kernel reads of the
+// On a resident set: the cap, then the signs per slot in one launch from the set's CSR (batch_kernels.h); everything else the kernel reads of the
 // problems is the set's (its record is RbProb's).
 int rb_create_on(const std::shared_ptr<PbSet>& set, desc_refine_batch* h) {
     auto t0 = std::chrono::steady_clock::now();
@@ -216,7 +205,7 @@ int rb_create_on(const std::shared_ptr<PbSet>& set, desc_refine_batch* h) {
     h->d_rowptr = set->d_rowptr; h->d_adj = set->d_adj; h->d_adj_eid = set->d_adj_eid; h->d_ii = set->d_ii; h->d_jj = set->d_jj;
     h->d_rij = set->d_rij;
     if ((rc = h->mem.alloc(&h->d_sgn, 2 * (size_t)h->M))) return rc;
-    hipLaunchKernelGGL(k_rb_sgn, dim3((unsigned)h->count), dim3(256), 0, h->stream, h->d_prob, h->d_rowptr, h->d_adj, h->d_sgn);
+    hipLaunchKernelGGL(k_batch_sgn<RbProb>, dim3((unsigned)h->count), dim3(256), 0, h->stream, h->d_prob, h->d_rowptr, h->d_adj, h->d_sgn);
     DESC_HIP(hipGetLastError());
     if ((rc = rb_alloc_work(h))) return rc;
     DESC_HIP(hipStreamSynchronize(h->stream));

@@ -11,8 +11,8 @@ The time the generation took is printed in both modes.
 
 --resident: the trials become ONE ProblemBatch -- validated, laid out and uploaded once -- and every selected curve runs on it: with
 --device-models the generator hands its problems over on the device (no rotation is copied back before a curve asks for it), otherwise
-the host-drawn trials are wrapped.  The DESC curves create their handles on the set; the other curves read its host mirror.  The curves
-are the same to the last bit as without the flag.
+the host-drawn trials are wrapped.  The DESC, CEMP, MST, MPLS and IRLS curves create their handles on the set; the LP curve reads its
+host mirror.  The curves are the same to the last bit as without the flag.
 
 --build: the builder of the cycle structures behind DESC_PGD_batch / DESC_init_batch / DESC_batch: per problem on host threads (the
 default) or for the whole batch on the device; the curves are the same to the last bit.

@@ -690,7 +690,7 @@ void desc_cemp_batch_destroy(desc_cemp_batch* h);
  * desc_mst_run's); rooting and propagation (:171-193) run per problem on host threads with desc_mst_run's own code.  Problem b's R and
  * tree edges are bit for bit what desc_mst_run gives for it.
  * desc_mst_batch_max_n: the largest problem (nodes) the tree kernel takes (4096).
- * desc_mst_batch_check: the host part alone (no device): DESC_ERR_INVALID naming the problem for an empty edge list, n >
+ * desc_mst_batch_check: the host part alone (no device; rij is not read and may be NULL): DESC_ERR_INVALID naming the problem for an empty edge list, n >
  * desc_mst_batch_max_n() (solve it with MST / MPLS) and a disconnected graph (union-find; a node id that no edge touches is a component).
  * desc_mst_batch_run: the same checks and a non-finite s_vec entry are refused before any device work.  s_vec: the concatenated S_vec in
  * the library's edge order; R_out: problem b's 3x3xn_b column-major blocks at 9 * node_off[b] (node_off = the running sum of n);
@@ -1024,7 +1024,16 @@ int desc_test_align_project(const double* A, int64_t count, int32_t device, doub
  * device work); what create derives from the CSR is formed on the device (the refinement's sign per slot, the device builder's edge ->
  * problem map), so the uploads of a create_on are O(B) bytes.  desc_pgd_batch_create_on takes either builder (the host builder reads
  * the set's host ii / jj; p->device is not read); the device builder's silent fallback is unchanged.  The run functions are unchanged
- * and give the bits of a handle created from the host arrays.  desc_*_batch_bytes: the bytes a handle's creates copied up / down. */
+ * and give the bits of a handle created from the host arrays.  desc_*_batch_bytes: the bytes a handle's creates copied up / down.
+ *
+ * desc_cemp_batch_create_on / desc_irls_batch_create_on: the same for the CEMP handle (with desc_mpls_batch_run on it) and the IRLS
+ * handle.  The degree cap of the sampler is checked on the set's host row starts or, for a device-built CSR, on a count over its host
+ * endpoints; the IRLS cap, the order check and the connectivity refusal run on the set's host endpoints.  Uploads: the CEMP problem
+ * records (32 bytes per problem); the IRLS tree sequences (4 bytes per node) and, only where some problem's order is not the identity,
+ * the row orders (4 bytes per edge).  The edge -> problem maps, the signs per slot and identity orders are formed by launches.
+ * desc_mst_batch_run_on: desc_mst_batch_run on the set's device: its refusals on the set's host endpoints, s_vec up (8 bytes per edge),
+ * the tree kernel on the set's CSR, the 3 x 3 blocks of the n_b - 1 tree edges gathered by a launch and brought down (72 bytes per tree
+ * edge) for the host's rooting and propagation.  bytes (nullable): {host -> device, device -> host} of this call. */
 typedef struct desc_problem_batch desc_problem_batch;   /* opaque */
 int desc_problem_batch_create(const desc_problem* probs, int32_t count, int32_t device, int32_t csr_where /* DESC_BUILD_HOST | DESC_BUILD_DEVICE */,
                               desc_problem_batch** out);
@@ -1041,6 +1050,13 @@ int desc_pgd_batch_create_on(desc_problem_batch* set, const desc_params* p, cons
 int desc_gcw_batch_bytes(const desc_gcw_batch* h, int64_t* h2d, int64_t* d2h);
 int desc_refine_batch_bytes(const desc_refine_batch* h, int64_t* h2d, int64_t* d2h);
 int desc_pgd_batch_bytes(const desc_pgd_batch* h, int64_t* h2d, int64_t* d2h);
+int desc_cemp_batch_create_on(desc_problem_batch* set, int32_t nsample, uint64_t seed, const uint64_t* seeds /* count, nullable */,
+                              desc_cemp_batch** out);
+int desc_irls_batch_create_on(desc_problem_batch* set, const int32_t* const* orders /* nullable, entries nullable */, desc_irls_batch** out);
+int desc_mst_batch_run_on(desc_problem_batch* set, const double* s_vec, double* R_out, int32_t* tree_edges /* nullable */,
+                          desc_mst_batch_timings* timings /* nullable */, int64_t* bytes /* nullable: {h2d, d2h} of this call */);
+int desc_cemp_batch_bytes(const desc_cemp_batch* h, int64_t* h2d, int64_t* d2h);
+int desc_irls_batch_bytes(const desc_irls_batch* h, int64_t* h2d, int64_t* d2h);
 
 /* One-shot: what the MEX shim calls.  Builds the structure (p->build_where),
  * uploads, runs, downloads, frees. */
