@@ -1404,11 +1404,12 @@ class Solver:
         return load().desc_pgd_kernel_name(self.handle).decode()
 
     def layout_stats(self):
-        out = np.zeros(6, dtype=np.int64)
-        k = load().desc_pgd_layout_stats(self.handle, ptr(out, I64P), 6)
+        out = np.zeros(10, dtype=np.int64)
+        k = load().desc_pgd_layout_stats(self.handle, ptr(out, I64P), 10)
         if k < 0:
             check(k)
-        return dict(zip(("colsum_entries", "pieces", "bands", "piece_row_entries", "cycles", "segments"), (int(x) for x in out[:k])))
+        return dict(zip(("colsum_entries", "pieces", "bands", "piece_row_entries", "cycles", "segments",
+                         "colsum_cl", "colsum_long", "colsum_nodes", "colsum_fx_bits"), (int(x) for x in out[:k])))
 
     def last_sweep(self):
         """Name + template arguments of the sweep kernel launched last (diagnostics)."""

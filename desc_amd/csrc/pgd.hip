@@ -900,12 +900,16 @@ int desc_debug_wg_plan(desc_pgd* h, int64_t* out, int32_t cap) {
 
 // What the layout of this handle moves per iteration (bench.py: the floor of its own traffic, next to the 72-byte algorithmic count):
 // out[0] = (cycle, endpoint) pairs read by the column sums, out[1] = pieces of the band sweep, out[2] = bands, out[3] = CSR entries of band
-// rows loaded into the LDS per sweep, out[4] = local cycles, out[5] = local segments.  Returns the number of values written.
+// rows loaded into the LDS per sweep, out[4] = local cycles, out[5] = local segments; then which path the column sums take (tests): out[6] = lanes per
+// segment (colsum_cl), out[7] = nodes with a workgroup each (colsum_long), out[8] = nodes visited (colsum_nodes), out[9] = colsum_fx_bits -- zeros on
+// the gather layout, which has no column-sum pass.  Returns the number of values written.
 int desc_pgd_layout_stats(const desc_pgd* h, int64_t* out, int32_t cap) {
     if (!h || !out) return fail(DESC_ERR_INVALID, "NULL argument");
-    const int64_t v[6] = {h->colsum_entries, h->n_pieces, h->n_bands, h->piece_row_entries, local_cycles(h), h->variant == VARIANT_NODE ? h->seg_hi - h->seg_lo : h->m_pos};
+    const bool node = h->variant == VARIANT_NODE;
+    const int64_t v[10] = {h->colsum_entries, h->n_pieces, h->n_bands, h->piece_row_entries, local_cycles(h), node ? h->seg_hi - h->seg_lo : h->m_pos,
+                           node ? h->colsum_cl : 0, node ? h->colsum_long : 0, node ? h->colsum_nodes : 0, node ? h->colsum_fx_bits : 0};
     int k = 0;
-    for (; k < 6 && k < cap; ++k) out[k] = v[k];
+    for (; k < 10 && k < cap; ++k) out[k] = v[k];
     return k;
 }
 

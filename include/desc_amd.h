@@ -213,7 +213,10 @@ int desc_pgd_get_s0(desc_pgd* h, double* s0 /* m_cycle */);       /* S0_long    
 int desc_pgd_sizes(const desc_pgd* h, int64_t* m, int64_t* m_pos, int64_t* m_cycle, int32_t* max_cnt);
 /* what this handle's layout streams per iteration (bench.py's `floor_bytes`): out[0] = (cycle, endpoint) pairs the mirror-sum pass reads
  * (DESC_PGD.m:185-191: cycles whose mirror was sampled), out[1] = pieces of the band sweep, out[2] = bands, out[3] = CSR entries of band rows
- * staged in the LDS per sweep, out[4] / out[5] = cycles / segments this rank owns.  Returns how many values were written (<= cap). */
+ * staged in the LDS per sweep, out[4] / out[5] = cycles / segments this rank owns; then how the mirror-sum pass runs on this handle (diagnostics):
+ * out[6] = lanes per segment of its kernel instance (8 or 16), out[7] = nodes that get a workgroup each, out[8] = nodes it visits (the
+ * out[8] - out[7] others: a wave each), out[9] = bits behind the binary point of the 64-bit fixed-point sums, 62 - ceil(log2(max degree + 1));
+ * all four are 0 on a handle without the node layout.  Returns how many values were written (<= cap, <= 10). */
 int desc_pgd_layout_stats(const desc_pgd* h, int64_t* out, int32_t cap);
 /* name of the main-sweep kernel variant chosen for this handle (rocprof cross-reference) */
 const char* desc_pgd_kernel_name(const desc_pgd* h);

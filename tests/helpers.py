@@ -43,9 +43,35 @@ def assert_structure_equal(a, b):
         assert np.array_equal(a[key], b[key]), key
 
 
-def emulate_sharded(lib, nn, ii, jj, rij, p, world, check_every=5, where=None, nmin=30):
+def csr(nn, ii, jj):
+    """CSR adjacency (neighbours ascending) with the edge id of every slot, as the library builds it: (rowptr, adj, adj_eid, row_of)."""
+    m = ii.shape[0]
+    src = np.concatenate([ii, jj]); dst = np.concatenate([jj, ii]); eid = np.concatenate([np.arange(m), np.arange(m)])
+    order = np.lexsort((dst, src))
+    rowptr = np.zeros(nn + 1, dtype=np.int64)
+    np.add.at(rowptr, src + 1, 1)
+    return np.cumsum(rowptr), dst[order], eid[order], src[order]
+
+
+def reduce_scatter_by_hand(shards):
+    """The reduce-scatter of the mirror sums between emulated ranks, part by part (desc_shard_info.xparts): blocks [c * world, (c + 1) * world)
+    of every rank's T, added -> block c of every rank's T_recv."""
+    import torch
+    world = len(shards)
+    Lp, X = shards[0].info.t_part, shards[0].info.xparts
+    for c in range(X):
+        tot = torch.zeros(world * Lp, dtype=shards[0].T.dtype, device=shards[0].T.device)
+        for s in shards:
+            tot += s.T[c * world * Lp:(c + 1) * world * Lp]
+        for r, s in enumerate(shards):
+            s.T_recv[c * Lp:(c + 1) * Lp].copy_(tot.view(world, Lp)[r])
+
+
+def emulate_sharded(lib, nn, ii, jj, rij, p, world, check_every=5, where=None, nmin=30, probe=None):
     """`world` ranks emulated in one process on one GPU: every rank's shard on the same card and stream, the collectives done by hand
-    between their exchange buffers.  Returns every rank's download (with the sweep it launched last) and its (seg_lo, seg_hi, cyc_lo, cyc_hi)."""
+    between their exchange buffers.  Returns every rank's download (with the sweep it launched last) and its (seg_lo, seg_hi, cyc_lo, cyc_hi).
+    probe(shards), if given, is called after the iteration loop and before the final objective exchange, inside the ranks' stream context:
+    the shards then hold the weights of the last sweep (tests/test_gpu_colsum.py reads the column sums there)."""
     import torch
     from desc_amd.sharded import HipShard
     prob = lib.ProblemArrays(nn, ii, jj, rij)
@@ -63,15 +89,6 @@ def emulate_sharded(lib, nn, ii, jj, rij, p, world, check_every=5, where=None, n
             for s in shards:
                 s.sall.view(world, L)[r].copy_(piece)
 
-    def reduce_scatter():                                    # part by part (desc_shard_info.xparts): blocks [c * world, (c + 1) * world) -> block c
-        Lp, X = shards[0].info.t_part, shards[0].info.xparts
-        for c in range(X):
-            tot = torch.zeros(world * Lp, dtype=shards[0].T.dtype, device=shards[0].T.device)
-            for s in shards:
-                tot += s.T[c * world * Lp:(c + 1) * world * Lp]
-            for r, s in enumerate(shards):
-                s.T_recv[c * Lp:(c + 1) * Lp].copy_(tot.view(world, Lp)[r])
-
     for s in shards: s.reset(p)
     for s in shards: s.finish(1)
     all_gather()
@@ -81,7 +98,7 @@ def emulate_sharded(lib, nn, ii, jj, rij, p, world, check_every=5, where=None, n
         n = min(left, check_every)
         for _ in range(n):
             for s in shards: s.colsum()
-            reduce_scatter()
+            reduce_scatter_by_hand(shards)
             for s in shards: s.sweep()
             all_gather()
             for s in shards: s.finish(0)
@@ -90,6 +107,13 @@ def emulate_sharded(lib, nn, ii, jj, rij, p, world, check_every=5, where=None, n
         assert len(set(flags)) == 1
         if left > 0 and flags[0]:
             break
+    if probe is not None:
+        try:
+            probe(shards)
+        except BaseException:                                # a failing probe leaves neither the stream context nor the shards behind
+            ctx.__exit__(None, None, None)
+            for s in shards: s.destroy()
+            raise
     for s in shards: s.objective(0)
     all_gather()
     for s in shards: s.objective(1)

@@ -8,7 +8,7 @@ import socket
 import numpy as np
 import pytest
 
-from tests.helpers import c_params, emulate_sharded as _emulate, make_problem, oracle_reference, run_unsharded as _unsharded
+from tests.helpers import c_params, csr as _csr, emulate_sharded as _emulate, make_problem, oracle_reference, run_unsharded as _unsharded
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
@@ -209,16 +209,6 @@ def test_sharded_band_sweep_emulated(lib, oracle, world, case, monkeypatch):
     dst.free()
     assert "one-rank" in one["last_sweep"] and one["iters_run"] == outs[0]["iters_run"]
     assert np.array_equal(one["S_vec"], outs[0]["S_vec"])
-
-
-def _csr(nn, ii, jj):
-    """CSR adjacency (neighbours ascending) with the edge id of every slot, as the library builds it."""
-    m = ii.shape[0]
-    src = np.concatenate([ii, jj]); dst = np.concatenate([jj, ii]); eid = np.concatenate([np.arange(m), np.arange(m)])
-    order = np.lexsort((dst, src))
-    rowptr = np.zeros(nn + 1, dtype=np.int64)
-    np.add.at(rowptr, src + 1, 1)
-    return np.cumsum(rowptr), dst[order], eid[order], src[order]
 
 
 @pytest.mark.parametrize("world,row_cap", [(2, 700), (3, 700), (8, 700), (8, 0)])
