@@ -1,6 +1,8 @@
-// Host part shared by the batched calls that walk per-problem CSR rows (gcw_batch.hip, cemp_batch.hip, mpls_batch.hip, mst_batch.hip, refine_batch.hip, irls_batch.hip, lp_batch.hip, batch_structure.hip):
-// validation, offsets and the CSR of every problem with LOCAL node and edge ids -- what desc_gcw_batch_csr returns -- and the host
-// loops every batched call repeats.  No device: the device half of a handle is BatchDevice (batch_device.h).
+// Host part shared by the batched calls that walk per-problem CSR rows: validation, offsets and the CSR of every problem with LOCAL node
+// and edge ids -- what desc_gcw_batch_csr returns -- and the host loops every batched call repeats.  No device: the device half of a
+// handle is BatchDevice (batch_device.h).  The builders are called by the resident problem set (problem_batch.hip: the eigen-solve, the
+// refinement, CEMP with MPLS and IRLS are created on a set and call none themselves) and by the calls that stay off a set:
+// mst_batch.hip, lp_batch.hip, batch_structure.hip.
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -14,7 +16,8 @@ struct BatchCsr {
     int32_t count = 0, max_n = 0;
     hvec<int64_t> node_off, edge_off;
     hvec<int32_t> ii, jj;                     // local endpoints of every problem behind one another (host checks, the refusal's node)
-    hvec<int32_t> rowptr, adj, adj_eid;       // per-problem CSR, local ids: rowptr of problem b at node_off[b] + b
+    hvec<int32_t> rowptr, adj, adj_eid;       // per-problem CSR, local ids: rowptr of problem b at node_off[b] + b; filled by batch_csr_host
+                                              // alone -- a handle on a set (pb_share_host) leaves them empty
     int64_t N = 0, M = 0;
 };
 

@@ -83,6 +83,7 @@ struct desc_cemp_batch : desc::BatchCsr, desc::BatchDevice {
     desc::CbArgs a{};
     double ms_build = 0;
     desc::MbLoop loop;
-    std::shared_ptr<desc::PbSet> set;         // desc_cemp_batch_create_on: the owner of the CSR, a.ii / a.jj and a.rij
+    std::shared_ptr<desc::PbSet> set;         // the owner of the CSR, a.ii / a.jj and a.rij
+    bool own_set = false;                     // the handle made the set from a problem list and is its only owner
     ~desc_cemp_batch() { close(); }           // the stream drains before the set may go
 };

@@ -2,7 +2,8 @@
 //
 // cemp.hip solves one problem per call: the device sampler's bitmap / rank / codegree launches, a histogram read-back, allocations, the S0
 // launch, max_iter round launches, one synchronise and one download -- a latency chain of a few milliseconds for a 100-node graph.  Here
-// the edge lists of all B problems lie behind one another and TWO kernels walk the concatenation, one wave per edge:
+// the edge lists of all B problems lie behind one another -- in the resident problem set (problem_batch.h) the handle is created on, the
+// caller's or one made from the caller's problem list -- and TWO kernels walk the concatenation, one wave per edge:
 //
 //   k_cemp_batch_build  CEMP.m:44-103, ONE launch in create.  The wave of edge (i, j) finds its problem through a per-edge table, intersects
 //                       the CSR rows of i and j in ascending k (lanes stride over the shorter row and binary-search the longer one, hits are
@@ -106,8 +107,8 @@ using namespace desc;
 
 namespace {
 
-// The sample arrays and CEMP.m:44-103 for the whole batch, behind either create: the problems' arrays are on the device or on their way
-// there on the handle's stream, t1 is when the device part began.
+// The sample arrays and CEMP.m:44-103 for the whole batch: the set's arrays are on the device, the handle's own are on their way there
+// on its stream, t1 is when the handle's device part began.
 int cb_build(desc_cemp_batch* h, std::chrono::steady_clock::time_point t1) {
     CbArgs& a = h->a;
     const int32_t nsample = h->nsample;
@@ -116,7 +117,7 @@ int cb_build(desc_cemp_batch* h, std::chrono::steady_clock::time_point t1) {
     if ((rc = h->mem.alloc(&a.e_jk, MC)) || (rc = h->mem.alloc(&a.e_ki, MC)) || (rc = h->mem.alloc(&a.S0, MC)) || (rc = h->mem.alloc(&a.S_init, M)) ||
         (rc = h->mem.alloc(&a.S_a, M)) || (rc = h->mem.alloc(&a.S_b, M)) || (rc = h->mem.alloc(&a.has_cycle, M))) return rc;
     DESC_HIP(hipStreamSynchronize(h->stream));         // the caller's staging vectors may go
-    h->ms_upload = ms_since(t1);
+    h->ms_upload = ms_since(t1) + (h->own_set ? h->set->ms_upload : 0);
 
     // ---- CEMP.m:44-103 for the whole batch: one launch
     auto t2 = std::chrono::steady_clock::now();
@@ -143,14 +144,22 @@ int cb_check_samples(const desc_cemp_batch* h, int32_t nsample) {
     return DESC_OK;
 }
 
-// On a resident set: the degree cap from the set's host row starts where it has them, else from a count over its host endpoints (a
-// device-built CSR stays on the device); the uploads are the CbProb records; the edge -> problem map is formed by a launch
+// The one create body, on a resident set: the caller's (desc_cemp_batch_create_on, probs = NULL), or one the handle makes from probs and
+// owns alone (the list path).  The degree cap from the set's host row starts where it has them, else from a count over its host
+// endpoints (a device-built CSR stays on the device); the uploads are the CbProb records; the edge -> problem map is formed by a launch
 // (batch_kernels.h); the CSR, the endpoints and the rotations are the set's.
-int cb_create_on(const std::shared_ptr<PbSet>& set, int32_t nsample, uint64_t seed, const uint64_t* seeds, desc_cemp_batch* h) {
+int cb_create(const desc_problem* probs, int32_t count, int32_t device, std::shared_ptr<PbSet> set, int32_t nsample, uint64_t seed, const uint64_t* seeds,
+              desc_cemp_batch* h) {
     auto t0 = std::chrono::steady_clock::now();
     h->nsample = nsample;
     if (nsample < 1) return fail(DESC_ERR_INVALID, "need nsample >= 1");
-    const int32_t count = set->count;
+    int rc;
+    h->own_set = !set;
+    if (h->own_set) {
+        set = std::make_shared<PbSet>();
+        if ((rc = pb_host_part(probs, count, DESC_BUILD_HOST, nullptr, set.get()))) return rc;
+    }
+    count = set->count;
     hvec<int32_t> deg;
     for (int32_t b = 0; b < count; ++b) {
         const int64_t no = set->node_off[(size_t)b], n = set->node_off[(size_t)b + 1] - no;
@@ -166,15 +175,19 @@ int cb_create_on(const std::shared_ptr<PbSet>& set, int32_t nsample, uint64_t se
             h->max_deg = std::max(h->max_deg, d);
         }
     }
-    pb_share_host(*set, h);
-    int rc = cb_check_samples(h, nsample);
-    if (rc) return rc;
+    h->set = set;
+    pb_share_host(*set, h, !h->own_set);             // an own set: h->ii / h->jj stay EMPTY until pb_take_endpoints below -- read set->ii / set->jj till then
+    if ((rc = cb_check_samples(h, nsample))) return rc;
     h->ms_structure = ms_since(t0);
     if (count == 0) return DESC_OK;
 
-    if ((rc = h->open(set->device, "the batched CEMP"))) return rc;        // nothing above touched the device
+    const char* what = "the batched CEMP";
+    if (h->own_set) {                                  // nothing above touched the device
+        if ((rc = pb_device_part(probs, device, what, set.get()))) return rc;
+        pb_take_endpoints(*set, h);
+    }
+    if ((rc = h->open(set->device, what))) return rc;
     auto t1 = std::chrono::steady_clock::now();
-    h->set = set;
     hvec<CbProb> pr((size_t)count);
     for (int32_t b = 0; b < count; ++b)
         pr[(size_t)b] = CbProb{(int32_t)(set->node_off[(size_t)b + 1] - set->node_off[(size_t)b]), (int32_t)(set->edge_off[(size_t)b + 1] - set->edge_off[(size_t)b]),
@@ -186,44 +199,6 @@ int cb_create_on(const std::shared_ptr<PbSet>& set, int32_t nsample, uint64_t se
     DESC_HIP(hipGetLastError());
     a.eprob = d_eprob; a.ii = set->d_ii; a.jj = set->d_jj; a.rowptr = set->d_rowptr; a.adj = set->d_adj; a.adj_eid = set->d_adj_eid; a.rij = set->d_rij;
     return cb_build(h, t1);                            // drains the stream while pr is in scope
-}
-
-int cb_create(const desc_problem* probs, int32_t count, int32_t nsample, uint64_t seed, const uint64_t* seeds, int32_t device, desc_cemp_batch* h) {
-    auto t0 = std::chrono::steady_clock::now();
-    h->nsample = nsample;
-    if (nsample < 1) return fail(DESC_ERR_INVALID, "need nsample >= 1");
-    // ---- host: validation, the per-problem CSR, the degree maxima
-    int rc = batch_csr_host(probs, count, nullptr, h);
-    if (rc) return rc;
-    for (int32_t b = 0; b < count; ++b) {
-        const int32_t* rp = h->rowptr.data() + h->node_off[(size_t)b] + b;
-        for (int64_t v = 0; v < probs[b].n; ++v) {
-            const int32_t d = rp[v + 1] - rp[v];
-            if (d > CEMP_BATCH_MAX_DEGREE) return cb_degree_refusal(b, v, d);
-            h->max_deg = std::max(h->max_deg, d);
-        }
-    }
-    if ((rc = cb_check_samples(h, nsample))) return rc;
-    h->ms_structure = ms_since(t0);
-    if (count == 0) return DESC_OK;
-
-    if ((rc = h->open(device, "the batched CEMP"))) return rc;             // nothing above touched the device
-    auto t1 = std::chrono::steady_clock::now();
-    const size_t M = (size_t)h->M;
-    hvec<CbProb> pr((size_t)count);
-    hvec<int32_t> eprob(M);
-    for (int32_t b = 0; b < count; ++b) {
-        const size_t eo = (size_t)h->edge_off[(size_t)b], m = (size_t)probs[b].m;
-        pr[(size_t)b] = CbProb{(int32_t)probs[b].n, (int32_t)m, (int32_t)h->node_off[(size_t)b], (int32_t)eo, seeds ? seeds[b] : seed};
-        std::fill(eprob.begin() + eo, eprob.begin() + eo + m, b);
-    }
-    const hvec<double> rij = stage_rotations(probs, count, h->edge_off);
-    CbArgs& a = h->a;
-    if ((rc = h->upload(&a.prob, pr.data(), pr.size())) || (rc = h->upload(&a.eprob, eprob.data(), M)) ||
-        (rc = h->upload(&a.ii, h->ii.data(), M)) || (rc = h->upload(&a.jj, h->jj.data(), M)) ||
-        (rc = h->upload(&a.rowptr, h->rowptr.data(), h->rowptr.size())) || (rc = h->upload(&a.adj, h->adj.data(), 2 * M)) ||
-        (rc = h->upload(&a.adj_eid, h->adj_eid.data(), 2 * M)) || (rc = h->upload(&a.rij, rij.data(), 9 * M))) return rc;
-    return cb_build(h, t1);                            // drains the stream while the staging vectors above are in scope
 }
 
 int cb_run(desc_cemp_batch* h, const double* beta, int32_t n_beta, int32_t max_iter, double* s_vec, desc_cemp_batch_timings* tm) {
@@ -260,19 +235,17 @@ int32_t desc_cemp_batch_max_degree(void) { return CEMP_BATCH_MAX_DEGREE; }
 int desc_cemp_batch_create(const desc_problem* probs, int32_t count, int32_t nsample, uint64_t seed, const uint64_t* seeds, int32_t device,
                            desc_cemp_batch** out) {
     return batch_create_guarded("desc_cemp_batch_create", out, probs, count,
-                                [&](desc_cemp_batch* h) { return cb_create(probs, count, nsample, seed, seeds, device, h); });
+                                [&](desc_cemp_batch* h) { return cb_create(probs, count, device, nullptr, nsample, seed, seeds, h); });
 }
 
 int desc_cemp_batch_create_on(desc_problem_batch* set, int32_t nsample, uint64_t seed, const uint64_t* seeds, desc_cemp_batch** out) {
     return batch_create_guarded("desc_cemp_batch_create_on", out, set, 0,
-                                [&](desc_cemp_batch* h) { return cb_create_on(set->s, nsample, seed, seeds, h); }, set != nullptr);
+                                [&](desc_cemp_batch* h) { return cb_create(nullptr, 0, 0, set->s, nsample, seed, seeds, h); }, set != nullptr);
 }
 
 int desc_cemp_batch_bytes(const desc_cemp_batch* h, int64_t* h2d, int64_t* d2h) {
     if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
-    if (h2d) *h2d = h->bytes_h2d;
-    if (d2h) *d2h = h->bytes_d2h;
-    return DESC_OK;
+    return batch_bytes_on_set(*h, h->own_set ? h->set.get() : nullptr, h2d, d2h);
 }
 
 int desc_cemp_batch_sizes(const desc_cemp_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off) {

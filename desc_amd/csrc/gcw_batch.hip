@@ -10,7 +10,7 @@
 // problem of the batch; a problem addresses it with its own n, so nothing it computes depends on that size.  The cap GCW_BATCH_MAX_N is
 // the largest n that fits the 160 KiB a workgroup may declare.
 //
-// Operator.  Each problem has its own CSR (local ids, built on the host in create).  The workgroup forms the weights 1/(S^1.5 + 1e-8),
+// Operator.  Each problem has its own CSR (local ids), the resident problem set's (problem_batch.h) the handle is created on.  The workgroup forms the weights 1/(S^1.5 + 1e-8),
 // the weighted degrees, D^-1/2 and the 2m blocks w dinv_v dinv_u R (k_assemble_blocks of spectral.hip) once into global memory, 72
 // contiguous bytes per slot, and reads them in every product.  The product gives thread (v, c) the three entries of node row v in column
 // c: it walks the row's slots in CSR order with plain f64 FMAs -- no partial sums to combine, so the order of additions is the CSR's.
@@ -66,11 +66,10 @@ inline size_t gb_lds_bytes(int n) { return sizeof(double) * ((size_t)4 * 3 * BW 
 
 inline size_t gb_streamed_lds_bytes(int n) { return sizeof(double) * ((size_t)3 * BW * (size_t)n + GB_SCRATCH); }
 
-struct GbProb { int32_t n, m; int64_t node_off, edge_off; };
 struct GbInfo { int32_t iters, products, converged, status; double residual, eig[3]; };       // status: 1 degenerate start basis, 2 breakdown
 
 struct GbArgs {
-    const GbProb* prob;
+    const PbProb* prob;
     const int32_t* rowptr;      // problem b's n_b + 1 row starts at node_off[b] + b, counted inside the problem
     const int32_t* adj;         // 2 m_b local neighbour ids at 2 edge_off[b]
     const int32_t* adj_eid;     // 2 m_b local edge ids
@@ -213,7 +212,7 @@ template <bool STREAM>
 __global__ __launch_bounds__(256, 2) void k_gcw_batch(GbArgs a) {
     extern __shared__ double gb_lds[];
     const int b = a.list ? a.list[blockIdx.x] : (int)blockIdx.x, tid = threadIdx.x;
-    const GbProb pd = a.prob[b];
+    const PbProb pd = a.prob[b];
     const int n = pd.n, m = pd.m, rows = 3 * n;
     const int32_t* rowptr = a.rowptr + pd.node_off + b;
     const int32_t* adj = a.adj + 2 * pd.edge_off;
@@ -430,10 +429,11 @@ int batch_csr_host(const desc_problem* probs, int32_t count, const std::function
 
 using namespace desc;
 
-struct desc_gcw_batch : desc::BatchCsr, desc::BatchDevice {     // offsets and the per-problem CSR (local ids); device, stream, arena, events
-    GbProb* d_prob = nullptr;
-    int32_t *d_rowptr = nullptr, *d_adj = nullptr, *d_adj_eid = nullptr;
-    double *d_rij = nullptr, *d_in = nullptr, *d_w = nullptr, *d_dinv = nullptr, *d_blocks = nullptr, *d_V = nullptr;
+struct desc_gcw_batch : desc::BatchCsr, desc::BatchDevice {     // the set's offsets and endpoints; device, stream, arena, events
+    const PbProb* d_prob = nullptr;
+    const int32_t *d_rowptr = nullptr, *d_adj = nullptr, *d_adj_eid = nullptr;
+    const double* d_rij = nullptr;
+    double *d_in = nullptr, *d_w = nullptr, *d_dinv = nullptr, *d_blocks = nullptr, *d_V = nullptr;
     GbInfo* d_info = nullptr;
     // which kernel solves which problem (a function of the problem's own n and the mode alone); the lists are uploaded only where both run
     int32_t eig = DESC_GCW_EIG_LDS;
@@ -441,7 +441,8 @@ struct desc_gcw_batch : desc::BatchCsr, desc::BatchDevice {     // offsets and t
     int32_t max_n_lds = 0, max_n_streamed = 0;
     int32_t *d_lds_list = nullptr, *d_streamed_list = nullptr;
     double* d_work = nullptr;
-    std::shared_ptr<desc::PbSet> set;         // desc_gcw_batch_create_on: the owner of d_prob, the CSR and d_rij
+    std::shared_ptr<desc::PbSet> set;         // the owner of d_prob, the CSR and d_rij
+    bool own_set = false;                     // the handle made the set from a problem list and is its only owner
     ~desc_gcw_batch() { close(); }            // the stream drains before the set may go
 };
 
@@ -475,18 +476,7 @@ void gb_split(desc_gcw_batch* h) {
     }
 }
 
-// validation, offsets and the per-problem CSR, the split of the batch between the two kernels: no device
-int gb_host_part(const desc_problem* probs, int32_t count, int32_t eig, desc_gcw_batch* h) {
-    int rc = gb_check_eig(eig);
-    if (rc) return rc;
-    h->eig = eig;
-    rc = batch_csr_host(probs, count, [eig](int32_t b, const desc_problem& q) -> int { return gb_check_n(eig, b, q.n); }, h);
-    if (rc) return rc;
-    gb_split(h);
-    return DESC_OK;
-}
-
-// the run's own buffers, the same behind either create
+// the run's own buffers
 int gb_alloc_work(desc_gcw_batch* h) {
     const size_t M = (size_t)h->M, N = (size_t)h->N;
     int rc;
@@ -501,53 +491,40 @@ int gb_alloc_work(desc_gcw_batch* h) {
     return DESC_OK;
 }
 
-// On a resident set: the refusals of gb_host_part that the set has not made already, then nothing but the run's buffers -- d_prob (the
-// set's record is GbProb's), the CSR and the rotations are the set's.
-int gb_create_on(const std::shared_ptr<PbSet>& set, int32_t eig, desc_gcw_batch* h) {
+// The one create body, on a resident set: the caller's (desc_gcw_batch_create_on, probs = NULL), or one the handle makes from probs and
+// owns alone (the list path; the cap is then refused per problem inside the set's host part, between the other refusals of that
+// problem).  The handle adds nothing but the run's buffers: d_prob, the CSR and the rotations are the set's.
+int gb_create(const desc_problem* probs, int32_t count, int32_t device, std::shared_ptr<PbSet> set, int32_t eig, desc_gcw_batch* h) {
     auto t0 = std::chrono::steady_clock::now();
-    static_assert(sizeof(GbProb) == sizeof(PbProb), "the set's problem record is the eigen-solve's");
     int rc = gb_check_eig(eig);
     if (rc) return rc;
     h->eig = eig;
-    for (int32_t b = 0; b < set->count; ++b)
-        if ((rc = gb_check_n(eig, b, set->node_off[(size_t)b + 1] - set->node_off[(size_t)b]))) return rc;
-    pb_share_host(*set, h);
+    h->own_set = !set;
+    if (h->own_set) {
+        set = std::make_shared<PbSet>();
+        rc = pb_host_part(probs, count, DESC_BUILD_HOST, [eig](int32_t b, const desc_problem& q) -> int { return gb_check_n(eig, b, q.n); }, set.get());
+        if (rc) return rc;
+    } else {
+        for (int32_t b = 0; b < set->count; ++b)
+            if ((rc = gb_check_n(eig, b, set->node_off[(size_t)b + 1] - set->node_off[(size_t)b]))) return rc;
+    }
+    h->set = set;
+    pb_share_host(*set, h, !h->own_set);             // an own set: h->ii / h->jj stay EMPTY until pb_take_endpoints below -- read set->ii / set->jj till then
     gb_split(h);
     h->ms_structure = ms_since(t0);
     if (h->count == 0) return DESC_OK;
 
-    if ((rc = h->open(set->device, "the batched eigen-solve"))) return rc;  // nothing above touched the device
+    const char* what = "the batched eigen-solve";
+    if (h->own_set) {                                  // nothing above touched the device
+        if ((rc = pb_device_part(probs, device, what, set.get()))) return rc;
+        pb_take_endpoints(*set, h);
+    }
+    if ((rc = h->open(set->device, what))) return rc;
     auto t1 = std::chrono::steady_clock::now();
-    h->set = set;
-    h->d_prob = reinterpret_cast<GbProb*>(set->d_prob);
-    h->d_rowptr = set->d_rowptr; h->d_adj = set->d_adj; h->d_adj_eid = set->d_adj_eid; h->d_rij = set->d_rij;
+    h->d_prob = set->d_prob; h->d_rowptr = set->d_rowptr; h->d_adj = set->d_adj; h->d_adj_eid = set->d_adj_eid; h->d_rij = set->d_rij;
     if ((rc = gb_alloc_work(h))) return rc;
     DESC_HIP(hipStreamSynchronize(h->stream));         // the two lists may be on their way
-    h->ms_upload = ms_since(t1);
-    return DESC_OK;
-}
-
-int gb_create(const desc_problem* probs, int32_t count, int32_t device, int32_t eig, desc_gcw_batch* h) {
-    auto t0 = std::chrono::steady_clock::now();
-    int rc = gb_host_part(probs, count, eig, h);
-    if (rc) return rc;
-    h->ms_structure = ms_since(t0);
-    if (count == 0) return DESC_OK;
-
-    if ((rc = h->open(device, "the batched eigen-solve"))) return rc;      // nothing above touched the device
-    auto t1 = std::chrono::steady_clock::now();
-    const size_t M = (size_t)h->M;
-    hvec<GbProb> pr((size_t)count);
-    for (int32_t b = 0; b < count; ++b) pr[(size_t)b] = GbProb{(int32_t)probs[b].n, (int32_t)probs[b].m, h->node_off[(size_t)b], h->edge_off[(size_t)b]};
-    const hvec<double> rij = stage_rotations(probs, count, h->edge_off);
-    if ((rc = h->upload(&h->d_prob, pr.data(), pr.size()))) return rc;
-    if ((rc = h->upload(&h->d_rowptr, h->rowptr.data(), h->rowptr.size()))) return rc;
-    if ((rc = h->upload(&h->d_adj, h->adj.data(), 2 * M))) return rc;
-    if ((rc = h->upload(&h->d_adj_eid, h->adj_eid.data(), 2 * M))) return rc;
-    if ((rc = h->upload(&h->d_rij, rij.data(), 9 * M))) return rc;
-    if ((rc = gb_alloc_work(h))) return rc;
-    DESC_HIP(hipStreamSynchronize(h->stream));         // the staging vectors go out of scope below
-    h->ms_upload = ms_since(t1);
+    h->ms_upload = ms_since(t1) + (h->own_set ? set->ms_upload : 0);
     return DESC_OK;
 }
 
@@ -640,23 +617,21 @@ int32_t desc_gcw_batch_streamed_max_n(void) { return GCW_BATCH_STREAMED_MAX_N; }
 
 int desc_gcw_batch_create(const desc_problem* probs, int32_t count, int32_t device, desc_gcw_batch** out) {
     return batch_create_guarded("desc_gcw_batch_create", out, probs, count,
-                                [&](desc_gcw_batch* h) { return gb_create(probs, count, device, DESC_GCW_EIG_LDS, h); });
+                                [&](desc_gcw_batch* h) { return gb_create(probs, count, device, nullptr, DESC_GCW_EIG_LDS, h); });
 }
 
 int desc_gcw_batch_create_where(const desc_problem* probs, int32_t count, int32_t device, int32_t eig, desc_gcw_batch** out) {
     return batch_create_guarded("desc_gcw_batch_create_where", out, probs, count,
-                                [&](desc_gcw_batch* h) { return gb_create(probs, count, device, eig, h); });
+                                [&](desc_gcw_batch* h) { return gb_create(probs, count, device, nullptr, eig, h); });
 }
 
 int desc_gcw_batch_create_on(desc_problem_batch* set, int32_t eig, desc_gcw_batch** out) {
-    return batch_create_guarded("desc_gcw_batch_create_on", out, set, 0, [&](desc_gcw_batch* h) { return gb_create_on(set->s, eig, h); }, set != nullptr);
+    return batch_create_guarded("desc_gcw_batch_create_on", out, set, 0, [&](desc_gcw_batch* h) { return gb_create(nullptr, 0, 0, set->s, eig, h); }, set != nullptr);
 }
 
 int desc_gcw_batch_bytes(const desc_gcw_batch* h, int64_t* h2d, int64_t* d2h) {
     if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
-    if (h2d) *h2d = h->bytes_h2d;
-    if (d2h) *d2h = h->bytes_d2h;
-    return DESC_OK;
+    return batch_bytes_on_set(*h, h->own_set ? h->set.get() : nullptr, h2d, d2h);
 }
 
 int desc_gcw_batch_sizes(const desc_gcw_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off) {
@@ -667,8 +642,8 @@ int desc_gcw_batch_sizes(const desc_gcw_batch* h, int32_t* count, int64_t* node_
 int desc_gcw_batch_csr(const desc_problem* probs, int32_t count, int64_t* node_off, int64_t* edge_off, int32_t* rowptr, int32_t* adj, int32_t* adj_eid) {
     return no_throw("desc_gcw_batch_csr", [&]() -> int {
         if (count < 0 || (count > 0 && !probs) || !node_off || !edge_off) return fail(DESC_ERR_INVALID, "NULL argument or negative count");
-        desc_gcw_batch h;
-        int rc = gb_host_part(probs, count, DESC_GCW_EIG_LDS, &h);
+        BatchCsr h;
+        int rc = batch_csr_host(probs, count, [](int32_t b, const desc_problem& q) -> int { return gb_check_n(DESC_GCW_EIG_LDS, b, q.n); }, &h);
         if (rc) return rc;
         batch_sizes(h, nullptr, node_off, edge_off);
         if (rowptr) std::copy(h.rowptr.begin(), h.rowptr.end(), rowptr);

@@ -14,7 +14,9 @@
 // PCG's r z p q) and the 26 of laa_wg.h in the reweighted stage, over the same block; a problem addresses it with its own n.  The
 // per-edge arrays (QQ, B, w and the sixteen m x 3 arrays of the primal-dual state) lie in global memory at the problem's edge offset.
 // The graph part of the spanning-tree start is host work (create): the passes over the edges in the caller's row order give a
-// sequence of (edge, direction), which one thread walks with irls_tree_step.
+// sequence of (edge, direction), which one thread walks with irls_tree_step.  The problems themselves (records, CSR, endpoints,
+// rotations) are those of the resident problem set (problem_batch.h) the handle is created on, the caller's or one made from the
+// caller's problem list; signs, edge -> problem map and identity row orders come from it by launches (batch_kernels.h).
 //
 // Arithmetic and summation orders.  Every per-element expression and every scalar rule is the text of irls_math.h and laa_math.h,
 // which irls.hip and laa.hip call too.  The sums keep the single path's orders:
@@ -64,7 +66,6 @@ constexpr int IB_EDGE_ARRAYS = 16;                     // Ax u f1 f2 l1 l2 w2 s1
 
 inline size_t ib_lds_bytes(int n) { return sizeof(double) * (size_t)IB_NODE_DOUBLES * (size_t)n; }
 
-struct IbProb { int32_t n, m; int64_t node_off, edge_off; };
 // status: 0 done, -1 the workgroup never finished
 struct IbInfo {
     int32_t status, l1_iters, irls_iters, pd_steps, pd_ill, pd_stuck, pd_solves, cg_l1, cg_irls, cg_unconverged;
@@ -72,7 +73,7 @@ struct IbInfo {
 };
 
 struct IbArgs {
-    const IbProb* prob;
+    const PbProb* prob;
     const int32_t* rowptr;      // problem b's n_b + 1 row starts at node_off[b] + b, counted inside the problem
     const int32_t* adj;         // 2 m_b local neighbour ids at 2 edge_off[b]
     const int32_t* adj_eid;     // 2 m_b local edge ids
@@ -305,7 +306,7 @@ __global__ __launch_bounds__(256) void k_irls_batch(IbArgs a) {
     __shared__ double sh_ext[24];
     __shared__ double sh_part3[3];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const IbProb pd = a.prob[b];
+    const PbProb pd = a.prob[b];
     const int n = uni(pd.n), m = uni(pd.m);
     const int32_t* ii = a.ii + pd.edge_off;
     const int32_t* jj = a.jj + pd.edge_off;
@@ -407,9 +408,9 @@ __global__ __launch_bounds__(256) void k_irls_batch(IbArgs a) {
     }
 }
 
-// desc_irls_batch_create_on with identity orders: order[edge_off[b] + e] = e, the caller's row of every edge, without an upload
-__global__ __launch_bounds__(256) void k_irls_identity_order(const IbProb* prob, int32_t* order) {
-    const IbProb pd = prob[blockIdx.x];
+// identity orders: order[edge_off[b] + e] = e, the caller's row of every edge, without an upload
+__global__ __launch_bounds__(256) void k_irls_identity_order(const PbProb* prob, int32_t* order) {
+    const PbProb pd = prob[blockIdx.x];
     for (int e = threadIdx.x; e < pd.m; e += 256) order[pd.edge_off + e] = e;
 }
 
@@ -418,18 +419,20 @@ __global__ __launch_bounds__(256) void k_irls_identity_order(const IbProb* prob,
 
 using namespace desc;
 
-struct desc_irls_batch : desc::BatchCsr, desc::BatchDevice {    // offsets and the per-problem CSR (local ids); device, stream, arena, events
+struct desc_irls_batch : desc::BatchCsr, desc::BatchDevice {    // the set's offsets and endpoints; device, stream, arena, events
     hvec<int32_t> order;                                // the caller's row of every edge, inside its problem
     hvec<int32_t> seq;                                  // the spanning-tree start: problem b's n_b - 1 entries at node_off[b] - b
     hvec<int32_t> flags0;                               // launch A's flags before the launch: {INT_MAX, 0} per problem
-    IbProb* d_prob = nullptr;
-    int32_t *d_rowptr = nullptr, *d_adj = nullptr, *d_adj_eid = nullptr, *d_ii = nullptr, *d_jj = nullptr, *d_seq = nullptr, *d_order = nullptr,
-            *d_eprob = nullptr, *d_flags = nullptr;
+    const PbProb* d_prob = nullptr;
+    const int32_t *d_rowptr = nullptr, *d_adj = nullptr, *d_adj_eid = nullptr, *d_ii = nullptr, *d_jj = nullptr;
+    int32_t *d_seq = nullptr, *d_order = nullptr, *d_eprob = nullptr, *d_flags = nullptr;
     int8_t* d_sgn = nullptr;
-    double *d_rij = nullptr, *d_P = nullptr, *d_B = nullptr, *d_w = nullptr, *d_edge = nullptr, *d_Rl1 = nullptr, *d_Rout = nullptr, *d_einfo = nullptr;
+    const double* d_rij = nullptr;
+    double *d_P = nullptr, *d_B = nullptr, *d_w = nullptr, *d_edge = nullptr, *d_Rl1 = nullptr, *d_Rout = nullptr, *d_einfo = nullptr;
     Quat* d_QQ = nullptr;
     IbInfo* d_info = nullptr;
-    std::shared_ptr<desc::PbSet> set;         // desc_irls_batch_create_on: the owner of d_prob, the CSR, d_ii / d_jj and d_rij
+    std::shared_ptr<desc::PbSet> set;         // the owner of d_prob, the CSR, d_ii / d_jj and d_rij
+    bool own_set = false;                     // the handle made the set from a problem list and is its only owner
     ~desc_irls_batch() { close(); }           // the stream drains before the set may go
 };
 
@@ -477,13 +480,6 @@ int ib_orders_and_trees(const desc_problem* probs, int32_t count, const int32_t*
     return DESC_OK;
 }
 
-// validation, offsets, the per-problem CSR and the tree sequences: no device
-int ib_host_part(const desc_problem* probs, int32_t count, const int32_t* const* orders, desc_irls_batch* h) {
-    int rc = batch_csr_host(probs, count, [](int32_t b, const desc_problem& q) -> int { return ib_check_n(b, q.n); }, h);
-    if (rc) return rc;
-    return ib_orders_and_trees(probs, count, orders, h);
-}
-
 void ib_flags0(desc_irls_batch* h) {
     h->flags0.resize(2 * (size_t)h->count);
     for (int32_t b = 0; b < h->count; ++b) { h->flags0[2 * (size_t)b] = INT_MAX; h->flags0[2 * (size_t)b + 1] = 0; }
@@ -500,7 +496,7 @@ int ib_check_lds(const desc_irls_batch* h) {
     return DESC_OK;
 }
 
-// the run's own buffers, the same behind either create; drains the stream
+// the run's own buffers; drains the stream
 int ib_alloc_work(desc_irls_batch* h) {
     const size_t M = (size_t)h->M, N = (size_t)h->N, count = (size_t)h->count;
     int rc;
@@ -515,22 +511,30 @@ int ib_alloc_work(desc_irls_batch* h) {
     return DESC_OK;
 }
 
-// On a resident set: the cap, then the row orders and the tree sequences from slices of the set's host endpoints (no rotation and no CSR
-// is read).  Uploads: the tree sequences, and the row orders only where one is not the identity; the problem records, the CSR, the
-// endpoints and the rotations are the set's; the signs, the edge -> problem map and identity orders are formed by launches.
-int ib_create_on(const std::shared_ptr<PbSet>& set, const int32_t* const* orders, desc_irls_batch* h) {
+// The one create body, on a resident set: the caller's (desc_irls_batch_create_on, probs = NULL), or one the handle makes from probs and
+// owns alone (the list path; the cap is then refused per problem inside the set's host part, between the other refusals of that
+// problem).  The row orders and the tree sequences come from slices of the set's host endpoints (no rotation and no CSR is read).
+// Uploads: the tree sequences, and the row orders only where one is not the identity; the problem records, the CSR, the endpoints and
+// the rotations are the set's; the signs, the edge -> problem map and identity orders are formed by launches.
+int ib_create(const desc_problem* probs, int32_t count, int32_t device, std::shared_ptr<PbSet> set, const int32_t* const* orders, desc_irls_batch* h) {
     auto t0 = std::chrono::steady_clock::now();
-    static_assert(sizeof(IbProb) == sizeof(PbProb), "the set's problem record is the batched IRLS's");
-    const int32_t count = set->count;
     int rc;
-    for (int32_t b = 0; b < count; ++b)
-        if ((rc = ib_check_n(b, set->node_off[(size_t)b + 1] - set->node_off[(size_t)b]))) return rc;
-    pb_share_host(*set, h);
+    h->own_set = !set;
+    if (h->own_set) {
+        set = std::make_shared<PbSet>();
+        if ((rc = pb_host_part(probs, count, DESC_BUILD_HOST, [](int32_t b, const desc_problem& q) -> int { return ib_check_n(b, q.n); }, set.get()))) return rc;
+    } else {
+        for (int32_t b = 0; b < set->count; ++b)
+            if ((rc = ib_check_n(b, set->node_off[(size_t)b + 1] - set->node_off[(size_t)b]))) return rc;
+    }
+    count = set->count;
+    h->set = set;
+    pb_share_host(*set, h, !h->own_set);             // an own set: h->ii / h->jj stay EMPTY until pb_take_endpoints below -- read set->ii / set->jj till then
     hvec<desc_problem> view((size_t)count);
     for (int32_t b = 0; b < count; ++b) {
         const size_t eo = (size_t)h->edge_off[(size_t)b];
         view[(size_t)b] = desc_problem{h->node_off[(size_t)b + 1] - h->node_off[(size_t)b], h->edge_off[(size_t)b + 1] - h->edge_off[(size_t)b],
-                                       h->ii.data() + eo, h->jj.data() + eo, nullptr};
+                                       set->ii.data() + eo, set->jj.data() + eo, nullptr};
     }
     if ((rc = ib_orders_and_trees(view.data(), count, orders, h))) return rc;
     bool identity = true;
@@ -540,12 +544,15 @@ int ib_create_on(const std::shared_ptr<PbSet>& set, const int32_t* const* orders
     h->ms_structure = ms_since(t0);
     if (count == 0) return DESC_OK;
 
-    if ((rc = h->open(set->device, "the batched IRLS"))) return rc;        // nothing above touched the device
+    const char* what = "the batched IRLS";
+    if (h->own_set) {                                  // nothing above touched the device
+        if ((rc = pb_device_part(probs, device, what, set.get()))) return rc;
+        pb_take_endpoints(*set, h);
+    }
+    if ((rc = h->open(set->device, what))) return rc;
     auto t1 = std::chrono::steady_clock::now();
     if ((rc = ib_check_lds(h))) return rc;
-    h->set = set;
-    h->d_prob = reinterpret_cast<IbProb*>(set->d_prob);
-    h->d_rowptr = set->d_rowptr; h->d_adj = set->d_adj; h->d_adj_eid = set->d_adj_eid; h->d_ii = set->d_ii; h->d_jj = set->d_jj;
+    h->d_prob = set->d_prob; h->d_rowptr = set->d_rowptr; h->d_adj = set->d_adj; h->d_adj_eid = set->d_adj_eid; h->d_ii = set->d_ii; h->d_jj = set->d_jj;
     h->d_rij = set->d_rij;
     const size_t M = (size_t)h->M;
     const dim3 grid((unsigned)count), block(256);
@@ -554,47 +561,11 @@ int ib_create_on(const std::shared_ptr<PbSet>& set, const int32_t* const* orders
         if ((rc = h->mem.alloc(&h->d_order, M))) return rc;
         hipLaunchKernelGGL(k_irls_identity_order, grid, block, 0, h->stream, h->d_prob, h->d_order);
     } else if ((rc = h->upload(&h->d_order, h->order.data(), M))) return rc;
-    hipLaunchKernelGGL(k_batch_sgn<IbProb>, grid, block, 0, h->stream, h->d_prob, h->d_rowptr, h->d_adj, h->d_sgn);
-    hipLaunchKernelGGL(k_batch_eprob<IbProb>, grid, block, 0, h->stream, h->d_prob, h->d_eprob);
+    hipLaunchKernelGGL(k_batch_sgn<PbProb>, grid, block, 0, h->stream, h->d_prob, h->d_rowptr, h->d_adj, h->d_sgn);
+    hipLaunchKernelGGL(k_batch_eprob<PbProb>, grid, block, 0, h->stream, h->d_prob, h->d_eprob);
     DESC_HIP(hipGetLastError());
     if ((rc = ib_alloc_work(h))) return rc;
-    h->ms_upload = ms_since(t1);
-    return DESC_OK;
-}
-
-int ib_create(const desc_problem* probs, int32_t count, const int32_t* const* orders, int32_t device, desc_irls_batch* h) {
-    auto t0 = std::chrono::steady_clock::now();
-    int rc = ib_host_part(probs, count, orders, h);
-    if (rc) return rc;
-    const size_t M = (size_t)h->M;
-    hvec<int8_t> sgn(2 * M);                           // Build_Amatrix.m:10 per CSR slot: -1 at the smaller endpoint i, +1 at j
-    hvec<int32_t> eprob(M);
-    for (int32_t b = 0; b < count; ++b) {
-        const int32_t* rp = h->rowptr.data() + h->node_off[(size_t)b] + b;
-        const size_t so = 2 * (size_t)h->edge_off[(size_t)b];
-        for (int64_t v = 0; v < probs[b].n; ++v)
-            for (int32_t t = rp[v]; t < rp[v + 1]; ++t) sgn[so + (size_t)t] = v < h->adj[so + (size_t)t] ? -1 : +1;
-        std::fill(eprob.begin() + h->edge_off[(size_t)b], eprob.begin() + h->edge_off[(size_t)b + 1], b);
-    }
-    ib_flags0(h);
-    h->ms_structure = ms_since(t0);
-    if (count == 0) return DESC_OK;
-
-    if ((rc = h->open(device, "the batched IRLS"))) return rc;             // nothing above touched the device
-    auto t1 = std::chrono::steady_clock::now();
-    if ((rc = ib_check_lds(h))) return rc;
-    hvec<IbProb> pr((size_t)count);
-    for (int32_t b = 0; b < count; ++b) pr[(size_t)b] = IbProb{(int32_t)probs[b].n, (int32_t)probs[b].m, h->node_off[(size_t)b], h->edge_off[(size_t)b]};
-    const hvec<double> rij = stage_rotations(probs, count, h->edge_off);
-    if ((rc = h->upload(&h->d_prob, pr.data(), pr.size())) || (rc = h->upload(&h->d_rowptr, h->rowptr.data(), h->rowptr.size())) ||
-        (rc = h->upload(&h->d_adj, h->adj.data(), 2 * M)) || (rc = h->upload(&h->d_adj_eid, h->adj_eid.data(), 2 * M)) ||
-        (rc = h->upload(&h->d_sgn, sgn.data(), 2 * M)) || (rc = h->upload(&h->d_ii, h->ii.data(), M)) ||
-        (rc = h->upload(&h->d_jj, h->jj.data(), M)) || (rc = h->upload(&h->d_rij, rij.data(), 9 * M)) ||
-        (rc = h->upload(&h->d_seq, h->seq.data(), h->seq.size())) || (rc = h->upload(&h->d_order, h->order.data(), M)) ||
-        (rc = h->upload(&h->d_eprob, eprob.data(), M)))
-        return rc;
-    if ((rc = ib_alloc_work(h))) return rc;             // drains the stream: the staging vectors go out of scope below
-    h->ms_upload = ms_since(t1);
+    h->ms_upload = ms_since(t1) + (h->own_set ? set->ms_upload : 0);
     return DESC_OK;
 }
 
@@ -683,18 +654,16 @@ extern "C" {
 int32_t desc_irls_batch_max_n(void) { return IRLS_BATCH_MAX_N; }
 
 int desc_irls_batch_create(const desc_problem* probs, int32_t count, const int32_t* const* orders, int32_t device, desc_irls_batch** out) {
-    return batch_create_guarded("desc_irls_batch_create", out, probs, count, [&](desc_irls_batch* h) { return ib_create(probs, count, orders, device, h); });
+    return batch_create_guarded("desc_irls_batch_create", out, probs, count, [&](desc_irls_batch* h) { return ib_create(probs, count, device, nullptr, orders, h); });
 }
 
 int desc_irls_batch_create_on(desc_problem_batch* set, const int32_t* const* orders, desc_irls_batch** out) {
-    return batch_create_guarded("desc_irls_batch_create_on", out, set, 0, [&](desc_irls_batch* h) { return ib_create_on(set->s, orders, h); }, set != nullptr);
+    return batch_create_guarded("desc_irls_batch_create_on", out, set, 0, [&](desc_irls_batch* h) { return ib_create(nullptr, 0, 0, set->s, orders, h); }, set != nullptr);
 }
 
 int desc_irls_batch_bytes(const desc_irls_batch* h, int64_t* h2d, int64_t* d2h) {
     if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
-    if (h2d) *h2d = h->bytes_h2d;
-    if (d2h) *d2h = h->bytes_d2h;
-    return DESC_OK;
+    return batch_bytes_on_set(*h, h->own_set ? h->set.get() : nullptr, h2d, d2h);
 }
 
 int desc_irls_batch_sizes(const desc_irls_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off) {

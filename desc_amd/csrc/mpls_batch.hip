@@ -9,8 +9,8 @@
 // State.  The loop runs on a CEMP batch handle (cemp_batch.h), which owns the CSR, the rotations and the sampled cycles (e_jk, e_ki, S0,
 // has_cycle: nsample slots per edge of the batch, batch-global edge ids).  The per-node arrays live in LDS, 26 doubles per node, as in
 // k_refine_batch (laa_wg.h); the LDS of a launch is sized from the largest problem of the batch and a problem addresses it with its own
-// n.  The per-edge arrays QQ, B, w, Res, RH lie in global memory at the problem's edge offset; the handle allocates them and uploads the
-// incidence signs at its first loop.
+// n.  The per-edge arrays QQ, B, w, Res, RH lie in global memory at the problem's edge offset; the handle allocates them and forms the
+// incidence signs by a launch at its first loop.
 //
 // Arithmetic and summation orders.  The Weighted-LAA step and the quantile are the text k_refine_batch runs (laa_wg.h), which
 // reproduces the single path's reductions; the residual is k_mpls_res's expression; the H step of an edge with cycles is
@@ -149,31 +149,18 @@ __global__ __launch_bounds__(256) void k_mpls_batch(MbArgs a) {
     }
 }
 
-// The loop's arrays, at the handle's first loop: the incidence signs as rb_create builds them, the per-edge and per-node buffers, the
+// The loop's arrays, at the handle's first loop: the incidence signs as rb_create forms them, the per-edge and per-node buffers, the
 // count of edges with cycles per problem.
 int mb_setup(desc_cemp_batch* h) {
     MbLoop& L = h->loop;
     const int32_t count = h->count;
     const size_t M = (size_t)h->M, N = (size_t)h->N;
-    hvec<int8_t> sgn;                                  // Build_Amatrix.m:10 per CSR slot: -1 at the smaller endpoint i, +1 at j
     int rc;
-    if (h->set) {                                      // a handle created on a set has no host CSR: the signs by a launch from the set's (batch_kernels.h)
-        int8_t* d_sgn = nullptr;
-        if ((rc = h->mem.alloc(&d_sgn, 2 * M))) return rc;
-        hipLaunchKernelGGL(k_batch_sgn<CbProb>, dim3((unsigned)count), dim3(256), 0, h->stream, h->a.prob, h->a.rowptr, h->a.adj, d_sgn);
-        DESC_HIP(hipGetLastError());
-        L.sgn = d_sgn;
-    } else {
-        sgn.resize(2 * M);
-        for (int32_t b = 0; b < count; ++b) {
-            const int32_t* rp = h->rowptr.data() + h->node_off[(size_t)b] + b;
-            const size_t so = 2 * (size_t)h->edge_off[(size_t)b];
-            const int64_t nb = h->node_off[(size_t)b + 1] - h->node_off[(size_t)b];
-            for (int64_t v = 0; v < nb; ++v)
-                for (int32_t t = rp[v]; t < rp[v + 1]; ++t) sgn[so + (size_t)t] = v < h->adj[so + (size_t)t] ? -1 : +1;
-        }
-        if ((rc = h->upload(&L.sgn, sgn.data(), 2 * M))) return rc;
-    }
+    int8_t* d_sgn = nullptr;                           // Build_Amatrix.m:10 per CSR slot, by a launch from the set's CSR (batch_kernels.h)
+    if ((rc = h->mem.alloc(&d_sgn, 2 * M))) return rc;
+    hipLaunchKernelGGL(k_batch_sgn<CbProb>, dim3((unsigned)count), dim3(256), 0, h->stream, h->a.prob, h->a.rowptr, h->a.adj, d_sgn);
+    DESC_HIP(hipGetLastError());
+    L.sgn = d_sgn;
     if ((rc = h->mem.alloc(&L.S, M)) || (rc = h->mem.alloc(&L.R_init, 9 * N)) || (rc = h->mem.alloc(&L.R_out, 9 * N)) ||
         (rc = h->mem.alloc(&L.QQ, M)) || (rc = h->mem.alloc(&L.B, 3 * M)) || (rc = h->mem.alloc(&L.w, M)) || (rc = h->mem.alloc(&L.Res, M)) ||
         (rc = h->mem.alloc(&L.RH, M)) || (rc = h->mem.alloc(&L.info, (size_t)count)))

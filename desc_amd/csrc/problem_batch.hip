@@ -1,7 +1,8 @@
 // A study's problems resident on the device across calls (desc_problem_batch_*): validation, layout and upload happen once, and the
-// batched handles of the DESC row are created ON the set (desc_gcw_batch_create_on, desc_refine_batch_create_on,
-// desc_pgd_batch_create_on): they borrow its device arrays and upload O(B) bytes of their own.  The generator hands its problems over
-// without a host copy of any rotation (desc_problem_batch_from_models).  problem_batch.h has the layout and the ownership rule.
+// batched handles are created ON the set (desc_*_batch_create_on): they borrow its device arrays and upload O(B) bytes of their own.
+// The list-path creates of the eigen-solve, the refinement, CEMP and IRLS make a set of their own here (pb_host_part, pb_device_part)
+// and take the same way.  The generator hands its problems over without a host copy of any rotation
+// (desc_problem_batch_from_models).  problem_batch.h has the layout and the ownership rule.
 //
 // k_pb_csr: the per-problem CSR (local ids) from the (i, j)-sorted local edge lists, element for element what batch_csr_host builds.
 // One workgroup of 256 threads per problem, four phases separated by barriers; everything is integer arithmetic and no slot depends on
@@ -124,45 +125,52 @@ int pb_csr_device(PbSet* s) {
 
 namespace {
 
-int pb_upload_prob(PbSet* s) {
-    hvec<PbProb> pr((size_t)s->count);
+// the records from the offsets, into the caller's staging vector: it lives until the caller has drained the stream
+int pb_upload_prob(PbSet* s, hvec<PbProb>& pr) {
+    pr.resize((size_t)s->count);
     for (int32_t b = 0; b < s->count; ++b) {
         const int64_t no = s->node_off[(size_t)b], eo = s->edge_off[(size_t)b];
         pr[(size_t)b] = PbProb{(int32_t)(s->node_off[(size_t)b + 1] - no), (int32_t)(s->edge_off[(size_t)b + 1] - eo), no, eo};
     }
-    int rc = s->upload(&s->d_prob, pr.data(), pr.size());
-    if (rc) return rc;
-    DESC_HIP(hipStreamSynchronize(s->stream));         // pr goes out of scope
-    return DESC_OK;
+    return s->upload(&s->d_prob, pr.data(), pr.size());
 }
 
-int pb_create(const desc_problem* probs, int32_t count, int32_t device, int32_t csr_where, PbSet* s) {
+}  // namespace
+
+int pb_host_part(const desc_problem* probs, int32_t count, int32_t csr_where, const std::function<int(int32_t, const desc_problem&)>& extra, PbSet* s) {
     auto t0 = std::chrono::steady_clock::now();
     // the words and the order of batch_csr_host in either case; the device builder needs the offsets and the endpoints only
-    int rc = csr_where == DESC_BUILD_HOST ? batch_csr_host(probs, count, nullptr, s) : batch_offsets_host(probs, count, nullptr, s);
+    const int rc = csr_where == DESC_BUILD_HOST ? batch_csr_host(probs, count, extra, s) : batch_offsets_host(probs, count, extra, s);
     if (rc) return rc;
     s->host_csr = csr_where == DESC_BUILD_HOST;
     s->ms_structure = ms_since(t0);
-    if (count == 0) return DESC_OK;
+    return DESC_OK;
+}
 
-    if ((rc = s->open(device, "the resident problem set"))) return rc;     // nothing above touched the device
+int pb_device_part(const desc_problem* probs, int32_t device, const char* what, PbSet* s) {
+    int rc = s->open(device, what);
+    if (rc) return rc;
     auto t1 = std::chrono::steady_clock::now();
     const size_t M = (size_t)s->M;
-    if ((rc = pb_upload_prob(s))) return rc;
-    const hvec<double> rij = stage_rotations(probs, count, s->edge_off);
-    if ((rc = s->upload(&s->d_ii, s->ii.data(), M)) || (rc = s->upload(&s->d_jj, s->jj.data(), M)) || (rc = s->upload(&s->d_rij, rij.data(), 9 * M)))
-        return rc;
-    if (s->host_csr) {
+    hvec<PbProb> pr;                                   // the two staging vectors live until the stream has drained, on every way out
+    const hvec<double> rij = stage_rotations(probs, s->count, s->edge_off);
+    rc = [&]() -> int {
+        int rc;
+        if ((rc = pb_upload_prob(s, pr)) || (rc = s->upload(&s->d_ii, s->ii.data(), M)) || (rc = s->upload(&s->d_jj, s->jj.data(), M)) ||
+            (rc = s->upload(&s->d_rij, rij.data(), 9 * M))) return rc;
+        if (!s->host_csr) return pb_csr_device(s);
         if ((rc = s->upload(&s->d_rowptr, s->rowptr.data(), s->rowptr.size())) || (rc = s->upload(&s->d_adj, s->adj.data(), 2 * M)) ||
             (rc = s->upload(&s->d_adj_eid, s->adj_eid.data(), 2 * M))) return rc;
         s->built_where = DESC_BUILD_HOST;
-    } else if ((rc = pb_csr_device(s))) {
-        return rc;
-    }
-    DESC_HIP(hipStreamSynchronize(s->stream));         // the staging vector goes out of scope; from here on the arrays are read-only
+        return DESC_OK;
+    }();
+    if (rc) { (void)hipStreamSynchronize(s->stream); return rc; }
+    DESC_HIP(hipStreamSynchronize(s->stream));         // from here on the arrays are read-only
     s->ms_upload = ms_since(t1);
     return DESC_OK;
 }
+
+namespace {
 
 int pb_from_models(desc_models_batch* m, PbSet* s) {
     ModelsView v;
@@ -198,7 +206,11 @@ int pb_from_models(desc_models_batch* m, PbSet* s) {
         s->max_n = std::max(s->max_n, n);
     }
     s->N = s->node_off[(size_t)count];
-    if ((rc = pb_upload_prob(s)) || (rc = pb_csr_device(s))) return rc;
+    hvec<PbProb> pr;
+    if ((rc = pb_upload_prob(s, pr)) || (rc = pb_csr_device(s))) {
+        (void)hipStreamSynchronize(s->stream);         // pr's copy may be on its way: drain before pr goes
+        return rc;
+    }
     DESC_HIP(hipStreamSynchronize(s->stream));
     return DESC_OK;
 }
@@ -239,7 +251,8 @@ int desc_problem_batch_create(const desc_problem* probs, int32_t count, int32_t 
     }
     return batch_create_guarded("desc_problem_batch_create", out, probs, count, [&](desc_problem_batch* h) {
         h->s = std::make_shared<PbSet>();
-        return pb_create(probs, count, device, csr_where, h->s.get());
+        const int rc = pb_host_part(probs, count, csr_where, nullptr, h->s.get());
+        return rc || count == 0 ? rc : pb_device_part(probs, device, "the resident problem set", h->s.get());     // the host part touched no device
     });
 }
 

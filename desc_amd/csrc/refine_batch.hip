@@ -9,7 +9,8 @@
 // State.  The per-node arrays (Q, the PCG's x r z p q, rhs, diag, the vector part Wv of the update) live in LDS, 26 doubles per node.
 // The LDS of a launch is sized from the largest problem of the batch; a problem addresses it with its own n, so nothing it computes
 // depends on that size.  The per-edge arrays (QQ, B, w, RS and the inputs S, ii, jj, rij) lie in global memory at the problem's edge
-// offset; the CSR (local ids) and the incidence sign per slot come from the host (batch_csr.h).
+// offset; the CSR (local ids), the endpoints and the rotations are those of the resident problem set (problem_batch.h) the handle is created
+// on, and the incidence sign per slot is formed from the set's CSR by a launch in create (batch_kernels.h).
 //
 // Arithmetic and summation orders.  The Weighted-LAA step and the quantile are the workgroup-level functions of laa_wg.h, which
 // k_mpls_batch (mpls_batch.hip) calls too.  Every per-element expression is the text of laa_math.h, which the kernels of the single path call
@@ -45,12 +46,11 @@ namespace {
 
 constexpr int RB_QR = 8;                               // entries of the quant_ratio table (the recurrence is constant after five steps)
 
-struct RbProb { int32_t n, m; int64_t node_off, edge_off; };
 // status: 0 done, 1 the selection found no candidate, 2 a score that is not finite, -1 the workgroup never finished
 struct RbInfo { int32_t iters, cg_total, cg_unconverged, status; double score, worst_sq; };
 
 struct RbArgs {
-    const RbProb* prob;
+    const PbProb* prob;
     const int32_t* rowptr;      // problem b's n_b + 1 row starts at node_off[b] + b, counted inside the problem
     const int32_t* adj;         // 2 m_b local neighbour ids at 2 edge_off[b]
     const int32_t* adj_eid;     // 2 m_b local edge ids
@@ -72,7 +72,7 @@ struct RbArgs {
 __global__ __launch_bounds__(256) void k_refine_batch(RbArgs a) {
     extern __shared__ double rb_lds[];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const RbProb pd = a.prob[b];
+    const PbProb pd = a.prob[b];
     const int n = uni(pd.n), m = uni(pd.m);
     const int32_t* ii = a.ii + pd.edge_off;
     const int32_t* jj = a.jj + pd.edge_off;
@@ -148,14 +148,16 @@ __global__ __launch_bounds__(256) void k_refine_batch(RbArgs a) {
 
 using namespace desc;
 
-struct desc_refine_batch : desc::BatchCsr, desc::BatchDevice {  // offsets and the per-problem CSR (local ids); device, stream, arena, events
-    RbProb* d_prob = nullptr;
-    int32_t *d_rowptr = nullptr, *d_adj = nullptr, *d_adj_eid = nullptr, *d_ii = nullptr, *d_jj = nullptr;
+struct desc_refine_batch : desc::BatchCsr, desc::BatchDevice {  // the set's offsets and endpoints; device, stream, arena, events
+    const PbProb* d_prob = nullptr;
+    const int32_t *d_rowptr = nullptr, *d_adj = nullptr, *d_adj_eid = nullptr, *d_ii = nullptr, *d_jj = nullptr;
     int8_t* d_sgn = nullptr;
-    double *d_rij = nullptr, *d_S = nullptr, *d_thresh0 = nullptr, *d_Rinit = nullptr, *d_Rout = nullptr, *d_B = nullptr, *d_w = nullptr, *d_RS = nullptr;
+    const double* d_rij = nullptr;
+    double *d_S = nullptr, *d_thresh0 = nullptr, *d_Rinit = nullptr, *d_Rout = nullptr, *d_B = nullptr, *d_w = nullptr, *d_RS = nullptr;
     Quat* d_QQ = nullptr;
     RbInfo* d_info = nullptr;
-    std::shared_ptr<desc::PbSet> set;         // desc_refine_batch_create_on: the owner of d_prob, the CSR, d_ii / d_jj and d_rij
+    std::shared_ptr<desc::PbSet> set;         // the owner of d_prob, the CSR, d_ii / d_jj and d_rij
+    bool own_set = false;                     // the handle made the set from a problem list and is its only owner
     ~desc_refine_batch() { close(); }         // the stream drains before the set may go
 };
 
@@ -168,12 +170,7 @@ int rb_check_n(int32_t b, int64_t n) {
     return DESC_OK;
 }
 
-// validation, offsets and the per-problem CSR: no device
-int rb_host_part(const desc_problem* probs, int32_t count, desc_refine_batch* h) {
-    return batch_csr_host(probs, count, [](int32_t b, const desc_problem& q) -> int { return rb_check_n(b, q.n); }, h);
-}
-
-// the run's own buffers, the same behind either create
+// the run's own buffers
 int rb_alloc_work(desc_refine_batch* h) {
     const size_t M = (size_t)h->M, N = (size_t)h->N, count = (size_t)h->count;
     int rc;
@@ -186,61 +183,41 @@ int rb_alloc_work(desc_refine_batch* h) {
     return DESC_OK;
 }
 
-// On a resident set: the cap, then the signs per slot in one launch from the set's CSR (batch_kernels.h); everything else the kernel reads of the
-// problems is the set's (its record is RbProb's).
-int rb_create_on(const std::shared_ptr<PbSet>& set, desc_refine_batch* h) {
+// The one create body, on a resident set: the caller's (desc_refine_batch_create_on, probs = NULL), or one the handle makes from probs
+// and owns alone (the list path; the cap is then refused per problem inside the set's host part, between the other refusals of that
+// problem).  The signs per slot come from the set's CSR in one launch (batch_kernels.h); everything else the kernel reads of the
+// problems is the set's.
+int rb_create(const desc_problem* probs, int32_t count, int32_t device, std::shared_ptr<PbSet> set, desc_refine_batch* h) {
     auto t0 = std::chrono::steady_clock::now();
-    static_assert(sizeof(RbProb) == sizeof(PbProb), "the set's problem record is the refinement's");
     int rc;
-    for (int32_t b = 0; b < set->count; ++b)
-        if ((rc = rb_check_n(b, set->node_off[(size_t)b + 1] - set->node_off[(size_t)b]))) return rc;
-    pb_share_host(*set, h);
+    h->own_set = !set;
+    if (h->own_set) {
+        set = std::make_shared<PbSet>();
+        if ((rc = pb_host_part(probs, count, DESC_BUILD_HOST, [](int32_t b, const desc_problem& q) -> int { return rb_check_n(b, q.n); }, set.get()))) return rc;
+    } else {
+        for (int32_t b = 0; b < set->count; ++b)
+            if ((rc = rb_check_n(b, set->node_off[(size_t)b + 1] - set->node_off[(size_t)b]))) return rc;
+    }
+    h->set = set;
+    pb_share_host(*set, h, !h->own_set);             // an own set: h->ii / h->jj stay EMPTY until pb_take_endpoints below -- read set->ii / set->jj till then
     h->ms_structure = ms_since(t0);
     if (h->count == 0) return DESC_OK;
 
-    if ((rc = h->open(set->device, "the batched refinement"))) return rc;   // nothing above touched the device
+    const char* what = "the batched refinement";
+    if (h->own_set) {                                  // nothing above touched the device
+        if ((rc = pb_device_part(probs, device, what, set.get()))) return rc;
+        pb_take_endpoints(*set, h);
+    }
+    if ((rc = h->open(set->device, what))) return rc;
     auto t1 = std::chrono::steady_clock::now();
-    h->set = set;
-    h->d_prob = reinterpret_cast<RbProb*>(set->d_prob);
-    h->d_rowptr = set->d_rowptr; h->d_adj = set->d_adj; h->d_adj_eid = set->d_adj_eid; h->d_ii = set->d_ii; h->d_jj = set->d_jj;
+    h->d_prob = set->d_prob; h->d_rowptr = set->d_rowptr; h->d_adj = set->d_adj; h->d_adj_eid = set->d_adj_eid; h->d_ii = set->d_ii; h->d_jj = set->d_jj;
     h->d_rij = set->d_rij;
     if ((rc = h->mem.alloc(&h->d_sgn, 2 * (size_t)h->M))) return rc;
-    hipLaunchKernelGGL(k_batch_sgn<RbProb>, dim3((unsigned)h->count), dim3(256), 0, h->stream, h->d_prob, h->d_rowptr, h->d_adj, h->d_sgn);
+    hipLaunchKernelGGL(k_batch_sgn<PbProb>, dim3((unsigned)h->count), dim3(256), 0, h->stream, h->d_prob, h->d_rowptr, h->d_adj, h->d_sgn);
     DESC_HIP(hipGetLastError());
     if ((rc = rb_alloc_work(h))) return rc;
     DESC_HIP(hipStreamSynchronize(h->stream));
-    h->ms_upload = ms_since(t1);
-    return DESC_OK;
-}
-
-int rb_create(const desc_problem* probs, int32_t count, int32_t device, desc_refine_batch* h) {
-    auto t0 = std::chrono::steady_clock::now();
-    int rc = rb_host_part(probs, count, h);
-    if (rc) return rc;
-    const size_t M = (size_t)h->M;
-    hvec<int8_t> sgn(2 * M);                           // Build_Amatrix.m:10 per CSR slot: -1 at the smaller endpoint i, +1 at j
-    for (int32_t b = 0; b < count; ++b) {
-        const int32_t* rp = h->rowptr.data() + h->node_off[(size_t)b] + b;
-        const size_t so = 2 * (size_t)h->edge_off[(size_t)b];
-        for (int64_t v = 0; v < probs[b].n; ++v)
-            for (int32_t t = rp[v]; t < rp[v + 1]; ++t) sgn[so + (size_t)t] = v < h->adj[so + (size_t)t] ? -1 : +1;
-    }
-    h->ms_structure = ms_since(t0);
-    if (count == 0) return DESC_OK;
-
-    if ((rc = h->open(device, "the batched refinement"))) return rc;       // nothing above touched the device
-    auto t1 = std::chrono::steady_clock::now();
-    hvec<RbProb> pr((size_t)count);
-    for (int32_t b = 0; b < count; ++b) pr[(size_t)b] = RbProb{(int32_t)probs[b].n, (int32_t)probs[b].m, h->node_off[(size_t)b], h->edge_off[(size_t)b]};
-    const hvec<double> rij = stage_rotations(probs, count, h->edge_off);
-    if ((rc = h->upload(&h->d_prob, pr.data(), pr.size())) || (rc = h->upload(&h->d_rowptr, h->rowptr.data(), h->rowptr.size())) ||
-        (rc = h->upload(&h->d_adj, h->adj.data(), 2 * M)) || (rc = h->upload(&h->d_adj_eid, h->adj_eid.data(), 2 * M)) ||
-        (rc = h->upload(&h->d_sgn, sgn.data(), 2 * M)) || (rc = h->upload(&h->d_ii, h->ii.data(), M)) ||
-        (rc = h->upload(&h->d_jj, h->jj.data(), M)) || (rc = h->upload(&h->d_rij, rij.data(), 9 * M)))
-        return rc;
-    if ((rc = rb_alloc_work(h))) return rc;
-    DESC_HIP(hipStreamSynchronize(h->stream));         // the staging vectors go out of scope below
-    h->ms_upload = ms_since(t1);
+    h->ms_upload = ms_since(t1) + (h->own_set ? set->ms_upload : 0);
     return DESC_OK;
 }
 
@@ -319,18 +296,16 @@ extern "C" {
 int32_t desc_refine_batch_max_n(void) { return REFINE_BATCH_MAX_N; }
 
 int desc_refine_batch_create(const desc_problem* probs, int32_t count, int32_t device, desc_refine_batch** out) {
-    return batch_create_guarded("desc_refine_batch_create", out, probs, count, [&](desc_refine_batch* h) { return rb_create(probs, count, device, h); });
+    return batch_create_guarded("desc_refine_batch_create", out, probs, count, [&](desc_refine_batch* h) { return rb_create(probs, count, device, nullptr, h); });
 }
 
 int desc_refine_batch_create_on(desc_problem_batch* set, desc_refine_batch** out) {
-    return batch_create_guarded("desc_refine_batch_create_on", out, set, 0, [&](desc_refine_batch* h) { return rb_create_on(set->s, h); }, set != nullptr);
+    return batch_create_guarded("desc_refine_batch_create_on", out, set, 0, [&](desc_refine_batch* h) { return rb_create(nullptr, 0, 0, set->s, h); }, set != nullptr);
 }
 
 int desc_refine_batch_bytes(const desc_refine_batch* h, int64_t* h2d, int64_t* d2h) {
     if (!h) return fail(DESC_ERR_INVALID, "NULL handle");
-    if (h2d) *h2d = h->bytes_h2d;
-    if (d2h) *d2h = h->bytes_d2h;
-    return DESC_OK;
+    return batch_bytes_on_set(*h, h->own_set ? h->set.get() : nullptr, h2d, d2h);
 }
 
 int desc_refine_batch_sizes(const desc_refine_batch* h, int32_t* count, int64_t* node_off, int64_t* edge_off) {

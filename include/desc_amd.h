@@ -1027,7 +1027,8 @@ int desc_test_align_project(const double* A, int64_t count, int32_t device, doub
  * device work); what create derives from the CSR is formed on the device (the refinement's sign per slot, the device builder's edge ->
  * problem map), so the uploads of a create_on are O(B) bytes.  desc_pgd_batch_create_on takes either builder (the host builder reads
  * the set's host ii / jj; p->device is not read); the device builder's silent fallback is unchanged.  The run functions are unchanged
- * and give the bits of a handle created from the host arrays.  desc_*_batch_bytes: the bytes a handle's creates copied up / down.
+ * and give the bits of a handle created from the host arrays.  desc_*_batch_bytes: the bytes a handle's create copied up / down;
+ * a handle created from a problem list (desc_{gcw,refine,cemp,irls}_batch_create) counts what the set it made for itself copied, too.
  *
  * desc_cemp_batch_create_on / desc_irls_batch_create_on: the same for the CEMP handle (with desc_mpls_batch_run on it) and the IRLS
  * handle.  The degree cap of the sampler is checked on the set's host row starts or, for a device-built CSR, on a count over its host
